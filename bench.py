@@ -9,11 +9,14 @@ column-grouped copy of the shard (default; it is built as part of the index buil
 scan (`--scan csr` forces it).  Index and queries are resident in HBM when the timed region
 starts.  Strong scaling: the 21 015 324-row index is re-partitioned over the N ranks.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel: the scan, HBM roofline) and
-`cpu_baseline` (the reference's three torch calls, oracle/torch_ref.py, timed on this host).
+Prints ONE JSON line (rank 0) with `roofline` (dominant kernel: the scan, HBM roofline).  A plain run sets up,
+warms up, times the K steps and prints the line; `--full` adds what takes runs of its own: the oracle parity
+check (`parity`), the secondary configurations on one GPU (`secondary`) and `cpu_baseline` (the reference's
+three torch calls, oracle/torch_ref.py, timed on this host).  `--dump-outputs DIR`: rank 0 writes the last
+timed step's result as DIR/ids.npy (float64) and DIR/scores.npy (float32).
 """
 import argparse
 import json
@@ -44,7 +47,7 @@ MFMA_F32_PEAK_TF = 157.3     # fp32-input MFMA = the fp32 vector peak (MI355X_MI
 WALK_KERNEL = {-1: "csr_scan_topk_mq", 0: "bp_walk_topk", 4: "bp_quad_topk", 5: "bp_bin_topk", 6: "bp_bq_topk"}     # vs_index_info_t.postings_walk -> the filter's kernel
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
@@ -52,9 +55,14 @@ def parse():
     ap.add_argument("--docs", type=int, default=N_DOCS, help="total index rows (default: the metric's 21 015 324)")
     ap.add_argument("--batch", type=int, default=BATCH)
     ap.add_argument("--k", type=int, default=K)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--dump-ids", default=None, help="rank 0 writes the last step's (ids, scores) to this .npz (tests)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary configurations (C3, C5, Zipf 21 M, small-batch latency, facade leg) "
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes the last timed step's result to DIR/ids.npy (float64) and DIR/scores.npy (float32), at most 64 MB "
+                         "(beyond that: a fixed sample of query rows, listed in DIR/query_rows.npy)")
+    ap.add_argument("--full", action="store_true", help="also run what the headline does not need: the oracle parity check, the secondary "
+                                                        "configurations and the CPU baseline (the last two on one GPU)")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary configurations (C3, C5, Zipf 21 M, small-batch latency, facade leg) "
                                                                 "that follow the headline measurement on one GPU")
     ap.add_argument("--scan", choices=["auto", "csr", "postings"], default="auto",
                     help="auto: blocked postings when HBM has room for the second copy (default); csr: the 8-query CSR scan only")
@@ -64,7 +72,10 @@ def parse():
                          "SURVEY 8(d) C3's secondary run: vsearch_amd/synth.py KIND_SKEW)")
     ap.add_argument("--store", choices=["fp32", "fp16"], default="fp32",
                     help="value dtype streamed by the scan (fp16 = the reference's fp16=True load default, index.py:135)")
-    return ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 KIND = {"uniform": 0, "zipf": 2}
@@ -118,6 +129,29 @@ def make_query_batches(n_batches, batch, device, kind=0):
         q[rows, torch.from_numpy(ix).to(device)] = torch.from_numpy(d).to(device)
         out.append(q)
     return out
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, ids, scores, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: the (ids, scores) a caller of the timed path received from its last step, as DIR/ids.npy (float64: ids are exact
+    below 2^53) and DIR/scores.npy (float32).  Beyond `limit` bytes in all, a fixed seeded sample of query rows (sorted) is written
+    instead, and their row numbers as DIR/query_rows.npy."""
+    ids = ids.cpu().numpy().astype(np.float64)
+    scores = scores.cpu().numpy().astype(np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    per_row = ids[0].nbytes + scores[0].nbytes + 8 if len(ids) else 1
+    keep_rows = (limit - 4096) // per_row                          # (room for the three .npy headers)
+    rows_path = os.path.join(out_dir, "query_rows.npy")
+    if os.path.exists(rows_path):
+        os.remove(rows_path)                                       # (an earlier run's sample)
+    if len(ids) > keep_rows:
+        rows = np.sort(np.random.default_rng(0).choice(len(ids), keep_rows, replace=False))
+        ids, scores = ids[rows], scores[rows]
+        np.save(rows_path, rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "ids.npy"), ids)
+    np.save(os.path.join(out_dir, "scores.npy"), scores)
 
 
 def parity_check(device, kind=0, nnz_doc=NNZ_DOC, store=0, val_law=0, expect_path=None, n=20_000, exact=False):
@@ -665,8 +699,11 @@ def main():
         per_rank["by_rank"] = [{n: float(m[r, i]) for i, n in enumerate(names)} for r in range(world)]
     if rank == 0 and args.dump_ids:
         np.savez(args.dump_ids, ids=ids.cpu().numpy(), scores=scores.cpu().numpy())
-    # N > 1: the oracle check through the sharded path (all ranks search, rank 0 compares); after the timed region
-    sharded_parity = parity_sharded(world, rank, local_rank, device, kind, expect_path=index.info().last_path if n_local >= 20_000 and args.scan == "auto" else None) if world > 1 else None
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, ids, scores)
+    # N > 1, --full: the oracle check through the sharded path (all ranks search, rank 0 compares); after the timed region
+    sharded_parity = parity_sharded(world, rank, local_rank, device, kind, expect_path=index.info().last_path if n_local >= 20_000 and args.scan == "auto" else None) \
+        if world > 1 and args.full else None
 
     if rank == 0:
         qps = args.steps * args.batch / elapsed
@@ -765,9 +802,9 @@ def main():
             line["roofline"][key] = (ut or {}).get(key)
         line["roofline"]["utilisation_source"] = (f"profiles/pmc_summary.json utilisation ({ut.get('tag')}: rocprofv3 --pmc passes, {ut.get('shape')}); ceiling: "
                                                   "tools/microbench/l2_requests.hip (0.40 requests a clock and CU from L2, 0.095 beyond)") if ut else None
-        if world > 1:
+        if world > 1 and args.full:
             line["parity"] = sharded_parity
-        if world == 1:
+        if world == 1 and args.full:
             line["parity"] = parity_check(local_rank, kind, expect_path=info.last_path if n_local >= 20_000 and args.scan == "auto" else None)
             if not args.no_secondary and args.docs == N_DOCS and args.columns == "uniform" and args.scan == "auto":
                 line["secondary"] = secondary(index, batches, args, local_rank, device, elapsed / args.steps)

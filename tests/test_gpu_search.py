@@ -313,7 +313,7 @@ def test_two_rank_bench_launch_on_one_gpu_equals_the_unsharded_search(tmp_path):
     out = str(tmp_path / "line.json")
     docs, batch, k = 400_000, 64, 100
     cmd = [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--docs", str(docs), "--batch", str(batch), "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline", "--dump-ids", dump]
+           "--full", "--no-cpu-baseline", "--dump-ids", dump]
     env = dict(os.environ, VS_BENCH_SHARE_GPU="1")
     # the parent of the ranks must not have touched the GPU: run the launcher in a fresh interpreter (this pytest process has)
     code = ("import sys, json; sys.path.insert(0, %r); from vsearch_amd import launch; "
@@ -334,6 +334,31 @@ def test_two_rank_bench_launch_on_one_gpu_equals_the_unsharded_search(tmp_path):
     assert (ids.cpu().numpy() == got["ids"]).all() and (sc.cpu().numpy() == got["scores"]).all()
 
 
+def test_plain_bench_run_times_its_steps_and_dumps_the_last_one(tmp_path):
+    """`bench.py --gpus 1` without --full: the headline fields, no parity / secondary / CPU baseline legs, `steps` timed steps, and
+    --dump-outputs holds the last timed step's ids (float64) and scores (float32) -- the same index's search of that batch, bit for bit."""
+    import json, os, subprocess, sys
+    import torch
+    import bench
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "outputs"
+    docs, batch, k = 200_000, 64, 100
+    r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--docs", str(docs), "--batch", str(batch), "--steps", "3",
+                        "--warmup", "1", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["unit"] == "queries/sec"
+    assert abs(line["value"] - 1e3 * batch / line["ms_per_step"]) <= 1e-6 * line["value"]
+    assert not {"parity", "secondary", "cpu_baseline"} & set(line)
+    ids, sc = np.load(out / "ids.npy"), np.load(out / "scores.npy")
+    assert ids.dtype == np.float64 and sc.dtype == np.float32 and ids.shape == sc.shape == (batch, k)
+    idx = DeviceIndex.synthetic(bench.INDEX_SEED, 0, docs, V, bench.NNZ_DOC, 0, 0, nat.VS_F32)
+    qb = bench.make_query_batches(4, batch, torch.device("cuda", 0))
+    want_ids, want_sc = idx.search(qb[3], k)                         # steps 3 + warmup 1: the last step searched batch 3
+    idx.close()
+    assert (want_ids.cpu().numpy() == ids).all() and (want_sc.cpu().numpy() == sc).all()
+
+
 def test_eight_rank_bench_launch_on_one_gpu_equals_the_unsharded_search(tmp_path):
     """eight rank processes sharing the one GPU (gloo exchange), 20 000-doc shards -- every rank's shard is big
     enough for the postings filter, the path the measured run takes (bench.parity_sharded asserts it) -- rank 0's ids and scores equal
@@ -344,7 +369,7 @@ def test_eight_rank_bench_launch_on_one_gpu_equals_the_unsharded_search(tmp_path
     dump = str(tmp_path / "ids8.npz")
     docs, batch, k, world = 8 * 20_000, 32, 100, 8
     cmd = [sys.executable, os.path.join(repo, "bench.py"), "--gpus", str(world), "--docs", str(docs), "--batch", str(batch), "--steps", "1", "--warmup", "1",
-           "--no-cpu-baseline", "--dump-ids", dump]
+           "--full", "--no-cpu-baseline", "--dump-ids", dump]
     env = dict(os.environ, VS_BENCH_SHARE_GPU="1")
     code = ("import sys, json; sys.path.insert(0, %r); from vsearch_amd import launch; "
             "raise SystemExit(launch.spawn_ranks(%r, %d, timeout_s=900, extra_env={'VS_BENCH_SHARE_GPU': '1'}))" % (repo, cmd, world))

@@ -54,3 +54,31 @@ def test_bench_parent_does_not_need_a_gpu():
     if not torch.cuda.is_available():
         assert p.returncode != 0 and "no HIP device visible" in p.stderr
         assert "torch.distributed.run" not in p.stderr
+
+
+def test_bench_options_and_output_dump(tmp_path):
+    """A plain `bench.py` run leaves the parity / secondary / CPU-baseline legs to --full; --dump-outputs writes ids as float64 and scores
+    as float32, and beyond 64 MB a fixed sample of query rows (the same rows every run) with their row numbers."""
+    import torch
+    import bench
+    a = bench.parse(["--steps", "5", "--warmup", "2"])
+    assert a.steps == 5 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    assert bench.parse(["--full", "--dump-outputs", str(tmp_path)]).full
+    ids = torch.arange(6 * 100, dtype=torch.int64).reshape(6, 100) + 21_000_000
+    sc = torch.rand((6, 100))
+    bench.dump_outputs(str(tmp_path / "small"), ids, sc)
+    got_ids, got_sc = np.load(tmp_path / "small" / "ids.npy"), np.load(tmp_path / "small" / "scores.npy")
+    assert got_ids.dtype == np.float64 and (got_ids == ids.numpy()).all()
+    assert got_sc.dtype == np.float32 and (got_sc == sc.numpy()).all()
+    assert not (tmp_path / "small" / "query_rows.npy").exists()
+    big_ids = torch.arange(4000 * 100, dtype=torch.int64).reshape(4000, 100)
+    big_sc = torch.rand((4000, 100))
+    limit = 1 << 20
+    rows = []
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), big_ids, big_sc, limit=limit)
+        assert sum(f.stat().st_size for f in (tmp_path / d).iterdir()) <= limit
+        r = np.load(tmp_path / d / "query_rows.npy").astype(np.int64)
+        assert (np.load(tmp_path / d / "ids.npy") == big_ids.numpy()[r]).all() and (np.load(tmp_path / d / "scores.npy") == big_sc.numpy()[r]).all()
+        rows.append(r)
+    assert len(rows[0]) > 0 and (rows[0] == rows[1]).all()

@@ -7,7 +7,7 @@ OUT=$ROOT/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 # 1. the bench line itself (with secondary configs and CPU baseline)
-python3 $ROOT/bench.py --steps 10 --warmup 2 > $OUT/${TAG}_bench_line.json 2> $OUT/${TAG}_bench_line.err
+python3 $ROOT/bench.py --steps 10 --warmup 2 --full > $OUT/${TAG}_bench_line.json 2> $OUT/${TAG}_bench_line.err
 # 2. kernel stats + HBM traffic of the headline command (separate --pmc passes; no secondary legs under the profiler)
 rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_stats -o $TAG -- python3 $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-secondary > $OUT/${TAG}_bench_prof.log 2>&1
 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $OUT/${TAG}_fetch -o $TAG -- python3 $ROOT/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-secondary > $OUT/${TAG}_fetch.log 2>&1
@@ -18,7 +18,7 @@ for LEG in C3 C5 zipf fp16; do
   rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $OUT/${TAG}_write_$LEG -o ${TAG}$LEG -- python3 $ROOT/tools/leg_pmc.py $LEG > $OUT/${TAG}_write_$LEG.log 2>&1
 done
 # 2b. the same with the secondary legs (C2 dense, C3, C5, Zipf, embed, head, rerank): kernel rows of the non-search kernels
-rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_stats_all -o ${TAG}all -- python3 $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline > $OUT/${TAG}_bench_prof_all.log 2>&1
+rocprofv3 --kernel-trace --stats -d $OUT/${TAG}_stats_all -o ${TAG}all -- python3 $ROOT/bench.py --steps 3 --warmup 1 --full --no-cpu-baseline > $OUT/${TAG}_bench_prof_all.log 2>&1
 # 3. HBM traffic of a 32-query batch on the same index (DESIGN 4's small-batch claim): FETCH_SIZE of the walk launch
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/${TAG}_fetch_b32 -- python3 $ROOT/tools/probe_filter.py 21015324 32 100 fp32 filter > $OUT/${TAG}_fetch_b32.log 2>&1
 # 4. utilisation counters of the walk (4 M docs) and its phase clocks
@@ -36,7 +36,7 @@ S=$OUT/${TAG}_summaries; mkdir -p $S; cp $ROOT/profiles/pmc_summary.json $S/ 2>/
 db() { find $OUT/$1 -name "*_results.db" | head -1; }
 python3 tools/rocprof_summary.py --stats "$(db ${TAG}_stats)" --fetch "$(db ${TAG}_fetch)" --write "$(db ${TAG}_write)" --tag $TAG --queries 1024 --out $S \
     --note "bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-secondary (stats); --steps 1 --warmup 0 (pmc passes)" > /dev/null
-python3 tools/rocprof_summary.py --stats "$(db ${TAG}_stats_all)" --tag ${TAG}_secondary --out $S --note "bench.py --steps 3 --warmup 1 --no-cpu-baseline (all legs)" > /dev/null
+python3 tools/rocprof_summary.py --stats "$(db ${TAG}_stats_all)" --tag ${TAG}_secondary --out $S --note "bench.py --steps 3 --warmup 1 --full --no-cpu-baseline (all legs)" > /dev/null
 for LEG in C3:C3_1m_sparse C5:C5_bot_21m zipf:zipf_21m fp16:fp16_21m; do
   python3 tools/rocprof_summary.py --fetch "$(db ${TAG}_fetch_${LEG%%:*})" --write "$(db ${TAG}_write_${LEG%%:*})" --tag ${TAG}_${LEG%%:*} --leg ${LEG##*:} --queries 1024 --searches 2 --out $S \
       --note "tools/leg_pmc.py ${LEG%%:*} under rocprofv3 --pmc (separate FETCH_SIZE / WRITE_SIZE passes)" > /dev/null
