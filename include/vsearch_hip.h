@@ -177,6 +177,24 @@ VS_API int vs_index_create_synthetic(uint64_t seed, int64_t row0, int64_t n_rows
 VS_API int vs_index_search(vs_index* index, const void* q, int q_dtype, int64_t ldq, int32_t B, int32_t k,
                            int64_t id_offset, int64_t* out_ids, float* out_scores, void* stream);
 
+/* Filtered search (no reference counterpart: the reference can only search a larger k and drop hits): what vs_index_search returns over
+ * the index that holds only the ALLOWED rows, bit for bit, with ids mapped back to the full index (+ id_offset), in the canonical order.
+ *   filter: a bitmap of uint32 words -- bit i is bit i & 31 of word i >> 5; row r is allowed for query b iff bit filter_bit0 + r of the
+ *   bitmap at filter + b * filter_ld is set.  filter_ld = 0: one bitmap for the whole batch; else >= the (filter_bit0 + n_rows + 31) / 32
+ *   words a bitmap spans.  Host pointer, or device pointer on the index's device (as q).  filter == NULL: exactly vs_index_search.
+ *   Fewer than k allowed rows: the positions behind them hold id -1, score -inf (an empty filter returns only those).  k > n_rows is
+ *   still VS_ERANGE.  Every path gates candidate admission inside its kernels (k does not grow); with device pointers and a non-NULL
+ *   stream the blocked-postings filter path (last_path == 3) only enqueues work, as vs_index_search does.                        */
+VS_API int vs_index_search_filtered(vs_index* index, const void* q, int q_dtype, int64_t ldq, int32_t B, int32_t k,
+                                    const uint32_t* filter, int64_t filter_bit0, int64_t filter_ld,
+                                    int64_t id_offset, int64_t* out_ids, float* out_scores, void* stream);
+
+/* bool / uint8 mask [B, n] (row stride ld_mask bytes; non-zero = allowed) -> the bitmap words [B, ld_words] vs_index_search_filtered
+ * reads (bits past n of a row's last word are 0).  mask and words: host pointers or device pointers on `device` (VS_EINVAL otherwise).  stream as in
+ * vs_index_search (host buffers block).                                                                                          */
+VS_API int vs_filter_pack(const uint8_t* mask, int32_t B, int64_t n, int64_t ld_mask, uint32_t* words, int64_t ld_words,
+                          int device, void* stream);
+
 /* Dense score matrix [B, n_rows] fp32 -- the intermediate index.py:91 materialises.  Used by the
  * parity tests to check every score, not just the top-k.                                         */
 VS_API int vs_index_scores(vs_index* index, const void* q, int q_dtype, int64_t ldq, int32_t B,
@@ -253,6 +271,12 @@ typedef struct vs_shard_group vs_shard_group;
 VS_API int  vs_shard_group_create(vs_index* const* shards, int32_t n_shards, vs_shard_group** out);
 VS_API int  vs_shard_group_search(vs_shard_group* group, const void* q, int q_dtype, int64_t ldq, int32_t B, int32_t k,
                                   int64_t* out_ids, float* out_scores);
+/* vs_shard_group_search under a document filter over the GROUP's rows (global ids): shard i reads the bitmap from bit = its first global
+ * row on (vs_index_search_filtered's filter_bit0; generally not a multiple of 32), on its own device -- a host bitmap or one on another
+ * GPU is copied there as q is.  filter_ld = 0: one bitmap for the batch, else >= (total rows + 31) / 32 words a query.  Padding (fewer
+ * than k allowed rows) comes out of the merge as id -1, score -inf.  filter == NULL: exactly vs_shard_group_search.              */
+VS_API int  vs_shard_group_search_filtered(vs_shard_group* group, const void* q, int q_dtype, int64_t ldq, int32_t B, int32_t k,
+                                           const uint32_t* filter, int64_t filter_ld, int64_t* out_ids, float* out_scores);
 VS_API void vs_shard_group_destroy(vs_shard_group* group);
 
 /* SparseIndex.save (index.py:181-202) needs crow/col/values back: int64 rowptr [n_rows+1], int64
@@ -264,7 +288,8 @@ VS_API void vs_index_destroy(vs_index* index);
 
 /* Row-sharded search, merge step (new in this build): candidates gathered from
  * all shards ([B, n_cand] global ids + scores, e.g. after an RCCL all-gather) -> canonical top-k. */
-/* (ids must be in [0, 2^32 - 1): the merge keys hold 32-bit ids; a candidate outside that range is dropped, never aliased) */
+/* (ids must be in [0, 2^32 - 1): the merge keys hold 32-bit ids; a candidate outside that range -- the id -1 padding of a filtered
+ *  search among them -- is dropped, never aliased; fewer than k candidates left: id -1, score -inf behind them)                     */
 VS_API int vs_merge_topk(const int64_t* cand_ids, const float* cand_scores, int32_t B, int64_t n_cand, int32_t k,
                          int64_t* out_ids, float* out_scores, int device, void* stream);
 

@@ -50,6 +50,8 @@ _SIGNATURES = {
     "vs_index_create_dense_auto": ([_vp, _int, _int, _i64, _i32, _i64, C.c_double, _int, C.POINTER(_vp)], _int),
     "vs_index_create_synthetic": ([C.c_uint64, _i64, _i64, _i32, _i32, _int, _int, _int, _int, C.POINTER(_vp)], _int),
     "vs_index_search": ([_vp, _vp, _int, _i64, _i32, _i32, _i64, _vp, _vp, _vp], _int),
+    "vs_index_search_filtered": ([_vp, _vp, _int, _i64, _i32, _i32, _vp, _i64, _i64, _i64, _vp, _vp, _vp], _int),
+    "vs_filter_pack": ([_vp, _i32, _i64, _i64, _vp, _i64, _int, _vp], _int),
     "vs_index_scores": ([_vp, _vp, _int, _i64, _i32, _vp, _vp], _int),
     "vs_index_prepare": ([_vp, _vp], _int),
     "vs_index_info": ([_vp, C.POINTER(IndexInfo)], _int),
@@ -60,6 +62,7 @@ _SIGNATURES = {
     "vs_index_destroy": ([_vp], None),
     "vs_shard_group_create": ([C.POINTER(_vp), _i32, C.POINTER(_vp)], _int),
     "vs_shard_group_search": ([_vp, _vp, _int, _i64, _i32, _i32, _vp, _vp], _int),
+    "vs_shard_group_search_filtered": ([_vp, _vp, _int, _i64, _i32, _i32, _vp, _i64, _vp, _vp], _int),
     "vs_shard_group_destroy": ([_vp], None),
     "vs_merge_topk": ([_vp, _vp, _i32, _i64, _i32, _vp, _vp, _int, _vp], _int),
     "vs_topk_mask": ([_vp, _i32, _i32, _i64, _i32, _vp, _int, _vp], _int),

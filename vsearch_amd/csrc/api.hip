@@ -49,6 +49,92 @@ extern "C" int vs_index_search(vs_index* idx, const void* q, int q_dtype, int64_
     return VS_OK;
 }
 
+// ---- filtered search (DocFilter): the bitmap reaches the kernels as vs_index::filt for the duration of the call ---------------------
+// words a bitmap of `rows` rows starting at bit `bit0` spans; a per-query bitmap (ld > 0) must hold them in its row of ld words
+static int64_t filter_words(int64_t bit0, int64_t rows) { return (bit0 + rows + 31) >> 5; }
+static int check_filter_args(int64_t bit0, int64_t ld, int64_t rows) {
+    if (bit0 < 0) return fail(VS_EINVAL, "filter_bit0 must be >= 0");
+    if (ld < 0) return fail(VS_EINVAL, "filter_ld must be >= 0");
+    if (ld > 0 && ld < filter_words(bit0, rows))
+        return fail(VS_EINVAL, "filter_ld = %lld words is shorter than the %lld a query's bitmap spans", (long long)ld, (long long)filter_words(bit0, rows));
+    return VS_OK;
+}
+
+extern "C" int vs_index_search_filtered(vs_index* idx, const void* q, int q_dtype, int64_t ldq, int32_t B, int32_t k, const uint32_t* filter,
+                                        int64_t filter_bit0, int64_t filter_ld, int64_t id_offset, int64_t* out_ids, float* out_scores, void* stream) {
+    if (!filter) return vs_index_search(idx, q, q_dtype, ldq, B, k, id_offset, out_ids, out_scores, stream);
+    VS_TRY(check_search_args(idx, q, ldq, B));
+    VS_TRY(check_filter_args(filter_bit0, filter_ld, idx->n_rows));
+    VS_HIP(hipSetDevice(idx->device));
+    hipStream_t s = (hipStream_t)stream;
+    const uint32_t* words = filter;
+    if (is_device_ptr(filter)) {
+        hipPointerAttribute_t attr;
+        VS_HIP(hipPointerGetAttributes(&attr, filter));
+        if (attr.device != idx->device) return fail(VS_EINVAL, "the filter lives on device %d, the index on device %d", attr.device, idx->device);
+    } else {
+        // host bitmap: the words the batch reads, staged on the index's device (as vs_index_search does with host queries)
+        const size_t bytes = (size_t)((filter_ld > 0 ? (int64_t)(B - 1) * filter_ld : 0) + filter_words(filter_bit0, idx->n_rows)) * 4;
+        VS_TRY(idx->ws_filt.reserve(bytes));
+        VS_HIP(hipMemcpyAsync(idx->ws_filt.p, filter, bytes, hipMemcpyHostToDevice, s));
+        words = idx->ws_filt.as<uint32_t>();
+    }
+    idx->filt = FilterArgs{words, filter_bit0, filter_ld};
+    const int rc = vs_index_search(idx, q, q_dtype, ldq, B, k, id_offset, out_ids, out_scores, stream);
+    idx->filt = FilterArgs{};
+    return rc;
+}
+
+// mask [B, n] (uint8 / bool, row stride ld_mask bytes) -> bitmap [B, ld_words]: a wave packs 64 consecutive elements of a row with one ballot
+__global__ __launch_bounds__(256) void filter_pack_kernel(const uint8_t* mask, int32_t B, int64_t n, int64_t ld_mask, uint32_t* words, int64_t ld_words) {
+    const int lane = threadIdx.x & 63;
+    const int64_t per_row = (n + 63) >> 6, nw = (n + 31) >> 5;
+    const int64_t items = (int64_t)B * per_row;
+    for (int64_t it = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); it < items; it += (int64_t)gridDim.x * 4) {
+        const int64_t b = it / per_row, j = it % per_row, e = j * 64 + lane;
+        const bool on = e < n && mask[(size_t)b * (size_t)ld_mask + (size_t)e] != 0;
+        const unsigned long long m = __builtin_amdgcn_ballot_w64(on);
+        if (lane < 2 && 2 * j + lane < nw) words[(size_t)b * (size_t)ld_words + (size_t)(2 * j + lane)] = (uint32_t)(m >> (32 * lane));
+    }
+}
+
+extern "C" int vs_filter_pack(const uint8_t* mask, int32_t B, int64_t n, int64_t ld_mask, uint32_t* words, int64_t ld_words, int device, void* stream) {
+    if (!mask || !words) return fail(VS_EINVAL, "NULL argument");
+    if (B <= 0 || n <= 0) return fail(VS_EINVAL, "B and n must be positive");
+    const int64_t nw = (n + 31) >> 5;
+    if (ld_mask < n && B > 1) return fail(VS_EINVAL, "ld_mask = %lld is shorter than a row of %lld elements", (long long)ld_mask, (long long)n);
+    if (ld_words < nw && B > 1) return fail(VS_EINVAL, "ld_words = %lld is shorter than the %lld words a row packs into", (long long)ld_words, (long long)nw);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return fail(VS_ENODEVICE, "no HIP device visible"); }
+    if (device < 0 || device >= ndev) return fail(VS_EINVAL, "device %d out of range (have %d)", device, ndev);
+    // device buffers must live on `device` (the kernel runs there)
+    for (const void* p : {(const void*)mask, (const void*)words}) {
+        if (!is_device_ptr(p)) continue;
+        hipPointerAttribute_t attr;
+        VS_HIP(hipPointerGetAttributes(&attr, p));
+        if (attr.device != device) return fail(VS_EINVAL, "a device buffer of vs_filter_pack lives on device %d, not on device %d", attr.device, device);
+    }
+    VS_HIP(hipSetDevice(device));
+    hipStream_t s = (hipStream_t)stream;
+    DevBuf st_mask, st_words;
+    const void* d_mask = nullptr;
+    VS_TRY(to_device(mask, (size_t)(B - 1) * (size_t)ld_mask + (size_t)n, st_mask, s, &d_mask));
+    const bool out_dev = is_device_ptr(words);
+    const size_t w_bytes = ((size_t)(B - 1) * (size_t)ld_words + (size_t)nw) * 4;
+    uint32_t* d_words = words;
+    if (!out_dev) {
+        VS_TRY(st_words.alloc(w_bytes));
+        d_words = st_words.as<uint32_t>();
+    }
+    const int64_t waves = (int64_t)B * ((n + 63) >> 6);
+    hipLaunchKernelGGL(filter_pack_kernel, dim3((unsigned)std::min<int64_t>((waves + 3) / 4, 65536)), dim3(256), 0, s, (const uint8_t*)d_mask, B, n, ld_mask,
+                       d_words, ld_words);
+    VS_HIP(hipGetLastError());
+    if (!out_dev) VS_HIP(hipMemcpyAsync(words, d_words, w_bytes, hipMemcpyDeviceToHost, s));
+    if (!out_dev || st_mask.p || !s) VS_HIP(hipStreamSynchronize(s));                 // host buffers / staging die here
+    return VS_OK;
+}
+
 extern "C" int vs_index_prepare(vs_index* idx, void* stream) {
     if (!idx) return fail(VS_EINVAL, "NULL index");
     VS_HIP(hipSetDevice(idx->device));
@@ -202,6 +288,7 @@ struct vs_shard_group {
     std::vector<bool> owns_stream;            // (shards on one device share the first one's stream)
     std::vector<hipEvent_t> done;
     std::vector<vs::DevBuf*> q, ids, sc;      // per shard, on the shard's device
+    std::vector<vs::DevBuf*> filt;            // per shard: a filtered search's bitmap, when it lives elsewhere
     vs::DevBuf all_ids, all_sc, out_ids, out_sc;   // on shards[0]'s device
     int64_t n_total = 0;
 };
@@ -215,6 +302,7 @@ extern "C" void vs_shard_group_destroy(vs_shard_group* g) {
         if (i < g->q.size()) delete g->q[i];
         if (i < g->ids.size()) delete g->ids[i];
         if (i < g->sc.size()) delete g->sc[i];
+        if (i < g->filt.size()) delete g->filt[i];
     }
     for (size_t i = 0; i < g->streams.size(); ++i)
         if (g->streams[i] && i < g->owns_stream.size() && g->owns_stream[i]) { (void)hipSetDevice(g->shards[i]->device); (void)hipStreamDestroy(g->streams[i]); }
@@ -251,6 +339,7 @@ extern "C" int vs_shard_group_create(vs_index* const* shards, int32_t n_shards, 
         g->q.push_back(new vs::DevBuf());
         g->ids.push_back(new vs::DevBuf());
         g->sc.push_back(new vs::DevBuf());
+        g->filt.push_back(new vs::DevBuf());
     }
     if (row >= 0xFFFFFFFFll) return fail(VS_EUNSUPPORTED, "a shard group addresses fewer than 2^32 - 1 documents (%lld given): merged ids are 32-bit", (long long)row);
     g->n_total = row;
@@ -259,7 +348,8 @@ extern "C" int vs_shard_group_create(vs_index* const* shards, int32_t n_shards, 
     return VS_OK;
 }
 
-extern "C" int vs_shard_group_search(vs_shard_group* g, const void* q, int q_dtype, int64_t ldq, int32_t B, int32_t k, int64_t* out_ids, float* out_scores) {
+static int shard_group_search(vs_shard_group* g, const void* q, int q_dtype, int64_t ldq, int32_t B, int32_t k, const uint32_t* filter, int64_t filter_ld,
+                              int64_t* out_ids, float* out_scores) {
     if (!g || !q || !out_ids || !out_scores) return fail(VS_EINVAL, "NULL argument");
     if (B <= 0 || k <= 0) return fail(VS_EINVAL, "B and k must be positive");
     if (k > g->n_total) return fail(VS_ERANGE, "selected index k out of range (k = %d > %lld rows)", k, (long long)g->n_total);
@@ -275,6 +365,20 @@ extern "C" int vs_shard_group_search(vs_shard_group* g, const void* q, int q_dty
         hipPointerAttribute_t attr;
         VS_HIP(hipPointerGetAttributes(&attr, q));
         q_device = attr.device;
+    }
+    // the global bitmap: shard i reads it from bit row0[i] on, on its own device (copied there as q is)
+    if (filter && filter_ld < 0) return fail(VS_EINVAL, "filter_ld must be >= 0");
+    if (filter && filter_ld > 0 && filter_ld < filter_words(0, g->n_total))
+        return fail(VS_EINVAL, "filter_ld = %lld words is shorter than the %lld the group's rows span", (long long)filter_ld, (long long)filter_words(0, g->n_total));
+    const size_t f_bytes = filter ? (size_t)((filter_ld > 0 ? (int64_t)(B - 1) * filter_ld : 0) + filter_words(0, g->n_total)) * 4 : 0;
+    const bool f_dev = filter && is_device_ptr(filter);
+    int f_device = 0;
+    if (f_dev) {
+        hipPointerAttribute_t attr;
+        VS_HIP(hipPointerGetAttributes(&attr, filter));
+        f_device = attr.device;
+        VS_HIP(hipSetDevice(f_device));
+        VS_HIP(hipDeviceSynchronize());
     }
     // Device-resident queries or outputs: the shards run on the group's OWN non-blocking streams, which nothing orders after the
     // stream that produced `q` (an encoder still writing it) or that last used the output buffers (an allocator that recycles them).
@@ -298,9 +402,17 @@ extern "C" int vs_shard_group_search(vs_shard_group* g, const void* q, int q_dty
             else VS_HIP(hipMemcpyAsync(g->q[i]->p, q, q_bytes, hipMemcpyHostToDevice, g->streams[i]));
             dq = g->q[i]->p;
         }
+        const uint32_t* df = filter;
+        if (filter && (!f_dev || f_device != s->device)) {
+            VS_TRY(g->filt[i]->reserve(f_bytes));
+            if (f_dev) VS_HIP(hipMemcpyPeerAsync(g->filt[i]->p, s->device, filter, f_device, f_bytes, g->streams[i]));
+            else VS_HIP(hipMemcpyAsync(g->filt[i]->p, filter, f_bytes, hipMemcpyHostToDevice, g->streams[i]));
+            df = g->filt[i]->as<uint32_t>();
+        }
         VS_TRY(g->ids[i]->reserve((size_t)B * ki[i] * 8));
         VS_TRY(g->sc[i]->reserve((size_t)B * ki[i] * 4));
-        VS_TRY(vs_index_search(s, dq, q_dtype, ldq, B, ki[i], g->row0[i], g->ids[i]->as<int64_t>(), g->sc[i]->as<float>(), (void*)g->streams[i]));
+        VS_TRY(vs_index_search_filtered(s, dq, q_dtype, ldq, B, ki[i], df, g->row0[i], filter_ld, g->row0[i], g->ids[i]->as<int64_t>(), g->sc[i]->as<float>(),
+                                        (void*)g->streams[i]));
         VS_HIP(hipEventRecord(g->done[i], g->streams[i]));
     }
     // 2. the exchange: every shard's [B, k_i] block lands in columns of the [B, sum k_i] candidate matrix on the first shard's GPU
@@ -335,6 +447,15 @@ extern "C" int vs_shard_group_search(vs_shard_group* g, const void* q, int q_dty
     }
     VS_HIP(hipStreamSynchronize(st0));
     return VS_OK;
+}
+
+extern "C" int vs_shard_group_search(vs_shard_group* g, const void* q, int q_dtype, int64_t ldq, int32_t B, int32_t k, int64_t* out_ids, float* out_scores) {
+    return shard_group_search(g, q, q_dtype, ldq, B, k, nullptr, 0, out_ids, out_scores);
+}
+
+extern "C" int vs_shard_group_search_filtered(vs_shard_group* g, const void* q, int q_dtype, int64_t ldq, int32_t B, int32_t k, const uint32_t* filter,
+                                              int64_t filter_ld, int64_t* out_ids, float* out_scores) {
+    return shard_group_search(g, q, q_dtype, ldq, B, k, filter, filter_ld, out_ids, out_scores);
 }
 
 extern "C" int vs_profile_enable(int on) {

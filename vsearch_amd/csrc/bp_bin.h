@@ -30,8 +30,8 @@ __host__ __device__ inline size_t bp_bin_lds_bytes(int ent_cap) {
     return (size_t)8 * (RMAX + kBinSpare) * 4 + (size_t)kFlCap * 8 + 8 * 16 + 32 * 4 + (size_t)ent_cap * 8;
 }
 
-template <int RMAX>
-__global__ __launch_bounds__(kScanThreads) void bp_bin_topk(BpArgs a) {
+template <int RMAX, int FL = 0>          // FL = 1: a filtered search (KArg, common.h)
+__global__ __launch_bounds__(kScanThreads) void bp_bin_topk(KArg<BpArgs, FL> a) {
     static_assert(RMAX == kBpRowsMaxBin && RMAX == 2 * kScanThreads, "pad postings carry document id kBpRowsMaxBin; a thread finishes documents 2 t and 2 t + 1");
     constexpr int QT = 8, NB = 8;
     constexpr int RS = 16;
@@ -266,11 +266,11 @@ __global__ __launch_bounds__(kScanThreads) void bp_bin_topk(BpArgs a) {
                             const uint64_t k0 = ((uint64_t)h0 << 32) | (uint32_t)(~(uint32_t)row);
                             const uint64_t k1 = ((uint64_t)h1 << 32) | (uint32_t)(~(uint32_t)(row + 1));
                             const unsigned long long tq = tau[q], uq = upper_sh[q];
-                            if (k0 > tq && k0 < uq) {
+                            if (k0 > tq && k0 < uq && (FL == 0 || filter_ok(a, q0 + q, row))) {
                                 const uint32_t pos = atomicAdd(&ccnt[q], 1u);
                                 my_gcand[(size_t)q * kFlCap + pos] = k0;
                             }
-                            if (d + 1 < rows_b && k1 > tq && k1 < uq) {
+                            if (d + 1 < rows_b && k1 > tq && k1 < uq && (FL == 0 || filter_ok(a, q0 + q, row + 1))) {
                                 const uint32_t pos = atomicAdd(&ccnt[q], 1u);
                                 my_gcand[(size_t)q * kFlCap + pos] = k1;
                             }

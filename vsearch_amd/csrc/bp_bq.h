@@ -185,8 +185,11 @@ __global__ __launch_bounds__(kScanThreads) void bq_split_kernel(const int2* tile
 // smallest power-of-two scale that makes the weights integers instead of the 2^30 one), bq_split_kernel sends the tiles whose queries
 // all qualify here and cuts the others into two-slot tiles for the int32 kernel.  The epilogue takes a block's sums as the difference
 // of the running dwords as before (mod 2^32 the carries of earlier blocks cancel) and splits the difference into its halves.
-template <int QT, int TM, int PK = 0>          // QT = query slots (2: blocks of up to 8192 documents, 4: up to 4096; PK: 4 on two planes of 8192); TM = 1: phase clocks (VS_BP_TIMING)
-__global__ __launch_bounds__(kScanThreads) void bp_bq_topk(BpArgs a) {
+// FL = 1: a filtered search -- a document a query's filter does not allow never enters that query's candidates (its pending bit is
+// cleared before the pushes; the sums, the thresholds and the cut decisions are the walk's as before).  The walk prefetches nothing
+// across the epilogue, so the filter words are read there.
+template <int QT, int TM, int PK = 0, int FL = 0>          // QT = query slots (2: blocks of up to 8192 documents, 4: up to 4096; PK: 4 on two planes of 8192); TM = 1: phase clocks (VS_BP_TIMING)
+__global__ __launch_bounds__(kScanThreads) void bp_bq_topk(KArg<BpArgs, FL> a) {
     constexpr int NP = PK ? QT / 2 : QT;                                                    // planes
     constexpr int RMAX = bq_rmax(NP), NH = RMAX / (4 * kScanThreads);
     constexpr uint32_t PLANE = bq_plane(NP);
@@ -424,6 +427,22 @@ __global__ __launch_bounds__(kScanThreads) void bp_bq_topk(BpArgs a) {
 #pragma unroll
                             for (int j = 0; j < 4; ++j)
                                 if (q < nq && h * 4096 + 4 * tid + j < rows_b && (sum_of(q, h, j) ^ 0x80000000u) >= thi[q]) pend |= 1u << ((q * NH + h) * 4 + j);
+                }
+                if constexpr (FL != 0) {
+                    uint32_t allow = 0u;
+#pragma unroll
+                    for (int h = 0; h < NH; ++h)
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            const int d = h * 4096 + 4 * tid + j;
+                            if (d < rows_b) {
+                                const int64_t row = (int64_t)b * a.rows + d;
+#pragma unroll
+                                for (int q = 0; q < QT; ++q)
+                                    if (q < nq && filter_ok(a, q0 + q, row)) allow |= 1u << ((q * NH + h) * 4 + j);
+                            }
+                        }
+                    pend &= allow;
                 }
                 lap(3);                                                  // (phase clocks: "dense" = reading the sums and testing them)
                 const bool last = b + 1 >= b1;

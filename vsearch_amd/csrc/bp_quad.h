@@ -253,10 +253,20 @@ __global__ __launch_bounds__(256) void quad_arrange_kernel(uint32_t* rec, unsign
 // waves walk the table (quad_walk_asm: wave w takes steps w, w + 16, ...); chunks that link to an overflow chunk leave a descriptor in
 // the wave's own list, which the wave walks right after (quad_list_asm), and so on down the chain; one LDS barrier; the epilogue turns
 // the block's sums into candidates.  The only global loads of a block are its chunks (and one scalar load of the next block's base).
+// (FL = 1: and the filter words of its documents -- before the epilogue, see below.)
 typedef unsigned short quad_us2 __attribute__((ext_vector_type(2)));
 
-template <int TM>          // TM = 1: phase clocks (VS_BP_TIMING)
-__global__ __launch_bounds__(kScanThreads) void bp_quad_topk(BpArgs a) {
+// FL = 1: a filtered search.  A thread's two documents of a block get their filter bits BEFORE the epilogue, from words loaded ahead of
+// the block's walk (in flight while it runs): a shared filter's two words of the thread's documents; a per-query filter's 65 words x 8
+// slots of the block, one per thread, staged in LDS behind the walk ([word][slot]: a document's 8 words are two 16-byte reads).  Either
+// way the bits -- one word: document round r, slot q at bit r * QT + q -- are in a register before the L2 prefetch of the next block is
+// issued, and the epilogue reads no global memory (a wait there would drain the prefetch).  The bits gate which documents are pushed.
+static_assert(kQuadRows <= 2 * kScanThreads && kQuadQT * 2 <= 32, "a thread's filter bits: two document rounds x the slots in one word");
+constexpr int kQuadFiltWords = kQuadRows / 32 + 1;                 // words a block's documents span from any bit offset
+constexpr size_t kQuadFiltStageBytes = (size_t)kQuadFiltWords * kQuadQT * 4;
+static_assert(kQuadFiltWords * kQuadQT <= kScanThreads && quad_lds_bytes() + kQuadFiltStageBytes <= (size_t)160 * 1024, "the per-query filter stage");
+template <int TM, int FL = 0>          // TM = 1: phase clocks (VS_BP_TIMING)
+__global__ __launch_bounds__(kScanThreads) void bp_quad_topk(KArg<BpArgs, FL> a) {
     constexpr int QT = kQuadQT;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     int32_t* acc = reinterpret_cast<int32_t*>(smem);                                        // LDS address 0 (no static LDS in this kernel)
@@ -336,6 +346,18 @@ __global__ __launch_bounds__(kScanThreads) void bp_quad_topk(BpArgs a) {
         for (int64_t b = b0; b < b1 || b == b0; ++b) {
             const bool have = b < b1;
             const int rows_b = have ? (int)min((int64_t)a.rows, a.n_rows - b * a.rows) : 0;
+            [[maybe_unused]] uint32_t fw0 = 0u, fw1 = 0u;                 // FL: shared filter -- the words of the thread's two documents; per query -- one word of the stage
+            if constexpr (FL != 0) {
+                if (a.filt.ld == 0) {
+                    const uint64_t bit = (uint64_t)(a.filt.bit0 + b * a.rows + tid);
+                    if (tid < rows_b) fw0 = a.filt.words[bit >> 5];
+                    if (tid + kScanThreads < rows_b) fw1 = a.filt.words[(bit + kScanThreads) >> 5];
+                } else if (have) {
+                    const int64_t w0 = (a.filt.bit0 + b * a.rows) >> 5, w1 = (a.filt.bit0 + b * a.rows + rows_b - 1) >> 5;
+                    const int q = tid & (QT - 1), w = tid / QT;
+                    if (w < kQuadFiltWords && q < nq && w0 + w <= w1) fw0 = a.filt.words[(size_t)(q0 + q) * (size_t)a.filt.ld + (size_t)(w0 + w)];
+                }
+            }
             if (have && trips > 0) {
                 const char* brec = a.rec + (size_t)base_cur * kQuadChunkBytes;
                 // the overflow chunks a walk found: the wave's list `cur` holds n of them; their own links go to the other list
@@ -382,7 +404,40 @@ __global__ __launch_bounds__(kScanThreads) void bp_quad_topk(BpArgs a) {
             }
             if (b + 1 < b1) base_cur = a.base[b + 1];
             if (a.gtau && tid < nq) { const unsigned long long g = a.gtau[q0 + tid]; if (g > tau[tid]) tau[tid] = g; }
+            [[maybe_unused]] uint32_t fbits = 0u;                          // FL: bit r * QT + q = document tid + r * kScanThreads allowed for slot q
+            [[maybe_unused]] uint32_t* fstage = reinterpret_cast<uint32_t*>(smem + quad_lds_bytes());      // FL, per query: [word][slot]
+            if constexpr (FL != 0) {
+                if (a.filt.ld == 0) {
+#pragma unroll
+                    for (int r = 0; r < 2; ++r) {
+                        const uint64_t bit = (uint64_t)(a.filt.bit0 + b * a.rows + r * kScanThreads + tid);
+                        if (r * kScanThreads + tid < rows_b && (((r ? fw1 : fw0) >> (bit & 31u)) & 1u)) fbits |= 0xFFu << (r * QT);
+                    }
+                } else if (tid < kQuadFiltWords * QT) {
+                    fstage[tid] = fw0;                                   // (the previous block's readers are past the epilogue's barriers)
+                }
+                // (the filter words are in, on every path, BEFORE the prefetch below is issued: a wait the compiler sees -- 0x0F70 = vmcnt(0) alone
+                //  on gfx9 -- so that it never waits for one of those loads again, behind the prefetch; an inline-asm wait it would not see)
+                __builtin_amdgcn_s_waitcnt(0x0F70);
+            }
             lds_barrier();                                               // the block's sums are complete
+            if constexpr (FL != 0) {
+                if (a.filt.ld != 0) {                                    // per query: the thread's two documents' 8 words each, from the stage
+                    const int64_t w0 = (a.filt.bit0 + b * a.rows) >> 5;
+#pragma unroll
+                    for (int r = 0; r < 2; ++r) {
+                        const int d = r * kScanThreads + tid;
+                        if (d < rows_b) {
+                            const uint64_t bit = (uint64_t)(a.filt.bit0 + b * a.rows + d);
+                            const uint4* p = reinterpret_cast<const uint4*>(fstage + ((int64_t)(bit >> 5) - w0) * QT);
+                            const uint4 lo = p[0], hi = p[1];
+                            const uint32_t w[QT] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+#pragma unroll
+                            for (int q = 0; q < QT; ++q) fbits |= ((w[q] >> (bit & 31u)) & 1u) << (r * QT + q);
+                        }
+                    }
+                }
+            }
             // The NEXT block's cold start: the epilogue below drains every load a wave had in flight, and the next walk's first steps would
             // each wait for a line that leaves the L2.  One dword per lane from the 64 lines of this wave's first 8 steps (lane l: step
             // l >> 3, lane group (l >> 1) & 3, half l & 1 of the 256-byte chunk) brings them into the XCD's L2 while the epilogue runs;
@@ -448,7 +503,7 @@ __global__ __launch_bounds__(kScanThreads) void bp_quad_topk(BpArgs a) {
 #endif
 #pragma unroll
                     for (int q = 0; q < QT; ++q) {
-                        if (sums[q] >= thr[q]) {
+                        if (sums[q] >= thr[q] && (FL == 0 || ((fbits >> ((d0 >= kScanThreads ? QT : 0) + q)) & 1u) != 0u)) {
                             const uint32_t hi = (uint32_t)sums[q] ^ 0x80000000u;
                             const uint64_t key = ((uint64_t)hi << 32) | (uint32_t)(~(uint32_t)row);
                             if (key > tau[q] && key < upper_sh[q]) {

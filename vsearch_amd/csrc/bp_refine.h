@@ -141,6 +141,9 @@ struct RefineArgs {
     int64_t out_ld;
     uint32_t* flags;          // [B] in: 2 = the query entered no tile; out: 1 = the top k could not be proven from K' candidates
 };
+// (a filtered search, PAD = 1: the walk admitted allowed documents only, so the K' candidates -- and the cut key the proof starts from --
+//  are taken over the allowed rows, and the proof holds as it stands: cut_key == 0 means every allowed row is a candidate.  Fewer than k
+//  of them: the positions behind the last come out as id -1, score -inf.)
 
 // IMG = 1: the query's dense fp32 row sits in LDS for the re-scoring (118 KB at V = 29 523: with the candidate buffers 159 KB, one
 // workgroup per CU).  The 98 k weight look-ups of a query's 128 candidates are random 4-byte reads: from L2 they ran at the CU's
@@ -149,7 +152,7 @@ struct RefineArgs {
 __host__ __device__ inline size_t refine_lds_bytes(int32_t n_cols, int img) {
     return (img ? scan_img_bytes(n_cols) : 0) + (size_t)kWgCap * 8 + (size_t)kBpMaxK * 8 + 16;
 }
-template <int VM, int IMG>
+template <int VM, int IMG, int PAD = 0>
 __global__ __launch_bounds__(kScanThreads) void refine_topk_kernel(RefineArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem_r[];
     float* img = reinterpret_cast<float*>(smem_r);
@@ -189,6 +192,13 @@ __global__ __launch_bounds__(kScanThreads) void refine_topk_kernel(RefineArgs a)
         wg_sort_desc<kScanThreads>(ex, pow2, tid);
         for (int i = tid; i < K; i += kScanThreads) {
             const uint64_t key = ex[i];
+            if constexpr (PAD != 0) {
+                if (key == 0ull) {
+                    a.out_ids[(size_t)b * a.out_ld + i] = -1;
+                    a.out_scores[(size_t)b * a.out_ld + i] = -INFINITY;
+                    continue;
+                }
+            }
             a.out_ids[(size_t)b * a.out_ld + i] = (int64_t)key_row(key) + a.id_offset;
             a.out_scores[(size_t)b * a.out_ld + i] = key_score(key);
         }

@@ -64,68 +64,83 @@ template <int AM>
 bool bp_flat_ok(const vs_index* idx, const BpArgs& a) { return AM == AM_FIX && !a.upper && bp_walk_kind(idx) >= 1; }
 // walk 2 (two accumulator sets, bp_duo.h) serves this call: 4 query slots per tile, K' within its candidate buffers
 bool bp_duo_ok(const vs_index* idx, int kp, const uint64_t* upper) { return bp_walk_kind(idx) == 2 && !upper && kp <= kDuoMaxK; }
-template <int QT, int AM>
-int launch_bp_walk(const vs_index* idx, const BpArgs& a, int grid, int ent_cap, hipStream_t s) {
+template <int QT, int AM, int FL>
+int launch_bp_walk_fl(const vs_index* idx, const BpArgs& a, int grid, int ent_cap, hipStream_t s) {
     const int vm = bp_record_vm(idx);
     size_t lds = bp_lds_bytes<QT, AM, kBpRowsMax>(ent_cap, AM == AM_FIX ? a.n_head : 0);
-    void (*kern)(BpArgs) = nullptr;
+    void (*kern)(KArg<BpArgs, FL>) = nullptr;
     if (idx->bp_quad) {
         // quad chunks (bp_quad.h): the fixed-point filter walk only
         if (AM != AM_FIX || a.upper || ent_cap > kBpEntCap) return fail(VS_EUNSUPPORTED, "quad postings serve the filter walk only");
-        kern = a.timing ? bp_quad_topk<1> : bp_quad_topk<0>;
-        lds = quad_lds_bytes();
+        kern = a.timing ? bp_quad_topk<1, FL> : bp_quad_topk<0, FL>;
+        lds = quad_lds_bytes() + (FL != 0 ? kQuadFiltStageBytes : 0);        // (FL: the per-query filter's stage behind the rest)
     } else if (idx->bp_bq) {
         // bag-of-token chunks (bp_bq.h): the fixed-point filter walk only
         if (AM != AM_FIX || a.upper || ent_cap > kBqEntCap) return fail(VS_EUNSUPPORTED, "bag-of-token chunks serve the filter walk only");
         const int bq_qt = bq_slots(idx->bp_rows);
-        kern = bq_qt == 2 ? (a.timing ? bp_bq_topk<2, 1> : bp_bq_topk<2, 0>) : (a.timing ? bp_bq_topk<4, 1> : bp_bq_topk<4, 0>);
+        kern = bq_qt == 2 ? (a.timing ? bp_bq_topk<2, 1, 0, FL> : bp_bq_topk<2, 0, 0, FL>) : (a.timing ? bp_bq_topk<4, 1, 0, FL> : bp_bq_topk<4, 0, 0, FL>);
         lds = bq_lds_bytes(bq_qt);
 #ifdef VS_EXPERIMENTAL_WALKS
     } else if (AM == AM_FIX && bp_duo_ok(idx, a.k, a.upper) && ent_cap <= kDuoEntCap) {
+        if constexpr (FL != 0) return fail(VS_EUNSUPPORTED, "the experimental walks take no document filter");
+        else {
         if (vm == VM_F32) kern = bp_duo_topk<VM_F32, kBpNB, kBpRowsMax>;
         else kern = bp_duo_topk<VM_F16, kBpNBWide, kBpRowsMax>;
+        }
         lds = bp_duo_lds_bytes<kBpRowsMax>(ent_cap);
     } else if (bp_flat_ok<AM>(idx, a) && bp_walk_kind(idx) == 3) {
+        if constexpr (FL != 0) return fail(VS_EUNSUPPORTED, "the experimental walks take no document filter");
+        else {
         if (vm == VM_F32) kern = bp_stream_topk<VM_F32, 3, kBpRowsMax>;
         else kern = bp_stream_topk<VM_F16, 4, kBpRowsMax>;
+        }
         lds = bp_stream_lds_bytes<kBpRowsMax>(ent_cap);
     } else if (bp_flat_ok<AM>(idx, a) && bp_walk_kind(idx) != 2) {
+        if constexpr (FL != 0) return fail(VS_EUNSUPPORTED, "the experimental walks take no document filter");
+        else {
         // valued records, no dense strips, fixed-point filter: the flat walk (bp_flat.h)
         if (vm == VM_F32) { kern = bp_flat_topk<VM_F32, kFlRoundsF32, kBpRowsMax>; lds = bp_flat_lds_bytes<kFlRoundsF32, kBpRowsMax>(ent_cap); }
         else { kern = bp_flat_topk<VM_F16, kFlRoundsF16, kBpRowsMax>; lds = bp_flat_lds_bytes<kFlRoundsF16, kBpRowsMax>(ent_cap); }
+        }
 #endif
     } else if (vm == VM_BIN && AM == AM_FIX && idx->bp_walk_pref != 0 && !a.upper && ent_cap <= kBpEntCap) {          // (records: postings_walk = 5, or no room for the chunks)
         // bag-of-token index: the walk with the next block's records prefetched across the barrier (bp_bin.h); postings_walk = 0: the list walk
-        kern = bp_bin_topk<kBpRowsMaxBin>;
+        kern = bp_bin_topk<kBpRowsMaxBin, FL>;
         lds = bp_bin_lds_bytes<kBpRowsMaxBin>(ent_cap);
     } else if (vm == VM_BIN) {
         if (AM != AM_FIX) return fail(VS_EUNSUPPORTED, "binary postings serve the filter walk only");
         // one lane per list; the option picks the records in flight per lane = the size of the chunks dealt to the waves (8: 512
         // entries, 13 chunks a block on the Wiki21M shape, 16.4 k q/s; 4: 25 chunks for 16 waves, 13.0 k)
-        kern = idx->bp_lanes == 4 ? bp_walk_topk<VM_BIN, kBpBinQT, AM_FIX, 1, kBpRowsMaxBin, 4> : bp_walk_topk<VM_BIN, kBpBinQT, AM_FIX, 1, kBpRowsMaxBin, 8>;
+        kern = idx->bp_lanes == 4 ? bp_walk_topk<VM_BIN, kBpBinQT, AM_FIX, 1, kBpRowsMaxBin, 4, 0, FL> : bp_walk_topk<VM_BIN, kBpBinQT, AM_FIX, 1, kBpRowsMaxBin, 8, 0, FL>;
         lds = bp_lds_bytes<kBpBinQT, AM_FIX, kBpRowsMaxBin>(ent_cap);
     } else if (AM == AM_FIX && a.n_head > 0 && a.head_out) {
         // head columns served by the head pre-pass (bp_head.h): the list walk adds its sums in the epilogue; no strip weights in LDS
         if constexpr (AM == AM_FIX) {
-            if (vm == VM_F32) kern = idx->bp_lanes != 4 ? bp_walk_topk<VM_F32, QT, AM_FIX, 8, kBpRowsMax, kBpNB, 2> : bp_walk_topk<VM_F32, QT, AM_FIX, 4, kBpRowsMax, kBpNB, 2>;
-            else kern = idx->bp_lanes != 4 ? bp_walk_topk<VM_F16, QT, AM_FIX, 8, kBpRowsMax, kBpNBWide, 2> : bp_walk_topk<VM_F16, QT, AM_FIX, 4, kBpRowsMax, kBpNB, 2>;
+            if (vm == VM_F32) kern = idx->bp_lanes != 4 ? bp_walk_topk<VM_F32, QT, AM_FIX, 8, kBpRowsMax, kBpNB, 2, FL> : bp_walk_topk<VM_F32, QT, AM_FIX, 4, kBpRowsMax, kBpNB, 2, FL>;
+            else kern = idx->bp_lanes != 4 ? bp_walk_topk<VM_F16, QT, AM_FIX, 8, kBpRowsMax, kBpNBWide, 2, FL> : bp_walk_topk<VM_F16, QT, AM_FIX, 4, kBpRowsMax, kBpNB, 2, FL>;
         }
         lds = bp_lds_bytes<QT, AM, kBpRowsMax>(ent_cap, 0);
     } else if (AM == AM_FIX && a.n_head > 0) {
         if constexpr (AM == AM_FIX) {
-            if (vm == VM_F32) kern = idx->bp_lanes != 4 ? bp_walk_topk<VM_F32, QT, AM_FIX, 8, kBpRowsMax, kBpNB, 1> : bp_walk_topk<VM_F32, QT, AM_FIX, 4, kBpRowsMax, kBpNB, 1>;
-            else kern = idx->bp_lanes != 4 ? bp_walk_topk<VM_F16, QT, AM_FIX, 8, kBpRowsMax, kBpNB, 1> : bp_walk_topk<VM_F16, QT, AM_FIX, 4, kBpRowsMax, kBpNB, 1>;
+            if (vm == VM_F32) kern = idx->bp_lanes != 4 ? bp_walk_topk<VM_F32, QT, AM_FIX, 8, kBpRowsMax, kBpNB, 1, FL> : bp_walk_topk<VM_F32, QT, AM_FIX, 4, kBpRowsMax, kBpNB, 1, FL>;
+            else kern = idx->bp_lanes != 4 ? bp_walk_topk<VM_F16, QT, AM_FIX, 8, kBpRowsMax, kBpNB, 1, FL> : bp_walk_topk<VM_F16, QT, AM_FIX, 4, kBpRowsMax, kBpNB, 1, FL>;
         }
     } else if (vm == VM_F32) {
-        kern = idx->bp_lanes != 4 ? bp_walk_topk<VM_F32, QT, AM, 8, kBpRowsMax> : bp_walk_topk<VM_F32, QT, AM, 4, kBpRowsMax>;
+        kern = idx->bp_lanes != 4 ? bp_walk_topk<VM_F32, QT, AM, 8, kBpRowsMax, kBpNB, 0, FL> : bp_walk_topk<VM_F32, QT, AM, 4, kBpRowsMax, kBpNB, 0, FL>;
     } else {
-        kern = idx->bp_lanes != 4 ? bp_walk_topk<VM_F16, QT, AM, 8, kBpRowsMax, (AM == AM_FIX ? kBpNBWide : kBpNB)> : bp_walk_topk<VM_F16, QT, AM, 4, kBpRowsMax>;
+        kern = idx->bp_lanes != 4 ? bp_walk_topk<VM_F16, QT, AM, 8, kBpRowsMax, (AM == AM_FIX ? kBpNBWide : kBpNB), 0, FL> : bp_walk_topk<VM_F16, QT, AM, 4, kBpRowsMax, kBpNB, 0, FL>;
     }
     if (lds > 160 * 1024) return fail(VS_EUNSUPPORTED, "postings walk needs %zu B of LDS", lds);
     VS_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kScanThreads), lds, s, a);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(kScanThreads), lds, s, with_filter<FL>(a, idx->filt));
     VS_HIP(hipGetLastError());
     return VS_OK;
+}
+
+// the walk's kernel for the search's filter (vs_index::filt): the FL = 1 instantiations gate candidate admission
+template <int QT, int AM>
+int launch_bp_walk(const vs_index* idx, const BpArgs& a, int grid, int ent_cap, hipStream_t s) {
+    return idx->filt.words ? launch_bp_walk_fl<QT, AM, 1>(idx, a, grid, ent_cap, s) : launch_bp_walk_fl<QT, AM, 0>(idx, a, grid, ent_cap, s);
 }
 
 int bp_build(vs_index* idx, hipStream_t s) {
@@ -637,6 +652,7 @@ int bp_filter_search(vs_index* idx, const float* dq, int32_t B, int32_t k, int64
     a.gcand = idx->ws_mq_cand.as<uint64_t>();
     a.qscale = qscale;
     a.gtau = gtau;
+    const bool fl = idx->filt.words != nullptr;
     a.df = idx->bp_df.p ? idx->bp_df.as<unsigned long long>() + V : nullptr;          // (second half of bp_df: non-zeros per column)
     a.hmap = idx->bp_n_head > 0 ? idx->bp_hmap.as<uint16_t>() : nullptr;
     a.strip = idx->bp_strip.as<__half>();
@@ -724,14 +740,23 @@ int bp_filter_search(vs_index* idx, const float* dq, int32_t B, int32_t k, int64
             BpArgs a16 = a, a2 = a;
             a16.tiles = tiles16; a16.n_tiles_dev = n_split;
             a2.tiles = tiles2; a2.n_tiles_dev = n_split + 1;
-            void (*k16)(BpArgs) = a.timing ? bp_bq_topk<4, 1, 1> : bp_bq_topk<4, 0, 1>;
-            void (*k2)(BpArgs) = a.timing ? bp_bq_topk<2, 1> : bp_bq_topk<2, 0>;
             const size_t lds = bq_lds_bytes(2);
             if (vals_cap > kBqEntCap) return fail(VS_EUNSUPPORTED, "bag-of-token chunks: tile entries beyond the table");
+            if (fl) {
+                void (*k16)(WithFilter<BpArgs>) = a.timing ? bp_bq_topk<4, 1, 1, 1> : bp_bq_topk<4, 0, 1, 1>;
+                void (*k2)(WithFilter<BpArgs>) = a.timing ? bp_bq_topk<2, 1, 0, 1> : bp_bq_topk<2, 0, 0, 1>;
+                VS_HIP(hipFuncSetAttribute((const void*)k16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+                VS_HIP(hipFuncSetAttribute((const void*)k2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+                hipLaunchKernelGGL(k16, dim3(grid), dim3(kScanThreads), lds, s, with_filter<1>(a16, idx->filt));
+                hipLaunchKernelGGL(k2, dim3(grid), dim3(kScanThreads), lds, s, with_filter<1>(a2, idx->filt));
+            } else {
+            void (*k16)(BpArgs) = a.timing ? bp_bq_topk<4, 1, 1> : bp_bq_topk<4, 0, 1>;
+            void (*k2)(BpArgs) = a.timing ? bp_bq_topk<2, 1> : bp_bq_topk<2, 0>;
             VS_HIP(hipFuncSetAttribute((const void*)k16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             VS_HIP(hipFuncSetAttribute((const void*)k2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             hipLaunchKernelGGL(k16, dim3(grid), dim3(kScanThreads), lds, s, a16);
             hipLaunchKernelGGL(k2, dim3(grid), dim3(kScanThreads), lds, s, a2);
+            }
             VS_HIP(hipGetLastError());
         } else
         VS_TRY((launch_bp_walk<kQT, AM_FIX>(idx, a, grid, vals_cap, s)));
@@ -829,6 +854,9 @@ int bp_filter_search(vs_index* idx, const float* dq, int32_t B, int32_t k, int64
         void (*rk)(RefineArgs) = idx->store_dtype == VS_F32 ? (img ? refine_topk_kernel<VM_F32, 1> : refine_topk_kernel<VM_F32, 0>)
                                : idx->store_dtype == VS_F16 ? (img ? refine_topk_kernel<VM_F16, 1> : refine_topk_kernel<VM_F16, 0>)
                                                             : (img ? refine_topk_kernel<VM_BIN, 1> : refine_topk_kernel<VM_BIN, 0>);
+        if (fl) rk = idx->store_dtype == VS_F32 ? (img ? refine_topk_kernel<VM_F32, 1, 1> : refine_topk_kernel<VM_F32, 0, 1>)
+                   : idx->store_dtype == VS_F16 ? (img ? refine_topk_kernel<VM_F16, 1, 1> : refine_topk_kernel<VM_F16, 0, 1>)
+                                                : (img ? refine_topk_kernel<VM_BIN, 1, 1> : refine_topk_kernel<VM_BIN, 0, 1>);
         VS_HIP(hipFuncSetAttribute((const void*)rk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rlds));
         hipLaunchKernelGGL(rk, dim3(rgrid), dim3(kScanThreads), rlds, s, r);
         VS_HIP(hipGetLastError());
@@ -851,10 +879,17 @@ int bp_filter_search(vs_index* idx, const float* dq, int32_t B, int32_t k, int64
         sa.rows_per_chunk = ceil_div64(idx->n_rows, nchunk_fb);
         sa.cand = a.cand;
         const size_t slds = scan_lds_bytes(V);
+        if (fl) {
+            void (*ek)(WithFilter<ScanArgs>, const int2*, const int32_t*) = idx->store_dtype == VS_NONE  ? exact_scan_topk_kernel<VM_BIN, 1>
+                                                                      : idx->store_dtype == VS_F16 ? exact_scan_topk_kernel<VM_F16, 1> : exact_scan_topk_kernel<VM_F32, 1>;
+            VS_HIP(hipFuncSetAttribute((const void*)ek, hipFuncAttributeMaxDynamicSharedMemorySize, (int)slds));
+            hipLaunchKernelGGL(ek, dim3(idx->cu_count), dim3(kScanThreads), slds, s, with_filter<1>(sa, idx->filt), (const int2*)fb_tiles, (const int32_t*)fb_n);
+        } else {
         void (*ek)(ScanArgs, const int2*, const int32_t*) = idx->store_dtype == VS_NONE  ? exact_scan_topk_kernel<VM_BIN>
                                                             : idx->store_dtype == VS_F16 ? exact_scan_topk_kernel<VM_F16> : exact_scan_topk_kernel<VM_F32>;
         VS_HIP(hipFuncSetAttribute((const void*)ek, hipFuncAttributeMaxDynamicSharedMemorySize, (int)slds));
         hipLaunchKernelGGL(ek, dim3(idx->cu_count), dim3(kScanThreads), slds, s, sa, (const int2*)fb_tiles, (const int32_t*)fb_n);
+        }
         MergeArgs m{};
         m.cand = a.cand;
         m.n_cand = (int64_t)nchunk_fb * k;
@@ -868,7 +903,7 @@ int bp_filter_search(vs_index* idx, const float* dq, int32_t B, int32_t k, int64
         m.run_len = k;
         m.sel = fb_tiles;
         m.sel_n = fb_n;
-        hipLaunchKernelGGL(merge_topk_kernel<0>, dim3(std::min(B, idx->cu_count)), dim3(kScanThreads), 0, s, m);
+        hipLaunchKernelGGL((fl ? merge_topk_kernel<1> : merge_topk_kernel<0>), dim3(std::min(B, idx->cu_count)), dim3(kScanThreads), 0, s, m);
         VS_HIP(hipGetLastError());
     }
     VS_STAGE("fallback", s);

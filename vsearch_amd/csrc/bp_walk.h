@@ -549,8 +549,9 @@ __device__ __forceinline__ uint32_t quad_bcast(uint32_t x) {          // lane U 
 // RMAX = block capacity in documents
 // HD = 1: the index has head columns (dense strips) multiplied in this kernel, one tile at a time; HD = 2: their part of the sums was
 // computed by the head pre-pass (bp_head.h) and is added in the epilogue; 0 compiles both out.
-template <int VM, int QT, int AM, int LG, int RMAX, int NB = kBpNB, int HD = 0>
-__global__ __launch_bounds__(kScanThreads) void bp_walk_topk(BpArgs a) {
+// FL = 1: a filtered search (KArg, common.h) -- only allowed rows become candidates; the sums are computed for every row as before.
+template <int VM, int QT, int AM, int LG, int RMAX, int NB = kBpNB, int HD = 0, int FL = 0>
+__global__ __launch_bounds__(kScanThreads) void bp_walk_topk(KArg<BpArgs, FL> a) {
     static_assert(!HD || (AM == AM_FIX && VM != VM_BIN && QT == 8), "dense strips: valued filter walk only");
     static_assert(bp_acc_bytes<QT, AM, RMAX>() >= kBpSortBytes, "the accumulator area holds the 8192-slot entry sort");
     static_assert(VM != VM_BIN || RMAX == kBpRowsMaxBin, "pad postings of a binary list carry document id kBpRowsMaxBin");
@@ -1024,7 +1025,9 @@ __global__ __launch_bounds__(kScanThreads) void bp_walk_topk(BpArgs a) {
                         else hi = (uint32_t)sums[q] ^ 0x80000000u;
                         if (q < nq && hi >= thi[q]) {
                             const uint64_t key = ((uint64_t)hi << 32) | (uint32_t)(~(uint32_t)row);
-                            if (key > tau[q] && key < upper_sh[q]) {
+                            bool pass = key > tau[q] && key < upper_sh[q];
+                            if constexpr (FL != 0) pass = pass && filter_ok(a, q0 + q, row);       // (the gate: which threads push, not how the counters are read)
+                            if (pass) {
                                 const uint32_t old = atomicAdd(&ccnt[q], inc);                 // (low half: first rounds, high half: last rounds -- below)
                                 my_gcand[(size_t)q * kBpCap + (old & 0xFFFFu) + (old >> 16)] = key;
                             }

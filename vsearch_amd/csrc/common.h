@@ -12,6 +12,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "vsearch_hip.h"
@@ -124,6 +125,43 @@ inline int to_device(const void* src, size_t bytes, DevBuf& stage, hipStream_t s
     VS_HIP(hipMemcpyAsync(stage.p, src, bytes, hipMemcpyHostToDevice, stream));
     *out = stage.p;
     return VS_OK;
+}
+
+// ---- document filter (vs_index_search_filtered) ------------------------------------------------
+// Row r of an index is allowed for query b iff bit bit0 + r of the bitmap at words + b * ld is set (bit i: bit i & 31 of word i >> 5;
+// ld = 0: one bitmap for the batch).  words == nullptr: no filter.
+struct FilterArgs {
+    const uint32_t* words;
+    int64_t bit0;
+    int64_t ld;
+};
+__device__ __forceinline__ bool filter_allows(const FilterArgs& f, int64_t b, int64_t row) {
+    const uint64_t bit = (uint64_t)(f.bit0 + row);
+    return ((f.words[(size_t)b * (size_t)f.ld + (size_t)(bit >> 5)] >> (bit & 31u)) & 1u) != 0u;
+}
+// A kernel's argument struct with the filter behind it.  A gated kernel takes KArg<Args, FL>: its FL = 0 instantiation takes the plain
+// struct -- the kernel it was, argument layout included -- and only the FL = 1 one the extended struct; filter_ok(a, b, row) is `true`
+// for the plain struct and the bitmap test for the extended one.
+template <class A>
+struct WithFilter : A {
+    FilterArgs filt;
+};
+template <class A, int FL>
+using KArg = typename std::conditional<FL != 0, WithFilter<A>, A>::type;
+template <int FL, class A>
+inline KArg<A, FL> with_filter(const A& a, const FilterArgs& f) {
+    if constexpr (FL != 0) return WithFilter<A>{a, f};
+    else return a;
+}
+template <class A>
+__device__ __forceinline__ bool filter_ok(const A&, int64_t, int64_t) { return true; }
+template <class A>
+__device__ __forceinline__ bool filter_ok(const WithFilter<A>& a, int64_t b, int64_t row) { return filter_allows(a.filt, b, row); }
+// the filter of queries [b0, ...) of the batch (the sub-batches of a search)
+inline FilterArgs filter_from(const FilterArgs& f, int64_t b0) {
+    FilterArgs r = f;
+    if (r.words) r.words += (size_t)b0 * (size_t)r.ld;
+    return r;
 }
 
 // ---- profiler: hipEvent pairs around named kernel launches --------------------------------------
@@ -270,6 +308,8 @@ struct vs_index {
     vs::DevBuf mat;      // [n_rows, n_cols] store_dtype
     // scratch owned by the handle (grow-only)
     vs::DevBuf ws_q, ws_cand, ws_out_ids, ws_out_scores, ws_misc, ws_mq_meta, ws_mq_q, ws_mq_cand, ws_fb, ws_pace;
+    vs::DevBuf ws_filt;           // a host filter's bitmap staged on the device
+    vs::FilterArgs filt{};        // the document filter of the search in progress (vs_index_search_filtered; words == nullptr: none)
     bool logical_dense = false;   // dense Index stored as CSR packets (sparsity-aware dense index)
     int qt_pref = 0;     // 0 = auto (multi-query pass when the batch qualifies), 1 = force the dense-image pass
     int last_qt = 0;     // queries per pass of the most recent search

@@ -658,7 +658,7 @@ ScanPlan plan_scan(const vs_index* idx, int B) {
 }
 
 template <int G, int VM>
-int launch_scan_g(int mode, const ScanArgs& a, int grid, size_t lds, hipStream_t s) {
+int launch_scan_g(int mode, const ScanArgs& a, const FilterArgs& f, int grid, size_t lds, hipStream_t s) {
     // mode 0: scores, 1: wave top-k, 2: shared top-k
     auto set_lds = [&](const void* f) -> int {
         VS_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -667,6 +667,11 @@ int launch_scan_g(int mode, const ScanArgs& a, int grid, size_t lds, hipStream_t
     if (mode == 0) {
         VS_TRY(set_lds((const void*)csr_scan_scores<G, VM>));
         hipLaunchKernelGGL((csr_scan_scores<G, VM>), dim3(grid), dim3(kScanThreads), lds, s, a);
+    } else if (f.words) {
+        // a filtered search: the FL = 1 instantiations (KArg, common.h)
+        void (*kern)(WithFilter<ScanArgs>) = mode == 1 ? csr_scan_topk_wave<G, VM, 1> : csr_scan_topk_shared<G, VM, 1>;
+        VS_TRY(set_lds((const void*)kern));
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(kScanThreads), lds, s, with_filter<1>(a, f));
     } else if (mode == 1) {
         VS_TRY(set_lds((const void*)csr_scan_topk_wave<G, VM>));
         hipLaunchKernelGGL((csr_scan_topk_wave<G, VM>), dim3(grid), dim3(kScanThreads), lds, s, a);
@@ -679,13 +684,13 @@ int launch_scan_g(int mode, const ScanArgs& a, int grid, size_t lds, hipStream_t
 }
 
 template <int VM>
-int launch_scan_vm(int g, int mode, const ScanArgs& a, int grid, size_t lds, hipStream_t s) {
+int launch_scan_vm(int g, int mode, const ScanArgs& a, const FilterArgs& f, int grid, size_t lds, hipStream_t s) {
     switch (g) {
-        case 4: return launch_scan_g<4, VM>(mode, a, grid, lds, s);
-        case 8: return launch_scan_g<8, VM>(mode, a, grid, lds, s);
-        case 16: return launch_scan_g<16, VM>(mode, a, grid, lds, s);
-        case 32: return launch_scan_g<32, VM>(mode, a, grid, lds, s);
-        default: return launch_scan_g<64, VM>(mode, a, grid, lds, s);
+        case 4: return launch_scan_g<4, VM>(mode, a, f, grid, lds, s);
+        case 8: return launch_scan_g<8, VM>(mode, a, f, grid, lds, s);
+        case 16: return launch_scan_g<16, VM>(mode, a, f, grid, lds, s);
+        case 32: return launch_scan_g<32, VM>(mode, a, f, grid, lds, s);
+        default: return launch_scan_g<64, VM>(mode, a, f, grid, lds, s);
     }
 }
 
@@ -693,9 +698,10 @@ int launch_scan(const vs_index* idx, int mode, const ScanArgs& a, int grid, hipS
     const size_t lds = scan_lds_bytes(idx->n_cols);
     if (lds > 160 * 1024) return fail(VS_EUNSUPPORTED, "n_cols = %d needs %zu B of LDS (> 160 KiB)", idx->n_cols, lds);
     ProfScope prof(mode == 0 ? "csr_scan_scores" : "csr_scan_topk", s);
-    if (idx->store_dtype == VS_F32) return launch_scan_vm<VM_F32>(idx->lanes_per_row, mode, a, grid, lds, s);
-    if (idx->store_dtype == VS_F16) return launch_scan_vm<VM_F16>(idx->lanes_per_row, mode, a, grid, lds, s);
-    return launch_scan_vm<VM_BIN>(idx->lanes_per_row, mode, a, grid, lds, s);
+    const FilterArgs f = mode == 0 ? FilterArgs{} : idx->filt;          // (the search's filter, of the sub-batch in flight)
+    if (idx->store_dtype == VS_F32) return launch_scan_vm<VM_F32>(idx->lanes_per_row, mode, a, f, grid, lds, s);
+    if (idx->store_dtype == VS_F16) return launch_scan_vm<VM_F16>(idx->lanes_per_row, mode, a, f, grid, lds, s);
+    return launch_scan_vm<VM_BIN>(idx->lanes_per_row, mode, a, f, grid, lds, s);
 }
 
 int prep_queries(vs_index* idx, const void* q, int q_dtype, int64_t ldq, int B, hipStream_t s, const float** out) {
@@ -754,6 +760,7 @@ int vs_csr_search(vs_index* idx, const void* q, int q_dtype, int64_t ldq, int32_
     idx->last_flags_n = 0;
     idx->last_plan_dev = nullptr;
     idx->last_path = 0;
+    const FilterArgs filt = idx->filt;                         // the search's filter (vs_index_search_filtered); sub-batches offset it
     if (idx->qt_pref != 1) {
         if (!idx->bp_ready && !idx->bp_tried && bp_wanted(idx)) VS_TRY(bp_build(idx, s));
         if (!idx->bp_ready && !idx->bp_tried) idx->bp_state = 4;
@@ -776,11 +783,13 @@ int vs_csr_search(vs_index* idx, const void* q, int q_dtype, int64_t ldq, int32_
             const int kk = std::min(k - col0, max_k);
             for (int b0 = 0; b0 < B && all; b0 += bs_mq) {
                 const int bs = std::min(bs_mq, B - b0);
+                idx->filt = filter_from(filt, b0);
                 VS_TRY(mq_search(idx, dq + (size_t)b0 * idx->n_cols, bs, kk, id_offset, d_ids + (size_t)b0 * k, d_scores + (size_t)b0 * k, plan, s,
                                  &done, k, col0, mq_passes > 1 ? mq_upper.as<uint64_t>() + b0 : nullptr));
                 all = all && done;
             }
         }
+        idx->filt = filt;
         if (mq_passes > 1) VS_HIP(hipStreamSynchronize(s));      // `mq_upper` is freed on return
         if (all) {
             idx->last_qt = kQT;
@@ -826,9 +835,11 @@ int vs_csr_search(vs_index* idx, const void* q, int q_dtype, int64_t ldq, int32_
             a.rows_per_chunk = rows_per_chunk1;
             a.cand = idx->ws_cand.as<uint64_t>();
             a.upper = passes > 1 ? upper.as<uint64_t>() + b0 : nullptr;
+            idx->filt = filter_from(filt, b0);
             const int grid = (int)std::min<int64_t>((int64_t)bs * nchunk1, idx->cu_count);
             idx->last_scan_bytes += (int64_t)bs * csr_bytes_per_pass(idx);
             VS_TRY(launch_scan(idx, kk <= kMaxKWave ? 1 : 2, a, grid, s));
+            idx->filt = filt;
             MergeArgs m{};
             m.cand = a.cand;
             m.n_cand = (int64_t)nchunk1 * kk;
@@ -843,7 +854,7 @@ int vs_csr_search(vs_index* idx, const void* q, int q_dtype, int64_t ldq, int32_
             m.upper_out = passes > 1 ? upper.as<uint64_t>() + b0 : nullptr;
             {
                 ProfScope prof("merge_topk", s);
-                hipLaunchKernelGGL(merge_topk_kernel<0>, dim3(std::min(bs, idx->cu_count * 2)), dim3(kScanThreads), 0, s, m);
+                hipLaunchKernelGGL((filt.words ? merge_topk_kernel<1> : merge_topk_kernel<0>), dim3(std::min(bs, idx->cu_count * 2)), dim3(kScanThreads), 0, s, m);
             }
             VS_HIP(hipGetLastError());
         }
@@ -927,7 +938,8 @@ extern "C" int vs_merge_topk(const int64_t* cand_ids, const float* cand_scores, 
     m.out_scores = ds;
     m.out_ld = k;
     m.col0 = 0;
-    hipLaunchKernelGGL(merge_topk_kernel<0>, dim3(std::min(B, 512)), dim3(kScanThreads), 0, s, m);
+    // (PAD = 1: fewer than k candidates -- id -1 pads of filtered shards map to key 0 above -- come out as id -1, score -inf)
+    hipLaunchKernelGGL(merge_topk_kernel<1>, dim3(std::min(B, 512)), dim3(kScanThreads), 0, s, m);
     VS_HIP(hipGetLastError());
     if (!out_dev) {
         VS_HIP(hipMemcpyAsync(out_ids, di, (size_t)B * k * 8, hipMemcpyDeviceToHost, s));

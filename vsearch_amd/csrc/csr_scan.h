@@ -14,6 +14,7 @@
 #include <hip/hip_fp16.h>
 #include <stdint.h>
 
+#include "common.h"
 #include "topk_keys.h"
 #include "dense_csr.h"
 
@@ -156,8 +157,8 @@ __global__ __launch_bounds__(kScanThreads) void csr_scan_scores(ScanArgs a) {
 // Each wave keeps its own <=256 candidate keys in LDS and prunes them to the best k with an
 // in-register bitonic network; a wave's k-th best key is a lower bound of the global k-th best, so
 // waves share the tightest bound through one LDS word and drop every row that cannot qualify.
-template <int G, int VM>
-__global__ __launch_bounds__(kScanThreads) void csr_scan_topk_wave(ScanArgs a) {
+template <int G, int VM, int FL = 0>          // FL = 1: a filtered search (KArg, common.h)
+__global__ __launch_bounds__(kScanThreads) void csr_scan_topk_wave(KArg<ScanArgs, FL> a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* img = reinterpret_cast<float*>(smem);
     uint64_t* cand = reinterpret_cast<uint64_t*>(smem + scan_img_bytes(a.n_cols));
@@ -189,6 +190,7 @@ __global__ __launch_bounds__(kScanThreads) void csr_scan_topk_wave(ScanArgs a) {
             const uint64_t ts = __hip_atomic_load(tau_sh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             tau = ts > tau ? ts : tau;
             bool pass = (lg == 0) && (row < r1) && (key > tau) && (key < upper);
+            if constexpr (FL != 0) pass = pass && filter_ok(a, qi, row);
             uint64_t m = __ballot(pass);
             if (m) {
                 int n = __popcll(m);
@@ -227,8 +229,8 @@ __global__ __launch_bounds__(kScanThreads) void csr_scan_topk_wave(ScanArgs a) {
 }
 
 // ---- fused scoring + top-k, 128 < k <= 2048: one shared 4096-slot buffer, barrier per superbatch --
-template <int G, int VM>
-__global__ __launch_bounds__(kScanThreads) void csr_scan_topk_shared(ScanArgs a) {
+template <int G, int VM, int FL = 0>
+__global__ __launch_bounds__(kScanThreads) void csr_scan_topk_shared(KArg<ScanArgs, FL> a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* img = reinterpret_cast<float*>(smem);
     uint64_t* cand = reinterpret_cast<uint64_t*>(smem + scan_img_bytes(a.n_cols));
@@ -260,7 +262,8 @@ __global__ __launch_bounds__(kScanThreads) void csr_scan_topk_shared(ScanArgs a)
                 if (row < r1) acc = row_partial<G, VM>(a, img, a.pk_ptr[row], a.pk_ptr[row + 1], lg);
                 acc = group_sum<G>(acc);
                 const uint64_t key = make_key(acc, (uint32_t)row);
-                const bool pass = (lg == 0) && (row < r1) && (key > tau) && (key < upper);
+                bool pass = (lg == 0) && (row < r1) && (key > tau) && (key < upper);
+                if constexpr (FL != 0) pass = pass && filter_ok(a, qi, row);
                 const uint64_t m = __ballot(pass);
                 if (m) {
                     int base = 0;
@@ -328,8 +331,8 @@ __device__ __forceinline__ double row_sum_f64(const uint32_t* pk_ptr, const uint
 
 // ---- exact pass for queries picked on the device (sel[i].x, i < sel_n[0]): the filter-and-refine search's unproven queries when
 // the postings copy is lossy.  One query per pass like csr_scan_topk_shared, one wave per row, fp64 row sums.
-template <int VM>
-__global__ __launch_bounds__(kScanThreads) void exact_scan_topk_kernel(ScanArgs a, const int2* sel, const int32_t* sel_n) {
+template <int VM, int FL = 0>
+__global__ __launch_bounds__(kScanThreads) void exact_scan_topk_kernel(KArg<ScanArgs, FL> a, const int2* sel, const int32_t* sel_n) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* img = reinterpret_cast<float*>(smem);
     uint64_t* cand = reinterpret_cast<uint64_t*>(smem + scan_img_bytes(a.n_cols));
@@ -352,7 +355,9 @@ __global__ __launch_bounds__(kScanThreads) void exact_scan_topk_kernel(ScanArgs 
             const int64_t it1 = min(iters, it0 + SB);
             for (int64_t it = it0; it < it1; ++it) {
                 const int64_t row = r0 + it * kScanWaves + w;
-                if (row < r1) {
+                bool live = row < r1;
+                if constexpr (FL != 0) live = live && filter_ok(a, qi, row);      // (one wave a row: a disallowed row is not summed)
+                if (live) {
                     const double sum = row_sum_f64<VM>(a.pk_ptr, a.cols, a.vals, (uint32_t)row, lane, [&](uint32_t col) { return img[col]; });
                     const uint64_t key = make_key((float)sum, (uint32_t)row);
                     if (lane == 0 && key > tau) cand[atomicAdd(cnt_sh, 1)] = key;
@@ -457,7 +462,8 @@ __device__ __forceinline__ void merge_select(const uint64_t* src, int64_t n_cand
     } while (consumed < n_cand);
 }
 
-template <int UNUSED>
+// PAD = 1: an empty slot (key 0: fewer candidates than k -- a filtered search) comes out as id -1, score -inf
+template <int PAD>
 __global__ __launch_bounds__(kScanThreads) void merge_topk_kernel(MergeArgs a) {
     __shared__ uint64_t buf[kWgCap];
     __shared__ int cnt_sh;
@@ -469,6 +475,14 @@ __global__ __launch_bounds__(kScanThreads) void merge_topk_kernel(MergeArgs a) {
         merge_select(a.cand + (size_t)b * a.n_cand, a.n_cand, a.run_len, K, a.upper_in ? a.upper_in + b : nullptr, buf, &cnt_sh, tid);
         for (int i = tid; i < K; i += kScanThreads) {
             const uint64_t key = buf[i];
+            if constexpr (PAD != 0) {
+                if (key == 0ull) {
+                    a.out_ids[(size_t)b * a.out_ld + a.col0 + i] = -1;
+                    a.out_scores[(size_t)b * a.out_ld + a.col0 + i] = -INFINITY;
+                    if (a.upper_out && i == K - 1) a.upper_out[b] = key;
+                    continue;
+                }
+            }
             a.out_ids[(size_t)b * a.out_ld + a.col0 + i] = (int64_t)key_row(key) + a.id_offset;
             a.out_scores[(size_t)b * a.out_ld + a.col0 + i] = key_score(key);
             if (a.upper_out && i == K - 1) a.upper_out[b] = key;
@@ -482,7 +496,7 @@ __global__ __launch_bounds__(kScanThreads) void merge_topk_kernel(MergeArgs a) {
 // 12 more bits of the k-th largest key; as soon as the keys at or above the current bin fit the 4096-slot
 // LDS buffer they are collected and sorted.  Keys are distinct (the low word is the row id), so the
 // refinement always terminates.  Same MergeArgs / output convention as merge_topk_kernel.
-template <int UNUSED>
+template <int PAD>
 __global__ __launch_bounds__(kScanThreads) void select_topk_kernel(MergeArgs a) {
     __shared__ uint64_t buf[kWgCap];
     __shared__ int hist[4096];
@@ -537,6 +551,7 @@ __global__ __launch_bounds__(kScanThreads) void select_topk_kernel(MergeArgs a) 
         for (int64_t i = tid; i < a.n_cand; i += kScanThreads) {
             uint64_t key = src[i];
             if (key >= upper) key = 0ull;
+            if constexpr (PAD != 0) { if (key == 0ull) continue; }      // (fewer non-empty keys than k: the k-th is 0, and only the others fit)
             if ((pbits >= 64 ? key : (key >> (64 - pbits))) >= prefix) {
                 const int pos = atomicAdd(&s_cnt, 1);
                 if (pos < kWgCap) buf[pos] = key;
@@ -545,6 +560,14 @@ __global__ __launch_bounds__(kScanThreads) void select_topk_kernel(MergeArgs a) 
         wg_sort_desc<kScanThreads>(buf, kWgCap, tid);
         for (int i = tid; i < K; i += kScanThreads) {
             const uint64_t key = buf[i];
+            if constexpr (PAD != 0) {
+                if (key == 0ull) {
+                    a.out_ids[(size_t)b * a.out_ld + a.col0 + i] = -1;
+                    a.out_scores[(size_t)b * a.out_ld + a.col0 + i] = -INFINITY;
+                    if (a.upper_out && i == K - 1) a.upper_out[b] = key;
+                    continue;
+                }
+            }
             a.out_ids[(size_t)b * a.out_ld + a.col0 + i] = (int64_t)key_row(key) + a.id_offset;
             a.out_scores[(size_t)b * a.out_ld + a.col0 + i] = key_score(key);
             if (a.upper_out && i == K - 1) a.upper_out[b] = key;

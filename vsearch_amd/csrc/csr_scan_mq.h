@@ -112,8 +112,8 @@ __host__ __device__ inline size_t mq_fixed_lds_bytes(int32_t n_cols, int rows_in
 // queries (T as low as the LDS slack allows, >= 3) are stored as zero-padded 8-float rows; a hit on such a
 // column costs two ds_read_b128 + 8 multiply-adds into per-lane fp64 registers (flushed once per row)
 // instead of up to 8 trips through the one-hit-at-a-time remainder loop.
-template <int G, int VM, int QT, int U, int DN>
-__global__ __launch_bounds__(kScanThreads) void csr_scan_topk_mq(MqArgs a) {
+template <int G, int VM, int QT, int U, int DN, int FL = 0>          // FL = 1: a filtered search (KArg, common.h)
+__global__ __launch_bounds__(kScanThreads) void csr_scan_topk_mq(KArg<MqArgs, FL> a) {
     static_assert(QT == 8 && G >= 8, "the packed hit word assumes 8 query slots per tile; lanes 0..7 of a row group finish them");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int RPW = 64 / G;
@@ -384,7 +384,9 @@ __global__ __launch_bounds__(kScanThreads) void csr_scan_topk_mq(MqArgs a) {
                         *pa = 0.0;
                     }
                     const uint64_t key = make_key((float)sum, (uint32_t)row);
-                    if (key > tau[lg] && key < my_upper) {
+                    bool pass = key > tau[lg] && key < my_upper;
+                    if constexpr (FL != 0) pass = pass && filter_ok(a, q0 + lg, row);
+                    if (pass) {
                         const uint32_t pos = atomicAdd(&ccnt[lg], 1u);
                         my_gcand[(size_t)lg * kMqCap + pos] = key;
                     }

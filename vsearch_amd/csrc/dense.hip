@@ -589,6 +589,17 @@ extern "C" int vs_head_project_pool(const float* hidden, const float* W, int32_t
     return VS_OK;
 }
 
+// A filtered search's key-forming step (vs_index_search_filtered): the key of a row the query's filter does not allow becomes 0 -- an
+// empty slot, which no select takes while a real key is left (and which comes out as id -1 / score -inf when too few are).  A separate
+// pass over the [B, N] keys, so that dense_scores_kernel stays the unfiltered kernel it was.
+__global__ __launch_bounds__(256) void filter_keys_kernel(uint64_t* keys, int32_t B, int64_t N, FilterArgs f) {
+    const int64_t total = (int64_t)B * N;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t b = i / N, n = i % N;
+        if (!filter_allows(f, b, n)) keys[i] = 0ull;
+    }
+}
+
 int vs_dense_search(vs_index* idx, const void* q, int q_dtype, int64_t ldq, int32_t B, int32_t k, int64_t id_offset,
                     int64_t* out_ids, float* out_scores, hipStream_t s) {
     const int ldp = dense_ldp(idx->n_cols);
@@ -616,6 +627,12 @@ int vs_dense_search(vs_index* idx, const void* q, int q_dtype, int64_t ldq, int3
             ProfScope prof("dense_scores", s);
             VS_TRY(launch_dense_scores(idx, dq + (size_t)b0 * ldp, bs, ldp, idx->ws_cand.as<uint64_t>(), nullptr, s));
         }
+        const bool fl = idx->filt.words != nullptr;
+        if (fl) {
+            hipLaunchKernelGGL(filter_keys_kernel, dim3((unsigned)std::min<int64_t>(ceil_div64((int64_t)bs * N, 256), (int64_t)idx->cu_count * 16)), dim3(256), 0, s,
+                               idx->ws_cand.as<uint64_t>(), bs, N, filter_from(idx->filt, b0));
+            VS_HIP(hipGetLastError());
+        }
         for (int pass = 0; pass < passes; ++pass) {
             const int col0 = pass * kMaxKShared;
             MergeArgs m{};
@@ -631,8 +648,8 @@ int vs_dense_search(vs_index* idx, const void* q, int q_dtype, int64_t ldq, int3
             m.upper_out = passes > 1 ? upper.as<uint64_t>() : nullptr;
             m.upper_in = pass > 0 ? upper.as<uint64_t>() : nullptr;
             ProfScope prof("merge_topk", s);
-            if (N > 2 * kWgCap) hipLaunchKernelGGL(select_topk_kernel<0>, dim3(std::min(bs, idx->cu_count * 2)), dim3(kScanThreads), 0, s, m);
-            else hipLaunchKernelGGL(merge_topk_kernel<0>, dim3(std::min(bs, idx->cu_count * 2)), dim3(kScanThreads), 0, s, m);
+            if (N > 2 * kWgCap) hipLaunchKernelGGL((fl ? select_topk_kernel<1> : select_topk_kernel<0>), dim3(std::min(bs, idx->cu_count * 2)), dim3(kScanThreads), 0, s, m);
+            else hipLaunchKernelGGL((fl ? merge_topk_kernel<1> : merge_topk_kernel<0>), dim3(std::min(bs, idx->cu_count * 2)), dim3(kScanThreads), 0, s, m);
         }
         VS_HIP(hipGetLastError());
     }

@@ -7,27 +7,33 @@ namespace vs {
 namespace {
 
 template <int G, int VM, int U, int DN>
-int launch_mq_gu(const MqArgs& a, int grid, size_t lds, hipStream_t s) {
+int launch_mq_gu(const MqArgs& a, const FilterArgs& f, int grid, size_t lds, hipStream_t s) {
+    if (f.words) {                     // a filtered search: the FL = 1 instantiation (KArg, common.h)
+        VS_HIP(hipFuncSetAttribute((const void*)csr_scan_topk_mq<G, VM, kQT, U, DN, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL((csr_scan_topk_mq<G, VM, kQT, U, DN, 1>), dim3(grid), dim3(kScanThreads), lds, s, with_filter<1>(a, f));
+        VS_HIP(hipGetLastError());
+        return VS_OK;
+    }
     VS_HIP(hipFuncSetAttribute((const void*)csr_scan_topk_mq<G, VM, kQT, U, DN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL((csr_scan_topk_mq<G, VM, kQT, U, DN>), dim3(grid), dim3(kScanThreads), lds, s, a);
     VS_HIP(hipGetLastError());
     return VS_OK;
 }
 template <int G, int VM>
-int launch_mq_g(int u, bool shared_cols, const MqArgs& a, int grid, size_t lds, hipStream_t s) {
+int launch_mq_g(int u, bool shared_cols, const MqArgs& a, const FilterArgs& f, int grid, size_t lds, hipStream_t s) {
     if (shared_cols)          // the shared-column variant keeps 16 more registers live: at most 2 packets in flight
-        return u <= 1 ? launch_mq_gu<G, VM, 1, 1>(a, grid, lds, s) : launch_mq_gu<G, VM, 2, 1>(a, grid, lds, s);
-    if (u <= 1) return launch_mq_gu<G, VM, 1, 0>(a, grid, lds, s);
-    if (u == 2) return launch_mq_gu<G, VM, 2, 0>(a, grid, lds, s);
-    return launch_mq_gu<G, VM, 3, 0>(a, grid, lds, s);
+        return u <= 1 ? launch_mq_gu<G, VM, 1, 1>(a, f, grid, lds, s) : launch_mq_gu<G, VM, 2, 1>(a, f, grid, lds, s);
+    if (u <= 1) return launch_mq_gu<G, VM, 1, 0>(a, f, grid, lds, s);
+    if (u == 2) return launch_mq_gu<G, VM, 2, 0>(a, f, grid, lds, s);
+    return launch_mq_gu<G, VM, 3, 0>(a, f, grid, lds, s);
 }
 template <int VM>
-int launch_mq_vm(int g, int u, bool shared_cols, const MqArgs& a, int grid, size_t lds, hipStream_t s) {
+int launch_mq_vm(int g, int u, bool shared_cols, const MqArgs& a, const FilterArgs& f, int grid, size_t lds, hipStream_t s) {
     switch (g) {
-        case 8: return launch_mq_g<8, VM>(u, shared_cols, a, grid, lds, s);
-        case 16: return launch_mq_g<16, VM>(u, shared_cols, a, grid, lds, s);
-        case 32: return launch_mq_g<32, VM>(u, shared_cols, a, grid, lds, s);
-        default: return launch_mq_g<64, VM>(u, shared_cols, a, grid, lds, s);
+        case 8: return launch_mq_g<8, VM>(u, shared_cols, a, f, grid, lds, s);
+        case 16: return launch_mq_g<16, VM>(u, shared_cols, a, f, grid, lds, s);
+        case 32: return launch_mq_g<32, VM>(u, shared_cols, a, f, grid, lds, s);
+        default: return launch_mq_g<64, VM>(u, shared_cols, a, f, grid, lds, s);
     }
 }
 
@@ -159,9 +165,9 @@ int mq_search(vs_index* idx, const float* dq, int32_t B, int32_t k, int64_t id_o
         // expected number of columns two queries of the batch share; uniform 776-nnz queries: ~20
         const double overlap = B > 1 ? (double)hplan[3] / ((double)B * (double)(B - 1)) : 0.0;
         const bool shared_cols = idx->mq_variant >= 0 ? idx->mq_variant == 1 : overlap > kMqSharedOverlap;
-        int rc = idx->store_dtype == VS_F32 ? launch_mq_vm<VM_F32>(mq_lanes(idx), u, shared_cols, a, grid, lds, s)
-               : idx->store_dtype == VS_F16 ? launch_mq_vm<VM_F16>(mq_lanes(idx), u, shared_cols, a, grid, lds, s)
-                                            : launch_mq_vm<VM_BIN>(mq_lanes(idx), u, shared_cols, a, grid, lds, s);
+        int rc = idx->store_dtype == VS_F32 ? launch_mq_vm<VM_F32>(mq_lanes(idx), u, shared_cols, a, idx->filt, grid, lds, s)
+               : idx->store_dtype == VS_F16 ? launch_mq_vm<VM_F16>(mq_lanes(idx), u, shared_cols, a, idx->filt, grid, lds, s)
+                                            : launch_mq_vm<VM_BIN>(mq_lanes(idx), u, shared_cols, a, idx->filt, grid, lds, s);
         VS_TRY(rc);
     }
     }
@@ -180,7 +186,7 @@ int mq_search(vs_index* idx, const float* dq, int32_t B, int32_t k, int64_t id_o
     m.run_len = k;                                 // every chunk's list is sorted
     {
         ProfScope prof("merge_topk", s);
-        hipLaunchKernelGGL(merge_topk_kernel<0>, dim3(std::min(B, idx->cu_count * 2)), dim3(kScanThreads), 0, s, m);
+        hipLaunchKernelGGL((idx->filt.words ? merge_topk_kernel<1> : merge_topk_kernel<0>), dim3(std::min(B, idx->cu_count * 2)), dim3(kScanThreads), 0, s, m);
     }
     VS_HIP(hipGetLastError());
     *done = true;

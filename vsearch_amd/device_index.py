@@ -203,25 +203,46 @@ class DeviceIndex:
         p, dt, keep = as_arg(q, (nat.VS_F32, nat.VS_F16))
         return p, dt, keep, int(q.shape[0]), int(q.shape[1])
 
-    def search(self, q, k: int, id_offset: int = 0):
+    def _filter_arg(self, filter, B):
+        """`filter=` -> (words pointer on this index's device, filter_ld, keep-alive DocFilter); (None, 0, None) without one."""
+        if filter is None:
+            return None, 0, None
+        from .doc_filter import as_doc_filter
+        f = as_doc_filter(filter, int(self.info().n_rows), device=self.device, batch=B)
+        return C.c_void_p(f.words.data_ptr()), f.ld, f
+
+    def search(self, q, k: int, id_offset: int = 0, filter=None):
         """Top-k per query -> (ids int64 [B,k], scores float32 [B,k]); canonical order (score desc, id asc).
         Device queries: the call returns once the kernels are enqueued on torch's current stream (no host synchronisation on
-        the postings filter path); host queries / outputs are copied and the call blocks."""
+        the postings filter path); host queries / outputs are copied and the call blocks.
+        filter: a DocFilter, a bool mask [N] / [B, N] or integer row ids to allow (vsearch_amd.doc_filter) -- the top k of the allowed
+        rows only; positions beyond them hold id -1, score -inf."""
         p, dt, keep, B, ldq = self._q_args(q)
         k = int(k)
+        fp, fld, fkeep = self._filter_arg(filter, B)
         if _is_torch(q) and q.is_cuda:
             import torch
             dev = torch.device("cuda", self.device)
             ids = torch.empty((B, k), dtype=torch.int64, device=dev)
             scores = torch.empty((B, k), dtype=torch.float32, device=dev)
             stream = current_stream(self.device)
-            nat.check(nat.lib().vs_index_search(self._h, p, dt, ldq, B, k, int(id_offset), C.c_void_p(ids.data_ptr()),
-                                                C.c_void_p(scores.data_ptr()), stream))
+            if fp is None:
+                nat.check(nat.lib().vs_index_search(self._h, p, dt, ldq, B, k, int(id_offset), C.c_void_p(ids.data_ptr()),
+                                                    C.c_void_p(scores.data_ptr()), stream))
+            else:
+                nat.check(nat.lib().vs_index_search_filtered(self._h, p, dt, ldq, B, k, fp, 0, fld, int(id_offset), C.c_void_p(ids.data_ptr()),
+                                                             C.c_void_p(scores.data_ptr()), stream))
             return ids, scores
         ids = np.empty((B, k), dtype=np.int64)
         scores = np.empty((B, k), dtype=np.float32)
-        nat.check(nat.lib().vs_index_search(self._h, p, dt, ldq, B, k, int(id_offset), C.c_void_p(ids.ctypes.data),
-                                            C.c_void_p(scores.ctypes.data), None))
+        if fp is None:
+            nat.check(nat.lib().vs_index_search(self._h, p, dt, ldq, B, k, int(id_offset), C.c_void_p(ids.ctypes.data),
+                                                C.c_void_p(scores.ctypes.data), None))
+        else:
+            import torch
+            torch.cuda.current_stream(self.device).synchronize()     # (the bitmap was packed on torch's stream; this call runs on the null stream)
+            nat.check(nat.lib().vs_index_search_filtered(self._h, p, dt, ldq, B, k, fp, 0, fld, int(id_offset), C.c_void_p(ids.ctypes.data),
+                                                         C.c_void_p(scores.ctypes.data), None))
         if _is_torch(q):
             import torch
             return torch.from_numpy(ids), torch.from_numpy(scores)
@@ -270,21 +291,36 @@ class ShardGroup:
         nat.check(nat.lib().vs_shard_group_create(arr, len(self._shards), C.byref(h)))
         self._h = h
 
-    def search(self, q, k: int):
+    @property
+    def n_rows(self) -> int:
+        return sum(int(s.info().n_rows) for s in self._shards)
+
+    def search(self, q, k: int, filter=None):
+        """filter: as DeviceIndex.search, over the GROUP's rows (global ids); every shard reads its own row range of it."""
         if q.ndim != 2:
             raise ValueError("queries must be [B, V]")
         p, dt, keep = as_arg(q, (nat.VS_F32, nat.VS_F16))
         B, ldq, k = int(q.shape[0]), int(q.shape[1]), int(k)
+        fkeep = None
+        if filter is not None:
+            from .doc_filter import as_doc_filter
+            fkeep = as_doc_filter(filter, self.n_rows, device=self._shards[0].device, batch=B)
+        def run(ids_p, sc_p):
+            if fkeep is None:
+                nat.check(nat.lib().vs_shard_group_search(self._h, p, dt, ldq, B, k, ids_p, sc_p))
+            else:
+                nat.check(nat.lib().vs_shard_group_search_filtered(self._h, p, dt, ldq, B, k, C.c_void_p(fkeep.words.data_ptr()), fkeep.ld,
+                                                                   ids_p, sc_p))
         if _is_torch(q) and q.is_cuda:
             import torch
             dev = torch.device("cuda", self._shards[0].device)
             ids = torch.empty((B, k), dtype=torch.int64, device=dev)
             sc = torch.empty((B, k), dtype=torch.float32, device=dev)
-            nat.check(nat.lib().vs_shard_group_search(self._h, p, dt, ldq, B, k, C.c_void_p(ids.data_ptr()), C.c_void_p(sc.data_ptr())))
+            run(C.c_void_p(ids.data_ptr()), C.c_void_p(sc.data_ptr()))
             return ids, sc
         ids = np.empty((B, k), dtype=np.int64)
         sc = np.empty((B, k), dtype=np.float32)
-        nat.check(nat.lib().vs_shard_group_search(self._h, p, dt, ldq, B, k, C.c_void_p(ids.ctypes.data), C.c_void_p(sc.ctypes.data)))
+        run(C.c_void_p(ids.ctypes.data), C.c_void_p(sc.ctypes.data))
         return ids, sc
 
     def close(self):

@@ -204,7 +204,10 @@ class Index:
         return self._load_line(self.data_file, self.offsets[index])
 
     # ---- search (index.py:88-94) -------------------------------------------------------------------
-    def search(self, q_embs: torch.Tensor, k: int) -> SearchResults:
+    def search(self, q_embs: torch.Tensor, k: int, filter=None) -> SearchResults:
+        """`filter` (not in the reference): search only part of the index -- a vsearch_amd.doc_filter.DocFilter, a bool mask [N] or
+        [B, N] (True = allowed) or an integer tensor of allowed row ids.  The result is the top k of the allowed rows; positions beyond
+        them hold id -1 and score -inf.  A mask whose length is not the index's row count raises ValueError."""
         if isinstance(q_embs, np.ndarray):
             q_embs = torch.from_numpy(q_embs)
         dev_index = self._device_index()
@@ -213,7 +216,7 @@ class Index:
         q = q.to(self._dtype) if self._dtype in (torch.float16, torch.float32) else q.float()   # `.type(self.vector.dtype)`
         if q.dim() == 1:
             q = q.unsqueeze(0)
-        ids, scores = dev_index.search(q.contiguous(), int(k))
+        ids, scores = dev_index.search(q.contiguous(), int(k), filter=filter)
         scores = scores.to(self._dtype)
         if torch.device(self.device).type != "cuda":
             ids, scores = ids.cpu(), scores.cpu()
@@ -341,9 +344,9 @@ class SparseIndex(Index):
         """GPU ordinal of every row shard (None: the index is not sharded)"""
         return [sh.device for sh in self._shards] if self._shards else None
 
-    def search(self, q_embs: torch.Tensor, k: int) -> SearchResults:
+    def search(self, q_embs: torch.Tensor, k: int, filter=None) -> SearchResults:
         if self._group is None:
-            return super().search(q_embs, k)
+            return super().search(q_embs, k, filter=filter)
         if isinstance(q_embs, np.ndarray):
             q_embs = torch.from_numpy(q_embs)
         gpu = torch.device("cuda", self._shards[0].device)
@@ -351,7 +354,7 @@ class SparseIndex(Index):
         q = q.to(self._dtype) if self._dtype in (torch.float16, torch.float32) else q.float()
         if q.dim() == 1:
             q = q.unsqueeze(0)
-        ids, scores = self._group.search(q.contiguous(), int(k))
+        ids, scores = self._group.search(q.contiguous(), int(k), filter=filter)
         return SearchResults(ids, scores.to(self._dtype))
 
     def move_to_device(self, device: str):

@@ -61,13 +61,15 @@ class Retriever(BiEncoder):
 
     # ---- retrieval (retriever.py:107-148) ----------------------------------------------------------
     def retrieve(self, queries: Union[List[str], np.ndarray, T], k: int = 5, dropout: float = 0, a: int = None,
-                 index: Index = None, rerank: bool = False, batch_size: int = 32) -> SearchResults:
+                 index: Index = None, rerank: bool = False, batch_size: int = 32, filter=None) -> SearchResults:
+        """`filter` (not in the reference): restrict the hits to part of the index (Index.search); hits beyond the allowed rows are
+        padding (id -1, score -inf), stay last through the rerank and are not re-embedded."""
         index = index or self.index
         if index is None:
             raise RuntimeError("no index: call build_index / load_index first")
         a = a or self.encoder_q.config.topk
         q_emb = self.process_query(queries, dropout, a, batch_size=batch_size)
-        results = index.search(q_emb, k=k)
+        results = index.search(q_emb, k=k, filter=filter) if filter is not None else index.search(q_emb, k=k)
         if rerank and index.index_type == IndexType.BAG_OF_TOKEN:
             results = self._rerank(index, q_emb, results, k, batch_size)
         return results
@@ -81,7 +83,8 @@ class Retriever(BiEncoder):
         from ...device_index import current_stream
         hit_ids = results.ids
         B = int(hit_ids.shape[0])
-        texts = [index.get_sample(i) for i in hit_ids.flatten().tolist()]
+        flat_ids = hit_ids.flatten().tolist()
+        texts = [index.get_sample(i) if i >= 0 else None for i in flat_ids]         # (id -1: a filtered search's padding, never re-embedded)
         nat.require_device()
         dev = hit_ids.device if hit_ids.is_cuda else torch.device("cuda", 0)
         ordinal = dev.index or 0
@@ -91,13 +94,24 @@ class Retriever(BiEncoder):
         scores = torch.empty((B, k), dtype=torch.float32, device=dev)
         chunk = max(int(batch_size), 1) * 32               # re-embedded passages held at a time
         for r0 in range(0, B * k, chunk):
-            p_emb = self.encoder_p.embed(texts[r0:r0 + chunk], batch_size=batch_size, require_grad=False)
+            part = texts[r0:r0 + chunk]
+            live = [i for i, t in enumerate(part) if t is not None]
+            if not live:
+                continue                                    # (all padding: its scores are set to -inf below)
+            p_emb = self.encoder_p.embed([part[i] for i in live], batch_size=batch_size, require_grad=False)
             if p_emb.dtype not in (torch.float32, torch.float16):
                 p_emb = p_emb.to(torch.float32)
-            p_emb = p_emb.to(dev).contiguous()
+            p_emb = p_emb.to(dev)
+            if len(live) < len(part):                       # padding rows: zeros in the batch, their scores overwritten below
+                full = torch.zeros((len(part), p_emb.shape[1]), dtype=p_emb.dtype, device=dev)
+                full[torch.as_tensor(live, device=dev)] = p_emb
+                p_emb = full
+            p_emb = p_emb.contiguous()
             nat.check(nat.lib().vs_rerank_scores(C.c_void_p(p_emb.data_ptr()), nat.VS_F16 if p_emb.dtype == torch.float16 else nat.VS_F32,
                                                  int(p_emb.shape[1]), int(p_emb.shape[0]), r0, C.c_void_p(q.data_ptr()), int(q.shape[1]), B, int(k),
                                                  int(q.shape[1]), C.c_void_p(scores.data_ptr()), ordinal, stream))
+        if (ids_dev < 0).any():
+            scores = scores.masked_fill(ids_dev < 0, float("-inf"))   # padding stays behind every real hit (and keeps its order)
         out_ids = torch.empty_like(ids_dev)
         out_scores = torch.empty_like(scores)
         nat.check(nat.lib().vs_rerank_topk(C.c_void_p(scores.data_ptr()), C.c_void_p(ids_dev.data_ptr()), B, int(k), C.c_void_p(out_ids.data_ptr()),
