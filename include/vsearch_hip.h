@@ -195,6 +195,24 @@ VS_API int vs_index_search_filtered(vs_index* index, const void* q, int q_dtype,
 VS_API int vs_filter_pack(const uint8_t* mask, int32_t B, int64_t n, int64_t ld_mask, uint32_t* words, int64_t ld_words,
                           int device, void* stream);
 
+/* Explain given (query, document id) pairs (no reference call site: what ir.explain(q, p) reports, biencoder.py:111-123, read from the
+ * index rows instead of re-embedded texts).  For pair (b, j) with id = ids[b * ld_ids + j]:
+ *   out_scores [B, k] fp32: the pair's score.  A CSR-packet index scores the row with the library's exact numerics (fp32 products summed
+ *     in fp64, the row summation of the refine step and the exact passes): bit-identical to the score those search paths return for the
+ *     pair.  A dense index on the matrix cores: the fp64 sum of the products, equal to its search score to within fp32 rounding.
+ *   out_matched [B, k] int32: terms whose product fl32(q[c] * v) is non-zero (> topn: the list below is truncated).
+ *   out_cols [B, k, topn] int32 / out_contrib [B, k, topn] fp32: the columns of the topn largest products, contribution descending
+ *     then column ascending; unused slots -1 / 0.  May be NULL when topn == 0 (score only).  topn in 0..1024.
+ *   id == -1 (a filtered search's padding): cols -1, contrib 0, score -inf, matched 0.  An id whose row id - id_offset is outside the
+ *   index: out_matched = -1 and nothing else written for the pair ("not mine": row-sharded callers pick each pair's owner by it).
+ *   q == NULL: disentangle mode -- each listed row's own stored values are ranked (contrib = value, 1 for a binary index), the score is
+ *   the fp64 sum of the values and out_matched the row's non-zeros.
+ *   q: as vs_index_search (rounded to the index dtype).  Host or device pointers (all outputs of one kind); device pointers must live
+ *   on the index's device (VS_EINVAL).  With a non-NULL stream and device pointers throughout, a CSR index only enqueues the work.   */
+VS_API int vs_index_explain(vs_index* index, const void* q, int q_dtype, int64_t ldq, int32_t B, const int64_t* ids, int64_t ld_ids,
+                            int32_t k, int64_t id_offset, int32_t topn, int32_t* out_cols, float* out_contrib, float* out_scores,
+                            int32_t* out_matched, void* stream);
+
 /* Dense score matrix [B, n_rows] fp32 -- the intermediate index.py:91 materialises.  Used by the
  * parity tests to check every score, not just the top-k.                                         */
 VS_API int vs_index_scores(vs_index* index, const void* q, int q_dtype, int64_t ldq, int32_t B,
@@ -277,6 +295,12 @@ VS_API int  vs_shard_group_search(vs_shard_group* group, const void* q, int q_dt
  * than k allowed rows) comes out of the merge as id -1, score -inf.  filter == NULL: exactly vs_shard_group_search.              */
 VS_API int  vs_shard_group_search_filtered(vs_shard_group* group, const void* q, int q_dtype, int64_t ldq, int32_t B, int32_t k,
                                            const uint32_t* filter, int64_t filter_ld, int64_t* out_ids, float* out_scores);
+/* vs_index_explain over the group's rows: ids are global; every shard explains the pairs of its row range on its own device, the first
+ * shard's device gathers each pair from its owner.  The result equals vs_index_explain of the unsharded index bit for bit.  q may be
+ * NULL (disentangle mode).  Inputs and outputs as in vs_shard_group_search (outputs on the first shard's device); blocking.        */
+VS_API int  vs_shard_group_explain(vs_shard_group* group, const void* q, int q_dtype, int64_t ldq, int32_t B, const int64_t* ids,
+                                   int64_t ld_ids, int32_t k, int32_t topn, int32_t* out_cols, float* out_contrib, float* out_scores,
+                                   int32_t* out_matched);
 VS_API void vs_shard_group_destroy(vs_shard_group* group);
 
 /* SparseIndex.save (index.py:181-202) needs crow/col/values back: int64 rowptr [n_rows+1], int64

@@ -53,6 +53,7 @@ _SIGNATURES = {
     "vs_index_search_filtered": ([_vp, _vp, _int, _i64, _i32, _i32, _vp, _i64, _i64, _i64, _vp, _vp, _vp], _int),
     "vs_filter_pack": ([_vp, _i32, _i64, _i64, _vp, _i64, _int, _vp], _int),
     "vs_index_scores": ([_vp, _vp, _int, _i64, _i32, _vp, _vp], _int),
+    "vs_index_explain": ([_vp, _vp, _int, _i64, _i32, _vp, _i64, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp], _int),
     "vs_index_prepare": ([_vp, _vp], _int),
     "vs_index_info": ([_vp, C.POINTER(IndexInfo)], _int),
     "vs_index_set_option": ([_vp, C.c_char_p, _int], _int),
@@ -63,6 +64,7 @@ _SIGNATURES = {
     "vs_shard_group_create": ([C.POINTER(_vp), _i32, C.POINTER(_vp)], _int),
     "vs_shard_group_search": ([_vp, _vp, _int, _i64, _i32, _i32, _vp, _vp], _int),
     "vs_shard_group_search_filtered": ([_vp, _vp, _int, _i64, _i32, _i32, _vp, _i64, _vp, _vp], _int),
+    "vs_shard_group_explain": ([_vp, _vp, _int, _i64, _i32, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp], _int),
     "vs_shard_group_destroy": ([_vp], None),
     "vs_merge_topk": ([_vp, _vp, _i32, _i64, _i32, _vp, _vp, _int, _vp], _int),
     "vs_topk_mask": ([_vp, _i32, _i32, _i64, _i32, _vp, _int, _vp], _int),

@@ -458,6 +458,17 @@ extern "C" int vs_shard_group_search_filtered(vs_shard_group* g, const void* q, 
     return shard_group_search(g, q, q_dtype, ldq, B, k, filter, filter_ld, out_ids, out_scores);
 }
 
+// (explain.hip: every shard explains the pairs of its row range on its own device, the first shard's device gathers them)
+int vs_shard_group_explain_impl(const std::vector<vs_index*>& shards, const std::vector<int64_t>& row0, const std::vector<hipStream_t>& streams,
+                                const void* q, int q_dtype, int64_t ldq, int32_t B, const int64_t* ids, int64_t ld_ids, int32_t k, int32_t topn,
+                                int32_t* out_cols, float* out_contrib, float* out_scores, int32_t* out_matched);
+
+extern "C" int vs_shard_group_explain(vs_shard_group* g, const void* q, int q_dtype, int64_t ldq, int32_t B, const int64_t* ids, int64_t ld_ids, int32_t k,
+                                      int32_t topn, int32_t* out_cols, float* out_contrib, float* out_scores, int32_t* out_matched) {
+    if (!g) return fail(VS_EINVAL, "NULL argument");
+    return vs_shard_group_explain_impl(g->shards, g->row0, g->streams, q, q_dtype, ldq, B, ids, ld_ids, k, topn, out_cols, out_contrib, out_scores, out_matched);
+}
+
 extern "C" int vs_profile_enable(int on) {
     Profiler::get().on = on != 0;
     return VS_OK;

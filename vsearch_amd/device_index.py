@@ -7,6 +7,7 @@ in -> torch tensors on the index device, on torch's current stream).
 from __future__ import annotations
 
 import ctypes as C
+from typing import Any, NamedTuple
 
 import numpy as np
 
@@ -63,6 +64,60 @@ def npz_inspect(path: str, shift: int = 0):
     n_rows, n_cols, nnz, packets = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
     nat.check(nat.lib().vs_npz_inspect(str(path).encode(), int(shift), C.byref(n_rows), C.byref(n_cols), C.byref(nnz), C.byref(packets)))
     return n_rows.value, n_cols.value, nnz.value, packets.value
+
+
+class Explanation(NamedTuple):
+    """Per (query, document) pair: the top contributing columns, their contributions q[c] * v (largest first, then column ascending;
+    -1 / 0 in unused slots), the pair's score and its number of matched terms (-1: the id is not a row of this index)."""
+    cols: Any          # int32 [B, k, topn]
+    contrib: Any       # float32 [B, k, topn]
+    scores: Any        # float32 [B, k]
+    n_matched: Any     # int32 [B, k]
+
+
+MAX_EXPLAIN_TOPN = 1024
+
+
+def _explain_args(q, ids, topn):
+    """Argument checks of explain() that need no device -> (B, k, topn, on_device)"""
+    if isinstance(topn, bool) or not isinstance(topn, (int, np.integer)):
+        raise TypeError(f"topn must be an int, got {type(topn).__name__}")
+    topn = int(topn)
+    if not 0 <= topn <= MAX_EXPLAIN_TOPN:
+        raise ValueError(f"topn must be in 0..{MAX_EXPLAIN_TOPN}, got {topn}")
+    if not hasattr(ids, "ndim") or ids.ndim != 2:
+        raise ValueError("ids must be a [B, k] array of document ids")
+    if _is_torch(ids):
+        import torch
+        if ids.dtype != torch.int64:
+            raise TypeError(f"ids must be int64, got {ids.dtype}")
+    elif np.asarray(ids).dtype != np.int64:
+        raise TypeError(f"ids must be int64, got {np.asarray(ids).dtype}")
+    ids_dev = _is_torch(ids) and ids.is_cuda
+    if q is not None:
+        if q.ndim != 2:
+            raise ValueError("queries must be [B, V]")
+        if int(q.shape[0]) != int(ids.shape[0]):
+            raise ValueError(f"{int(q.shape[0])} queries but ids has {int(ids.shape[0])} rows")
+        q_dev = _is_torch(q) and q.is_cuda
+        if q_dev != ids_dev or (q_dev and q.device != ids.device):
+            raise ValueError("queries and ids must live on the same device (both host, or both on the index's GPU)")
+    return int(ids.shape[0]), int(ids.shape[1]), topn, ids_dev
+
+
+def _explain_outputs(B, k, topn, device):
+    """(numpy | torch on `device`) output arrays of explain() and their pointers"""
+    if device is not None:
+        import torch
+        dev = torch.device("cuda", device)
+        out = (torch.full((B, k, topn), -1, dtype=torch.int32, device=dev), torch.zeros((B, k, topn), dtype=torch.float32, device=dev),
+               torch.empty((B, k), dtype=torch.float32, device=dev), torch.empty((B, k), dtype=torch.int32, device=dev))
+        ptrs = [C.c_void_p(t.data_ptr()) if t.numel() else None for t in out]
+    else:
+        out = (np.full((B, k, topn), -1, dtype=np.int32), np.zeros((B, k, topn), dtype=np.float32),
+               np.empty((B, k), dtype=np.float32), np.empty((B, k), dtype=np.int32))
+        ptrs = [C.c_void_p(a.ctypes.data) if a.size else None for a in out]
+    return out, ptrs
 
 
 class DeviceIndex:
@@ -248,6 +303,28 @@ class DeviceIndex:
             return torch.from_numpy(ids), torch.from_numpy(scores)
         return ids, scores
 
+    def explain(self, q, ids, topn: int = 10, id_offset: int = 0) -> Explanation:
+        """Score and explain the pairs (query b, document ids[b, j]) from the stored rows (vs_index_explain): per pair the top `topn`
+        columns by contribution q[c] * v, the score (bit-identical to the exact search paths' score on a CSR index) and the number of
+        matched terms.  q: [B, V] queries as in search(), or None to rank each row's own stored values (disentangle).  ids: int64 [B, k]
+        (id -1 = a filtered search's padding: cols -1, score -inf, 0 matched); ids are global, rows start at id_offset.
+        numpy in -> numpy out; torch CUDA in -> tensors on the index's device, enqueued on torch's current stream."""
+        B, k, topn, on_dev = _explain_args(q, ids, topn)
+        nat.require_device()
+        p, dt, keep, ldq = None, nat.VS_F32, None, 0
+        if q is not None:
+            p, dt, keep, _, ldq = self._q_args(q)
+        p_ids, _, keep_ids = as_arg(ids, (nat.VS_I64,))
+        out, ptrs = _explain_outputs(B, k, topn, self.device if on_dev else None)
+        if k == 0:
+            return Explanation(*out)
+        stream = current_stream(self.device) if on_dev else None
+        nat.check(nat.lib().vs_index_explain(self._h, p, dt, ldq, B, p_ids, k, k, int(id_offset), topn, *ptrs, stream))
+        if not on_dev and (_is_torch(ids) or _is_torch(q)):
+            import torch
+            out = tuple(torch.from_numpy(a) for a in out)
+        return Explanation(*out)
+
     def scores(self, q):
         """Dense [B, n_rows] fp32 score matrix (what index.py:91 materialises). numpy out."""
         info = self.info()
@@ -322,6 +399,25 @@ class ShardGroup:
         sc = np.empty((B, k), dtype=np.float32)
         run(C.c_void_p(ids.ctypes.data), C.c_void_p(sc.ctypes.data))
         return ids, sc
+
+    def explain(self, q, ids, topn: int = 10) -> Explanation:
+        """DeviceIndex.explain over the group's rows (global ids): every shard explains the pairs it owns on its own GPU, the first
+        shard's GPU gathers them; equal to explaining the unsharded index.  Blocking (vs_shard_group_explain)."""
+        B, k, topn, on_dev = _explain_args(q, ids, topn)
+        nat.require_device()
+        p, dt, keep, ldq = None, nat.VS_F32, None, 0
+        if q is not None:
+            p, dt, keep = as_arg(q, (nat.VS_F32, nat.VS_F16))
+            ldq = int(q.shape[1])
+        p_ids, _, keep_ids = as_arg(ids, (nat.VS_I64,))
+        out, ptrs = _explain_outputs(B, k, topn, self._shards[0].device if on_dev else None)
+        if k == 0:
+            return Explanation(*out)
+        nat.check(nat.lib().vs_shard_group_explain(self._h, p, dt, ldq, B, p_ids, k, k, topn, *ptrs))
+        if not on_dev and (_is_torch(ids) or _is_torch(q)):
+            import torch
+            out = tuple(torch.from_numpy(a) for a in out)
+        return Explanation(*out)
 
     def close(self):
         if self._h:

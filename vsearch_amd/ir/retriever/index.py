@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from ... import _native as nat
-from ...device_index import DeviceIndex, NotBinaryError, ShardGroup
+from ...device_index import DeviceIndex, Explanation, NotBinaryError, ShardGroup, _explain_args
 
 logger = logging.getLogger(__name__)
 
@@ -222,6 +222,61 @@ class Index:
             ids, scores = ids.cpu(), scores.cpu()
         return SearchResults(ids, scores)
 
+    # ---- explain (not in the reference: ir.explain(q, p) read from the index rows) -----------------------------------------------
+    def _n_rows(self) -> int:
+        return int(self._device_index().info().n_rows)
+
+    def _explain_target(self):
+        """(object with .explain(q, ids, topn), its first GPU)"""
+        dev = self._device_index()
+        return dev, dev.device
+
+    def explain(self, q_embs, ids, topn: int = 10) -> Explanation:
+        """Why document ids[b, j] is a hit of query b: the top `topn` columns by contribution q_w * p_w (largest first), the pair's
+        score (a sparse index: bit-identical to its search score) and the number of matched terms, all read from the stored rows --
+        nothing is re-embedded.  ids: int64 [B, k] (e.g. ``search(...).ids``); -1 is a filtered search's padding (cols -1, score -inf).
+        Columns are in the index file's column space (+ ``shift``).  An id outside [-1, N) raises IndexError."""
+        return self._explain(q_embs, ids, topn)
+
+    def disentangle(self, ids, topn: int = 10) -> Explanation:
+        """The top `topn` stored values of each listed row (no query, no encoder): contrib = the value (1 for a bag-of-token index),
+        score = the row's sum, n_matched = its non-zeros.  ids: int64 [B, k] (or [k]: one row of ids)."""
+        return self._explain(None, ids, topn)
+
+    def _explain(self, q_embs, ids, topn):
+        if isinstance(ids, np.ndarray):
+            ids = torch.from_numpy(ids)
+        if not isinstance(ids, torch.Tensor):
+            raise TypeError(f"ids must be a tensor or an ndarray, got {type(ids).__name__}")
+        if ids.dim() == 1:
+            ids = ids.unsqueeze(0)
+        q = None
+        if q_embs is not None:
+            if isinstance(q_embs, np.ndarray):
+                q_embs = torch.from_numpy(q_embs)
+            q = q_embs.detach()
+            if q.dim() == 1:
+                q = q.unsqueeze(0)
+        _explain_args(q, ids.cpu() if q is None or not q.is_cuda else ids.to(q.device), topn)     # (argument errors before any device work)
+        if ids.numel():
+            lo, hi = int(ids.min()), int(ids.max())
+            n = self._n_rows()
+            if lo < -1 or hi >= n:
+                raise IndexError(f"document id {lo if lo < -1 else hi} out of range [-1, {n})")
+        target, gpu_ord = self._explain_target()
+        gpu = torch.device("cuda", gpu_ord)
+        if q is not None:
+            q = q.to(gpu)
+            q = q.to(self._dtype) if self._dtype in (torch.float16, torch.float32) else q.float()
+            q = q.contiguous()
+        ex = target.explain(q, ids.to(gpu).contiguous(), int(topn))
+        shift = int(getattr(self, "shift", 0) or 0)
+        cols = torch.where(ex.cols >= 0, ex.cols + shift, ex.cols) if shift else ex.cols
+        ex = Explanation(cols, ex.contrib, ex.scores, ex.n_matched)
+        if torch.device(self.device).type != "cuda":
+            ex = Explanation(*(t.cpu() for t in ex))
+        return ex
+
     # ---- persistence -------------------------------------------------------------------------------
     def save(self, path):
         """Dense index -> ``.pt`` (torch.save of the CPU tensor), like index.py:96-109."""
@@ -356,6 +411,14 @@ class SparseIndex(Index):
             q = q.unsqueeze(0)
         ids, scores = self._group.search(q.contiguous(), int(k), filter=filter)
         return SearchResults(ids, scores.to(self._dtype))
+
+    def _n_rows(self) -> int:
+        return self._group.n_rows if self._group is not None else super()._n_rows()
+
+    def _explain_target(self):
+        if self._group is None:
+            return super()._explain_target()
+        return self._group, self._shards[0].device
 
     def move_to_device(self, device: str):
         if self._group is not None:

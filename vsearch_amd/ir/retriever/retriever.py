@@ -12,7 +12,7 @@ retriever.py:150-205) are out of scope and absent.
 from __future__ import annotations
 
 import logging
-from typing import List, Union
+from typing import Dict, List, Union
 
 import numpy as np
 import torch
@@ -73,6 +73,35 @@ class Retriever(BiEncoder):
         if rerank and index.index_type == IndexType.BAG_OF_TOKEN:
             results = self._rerank(index, q_emb, results, k, batch_size)
         return results
+
+    def explain_results(self, queries: Union[List[str], np.ndarray, T], results: SearchResults, topn: int = 10, index: Index = None,
+                        a: int = None, batch_size: int = 32) -> List[List[Dict[str, float]]]:
+        """Why each hit of `results` (from ``retrieve``) was returned: per query, per hit, token -> contribution q_w * p_w, largest
+        first -- the shape ``explain`` returns -- read from the index rows on the device (Index.explain), not re-embedded.  `queries`:
+        texts or embeddings, as ``retrieve`` takes them.  Padding hits (id -1) give {}."""
+        index = index or self.index
+        if index is None:
+            raise RuntimeError("no index: call build_index / load_index first")
+        a = a or self.encoder_q.config.topk
+        q_emb = self.process_query(queries, 0, a, batch_size=batch_size)
+        ex = index.explain(q_emb, results.ids, topn=topn)
+        cols, contrib = ex.cols.cpu().numpy(), ex.contrib.cpu().numpy()
+        ids = results.ids.cpu().numpy() if isinstance(results.ids, T) else np.asarray(results.ids)
+        shift = int(self.encoder_p.config.shift_vocab_num)
+        tok = self.encoder_p.tokenizer
+        out: List[List[Dict[str, float]]] = []
+        for b in range(cols.shape[0]):
+            row = []
+            for j in range(cols.shape[1]):
+                live = cols[b, j] >= 0
+                if ids.ndim == 2 and ids[b, j] < 0 or not live.any():
+                    row.append({})
+                    continue
+                c = cols[b, j][live]
+                names = tok.convert_ids_to_tokens([int(x) + shift for x in c])
+                row.append({name: float(v) for name, v in zip(names, contrib[b, j][live])})
+            out.append(row)
+        return out
 
     def _rerank(self, index: Index, q_emb: T, results: SearchResults, k: int, batch_size: int) -> SearchResults:
         """Re-embed the k hits with encoder_p, score against q, re-sort (retriever.py:137-147) -- on the device:
