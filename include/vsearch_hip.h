@@ -213,6 +213,31 @@ VS_API int vs_index_explain(vs_index* index, const void* q, int q_dtype, int64_t
                             int32_t k, int64_t id_offset, int32_t topn, int32_t* out_cols, float* out_contrib, float* out_scores,
                             int32_t* out_matched, void* stream);
 
+/* Query by example (no reference call site: what index.vector[ids] gives the reference, without exporting the index).
+ * vs_index_get_rows: the stored rows of ids [n] (row = id - id_offset) as a compact CSR -- out_rowptr int64 [n + 1], out_cols int32 and
+ *   out_vals fp32 [out_rowptr[n]]: columns ascending as stored, fp16 values widened exactly, 1 for a binary index, the non-zeros of a dense
+ *   (MFMA) row.  Id -1 gives an empty row; any other id outside the index: VS_EINVAL.  Two calls, like vs_index_export_csr: out_cols ==
+ *   out_vals == NULL fills out_rowptr only (sizes the others).  Host or device pointers (outputs all of one kind; device pointers on the
+ *   index's device).  Blocking.                                                                                                          */
+VS_API int vs_index_get_rows(vs_index* index, const int64_t* ids, int64_t n, int64_t id_offset, int64_t* out_rowptr, int32_t* out_cols,
+                             float* out_vals, void* stream);
+/* vs_index_queries_from_rows: dense fp32 query rows out_q [B, ldo] built from stored rows, with these numerics (fl32 = fp32 rounding):
+ *     acc[c] = fl32(alpha * q[b, c])            (0 without q; an fp16 q is widened first)
+ *     for j = 0 .. m-1, skipping id -1:  for every stored column c of row ids[b * ld_ids + j]:  acc[c] = fl32(acc[c] + fl32(w[b, j] * v))
+ *   weights [B, ldw] fp32 or NULL (all 1); q [B, ldq] VS_F32 | VS_F16 or NULL; m >= 1, ldq and ldo >= n_cols.  Host ids outside [-1, n_rows):
+ *   VS_EINVAL (device ids are not read on the host: such rows are skipped).  Host or device pointers; device pointers on the index's device.
+ *   With device pointers throughout and a non-NULL stream the call only enqueues the work.                                             */
+VS_API int vs_index_queries_from_rows(vs_index* index, const int64_t* ids, int32_t B, int32_t m, int64_t ld_ids, const float* weights,
+                                      int64_t ldw, const void* q, int q_dtype, int64_t ldq, float alpha, float* out_q, int64_t ldo,
+                                      void* stream);
+/* vs_topk_exclude: per query b, its top list ids / scores [B, ld] (kk entries, canonical order) without the ids excl[b * ld_excl + 0 .. m)
+ *   (-1 in excl is no id) -> the first k survivors in out_ids / out_scores [B, k]; fewer than k survivors: id -1, score -inf behind them.
+ *   Padding (id -1) of a filtered search stays last.  Searching kk = min(k + m, N) and excluding is exact: under the canonical order the top
+ *   k of "all rows minus E" lies inside the top k + |E|.  m in 1..16384.  Host or device pointers (device ones on `device`); stream as in
+ *   vs_topk_mask.                                                                                                                        */
+VS_API int vs_topk_exclude(const int64_t* ids, const float* scores, int32_t B, int32_t kk, int64_t ld, const int64_t* excl, int32_t m,
+                           int64_t ld_excl, int32_t k, int64_t* out_ids, float* out_scores, int device, void* stream);
+
 /* Dense score matrix [B, n_rows] fp32 -- the intermediate index.py:91 materialises.  Used by the
  * parity tests to check every score, not just the top-k.                                         */
 VS_API int vs_index_scores(vs_index* index, const void* q, int q_dtype, int64_t ldq, int32_t B,
@@ -301,6 +326,15 @@ VS_API int  vs_shard_group_search_filtered(vs_shard_group* group, const void* q,
 VS_API int  vs_shard_group_explain(vs_shard_group* group, const void* q, int q_dtype, int64_t ldq, int32_t B, const int64_t* ids,
                                    int64_t ld_ids, int32_t k, int32_t topn, int32_t* out_cols, float* out_contrib, float* out_scores,
                                    int32_t* out_matched);
+/* vs_index_get_rows / vs_index_queries_from_rows over the group's rows: ids are global.  Every shard extracts the rows it owns on its own
+ * device, the first shard's device stitches them (and accumulates the queries from the stitched rows: the same fl32 operations in the same
+ * order).  The results equal the unsharded calls bit for bit.  Inputs: host or device pointers on any GPU; outputs: host pointers or device
+ * pointers on the first shard's device.  An id outside [-1, total rows): VS_EINVAL.  Blocking.                                          */
+VS_API int  vs_shard_group_get_rows(vs_shard_group* group, const int64_t* ids, int64_t n, int64_t* out_rowptr, int32_t* out_cols,
+                                    float* out_vals);
+VS_API int  vs_shard_group_queries_from_rows(vs_shard_group* group, const int64_t* ids, int32_t B, int32_t m, int64_t ld_ids,
+                                             const float* weights, int64_t ldw, const void* q, int q_dtype, int64_t ldq, float alpha,
+                                             float* out_q, int64_t ldo);
 VS_API void vs_shard_group_destroy(vs_shard_group* group);
 
 /* SparseIndex.save (index.py:181-202) needs crow/col/values back: int64 rowptr [n_rows+1], int64

@@ -54,6 +54,8 @@ _SIGNATURES = {
     "vs_filter_pack": ([_vp, _i32, _i64, _i64, _vp, _i64, _int, _vp], _int),
     "vs_index_scores": ([_vp, _vp, _int, _i64, _i32, _vp, _vp], _int),
     "vs_index_explain": ([_vp, _vp, _int, _i64, _i32, _vp, _i64, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp], _int),
+    "vs_index_get_rows": ([_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp], _int),
+    "vs_index_queries_from_rows": ([_vp, _vp, _i32, _i32, _i64, _vp, _i64, _vp, _int, _i64, C.c_float, _vp, _i64, _vp], _int),
     "vs_index_prepare": ([_vp, _vp], _int),
     "vs_index_info": ([_vp, C.POINTER(IndexInfo)], _int),
     "vs_index_set_option": ([_vp, C.c_char_p, _int], _int),
@@ -65,8 +67,11 @@ _SIGNATURES = {
     "vs_shard_group_search": ([_vp, _vp, _int, _i64, _i32, _i32, _vp, _vp], _int),
     "vs_shard_group_search_filtered": ([_vp, _vp, _int, _i64, _i32, _i32, _vp, _i64, _vp, _vp], _int),
     "vs_shard_group_explain": ([_vp, _vp, _int, _i64, _i32, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp], _int),
+    "vs_shard_group_get_rows": ([_vp, _vp, _i64, _vp, _vp, _vp], _int),
+    "vs_shard_group_queries_from_rows": ([_vp, _vp, _i32, _i32, _i64, _vp, _i64, _vp, _int, _i64, C.c_float, _vp, _i64], _int),
     "vs_shard_group_destroy": ([_vp], None),
     "vs_merge_topk": ([_vp, _vp, _i32, _i64, _i32, _vp, _vp, _int, _vp], _int),
+    "vs_topk_exclude": ([_vp, _vp, _i32, _i32, _i64, _vp, _i32, _i64, _i32, _vp, _vp, _int, _vp], _int),
     "vs_topk_mask": ([_vp, _i32, _i32, _i64, _i32, _vp, _int, _vp], _int),
     "vs_bow_mask": ([_vp, _i32, _i32, _i32, _i32, _int, _vp, _int, _vp], _int),
     "vs_embed_mask": ([_vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _int, _int, _int, _vp], _int),

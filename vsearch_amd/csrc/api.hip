@@ -469,6 +469,35 @@ extern "C" int vs_shard_group_explain(vs_shard_group* g, const void* q, int q_dt
     return vs_shard_group_explain_impl(g->shards, g->row0, g->streams, q, q_dtype, ldq, B, ids, ld_ids, k, topn, out_cols, out_contrib, out_scores, out_matched);
 }
 
+// (by_example.hip: the owners extract the rows of their ids, the first shard's device stitches them -- and accumulates the queries)
+int vs_shard_group_get_rows_impl(const std::vector<vs_index*>& shards, const std::vector<int64_t>& row0, const std::vector<hipStream_t>& streams,
+                                 const int64_t* ids, int64_t n, int64_t* out_rowptr, int32_t* out_cols, float* out_vals);
+int vs_shard_group_queries_from_rows_impl(const std::vector<vs_index*>& shards, const std::vector<int64_t>& row0, const std::vector<hipStream_t>& streams,
+                                          const int64_t* ids, int32_t B, int32_t m, int64_t ld_ids, const float* weights, int64_t ldw, const void* q,
+                                          int q_dtype, int64_t ldq, float alpha, float* out_q, int64_t ldo);
+
+static int group_need_device() {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        (void)hipGetLastError();
+        return fail(VS_ENODEVICE, "no HIP device visible: libvsearch_hip has no CPU fallback");
+    }
+    return VS_OK;
+}
+
+extern "C" int vs_shard_group_get_rows(vs_shard_group* g, const int64_t* ids, int64_t n, int64_t* out_rowptr, int32_t* out_cols, float* out_vals) {
+    VS_TRY(group_need_device());
+    if (!g) return fail(VS_EINVAL, "NULL argument");
+    return vs_shard_group_get_rows_impl(g->shards, g->row0, g->streams, ids, n, out_rowptr, out_cols, out_vals);
+}
+
+extern "C" int vs_shard_group_queries_from_rows(vs_shard_group* g, const int64_t* ids, int32_t B, int32_t m, int64_t ld_ids, const float* weights,
+                                                int64_t ldw, const void* q, int q_dtype, int64_t ldq, float alpha, float* out_q, int64_t ldo) {
+    VS_TRY(group_need_device());
+    if (!g) return fail(VS_EINVAL, "NULL argument");
+    return vs_shard_group_queries_from_rows_impl(g->shards, g->row0, g->streams, ids, B, m, ld_ids, weights, ldw, q, q_dtype, ldq, alpha, out_q, ldo);
+}
+
 extern "C" int vs_profile_enable(int on) {
     Profiler::get().on = on != 0;
     return VS_OK;

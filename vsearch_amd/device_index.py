@@ -120,6 +120,141 @@ def _explain_outputs(B, k, topn, device):
     return out, ptrs
 
 
+def _int64_ids(ids, ndim, name="ids"):
+    """checks of an id array: int64, `ndim` dimensions -> on_device"""
+    if not hasattr(ids, "ndim") or ids.ndim != ndim:
+        raise ValueError(f"{name} must be a {'[n]' if ndim == 1 else '[B, m]'} array of document ids")
+    if _is_torch(ids):
+        import torch
+        if ids.dtype != torch.int64:
+            raise TypeError(f"{name} must be int64, got {ids.dtype}")
+    elif np.asarray(ids).dtype != np.int64:
+        raise TypeError(f"{name} must be int64, got {np.asarray(ids).dtype}")
+    return _is_torch(ids) and ids.is_cuda
+
+
+def _by_example_args(ids, weights=None, q=None, k=None, a=None):
+    """Argument checks of queries_from_rows() / search_by_example() that need no device -> (B, m, on_device)"""
+    on_dev = _int64_ids(ids, 2)
+    B, m = int(ids.shape[0]), int(ids.shape[1])
+    if m < 1:
+        raise ValueError("ids must hold at least one example id per query (m >= 1)")
+    for name, x in (("weights", weights), ("q", q)):
+        if x is None:
+            continue
+        if not hasattr(x, "ndim") or x.ndim != 2:
+            raise ValueError(f"{name} must be a 2-D array")
+        if int(x.shape[0]) != B or (name == "weights" and int(x.shape[1]) != m):
+            raise ValueError(f"{name} has shape {tuple(x.shape)}, ids {tuple(ids.shape)}")
+        x_dev = _is_torch(x) and x.is_cuda
+        if x_dev != on_dev or (x_dev and x.device != ids.device):
+            raise ValueError(f"{name} and ids must live on the same device (both host, or both on the index's GPU)")
+    _k_a_args(k, a)
+    return B, m, on_dev
+
+
+def _k_a_args(k=None, a=None):
+    if k is not None:
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+            raise TypeError(f"k must be an int, got {type(k).__name__}")
+        if k < 1:
+            raise ValueError(f"k must be >= 1, got {k}")
+    if a is not None:
+        if isinstance(a, bool) or not isinstance(a, (int, np.integer)):
+            raise TypeError(f"a must be an int, got {type(a).__name__}")
+        if a < 1:
+            raise ValueError(f"a must be in 1..V, got {a}")
+
+
+def _check_a(a, V):
+    if a is not None and not 1 <= int(a) <= V:
+        raise ValueError(f"a must be in 1..{V}, got {a}")
+
+
+def resparsify(q, a: int, device: int):
+    """Keep the `a` largest entries of every row of fp32 queries q [B, V] (vs_topk_mask: ties at the a-th value go to the lower column,
+    as build_topk_mask), zeros elsewhere.  numpy in -> numpy out; torch CUDA in -> a new tensor on torch's current stream."""
+    B, V = int(q.shape[0]), int(q.shape[1])
+    _check_a(a, V)
+    if _is_torch(q) and q.is_cuda:
+        import torch
+        x = q.contiguous()
+        mask = torch.empty((B, V), dtype=torch.uint8, device=x.device)
+        nat.check(nat.lib().vs_topk_mask(C.c_void_p(x.data_ptr()), B, V, V, int(a), C.c_void_p(mask.data_ptr()), int(device),
+                                         current_stream(int(device))))
+        return x.masked_fill(mask == 0, 0.0)
+    x = np.ascontiguousarray(q, dtype=np.float32)
+    mask = np.empty((B, V), dtype=np.uint8)
+    nat.check(nat.lib().vs_topk_mask(C.c_void_p(x.ctypes.data), B, V, V, int(a), C.c_void_p(mask.ctypes.data), int(device), None))
+    return np.where(mask != 0, x, np.float32(0))
+
+
+def topk_exclude(ids, scores, excl, k: int, device: int = 0):
+    """Per query b: the top list ids / scores [B, kk] (canonical order) without the ids excl[b] ([B, m]; -1 is no id) -> the first k
+    survivors [B, k], padded with id -1 / score -inf (vs_topk_exclude).  numpy in -> numpy out; torch CUDA in -> torch's current stream."""
+    nat.require_device()
+    B, kk, m = int(ids.shape[0]), int(ids.shape[1]), int(excl.shape[1])
+    p_i, _, k1 = as_arg(ids, (nat.VS_I64,))
+    p_s, _, k2 = as_arg(scores, (nat.VS_F32,))
+    p_e, _, k3 = as_arg(excl, (nat.VS_I64,))
+    if _is_torch(ids) and ids.is_cuda:
+        import torch
+        out_i = torch.empty((B, k), dtype=torch.int64, device=ids.device)
+        out_s = torch.empty((B, k), dtype=torch.float32, device=ids.device)
+        nat.check(nat.lib().vs_topk_exclude(p_i, p_s, B, kk, kk, p_e, m, m, int(k), C.c_void_p(out_i.data_ptr()), C.c_void_p(out_s.data_ptr()),
+                                            int(device), current_stream(int(device))))
+        return out_i, out_s
+    out_i = np.empty((B, k), dtype=np.int64)
+    out_s = np.empty((B, k), dtype=np.float32)
+    nat.check(nat.lib().vs_topk_exclude(p_i, p_s, B, kk, kk, p_e, m, m, int(k), C.c_void_p(out_i.ctypes.data), C.c_void_p(out_s.ctypes.data),
+                                        int(device), None))
+    if _is_torch(ids):
+        import torch
+        return torch.from_numpy(out_i), torch.from_numpy(out_s)
+    return out_i, out_s
+
+
+def _search_by_example(obj, ids, k, weights, q, alpha, a, exclude, filter):
+    """queries_from_rows -> optional top-`a` re-sparsify -> search of k + m (or k) -> exclusion of the example ids"""
+    B, m, on_dev = _by_example_args(ids, weights, q, k, a)
+    nat.require_device()
+    device = obj.device
+    qq = obj.queries_from_rows(ids, weights=weights, q=q, alpha=alpha)
+    if a is not None:
+        qq = resparsify(qq, a, device)
+    k = int(k)
+    if not exclude:
+        return obj.search(qq, k, filter=filter)
+    n = obj.n_rows
+    kk = min(k + m, n) if k <= n else k                                 # (k > n: the search raises as it does for any query)
+    out_ids, out_sc = obj.search(qq, kk, filter=filter)
+    if _is_torch(ids) and not on_dev:
+        ids = ids.numpy()
+    return topk_exclude(out_ids, out_sc, ids, k, device)
+
+
+def _queries_from_rows(call, ids, weights, q, alpha, B, m, V, device, stream):
+    """the shared body of DeviceIndex / ShardGroup .queries_from_rows: call(ids, B, m, ld_ids, w, ldw, q, q_dtype, ldq, alpha, out, ldo[, stream])"""
+    p_ids, _, k1 = as_arg(ids, (nat.VS_I64,))
+    p_w, _, k2 = as_arg(weights, (nat.VS_F32,))
+    p_q, dt, k3 = as_arg(q, (nat.VS_F32, nat.VS_F16))
+    ldq = int(q.shape[1]) if q is not None else 0
+    if q is None:
+        dt = nat.VS_F32
+    if device is not None:
+        import torch
+        out = torch.empty((B, V), dtype=torch.float32, device=torch.device("cuda", device))
+        args = (p_ids, B, m, m, p_w, m, p_q, dt, ldq, float(alpha), C.c_void_p(out.data_ptr()), V)
+        nat.check(call(*args, current_stream(device)) if stream else call(*args))
+        return out
+    out = np.empty((B, V), dtype=np.float32)
+    args = (p_ids, B, m, m, p_w, m, p_q, dt, ldq, float(alpha), C.c_void_p(out.ctypes.data), V)
+    nat.check(call(*args, None) if stream else call(*args))
+    if _is_torch(ids) or _is_torch(q) or _is_torch(weights):
+        import torch
+        return torch.from_numpy(out)
+    return out
+
 class DeviceIndex:
     """Owner of one device-resident index shard (CSR packets or dense)."""
 
@@ -325,6 +460,67 @@ class DeviceIndex:
             out = tuple(torch.from_numpy(a) for a in out)
         return Explanation(*out)
 
+    # ---- query by example ------------------------------------------------------------------------
+    @property
+    def n_rows(self) -> int:
+        return int(self.info().n_rows)
+
+    def _n_cols(self) -> int:
+        if getattr(self, "_cols", None) is None:
+            self._cols = int(self.info().n_cols)
+        return self._cols
+
+    def get_rows(self, ids, id_offset: int = 0):
+        """The stored rows of ids (int64 [n]; -1 = an empty row) -> (indptr int64 [n + 1], indices int32, values float32): columns ascending,
+        fp16 values widened exactly, 1 for a binary index, the non-zeros of a dense row (vs_index_get_rows).  An id outside [-1, N) raises
+        ValueError.  numpy in -> numpy out; torch CUDA in -> tensors on the index's device.  Blocking."""
+        on_dev = _int64_ids(ids, 1)
+        nat.require_device()
+        n = int(ids.shape[0])
+        p_ids, _, keep = as_arg(ids, (nat.VS_I64,))
+        if on_dev:
+            import torch
+            dev = torch.device("cuda", self.device)
+            stream = current_stream(self.device)
+            indptr = torch.empty(n + 1, dtype=torch.int64, device=dev)
+            nat.check(nat.lib().vs_index_get_rows(self._h, p_ids, n, int(id_offset), C.c_void_p(indptr.data_ptr()), None, None, stream))
+            nnz = int(indptr[-1])
+            indices = torch.empty(nnz, dtype=torch.int32, device=dev)
+            values = torch.empty(nnz, dtype=torch.float32, device=dev)
+            if nnz:
+                nat.check(nat.lib().vs_index_get_rows(self._h, p_ids, n, int(id_offset), C.c_void_p(indptr.data_ptr()),
+                                                      C.c_void_p(indices.data_ptr()), C.c_void_p(values.data_ptr()), stream))
+            return indptr, indices, values
+        indptr = np.empty(n + 1, dtype=np.int64)
+        nat.check(nat.lib().vs_index_get_rows(self._h, p_ids, n, int(id_offset), C.c_void_p(indptr.ctypes.data), None, None, None))
+        nnz = int(indptr[-1])
+        indices = np.empty(nnz, dtype=np.int32)
+        values = np.empty(nnz, dtype=np.float32)
+        if nnz:
+            nat.check(nat.lib().vs_index_get_rows(self._h, p_ids, n, int(id_offset), C.c_void_p(indptr.ctypes.data), C.c_void_p(indices.ctypes.data),
+                                                  C.c_void_p(values.ctypes.data), None))
+        if _is_torch(ids):
+            import torch
+            return torch.from_numpy(indptr), torch.from_numpy(indices), torch.from_numpy(values)
+        return indptr, indices, values
+
+    def queries_from_rows(self, ids, weights=None, q=None, alpha: float = 1.0):
+        """Dense fp32 queries [B, V] from stored rows (vs_index_queries_from_rows): row b is fl32(alpha * q[b]) (0 without q) plus
+        fl32(weights[b, j] * row ids[b, j]) for j = 0 .. m-1 in order, each add rounded to fp32; id -1 adds nothing.  ids: int64 [B, m];
+        weights: float32 [B, m] (default 1); q: [B, V] fp32 | fp16.  numpy in -> numpy out; torch CUDA in -> a tensor on the index's
+        device, enqueued on torch's current stream."""
+        B, m, on_dev = _by_example_args(ids, weights, q)
+        nat.require_device()
+        V = self._n_cols()
+        return _queries_from_rows(lambda *args: nat.lib().vs_index_queries_from_rows(self._h, *args), ids, weights, q, alpha, B, m, V,
+                                  self.device if on_dev else None, True)
+
+    def search_by_example(self, ids, k: int, weights=None, q=None, alpha: float = 1.0, a=None, exclude: bool = True, filter=None):
+        """Search with stored rows as queries: queries_from_rows(ids, weights, q, alpha), then (a = int) only the a largest entries of
+        each query (vs_topk_mask), then the top k -- without each query's own example ids when `exclude` (the search takes k + m and
+        vs_topk_exclude drops them: exact).  filter: as search().  -> (ids, scores); fewer than k rows left: id -1, score -inf."""
+        return _search_by_example(self, ids, k, weights, q, alpha, a, exclude, filter)
+
     def scores(self, q):
         """Dense [B, n_rows] fp32 score matrix (what index.py:91 materialises). numpy out."""
         info = self.info()
@@ -372,6 +568,11 @@ class ShardGroup:
     def n_rows(self) -> int:
         return sum(int(s.info().n_rows) for s in self._shards)
 
+    @property
+    def device(self) -> int:
+        """the first shard's GPU: where the group's results land"""
+        return self._shards[0].device
+
     def search(self, q, k: int, filter=None):
         """filter: as DeviceIndex.search, over the GROUP's rows (global ids); every shard reads its own row range of it."""
         if q.ndim != 2:
@@ -418,6 +619,47 @@ class ShardGroup:
             import torch
             out = tuple(torch.from_numpy(a) for a in out)
         return Explanation(*out)
+
+    def get_rows(self, ids):
+        """DeviceIndex.get_rows over the group's rows (global ids): every shard extracts the rows it owns, the first shard's GPU stitches
+        them (vs_shard_group_get_rows); equal to the unsharded index.  Blocking."""
+        on_dev = _int64_ids(ids, 1)
+        nat.require_device()
+        n = int(ids.shape[0])
+        p_ids, _, keep = as_arg(ids, (nat.VS_I64,))
+        if on_dev:
+            import torch
+            dev = torch.device("cuda", self._shards[0].device)
+            alloc = lambda size, dt: torch.empty(size, dtype=dt, device=dev)
+            ptr = lambda t: C.c_void_p(t.data_ptr())
+            i64, i32, f32 = torch.int64, torch.int32, torch.float32
+        else:
+            alloc = lambda size, dt: np.empty(size, dtype=dt)
+            ptr = lambda a: C.c_void_p(a.ctypes.data)
+            i64, i32, f32 = np.int64, np.int32, np.float32
+        indptr = alloc(n + 1, i64)
+        nat.check(nat.lib().vs_shard_group_get_rows(self._h, p_ids, n, ptr(indptr), None, None))
+        nnz = int(indptr[-1])
+        indices, values = alloc(nnz, i32), alloc(nnz, f32)
+        if nnz:
+            nat.check(nat.lib().vs_shard_group_get_rows(self._h, p_ids, n, ptr(indptr), ptr(indices), ptr(values)))
+        if not on_dev and _is_torch(ids):
+            import torch
+            return torch.from_numpy(indptr), torch.from_numpy(indices), torch.from_numpy(values)
+        return indptr, indices, values
+
+    def queries_from_rows(self, ids, weights=None, q=None, alpha: float = 1.0):
+        """DeviceIndex.queries_from_rows over the group's rows (global ids): the owners extract the rows, the first shard's GPU accumulates
+        them with the same numerics -- equal to the unsharded index bit for bit (vs_shard_group_queries_from_rows).  Blocking."""
+        B, m, on_dev = _by_example_args(ids, weights, q)
+        nat.require_device()
+        V = int(self._shards[0].info().n_cols)
+        return _queries_from_rows(lambda *args: nat.lib().vs_shard_group_queries_from_rows(self._h, *args), ids, weights, q, alpha, B, m, V,
+                                  self._shards[0].device if on_dev else None, False)
+
+    def search_by_example(self, ids, k: int, weights=None, q=None, alpha: float = 1.0, a=None, exclude: bool = True, filter=None):
+        """DeviceIndex.search_by_example over the group's rows (global ids)."""
+        return _search_by_example(self, ids, k, weights, q, alpha, a, exclude, filter)
 
     def close(self):
         if self._h:

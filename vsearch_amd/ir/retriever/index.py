@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from ... import _native as nat
-from ...device_index import DeviceIndex, Explanation, NotBinaryError, ShardGroup, _explain_args
+from ...device_index import DeviceIndex, Explanation, NotBinaryError, ShardGroup, _by_example_args, _explain_args, _int64_ids, _k_a_args, resparsify, topk_exclude
 
 logger = logging.getLogger(__name__)
 
@@ -276,6 +276,99 @@ class Index:
         if torch.device(self.device).type != "cuda":
             ex = Explanation(*(t.cpu() for t in ex))
         return ex
+
+    # ---- query by example (not in the reference: stored rows as queries) -----------------------------------------------------------
+    def _example_ids(self, ids, ndim):
+        """ids (tensor | ndarray | list) -> int64 tensor of `ndim` dimensions; IndexError for an id outside [-1, N), before any device work"""
+        if isinstance(ids, np.ndarray):
+            ids = torch.from_numpy(ids)
+        elif isinstance(ids, (list, tuple)):
+            ids = torch.as_tensor(ids, dtype=torch.int64)
+        if not isinstance(ids, torch.Tensor):
+            raise TypeError(f"ids must be a tensor, an ndarray or a list, got {type(ids).__name__}")
+        if ndim == 2 and ids.dim() == 1:
+            ids = ids.unsqueeze(0)
+        _int64_ids(ids, ndim)
+        if ids.numel():
+            lo, hi = int(ids.min()), int(ids.max())
+            n = self._n_rows()
+            if lo < -1 or hi >= n:
+                raise IndexError(f"document id {lo if lo < -1 else hi} out of range [-1, {n})")
+        return ids
+
+    def _on_gpu(self, x, gpu, dtype=None):
+        if x is None:
+            return None
+        if isinstance(x, np.ndarray):
+            x = torch.from_numpy(x)
+        x = x.detach().to(gpu)
+        if dtype is not None:
+            x = x.to(dtype)
+        return x.contiguous()
+
+    def _to_api(self, t):
+        return t if torch.device(self.device).type == "cuda" else t.cpu()
+
+    def get_vectors(self, ids):
+        """The stored vectors of documents ids (int64 [n]) -- what ``index.vector[ids]`` gives the reference, read from the device rows
+        without exporting the index: a sparse / bag-of-token index gives a torch sparse-CSR [n, V], a dense Index a dense [n, V], in the
+        index dtype, columns in the vector's space (no shift).  Id -1 gives an empty row; an id outside [-1, N) raises IndexError."""
+        ids = self._example_ids(ids, 1)
+        target, gpu_ord = self._explain_target()
+        gpu = torch.device("cuda", gpu_ord)
+        if self.index_type == IndexType.DENSE:
+            rows = target.queries_from_rows(ids.to(gpu).unsqueeze(1).contiguous())       # (0 + 1 * v: the stored values, exactly)
+            return self._to_api(rows.to(self._dtype))
+        indptr, indices, values = target.get_rows(ids.to(gpu).contiguous())
+        t = torch.sparse_csr_tensor(indptr, indices.to(torch.int64), values.to(self._dtype), size=(int(ids.numel()), int(self._vector_meta()[0][1])))
+        return self._to_api(t)
+
+    def queries_from_rows(self, ids, weights=None, q=None, alpha: float = 1.0):
+        """Queries [B, V] (fp32) built from stored rows: fl32(alpha * q[b]) plus fl32(weights[b, j] * vector[ids[b, j]]) for j in order,
+        every add rounded to fp32 (id -1 adds nothing).  ids: int64 [B, m] (or [m]: one query); weights [B, m] (default 1); q [B, V]."""
+        return self._to_api(self._queries_from_rows(ids, weights, q, alpha)[0])
+
+    def _queries_from_rows(self, ids, weights, q, alpha):
+        ids = self._example_ids(ids, 2)
+        if weights is not None and not isinstance(weights, (torch.Tensor, np.ndarray)):
+            weights = torch.as_tensor(weights, dtype=torch.float32)
+        w = self._on_gpu(weights, "cpu", torch.float32)
+        if w is not None and w.dim() == 1:
+            w = w.unsqueeze(0)
+        qc = None
+        if q is not None:
+            qc = q if isinstance(q, torch.Tensor) else torch.from_numpy(np.asarray(q))
+            qc = qc.detach()
+            if qc.dim() == 1:
+                qc = qc.unsqueeze(0)
+            if qc.dtype not in (torch.float32, torch.float16):
+                qc = qc.float()
+        _by_example_args(ids.cpu(), w, qc.cpu() if qc is not None else None)  # (argument errors before any device work)
+        target, gpu_ord = self._explain_target()
+        gpu = torch.device("cuda", gpu_ord)
+        ids = self._on_gpu(ids, gpu)
+        out = target.queries_from_rows(ids, weights=self._on_gpu(w, gpu), q=self._on_gpu(qc, gpu), alpha=float(alpha))
+        return out, ids, gpu_ord
+
+    def search_by_example(self, ids, k: int, weights=None, q=None, alpha: float = 1.0, a: Optional[int] = None, exclude: bool = True,
+                          filter=None) -> SearchResults:
+        """Search with stored documents as queries (more-like-this, relevance feedback): the queries of ``queries_from_rows``, cut to
+        their `a` largest entries when `a` is given, searched for the top k.  exclude=True leaves each query's own example ids out of its
+        results (exact: the search takes k + m and drops them); exclude=False is exactly ``search(queries_from_rows(...), k)``.
+        filter: as ``search``.  Fewer than k rows left: id -1, score -inf."""
+        _k_a_args(k, a)
+        qq, ids, gpu_ord = self._queries_from_rows(ids, weights, q, alpha)
+        if a is not None:
+            qq = resparsify(qq, int(a), gpu_ord)
+        k = int(k)
+        if not exclude:
+            return self.search(qq, k, filter=filter)
+        n = self._n_rows()
+        kk = min(k + int(ids.shape[1]), n) if k <= n else k
+        res = self.search(qq, kk, filter=filter)
+        gpu = torch.device("cuda", gpu_ord)
+        out_ids, out_sc = topk_exclude(res.ids.to(gpu).contiguous(), res.scores.to(gpu).float().contiguous(), ids, k, gpu_ord)
+        return SearchResults(self._to_api(out_ids), self._to_api(out_sc.to(self._dtype)))
 
     # ---- persistence -------------------------------------------------------------------------------
     def save(self, path):

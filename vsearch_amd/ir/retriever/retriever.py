@@ -103,6 +103,45 @@ class Retriever(BiEncoder):
             out.append(row)
         return out
 
+    def more_like_this(self, ids, k: int = 5, exclude: bool = True, filter=None, a: int = None, index: Index = None) -> SearchResults:
+        """Documents like the given ones, with no encoder: ids [B] (one query per document) or [B, m] (the sum of m documents' rows a
+        query) are searched as queries (Index.search_by_example); `exclude` leaves each query's own documents out of its hits, `a` keeps
+        only the a largest entries of each query."""
+        index = index or self.index
+        if index is None:
+            raise RuntimeError("no index: call build_index / load_index first")
+        if isinstance(ids, (list, tuple)):
+            ids = torch.as_tensor(ids, dtype=torch.int64)
+        elif isinstance(ids, np.ndarray):
+            ids = torch.from_numpy(ids)
+        if isinstance(ids, T) and ids.dim() == 1:
+            ids = ids.unsqueeze(1)
+        return index.search_by_example(ids, k, a=a, exclude=exclude, filter=filter)
+
+    def retrieve_with_feedback(self, queries: Union[List[str], np.ndarray, T], k: int = 5, fb_docs: int = 10, fb_weight: float = 0.75,
+                               a: int = None, filter=None, rerank: bool = False, batch_size: int = 32, index: Index = None) -> SearchResults:
+        """Rocchio pseudo-relevance feedback: retrieve the top `fb_docs` hits of each query, form q' = q + (fb_weight / m_b) * (sum of
+        their stored rows) -- m_b the query's real (non-padding) hits; every add rounded to fp32, Index.queries_from_rows --, keep the `a`
+        largest entries of q' (default: the encoder's topk, so q' costs what an encoded query costs) and search the top k.  The feedback
+        documents stay eligible.  `filter` restricts both searches; `rerank` as in ``retrieve`` (against the original query)."""
+        index = index or self.index
+        if index is None:
+            raise RuntimeError("no index: call build_index / load_index first")
+        a = a or self.encoder_q.config.topk
+        q_emb = self.process_query(queries, 0, a, batch_size=batch_size)
+        if q_emb.dim() == 1:
+            q_emb = q_emb.unsqueeze(0)
+        first = index.search(q_emb, k=fb_docs, filter=filter) if filter is not None else index.search(q_emb, k=fb_docs)
+        fb_ids = first.ids
+        m_b = (fb_ids >= 0).sum(dim=1, keepdim=True).clamp(min=1).to(torch.float64)
+        w = (float(fb_weight) / m_b).to(torch.float32).expand(fb_ids.shape).contiguous()
+        q_fb = index.queries_from_rows(fb_ids, weights=w, q=q_emb, alpha=1.0)
+        q_fb = q_fb.masked_fill(~sp.build_topk_mask(q_fb, k=int(a)), 0.0)
+        results = index.search(q_fb, k=k, filter=filter) if filter is not None else index.search(q_fb, k=k)
+        if rerank and index.index_type == IndexType.BAG_OF_TOKEN:
+            results = self._rerank(index, q_emb, results, k, batch_size)
+        return results
+
     def _rerank(self, index: Index, q_emb: T, results: SearchResults, k: int, batch_size: int) -> SearchResults:
         """Re-embed the k hits with encoder_p, score against q, re-sort (retriever.py:137-147) -- on the device:
         ``vs_rerank_scores`` per re-embedding batch (the reference's dense [B*k, V] tensor is never held) and
