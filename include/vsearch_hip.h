@@ -97,6 +97,8 @@ typedef struct vs_index_info_t {
                               * -1 = no copy                                                                                     */
     int32_t last_packed_tiles; /* path 3 on bag-of-token chunks: query tiles of the most recent search() that took the packed walk (four slots
                               * on 16-bit sums, option "postings_packed"); the other tiles ran two int32 slots each                     */
+    int64_t n_live;          /* rows not deleted (vs_index_delete_rows): n_rows on a handle without tombstones.  The count lives on the device:
+                              * reading it synchronises once the handle has tombstones                                                     */
 } vs_index_info_t;
 
 /* ---- library ------------------------------------------------------------------------------- */
@@ -238,6 +240,44 @@ VS_API int vs_index_queries_from_rows(vs_index* index, const int64_t* ids, int32
 VS_API int vs_topk_exclude(const int64_t* ids, const float* scores, int32_t B, int32_t kk, int64_t ld, const int64_t* excl, int32_t m,
                            int64_t ld_excl, int32_t k, int64_t* out_ids, float* out_scores, int device, void* stream);
 
+/* ---- mutable index: delete, restore, compact (no reference counterpart: the reference rebuilds its tensor, index.py:163-179) -------------
+ * Deletion state lives IN THE HANDLE: a bitmap of live rows (uint32 words, the bit layout of vs_index_search_filtered), allocated by the first
+ * deletion and covering the handle's row capacity.
+ *   - A handle on which nothing was ever deleted (or whose rows were all restored with ids == NULL) behaves exactly as before: the same
+ *     kernels, the same results, the same .vsx bytes.
+ *   - With tombstones, vs_index_search / vs_index_search_filtered / vs_shard_group_search* return what vs_index_search_filtered returns for
+ *     the bitmap (live AND the caller's filter): bit for bit, canonical order, id -1 / score -inf behind fewer than k live (and allowed)
+ *     rows.  No score changes: deletion only gates candidate admission.  k > n_rows (STORED rows) stays VS_ERANGE.  Without a caller's filter
+ *     the kernels read the live bitmap itself; with one, a kernel in front of the search, on the same stream, writes live & filter into
+ *     scratch of the handle (B x n_rows / 8 bytes for a per-query filter: VS_ENOMEM when that does not fit).
+ *   - Row ids do not move.  vs_index_explain, vs_index_get_rows, vs_index_queries_from_rows, vs_index_export_csr, vs_index_scores still read a
+ *     deleted row: it stays stored until vs_index_compact, and vs_index_restore_rows depends on that.
+ *   - vs_index_append_csr after deletions: the new rows are live.  vs_index_slice_rows carries the slice's bits over.
+ *   - vs_index_save_native writes the bitmap behind the three arrays (flagged in the header) when rows are deleted, vs_index_load_native reads
+ *     it back; a handle without deleted rows writes the file it always wrote.  vs_index_save_npz of a handle with deleted rows: VS_EINVAL
+ *     ("compact first") -- an .npz cannot record them and a reload would resurrect the rows.
+ * vs_index_delete_rows: clears the live bits of ids [n] (row = id - id_offset).  Id -1 is ignored; any other id outside the index: VS_EINVAL for
+ *   host ids, skipped for device ids (they are not read on the host, as in vs_index_queries_from_rows).  Deleting a row twice -- in one call
+ *   or in two -- counts once.  Host or device ids (device ids on the index's device).  stream as in vs_index_search: NULL blocks; device ids
+ *   and a non-NULL stream only enqueue (the live count stays on the device).
+ * vs_index_restore_rows: sets them again; ids == NULL restores every row.
+ * vs_index_live_rows: rows not deleted; synchronises the device.
+ * vs_index_live_bitmap: the live bits of rows [0, n_rows) into out_words [n_words >= (n_rows + 31) / 32] (host, or device on the index's
+ *   device; bits and words past n_rows are 0): what a caller ANDs with or inspects.  Blocking.                                         */
+VS_API int vs_index_delete_rows(vs_index* index, const int64_t* ids, int64_t n, int64_t id_offset, void* stream);
+VS_API int vs_index_restore_rows(vs_index* index, const int64_t* ids, int64_t n, int64_t id_offset, void* stream);
+VS_API int vs_index_live_rows(const vs_index* index, int64_t* out);
+VS_API int vs_index_live_bitmap(const vs_index* index, uint32_t* out_words, int64_t n_words);
+/* vs_index_compact: a NEW index on GPU `device` holding the live rows of `src` in order, with room for rows_extra more rows and packets_extra
+ *   more 8-nnz packets (vs_index_append_csr).  out_old_ids [live rows] int64 (host, or device on src's device; may be NULL): the row of `src`
+ *   that new row j was.  Packets are copied whole on the device -- stored values and their order inside a row do not change, so scores do
+ *   not either; nnz is recounted.  fp32 / fp16 / binary stores, a dense index stored as packets (still reported VS_KIND_DENSE), and the dense
+ *   matrix kind (row gather; no spare capacity, same device only).  A source without tombstones compacts to a copy with the spare capacity:
+ *   that is how an index without reserved room grows.  `src` is untouched and stays the caller's to destroy; the result has no tombstones
+ *   and no postings copy yet (vs_index_prepare).  Source and new index are both resident during the call: VS_ENOMEM (the message names the
+ *   bytes needed) when HBM cannot hold them -- setting option "blocked_postings" to 0 on `src` releases its postings copy.  Blocking.  */
+VS_API int vs_index_compact(const vs_index* src, int64_t rows_extra, int64_t packets_extra, int device, vs_index** out, int64_t* out_old_ids);
+
 /* Dense score matrix [B, n_rows] fp32 -- the intermediate index.py:91 materialises.  Used by the
  * parity tests to check every score, not just the top-k.                                         */
 VS_API int vs_index_scores(vs_index* index, const void* q, int q_dtype, int64_t ldq, int32_t B,
@@ -335,6 +375,11 @@ VS_API int  vs_shard_group_get_rows(vs_shard_group* group, const int64_t* ids, i
 VS_API int  vs_shard_group_queries_from_rows(vs_shard_group* group, const int64_t* ids, int32_t B, int32_t m, int64_t ld_ids,
                                              const float* weights, int64_t ldw, const void* q, int q_dtype, int64_t ldq, float alpha,
                                              float* out_q, int64_t ldo);
+/* vs_index_delete_rows / vs_index_restore_rows over the group's rows: ids [n] are global, every shard clears / sets the bits of the rows it
+ * owns.  Id -1 ignored; another id outside [0, total rows): VS_EINVAL for host ids, skipped for device ids (any GPU; they are copied to the
+ * host).  vs_shard_group_restore_rows with ids == NULL restores every row.  Blocking.                                                  */
+VS_API int  vs_shard_group_delete_rows(vs_shard_group* group, const int64_t* ids, int64_t n);
+VS_API int  vs_shard_group_restore_rows(vs_shard_group* group, const int64_t* ids, int64_t n);
 VS_API void vs_shard_group_destroy(vs_shard_group* group);
 
 /* SparseIndex.save (index.py:181-202) needs crow/col/values back: int64 rowptr [n_rows+1], int64

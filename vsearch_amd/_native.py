@@ -29,7 +29,7 @@ class IndexInfo(C.Structure):
                 ("bytes_per_pass", C.c_int64), ("lanes_per_row", C.c_int32), ("queries_per_pass", C.c_int32),
                 ("last_scan_bytes", C.c_int64), ("aux_bytes", C.c_int64), ("last_path", C.c_int32), ("last_fallbacks", C.c_int32),
                 ("last_walk_postings", C.c_int64), ("head_columns", C.c_int32), ("postings_state", C.c_int32),
-                ("postings_walk", C.c_int32), ("last_packed_tiles", C.c_int32)]
+                ("postings_walk", C.c_int32), ("last_packed_tiles", C.c_int32), ("n_live", C.c_int64)]
 
 
 _vp, _i32, _i64, _int = C.c_void_p, C.c_int32, C.c_int64, C.c_int
@@ -56,6 +56,11 @@ _SIGNATURES = {
     "vs_index_explain": ([_vp, _vp, _int, _i64, _i32, _vp, _i64, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp], _int),
     "vs_index_get_rows": ([_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp], _int),
     "vs_index_queries_from_rows": ([_vp, _vp, _i32, _i32, _i64, _vp, _i64, _vp, _int, _i64, C.c_float, _vp, _i64, _vp], _int),
+    "vs_index_delete_rows": ([_vp, _vp, _i64, _i64, _vp], _int),
+    "vs_index_restore_rows": ([_vp, _vp, _i64, _i64, _vp], _int),
+    "vs_index_live_rows": ([_vp, C.POINTER(_i64)], _int),
+    "vs_index_live_bitmap": ([_vp, _vp, _i64], _int),
+    "vs_index_compact": ([_vp, _i64, _i64, _int, C.POINTER(_vp), _vp], _int),
     "vs_index_prepare": ([_vp, _vp], _int),
     "vs_index_info": ([_vp, C.POINTER(IndexInfo)], _int),
     "vs_index_set_option": ([_vp, C.c_char_p, _int], _int),
@@ -69,6 +74,8 @@ _SIGNATURES = {
     "vs_shard_group_explain": ([_vp, _vp, _int, _i64, _i32, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp], _int),
     "vs_shard_group_get_rows": ([_vp, _vp, _i64, _vp, _vp, _vp], _int),
     "vs_shard_group_queries_from_rows": ([_vp, _vp, _i32, _i32, _i64, _vp, _i64, _vp, _int, _i64, C.c_float, _vp, _i64], _int),
+    "vs_shard_group_delete_rows": ([_vp, _vp, _i64], _int),
+    "vs_shard_group_restore_rows": ([_vp, _vp, _i64], _int),
     "vs_shard_group_destroy": ([_vp], None),
     "vs_merge_topk": ([_vp, _vp, _i32, _i64, _i32, _vp, _vp, _int, _vp], _int),
     "vs_topk_exclude": ([_vp, _vp, _i32, _i32, _i64, _vp, _i32, _i64, _i32, _vp, _vp, _int, _vp], _int),

@@ -1,6 +1,7 @@
 // api.hip -- library-level entry points and the kind dispatch of Index.search (index.py:88-94).
 #include "common.h"
 
+#include <algorithm>
 #include <string>
 
 using namespace vs;
@@ -41,8 +42,13 @@ extern "C" int vs_index_search(vs_index* idx, const void* q, int q_dtype, int64_
     if (k > idx->n_rows) return fail(VS_ERANGE, "selected index k out of range (k = %d > %lld rows)", k, (long long)idx->n_rows);
     VS_HIP(hipSetDevice(idx->device));
     hipStream_t s = (hipStream_t)stream;
+    // a handle with tombstones (mutable.hip) searches under live AND the caller's filter: the FL = 1 kernels of a filtered search.  Without
+    // tombstones nothing changes here: idx->filt is what vs_index_search_filtered set, or none
+    const FilterArgs user = idx->filt;
+    if (idx->has_tomb) VS_TRY(tomb_effective_filter(idx, user, B, s, &idx->filt));
     int rc = idx->kind == VS_KIND_CSR ? vs_csr_search(idx, q, q_dtype, ldq, B, k, id_offset, out_ids, out_scores, s)
                                       : vs_dense_search(idx, q, q_dtype, ldq, B, k, id_offset, out_ids, out_scores, s);
+    idx->filt = user;
     if (rc != VS_OK) return rc;
     if (!stream) VS_HIP(hipStreamSynchronize(s));
     if (Profiler::get().on) Profiler::get().drain();
@@ -458,6 +464,46 @@ extern "C" int vs_shard_group_search_filtered(vs_shard_group* g, const void* q, 
     return shard_group_search(g, q, q_dtype, ldq, B, k, filter, filter_ld, out_ids, out_scores);
 }
 
+// Deletion over the group's rows: the global ids are dealt to their owners on the host (device ids are read back first), every shard
+// clears / sets its own bits.  Blocking, like every call of the group.
+static int shard_group_tombstones(vs_shard_group* g, const int64_t* ids, int64_t n, bool del) {
+    if (!g) return fail(VS_EINVAL, "NULL argument");
+    if (n < 0 || (n > 0 && !ids && del)) return fail(VS_EINVAL, "bad ids / n");
+    const int ns = (int)g->shards.size();
+    if (!ids) {                                                            // restore everything
+        for (int i = 0; i < ns; ++i) VS_TRY(vs_index_restore_rows(g->shards[i], nullptr, 0, 0, nullptr));
+        return VS_OK;
+    }
+    std::vector<int64_t> host;
+    const bool dev = is_device_ptr(ids);
+    if (dev && n > 0) {
+        hipPointerAttribute_t attr;
+        VS_HIP(hipPointerGetAttributes(&attr, ids));
+        VS_HIP(hipSetDevice(attr.device));
+        VS_HIP(hipDeviceSynchronize());
+        host.resize((size_t)n);
+        VS_HIP(hipMemcpy(host.data(), ids, (size_t)n * 8, hipMemcpyDeviceToHost));
+        ids = host.data();
+    }
+    std::vector<std::vector<int64_t>> mine((size_t)ns);
+    for (int64_t j = 0; j < n; ++j) {
+        const int64_t id = ids[j];
+        if (id == -1) continue;
+        if (id < 0 || id >= g->n_total) {
+            if (dev) continue;                                             // (device ids are not checked: skipped, as in vs_index_delete_rows)
+            return fail(VS_EINVAL, "document id %lld is outside [-1, %lld)", (long long)id, (long long)g->n_total);
+        }
+        int i = (int)(std::upper_bound(g->row0.begin(), g->row0.end(), id) - g->row0.begin()) - 1;
+        mine[(size_t)i].push_back(id);
+    }
+    for (int i = 0; i < ns; ++i) {
+        if (mine[(size_t)i].empty()) continue;
+        VS_TRY(del ? vs_index_delete_rows(g->shards[i], mine[(size_t)i].data(), (int64_t)mine[(size_t)i].size(), g->row0[i], nullptr)
+                   : vs_index_restore_rows(g->shards[i], mine[(size_t)i].data(), (int64_t)mine[(size_t)i].size(), g->row0[i], nullptr));
+    }
+    return VS_OK;
+}
+
 // (explain.hip: every shard explains the pairs of its row range on its own device, the first shard's device gathers them)
 int vs_shard_group_explain_impl(const std::vector<vs_index*>& shards, const std::vector<int64_t>& row0, const std::vector<hipStream_t>& streams,
                                 const void* q, int q_dtype, int64_t ldq, int32_t B, const int64_t* ids, int64_t ld_ids, int32_t k, int32_t topn,
@@ -496,6 +542,16 @@ extern "C" int vs_shard_group_queries_from_rows(vs_shard_group* g, const int64_t
     VS_TRY(group_need_device());
     if (!g) return fail(VS_EINVAL, "NULL argument");
     return vs_shard_group_queries_from_rows_impl(g->shards, g->row0, g->streams, ids, B, m, ld_ids, weights, ldw, q, q_dtype, ldq, alpha, out_q, ldo);
+}
+
+extern "C" int vs_shard_group_delete_rows(vs_shard_group* g, const int64_t* ids, int64_t n) {
+    VS_TRY(group_need_device());
+    return shard_group_tombstones(g, ids, n, true);
+}
+
+extern "C" int vs_shard_group_restore_rows(vs_shard_group* g, const int64_t* ids, int64_t n) {
+    VS_TRY(group_need_device());
+    return shard_group_tombstones(g, ids, n, false);
 }
 
 extern "C" int vs_profile_enable(int on) {

@@ -228,6 +228,14 @@ inline bool debug_sync_on() {
         }                                                                                             \
     } while (0)
 
+// ---- mutable.hip: tombstones ------------------------------------------------------------------
+// the filter a search on a handle with tombstones runs under: live (no user filter) or live AND user (written to the handle's scratch on `s`)
+int tomb_effective_filter(vs_index* idx, const FilterArgs& user, int32_t B, hipStream_t s, FilterArgs* out);
+int tomb_dead_count(const vs_index* idx, int64_t* out);                               // rows deleted at present (synchronises when there are tombstones)
+int tomb_from_bits(vs_index* dst, const vs_index* src, int64_t row0);                 // dst's tombstones = src's bits [row0, row0 + dst->n_rows) (vs_index_slice_rows)
+int tomb_from_host(vs_index* idx, const uint32_t* words);                             // tombstones from (n_rows + 31) / 32 host words (vs_index_load_native)
+int tomb_to_host(const vs_index* idx, std::vector<uint32_t>& words);                  // the words vs_index_save_native writes
+
 inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline uint32_t pow2_ceil(uint32_t x) {
@@ -311,6 +319,11 @@ struct vs_index {
     vs::DevBuf ws_filt;           // a host filter's bitmap staged on the device
     vs::FilterArgs filt{};        // the document filter of the search in progress (vs_index_search_filtered; words == nullptr: none)
     bool logical_dense = false;   // dense Index stored as CSR packets (sparsity-aware dense index)
+    // tombstones (mutable.hip): deletion state of the handle, applied by every search as a document filter
+    vs::DevBuf live;              // uint32 words, bit r set = row r is live; covers max(rows_cap, n_rows) rows; allocated by the first deletion (all ones)
+    vs::DevBuf dead_cnt;          // int64 [1] on the device: rows deleted at present (n_live = n_rows - it)
+    bool has_tomb = false;        // `live` may hold cleared bits: searches take the FL = 1 kernels with it (false again after "restore all")
+    vs::DevBuf ws_live;           // grow-only: live AND the user's filter of the search in progress, re-based to bit 0
     int qt_pref = 0;     // 0 = auto (multi-query pass when the batch qualifies), 1 = force the dense-image pass
     int last_qt = 0;     // queries per pass of the most recent search
     int cu_count = 256;

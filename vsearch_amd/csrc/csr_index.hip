@@ -423,6 +423,7 @@ extern "C" int vs_index_slice_rows(const vs_index* src, int64_t row0, int64_t n_
     idx->nnz = (int64_t)nnz;
     idx->logical_dense = src->logical_dense;
     idx->lanes_per_row = pick_lanes_per_row(idx->n_packets, idx->n_rows);
+    VS_TRY(tomb_from_bits(idx, src, row0));                   // the slice's rows keep their deletion state
     guard.p = nullptr;
     *out = idx;
     return VS_OK;
@@ -531,6 +532,11 @@ extern "C" int vs_index_info(const vs_index* idx, vs_index_info_t* o) {
     o->postings_state = idx->bp_ready ? 1 : idx->bp_state;
     o->postings_walk = !idx->bp_ready ? -1 : idx->bp_quad ? 4 : idx->bp_bq ? 6 : (idx->store_dtype == VS_NONE && idx->bp_walk_pref != 0) ? 5 : 0;
     o->last_packed_tiles = 0;
+    {
+        int64_t dead = 0;
+        VS_TRY(tomb_dead_count(idx, &dead));                   // (kept on the device: synchronises when the handle has tombstones)
+        o->n_live = idx->n_rows - dead;
+    }
     if (idx->last_path == 3 && idx->last_plan_dev) {               // the filter search keeps its plan on the device: read it now
         int64_t hp[6] = {0, 0, 0, 0, 0, 0};
         VS_HIP(hipSetDevice(idx->device));
@@ -1057,10 +1063,21 @@ extern "C" int vs_index_save_native(const vs_index* idx, const char* path) {
     h.n_packets = idx->n_packets;
     h.nnz = idx->nnz;
     h.reserved[0] = idx->logical_dense ? 1 : 0;
+    // tombstones: reserved[1] = 1 and the live bitmap ((n_rows + 31) / 32 words) behind the three arrays.  A handle without deleted rows
+    // writes the file it always wrote
+    std::vector<uint32_t> live_bits;
+    {
+        int64_t dead = 0;
+        int rc0 = tomb_dead_count(idx, &dead);
+        if (rc0 == VS_OK && dead > 0) rc0 = tomb_to_host(idx, live_bits);
+        if (rc0 != VS_OK) { fclose(f); return rc0; }
+        if (dead > 0) h.reserved[1] = 1;
+    }
     int rc = fwrite(&h, sizeof(h), 1, f) == 1 ? VS_OK : fail(VS_EINVAL, "short write");
     if (rc == VS_OK) rc = copy_dev_to_file(f, idx->pk_ptr.p, (size_t)(idx->n_rows + 1) * 4);
     if (rc == VS_OK) rc = copy_dev_to_file(f, idx->cols.p, (size_t)idx->n_packets * 16);
     if (rc == VS_OK && idx->store_dtype != VS_NONE) rc = copy_dev_to_file(f, idx->vals.p, (size_t)idx->n_packets * (idx->store_dtype == VS_F32 ? 32 : 16));
+    if (rc == VS_OK && !live_bits.empty() && fwrite(live_bits.data(), 4, live_bits.size(), f) != live_bits.size()) rc = fail(VS_EINVAL, "short write");
     fclose(f);
     return rc;
 }
@@ -1077,14 +1094,15 @@ extern "C" int vs_index_load_native(const char* path, int device, vs_index** out
     if (h.n_packets < 0 || h.n_packets >= (1ll << 32) || h.nnz < 0 || h.nnz > h.n_packets * 8) return fail(VS_EINVAL, "corrupt header");
     // the payload must be exactly what the header announces
     const size_t b_ptr = (size_t)(h.n_rows + 1) * 4, b_cols = (size_t)h.n_packets * 16,
-                 b_vals = h.store_dtype == VS_NONE ? 0 : (size_t)h.n_packets * (h.store_dtype == VS_F32 ? 32 : 16);
+                 b_vals = h.store_dtype == VS_NONE ? 0 : (size_t)h.n_packets * (h.store_dtype == VS_F32 ? 32 : 16),
+                 b_live = h.reserved[1] == 1 ? (size_t)((h.n_rows + 31) / 32) * 4 : 0;       // tombstones (vs_index_save_native)
     {
         const long here = ftell(f);
         if (fseek(f, 0, SEEK_END) != 0) return fail(VS_EINVAL, "cannot seek in %s", path);
         const long long end = ftell(f);
         if (fseek(f, here, SEEK_SET) != 0) return fail(VS_EINVAL, "cannot seek in %s", path);
-        if ((unsigned long long)end != sizeof(h) + b_ptr + b_cols + b_vals)
-            return fail(VS_EINVAL, "%s: %lld bytes on disk, the header announces %zu (truncated or mismatched file)", path, end, sizeof(h) + b_ptr + b_cols + b_vals);
+        if ((unsigned long long)end != sizeof(h) + b_ptr + b_cols + b_vals + b_live)
+            return fail(VS_EINVAL, "%s: %lld bytes on disk, the header announces %zu (truncated or mismatched file)", path, end, sizeof(h) + b_ptr + b_cols + b_vals + b_live);
     }
     vs_index* idx = nullptr;
     VS_TRY(vs_index_create_reserved(h.n_rows, h.n_packets, h.n_cols, h.store_dtype, device, &idx));
@@ -1124,6 +1142,11 @@ extern "C" int vs_index_load_native(const char* path, int device, vs_index** out
     idx->nnz = h.nnz;
     idx->logical_dense = h.reserved[0] == 1;
     idx->lanes_per_row = pick_lanes_per_row(idx->n_packets, idx->n_rows);
+    if (b_live) {
+        std::vector<uint32_t> live_bits(b_live / 4);
+        if (fread(live_bits.data(), 1, b_live, f) != b_live) return fail(VS_EINVAL, "short read: truncated .vsx file");
+        VS_TRY(tomb_from_host(idx, live_bits.data()));
+    }
     guard.p = nullptr;
     *out = idx;
     return VS_OK;

@@ -1,0 +1,604 @@
+// mutable.hip -- the writable index: tombstones kept in the handle (delete / restore rows, applied by every search as a document filter)
+// and compaction (a new index of the live rows, with spare capacity for appends).  No reference counterpart: the reference's index is
+// a tensor that is rebuilt (index.py:163-179).  Nothing here touches a walk or scan kernel: deletion reaches them as FilterArgs.
+#include "common.h"
+
+#include <algorithm>
+
+using namespace vs;
+
+namespace {
+
+int need_device() {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+        (void)hipGetLastError();
+        return fail(VS_ENODEVICE, "no HIP device visible: libvsearch_hip has no CPU fallback");
+    }
+    return VS_OK;
+}
+
+int64_t bit_words(int64_t rows) { return (rows + 31) >> 5; }
+// words of the handle's live bitmap: the rows it can ever hold, rounded to whole 16-byte quads (the AND kernel reads and writes quads)
+int64_t live_words(const vs_index* idx) { return (bit_words(std::max(idx->rows_cap, idx->n_rows)) + 3) / 4 * 4; }
+
+// ---- bit clear / set from an id list: one thread an id; the dead count moves by what the atomic found (duplicates count once) --------
+template <int DEL>
+__global__ __launch_bounds__(256) void tomb_update_kernel(const int64_t* ids, int64_t n, int64_t id_offset, int64_t n_rows, uint32_t* live,
+                                                          unsigned long long* dead) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const int64_t id = ids[i], row = id - id_offset;
+        if (id == -1 || row < 0 || row >= n_rows) continue;              // (never dereferenced: not a row of this index)
+        const uint32_t bit = 1u << (row & 31);
+        if (DEL) {
+            const uint32_t old = atomicAnd(&live[row >> 5], ~bit);
+            if (old & bit) atomicAdd(dead, 1ull);
+        } else {
+            const uint32_t old = atomicOr(&live[row >> 5], bit);
+            if (!(old & bit)) atomicAdd(dead, ~0ull);                     // (- 1)
+        }
+    }
+}
+
+// ---- effective filter: out[b][w] = live[w] & (user bitmap of query b from bit `bit0` on), re-based to bit 0 --------------------------
+// A lane takes four output words (16-byte load of `live`, 16-byte store); the user's words start at an arbitrary word and bit -- a shard of
+// a group reads the global bitmap from its first row -- so five neighbouring words are funnel-shifted into four.  live == nullptr: all
+// ones (a plain re-base).  Words of the user's bitmap past `span` (what it is promised to hold) are not read.
+struct AndArgs {
+    const uint32_t* live;
+    const uint32_t* user;
+    int64_t user_ld, bit0, span;
+    uint32_t* out;
+    int64_t out_ld, n_quads;
+};
+__global__ __launch_bounds__(256) void live_and_kernel(AndArgs a) {
+    const uint32_t* u = a.user + (size_t)blockIdx.y * (size_t)a.user_ld;
+    uint4* o = reinterpret_cast<uint4*>(a.out + (size_t)blockIdx.y * (size_t)a.out_ld);
+    const int64_t w0 = a.bit0 >> 5;
+    const uint32_t sh = (uint32_t)(a.bit0 & 31);
+    for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < a.n_quads; q += (int64_t)gridDim.x * 256) {
+        uint4 lv = make_uint4(~0u, ~0u, ~0u, ~0u);
+        if (a.live) lv = reinterpret_cast<const uint4*>(a.live)[q];
+        uint32_t x[5];
+#pragma unroll
+        for (int i = 0; i < 5; ++i) {
+            const int64_t w = w0 + 4 * q + i;
+            x[i] = w < a.span ? u[w] : 0u;
+        }
+        uint4 r;
+        r.x = lv.x & __funnelshift_r(x[0], x[1], sh);
+        r.y = lv.y & __funnelshift_r(x[1], x[2], sh);
+        r.z = lv.z & __funnelshift_r(x[2], x[3], sh);
+        r.w = lv.w & __funnelshift_r(x[3], x[4], sh);
+        o[q] = r;
+    }
+}
+
+// set bits among rows [0, n_rows) of a bitmap
+__global__ __launch_bounds__(256) void count_bits_kernel(const uint32_t* words, int64_t n_rows, unsigned long long* out) {
+    const int64_t nw = (n_rows + 31) >> 5;
+    unsigned long long c = 0;
+    for (int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x; w < nw; w += (int64_t)gridDim.x * 256) {
+        uint32_t v = words[w];
+        if (w == nw - 1 && (n_rows & 31)) v &= (1u << (n_rows & 31)) - 1u;
+        c += __popc(v);
+    }
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
+    if ((threadIdx.x & 63) == 0 && c) atomicAdd(out, c);
+}
+
+// the bitmap a caller inspects: bits of rows [0, n_rows), zeros behind them (live == nullptr: every row live)
+__global__ __launch_bounds__(256) void live_out_kernel(const uint32_t* live, int64_t n_rows, uint32_t* out, int64_t n_words) {
+    const int64_t nw = (n_rows + 31) >> 5;
+    for (int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x; w < n_words; w += (int64_t)gridDim.x * 256) {
+        uint32_t v = w < nw ? (live ? live[w] : ~0u) : 0u;
+        if (w == nw - 1 && (n_rows & 31)) v &= (1u << (n_rows & 31)) - 1u;
+        out[w] = v;
+    }
+}
+
+unsigned grid_for(int64_t items, int per_block = 256, int64_t cap = 8192) {
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((items + per_block - 1) / per_block, cap));
+}
+
+// the handle's bitmap, allocated on the first deletion: every row (and every row still to be appended) live
+int ensure_live(vs_index* idx, hipStream_t s) {
+    const size_t bytes = (size_t)live_words(idx) * 4;
+    if (idx->live.p && idx->live.bytes >= bytes && idx->dead_cnt.p) return VS_OK;
+    VS_TRY(idx->live.alloc(std::max<size_t>(bytes, 16)));
+    VS_TRY(idx->dead_cnt.alloc(8));
+    VS_HIP(hipMemsetAsync(idx->live.p, 0xFF, idx->live.bytes, s));
+    VS_HIP(hipMemsetAsync(idx->dead_cnt.p, 0, 8, s));
+    return VS_OK;
+}
+
+int ptr_on(const void* p, int device, const char* what) {
+    if (!is_device_ptr(p)) return VS_OK;
+    hipPointerAttribute_t attr;
+    VS_HIP(hipPointerGetAttributes(&attr, p));
+    if (attr.device != device) return fail(VS_EINVAL, "%s lives on device %d, the index on device %d", what, attr.device, device);
+    return VS_OK;
+}
+
+int tomb_update(vs_index* idx, const int64_t* ids, int64_t n, int64_t id_offset, void* stream, bool del) {
+    VS_TRY(need_device());
+    if (!idx) return fail(VS_EINVAL, "NULL index");
+    if (n < 0) return fail(VS_EINVAL, "n must be >= 0");
+    if (!ids && n > 0 && del) return fail(VS_EINVAL, "ids is NULL");
+    VS_HIP(hipSetDevice(idx->device));
+    hipStream_t s = (hipStream_t)stream;
+    if (!del && !ids) {                                        // restore all: the bitmap is kept for the next deletion, searches go back to FL = 0
+        if (idx->live.p) {
+            VS_HIP(hipMemsetAsync(idx->live.p, 0xFF, idx->live.bytes, s));
+            VS_HIP(hipMemsetAsync(idx->dead_cnt.p, 0, 8, s));
+        }
+        idx->has_tomb = false;
+        if (!stream) VS_HIP(hipStreamSynchronize(s));
+        return VS_OK;
+    }
+    if (n == 0) return VS_OK;
+    const bool dev_ids = is_device_ptr(ids);
+    if (dev_ids) VS_TRY(ptr_on(ids, idx->device, "ids"));
+    else
+        for (int64_t i = 0; i < n; ++i) {
+            const int64_t row = ids[i] - id_offset;
+            if (ids[i] != -1 && (row < 0 || row >= idx->n_rows))
+                return fail(VS_EINVAL, "document id %lld is outside [%lld, %lld)", (long long)ids[i], (long long)id_offset, (long long)(id_offset + idx->n_rows));
+        }
+    if (!del && !idx->live.p) return VS_OK;                    // nothing was ever deleted
+    VS_TRY(ensure_live(idx, s));
+    DevBuf stage;
+    const void* d_ids = nullptr;
+    VS_TRY(to_device(ids, (size_t)n * 8, stage, s, &d_ids));
+    if (del)
+        hipLaunchKernelGGL(tomb_update_kernel<1>, dim3(grid_for(n)), dim3(256), 0, s, (const int64_t*)d_ids, n, id_offset, idx->n_rows, idx->live.as<uint32_t>(),
+                           idx->dead_cnt.as<unsigned long long>());
+    else
+        hipLaunchKernelGGL(tomb_update_kernel<0>, dim3(grid_for(n)), dim3(256), 0, s, (const int64_t*)d_ids, n, id_offset, idx->n_rows, idx->live.as<uint32_t>(),
+                           idx->dead_cnt.as<unsigned long long>());
+    VS_HIP(hipGetLastError());
+    if (del) idx->has_tomb = true;
+    if (!stream || stage.p) VS_HIP(hipStreamSynchronize(s));   // blocking call / the staged ids die here
+    return VS_OK;
+}
+
+}  // namespace
+
+// =================================================================================================
+// what the rest of the library asks of the tombstones (common.h)
+// =================================================================================================
+namespace vs {
+
+int tomb_effective_filter(vs_index* idx, const FilterArgs& user, int32_t B, hipStream_t s, FilterArgs* out) {
+    if (!idx->has_tomb) { *out = user; return VS_OK; }
+    if (!user.words) {                                         // the live bitmap itself: no copy
+        *out = FilterArgs{idx->live.as<uint32_t>(), 0, 0};
+        return VS_OK;
+    }
+    AndArgs a;
+    a.live = idx->live.as<uint32_t>();
+    a.user = user.words;
+    a.user_ld = user.ld;
+    a.bit0 = user.bit0;
+    a.span = (user.bit0 + idx->n_rows + 31) >> 5;
+    a.n_quads = (bit_words(idx->n_rows) + 3) / 4;
+    a.out_ld = a.n_quads * 4;
+    const int64_t nb = user.ld > 0 ? B : 1;
+    if (nb > 65535) return fail(VS_EUNSUPPORTED, "a per-query filter on an index with deleted rows takes at most 65535 queries a call (got %d)", B);
+    const size_t bytes = (size_t)nb * (size_t)a.out_ld * 4;
+    if (idx->ws_live.reserve(bytes) != VS_OK)
+        return fail(VS_ENOMEM, "no room for the %zu bytes of (live rows AND filter) of %lld queries x %lld rows: compact the index, or search in smaller batches",
+                    bytes, (long long)nb, (long long)idx->n_rows);
+    a.out = idx->ws_live.as<uint32_t>();
+    hipLaunchKernelGGL(live_and_kernel, dim3(grid_for(a.n_quads, 256, 4096), (unsigned)nb), dim3(256), 0, s, a);
+    VS_HIP(hipGetLastError());
+    *out = FilterArgs{a.out, 0, user.ld > 0 ? a.out_ld : 0};
+    return VS_OK;
+}
+
+int tomb_dead_count(const vs_index* idx, int64_t* out) {
+    *out = 0;
+    if (!idx->has_tomb) return VS_OK;
+    VS_HIP(hipSetDevice(idx->device));
+    VS_HIP(hipDeviceSynchronize());
+    VS_HIP(hipMemcpy(out, idx->dead_cnt.p, 8, hipMemcpyDeviceToHost));
+    return VS_OK;
+}
+
+// after new bits were written into idx->live on the null stream: the dead count they imply
+static int recount(vs_index* idx) {
+    DevBuf cnt;
+    VS_TRY(cnt.alloc(8));
+    VS_HIP(hipMemset(cnt.p, 0, 8));
+    if (idx->n_rows > 0)
+        hipLaunchKernelGGL(count_bits_kernel, dim3(grid_for(bit_words(idx->n_rows))), dim3(256), 0, 0, idx->live.as<uint32_t>(), idx->n_rows,
+                           cnt.as<unsigned long long>());
+    VS_HIP(hipGetLastError());
+    int64_t live = 0;
+    VS_HIP(hipMemcpy(&live, cnt.p, 8, hipMemcpyDeviceToHost));
+    const int64_t dead = idx->n_rows - live;
+    VS_HIP(hipMemcpy(idx->dead_cnt.p, &dead, 8, hipMemcpyHostToDevice));
+    idx->has_tomb = dead > 0;
+    return VS_OK;
+}
+
+int tomb_from_bits(vs_index* dst, const vs_index* src, int64_t row0) {
+    if (!src->has_tomb || dst->n_rows == 0) return VS_OK;
+    // re-based on the source's device (live_and_kernel with no `live` operand), then copied to the new index's
+    VS_HIP(hipSetDevice(src->device));
+    AndArgs a;
+    a.live = nullptr;
+    a.user = src->live.as<uint32_t>();
+    a.user_ld = 0;
+    a.bit0 = row0;
+    a.span = (row0 + dst->n_rows + 31) >> 5;
+    a.n_quads = (bit_words(dst->n_rows) + 3) / 4;
+    a.out_ld = a.n_quads * 4;
+    DevBuf tmp;
+    VS_TRY(tmp.alloc((size_t)a.out_ld * 4));
+    a.out = tmp.as<uint32_t>();
+    hipLaunchKernelGGL(live_and_kernel, dim3(grid_for(a.n_quads, 256, 4096), 1), dim3(256), 0, 0, a);
+    VS_HIP(hipGetLastError());
+    VS_HIP(hipDeviceSynchronize());
+    VS_HIP(hipSetDevice(dst->device));
+    VS_TRY(ensure_live(dst, 0));
+    VS_HIP(hipDeviceSynchronize());
+    if (dst->device == src->device) VS_HIP(hipMemcpy(dst->live.p, tmp.p, (size_t)bit_words(dst->n_rows) * 4, hipMemcpyDeviceToDevice));
+    else VS_HIP(hipMemcpyPeer(dst->live.p, dst->device, tmp.p, src->device, (size_t)bit_words(dst->n_rows) * 4));
+    // (bits past the slice's last row came from the source's next rows: a slice holds exactly its rows, so they are never read or appended to)
+    return recount(dst);
+}
+
+int tomb_from_host(vs_index* idx, const uint32_t* words) {
+    VS_HIP(hipSetDevice(idx->device));
+    VS_TRY(ensure_live(idx, 0));
+    VS_HIP(hipDeviceSynchronize());
+    VS_HIP(hipMemcpy(idx->live.p, words, (size_t)bit_words(idx->n_rows) * 4, hipMemcpyHostToDevice));
+    return recount(idx);
+}
+
+int tomb_to_host(const vs_index* idx, std::vector<uint32_t>& words) {
+    words.assign((size_t)bit_words(idx->n_rows), 0u);
+    if (words.empty()) return VS_OK;
+    VS_HIP(hipSetDevice(idx->device));
+    DevBuf tmp;
+    VS_TRY(tmp.alloc(words.size() * 4));
+    hipLaunchKernelGGL(live_out_kernel, dim3(grid_for((int64_t)words.size())), dim3(256), 0, 0, idx->has_tomb ? idx->live.as<uint32_t>() : nullptr, idx->n_rows,
+                       tmp.as<uint32_t>(), (int64_t)words.size());
+    VS_HIP(hipGetLastError());
+    VS_HIP(hipMemcpy(words.data(), tmp.p, words.size() * 4, hipMemcpyDeviceToHost));
+    return VS_OK;
+}
+
+}  // namespace vs
+
+// =================================================================================================
+// C entry points: delete / restore / live count / live bitmap
+// =================================================================================================
+extern "C" int vs_index_delete_rows(vs_index* idx, const int64_t* ids, int64_t n, int64_t id_offset, void* stream) {
+    VS_TRY(need_device());
+    if (!idx || (!ids && n > 0)) return fail(VS_EINVAL, "NULL argument");
+    return tomb_update(idx, ids, n, id_offset, stream, true);
+}
+
+extern "C" int vs_index_restore_rows(vs_index* idx, const int64_t* ids, int64_t n, int64_t id_offset, void* stream) {
+    VS_TRY(need_device());
+    if (!idx) return fail(VS_EINVAL, "NULL argument");
+    return tomb_update(idx, ids, n, id_offset, stream, false);
+}
+
+extern "C" int vs_index_live_rows(const vs_index* idx, int64_t* out) {
+    VS_TRY(need_device());
+    if (!idx || !out) return fail(VS_EINVAL, "NULL argument");
+    int64_t dead = 0;
+    VS_TRY(tomb_dead_count(idx, &dead));
+    *out = idx->n_rows - dead;
+    return VS_OK;
+}
+
+extern "C" int vs_index_live_bitmap(const vs_index* idx, uint32_t* out_words, int64_t n_words) {
+    VS_TRY(need_device());
+    if (!idx || !out_words) return fail(VS_EINVAL, "NULL argument");
+    if (n_words < bit_words(idx->n_rows)) return fail(VS_EINVAL, "n_words = %lld is shorter than the %lld words of %lld rows", (long long)n_words,
+                                                      (long long)bit_words(idx->n_rows), (long long)idx->n_rows);
+    if (n_words == 0) return VS_OK;
+    VS_TRY(ptr_on(out_words, idx->device, "out_words"));
+    VS_HIP(hipSetDevice(idx->device));
+    VS_HIP(hipDeviceSynchronize());                            // (deletions enqueued on a caller's stream)
+    const bool out_dev = is_device_ptr(out_words);
+    DevBuf tmp;
+    uint32_t* d = out_words;
+    if (!out_dev) {
+        VS_TRY(tmp.alloc((size_t)n_words * 4));
+        d = tmp.as<uint32_t>();
+    }
+    hipLaunchKernelGGL(live_out_kernel, dim3(grid_for(n_words)), dim3(256), 0, 0, idx->has_tomb ? idx->live.as<uint32_t>() : nullptr, idx->n_rows, d, n_words);
+    VS_HIP(hipGetLastError());
+    if (!out_dev) VS_HIP(hipMemcpy(out_words, d, (size_t)n_words * 4, hipMemcpyDeviceToHost));
+    VS_HIP(hipDeviceSynchronize());
+    return VS_OK;
+}
+
+// =================================================================================================
+// compaction
+// =================================================================================================
+namespace {
+
+constexpr int kScanItems = 16;                       // rows per thread of a scan block: 256 x 16 = 4096 rows a block
+constexpr int kScanRows = 256 * kScanItems;
+
+__device__ __forceinline__ uint2 add2(uint2 a, uint2 b) { return make_uint2(a.x + b.x, a.y + b.y); }
+
+// (live?, packets) of row r; a dead row and a row past the end count nothing.  pk == nullptr (dense matrix): no packets
+__device__ __forceinline__ uint2 row_stat(const uint32_t* live, const uint32_t* pk, int64_t r, int64_t n_rows) {
+    if (r >= n_rows) return make_uint2(0u, 0u);
+    if (live && !((live[r >> 5] >> (r & 31)) & 1u)) return make_uint2(0u, 0u);
+    return make_uint2(1u, pk ? pk[r + 1] - pk[r] : 0u);
+}
+
+// exclusive scan over the NW waves of a workgroup; *total = the workgroup's sum.  sh: [NW] uint2 of LDS
+template <int NW>
+__device__ __forceinline__ uint2 block_excl_scan(uint2 v, uint2* sh, uint2* total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    uint2 inc = v;
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t a = __shfl_up(inc.x, o, 64), b = __shfl_up(inc.y, o, 64);
+        if (lane >= o) { inc.x += a; inc.y += b; }
+    }
+    if (lane == 63) sh[w] = inc;
+    __syncthreads();
+    uint2 base = make_uint2(0u, 0u), tot = make_uint2(0u, 0u);
+#pragma unroll
+    for (int i = 0; i < NW; ++i) {
+        if (i < w) base = add2(base, sh[i]);
+        tot = add2(tot, sh[i]);
+    }
+    __syncthreads();                                  // (sh is written again by the caller's next round)
+    *total = tot;
+    return make_uint2(base.x + inc.x - v.x, base.y + inc.y - v.y);
+}
+
+// step 1a: (live rows, their packets) of every block of kScanRows rows
+__global__ __launch_bounds__(256) void compact_sums_kernel(const uint32_t* live, const uint32_t* pk, int64_t n_rows, uint2* sums) {
+    __shared__ uint2 sh[4];
+    const int64_t r0 = (int64_t)blockIdx.x * kScanRows;
+    uint2 acc = make_uint2(0u, 0u);
+    for (int it = 0; it < kScanItems; ++it) acc = add2(acc, row_stat(live, pk, r0 + it * 256 + threadIdx.x, n_rows));
+    uint2 tot;
+    (void)block_excl_scan<4>(acc, sh, &tot);
+    if (threadIdx.x == 0) sums[blockIdx.x] = tot;
+}
+
+// step 1b: exclusive scan of the block sums in place (one workgroup walks them 1024 at a time); total[0] = (live rows, packets) of the index
+__global__ __launch_bounds__(1024) void compact_scan_sums_kernel(uint2* sums, int64_t n_blocks, uint2* total) {
+    __shared__ uint2 sh[16];
+    uint2 carry = make_uint2(0u, 0u);
+    for (int64_t b0 = 0; b0 < n_blocks; b0 += 1024) {
+        const int64_t b = b0 + threadIdx.x;
+        const uint2 v = b < n_blocks ? sums[b] : make_uint2(0u, 0u);
+        uint2 tot;
+        const uint2 ex = block_excl_scan<16>(v, sh, &tot);
+        if (b < n_blocks) sums[b] = add2(carry, ex);
+        carry = add2(carry, tot);
+    }
+    if (threadIdx.x == 0) total[0] = carry;
+}
+
+// step 1c: every live row learns its new row id j and first packet: old_ids[j] = row, new_pk[j] = packets of the live rows before it
+__global__ __launch_bounds__(256) void compact_map_kernel(const uint32_t* live, const uint32_t* pk, int64_t n_rows, const uint2* sums, int64_t* old_ids,
+                                                          uint32_t* new_pk) {
+    __shared__ uint2 sh[4];
+    const int64_t r0 = (int64_t)blockIdx.x * kScanRows;
+    uint2 carry = sums[blockIdx.x];
+    for (int it = 0; it < kScanItems; ++it) {
+        const int64_t r = r0 + it * 256 + threadIdx.x;
+        const uint2 v = row_stat(live, pk, r, n_rows);
+        uint2 tot;
+        const uint2 ex = block_excl_scan<4>(v, sh, &tot);
+        if (v.x) {
+            const int64_t j = (int64_t)carry.x + ex.x;
+            old_ids[j] = r;
+            if (new_pk) new_pk[j] = carry.y + ex.y;
+        }
+        carry = add2(carry, tot);
+    }
+}
+
+// step 2: packet gather.  A wave takes a run of 64 new rows: their packets are one contiguous range of the new index, lane p of it finds its row
+// among the run's 65 row pointers (held one a lane, searched with shuffles) and copies the packet whole -- 16 bytes of column ids, VB bytes of
+// values.  Padding sits in a row's last packet and moves with it.
+template <int VB>
+__global__ __launch_bounds__(256) void compact_gather_kernel(const int64_t* old_ids, const uint32_t* src_pk, const uint32_t* new_pk, int64_t n_new,
+                                                             const uint4* src_cols, const uint4* src_vals, uint4* dst_cols, uint4* dst_vals) {
+    const int lane = threadIdx.x & 63;
+    const int64_t n_runs = (n_new + 63) >> 6;
+    for (int64_t run = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); run < n_runs; run += (int64_t)gridDim.x * 4) {
+        const int64_t j = run * 64 + lane;
+        const uint32_t np = new_pk[j < n_new ? j : n_new];
+        const uint32_t sp = j < n_new ? src_pk[old_ids[j]] : 0u;
+        const int64_t j_end = (run * 64 + 64 < n_new) ? run * 64 + 64 : n_new;
+        const uint32_t p_begin = __shfl(np, 0, 64), p_end = new_pk[j_end];
+        for (int64_t base = p_begin; base < (int64_t)p_end; base += 64) {
+            const int64_t p = base + lane;
+            int i = 0;                                            // the last row of the run whose first packet is <= p: the row p belongs to
+#pragma unroll
+            for (int step = 32; step > 0; step >>= 1) {
+                const uint32_t v = __shfl(np, i + step, 64);
+                if ((int64_t)v <= p) i += step;
+            }
+            const uint32_t npi = __shfl(np, i, 64), spi = __shfl(sp, i, 64);
+            if (p < (int64_t)p_end) {
+                const size_t s = (size_t)spi + (size_t)(p - (int64_t)npi);
+                dst_cols[p] = src_cols[s];
+                if (VB == 16) dst_vals[p] = src_vals[s];
+                if (VB == 32) {
+                    dst_vals[(size_t)p * 2] = src_vals[s * 2];
+                    dst_vals[(size_t)p * 2 + 1] = src_vals[s * 2 + 1];
+                }
+            }
+        }
+    }
+}
+
+// dense (matrix-core) index: row gather of the padded matrix, 16 bytes a lane (ldp is a multiple of 32 floats)
+__global__ __launch_bounds__(256) void compact_dense_kernel(const int64_t* old_ids, int64_t n_new, int64_t quads_per_row, const uint4* src, uint4* dst) {
+    const int64_t n = n_new * quads_per_row;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const int64_t j = i / quads_per_row, c = i % quads_per_row;
+        dst[i] = src[(size_t)old_ids[j] * (size_t)quads_per_row + (size_t)c];
+    }
+}
+
+// step 3: non-zeros of the new index (pads sit at the tail of a row's last packet only)
+__global__ __launch_bounds__(256) void compact_nnz_kernel(const uint32_t* pk, int64_t n_rows, const uint16_t* cols, int32_t n_cols, unsigned long long* out) {
+    unsigned long long nnz = 0;
+    for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < n_rows; r += (int64_t)gridDim.x * 256) {
+        const uint32_t a = pk[r], b = pk[r + 1];
+        if (b > a) {
+            nnz += (unsigned long long)(b - a - 1) * 8ull;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) nnz += cols[(size_t)(b - 1) * 8 + i] != (uint16_t)n_cols ? 1ull : 0ull;
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) nnz += __shfl_xor(nnz, o, 64);
+    if ((threadIdx.x & 63) == 0 && nnz) atomicAdd(out, nnz);
+}
+
+int pick_lanes(int64_t n_packets, int64_t n_rows) {             // (csr_index.hip: pick_lanes_per_row)
+    const double mp = n_rows > 0 ? (double)n_packets / (double)n_rows : 1.0;
+    int g = 4;
+    while (g < 64 && mp / g > 4.0) g <<= 1;
+    return g;
+}
+
+// a CSR index with its capacity, moved whole to another GPU (peer copies): compaction across devices compacts on the source's GPU first
+int move_csr(const vs_index* a, int device, vs_index** out) {
+    vs_index* idx = nullptr;
+    VS_TRY(vs_index_create_reserved(a->rows_cap, a->packets_cap, a->n_cols, a->store_dtype, device, &idx));
+    struct Guard { vs_index* p; ~Guard() { if (p) vs_index_destroy(p); } } guard{idx};
+    const size_t vb = a->store_dtype == VS_F32 ? 32 : (a->store_dtype == VS_F16 ? 16 : 0);
+    VS_HIP(hipMemcpyPeer(idx->pk_ptr.p, device, a->pk_ptr.p, a->device, (size_t)(a->n_rows + 1) * 4));
+    if (a->n_packets) VS_HIP(hipMemcpyPeer(idx->cols.p, device, a->cols.p, a->device, (size_t)a->n_packets * 16));
+    if (a->n_packets && vb) VS_HIP(hipMemcpyPeer(idx->vals.p, device, a->vals.p, a->device, (size_t)a->n_packets * vb));
+    idx->n_rows = a->n_rows;
+    idx->n_packets = a->n_packets;
+    idx->nnz = a->nnz;
+    idx->logical_dense = a->logical_dense;
+    idx->lanes_per_row = a->lanes_per_row;
+    guard.p = nullptr;
+    *out = idx;
+    return VS_OK;
+}
+
+}  // namespace
+
+extern "C" int vs_index_compact(const vs_index* src, int64_t rows_extra, int64_t packets_extra, int device, vs_index** out, int64_t* out_old_ids) {
+    VS_TRY(need_device());
+    if (!src || !out) return fail(VS_EINVAL, "NULL argument");
+    *out = nullptr;
+    if (rows_extra < 0 || packets_extra < 0) return fail(VS_EINVAL, "rows_extra and packets_extra must be >= 0");
+    int ndev = 0;
+    VS_HIP(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) return fail(VS_EINVAL, "device %d out of range (have %d)", device, ndev);
+    const bool dense = src->kind != VS_KIND_CSR;
+    if (dense && (rows_extra || packets_extra)) return fail(VS_EINVAL, "a dense (matrix) index has no append: rows_extra and packets_extra must be 0");
+    if (dense && device != src->device) return fail(VS_EUNSUPPORTED, "a dense (matrix) index compacts on its own device");
+    if (out_old_ids) VS_TRY(ptr_on(out_old_ids, src->device, "out_old_ids"));
+    VS_HIP(hipSetDevice(src->device));
+    VS_HIP(hipDeviceSynchronize());                            // deletions enqueued on a caller's stream; everything below runs on the null stream
+    const int64_t n = src->n_rows;
+    const uint32_t* live = src->has_tomb ? src->live.as<uint32_t>() : nullptr;
+    const uint32_t* pk = dense ? nullptr : src->pk_ptr.as<uint32_t>();
+    // 1. scan: live rows and their packets
+    const int64_t n_blocks = std::max<int64_t>(1, (n + kScanRows - 1) / kScanRows);
+    DevBuf sums;
+    VS_TRY(sums.alloc((size_t)(n_blocks + 1) * 8));
+    uint2* d_sums = sums.as<uint2>();
+    hipLaunchKernelGGL(compact_sums_kernel, dim3((unsigned)n_blocks), dim3(256), 0, 0, live, pk, n, d_sums);
+    hipLaunchKernelGGL(compact_scan_sums_kernel, dim3(1), dim3(1024), 0, 0, d_sums, n_blocks, d_sums + n_blocks);
+    VS_HIP(hipGetLastError());
+    uint32_t tot[2] = {0u, 0u};
+    VS_HIP(hipMemcpy(tot, d_sums + n_blocks, 8, hipMemcpyDeviceToHost));
+    const int64_t n_new = tot[0], p_new = tot[1];
+    if (dense && n_new == 0) return fail(VS_EINVAL, "every row is deleted: a dense (matrix) index cannot be empty");
+    const bool ids_dev = out_old_ids && is_device_ptr(out_old_ids);
+    DevBuf old_buf;
+    int64_t* d_old = out_old_ids;
+    if (!ids_dev) {
+        VS_TRY(old_buf.alloc(std::max<size_t>((size_t)n_new * 8, 8)));
+        d_old = old_buf.as<int64_t>();
+    }
+    vs_index* idx = nullptr;
+    struct Guard { vs_index* p; ~Guard() { if (p) vs_index_destroy(p); } } guard{nullptr};
+    if (!dense) {
+        if (n_new + rows_extra >= (1ll << 32) - 1 || p_new + packets_extra >= (1ll << 32)) return fail(VS_EUNSUPPORTED, "the compacted index with its spare capacity exceeds 2^32 rows or packets");
+        const size_t vb = src->store_dtype == VS_F32 ? 32 : (src->store_dtype == VS_F16 ? 16 : 0);
+        if (vs_index_create_reserved(n_new + rows_extra, p_new + packets_extra, src->n_cols, src->store_dtype, src->device, &idx) != VS_OK) {
+            const size_t need = (size_t)(p_new + packets_extra) * (16 + vb) + (size_t)(n_new + rows_extra + 1) * 4;
+            return fail(VS_ENOMEM, "compaction needs %zu bytes of HBM for the new index next to the source's (drop the postings copy of the source, or compact onto another GPU)", need);
+        }
+        guard.p = idx;
+        hipLaunchKernelGGL(compact_map_kernel, dim3((unsigned)n_blocks), dim3(256), 0, 0, live, pk, n, (const uint2*)d_sums, d_old, idx->pk_ptr.as<uint32_t>());
+        VS_HIP(hipGetLastError());
+        const uint32_t last = (uint32_t)p_new;
+        VS_HIP(hipMemcpy(idx->pk_ptr.as<uint32_t>() + n_new, &last, 4, hipMemcpyHostToDevice));
+        // 2. gather
+        if (p_new > 0) {
+            const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(((n_new + 63) / 64 + 3) / 4, (int64_t)src->cu_count * 32));
+            const uint4 *sc = src->cols.as<uint4>(), *sv = src->vals.as<uint4>();
+            uint4 *dc = idx->cols.as<uint4>(), *dv = idx->vals.as<uint4>();
+            const uint32_t* npk = idx->pk_ptr.as<uint32_t>();
+            if (vb == 32) hipLaunchKernelGGL(compact_gather_kernel<32>, dim3(grid), dim3(256), 0, 0, (const int64_t*)d_old, pk, npk, n_new, sc, sv, dc, dv);
+            else if (vb == 16) hipLaunchKernelGGL(compact_gather_kernel<16>, dim3(grid), dim3(256), 0, 0, (const int64_t*)d_old, pk, npk, n_new, sc, sv, dc, dv);
+            else hipLaunchKernelGGL(compact_gather_kernel<0>, dim3(grid), dim3(256), 0, 0, (const int64_t*)d_old, pk, npk, n_new, sc, sv, dc, dv);
+            VS_HIP(hipGetLastError());
+        }
+        // 3. non-zeros
+        DevBuf cnt;
+        VS_TRY(cnt.alloc(8));
+        VS_HIP(hipMemset(cnt.p, 0, 8));
+        if (n_new > 0)
+            hipLaunchKernelGGL(compact_nnz_kernel, dim3(grid_for(n_new, 256, 4096)), dim3(256), 0, 0, idx->pk_ptr.as<uint32_t>(), n_new, idx->cols.as<uint16_t>(),
+                               src->n_cols, cnt.as<unsigned long long>());
+        VS_HIP(hipGetLastError());
+        unsigned long long nnz = 0;
+        VS_HIP(hipMemcpy(&nnz, cnt.p, 8, hipMemcpyDeviceToHost));
+        idx->n_rows = n_new;
+        idx->n_packets = p_new;
+        idx->nnz = (int64_t)nnz;
+        idx->logical_dense = src->logical_dense;
+        idx->lanes_per_row = pick_lanes(p_new, n_new);
+    } else {
+        idx = new (std::nothrow) vs_index();
+        if (!idx) return fail(VS_ENOMEM, "host allocation failed");
+        guard.p = idx;
+        idx->kind = VS_KIND_DENSE;
+        idx->device = src->device;
+        idx->cu_count = src->cu_count;
+        idx->store_dtype = src->store_dtype;
+        idx->n_rows = n_new;
+        idx->n_cols = src->n_cols;
+        idx->nnz = n_new * (int64_t)src->n_cols;
+        const size_t row_bytes = src->mat.bytes / (size_t)n;               // the padded row (dense.hip: a multiple of 32 floats)
+        if (idx->mat.alloc((size_t)n_new * row_bytes) != VS_OK)
+            return fail(VS_ENOMEM, "compaction needs %zu bytes of HBM for the new matrix next to the source's", (size_t)n_new * row_bytes);
+        hipLaunchKernelGGL(compact_map_kernel, dim3((unsigned)n_blocks), dim3(256), 0, 0, live, pk, n, (const uint2*)d_sums, d_old, (uint32_t*)nullptr);
+        const int64_t qpr = (int64_t)(row_bytes / 16);
+        hipLaunchKernelGGL(compact_dense_kernel, dim3(grid_for(n_new * qpr, 256, (int64_t)src->cu_count * 32)), dim3(256), 0, 0, (const int64_t*)d_old, n_new, qpr,
+                           src->mat.as<uint4>(), idx->mat.as<uint4>());
+        VS_HIP(hipGetLastError());
+    }
+    if (out_old_ids && !ids_dev && n_new > 0) VS_HIP(hipMemcpy(out_old_ids, d_old, (size_t)n_new * 8, hipMemcpyDeviceToHost));
+    VS_HIP(hipDeviceSynchronize());
+    if (device != src->device) {                                // the compacted index moves to its GPU; the copy on the source's GPU is dropped
+        vs_index* moved = nullptr;
+        VS_TRY(move_csr(idx, device, &moved));
+        VS_HIP(hipSetDevice(src->device));
+        vs_index_destroy(idx);
+        guard.p = nullptr;
+        idx = moved;
+    }
+    guard.p = nullptr;
+    *out = idx;
+    return VS_OK;
+}

@@ -521,6 +521,11 @@ std::vector<char> npy_header(const char* descr, const std::vector<int64_t>& shap
 static int index_save_npz_impl(const vs_index* idx, const char* path, int compressed) {
     if (!idx || !path) return fail(VS_EINVAL, "NULL argument");
     if (idx->kind != VS_KIND_CSR) return fail(VS_EINVAL, "not a CSR index");
+    {
+        int64_t dead = 0;                                      // an .npz has no place for tombstones: a reload would resurrect the rows
+        VS_TRY(tomb_dead_count(idx, &dead));
+        if (dead > 0) return fail(VS_EINVAL, "the index has %lld deleted rows and an .npz file cannot record them: compact first (or save a .vsx file)", (long long)dead);
+    }
     std::vector<int64_t> rp((size_t)idx->n_rows + 1);
     VS_TRY(vs_index_export_csr(idx, rp.data(), nullptr, nullptr, VS_F32));
     const int64_t nnz = rp[(size_t)idx->n_rows];

@@ -133,6 +133,37 @@ def _int64_ids(ids, ndim, name="ids"):
     return _is_torch(ids) and ids.is_cuda
 
 
+def _row_ids(ids, name="ids"):
+    """An id list of delete_rows / restore_rows -> (int64 1-D numpy array | CUDA tensor, on_device).  Lists, tuples and integer arrays of any
+    width are taken; anything that is not integer is a TypeError, more than one dimension a ValueError (checked before the library is reached)."""
+    if _is_torch(ids):
+        import torch
+        if ids.dtype in (torch.bool,) or ids.is_floating_point() or ids.is_complex():
+            raise TypeError(f"{name} must be integer document ids, got {ids.dtype}")
+        if ids.ndim != 1:
+            raise ValueError(f"{name} must be a 1-D list of document ids, got {ids.ndim} dimensions")
+        if ids.is_cuda:
+            return ids.to(torch.int64).contiguous(), True
+        ids = ids.numpy()
+    a = np.asarray(ids)
+    if a.size == 0 and a.ndim == 1:
+        return np.zeros(0, dtype=np.int64), False
+    if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
+        raise TypeError(f"{name} must be integer document ids, got {a.dtype}")
+    if a.ndim != 1:
+        raise ValueError(f"{name} must be a 1-D list of document ids, got {a.ndim} dimensions")
+    return np.ascontiguousarray(a, dtype=np.int64), False
+
+
+def _compact_args(rows_extra, packets_extra):
+    for name, v in (("rows_extra", rows_extra), ("packets_extra", packets_extra)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise TypeError(f"{name} must be an int, got {type(v).__name__}")
+        if v < 0:
+            raise ValueError(f"{name} must be >= 0, got {v}")
+    return int(rows_extra), int(packets_extra)
+
+
 def _by_example_args(ids, weights=None, q=None, k=None, a=None):
     """Argument checks of queries_from_rows() / search_by_example() that need no device -> (B, m, on_device)"""
     on_dev = _int64_ids(ids, 2)
@@ -460,6 +491,75 @@ class DeviceIndex:
             out = tuple(torch.from_numpy(a) for a in out)
         return Explanation(*out)
 
+    # ---- mutable index: delete / restore / compact --------------------------------------------------
+    def _tombstones(self, fn, ids):
+        ids, on_dev = _row_ids(ids)
+        nat.require_device()
+        n = int(ids.shape[0])
+        if n == 0:
+            return
+        fn = getattr(nat.lib(), fn)
+        if on_dev:
+            nat.check(fn(self._h, C.c_void_p(ids.data_ptr()), n, 0, current_stream(self.device)))
+        else:
+            nat.check(fn(self._h, C.c_void_p(ids.ctypes.data), n, 0, None))
+
+    def delete_rows(self, ids):
+        """Mark rows deleted (vs_index_delete_rows): from now on no search of this handle returns them -- search, search_by_example and
+        the shards of a group apply the handle's live bitmap like a deny DocFilter, ANDed with a `filter=` of the call.  Ids do not move and
+        the rows stay stored (explain / get_rows still answer; restore_rows brings them back) until compact().  ids: integers, 1-D; -1 is
+        ignored, deleting twice is a no-op; an id outside the index raises ValueError (CUDA tensors are not checked: such ids are skipped,
+        and the call only enqueues on torch's current stream)."""
+        self._tombstones("vs_index_delete_rows", ids)
+
+    def restore_rows(self, ids=None):
+        """Undo delete_rows for `ids`; None restores every row (the handle then searches exactly as one that never had deletions)."""
+        if ids is None:
+            nat.require_device()
+            nat.check(nat.lib().vs_index_restore_rows(self._h, None, 0, 0, None))
+            return
+        self._tombstones("vs_index_restore_rows", ids)
+
+    @property
+    def n_live(self) -> int:
+        """rows not deleted (synchronises)"""
+        out = C.c_int64(0)
+        nat.check(nat.lib().vs_index_live_rows(self._h, C.byref(out)))
+        return out.value
+
+    def live_mask(self):
+        """bool tensor [n_rows] on the index's device: True = live (vs_index_live_bitmap, unpacked)"""
+        import torch
+        nat.require_device()
+        n = self.n_rows
+        dev = torch.device("cuda", self.device)
+        words = torch.zeros(max((n + 31) // 32, 1), dtype=torch.int32, device=dev)
+        torch.cuda.current_stream(self.device).synchronize()
+        nat.check(nat.lib().vs_index_live_bitmap(self._h, C.c_void_p(words.data_ptr()), int(words.numel())))
+        bits = (words[:, None] >> torch.arange(32, device=dev, dtype=torch.int32)[None, :]) & 1
+        return bits.reshape(-1)[:n].to(torch.bool)
+
+    def compact(self, rows_extra: int = 0, packets_extra: int = 0, device: int = None):
+        """-> (new DeviceIndex holding the live rows in order, old_ids int64 numpy [n_live]: the row of this index each new row was), with
+        room for rows_extra more rows / packets_extra more 8-nnz packets of append_csr (vs_index_compact).  This index is untouched.  If HBM
+        cannot hold both, this index's postings copy is dropped (prepare() rebuilds it) and the call retried once."""
+        rows_extra, packets_extra = _compact_args(rows_extra, packets_extra)
+        nat.require_device()
+        device = self.device if device is None else int(device)
+        old = np.empty(self.n_live, dtype=np.int64)
+        h = C.c_void_p()
+        args = (self._h, rows_extra, packets_extra, device, C.byref(h), C.c_void_p(old.ctypes.data) if old.size else None)
+        try:
+            nat.check(nat.lib().vs_index_compact(*args))
+        except MemoryError:
+            info = self.info()
+            if not info.aux_bytes:
+                raise
+            self.set_option("blocked_postings", 0)             # releases the copy; back to auto for the next prepare()
+            self.set_option("blocked_postings", -1)
+            nat.check(nat.lib().vs_index_compact(*args))
+        return DeviceIndex(h), old
+
     # ---- query by example ------------------------------------------------------------------------
     @property
     def n_rows(self) -> int:
@@ -600,6 +700,49 @@ class ShardGroup:
         sc = np.empty((B, k), dtype=np.float32)
         run(C.c_void_p(ids.ctypes.data), C.c_void_p(sc.ctypes.data))
         return ids, sc
+
+    # ---- mutable index ----------------------------------------------------------------------------------
+    def _tombstones(self, fn, ids):
+        ids, on_dev = _row_ids(ids)
+        nat.require_device()
+        n = int(ids.shape[0])
+        if n == 0:
+            return
+        fn = getattr(nat.lib(), fn)
+        if on_dev:
+            import torch
+            torch.cuda.current_stream(ids.device).synchronize()
+            nat.check(fn(self._h, C.c_void_p(ids.data_ptr()), n))
+        else:
+            nat.check(fn(self._h, C.c_void_p(ids.ctypes.data), n))
+
+    def delete_rows(self, ids):
+        """DeviceIndex.delete_rows with global ids: every shard marks the rows it owns (vs_shard_group_delete_rows).  Blocking."""
+        self._tombstones("vs_shard_group_delete_rows", ids)
+
+    def restore_rows(self, ids=None):
+        if ids is None:
+            nat.require_device()
+            nat.check(nat.lib().vs_shard_group_restore_rows(self._h, None, 0))
+            return
+        self._tombstones("vs_shard_group_restore_rows", ids)
+
+    @property
+    def n_live(self) -> int:
+        return sum(s.n_live for s in self._shards)
+
+    def compact(self, rows_extra: int = 0, packets_extra: int = 0):
+        """Every shard compacted on its own GPU -> (new ShardGroup, old_ids int64 numpy: the GLOBAL id each new global row had).  The spare
+        capacity goes to the last shard (rows are appended at the end of the corpus)."""
+        rows_extra, packets_extra = _compact_args(rows_extra, packets_extra)
+        new, olds, row0 = [], [], 0
+        for i, s in enumerate(self._shards):
+            last = i == len(self._shards) - 1
+            c, old = s.compact(rows_extra if last else 0, packets_extra if last else 0)
+            new.append(c)
+            olds.append(old + row0)
+            row0 += s.n_rows
+        return ShardGroup(new), (np.concatenate(olds) if olds else np.zeros(0, dtype=np.int64))
 
     def explain(self, q, ids, topn: int = 10) -> Explanation:
         """DeviceIndex.explain over the group's rows (global ids): every shard explains the pairs it owns on its own GPU, the first

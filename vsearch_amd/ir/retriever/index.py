@@ -60,6 +60,21 @@ def _gpu_ordinal(device) -> int:
     return 0
 
 
+def remap_text_store(data, offsets, old_ids):
+    """The text store after a compaction: entry j of the result is entry old_ids[j] of the input, for the in-memory list (`data`) and for
+    the line offsets of a low_memory store (`offsets`); either may be None.  Pure host work."""
+    old = [int(i) for i in old_ids]
+    new_data = [data[i] for i in old] if data is not None else None
+    new_offsets = [offsets[i] for i in old] if offsets is not None else None
+    return new_data, new_offsets
+
+
+def _packets_of(indptr) -> int:
+    """8-nnz packets the CSR rows of `indptr` take in the device format"""
+    ip = indptr.cpu().numpy() if isinstance(indptr, torch.Tensor) else np.asarray(indptr)
+    return int(((np.diff(ip.astype(np.int64)) + 7) // 8).sum())
+
+
 class Index:
     index_type = IndexType.DENSE
     DENSE_AS_CSR_DENSITY = 0.05        # set to 0 to always use the dense (MFMA) search kernel
@@ -170,6 +185,8 @@ class Index:
         if self._vector is not None:
             self._vector = self._vector.to(device)
         same_gpu = self._dev is not None and self._dev.device == _gpu_ordinal(device)
+        if not same_gpu and self._dev is not None and self._dev.n_live != self._dev.n_rows:
+            raise RuntimeError("the index has deleted rows, which a move to another device would resurrect: compact() first")
         if not same_gpu:
             if self._vector is None and self._dev is not None:
                 self._vector = self._export_vector()
@@ -370,9 +387,131 @@ class Index:
         out_ids, out_sc = topk_exclude(res.ids.to(gpu).contiguous(), res.scores.to(gpu).float().contiguous(), ids, k, gpu_ord)
         return SearchResults(self._to_api(out_ids), self._to_api(out_sc.to(self._dtype)))
 
+    # ---- mutable index (not in the reference: its index is rebuilt) ------------------------------------------------------------------
+    def _mutable_target(self):
+        """DeviceIndex, or the ShardGroup of a row-sharded index: both have delete_rows / restore_rows / n_live / compact"""
+        return self._explain_target()[0]
+
+    def delete(self, ids):
+        """Delete documents by id: no search of this index (retrieve, rerank, more_like_this, feedback, every shard) returns them from now
+        on.  Ids do not move and len(index) stays the stored row count; explain / get_vectors still answer for a deleted id and restore()
+        brings it back, until compact() drops the rows for good.  ids: integers (list / numpy / torch), -1 ignored."""
+        self._mutable_target().delete_rows(ids.detach() if isinstance(ids, torch.Tensor) else ids)
+
+    def restore(self, ids=None):
+        """Undo delete() for `ids`; None restores every document."""
+        self._mutable_target().restore_rows(ids.detach() if isinstance(ids, torch.Tensor) else ids)
+
+    @property
+    def n_live(self) -> int:
+        """documents not deleted"""
+        return int(self._mutable_target().n_live)
+
+    def _check_no_deletions(self, what):
+        if (self._dev is not None or getattr(self, "_group", None) is not None) and self.n_live != self._n_rows():
+            raise ValueError(f"the index has {self._n_rows() - self.n_live} deleted documents that {what} cannot record: compact() first"
+                             " (a .vsx file keeps them)")
+
+    def _swap_compacted(self, rows_extra=0, packets_extra=0):
+        """replace the device index (or every shard) by its compaction -> old ids (numpy)"""
+        group = getattr(self, "_group", None)
+        if group is not None:
+            new_group, old = group.compact(rows_extra, packets_extra)
+            group.close()
+            for sh in self._shards:
+                sh.close()
+            self._adopt_shards(list(new_group._shards))
+            new_group.close()
+        else:
+            new, old = self._device_index().compact(rows_extra, packets_extra)
+            self._dev.close()
+            self._dev = new
+            self._prepare()
+        self._vector = None                                         # re-exported from the new rows on demand
+        if self._shape is not None:
+            self._shape = (int(old.shape[0]), self._shape[1])
+        return old
+
+    def compact(self):
+        """Drop the deleted rows for good (vs_index_compact on the GPU) -> old_ids: new document j was document old_ids[j].  The text store
+        follows: get_sample(j) returns the text that belonged to old_ids[j]."""
+        old = self._swap_compacted()
+        self.data, offsets = remap_text_store(self.data, getattr(self, "offsets", None) if self.low_memory else None, old)
+        if offsets is not None:
+            self.offsets = offsets
+        return torch.from_numpy(old)
+
+    def _add_csr(self, vectors):
+        """vectors -> (indptr, indices, data) of the rows to append"""
+        if isinstance(vectors, np.ndarray):
+            vectors = torch.from_numpy(vectors)
+        if isinstance(vectors, torch.Tensor) and vectors.layout == torch.strided:
+            if vectors.dim() == 1:
+                vectors = vectors.unsqueeze(0)
+            vectors = vectors.detach().cpu().float().to_sparse_csr()
+        indptr, indices, data, shape = SparseIndex._csr_parts(vectors)
+        return indptr, indices, data, shape
+
+    def add(self, vectors, samples=None):
+        """Append documents -> their new ids (int64 tensor).  vectors: a sparse CSR tensor / scipy CSR (or a dense [n, V] tensor) whose
+        columns match the index.  When the index has no spare capacity it is compacted with room to grow (at least the rows asked for, at
+        least a quarter of its size); that moves ids if rows are deleted, so then add() raises and asks for compact().  samples: the
+        documents' texts, appended to `data`."""
+        indptr, indices, data, shape = self._add_csr(vectors)
+        n_add = int(indptr.shape[0]) - 1
+        target = self._shards[-1] if getattr(self, "_shards", None) else self._device_index()
+        info = target.info()
+        if info.kind != nat.VS_KIND_CSR and not (info.kind == nat.VS_KIND_DENSE and info.n_packets > 0):
+            raise NotImplementedError("a dense index on the matrix cores has no append: build it below DENSE_AS_CSR_DENSITY or rebuild it")
+        if int(shape[1]) != int(info.n_cols):
+            raise ValueError(f"vectors have {int(shape[1])} columns, the index has {int(info.n_cols)}")
+        if samples is not None and (self.low_memory or len(samples) != n_add):
+            raise ValueError("samples must hold one text per added vector (and the text store must be in memory: low_memory=False)")
+        n0 = self._n_rows()
+        if isinstance(data, torch.Tensor) and data.dtype not in (torch.float32, torch.float16):
+            data = data.float()
+        if isinstance(data, np.ndarray) and data.dtype not in (np.float32, np.float16):
+            data = data.astype(np.float32)
+        if info.store_dtype == nat.VS_NONE:
+            if not bool((data == 1).all()):
+                raise ValueError("a bag-of-token (binary) index takes only values of 1")
+            data = None
+        def append():
+            tgt = self._shards[-1] if getattr(self, "_shards", None) else self._dev
+            tgt.append_csr(indptr, indices, data)
+        try:
+            append()
+        except ValueError as e:
+            if "exceeds the reserved" not in str(e):
+                raise
+            if self.n_live != n0:
+                raise RuntimeError("the index is full and has deleted rows: growing it compacts it, which moves ids -- call compact() first, "
+                                   "then add()") from None
+            self._swap_compacted(max(n_add, n0 // 4), max(_packets_of(indptr), int(info.n_packets) // 4))
+            append()
+        if getattr(self, "_shards", None):
+            self._group.close()                                     # (the group caches its shards' row ranges)
+            self._group = ShardGroup(self._shards)
+            if self.EAGER_POSTINGS:
+                self._shards[-1].prepare()
+        else:
+            self._prepare()
+        self._vector = None
+        if self._shape is not None:
+            self._shape = (n0 + n_add, self._shape[1])
+        if samples is not None:
+            self.data = (self.data or []) + list(samples)
+        return torch.arange(n0, n0 + n_add, dtype=torch.int64)
+
+    def update(self, ids, vectors, samples=None):
+        """delete(ids) + add(vectors, samples) -> the new ids of the replacements"""
+        self.delete(ids)
+        return self.add(vectors, samples)
+
     # ---- persistence -------------------------------------------------------------------------------
     def save(self, path):
         """Dense index -> ``.pt`` (torch.save of the CPU tensor), like index.py:96-109."""
+        self._check_no_deletions("a .pt file")
         try:
             torch.save(self.vector.cpu(), path)
             logger.info("Index successfully saved to %s", path)
@@ -796,6 +935,7 @@ class SparseIndex(Index):
             self._device_index().save_native(path)
             logger.info("Index successfully saved to %s", path)
             return
+        self._check_no_deletions("an .npz file")
         try:
             # values go to disk as float32: scipy.sparse has no float16, and the loader re-applies fp16 (fp16=True)
             if self._dev is not None and not self._shards:

@@ -320,6 +320,15 @@ class Retriever(BiEncoder):
                 raise NotImplementedError("devices=: row sharding serves the sparse and bag-of-token indexes")
             self.index.shard_rows(devices)
 
+    def delete_documents(self, ids, index: Index = None):
+        """Delete documents of the index by id (Index.delete): retrieve, rerank, more_like_this and retrieve_with_feedback never return
+        them again; ids do not move until compact_index()."""
+        (index or self.index).delete(ids)
+
+    def compact_index(self, index: Index = None):
+        """Drop deleted documents for good (Index.compact) -> old_ids: document j of the index was document old_ids[j] before."""
+        return (index or self.index).compact()
+
     def save_index(self, path):
         self.index.save(path)
 
