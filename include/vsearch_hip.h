@@ -393,6 +393,8 @@ VS_API void vs_index_destroy(vs_index* index);
  * all shards ([B, n_cand] global ids + scores, e.g. after an RCCL all-gather) -> canonical top-k. */
 /* (ids must be in [0, 2^32 - 1): the merge keys hold 32-bit ids; a candidate outside that range -- the id -1 padding of a filtered
  *  search among them -- is dropped, never aliased; fewer than k candidates left: id -1, score -inf behind them)                     */
+/* (order: score descending, id ascending, scores compared as floats: -0.0 and +0.0 tie -- the id decides -- and both come back as
+ *  +0.0; a real candidate that scores -inf precedes the pads; NaN scores are not ordered)                                         */
 VS_API int vs_merge_topk(const int64_t* cand_ids, const float* cand_scores, int32_t B, int64_t n_cand, int32_t k,
                          int64_t* out_ids, float* out_scores, int device, void* stream);
 
@@ -451,7 +453,11 @@ VS_API int vs_head_pool_mean_topk(const float* logits, int32_t B, int32_t L, int
  * streamed in batches (the dense tensor is 12 GB at B = 1024, k = 100): vs_rerank_scores fills scores[row0 .. row0 + n_rows) of
  * the flat [B * k] score array from one batch of passage embeddings (row r of the batch is hit (row0 + r) % k of query
  * (row0 + r) / k; fp32 products, fp64 sums), vs_rerank_topk then orders every query's k hits by (score descending,
- * first-stage rank ascending) and gathers their ids.  Device pointers only; k <= 2048.                                    */
+ * first-stage rank ascending) and gathers their ids.  Device pointers only; k <= 2048.
+ * vs_rerank_scores: a zero passage element (+0.0 or -0.0) contributes nothing whatever the query holds (inf, NaN); a call writes
+ * scores[row0 .. row0 + n_rows) and nothing else (n_rows = 0: nothing).  vs_rerank_topk compares scores as floats: -0.0 and +0.0
+ * tie -- the first-stage rank decides -- and both come back as +0.0; -inf (the padding of a filtered first stage, id -1) stays
+ * last in its first-stage order; 64-bit ids pass through unchanged.                                                          */
 VS_API int vs_rerank_scores(const void* p_emb, int p_dtype, int64_t ldp, int64_t n_rows, int64_t row0, const float* q, int64_t ldq, int32_t B,
                             int32_t k, int32_t n_cols, float* scores, int device, void* stream);
 VS_API int vs_rerank_topk(const float* scores, const int64_t* hit_ids, int32_t B, int32_t k, int64_t* out_ids, float* out_scores, int device,

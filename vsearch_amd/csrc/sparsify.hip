@@ -349,6 +349,7 @@ __global__ __launch_bounds__(256) void rerank_scores_kernel(const T* p, int64_t 
 }
 
 // per query: (score desc, first-stage rank asc) -> ids of the hits in the new order + their scores.  k <= kSpThreads * 2.
+// Scores compare as floats: -0.0 enters the key as +0.0 (the two tie, the rank decides).
 __global__ __launch_bounds__(kSpThreads) void rerank_topk_kernel(const float* scores, const int64_t* hit_ids, int32_t B, int32_t k, int64_t* out_ids, float* out_scores) {
     __shared__ uint64_t keys[2 * kSpThreads];
     const int tid = threadIdx.x;
@@ -356,7 +357,7 @@ __global__ __launch_bounds__(kSpThreads) void rerank_topk_kernel(const float* sc
     while (n2 < k) n2 <<= 1;
     for (int b = blockIdx.x; b < B; b += gridDim.x) {
         __syncthreads();
-        for (int i = tid; i < n2; i += kSpThreads) keys[i] = i < k ? make_key(scores[(size_t)b * k + i], (uint32_t)i) : 0ull;
+        for (int i = tid; i < n2; i += kSpThreads) keys[i] = i < k ? make_key(canon_zero(scores[(size_t)b * k + i]), (uint32_t)i) : 0ull;
         wg_sort_desc<kSpThreads>(keys, n2, tid);
         for (int i = tid; i < k; i += kSpThreads) {
             const uint64_t key = keys[i];

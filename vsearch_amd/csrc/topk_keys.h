@@ -19,6 +19,9 @@ __device__ __forceinline__ float unflip_f32(uint32_t u) {
 __device__ __forceinline__ uint64_t make_key(float score, uint32_t row) {
     return ((uint64_t)flip_f32(score) << 32) | (uint32_t)(~row);
 }
+// flip_f32 orders -0.0 strictly below +0.0, the canonical order compares scores as floats (-0.0 == +0.0).  The search accumulators start
+// at +0.0 and never hold -0.0; keys built from CALLER-supplied scores (vs_merge_topk, vs_rerank_topk) pass them through this first.
+__device__ __forceinline__ float canon_zero(float f) { return (__float_as_uint(f) & 0x7FFFFFFFu) ? f : 0.f; }
 __device__ __forceinline__ float key_score(uint64_t k) { return unflip_f32((uint32_t)(k >> 32)); }
 __device__ __forceinline__ uint32_t key_row(uint64_t k) { return ~(uint32_t)k; }
 
