@@ -278,6 +278,36 @@ VS_API int vs_index_live_bitmap(const vs_index* index, uint32_t* out_words, int6
  *   bytes needed) when HBM cannot hold them -- setting option "blocked_postings" to 0 on `src` releases its postings copy.  Blocking.  */
 VS_API int vs_index_compact(const vs_index* src, int64_t rows_extra, int64_t packets_extra, int device, vs_index** out, int64_t* out_old_ids);
 
+/* ---- term constraints: must / must-not / should filters built from the index's own columns (no reference counterpart) --------------------
+ * A row HAS term c (a column id in [0, n_cols)) iff it stores column c with a non-zero value; under a threshold thr, iff the stored value
+ * v satisfies v >= thr (an fp16 store widens exactly, as vs_index_get_rows; a binary index stores 1; a stored zero counts under thr <= 0).
+ * The packets' padding column never matches; a dense index on the matrix cores stores its non-zero elements (vs_index_get_rows).  Tombstones do not enter: a deleted row still reports its terms (the search ANDs the live
+ * bitmap itself).  A program (must, must_not, should, min_should) allows row r iff r has every must term, no must_not term and at least
+ * min_should of the should terms: empty lists constrain nothing, min_should <= 0 constrains nothing, min_should above the number of should
+ * terms allows no row.  Bitmaps have the layout of vs_index_search_filtered (row r = bit r & 31 of word r >> 5).
+ * vs_index_term_bitmaps: out_words [T, ld_words] (ld_words >= W = (n_rows + 31) / 32): bitmap t holds the rows that have cols[t] (under
+ *   thr[t] when thr != NULL; a NaN thr[t] = no threshold for that term).  Words [0, W) of every bitmap are written whole, the bits past
+ *   n_rows are 0; words [W, ld_words) are not touched.  T in 1..4096; duplicate terms give identical bitmaps; a column outside [0, n_cols):
+ *   VS_EINVAL.  out_df [T] int64 (may be NULL): the set bits of every bitmap -- of its live rows only when live_only != 0.
+ *   One pass over the packets' column ids serves up to VS_TERM_FILTER_SLOTS distinct terms (more: further passes); values are read only for
+ *   the entries whose column is a term.  cols / thr: host arrays (control data; device arrays are copied back first, which synchronises
+ *   the stream).  out_words / out_df: host pointers, or device pointers on the index's device: with those and a non-NULL stream a CSR-packet
+ *   index only enqueues work.
+ * vs_term_filter_combine: out_words [B, out_ld] from T term bitmaps term_words [T, ld_words] of n_rows rows.  must / must_not / should:
+ *   [B, n_*] indices into the T bitmaps, padded with -1, each at most VS_TERM_FILTER_LIST wide (NULL with n_* = 0); min_should [B] (NULL: 0).
+ *   B = 1 is a program shared by the batch.  Words [0, W) of every output bitmap are written (bits past n_rows 0); when out_ld is a multiple
+ *   of 4 words and out_words is 16-byte aligned, so are the zero words up to the next multiple of 4.  An index outside [-1, T): VS_EINVAL for
+ *   host lists, ignored for device lists.  All pointers host, or all device pointers on `device`; with device pointers and a non-NULL stream
+ *   the call only enqueues work.                                                                                                          */
+#define VS_TERM_FILTER_SLOTS 255     /* distinct terms one pass of the scan serves */
+#define VS_TERM_FILTER_TERMS 4096    /* terms a call takes at most */
+#define VS_TERM_FILTER_LIST  64      /* entries of a must / must_not / should list at most */
+VS_API int vs_index_term_bitmaps(vs_index* index, const int32_t* cols, const float* thr, int32_t T, uint32_t* out_words, int64_t ld_words,
+                                 int64_t* out_df, int live_only, void* stream);
+VS_API int vs_term_filter_combine(const uint32_t* term_words, int64_t ld_words, int64_t n_rows, int32_t T, const int32_t* must, int32_t n_must,
+                                  const int32_t* must_not, int32_t n_must_not, const int32_t* should, int32_t n_should,
+                                  const int32_t* min_should, int32_t B, uint32_t* out_words, int64_t out_ld, int device, void* stream);
+
 /* Dense score matrix [B, n_rows] fp32 -- the intermediate index.py:91 materialises.  Used by the
  * parity tests to check every score, not just the top-k.                                         */
 VS_API int vs_index_scores(vs_index* index, const void* q, int q_dtype, int64_t ldq, int32_t B,
@@ -380,6 +410,12 @@ VS_API int  vs_shard_group_queries_from_rows(vs_shard_group* group, const int64_
  * host).  vs_shard_group_restore_rows with ids == NULL restores every row.  Blocking.                                                  */
 VS_API int  vs_shard_group_delete_rows(vs_shard_group* group, const int64_t* ids, int64_t n);
 VS_API int  vs_shard_group_restore_rows(vs_shard_group* group, const int64_t* ids, int64_t n);
+/* vs_index_term_bitmaps over the group's rows: every shard scans its rows on its own GPU; the first shard's device re-bases each shard's
+ * words to the shard's first global row (generally not a multiple of 32: the seam words take bits of two shards) and ORs them into the
+ * global bitmaps; document frequencies are summed.  Equal to the unsharded call bit for bit.  out_words [T, ld_words >= (total rows + 31)
+ * / 32] / out_df: host pointers or device pointers on the first shard's device.  Blocking.                                              */
+VS_API int  vs_shard_group_term_bitmaps(vs_shard_group* group, const int32_t* cols, const float* thr, int32_t T, uint32_t* out_words,
+                                        int64_t ld_words, int64_t* out_df, int live_only);
 VS_API void vs_shard_group_destroy(vs_shard_group* group);
 
 /* SparseIndex.save (index.py:181-202) needs crow/col/values back: int64 rowptr [n_rows+1], int64

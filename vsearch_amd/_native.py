@@ -17,6 +17,8 @@ CSRC = os.path.join(_HERE, "csrc")
 VS_OK, VS_EINVAL, VS_ERANGE, VS_ENOMEM, VS_EHIP, VS_EUNSUPPORTED, VS_ENODEVICE = 0, -1, -2, -3, -4, -5, -6
 VS_F32, VS_F16, VS_I32, VS_I64, VS_U16, VS_U8, VS_NONE = 0, 1, 2, 3, 4, 5, -1
 VS_KIND_DENSE, VS_KIND_CSR = 0, 1
+# term filters (VS_TERM_FILTER_*): distinct terms a pass of the scan serves, terms a call takes, entries of a must / must_not / should list
+TERM_FILTER_SLOTS, TERM_FILTER_TERMS, TERM_FILTER_LIST = 255, 4096, 64
 
 
 class VsearchNativeError(RuntimeError):
@@ -61,6 +63,8 @@ _SIGNATURES = {
     "vs_index_live_rows": ([_vp, C.POINTER(_i64)], _int),
     "vs_index_live_bitmap": ([_vp, _vp, _i64], _int),
     "vs_index_compact": ([_vp, _i64, _i64, _int, C.POINTER(_vp), _vp], _int),
+    "vs_index_term_bitmaps": ([_vp, _vp, _vp, _i32, _vp, _i64, _vp, _int, _vp], _int),
+    "vs_term_filter_combine": ([_vp, _i64, _i64, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i64, _int, _vp], _int),
     "vs_index_prepare": ([_vp, _vp], _int),
     "vs_index_info": ([_vp, C.POINTER(IndexInfo)], _int),
     "vs_index_set_option": ([_vp, C.c_char_p, _int], _int),
@@ -76,6 +80,7 @@ _SIGNATURES = {
     "vs_shard_group_queries_from_rows": ([_vp, _vp, _i32, _i32, _i64, _vp, _i64, _vp, _int, _i64, C.c_float, _vp, _i64], _int),
     "vs_shard_group_delete_rows": ([_vp, _vp, _i64], _int),
     "vs_shard_group_restore_rows": ([_vp, _vp, _i64], _int),
+    "vs_shard_group_term_bitmaps": ([_vp, _vp, _vp, _i32, _vp, _i64, _vp, _int], _int),
     "vs_shard_group_destroy": ([_vp], None),
     "vs_merge_topk": ([_vp, _vp, _i32, _i64, _i32, _vp, _vp, _int, _vp], _int),
     "vs_topk_exclude": ([_vp, _vp, _i32, _i32, _i64, _vp, _i32, _i64, _i32, _vp, _vp, _int, _vp], _int),

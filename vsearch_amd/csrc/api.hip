@@ -289,6 +289,7 @@ extern "C" int vs_index_set_option(vs_index* idx, const char* name, int value) {
 // pairs per shard, moved with peer copies over xGMI to the first shard's device and merged there.
 struct vs_shard_group {
     std::vector<vs_index*> shards;
+    std::vector<int> device;                  // of every shard: destroy must not read the shards, which their owner may have freed first
     std::vector<int64_t> row0;
     std::vector<hipStream_t> streams;
     std::vector<bool> owns_stream;            // (shards on one device share the first one's stream)
@@ -301,8 +302,8 @@ struct vs_shard_group {
 
 extern "C" void vs_shard_group_destroy(vs_shard_group* g) {
     if (!g) return;
-    for (size_t i = 0; i < g->shards.size(); ++i) {
-        (void)hipSetDevice(g->shards[i]->device);
+    for (size_t i = 0; i < g->device.size(); ++i) {
+        (void)hipSetDevice(g->device[i]);
         if (i < g->streams.size() && g->streams[i]) (void)hipStreamSynchronize(g->streams[i]);
         if (i < g->done.size() && g->done[i]) (void)hipEventDestroy(g->done[i]);
         if (i < g->q.size()) delete g->q[i];
@@ -311,8 +312,8 @@ extern "C" void vs_shard_group_destroy(vs_shard_group* g) {
         if (i < g->filt.size()) delete g->filt[i];
     }
     for (size_t i = 0; i < g->streams.size(); ++i)
-        if (g->streams[i] && i < g->owns_stream.size() && g->owns_stream[i]) { (void)hipSetDevice(g->shards[i]->device); (void)hipStreamDestroy(g->streams[i]); }
-    if (!g->shards.empty()) (void)hipSetDevice(g->shards[0]->device);
+        if (g->streams[i] && i < g->owns_stream.size() && g->owns_stream[i]) { (void)hipSetDevice(g->device[i]); (void)hipStreamDestroy(g->streams[i]); }
+    if (!g->device.empty()) (void)hipSetDevice(g->device[0]);
     delete g;
 }
 
@@ -327,6 +328,7 @@ extern "C" int vs_shard_group_create(vs_index* const* shards, int32_t n_shards, 
         if (!s) return fail(VS_EINVAL, "shard %d is NULL", i);
         if (s->n_cols != shards[0]->n_cols) return fail(VS_EINVAL, "shard %d has %d columns, shard 0 has %d", i, s->n_cols, shards[0]->n_cols);
         g->shards.push_back(s);
+        g->device.push_back(s->device);
         g->row0.push_back(row);
         row += s->n_rows;
         VS_HIP(hipSetDevice(s->device));
@@ -542,6 +544,18 @@ extern "C" int vs_shard_group_queries_from_rows(vs_shard_group* g, const int64_t
     VS_TRY(group_need_device());
     if (!g) return fail(VS_EINVAL, "NULL argument");
     return vs_shard_group_queries_from_rows_impl(g->shards, g->row0, g->streams, ids, B, m, ld_ids, weights, ldw, q, q_dtype, ldq, alpha, out_q, ldo);
+}
+
+// (term_filter.hip: every shard scans its own rows, the first shard's device ORs the re-based words into the global bitmaps)
+int vs_shard_group_term_bitmaps_impl(const std::vector<vs_index*>& shards, const std::vector<int64_t>& row0, const std::vector<hipStream_t>& streams,
+                                     const int32_t* cols, const float* thr, int32_t T, uint32_t* out_words, int64_t ld_words, int64_t* out_df,
+                                     int live_only);
+
+extern "C" int vs_shard_group_term_bitmaps(vs_shard_group* g, const int32_t* cols, const float* thr, int32_t T, uint32_t* out_words, int64_t ld_words,
+                                           int64_t* out_df, int live_only) {
+    VS_TRY(group_need_device());
+    if (!g) return fail(VS_EINVAL, "NULL argument");
+    return vs_shard_group_term_bitmaps_impl(g->shards, g->row0, g->streams, cols, thr, T, out_words, ld_words, out_df, live_only);
 }
 
 extern "C" int vs_shard_group_delete_rows(vs_shard_group* g, const int64_t* ids, int64_t n) {

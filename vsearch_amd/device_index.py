@@ -286,6 +286,57 @@ def _queries_from_rows(call, ids, weights, q, alpha, B, m, V, device, stream):
         return torch.from_numpy(out)
     return out
 
+def _term_args(cols, thr=None):
+    """Terms of term_bitmaps() / doc_freq() -> (int32 [T] columns, float32 [T] thresholds or None).  cols: integer column ids (a
+    list / ndarray / tensor, or one int); thr: None, a dict {column: threshold}, or one threshold per term (None / NaN: no threshold).
+    Pure host work: argument errors come before any device work."""
+    if _is_torch(cols):
+        cols = cols.detach().cpu().numpy()
+    c = np.atleast_1d(np.asarray(cols))
+    if c.ndim != 1 or c.size == 0:
+        raise ValueError("cols must be a non-empty 1-D list of column ids")
+    if c.dtype == np.bool_ or not np.issubdtype(c.dtype, np.integer):
+        raise TypeError(f"cols must be integer column ids, got {c.dtype}")
+    if c.size > nat.TERM_FILTER_TERMS:
+        raise ValueError(f"at most {nat.TERM_FILTER_TERMS} terms a call, got {c.size}")
+    if int(c.min()) < 0 or int(c.max()) > 0x7FFFFFFF:
+        raise ValueError(f"column {int(c.min()) if int(c.min()) < 0 else int(c.max())} is not a column of the index")
+    c = np.ascontiguousarray(c, dtype=np.int32)
+    if thr is None:
+        return c, None
+    if isinstance(thr, dict):
+        t = np.array([float(thr.get(int(x), np.nan)) for x in c], dtype=np.float32)
+    else:
+        if _is_torch(thr):
+            thr = thr.detach().cpu().numpy()
+        t = np.array([np.nan if x is None else float(x) for x in np.atleast_1d(np.asarray(thr, dtype=object))], dtype=np.float32)
+        if t.shape != c.shape:
+            raise ValueError(f"thr has {t.size} entries, cols {c.size}")
+    return c, (None if bool(np.isnan(t).all()) else np.ascontiguousarray(t))
+
+
+def _term_bitmaps(call, n_rows, n_cols, device, cols, thr, want_df=False, live_only=True, ld=None, stream=True):
+    """the shared body of DeviceIndex / ShardGroup .term_bitmaps / .doc_freq: call(cols, thr, T, words, ld, df, live_only[, stream])
+    -> (int32 CUDA tensor [T, ld], int64 CUDA tensor [T] or None)"""
+    import torch
+    c, t = _term_args(cols, thr)
+    if int(c.max()) >= n_cols:
+        raise ValueError(f"column {int(c.max())} is outside [0, {n_cols})")
+    nat.require_device()
+    T, W = int(c.shape[0]), (int(n_rows) + 31) // 32
+    ld = W if ld is None else int(ld)
+    dev = torch.device("cuda", device)
+    words = torch.zeros((T, max(ld, 1)), dtype=torch.int32, device=dev) if ld > W else torch.empty((T, max(ld, 1)), dtype=torch.int32, device=dev)
+    df = torch.zeros(T, dtype=torch.int64, device=dev) if want_df else None
+    args = (C.c_void_p(c.ctypes.data), C.c_void_p(t.ctypes.data) if t is not None else None, T, C.c_void_p(words.data_ptr()), ld,
+            C.c_void_p(df.data_ptr()) if want_df else None, 1 if live_only else 0)
+    if stream:
+        nat.check(call(*args, current_stream(device)))
+    else:
+        torch.cuda.current_stream(device).synchronize()             # (the group runs on its own streams)
+        nat.check(call(*args))
+    return words, df
+
 class DeviceIndex:
     """Owner of one device-resident index shard (CSR packets or dense)."""
 
@@ -560,6 +611,23 @@ class DeviceIndex:
             nat.check(nat.lib().vs_index_compact(*args))
         return DeviceIndex(h), old
 
+    # ---- term constraints (vsearch_amd.doc_filter.DocFilter.from_terms) ------------------------------
+    def _term_words(self, cols, thr=None, want_df=False, live_only=True, ld=None):
+        info = self.info()
+        return _term_bitmaps(lambda *a: nat.lib().vs_index_term_bitmaps(self._h, *a), info.n_rows, info.n_cols, self.device, cols, thr,
+                             want_df, live_only, ld, True)
+
+    def term_bitmaps(self, cols, thr=None):
+        """One bitmap of rows per term (vs_index_term_bitmaps) -> int32 CUDA tensor [T, W], W = ceil(n_rows / 32): bit r of bitmap t is set
+        iff row r stores column cols[t] with a non-zero value -- with a threshold, iff the stored value is >= it.  thr: a dict {column:
+        threshold} or one threshold per term (None / NaN: none).  A deleted row still reports its terms.  A column outside [0, V) raises
+        ValueError.  Enqueued on torch's current stream."""
+        return self._term_words(cols, thr)[0]
+
+    def doc_freq(self, cols, thr=None, live_only=True):
+        """Rows that have each term -> int64 CUDA tensor [T]; live_only: deleted rows do not count."""
+        return self._term_words(cols, thr, True, live_only)[1]
+
     # ---- query by example ------------------------------------------------------------------------
     @property
     def n_rows(self) -> int:
@@ -743,6 +811,21 @@ class ShardGroup:
             olds.append(old + row0)
             row0 += s.n_rows
         return ShardGroup(new), (np.concatenate(olds) if olds else np.zeros(0, dtype=np.int64))
+
+    # ---- term constraints -----------------------------------------------------------------------------------
+    def _term_words(self, cols, thr=None, want_df=False, live_only=True, ld=None):
+        n_cols = int(self._shards[0].info().n_cols)
+        return _term_bitmaps(lambda *a: nat.lib().vs_shard_group_term_bitmaps(self._h, *a), self.n_rows, n_cols, self._shards[0].device, cols, thr,
+                             want_df, live_only, ld, False)
+
+    def term_bitmaps(self, cols, thr=None):
+        """DeviceIndex.term_bitmaps over the group's rows (vs_shard_group_term_bitmaps): every shard scans its rows on its own GPU, the first
+        shard's GPU ORs the re-based words together; equal to the unsharded index word for word.  Blocking."""
+        return self._term_words(cols, thr)[0]
+
+    def doc_freq(self, cols, thr=None, live_only=True):
+        """DeviceIndex.doc_freq summed over the shards."""
+        return self._term_words(cols, thr, True, live_only)[1]
 
     def explain(self, q, ids, topn: int = 10) -> Explanation:
         """DeviceIndex.explain over the group's rows (global ids): every shard explains the pairs it owns on its own GPU, the first

@@ -8,12 +8,19 @@ the index of only those rows returns, with the full index's ids); positions beyo
     f = DocFilter.from_mask(visible)                          # bool [N] or [B, N]
     f = DocFilter.from_ids(deleted_ids, n_rows, allow=False)  # everything but these rows
     res = index.search(q, k, filter=f)
+
+Term constraints build the bitmap from the index's own columns on the GPU (``vs_index_term_bitmaps`` + ``vs_term_filter_combine``):
+
+    f = DocFilter.from_terms(index, must=[c1], must_not=[c2], should=[c3, c4, c5], min_should=2)
+    res = index.search(q, k, filter=visible & f)
 """
 from __future__ import annotations
 
 import ctypes as C
 
 import numpy as np
+
+from typing import NamedTuple
 
 from . import _native as nat
 
@@ -31,6 +38,147 @@ def _device_of(device):
     if d.type != "cuda":
         raise ValueError(f"a DocFilter lives on a GPU, not on {d}")
     return torch.device("cuda", d.index if d.index is not None else torch.cuda.current_device())
+
+
+# ---- term programs: pure argument normalisation (no GPU, no torch) ------------------------------------------------------------------
+class TermProgram(NamedTuple):
+    """A must / must_not / should program in the form vs_term_filter_combine takes: `cols` the union of distinct columns in order of first
+    appearance, `thr` their thresholds (NaN: none) or None, the lists as indices into `cols` ([B, n], padded with -1; B = 1 for a program
+    shared by the batch), `min_should` [B], and whether the program is one per query."""
+    cols: np.ndarray          # int32 [T]
+    thr: object               # float32 [T] or None
+    must: np.ndarray          # int32 [B, n_must]
+    must_not: np.ndarray      # int32 [B, n_must_not]
+    should: np.ndarray        # int32 [B, n_should]
+    min_should: np.ndarray    # int32 [B]
+    per_query: bool
+
+
+def _is_seq(x) -> bool:
+    return isinstance(x, (list, tuple, np.ndarray)) or type(x).__module__.startswith("torch")
+
+
+def _as_column(x, name) -> int:
+    if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)):
+        if type(x).__module__.startswith("torch") and getattr(x, "ndim", 1) == 0 and not x.is_floating_point() and str(x.dtype) != "torch.bool":
+            x = int(x)
+        else:
+            raise TypeError(f"{name}: a term is an integer column id, got {type(x).__name__} {x!r}")
+    x = int(x)
+    if x < 0:
+        raise ValueError(f"{name}: column id {x} is negative")
+    return x
+
+
+def _term_lists(x, name):
+    """one list argument -> (list of per-query lists of ints, per_query)"""
+    if x is None:
+        return [[]], False
+    if not _is_seq(x):
+        raise TypeError(f"{name}: a sequence of column ids, or one sequence per query; got {type(x).__name__}")
+    items = list(x)
+    nested = [_is_seq(it) and getattr(it, "ndim", 1) != 0 for it in items]
+    if items and all(nested):
+        return [[_as_column(c, name) for c in it] for it in items], True
+    if any(nested):
+        raise TypeError(f"{name}: either column ids, or one sequence per query -- not a mix of both")
+    return [[_as_column(c, name) for c in items]], False
+
+
+def normalize_terms(must=None, must_not=None, should=None, min_should=None, thr=None, max_list: int = nat.TERM_FILTER_LIST,
+                    max_terms: int = nat.TERM_FILTER_TERMS) -> TermProgram:
+    """The arguments of DocFilter.from_terms -> a TermProgram.  Each list: None, a flat sequence of column ids (the same for every query)
+    or a list of B sequences (one per query, ragged).  Duplicate terms collapse -- inside a list, and across lists to one slot of the
+    union.  min_should: None (1 for a query whose should list is non-empty, else 0), an int, or B ints.  thr: {column: threshold}.
+    Raises TypeError / ValueError for non-integer or negative terms, lists of different batch sizes, a list of more than `max_list` terms, more
+    than `max_terms` distinct terms, a negative min_should."""
+    parsed = {}
+    B = None
+    for name, x in (("must", must), ("must_not", must_not), ("should", should)):
+        lists, per = _term_lists(x, name)
+        parsed[name] = (lists, per)
+        if per:
+            if B is not None and B != len(lists):
+                raise ValueError(f"{name} holds lists for {len(lists)} queries, another list for {B}")
+            B = len(lists)
+    ms_seq = None
+    if min_should is not None:
+        if _is_seq(min_should) and getattr(min_should, "ndim", 1) != 0:
+            ms_seq = [m for m in min_should]
+            if B is not None and B != len(ms_seq):
+                raise ValueError(f"min_should holds {len(ms_seq)} entries, the lists are for {B} queries")
+            B = len(ms_seq)
+        else:
+            ms_seq = None
+        for m in (ms_seq if ms_seq is not None else [min_should]):
+            if isinstance(m, (bool, np.bool_)) or not isinstance(m, (int, np.integer)):
+                raise TypeError(f"min_should must be an int, got {type(m).__name__}")
+            if int(m) < 0:
+                raise ValueError(f"min_should must be >= 0, got {int(m)}")
+    per_query = B is not None
+    if B == 0:
+        raise ValueError("per-query lists for zero queries")
+    B = B or 1
+    if thr is not None and not isinstance(thr, dict):
+        raise TypeError("thr: a dict {column: threshold}")
+    slot = {}
+    out = {}
+    for name in ("must", "must_not", "should"):
+        lists, per = parsed[name]
+        rows = []
+        for b in range(B):
+            seen = []
+            for c in (lists[b] if per else lists[0]):
+                if c not in slot:
+                    slot[c] = len(slot)
+                if slot[c] not in seen:
+                    seen.append(slot[c])
+            if len(seen) > max_list:
+                raise ValueError(f"{name}: {len(seen)} terms for query {b}, at most {max_list}")
+            rows.append(seen)
+        width = max(len(r) for r in rows)
+        arr = np.full((B, width), -1, dtype=np.int32)
+        for b, r in enumerate(rows):
+            arr[b, :len(r)] = r
+        out[name] = arr
+    if len(slot) > max_terms:
+        raise ValueError(f"{len(slot)} distinct terms, at most {max_terms} a filter")
+    cols = np.array(list(slot), dtype=np.int64)
+    if cols.size and int(cols.max()) > 0x7FFFFFFF:
+        raise ValueError(f"column id {int(cols.max())} is not a column of an index")
+    n_should = (out["should"] >= 0).sum(axis=1)
+    if min_should is None:
+        ms = (n_should > 0).astype(np.int32)
+    elif ms_seq is not None:
+        ms = np.array([int(m) for m in ms_seq], dtype=np.int32)
+    else:
+        ms = np.full(B, int(min_should), dtype=np.int32)
+    t = None
+    if thr:
+        t = np.array([float(thr.get(int(c), np.nan)) for c in cols], dtype=np.float32)
+        if bool(np.isnan(t).all()):
+            t = None
+    return TermProgram(cols.astype(np.int32), t, out["must"], out["must_not"], out["should"], np.minimum(ms, max_list + 1).astype(np.int32), per_query)
+
+
+def terms_to_columns(terms, vocab, shift: int, name: str = "terms"):
+    """Terms given as column ids or vocabulary tokens (strings) -> column ids; nesting (one list per query) is kept.  A string is looked up in
+    `vocab` (the tokenizer's token -> id mapping); its column is token id - shift.  A string that is not one vocabulary entry, or whose id
+    is below the shift, raises ValueError naming it."""
+    if terms is None:
+        return None
+    if isinstance(terms, str):
+        terms = [terms]
+    def one(t):
+        if isinstance(t, str):
+            tid = vocab.get(t) if hasattr(vocab, "get") else None
+            if tid is None:
+                raise ValueError(f"{name}: {t!r} is not one entry of the vocabulary (pass the word pieces of a longer word one by one)")
+            if int(tid) < int(shift):
+                raise ValueError(f"{name}: {t!r} (token id {int(tid)}) lies below the vocabulary shift {int(shift)}: the index has no column for it")
+            return int(tid) - int(shift)
+        return t
+    return [[one(t) for t in it] if (_is_seq(it) and getattr(it, "ndim", 1) != 0) else one(it) for it in terms]
 
 
 class DocFilter:
@@ -114,6 +262,63 @@ class DocFilter:
             r, c = (ids >= 0).nonzero(as_tuple=True)                     # only the real entries: a -1 pad writes nothing
             mask[r, ids[r, c]] = True
         return cls.from_mask(mask if allow else ~mask, device=dev)
+
+    @classmethod
+    def from_terms(cls, index, must=None, must_not=None, should=None, min_should=None, thr=None) -> "DocFilter":
+        """The rows of `index` that have every `must` term, no `must_not` term and at least `min_should` of the `should` terms (default 1
+        when `should` is given).  A row has term c -- a column id -- iff it stores column c with a non-zero value; with thr = {c: t}, iff
+        the stored value is >= t.  Each list is a flat sequence of column ids (one program for the batch) or a list of B sequences (one per
+        query, ragged).  index: a DeviceIndex, a ShardGroup, or a facade Index (columns in its vector's space).  The union of the distinct
+        terms is scanned once on the GPU (vs_index_term_bitmaps), then combined (vs_term_filter_combine); deleted rows are not special
+        here -- every search ANDs the live rows itself."""
+        prog = normalize_terms(must, must_not, should, min_should, thr)
+        target = index._explain_target()[0] if hasattr(index, "_explain_target") else index
+        if not hasattr(target, "_term_words"):
+            raise TypeError(f"DocFilter.from_terms takes a DeviceIndex, a ShardGroup or an Index, not {type(index).__name__}")
+        torch = _torch()
+        from .device_index import current_stream
+        n = int(target.n_rows)
+        if n <= 0:
+            raise ValueError("the index has no rows")
+        nat.require_device()
+        dev = torch.device("cuda", int(target.device))
+        W = (n + 31) // 32
+        T = int(prog.cols.shape[0])
+        ld = (W + 3) // 4 * 4
+        terms = target._term_words(prog.cols, prog.thr, ld=ld)[0] if T else None
+        B = int(prog.min_should.shape[0])
+        lists = [torch.from_numpy(np.ascontiguousarray(a)).to(dev) if a.shape[1] else None for a in (prog.must, prog.must_not, prog.should)]
+        ms = torch.from_numpy(prog.min_should).to(dev)
+        words = torch.empty((B, W), dtype=torch.int32, device=dev)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+        nat.check(nat.lib().vs_term_filter_combine(ptr(terms), ld, n, T, ptr(lists[0]), int(prog.must.shape[1]), ptr(lists[1]), int(prog.must_not.shape[1]),
+                                                   ptr(lists[2]), int(prog.should.shape[1]), ptr(ms), B, ptr(words), W, dev.index,
+                                                   current_stream(dev.index)))
+        return cls(words if prog.per_query else words[0], n)
+
+    # ---- set algebra on the packed words --------------------------------------------------------------
+    def _pair(self, other):
+        if not isinstance(other, DocFilter):
+            return None
+        if other.n_rows != self.n_rows:
+            raise ValueError(f"filters over {self.n_rows} and {other.n_rows} rows do not combine")
+        if self.per_query and other.per_query and self.n_queries != other.n_queries:
+            raise ValueError(f"per-query filters for {self.n_queries} and {other.n_queries} queries do not combine")
+        return self.words, other.words.to(self.words.device)         # (a shared filter [W] broadcasts against a per-query one [B, W])
+
+    def __and__(self, other):
+        p = self._pair(other)
+        return NotImplemented if p is None else DocFilter(p[0] & p[1], self.n_rows)
+
+    def __or__(self, other):
+        p = self._pair(other)
+        return NotImplemented if p is None else DocFilter(p[0] | p[1], self.n_rows)
+
+    def __invert__(self):
+        w = ~self.words
+        if self.n_rows & 31:                                         # the bits past n_rows stay 0
+            w[..., -1] &= (1 << (self.n_rows & 31)) - 1
+        return DocFilter(w, self.n_rows)
 
     def to(self, device) -> "DocFilter":
         dev = _device_of(device)

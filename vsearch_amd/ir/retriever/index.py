@@ -387,6 +387,21 @@ class Index:
         out_ids, out_sc = topk_exclude(res.ids.to(gpu).contiguous(), res.scores.to(gpu).float().contiguous(), ids, k, gpu_ord)
         return SearchResults(self._to_api(out_ids), self._to_api(out_sc.to(self._dtype)))
 
+    # ---- term constraints (not in the reference: must / must-not / should filters from the index's own columns) --------------------
+    def term_filter(self, must=None, must_not=None, should=None, min_should=None, thr=None):
+        """A DocFilter of the documents that have every `must` term, no `must_not` term and at least `min_should` of the `should` terms
+        (default 1 when `should` is given) -- for ``search(..., filter=)``.  Terms are column ids of the vector (no shift); a document has
+        a term iff it stores a non-zero value there, with thr = {column: t} iff the value is >= t.  Each list: column ids (one program for
+        the batch) or one list per query.  Built on the GPU from the index rows (DocFilter.from_terms), on every shard of a row-sharded
+        index; combine with other filters by ``&``, ``|``, ``~``."""
+        from ...doc_filter import DocFilter
+        return DocFilter.from_terms(self, must=must, must_not=must_not, should=should, min_should=min_should, thr=thr)
+
+    def doc_freq(self, cols, thr=None, live_only: bool = True):
+        """Documents that have each term of `cols` (column ids of the vector) -> int64 tensor [T]; deleted documents do not count unless
+        live_only=False."""
+        return self._to_api(self._explain_target()[0].doc_freq(cols, thr=thr, live_only=live_only))
+
     # ---- mutable index (not in the reference: its index is rebuilt) ------------------------------------------------------------------
     def _mutable_target(self):
         """DeviceIndex, or the ShardGroup of a row-sharded index: both have delete_rows / restore_rows / n_live / compact"""

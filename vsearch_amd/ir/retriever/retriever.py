@@ -61,18 +61,42 @@ class Retriever(BiEncoder):
 
     # ---- retrieval (retriever.py:107-148) ----------------------------------------------------------
     def retrieve(self, queries: Union[List[str], np.ndarray, T], k: int = 5, dropout: float = 0, a: int = None,
-                 index: Index = None, rerank: bool = False, batch_size: int = 32, filter=None) -> SearchResults:
+                 index: Index = None, rerank: bool = False, batch_size: int = 32, filter=None, must=None, must_not=None, should=None,
+                 min_should: int = None) -> SearchResults:
         """`filter` (not in the reference): restrict the hits to part of the index (Index.search); hits beyond the allowed rows are
-        padding (id -1, score -inf), stay last through the rerank and are not re-embedded."""
+        padding (id -1, score -inf), stay last through the rerank and are not re-embedded.  `must` / `must_not` / `should` / `min_should`:
+        term constraints (``term_filter``), ANDed with `filter` when both are given."""
         index = index or self.index
         if index is None:
             raise RuntimeError("no index: call build_index / load_index first")
+        if must is not None or must_not is not None or should is not None or min_should is not None:
+            terms = self.term_filter(must=must, must_not=must_not, should=should, min_should=min_should, index=index)
+            if filter is not None:
+                from ...doc_filter import as_doc_filter
+                filter = as_doc_filter(filter, terms.n_rows, device=terms.device) & terms
+            else:
+                filter = terms
         a = a or self.encoder_q.config.topk
         q_emb = self.process_query(queries, dropout, a, batch_size=batch_size)
         results = index.search(q_emb, k=k, filter=filter) if filter is not None else index.search(q_emb, k=k)
         if rerank and index.index_type == IndexType.BAG_OF_TOKEN:
             results = self._rerank(index, q_emb, results, k, batch_size)
         return results
+
+    def term_filter(self, must=None, must_not=None, should=None, min_should: int = None, thr=None, index: Index = None):
+        """Index.term_filter with terms given as column ids or as vocabulary tokens (strings): a string is looked up in the passage
+        tokenizer's vocabulary and its column is token id - shift.  A string that is not one vocabulary entry (a longer word: pass its word
+        pieces), or whose id lies below the shift, raises ValueError.  thr: {column id or token: threshold}."""
+        from ...doc_filter import terms_to_columns
+        index = index or self.index
+        if index is None:
+            raise RuntimeError("no index: call build_index / load_index first")
+        vocab = self.encoder_p.tokenizer.vocab
+        shift = int(self.encoder_p.config.shift_vocab_num)
+        cols = {name: terms_to_columns(x, vocab, shift, name) for name, x in (("must", must), ("must_not", must_not), ("should", should))}
+        if thr is not None:
+            thr = dict(zip(terms_to_columns(list(thr), vocab, shift, "thr"), thr.values()))
+        return index.term_filter(must=cols["must"], must_not=cols["must_not"], should=cols["should"], min_should=min_should, thr=thr)
 
     def explain_results(self, queries: Union[List[str], np.ndarray, T], results: SearchResults, topn: int = 10, index: Index = None,
                         a: int = None, batch_size: int = 32) -> List[List[Dict[str, float]]]:
