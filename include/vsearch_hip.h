@@ -346,8 +346,8 @@ VS_API int  vs_index_prepare(vs_index* index, void* stream);
  *                       postings per (block, column), walked by a generated asm loop) while they stay within 3 x the CSR bytes, else the
  *                       list walk over records; a binary index gets BAG-OF-TOKEN CHUNKS (bp_bq.h: 64-byte chunks of 32 document ids);
  *                       0 = the list walk over records (bp_walk.h: a list per 8-lane group), 4 = quad chunks whatever their size,
- *                       5 = the record walk of a binary index (bp_bin.h), 6 = bag-of-token chunks; 1 - 3 = the experimental walks of round 3
- *                       (flat worklists, two accumulator sets, streamed records: only in a `make EXPERIMENTAL=1` build).  A copy that does
+ *                       5 = the record walk of a binary index (bp_bin.h), 6 = bag-of-token chunks; 1 - 3 = the experimental walks of round 3,
+ *                       removed (VS_EUNSUPPORTED; their measurements: docs/EXPERIMENTS.md).  A copy that does
  *                       not fit HBM falls back to the records, then to the CSR scan.  All return identical results; a change rebuilds the copy.
  *   "postings_head_gemm" -1 / 1 = the head columns' part of the filter sums comes from the head pre-pass (bp_head.h: one MFMA product per
  *                       pass of query tiles, columns in >= 1/8 of the documents, up to 1024; from 1 M documents on, HBM permitting: >= 1/16, up to 1536), 0 = multiplied inside the walk (round 4)

@@ -60,19 +60,9 @@ def _oracle_pin(seed, n, q, ids, sc, k, kind=0, val_law=0, nnz=768, windows=48, 
             assert missing.size == 0, f"query {b}: rows {missing[:5]} beat the k-th score {kth} and were not returned"
 
 
-def _experimental_walks(idx):
-    """the experimental walks of round 3 (postings_walk = 1 .. 3) are compiled only with `make EXPERIMENTAL=1`"""
-    try:
-        idx.set_option("postings_walk", 1)
-    except Exception:
-        return False
-    idx.set_option("postings_walk", -1)
-    return True
-
-
 def _modes(idx, q, k, want_quant, tied_queries=0):
     """-> results of {csr scan, filter on the default walk (quad chunks where they apply), filter on the list walk, both on exact records,
-    forced fallback x 2, the experimental walks when the library has them, fp64 walk}; checks paths and bit-equality."""
+    forced fallback x 2, fp64 walk}; checks paths and bit-equality."""
     ref_ids, ref_sc, info = _search(idx, q, k, blocked_postings=0)
     assert info.last_path == 1
     out = {}
@@ -83,13 +73,6 @@ def _modes(idx, q, k, want_quant, tied_queries=0):
              ("fallback", dict(postings_filter=1, postings_quant=-1, postings_force_fallback=1, postings_walk=-1)),
              ("fallback-list-walk", dict(postings_filter=1, postings_quant=-1, postings_force_fallback=1, postings_walk=0)),
              ("fallback-exact-records", dict(postings_filter=1, postings_quant=0, postings_force_fallback=1, postings_walk=-1))]
-    if _experimental_walks(idx):
-        modes += [("filter-flat-walk", dict(postings_filter=1, postings_quant=-1, postings_force_fallback=0, postings_walk=1)),
-                  ("filter-flat-walk-exact-records", dict(postings_filter=1, postings_quant=0, postings_force_fallback=0, postings_walk=1)),
-                  ("filter-pipe-walk", dict(postings_filter=1, postings_quant=-1, postings_force_fallback=0, postings_walk=2)),
-                  ("filter-pipe-walk-exact-records", dict(postings_filter=1, postings_quant=0, postings_force_fallback=0, postings_walk=2)),
-                  ("filter-stream-walk", dict(postings_filter=1, postings_quant=-1, postings_force_fallback=0, postings_walk=3)),
-                  ("filter-stream-walk-exact-records", dict(postings_filter=1, postings_quant=0, postings_force_fallback=0, postings_walk=3))]
     modes += [("fp64-walk", dict(postings_filter=0, postings_force_fallback=0, postings_walk=-1))]
     for name, opts in modes:
         ids, sc, info = _search(idx, q, k, blocked_postings=1, **opts)
@@ -105,6 +88,37 @@ def _modes(idx, q, k, want_quant, tied_queries=0):
     idx.set_option("postings_filter", 1)
     idx.set_option("postings_walk", -1)
     return ref_ids, ref_sc
+
+
+def test_removed_walks_are_refused_and_leave_the_handle_as_it_was():
+    """postings_walk = 1, 2, 3 named the three experimental walks of round 3; their source is gone (docs/EXPERIMENTS.md keeps the
+    measurements).  The library refuses the values with VS_EUNSUPPORTED -- through the Python layer that code is NotImplementedError
+    (nat.check) -- and a refused call changes nothing.  The library has no getter for an option: the preference is read back through the
+    copy it selects.  4 forces quad chunks, where auto (and 0 .. 3) would keep records on an index this small; a changed preference would
+    also release the copy that prepare() built."""
+    ip, ix, d = oracle.synth_csr(0, 0, 300)
+    q = oracle.synth_queries(1, 5)
+
+    def handle():
+        idx = DeviceIndex.from_csr(ip, ix, d, V)
+        idx.set_option("blocked_postings", 1)
+        idx.set_option("postings_walk", 4)
+        return idx.prepare()
+
+    idx = handle()
+    before = idx.info()
+    assert before.postings_state == 1 and before.postings_walk == 4 and before.aux_bytes > 0
+    for v in (1, 2, 3):
+        assert nat.lib().vs_index_set_option(idx._h, b"postings_walk", v) == nat.VS_EUNSUPPORTED
+        assert "removed" in nat.last_error()
+        with pytest.raises(NotImplementedError, match="removed"):
+            idx.set_option("postings_walk", v)
+        after = idx.prepare().info()
+        assert (after.postings_state, after.postings_walk, after.aux_bytes) == (1, 4, before.aux_bytes), v
+    ids, sc, info = _search(idx, q, 10)
+    ref_ids, ref_sc, ref_info = _search(handle(), q, 10)
+    assert info.last_path == ref_info.last_path == 3 and info.postings_walk == ref_info.postings_walk == 4
+    assert (ids == ref_ids).all() and (sc == ref_sc).all()
 
 
 @pytest.mark.parametrize("store", [nat.VS_F32, nat.VS_F16], ids=["fp32", "fp16"])
@@ -199,7 +213,7 @@ def test_short_and_dominant_weight_queries(quant):
     idx = DeviceIndex.from_csr(ip, ix, d, V)
     ref_ids, ref_sc, info = _search(idx, q, 100, blocked_postings=0)
     assert info.last_path == 1
-    for walk in (-1, 4, 0) + ((1, 2, 3) if _experimental_walks(idx) else ()):
+    for walk in (-1, 4, 0):
         ids, sc, info = _search(idx, q, 100, blocked_postings=1, postings_quant=quant, postings_walk=walk)
         assert info.last_path == 3
         assert (ids == ref_ids).all() and (sc == ref_sc).all(), f"walk {walk}: differs from the CSR scan"

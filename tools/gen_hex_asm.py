@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Generates vsearch_amd/csrc/bp_hex_asm.h: the inner loops of the 16-slot ("hex") walk (bp_hex.h states the data layout), each ONE
+"""Generates tools/microbench/bp_hex_asm.h: the inner loops of the 16-slot ("hex") walk (bp_hex_loop.h states the data layout), each ONE
 inline-asm statement -- the recipe of tools/gen_quad_asm.py (named VGPR sets, counted s_waitcnt vmcnt / lgkmcnt, loads, waits and
 consumers in one statement) re-cut for tiles of 16 queries over blocks of <= 1024 documents:
 
@@ -41,7 +41,7 @@ usage: gen_hex_asm.py [S] [out] [variant]      variant (microbenchmarks): nolds 
 import sys
 
 S = int(sys.argv[1]) if len(sys.argv) > 1 else 6
-OUT = sys.argv[2] if len(sys.argv) > 2 else "vsearch_amd/csrc/bp_hex_asm.h"
+OUT = sys.argv[2] if len(sys.argv) > 2 else "tools/microbench/bp_hex_asm.h"
 VARIANT = sys.argv[3] if len(sys.argv) > 3 else ""
 NW = 16                      # waves of the workgroup
 V0 = 64

@@ -1,8 +1,9 @@
-// The inner loop of the 16-slot walk (vsearch_amd/csrc/bp_hex_loop.h, tools/gen_hex_asm.py) on its own, next to tools/microbench/quad_walk.hip:
+// The inner loop of the 16-slot walk (tools/microbench/bp_hex_loop.h, tools/gen_hex_asm.py) on its own, next to tools/microbench/quad_walk.hip:
 // every CU walks n_list posting lists (one 128-byte chunk each; 16 queries' worth, slot by slot, columns sorted inside a slot) of NBLK
 // blocks and scatter-adds them into LDS.  Prints cycles per block and CU and per 256 cells (= one quad-walk step of 4 chunks), and checks
 // workgroup 0's sums against the host.
-//   hipcc -O3 --offload-arch=gfx950 -I vsearch_amd/csrc tools/microbench/hex_walk.hip -o tools/microbench/bin/hex_walk
+//   hipcc -O3 --offload-arch=gfx950 -I tools/microbench tools/microbench/hex_walk.hip -o tools/microbench/bin/hex_walk
+// (the generated loop is included from the -I path, not from beside this file: run_hex_variants.sh points it at other generations)
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <cstdio>
@@ -12,7 +13,7 @@
 #include <vector>
 #include <algorithm>
 #include "bp_hex_loop.h"
-#include "bp_hex_asm.h"
+#include <bp_hex_asm.h>
 
 using namespace vs;
 

@@ -11,13 +11,23 @@
 // After the barrier a wave finds its records in registers and only has to add.  A wave's chunk is its own number (static): chunk c
 // holds entries c C .. c C + C - 1, C = ceil(entries / 16), lane l takes entries c C + 64 u + l, u = 0 .. 7 (neighbouring lanes
 // read neighbouring directory words and lists).
-// Accumulators slot-major [8][2048 + 66]: pad postings of a binary list carry document id 2048 (bp_fill_kernel), the spare
-// documents behind each plane absorb them.  Epilogue, candidate keys, thresholds, output: bp_flat_topk's.
+// Accumulators are SLOT-MAJOR, acc[slot][2048 + 66]: the address of a posting is slot plane + 4 * document (one v_mad_u32_u16 on the
+// packed id word), a list's adds spread over all banks without a padded pitch.  Pad postings of a binary list carry document id
+// 2048 (bp_fill_kernel); the spare documents behind each plane absorb them (kBinSpare).
+// Epilogue: a thread finishes documents 2 t and 2 t + 1 in one round -- it reads TWO documents' sums of a slot per ds_read_b64,
+// conflict-free, zeroes them, and pushes the keys above the slot's threshold to the workgroup's candidate buffer (kFlCap keys per
+// slot, bp_walk.h); a buffer that could not take another round is sorted and cut to its best K'.  Numerics, candidate keys,
+// thresholds and output are bp_walk_topk's: the two kernels return the same candidate sets.
 //
-// Hand-issued loads (rules learnt in bp_stream.h): every one gets a wait with its registers tied; values are copied out of a
-// register in the SAME asm statement that waits for it; no compiler-issued vector load between them.
+// Hand-issued loads (global_load in asm, waited for by count) -- the rules:
+//   * every load gets a wait with its registers TIED ("+v"), also a load whose value is never used (past the item's last block):
+//     a register the compiler considers dead is handed to something else and then overwritten by the late load;
+//   * a value is copied out of a loaded register in the SAME asm statement that waits for it: given a wait with the register merely
+//     tied, the compiler may satisfy the tie by copying the register IN FRONT of the wait -- a stale word;
+//   * no compiler-issued vector load between a hand-issued load and its wait: it counts in vmcnt (the wait counts are constants),
+//     and the compiler drains the counter with s_waitcnt vmcnt(0) for its own load.  Scalar loads are spelled out for that reason.
 #pragma once
-#include "bp_flat.h"
+#include "bp_walk.h"
 
 namespace vs {
 

@@ -524,6 +524,7 @@ __global__ __launch_bounds__(kScanThreads) void bp_quad_topk(KArg<BpArgs, FL> a)
                 //  counter exactly at the limit -- 1024 after the first round of a work item's first block, where every document is a
                 //  candidate -- the late reader went into the cut's barriers alone: whole blocks of candidates lost once other
                 //  processes' waves on the CU stretched the window.  docs/EXPERIMENTS.md round 6, profiles/r06_prune_decision_race.txt.)
+                static_assert(kQuadRows <= 2 * kScanThreads, "the cut counter has two fields, first rounds | last round: a block is at most two epilogue rounds");
                 lds_barrier();                                          // (the counters and sums are LDS; candidates other threads stored are read only when a prune follows)
                 // (VS_BP_KNOB = 128 + 4096 n, tests: one wave reads the counters n x 512 cycles late -- the others are pushing the next round's
                 //  candidates by then.  A SCALAR branch: s_sleep does not care about exec -- behind a vector condition every wave slept)

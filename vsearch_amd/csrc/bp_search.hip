@@ -4,15 +4,6 @@
 #include "csr_internal.h"
 #include "bp_refine.h"
 #include "bp_bin.h"
-// The three experimental walks of round 3 (flat worklists, streamed flat walk, two accumulator sets: all correct, all slower than the
-// list walk -- docs/EXPERIMENTS.md) are lab results, not components: compiled only with -DVS_EXPERIMENTAL_WALKS (make EXPERIMENTAL=1).
-// (bp_flat.h itself stays in: the bag-of-token walk, bp_bin.h, shares its candidate handling)
-#ifdef VS_EXPERIMENTAL_WALKS
-#include "bp_stream.h"
-#include "bp_duo.h"
-#else
-namespace vs { constexpr int kDuoMaxK = 0, kDuoEntCap = 0, kDuoQT = 4; }
-#endif
 #include "bp_quad.h"
 #include "bp_head.h"
 #include "bp_bq.h"
@@ -43,31 +34,25 @@ void bp_release(vs_index* idx) {
     idx->bp_ready = false;
 }
 
+// The list walk's kernel (bp_walk_topk, one list per lane group) on a valued index: QT query slots, accumulation AM, head mode HD (0 none,
+// 1 strips multiplied inside the walk, 2 sums from the head pre-pass), `vm` the records' values, `lanes` per list (option "postings_lanes").
+// Record loads in flight per lane group: the wide depth kBpNBWide ONLY for fp16 records on 8 lanes in the fixed-point walk with head mode
+// 0 or 2; head mode 1, fp32 records, the fp64 walk and every 4-lane form take kBpNB.  That is as measured, form by form -- not an
+// oversight to fix in passing: another depth is another kernel.
+template <int QT, int AM, int HD, int FL>
+auto bp_list_walk(int vm, int lanes) -> void (*)(KArg<BpArgs, FL>) {
+    constexpr int NB16 = AM == AM_FIX && HD != 1 ? kBpNBWide : kBpNB;
+    if (vm == VM_F32) return lanes != 4 ? bp_walk_topk<VM_F32, QT, AM, 8, kBpRowsMax, kBpNB, HD, FL> : bp_walk_topk<VM_F32, QT, AM, 4, kBpRowsMax, kBpNB, HD, FL>;
+    return lanes != 4 ? bp_walk_topk<VM_F16, QT, AM, 8, kBpRowsMax, NB16, HD, FL> : bp_walk_topk<VM_F16, QT, AM, 4, kBpRowsMax, kBpNB, HD, FL>;
+}
+
+// Which kernel, with how much dynamic LDS, walks this index for these arguments: every arm sets both.
 // valued index: QT queries per tile, blocks of <= 2048 documents (exact fp64 walk: QT = 4, filter walk: QT = 8);
 // binary index: filter walk only, one lane per (short) list
-#ifdef VS_EXPERIMENTAL_WALKS
-constexpr int kFlRoundsF16 = 8, kFlRoundsF32 = 5;     // record loads in flight per lane (registers: 8 / 12 per record)
-#endif
-// which walk serves the fixed-point filter of this index: 0 = a list per lane group (bp_walk.h), 1 = flat worklists (bp_flat.h),
-// 2 = the list walk on two accumulator sets, no block barrier (bp_duo.h), 3 = flat worklists, record loads software-pipelined (bp_stream.h)
-int bp_walk_kind(const vs_index* idx) {
-#ifdef VS_EXPERIMENTAL_WALKS
-    const bool can = !idx->bp_quad && idx->store_dtype != VS_NONE && idx->bp_n_head == 0 && idx->bp_max_block_recs < ((int64_t)1 << kFlRecBits) - 4096;
-    if (!can) return 0;
-    return idx->bp_walk_pref < 0 || idx->bp_walk_pref > 3 ? 0 : idx->bp_walk_pref;
-#else
-    (void)idx;
-    return 0;
-#endif
-}
-template <int AM>
-bool bp_flat_ok(const vs_index* idx, const BpArgs& a) { return AM == AM_FIX && !a.upper && bp_walk_kind(idx) >= 1; }
-// walk 2 (two accumulator sets, bp_duo.h) serves this call: 4 query slots per tile, K' within its candidate buffers
-bool bp_duo_ok(const vs_index* idx, int kp, const uint64_t* upper) { return bp_walk_kind(idx) == 2 && !upper && kp <= kDuoMaxK; }
 template <int QT, int AM, int FL>
 int launch_bp_walk_fl(const vs_index* idx, const BpArgs& a, int grid, int ent_cap, hipStream_t s) {
     const int vm = bp_record_vm(idx);
-    size_t lds = bp_lds_bytes<QT, AM, kBpRowsMax>(ent_cap, AM == AM_FIX ? a.n_head : 0);
+    size_t lds = 0;
     void (*kern)(KArg<BpArgs, FL>) = nullptr;
     if (idx->bp_quad) {
         // quad chunks (bp_quad.h): the fixed-point filter walk only
@@ -80,29 +65,6 @@ int launch_bp_walk_fl(const vs_index* idx, const BpArgs& a, int grid, int ent_ca
         const int bq_qt = bq_slots(idx->bp_rows);
         kern = bq_qt == 2 ? (a.timing ? bp_bq_topk<2, 1, 0, FL> : bp_bq_topk<2, 0, 0, FL>) : (a.timing ? bp_bq_topk<4, 1, 0, FL> : bp_bq_topk<4, 0, 0, FL>);
         lds = bq_lds_bytes(bq_qt);
-#ifdef VS_EXPERIMENTAL_WALKS
-    } else if (AM == AM_FIX && bp_duo_ok(idx, a.k, a.upper) && ent_cap <= kDuoEntCap) {
-        if constexpr (FL != 0) return fail(VS_EUNSUPPORTED, "the experimental walks take no document filter");
-        else {
-        if (vm == VM_F32) kern = bp_duo_topk<VM_F32, kBpNB, kBpRowsMax>;
-        else kern = bp_duo_topk<VM_F16, kBpNBWide, kBpRowsMax>;
-        }
-        lds = bp_duo_lds_bytes<kBpRowsMax>(ent_cap);
-    } else if (bp_flat_ok<AM>(idx, a) && bp_walk_kind(idx) == 3) {
-        if constexpr (FL != 0) return fail(VS_EUNSUPPORTED, "the experimental walks take no document filter");
-        else {
-        if (vm == VM_F32) kern = bp_stream_topk<VM_F32, 3, kBpRowsMax>;
-        else kern = bp_stream_topk<VM_F16, 4, kBpRowsMax>;
-        }
-        lds = bp_stream_lds_bytes<kBpRowsMax>(ent_cap);
-    } else if (bp_flat_ok<AM>(idx, a) && bp_walk_kind(idx) != 2) {
-        if constexpr (FL != 0) return fail(VS_EUNSUPPORTED, "the experimental walks take no document filter");
-        else {
-        // valued records, no dense strips, fixed-point filter: the flat walk (bp_flat.h)
-        if (vm == VM_F32) { kern = bp_flat_topk<VM_F32, kFlRoundsF32, kBpRowsMax>; lds = bp_flat_lds_bytes<kFlRoundsF32, kBpRowsMax>(ent_cap); }
-        else { kern = bp_flat_topk<VM_F16, kFlRoundsF16, kBpRowsMax>; lds = bp_flat_lds_bytes<kFlRoundsF16, kBpRowsMax>(ent_cap); }
-        }
-#endif
     } else if (vm == VM_BIN && AM == AM_FIX && idx->bp_walk_pref != 0 && !a.upper && ent_cap <= kBpEntCap) {          // (records: postings_walk = 5, or no room for the chunks)
         // bag-of-token index: the walk with the next block's records prefetched across the barrier (bp_bin.h); postings_walk = 0: the list walk
         kern = bp_bin_topk<kBpRowsMaxBin, FL>;
@@ -113,22 +75,14 @@ int launch_bp_walk_fl(const vs_index* idx, const BpArgs& a, int grid, int ent_ca
         // entries, 13 chunks a block on the Wiki21M shape, 16.4 k q/s; 4: 25 chunks for 16 waves, 13.0 k)
         kern = idx->bp_lanes == 4 ? bp_walk_topk<VM_BIN, kBpBinQT, AM_FIX, 1, kBpRowsMaxBin, 4, 0, FL> : bp_walk_topk<VM_BIN, kBpBinQT, AM_FIX, 1, kBpRowsMaxBin, 8, 0, FL>;
         lds = bp_lds_bytes<kBpBinQT, AM_FIX, kBpRowsMaxBin>(ent_cap);
-    } else if (AM == AM_FIX && a.n_head > 0 && a.head_out) {
-        // head columns served by the head pre-pass (bp_head.h): the list walk adds its sums in the epilogue; no strip weights in LDS
-        if constexpr (AM == AM_FIX) {
-            if (vm == VM_F32) kern = idx->bp_lanes != 4 ? bp_walk_topk<VM_F32, QT, AM_FIX, 8, kBpRowsMax, kBpNB, 2, FL> : bp_walk_topk<VM_F32, QT, AM_FIX, 4, kBpRowsMax, kBpNB, 2, FL>;
-            else kern = idx->bp_lanes != 4 ? bp_walk_topk<VM_F16, QT, AM_FIX, 8, kBpRowsMax, kBpNBWide, 2, FL> : bp_walk_topk<VM_F16, QT, AM_FIX, 4, kBpRowsMax, kBpNB, 2, FL>;
-        }
-        lds = bp_lds_bytes<QT, AM, kBpRowsMax>(ent_cap, 0);
     } else if (AM == AM_FIX && a.n_head > 0) {
-        if constexpr (AM == AM_FIX) {
-            if (vm == VM_F32) kern = idx->bp_lanes != 4 ? bp_walk_topk<VM_F32, QT, AM_FIX, 8, kBpRowsMax, kBpNB, 1, FL> : bp_walk_topk<VM_F32, QT, AM_FIX, 4, kBpRowsMax, kBpNB, 1, FL>;
-            else kern = idx->bp_lanes != 4 ? bp_walk_topk<VM_F16, QT, AM_FIX, 8, kBpRowsMax, kBpNB, 1, FL> : bp_walk_topk<VM_F16, QT, AM_FIX, 4, kBpRowsMax, kBpNB, 1, FL>;
-        }
-    } else if (vm == VM_F32) {
-        kern = idx->bp_lanes != 4 ? bp_walk_topk<VM_F32, QT, AM, 8, kBpRowsMax, kBpNB, 0, FL> : bp_walk_topk<VM_F32, QT, AM, 4, kBpRowsMax, kBpNB, 0, FL>;
+        // head columns: behind the head pre-pass (bp_head.h; a.head_out set) the walk adds the pre-pass's sums in the epilogue and keeps no
+        // strip weights in LDS; without it the walk multiplies the strips itself
+        if constexpr (AM == AM_FIX) kern = a.head_out ? bp_list_walk<QT, AM_FIX, 2, FL>(vm, idx->bp_lanes) : bp_list_walk<QT, AM_FIX, 1, FL>(vm, idx->bp_lanes);
+        lds = bp_lds_bytes<QT, AM, kBpRowsMax>(ent_cap, a.head_out ? 0 : a.n_head);
     } else {
-        kern = idx->bp_lanes != 4 ? bp_walk_topk<VM_F16, QT, AM, 8, kBpRowsMax, (AM == AM_FIX ? kBpNBWide : kBpNB), 0, FL> : bp_walk_topk<VM_F16, QT, AM, 4, kBpRowsMax, kBpNB, 0, FL>;
+        kern = bp_list_walk<QT, AM, 0, FL>(vm, idx->bp_lanes);
+        lds = bp_lds_bytes<QT, AM, kBpRowsMax>(ent_cap);
     }
     if (lds > 160 * 1024) return fail(VS_EUNSUPPORTED, "postings walk needs %zu B of LDS", lds);
     VS_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -153,7 +107,7 @@ int bp_build(vs_index* idx, hipStream_t s) {
     // Quad chunks (bp_quad.h) -- the default copy of a valued index searched by filter + refine: a list is cut into 64-cell chunks of
     // one-dword postings (fp16 values).  Not for: a binary index; exact fp32 records ("postings_quant" = 0, signed / huge values);
     // the fp64 walk ("postings_filter" = 0); a corpus with head columns (their dense strips belong to the list walk: bp_build starts
-    // over without quad when it finds any); the experimental walks 0 .. 3 ("postings_walk"), aligned or arranged records.
+    // over without quad when it finds any); a walk asked for by name ("postings_walk" = 0), aligned or arranged records.
     // Size gate (profiles/r05_quad_policy.txt): a block's main chunks cost n_cols x 256 bytes whatever the lists hold.
     // Measured at 4 M docs, 64 .. 768 nnz per document: the quad walk is FASTER than the record walk at every density (31.6 vs 39.7 ms at
     // 64 nnz: a chunk step per list against the list walk's per-list bookkeeping), so speed never argues against it -- memory does: at
@@ -526,6 +480,29 @@ int bp_choose_chunks(const vs_index* idx, int n_tiles, int64_t n_blocks, int pla
     return std::max(1, nchunk);
 }
 
+// the two launches of a bag-of-token search on four-query tiles: the packed walk on a16's tiles, the int32 walk on a2's
+template <int FL>
+int launch_bq_split(const vs_index* idx, const BpArgs& a16, const BpArgs& a2, int grid, size_t lds, hipStream_t s) {
+    void (*k16)(KArg<BpArgs, FL>) = a16.timing ? bp_bq_topk<4, 1, 1, FL> : bp_bq_topk<4, 0, 1, FL>;
+    void (*k2)(KArg<BpArgs, FL>) = a2.timing ? bp_bq_topk<2, 1, 0, FL> : bp_bq_topk<2, 0, 0, FL>;
+    VS_HIP(hipFuncSetAttribute((const void*)k16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    VS_HIP(hipFuncSetAttribute((const void*)k2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k16, dim3(grid), dim3(kScanThreads), lds, s, with_filter<FL>(a16, idx->filt));
+    hipLaunchKernelGGL(k2, dim3(grid), dim3(kScanThreads), lds, s, with_filter<FL>(a2, idx->filt));
+    return VS_OK;
+}
+
+// the exact one-query scan of the CSR packets for the flagged queries listed in `sel`
+template <int FL>
+int launch_exact_scan(const vs_index* idx, const ScanArgs& sa, const int2* sel, const int32_t* sel_n, hipStream_t s) {
+    void (*ek)(KArg<ScanArgs, FL>, const int2*, const int32_t*) = idx->store_dtype == VS_NONE  ? exact_scan_topk_kernel<VM_BIN, FL>
+                                                                  : idx->store_dtype == VS_F16 ? exact_scan_topk_kernel<VM_F16, FL> : exact_scan_topk_kernel<VM_F32, FL>;
+    const size_t lds = scan_lds_bytes(sa.n_cols);
+    VS_HIP(hipFuncSetAttribute((const void*)ek, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(ek, dim3(idx->cu_count), dim3(kScanThreads), lds, s, with_filter<FL>(sa, idx->filt), sel, sel_n);
+    return VS_OK;
+}
+
 // the filter-and-refine search takes this call: one pass, k + margin within the candidate buffers
 bool bp_filter_ok(const vs_index* idx, int k, int col0, const uint64_t* upper) {
     return idx->bp_ready && idx->bp_filter != 0 && col0 == 0 && !upper && k + std::max(28, k / 4) <= kBpMaxK &&
@@ -540,14 +517,13 @@ int bp_filter_search(vs_index* idx, const float* dq, int32_t B, int32_t k, int64
                      hipStream_t s, bool* done, int32_t out_ld) {
     const int V = idx->n_cols;
     const int kp = k + std::max(28, k / 4);
-    const bool duo = bp_duo_ok(idx, kp, nullptr);
     static const int qt_env = getenv("VS_BP_QT") ? atoi(getenv("VS_BP_QT")) : 0;                       // (developer: smaller tiles on the 8-slot walk)
     // bag-of-token chunks in blocks of more than 4096 documents (two sum planes): tiles of FOUR queries -- the packed walk takes those whose
     // queries all qualify for 16-bit sums, the others are cut into two-slot tiles for the int32 walk (bq_split_kernel, bp_bq.h)
     const bool bq_pk = idx->bp_bq && bq_slots(idx->bp_rows) == 2 && idx->bp_packed_pref != 0 && idx->bp_bq_maxrow > 0;
-    const int qt = bq_pk ? 4 : idx->bp_bq ? bq_slots(idx->bp_rows) : qt_env > 0 ? std::min(qt_env, kQT) : idx->store_dtype == VS_NONE ? kBpBinQT : (duo ? kDuoQT : kQT);
+    const int qt = bq_pk ? 4 : idx->bp_bq ? bq_slots(idx->bp_rows) : qt_env > 0 ? std::min(qt_env, kQT) : idx->store_dtype == VS_NONE ? kBpBinQT : kQT;
     // (dense strips: their weight matrix takes 16 KB of the LDS the entries would use)
-    const int vals_cap = std::min(mq_vals_cap(idx), idx->bp_bq ? kBqEntCap : duo ? kDuoEntCap : (idx->bp_n_head > 0 ? kBpEntCap - 512 : kBpEntCap));
+    const int vals_cap = std::min(mq_vals_cap(idx), idx->bp_bq ? kBqEntCap : (idx->bp_n_head > 0 ? kBpEntCap - 512 : kBpEntCap));
     const int64_t qcap = (int64_t)B * vals_cap;                               // bound of the batch's (query, column) entries that enter a tile
     const int64_t n_blocks = ceil_div64(idx->n_rows, idx->bp_rows);
     if (idx->bp_rows > (idx->bp_bq ? kBqRowsMax : idx->store_dtype == VS_NONE ? kBpRowsMaxBin : kBpRowsMax)) return fail(VS_EINVAL, "postings_rows beyond the walk's block capacity");
@@ -673,8 +649,7 @@ int bp_filter_search(vs_index* idx, const float* dq, int32_t B, int32_t k, int64
     // (off by default for the list walk: it costs it 10 %; the bag-of-token walk of bp_bin.h runs ahead of its memory and
     //  NEEDS it: free running 81 ms, window 16: 66.7, 32: 56.5, 48: 57.2, 64: 58.7, 128: 73 -- the list walk: 61.3)
     const bool bin_walk = idx->store_dtype == VS_NONE && idx->bp_walk_pref != 0 && !idx->bp_bq;
-    // (the two-set walk has no block barrier to keep its workgroups at one pace: 4 M docs 56.9 ms free running, window 1: 39.8, 2: 37.9, 4: 42.2)
-    const int pace_w = pace_env >= 0 ? pace_env : (idx->bp_pace >= 0 ? idx->bp_pace : (idx->bp_bq ? kBqPaceDefault : bin_walk ? 32 : (duo ? 2 : (idx->bp_quad ? kQuadPaceDefault : 0))));
+    const int pace_w = pace_env >= 0 ? pace_env : (idx->bp_pace >= 0 ? idx->bp_pace : (idx->bp_bq ? kBqPaceDefault : bin_walk ? 32 : (idx->bp_quad ? kQuadPaceDefault : 0)));
     if (pace_w > 0) {
         VS_TRY(idx->ws_pace.reserve((size_t)nchunk * a.blocks_per_chunk * 4));
         VS_HIP(hipMemsetAsync(idx->ws_pace.p, 0, (size_t)nchunk * a.blocks_per_chunk * 4, s));
@@ -683,13 +658,6 @@ int bp_filter_search(vs_index* idx, const float* dq, int32_t B, int32_t k, int64
     }
     static const int knob_env = getenv("VS_BP_KNOB") ? atoi(getenv("VS_BP_KNOB")) : 0;
     a.knob = knob_env;
-    static const bool debug_on = getenv("VS_BP_DEBUG") != nullptr;
-    DevBuf dbg;
-    if (debug_on) {
-        VS_TRY(dbg.alloc(64));
-        VS_HIP(hipMemsetAsync(dbg.p, 0, 64, s));
-        a.debug = dbg.as<unsigned long long>();
-    }
     static const bool timing_on = getenv("VS_BP_TIMING") != nullptr;            // developer aid: where the walk's wave-cycles go
     DevBuf timing;
     if (timing_on) {
@@ -742,31 +710,10 @@ int bp_filter_search(vs_index* idx, const float* dq, int32_t B, int32_t k, int64
             a2.tiles = tiles2; a2.n_tiles_dev = n_split + 1;
             const size_t lds = bq_lds_bytes(2);
             if (vals_cap > kBqEntCap) return fail(VS_EUNSUPPORTED, "bag-of-token chunks: tile entries beyond the table");
-            if (fl) {
-                void (*k16)(WithFilter<BpArgs>) = a.timing ? bp_bq_topk<4, 1, 1, 1> : bp_bq_topk<4, 0, 1, 1>;
-                void (*k2)(WithFilter<BpArgs>) = a.timing ? bp_bq_topk<2, 1, 0, 1> : bp_bq_topk<2, 0, 0, 1>;
-                VS_HIP(hipFuncSetAttribute((const void*)k16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                VS_HIP(hipFuncSetAttribute((const void*)k2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                hipLaunchKernelGGL(k16, dim3(grid), dim3(kScanThreads), lds, s, with_filter<1>(a16, idx->filt));
-                hipLaunchKernelGGL(k2, dim3(grid), dim3(kScanThreads), lds, s, with_filter<1>(a2, idx->filt));
-            } else {
-            void (*k16)(BpArgs) = a.timing ? bp_bq_topk<4, 1, 1> : bp_bq_topk<4, 0, 1>;
-            void (*k2)(BpArgs) = a.timing ? bp_bq_topk<2, 1> : bp_bq_topk<2, 0>;
-            VS_HIP(hipFuncSetAttribute((const void*)k16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            VS_HIP(hipFuncSetAttribute((const void*)k2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(k16, dim3(grid), dim3(kScanThreads), lds, s, a16);
-            hipLaunchKernelGGL(k2, dim3(grid), dim3(kScanThreads), lds, s, a2);
-            }
+            VS_TRY(fl ? launch_bq_split<1>(idx, a16, a2, grid, lds, s) : launch_bq_split<0>(idx, a16, a2, grid, lds, s));
             VS_HIP(hipGetLastError());
         } else
         VS_TRY((launch_bp_walk<kQT, AM_FIX>(idx, a, grid, vals_cap, s)));
-    }
-    if (debug_on) {
-        unsigned long long d[8] = {0};
-        VS_HIP(hipMemcpyAsync(d, dbg.p, 64, hipMemcpyDeviceToHost, s));
-        VS_HIP(hipStreamSynchronize(s));
-        fprintf(stderr, "[vsearch_hip] stream walk debug: %llu bad items (e.g. item %08llx, block of %llu records, block %llu, batch of %llu)\n", d[0], d[1] >> 32, d[1] & 0xFFFFFFFFull,
-                d[2] >> 32, d[2] & 0xFFFFFFFFull);
     }
     if (timing_on) {
         unsigned long long h[16] = {0};
@@ -810,10 +757,6 @@ int bp_filter_search(vs_index* idx, const float* dq, int32_t B, int32_t k, int64
             const double bw = (double)std::max<unsigned long long>(1, h[5]) / 16.0;
             fprintf(stderr, "[vsearch_hip] binary walk, cycles per block: wave 0 walk %.0f wait %.0f; wave 8 walk %.0f wait %.0f\n", (double)h[12] / bw, (double)h[13] / bw,
                     (double)h[14] / bw, (double)h[15] / bw);
-        }
-        if (bp_flat_ok<AM_FIX>(idx, a)) {        // the flat walk has no dense part: slot 3 carries 100 MHz ticks
-            fprintf(stderr, "[vsearch_hip] flat walk: shader clock %.0f MHz\n", 100.0 * (double)(h[0] + h[1] + h[2] + h[4]) / (double)std::max<unsigned long long>(1, h[3]));
-            h[3] = 0;
         }
         const double tot = (double)(h[0] + h[1] + h[2] + h[3] + h[4]);
         fprintf(stderr, "[vsearch_hip] walk wave-cycles: prologue %.1f %%, list walk %.1f %%, barrier wait %.1f %%, dense %.1f %%, epilogue %.1f %%; per block and wave: "
@@ -878,18 +821,7 @@ int bp_filter_search(vs_index* idx, const float* dq, int32_t B, int32_t k, int64
         sa.nchunk = nchunk_fb;
         sa.rows_per_chunk = ceil_div64(idx->n_rows, nchunk_fb);
         sa.cand = a.cand;
-        const size_t slds = scan_lds_bytes(V);
-        if (fl) {
-            void (*ek)(WithFilter<ScanArgs>, const int2*, const int32_t*) = idx->store_dtype == VS_NONE  ? exact_scan_topk_kernel<VM_BIN, 1>
-                                                                      : idx->store_dtype == VS_F16 ? exact_scan_topk_kernel<VM_F16, 1> : exact_scan_topk_kernel<VM_F32, 1>;
-            VS_HIP(hipFuncSetAttribute((const void*)ek, hipFuncAttributeMaxDynamicSharedMemorySize, (int)slds));
-            hipLaunchKernelGGL(ek, dim3(idx->cu_count), dim3(kScanThreads), slds, s, with_filter<1>(sa, idx->filt), (const int2*)fb_tiles, (const int32_t*)fb_n);
-        } else {
-        void (*ek)(ScanArgs, const int2*, const int32_t*) = idx->store_dtype == VS_NONE  ? exact_scan_topk_kernel<VM_BIN>
-                                                            : idx->store_dtype == VS_F16 ? exact_scan_topk_kernel<VM_F16> : exact_scan_topk_kernel<VM_F32>;
-        VS_HIP(hipFuncSetAttribute((const void*)ek, hipFuncAttributeMaxDynamicSharedMemorySize, (int)slds));
-        hipLaunchKernelGGL(ek, dim3(idx->cu_count), dim3(kScanThreads), slds, s, sa, (const int2*)fb_tiles, (const int32_t*)fb_n);
-        }
+        VS_TRY(fl ? launch_exact_scan<1>(idx, sa, fb_tiles, fb_n, s) : launch_exact_scan<0>(idx, sa, fb_tiles, fb_n, s));
         MergeArgs m{};
         m.cand = a.cand;
         m.n_cand = (int64_t)nchunk_fb * k;

@@ -55,6 +55,8 @@ constexpr int kBpRowsMaxBin = 2048;   // binary (bag-of-token) index: same block
                                       // half the list visits -- lose to the doubled number of tiles: 11.8 k vs 14.1 k q/s on the Wiki21M shape)
 constexpr int kBpCap = 2048;          // candidate slots per (workgroup, query slot): K' kept + 1024 new per epilogue round
 constexpr int kBpMaxK = kBpCap - kScanThreads;
+constexpr int kFlCap = 4096;          // candidate slots per (workgroup, query slot) of the two bag-of-token walks: bp_bin.h keeps K' + 2048 new per
+                                      // epilogue round; bp_bq.h (blocks of up to 8192 documents) holds back the pushes that find no room
 constexpr int kBpEntCap = 7168;       // (query, column) entries per tile: 56 KB of LDS, and the 8192-slot entry sort must hold them
 constexpr int kBpNB = 4;              // posting lists whose loads are in flight together per lane group
 constexpr int kBpNBWide = 6;          // ... for 32-byte records on 8-lane groups (the filter walk of a valued index): 6 x 8 + 8 registers of records
@@ -275,7 +277,7 @@ __global__ __launch_bounds__(kScanThreads) void bp_fill_kernel(const uint32_t* p
         } else {
             // pad postings of a valued list carry value 0 (the array was zero-filled): they add nothing WHEREVER they point, so
             // they point at scattered documents of the block -- all on document 0, the pads of a wave's ds_add pile up on one
-            // LDS bank (slot-major accumulators, bp_flat.h: every slot's document 0 is bank 0)
+            // LDS bank (slot-major accumulators: every slot's document 0 is bank 0)
             __syncthreads();
             const uint32_t nb = (uint32_t)(r1 - r0);
             for (int i = tid; i < n_cols; i += kScanThreads) {
@@ -445,10 +447,10 @@ struct BpArgs {
     float head_pre, head_mul; // powers of two: weights enter the fp16 operand as w * scale * head_pre (< 2^15), the sums leave as C * head_mul
     const uint16_t* head_out; // HD = 2 (head pre-pass, bp_head.h): the dense part of the sums, [tile - tile0][block][document / 16][slot][16] uint16 in units of 2^kHeadOutShift
     int32_t tile0, tile_cnt;  // tile_cnt > 0: this launch walks tiles [tile0, tile0 + tile_cnt) only (the passes of the head pre-pass)
-    uint32_t* pace;           // optional [nchunk][blocks_per_chunk], zeroed per search: work items that have finished a block (flat walk: lock-step window)
+    uint32_t* pace;           // optional [nchunk][blocks_per_chunk], zeroed per search: work items that have finished a block (the lock-step window)
     int32_t pace_window;      // blocks an item may run ahead of the slowest item of its chunk
     int32_t knob;             // developer switches (VS_BP_KNOB)
-    unsigned long long* debug;    // optional (VS_BP_DEBUG=1): [8] consistency counters of the streamed walk
+    unsigned long long* debug;    // unused, always null: kept for the argument layout
     unsigned long long* timing;   // optional (VS_BP_TIMING=1): [8] wave-cycles per phase, summed over waves: 0 item prologue, 1 list walk,
                                   // 2 wait at the barrier after the walk, 3 dense part, 4 epilogue; [5] = blocks x waves
 };
@@ -1038,6 +1040,7 @@ __global__ __launch_bounds__(kScanThreads) void bp_walk_topk(KArg<BpArgs, FL> a)
                 // counters behind the round's barrier: a block's first round counts in the LOW half of a slot's counter, its last round in
                 // the HIGH half; behind the first round the waves already in the second change the high halves only, and the count is low
                 // half + the high half as it stood at the end of the previous block (chi[]) -- bp_quad.h, docs/EXPERIMENTS.md round 6
+                static_assert(RMAX <= 2 * kScanThreads, "the cut counter has two fields, first rounds | last round: a block is at most two epilogue rounds");
                 __syncthreads();
                 // (VS_BP_KNOB = 128 + 4096 n, tests: one wave reads the counters n x 512 cycles late; a scalar branch -- s_sleep ignores exec)
                 if ((a.knob & 128) && __builtin_amdgcn_readfirstlane((tid >> 6)) == 5)

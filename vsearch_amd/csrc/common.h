@@ -302,7 +302,7 @@ struct vs_index {
     int bp_pref = -1;    // option "blocked_postings": -1 auto, 0 never, 1 always
     int bp_rows_pref = 0;// option "postings_rows": 0 = auto, else documents per block (multiple of 64, 256..2048); applies at the next build
     int bp_chunks = 0;   // option "postings_chunks": 0 = auto, else block runs per tile on the postings path
-    int bp_walk_pref = -1;   // option "postings_walk": -1 auto (= 4 where it applies, else 0), 4 = quad chunks (bp_quad.h), 0 = one list per lane group (bp_walk.h), 1 = flat worklists (bp_flat.h), 2 = list walk on two accumulator sets (bp_duo.h), 3 = streamed flat walk (bp_stream.h)
+    int bp_walk_pref = -1;   // option "postings_walk": -1 auto (= 4 where it applies, else 0), 4 = quad chunks (bp_quad.h), 0 = one list per lane group (bp_walk.h), 5 / 6 = binary index: prefetched records (bp_bin.h) / bag-of-token chunks (bp_bq.h); 1 .. 3 = removed walks, refused by set_option
     bool bp_quad = false;       // bp_rec holds quad chunks (bp_quad.h): 64-cell chunks of one-dword postings; dir / base count chunks
     int bp_bq_maxrow = 0;       // bag-of-token chunks: non-zeros of the longest row (an upper bound: packets x 8) -- what a document can match of a query at most
     int bp_packed_pref = -1;    // option "postings_packed": -1 / 1 = four query slots a tile on packed 16-bit sums where the batch allows it (bp_bq.h), 0 = two int32 slots
@@ -310,7 +310,7 @@ struct vs_index {
     bool bp_no_quad = false;    // bp_build restarting itself without quad chunks (head columns found): consumed by the next bp_build
     int bp_arrange_pref = -1;   // option "postings_arrange": 1 = bank-aware order inside the lists (bp_arrange_kernel), -1 / 0 = as filled
     int bp_pace = -1;        // option "postings_pace": blocks a work item may run ahead of the slowest item of its chunk (-1 auto, 0 = free running)
-    int64_t bp_max_block_recs = 0;   // records of the fullest block (the flat walk's items address 2^19)
+    int64_t bp_max_block_recs = 0;   // records of the fullest block (bag-of-token chunks: a descriptor's chunk index has 16 bits, bp_build)
     int mq_variant = -1; // option "mq_variant": -1 auto (from the batch's query overlap), 0 plain, 1 shared columns
     // dense
     vs::DevBuf mat;      // [n_rows, n_cols] store_dtype
