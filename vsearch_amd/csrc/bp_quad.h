@@ -52,6 +52,9 @@ static_assert(2 * kQuadListBytes * kScanWaves <= kBpCap * 8, "the link lists fit
 // postings a chunk holds when its list goes on in another chunk (the last two cells are the link), overflow chunks of a list of n postings
 constexpr int kQuadLinked = kQuadCells - 2;
 constexpr double kQuadMaxRatio = 3.0;                              // auto policy: quad chunks while their main area is within this multiple of the CSR bytes (bp_build)
+constexpr int kQuadPfLines = 384;                                  // lines of the next block a workgroup prefetches when its XCD's workgroups share them out (the walk, docs/EXPERIMENTS.md)
+                                                                   // (what the L2 feels is the XCD's footprint, ranks x lines x 128 bytes: the ranks are at most cu_count / 8 = 32, so 1.5 MB
+                                                                   //  of the 4 MB at most; measured at 32 ranks: 16 384 lines = 2 MB still gain, 24 576 = 3 MB evict the walk's own lines)
 constexpr int kQuadPaceDefault = 0;                                // lock-step window in blocks (see the walk): off since the work items take FOUR block chunks
                                                                    // (round 5: free running 67.0 / 36.5 / 7.57 ms against 69.8 / 37.7 / 7.71 in lock step, 21 M docs B = 512 / 256, 1 M docs B = 1024)
 // overflow chunks of a list of n postings: a chunk holds CELLS postings when it is the list's last, LINKED when another follows it
@@ -292,6 +295,16 @@ __global__ __launch_bounds__(kScanThreads) void bp_quad_topk(KArg<BpArgs, FL> a)
     const uint32_t list_a = (uint32_t)kQuadAccBytes + (uint32_t)wv * 2u * kQuadListBytes, list_b = list_a + kQuadListBytes;
     const uint32_t g8 = (uint32_t)(lane >> 4) * 8u, s16 = (uint32_t)(lane & 15) * 16u;
 
+    // Cooperative prefetch (below, behind the walk's barrier): with ONE item per workgroup and a chunk count that divides the XCD count
+    // (BpArgs::pf_xcds, set by the host only then) the workgroups of an XCD -- blockIdx.x % pf_xcds, the mapping bp_choose_chunks relies
+    // on -- all sweep the same block range: workgroup pf_r of the pf_R that have an item there takes every pf_R-th line of the next block.
+    // pf_R = 0: every wave prefetches for itself (items loop, unknown CU count, more chunks than XCDs, a lone workgroup, VS_BP_KNOB=1024).
+    uint32_t pf_r = 0u, pf_R = 0u;
+    if (a.pf_xcds > 0 && items <= (int64_t)gridDim.x && (int64_t)blockIdx.x < items) {
+        const uint32_t X = (uint32_t)a.pf_xcds, R = ((uint32_t)items - blockIdx.x % X + X - 1u) / X;      // items j < items with j % X == blockIdx.x % X
+        if (R >= 2u) { pf_r = blockIdx.x / X; pf_R = R; }
+    }
+    [[maybe_unused]] uint32_t n_coop = 0u;                               // (phase clocks: block boundaries prefetched across cooperatively)
     for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
         const int tile = (int)(item / a.nchunk), c = (int)(item % a.nchunk);
         const int q0 = a.tiles[tile].x, nq = a.tiles[tile].y;
@@ -439,16 +452,41 @@ __global__ __launch_bounds__(kScanThreads) void bp_quad_topk(KArg<BpArgs, FL> a)
                 }
             }
             // The NEXT block's cold start: the epilogue below drains every load a wave had in flight, and the next walk's first steps would
-            // each wait for a line that leaves the L2.  One dword per lane from the 64 lines of this wave's first 8 steps (lane l: step
-            // l >> 3, lane group (l >> 1) & 3, half l & 1 of the 256-byte chunk) brings them into the XCD's L2 while the epilogue runs;
-            // the value is never used (the register is held until the loads are back: the compiler does not know it is a load's).
-            // (measured, 21 M docs: 8 steps 127.2 ms, 4 steps 129.1, 16 steps 131.3 -- 8 steps of 32 workgroups are the XCD's 4 MB --, none 130.2;
-            //  VS_BP_KNOB=512 turns it off)
+            // each wait for a line that leaves the L2.  One dword per lane, issued here, brings lines of the next block into the XCD's L2
+            // while the epilogue runs -- the texture path is idle then; the value is never used (the register is held until the loads are
+            // back: the compiler does not know it is a load's).  Which lines:
+            //  * cooperative (pf_R > 0, see above): the XCD's workgroups sweep the same blocks, and between them their tiles touch nearly
+            //    every main-chunk line, so the lines are dealt out without looking at any tile's columns: thread s < pf_lines of workgroup
+            //    pf_r takes line L = pf_r + pf_R * s of the next block's main area -- every request of the XCD a different line, a true
+            //    first touch.  (When every workgroup asked for ITS first steps' lines -- the other arm --, the 32 tiles of an XCD asked for
+            //    the same ~ 4 900 lines 6.7 times over: a request that hits still costs the texture path its 2.5 clocks.)
+            //    The range guard, evaluated before the load: b + 1 < b1 <= n_blocks, so block b + 1 exists, base_cur IS base[b + 1]
+            //    (loaded above under the same condition, back since the barrier's lgkmcnt(0)), and its chunks 0 .. n_cols - 1 are its main
+            //    chunks whatever its row count (quad_count_kernel: a block's chunk count is n_cols + overflow, a short last block included):
+            //    n_cols * 256 bytes = 2 * n_cols lines.  L < 2 * n_cols puts the dword at byte L * 128 <= n_cols * 256 - 128 of that area:
+            //    inside [rec + base[b + 1] * 256, rec + (base[b + 1] + n_cols) * 256), never in an overflow chunk.  The last block of a
+            //    chunk range and of the index (b + 1 == b1) issue nothing; n_cols < 64 cuts the lanes off at 2 * n_cols; nothing here reads
+            //    the descriptor table or rows_b.  L <= 31 + 32 * 1023 < 2^16: no overflow.  A tile without entries (trips == 0) skips its walks
+            //    and runs ahead of the XCD's sweep: it prefetches nothing.
+            //  * per wave (pf_R == 0): the 64 lines of this wave's first 8 steps (lane l: step l >> 3, lane group (l >> 1) & 3, half l & 1 of
+            //    the 256-byte chunk).
+            // (measured, 21 M docs, per wave: 8 steps 127.2 ms, 4 steps 129.1, 16 steps 131.3, none 130.2; cooperative, lines a workgroup: 128 129.3 / 256 128.1 / 384 126.7 / 512 125.4 /
+            //  768 164.6 / 1024 174.0 against 130.1 per wave in the same session -- beyond 512 the prefetched lines evict the walk's: docs/EXPERIMENTS.md.
+            //  VS_BP_KNOB=512: no prefetch; VS_BP_KNOB=1024: per wave always)
             uint32_t pf = 0;
-            if ((a.knob & 512) == 0 && b + 1 < b1 && (uint32_t)(lane >> 3) < trips) {
-                const uint32_t dx = *reinterpret_cast<const uint32_t*>(smem + desc_lds + (uint32_t)(lane >> 3) * 512u + (uint32_t)wv * 32u + (uint32_t)((lane >> 1) & 3) * 8u);
-                const char* pl = a.rec + (size_t)base_cur * kQuadChunkBytes + (dx & 0xFFFFFF00u) + (uint32_t)(lane & 1) * 128u;
-                asm volatile("global_load_dword %0, %1, off" : "=v"(pf) : "v"(pl) : "memory");
+            if ((a.knob & 512) == 0 && b + 1 < b1 && trips > 0) {
+                if (pf_R != 0u) {
+                    const uint32_t L = pf_r + pf_R * (uint32_t)tid;
+                    if (tid < a.pf_lines && L < 2u * (uint32_t)a.n_cols) {
+                        const char* pl = a.rec + (size_t)base_cur * kQuadChunkBytes + (size_t)L * 128u;
+                        asm volatile("global_load_dword %0, %1, off" : "=v"(pf) : "v"(pl) : "memory");
+                    }
+                    if constexpr (TM != 0) n_coop += 1u;
+                } else if ((uint32_t)(lane >> 3) < trips) {
+                    const uint32_t dx = *reinterpret_cast<const uint32_t*>(smem + desc_lds + (uint32_t)(lane >> 3) * 512u + (uint32_t)wv * 32u + (uint32_t)((lane >> 1) & 3) * 8u);
+                    const char* pl = a.rec + (size_t)base_cur * kQuadChunkBytes + (dx & 0xFFFFFF00u) + (uint32_t)(lane & 1) * 128u;
+                    asm volatile("global_load_dword %0, %1, off" : "=v"(pf) : "v"(pl) : "memory");
+                }
             }
             lap(2);
             // epilogue: 1024 documents at a time, one per thread: its QT sums -> order keys -> candidates; prune when a buffer could overflow
@@ -602,6 +640,7 @@ __global__ __launch_bounds__(kScanThreads) void bp_quad_topk(KArg<BpArgs, FL> a)
         }
     }
     if (TM && threadIdx.x == 0) {
+        if (n_coop) atomicAdd(a.timing + 10, (unsigned long long)n_coop);
         a.timing[16 + 4 * blockIdx.x] = __builtin_amdgcn_s_memrealtime() - k_rt0;
         a.timing[17 + 4 * blockIdx.x] = k_rt0;
         a.timing[18 + 4 * blockIdx.x] = (unsigned long long)__builtin_amdgcn_s_getreg((3 << 11) | 20);

@@ -658,6 +658,15 @@ int bp_filter_search(vs_index* idx, const float* dq, int32_t B, int32_t k, int64
     }
     static const int knob_env = getenv("VS_BP_KNOB") ? atoi(getenv("VS_BP_KNOB")) : 0;
     a.knob = knob_env;
+    // Quad walk: behind a block's barrier the workgroups of an XCD prefetch the next block's lines BETWEEN them (bp_quad.h) -- where they all
+    // sweep the same blocks: work items go to the XCDs round robin (item % 8, as bp_choose_chunks has it) and take chunk item % nchunk, so
+    // nchunk must divide 8; a CU count that is no multiple of 8 says nothing about the mapping.  Otherwise (and with VS_BP_KNOB=1024) every
+    // wave prefetches its own first steps' lines, as before.  Lines a workgroup asks for per block: docs/EXPERIMENTS.md has the sweep.
+    static const int pf_env = getenv("VS_BP_PF_LINES") ? atoi(getenv("VS_BP_PF_LINES")) : 0;       // (developer override)
+    if (idx->bp_quad && idx->cu_count % 8 == 0 && 8 % nchunk == 0 && !(knob_env & 1024)) {
+        a.pf_xcds = 8;
+        a.pf_lines = std::min(pf_env > 0 ? pf_env : kQuadPfLines, kScanThreads);
+    }
     static const bool timing_on = getenv("VS_BP_TIMING") != nullptr;            // developer aid: where the walk's wave-cycles go
     DevBuf timing;
     if (timing_on) {
@@ -749,8 +758,9 @@ int bp_filter_search(vs_index* idx, const float* dq, int32_t B, int32_t k, int64
         }
         if (idx->bp_quad) {
             const double bw = (double)std::max<unsigned long long>(1, h[5]);
-            fprintf(stderr, "[vsearch_hip] quad walk, cycles per block and wave: gathers back %.0f, scan %.0f, barrier %.0f, emit %.0f, barrier (+ rest of the plan) %.0f\n", (double)h[6] / bw, (double)h[7] / bw,
-                    (double)h[8] / bw, (double)h[9] / bw, (double)h[3] / bw);
+            // (last word: how the next block was prefetched -- coop: by the XCD's workgroups between them, h[10] block boundaries in all)
+            fprintf(stderr, "[vsearch_hip] quad walk, cycles per block and wave: gathers back %.0f, scan %.0f, barrier %.0f, emit %.0f, barrier (+ rest of the plan) %.0f; prefetch %s\n", (double)h[6] / bw,
+                    (double)h[7] / bw, (double)h[8] / bw, (double)h[9] / bw, (double)h[3] / bw, (a.knob & 512) ? "none" : h[10] ? "coop" : "wave");
             h[12] = h[14] = 0;
         }
         if (h[12] | h[14]) {

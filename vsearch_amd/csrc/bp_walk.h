@@ -450,9 +450,14 @@ struct BpArgs {
     uint32_t* pace;           // optional [nchunk][blocks_per_chunk], zeroed per search: work items that have finished a block (the lock-step window)
     int32_t pace_window;      // blocks an item may run ahead of the slowest item of its chunk
     int32_t knob;             // developer switches (VS_BP_KNOB)
+    int32_t pf_xcds;          // quad walk, cooperative prefetch (bp_quad.h): XCDs the work items go to round robin, 0 = every wave prefetches for itself.
+                              // The host sets it only when nchunk divides it; a workgroup's rank among its XCD's workgroups (blockIdx.x / pf_xcds) and their
+                              // count follow from the item count, which lives on the device
+    int32_t pf_lines;         // ... 128-byte lines of the next block a workgroup asks for, <= kScanThreads: one per thread
     unsigned long long* debug;    // unused, always null: kept for the argument layout
     unsigned long long* timing;   // optional (VS_BP_TIMING=1): [8] wave-cycles per phase, summed over waves: 0 item prologue, 1 list walk,
-                                  // 2 wait at the barrier after the walk, 3 dense part, 4 epilogue; [5] = blocks x waves
+                                  // 2 wait at the barrier after the walk, 3 dense part, 4 epilogue; [5] = blocks x waves; [10] quad walk: block
+                                  // boundaries x workgroups prefetched across cooperatively
 };
 
 // accumulators [RMAX + 1][QT + 1]: the extra row absorbs the pad postings of a binary list (document id RMAX)
