@@ -422,6 +422,8 @@ VS_API void vs_shard_group_destroy(vs_shard_group* group);
  * colidx [nnz], values [nnz] as val_dtype (VS_F32 | VS_F16).  Pass NULL colidx/values to get rowptr
  * only (to size the other two).                                                                  */
 VS_API int  vs_index_export_csr(const vs_index* index, int64_t* rowptr, int64_t* colidx, void* values, int val_dtype);
+/* vs_index_export_dense: the stored matrix as dtype (VS_F32 | VS_F16) into mat [n_rows, ld], ld >= n_cols, host or device pointer.  Only
+ * the n_cols columns of every row are written: what the caller keeps in the ld - n_cols elements behind them stays.              */
 VS_API int  vs_index_export_dense(const vs_index* index, void* mat, int dtype, int64_t ld);
 VS_API void vs_index_destroy(vs_index* index);
 

@@ -664,7 +664,7 @@ ScanPlan plan_scan(const vs_index* idx, int B) {
     return p;
 }
 
-template <int G, int VM>
+template <int G, int VM, int IMG>
 int launch_scan_g(int mode, const ScanArgs& a, const FilterArgs& f, int grid, size_t lds, hipStream_t s) {
     // mode 0: scores, 1: wave top-k, 2: shared top-k
     auto set_lds = [&](const void* f) -> int {
@@ -672,43 +672,55 @@ int launch_scan_g(int mode, const ScanArgs& a, const FilterArgs& f, int grid, si
         return VS_OK;
     };
     if (mode == 0) {
-        VS_TRY(set_lds((const void*)csr_scan_scores<G, VM>));
-        hipLaunchKernelGGL((csr_scan_scores<G, VM>), dim3(grid), dim3(kScanThreads), lds, s, a);
+        VS_TRY(set_lds((const void*)csr_scan_scores<G, VM, IMG>));
+        hipLaunchKernelGGL((csr_scan_scores<G, VM, IMG>), dim3(grid), dim3(kScanThreads), lds, s, a);
     } else if (f.words) {
         // a filtered search: the FL = 1 instantiations (KArg, common.h)
-        void (*kern)(WithFilter<ScanArgs>) = mode == 1 ? csr_scan_topk_wave<G, VM, 1> : csr_scan_topk_shared<G, VM, 1>;
+        void (*kern)(WithFilter<ScanArgs>) = mode == 1 ? csr_scan_topk_wave<G, VM, 1, IMG> : csr_scan_topk_shared<G, VM, 1, IMG>;
         VS_TRY(set_lds((const void*)kern));
         hipLaunchKernelGGL(kern, dim3(grid), dim3(kScanThreads), lds, s, with_filter<1>(a, f));
     } else if (mode == 1) {
-        VS_TRY(set_lds((const void*)csr_scan_topk_wave<G, VM>));
-        hipLaunchKernelGGL((csr_scan_topk_wave<G, VM>), dim3(grid), dim3(kScanThreads), lds, s, a);
+        VS_TRY(set_lds((const void*)csr_scan_topk_wave<G, VM, 0, IMG>));
+        hipLaunchKernelGGL((csr_scan_topk_wave<G, VM, 0, IMG>), dim3(grid), dim3(kScanThreads), lds, s, a);
     } else {
-        VS_TRY(set_lds((const void*)csr_scan_topk_shared<G, VM>));
-        hipLaunchKernelGGL((csr_scan_topk_shared<G, VM>), dim3(grid), dim3(kScanThreads), lds, s, a);
+        VS_TRY(set_lds((const void*)csr_scan_topk_shared<G, VM, 0, IMG>));
+        hipLaunchKernelGGL((csr_scan_topk_shared<G, VM, 0, IMG>), dim3(grid), dim3(kScanThreads), lds, s, a);
     }
     VS_HIP(hipGetLastError());
     return VS_OK;
 }
 
-template <int VM>
+template <int VM, int IMG>
 int launch_scan_vm(int g, int mode, const ScanArgs& a, const FilterArgs& f, int grid, size_t lds, hipStream_t s) {
     switch (g) {
-        case 4: return launch_scan_g<4, VM>(mode, a, f, grid, lds, s);
-        case 8: return launch_scan_g<8, VM>(mode, a, f, grid, lds, s);
-        case 16: return launch_scan_g<16, VM>(mode, a, f, grid, lds, s);
-        case 32: return launch_scan_g<32, VM>(mode, a, f, grid, lds, s);
-        default: return launch_scan_g<64, VM>(mode, a, f, grid, lds, s);
+        case 4: return launch_scan_g<4, VM, IMG>(mode, a, f, grid, lds, s);
+        case 8: return launch_scan_g<8, VM, IMG>(mode, a, f, grid, lds, s);
+        case 16: return launch_scan_g<16, VM, IMG>(mode, a, f, grid, lds, s);
+        case 32: return launch_scan_g<32, VM, IMG>(mode, a, f, grid, lds, s);
+        default: return launch_scan_g<64, VM, IMG>(mode, a, f, grid, lds, s);
     }
 }
 
-int launch_scan(const vs_index* idx, int mode, const ScanArgs& a, int grid, hipStream_t s) {
-    const size_t lds = scan_lds_bytes(idx->n_cols);
-    if (lds > 160 * 1024) return fail(VS_EUNSUPPORTED, "n_cols = %d needs %zu B of LDS (> 160 KiB)", idx->n_cols, lds);
+template <int IMG>
+int launch_scan_img(const vs_index* idx, int mode, const ScanArgs& a, int grid, size_t lds, hipStream_t s) {
     ProfScope prof(mode == 0 ? "csr_scan_scores" : "csr_scan_topk", s);
     const FilterArgs f = mode == 0 ? FilterArgs{} : idx->filt;          // (the search's filter, of the sub-batch in flight)
-    if (idx->store_dtype == VS_F32) return launch_scan_vm<VM_F32>(idx->lanes_per_row, mode, a, f, grid, lds, s);
-    if (idx->store_dtype == VS_F16) return launch_scan_vm<VM_F16>(idx->lanes_per_row, mode, a, f, grid, lds, s);
-    return launch_scan_vm<VM_BIN>(idx->lanes_per_row, mode, a, f, grid, lds, s);
+    if (idx->store_dtype == VS_F32) return launch_scan_vm<VM_F32, IMG>(idx->lanes_per_row, mode, a, f, grid, lds, s);
+    if (idx->store_dtype == VS_F16) return launch_scan_vm<VM_F16, IMG>(idx->lanes_per_row, mode, a, f, grid, lds, s);
+    return launch_scan_vm<VM_BIN, IMG>(idx->lanes_per_row, mode, a, f, grid, lds, s);
+}
+
+int launch_scan(vs_index* idx, int mode, const ScanArgs& a, int grid, hipStream_t s) {
+    if (scan_image_fits(idx->n_cols)) return launch_scan_img<1>(idx, mode, a, grid, scan_lds_bytes(idx->n_cols), s);
+    // too wide for the LDS image (csr_scan.h): the kernels read the weights from memory, from rows of n_cols + 1 floats that end in the pad
+    // column's 0
+    const size_t ldw = (size_t)idx->n_cols + 1;
+    VS_TRY(idx->ws_qpad.reserve((size_t)a.B * ldw * 4));
+    VS_HIP(hipMemcpy2DAsync(idx->ws_qpad.p, ldw * 4, a.q, (size_t)idx->n_cols * 4, (size_t)idx->n_cols * 4, (size_t)a.B, hipMemcpyDeviceToDevice, s));
+    VS_HIP(hipMemset2DAsync(idx->ws_qpad.as<float>() + idx->n_cols, ldw * 4, 0, 4, (size_t)a.B, s));
+    ScanArgs w = a;
+    w.q = idx->ws_qpad.as<float>();
+    return launch_scan_img<0>(idx, mode, w, grid, scan_lds_bytes_no_image(), s);
 }
 
 int prep_queries(vs_index* idx, const void* q, int q_dtype, int64_t ldq, int B, hipStream_t s, const float** out) {

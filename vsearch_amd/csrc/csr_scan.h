@@ -51,6 +51,12 @@ __host__ __device__ inline size_t scan_img_bytes(int32_t n_cols) {
 __host__ __device__ inline size_t scan_lds_bytes(int32_t n_cols) {
     return scan_img_bytes(n_cols) + (size_t)kWgCap * 8 + 16;
 }
+// An index too wide for the image (n_cols > 32 763: image + candidate keys would pass the 160 KB of LDS) is scanned by the IMG = 0 instantiations of the
+// three kernels below: no image, the weights are read from memory -- a.q then holds rows of n_cols + 1 floats, the last one the pad
+// column's 0 (launch_scan builds them).  The same fmaf chains in the same order: the same scores bit for bit.
+constexpr size_t kScanLdsMax = 160 * 1024;
+__host__ __device__ inline bool scan_image_fits(int32_t n_cols) { return scan_lds_bytes(n_cols) <= kScanLdsMax; }
+__host__ __device__ inline size_t scan_lds_bytes_no_image() { return (size_t)kWgCap * 8 + 16; }
 
 // Partial score of one row for this lane's packets p0+lg, p0+lg+G, ...
 template <int G, int VM>
@@ -128,10 +134,10 @@ __device__ __forceinline__ void load_image(const ScanArgs& a, float* img, int qi
 }
 
 // ---- scores-only pass: writes the dense [B, N] matrix the reference materialises (tests) --------
-template <int G, int VM>
+template <int G, int VM, int IMG = 1>
 __global__ __launch_bounds__(kScanThreads) void csr_scan_scores(ScanArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* img = reinterpret_cast<float*>(smem);
+    float* img_lds = reinterpret_cast<float*>(smem);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     constexpr int RPW = 64 / G;
     const int g = lane / G, lg = lane % G;
@@ -140,9 +146,14 @@ __global__ __launch_bounds__(kScanThreads) void csr_scan_scores(ScanArgs a) {
         const int qi = (int)(item / a.nchunk), c = (int)(item % a.nchunk);
         const int64_t r0 = (int64_t)c * a.rows_per_chunk;
         const int64_t r1 = min(a.n_rows, r0 + a.rows_per_chunk);
-        __syncthreads();
-        load_image(a, img, qi, tid);
-        __syncthreads();
+        const float* img = img_lds;
+        if constexpr (IMG != 0) {
+            __syncthreads();
+            load_image(a, img_lds, qi, tid);
+            __syncthreads();
+        } else {
+            img = a.q + (size_t)qi * ((size_t)a.n_cols + 1);
+        }
         for (int64_t rb = r0 + (int64_t)w * RPW; rb < r1; rb += (int64_t)kScanWaves * RPW) {
             const int64_t row = rb + g;
             float acc = 0.f;
@@ -157,11 +168,11 @@ __global__ __launch_bounds__(kScanThreads) void csr_scan_scores(ScanArgs a) {
 // Each wave keeps its own <=256 candidate keys in LDS and prunes them to the best k with an
 // in-register bitonic network; a wave's k-th best key is a lower bound of the global k-th best, so
 // waves share the tightest bound through one LDS word and drop every row that cannot qualify.
-template <int G, int VM, int FL = 0>          // FL = 1: a filtered search (KArg, common.h)
+template <int G, int VM, int FL = 0, int IMG = 1>          // FL = 1: a filtered search (KArg, common.h)
 __global__ __launch_bounds__(kScanThreads) void csr_scan_topk_wave(KArg<ScanArgs, FL> a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* img = reinterpret_cast<float*>(smem);
-    uint64_t* cand = reinterpret_cast<uint64_t*>(smem + scan_img_bytes(a.n_cols));
+    float* img_lds = reinterpret_cast<float*>(smem);
+    uint64_t* cand = reinterpret_cast<uint64_t*>(smem + (IMG != 0 ? scan_img_bytes(a.n_cols) : 0));
     unsigned long long* tau_sh = reinterpret_cast<unsigned long long*>(cand + kWgCap);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     constexpr int RPW = 64 / G;
@@ -174,8 +185,10 @@ __global__ __launch_bounds__(kScanThreads) void csr_scan_topk_wave(KArg<ScanArgs
         const int qi = (int)(item / a.nchunk), c = (int)(item % a.nchunk);
         const int64_t r0 = (int64_t)c * a.rows_per_chunk;
         const int64_t r1 = min(a.n_rows, r0 + a.rows_per_chunk);
+        const float* img = img_lds;
         __syncthreads();
-        load_image(a, img, qi, tid);
+        if constexpr (IMG != 0) load_image(a, img_lds, qi, tid);
+        else img = a.q + (size_t)qi * ((size_t)a.n_cols + 1);
         if (tid == 0) *tau_sh = 0ull;
         __syncthreads();
         const uint64_t upper = a.upper ? a.upper[qi] : ~0ull;
@@ -229,11 +242,11 @@ __global__ __launch_bounds__(kScanThreads) void csr_scan_topk_wave(KArg<ScanArgs
 }
 
 // ---- fused scoring + top-k, 128 < k <= 2048: one shared 4096-slot buffer, barrier per superbatch --
-template <int G, int VM, int FL = 0>
+template <int G, int VM, int FL = 0, int IMG = 1>
 __global__ __launch_bounds__(kScanThreads) void csr_scan_topk_shared(KArg<ScanArgs, FL> a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* img = reinterpret_cast<float*>(smem);
-    uint64_t* cand = reinterpret_cast<uint64_t*>(smem + scan_img_bytes(a.n_cols));
+    float* img_lds = reinterpret_cast<float*>(smem);
+    uint64_t* cand = reinterpret_cast<uint64_t*>(smem + (IMG != 0 ? scan_img_bytes(a.n_cols) : 0));
     int* cnt_sh = reinterpret_cast<int*>(cand + kWgCap);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     constexpr int RPW = 64 / G;
@@ -247,8 +260,10 @@ __global__ __launch_bounds__(kScanThreads) void csr_scan_topk_shared(KArg<ScanAr
         const int qi = (int)(item / a.nchunk), c = (int)(item % a.nchunk);
         const int64_t r0 = (int64_t)c * a.rows_per_chunk;
         const int64_t r1 = min(a.n_rows, r0 + a.rows_per_chunk);
+        const float* img = img_lds;
         __syncthreads();
-        load_image(a, img, qi, tid);
+        if constexpr (IMG != 0) load_image(a, img_lds, qi, tid);
+        else img = a.q + (size_t)qi * ((size_t)a.n_cols + 1);
         if (tid == 0) *cnt_sh = 0;
         __syncthreads();
         const uint64_t upper = a.upper ? a.upper[qi] : ~0ull;

@@ -344,23 +344,25 @@ int export_dense_from_csr(const vs_index* idx, void* mat, int dtype, int64_t ld)
     for (int64_t r = 0; r < idx->n_rows; r += rows_per_chunk) {
         const int64_t nr = std::min(rows_per_chunk, idx->n_rows - r);
         void* ddst = (char*)mat + (size_t)r * ld * esz;
+        int64_t dld = ld;
         if (!dst_dev) {
-            VS_TRY(stage.reserve((size_t)nr * ld * esz));
+            // the stage holds the rows packed; only their n_cols columns go to the caller's rows (the padding behind them is the caller's)
+            dld = idx->n_cols;
+            VS_TRY(stage.reserve((size_t)nr * dld * esz));
             ddst = stage.p;
         }
         const unsigned grid = (unsigned)ceil_div64(nr, 4);
         if (dtype == VS_F32)
             hipLaunchKernelGGL((csr_rows_to_dense_kernel<float>), dim3(grid), dim3(256), 0, 0, idx->pk_ptr.as<uint32_t>(), idx->cols.as<uint16_t>(),
-                               idx->vals.p, idx->store_dtype, idx->n_cols, r, r + nr, ld, (float*)ddst);
+                               idx->vals.p, idx->store_dtype, idx->n_cols, r, r + nr, dld, (float*)ddst);
         else
             hipLaunchKernelGGL((csr_rows_to_dense_kernel<__half>), dim3(grid), dim3(256), 0, 0, idx->pk_ptr.as<uint32_t>(), idx->cols.as<uint16_t>(),
-                               idx->vals.p, idx->store_dtype, idx->n_cols, r, r + nr, ld, (__half*)ddst);
+                               idx->vals.p, idx->store_dtype, idx->n_cols, r, r + nr, dld, (__half*)ddst);
         VS_HIP(hipGetLastError());
         VS_HIP(hipDeviceSynchronize());
-        if (!dst_dev) {
-            const size_t bytes = ((size_t)(nr - 1) * ld + idx->n_cols) * esz;
-            VS_HIP(hipMemcpy((char*)mat + (size_t)r * ld * esz, stage.p, bytes, hipMemcpyDeviceToHost));
-        }
+        if (!dst_dev)
+            VS_HIP(hipMemcpy2D((char*)mat + (size_t)r * ld * esz, (size_t)ld * esz, stage.p, (size_t)dld * esz, (size_t)idx->n_cols * esz, (size_t)nr,
+                               hipMemcpyDeviceToHost));
     }
     return VS_OK;
 }
@@ -525,21 +527,22 @@ extern "C" int vs_index_export_dense(const vs_index* idx, void* mat, int dtype, 
     for (int64_t r = 0; r < idx->n_rows; r += rows_per_chunk) {
         const int64_t nr = std::min(rows_per_chunk, idx->n_rows - r);
         void* ddst = (char*)mat + (size_t)r * ld * esz;
+        int64_t dld = ld;
         if (!dst_dev) {
-            VS_TRY(stage.reserve((size_t)nr * ld * esz));
+            // the stage holds the rows packed; only their n_cols columns go to the caller's rows (the padding behind them is the caller's)
+            dld = idx->n_cols;
+            VS_TRY(stage.reserve((size_t)nr * dld * esz));
             ddst = stage.p;
         }
         const unsigned grid = (unsigned)std::min<int64_t>(ceil_div64(nr * idx->n_cols, 256), 16384);
         const float* src = idx->mat.as<float>() + (size_t)r * ldp;
-        if (dtype == VS_F32) hipLaunchKernelGGL((unpad_rows_kernel<float>), dim3(grid), dim3(256), 0, 0, src, ldp, nr, idx->n_cols, ld, (float*)ddst);
-        else hipLaunchKernelGGL((unpad_rows_kernel<__half>), dim3(grid), dim3(256), 0, 0, src, ldp, nr, idx->n_cols, ld, (__half*)ddst);
+        if (dtype == VS_F32) hipLaunchKernelGGL((unpad_rows_kernel<float>), dim3(grid), dim3(256), 0, 0, src, ldp, nr, idx->n_cols, dld, (float*)ddst);
+        else hipLaunchKernelGGL((unpad_rows_kernel<__half>), dim3(grid), dim3(256), 0, 0, src, ldp, nr, idx->n_cols, dld, (__half*)ddst);
         VS_HIP(hipGetLastError());
         VS_HIP(hipDeviceSynchronize());
-        if (!dst_dev) {
-            // rows are written with stride ld inside the stage; copy the used span
-            const size_t bytes = ((size_t)(nr - 1) * ld + idx->n_cols) * esz;
-            VS_HIP(hipMemcpy((char*)mat + (size_t)r * ld * esz, stage.p, bytes, hipMemcpyDeviceToHost));
-        }
+        if (!dst_dev)
+            VS_HIP(hipMemcpy2D((char*)mat + (size_t)r * ld * esz, (size_t)ld * esz, stage.p, (size_t)dld * esz, (size_t)idx->n_cols * esz, (size_t)nr,
+                               hipMemcpyDeviceToHost));
     }
     return VS_OK;
 }
