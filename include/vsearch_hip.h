@@ -308,6 +308,44 @@ VS_API int vs_term_filter_combine(const uint32_t* term_words, int64_t ld_words, 
                                   const int32_t* must_not, int32_t n_must_not, const int32_t* should, int32_t n_should,
                                   const int32_t* min_should, int32_t B, uint32_t* out_words, int64_t out_ld, int device, void* stream);
 
+/* ---- grouped search: the top k GROUPS of a ranking, each with its best m rows (field collapsing; no reference counterpart) ----------------
+ * groups [n_rows] int32, every value >= 0: rows with equal values form a group (a row with a negative value is never kept).  For a query
+ * let L be the canonical ranking (score descending, id ascending) of its live, allowed rows.  L is walked in order with a set of OPEN groups:
+ * a row whose group is open and holds fewer than m kept rows is kept as that group's next member; a row whose group is not open opens it,
+ * and is kept as its first member, iff fewer than k groups are open; every other row is skipped.  The result: the open groups in opening
+ * order (the order of their best rows), each with its kept rows in keep order.  The walk runs in ROUNDS: a search to some depth under a
+ * filter, vs_topk_collapse over its list, and -- for the queries the list did not complete -- vs_group_filter for the next, deeper search.
+ * The state between the rounds is the result itself:
+ *   out_group [B, k] int32 (-1: unused slot), out_count [B, k] int32 (rows kept of the slot), out_ids [B, k, m] int64 / out_scores [B, k, m]
+ *   fp32 (unused member slots: id -1, score -inf; scores are copied from the lists bit for bit), out_status [B] int32 (1 = complete).
+ * vs_topk_collapse: continues the walk of query qmap[i] (qmap == NULL: query i) over list i of ids / scores [Bp, ld] (kk entries, canonical
+ *   order) for i = 0 .. Bp-1; a query must be listed once at most.  init != 0: the listed queries start from the empty state and their unused
+ *   slots are padded; init == 0: they go on from their state (a query whose status is 1 is left as it is).  A list ends at its first id -1
+ *   (the padding of a filtered search).  A query is complete when its list ended inside the kk entries, when exhausted_hint != 0 (the
+ *   caller searched kk == n_rows: nothing ranks behind the list), or when k groups are open and all hold m rows.  *out_incomplete (int32 [1]) =
+ *   the listed queries left incomplete.  k in 1..1024, m in 1..64, k * m <= 8192, kk in 1..16384; anything else: VS_EINVAL.  An id outside
+ *   [-1, n_rows): VS_EINVAL for host lists; a device list ends there (it is not read on the host).  One wave per query, the open groups in an
+ *   LDS table; no thread walks a list serially.
+ * vs_group_filter: the rows the next round of the Bp listed queries has to rank, as bitmaps out_words [Bp, ld_words] in the layout of
+ *   vs_index_search_filtered: row r is allowed for list i (query b = qmap[i]) iff the caller's filter allows it (filter + b * filter_ld;
+ *   filter_ld = 0: one bitmap for the batch; filter == NULL: none), r is not a kept row of b, r's group is not full, and r's group is open or
+ *   fewer than k groups are.  Every row outside it is kept already or would be skipped whatever comes later, so the next list ranks wholly behind
+ *   this one.  Words [0, (n_rows + 31) / 32) of every bitmap are written whole, bits past n_rows 0.  Tombstones do not enter: the search ANDs
+ *   the live bitmap itself.  The bitmaps cost what any per-query filter costs (Bp x n_rows / 8 bytes): VS_ENOMEM, with the size in the message,
+ *   when a host caller's do not fit on the device.
+ * Both: all buffers host pointers, or all device pointers on `device` (VS_EINVAL for a mix); host buffers are staged and the call blocks; device
+ * pointers and a non-NULL stream only enqueue, as vs_topk_exclude.
+ * Not covered: `groups` is the caller's array -- no index file (.vsx, .npz) stores it, and vs_index_compact does not remap it (the Python
+ * facade does both sides of that: Index.compact / add(groups=)); a shard group has no entry point of its own -- its rounds are
+ * vs_shard_group_search_filtered with global groups and bitmaps on the first shard's device; the one-process-per-GPU RCCL path has none.   */
+VS_API int vs_topk_collapse(const int64_t* ids, const float* scores, int32_t Bp, int32_t kk, int64_t ld, const int32_t* qmap,
+                            const int32_t* groups, int64_t n_rows, int32_t B, int32_t k, int32_t m, int32_t* out_group, int32_t* out_count,
+                            int64_t* out_ids, float* out_scores, int32_t* out_status, int32_t* out_incomplete, int init, int exhausted_hint,
+                            int device, void* stream);
+VS_API int vs_group_filter(const int32_t* groups, int64_t n_rows, int32_t Bp, const int32_t* qmap, int32_t B, int32_t k, int32_t m,
+                           const int32_t* state_group, const int32_t* state_count, const int64_t* state_ids, const uint32_t* filter,
+                           int64_t filter_ld, uint32_t* out_words, int64_t ld_words, int device, void* stream);
+
 /* Dense score matrix [B, n_rows] fp32 -- the intermediate index.py:91 materialises.  Used by the
  * parity tests to check every score, not just the top-k.                                         */
 VS_API int vs_index_scores(vs_index* index, const void* q, int q_dtype, int64_t ldq, int32_t B,

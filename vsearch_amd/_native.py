@@ -84,6 +84,8 @@ _SIGNATURES = {
     "vs_shard_group_destroy": ([_vp], None),
     "vs_merge_topk": ([_vp, _vp, _i32, _i64, _i32, _vp, _vp, _int, _vp], _int),
     "vs_topk_exclude": ([_vp, _vp, _i32, _i32, _i64, _vp, _i32, _i64, _i32, _vp, _vp, _int, _vp], _int),
+    "vs_topk_collapse": ([_vp, _vp, _i32, _i32, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _vp], _int),
+    "vs_group_filter": ([_vp, _i64, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _int, _vp], _int),
     "vs_topk_mask": ([_vp, _i32, _i32, _i64, _i32, _vp, _int, _vp], _int),
     "vs_bow_mask": ([_vp, _i32, _i32, _i32, _i32, _int, _vp, _int, _vp], _int),
     "vs_embed_mask": ([_vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _int, _int, _int, _vp], _int),

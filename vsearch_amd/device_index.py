@@ -264,6 +264,160 @@ def _search_by_example(obj, ids, k, weights, q, alpha, a, exclude, filter):
     return topk_exclude(out_ids, out_sc, ids, k, device)
 
 
+class GroupedResults(NamedTuple):
+    """Per query: the top k groups in the order of their best rows (-1 in unused slots), and each group's best `per_group` rows in rank
+    order with their scores (id -1 / score -inf in unused slots)."""
+    groups: Any        # int32 [B, k]
+    ids: Any           # int64 [B, k, per_group]
+    scores: Any        # float32 [B, k, per_group]
+
+
+MAX_GROUPS_K, MAX_PER_GROUP, MAX_GROUP_ROWS, MAX_COLLAPSE_KK = 1024, 64, 8192, 16384
+
+
+def _grouped_args(k, per_group, depth=None):
+    """Argument checks of search_grouped() that need no device -> (k, per_group, depth or None)"""
+    for name, v in (("k", k), ("per_group", per_group)) + ((("depth", depth),) if depth is not None else ()):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise TypeError(f"{name} must be an int, got {type(v).__name__}")
+        if v < 1:
+            raise ValueError(f"{name} must be >= 1, got {v}")
+    k, m = int(k), int(per_group)
+    if k > MAX_GROUPS_K:
+        raise ValueError(f"k must be at most {MAX_GROUPS_K} groups, got {k}")
+    if m > MAX_PER_GROUP:
+        raise ValueError(f"per_group must be at most {MAX_PER_GROUP}, got {m}")
+    if k * m > MAX_GROUP_ROWS:
+        raise ValueError(f"k * per_group must be at most {MAX_GROUP_ROWS}, got {k} x {m}")
+    return k, m, (None if depth is None else int(depth))
+
+
+class GroupState:
+    """The state of a grouped walk for B queries (what vs_topk_collapse keeps in its output buffers) as numpy arrays or as torch tensors on
+    GPU `device`: group [B, k], count [B, k], ids [B, k, m], scores [B, k, m], status [B], incomplete [1]."""
+
+    def __init__(self, B, k, m, device=None):
+        self.B, self.k, self.m, self.device = int(B), int(k), int(m), device
+        if device is not None:
+            import torch
+            dev = torch.device("cuda", device)
+            self.group = torch.empty((B, k), dtype=torch.int32, device=dev)
+            self.count = torch.empty((B, k), dtype=torch.int32, device=dev)
+            self.ids = torch.empty((B, k, m), dtype=torch.int64, device=dev)
+            self.scores = torch.empty((B, k, m), dtype=torch.float32, device=dev)
+            self.status = torch.zeros(B, dtype=torch.int32, device=dev)
+            self.incomplete = torch.zeros(1, dtype=torch.int32, device=dev)
+        else:
+            self.group = np.full((B, k), -1, dtype=np.int32)
+            self.count = np.zeros((B, k), dtype=np.int32)
+            self.ids = np.full((B, k, m), -1, dtype=np.int64)
+            self.scores = np.full((B, k, m), -np.inf, dtype=np.float32)
+            self.status = np.zeros(B, dtype=np.int32)
+            self.incomplete = np.zeros(1, dtype=np.int32)
+
+
+def _ptr(x, offset_bytes=0):
+    if x is None:
+        return None
+    return C.c_void_p((x.data_ptr() if _is_torch(x) else x.ctypes.data) + offset_bytes)
+
+
+def topk_collapse(state: GroupState, ids, scores, groups, qmap=None, init=False, exhausted_hint=False, device: int = 0):
+    """Continue the grouped walk of query qmap[i] (None: query i) over list i of ids / scores [B', kk] (canonical order; vs_topk_collapse)
+    -> None; the state is updated in place and state.incomplete[0] holds the listed queries left incomplete.  Lists longer than 16 384
+    entries are walked in column blocks.  All numpy, or all torch CUDA tensors on `device` (enqueued on torch's current stream)."""
+    nat.require_device()
+    Bp, kk = int(ids.shape[0]), int(ids.shape[1])
+    on_dev = state.device is not None
+    ids = ids.contiguous() if _is_torch(ids) else np.ascontiguousarray(ids, dtype=np.int64)
+    scores = scores.contiguous() if _is_torch(scores) else np.ascontiguousarray(scores, dtype=np.float32)
+    stream = current_stream(int(device)) if on_dev else None
+    for c0 in range(0, kk, MAX_COLLAPSE_KK):
+        c = min(MAX_COLLAPSE_KK, kk - c0)
+        nat.check(nat.lib().vs_topk_collapse(_ptr(ids, c0 * 8), _ptr(scores, c0 * 4), Bp, c, kk, _ptr(qmap), _ptr(groups), int(groups.shape[0]),
+                                             state.B, state.k, state.m, _ptr(state.group), _ptr(state.count), _ptr(state.ids),
+                                             _ptr(state.scores), _ptr(state.status), _ptr(state.incomplete), 1 if (init and c0 == 0) else 0,
+                                             1 if (exhausted_hint and c0 + c == kk) else 0, int(device), stream))
+
+
+def group_filter(state: GroupState, groups, qmap, filter_words=None, filter_ld: int = 0, out=None, device: int = 0):
+    """The rows the next round of the listed queries still has to rank (vs_group_filter) -> int32 words [B', W], W = ceil(n_rows / 32): the
+    caller's filter (filter_words: [W] with filter_ld = 0, or [B, filter_ld]) AND group not full AND (group open OR fewer than k open) AND
+    not kept.  All numpy, or all torch CUDA tensors on `device`."""
+    nat.require_device()
+    n = int(groups.shape[0])
+    W = (n + 31) // 32
+    Bp = int(qmap.shape[0]) if qmap is not None else state.B
+    on_dev = state.device is not None
+    if out is None:
+        if on_dev:
+            import torch
+            try:
+                out = torch.empty((Bp, W), dtype=torch.int32, device=torch.device("cuda", state.device))
+            except torch.cuda.OutOfMemoryError:
+                raise MemoryError(f"the per-query bitmaps of {Bp} unfinished queries over {n} rows take {Bp * W * 4} bytes of device memory: "
+                                  f"search fewer queries a call, or start deeper (depth=)") from None
+        else:
+            out = np.zeros((Bp, W), dtype=np.uint32)
+    nat.check(nat.lib().vs_group_filter(_ptr(groups), n, Bp, _ptr(qmap), state.B, state.k, state.m, _ptr(state.group), _ptr(state.count),
+                                        _ptr(state.ids), _ptr(filter_words), int(filter_ld), _ptr(out), int(out.shape[1]), int(device),
+                                        current_stream(int(device)) if on_dev else None))
+    return out
+
+
+def _search_grouped(obj, q, k, per_group, groups, filter, depth, rounds_out=None, left_out=None):
+    """The rounds of a grouped search: search of depth kk under F_t -> vs_topk_collapse -> (for the queries left
+    incomplete) vs_group_filter, kk doubled; ends when the device counter of incomplete queries reads 0.  obj: a DeviceIndex or a ShardGroup
+    (its search(filter=) runs every round); groups: int32 [n_rows], on obj.device when it is a CUDA tensor.  rounds_out / left_out: lists
+    that receive the number of rounds / the incomplete queries after each round (tests, tools/probe_grouped.py)."""
+    import torch
+    from .doc_filter import DocFilter, as_doc_filter
+    k, m, depth = _grouped_args(k, per_group, depth)
+    if q.ndim != 2:
+        raise ValueError("queries must be [B, V]")
+    n = int(obj.n_rows)
+    if not hasattr(groups, "shape") or groups.ndim != 1 or int(groups.shape[0]) != n:
+        raise ValueError(f"groups must hold one entry per row ({n}), got shape {tuple(getattr(groups, 'shape', ()))}")
+    nat.require_device()
+    device = int(obj.device)
+    dev = torch.device("cuda", device)
+    as_numpy = not _is_torch(q)
+    qd = (torch.from_numpy(np.ascontiguousarray(q)) if as_numpy else q).to(dev)
+    g = groups if _is_torch(groups) else torch.from_numpy(np.ascontiguousarray(groups))
+    if g.dtype != torch.int32:
+        if g.is_floating_point() or g.dtype == torch.bool:
+            raise TypeError(f"groups must be integer group ids, got {g.dtype}")
+        g = g.to(torch.int32)
+    g = g.to(dev).contiguous()
+    B = int(qd.shape[0])
+    f = as_doc_filter(filter, n, device=device, batch=B) if filter is not None else None
+    st = GroupState(B, k, m, device)
+    kk = min(n, 2 * k * m if depth is None else depth)
+    qa, fa, qmap, t = qd, f, None, 0
+    while True:
+        if isinstance(obj, ShardGroup):
+            torch.cuda.current_stream(device).synchronize()              # (the group runs on its own streams)
+        ids, sc = obj.search(qa, kk, filter=fa)
+        topk_collapse(st, ids, sc, g, qmap=qmap, init=t == 0, exhausted_hint=kk >= n, device=device)
+        t += 1
+        left = int(st.incomplete.item())                                 # the one synchronisation of a round
+        if left_out is not None:
+            left_out.append(left)
+        if left == 0:
+            break
+        qmap = (st.status == 0).nonzero().flatten().to(torch.int32)
+        qa = qd.index_select(0, qmap.to(torch.int64))
+        words = group_filter(st, g, qmap, None if f is None else f.words, 0 if f is None else f.ld, device=device)
+        fa = DocFilter(words, n)
+        kk = min(n, 2 * kk)
+    if rounds_out is not None:
+        rounds_out.append(t)
+    if as_numpy:
+        torch.cuda.current_stream(device).synchronize()
+        return GroupedResults(st.group.cpu().numpy(), st.ids.cpu().numpy(), st.scores.cpu().numpy())
+    return GroupedResults(st.group, st.ids, st.scores)
+
+
 def _queries_from_rows(call, ids, weights, q, alpha, B, m, V, device, stream):
     """the shared body of DeviceIndex / ShardGroup .queries_from_rows: call(ids, B, m, ld_ids, w, ldw, q, q_dtype, ldq, alpha, out, ldo[, stream])"""
     p_ids, _, k1 = as_arg(ids, (nat.VS_I64,))
@@ -689,6 +843,15 @@ class DeviceIndex:
         vs_topk_exclude drops them: exact).  filter: as search().  -> (ids, scores); fewer than k rows left: id -1, score -inf."""
         return _search_by_example(self, ids, k, weights, q, alpha, a, exclude, filter)
 
+    def search_grouped(self, q, k: int, groups, per_group: int = 1, filter=None, depth=None) -> GroupedResults:
+        """The top k GROUPS per query, each with its best `per_group` rows: the collapse of the complete canonical ranking (live rows allowed
+        by `filter`), exact -- searches of doubling depth, each collapsed on the GPU (vs_topk_collapse), the next one filtered to the rows
+        that can still matter (vs_group_filter), until every query is proven complete.  groups: int32 [n_rows], values >= 0 (rows with
+        equal values form a group).  depth: the first search's depth (default min(n_rows, 2 k per_group)); the result does not depend
+        on it.  filter: as search().  k <= 1024, per_group <= 64, k * per_group <= 8192.  numpy queries -> numpy results; CUDA tensors ->
+        tensors on the index's device, on torch's current stream."""
+        return _search_grouped(self, q, k, per_group, groups, filter, depth)
+
     def scores(self, q):
         """Dense [B, n_rows] fp32 score matrix (what index.py:91 materialises). numpy out."""
         info = self.info()
@@ -886,6 +1049,11 @@ class ShardGroup:
     def search_by_example(self, ids, k: int, weights=None, q=None, alpha: float = 1.0, a=None, exclude: bool = True, filter=None):
         """DeviceIndex.search_by_example over the group's rows (global ids)."""
         return _search_by_example(self, ids, k, weights, q, alpha, a, exclude, filter)
+
+    def search_grouped(self, q, k: int, groups, per_group: int = 1, filter=None, depth=None) -> GroupedResults:
+        """DeviceIndex.search_grouped over the group's rows: `groups` and the rounds' bitmaps are global and live on the first shard's GPU;
+        every round is a search(filter=) of the group.  Equal to the unsharded index bit for bit."""
+        return _search_grouped(self, q, k, per_group, groups, filter, depth)
 
     def close(self):
         if self._h:

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from ... import _native as nat
-from ...device_index import DeviceIndex, Explanation, NotBinaryError, ShardGroup, _by_example_args, _explain_args, _int64_ids, _k_a_args, resparsify, topk_exclude
+from ...device_index import DeviceIndex, Explanation, GroupedResults, NotBinaryError, ShardGroup, _grouped_args, _by_example_args, _explain_args, _int64_ids, _k_a_args, resparsify, topk_exclude
 
 logger = logging.getLogger(__name__)
 
@@ -387,6 +387,93 @@ class Index:
         out_ids, out_sc = topk_exclude(res.ids.to(gpu).contiguous(), res.scores.to(gpu).float().contiguous(), ids, k, gpu_ord)
         return SearchResults(self._to_api(out_ids), self._to_api(out_sc.to(self._dtype)))
 
+    # ---- grouped search (not in the reference: it searches a larger k on a guess and de-duplicates on the host) ---------------------
+    def set_groups(self, groups):
+        """Give every document a group id (an article, a source, a near-duplicate cluster): int array / tensor [N], values >= 0;
+        documents with equal values form a group.  Kept as an int32 tensor on the index's GPU for ``search_grouped``; None removes it.
+        Groups follow compact() and add(groups=); they are NOT written by save() -- call set_groups again after a load."""
+        if groups is None:
+            self._groups = None
+            return
+        g = groups.detach() if isinstance(groups, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(groups)))
+        if g.dim() != 1:
+            raise ValueError(f"groups must be 1-D (one id per document), got {g.dim()} dimensions")
+        if g.is_floating_point() or g.is_complex() or g.dtype == torch.bool:
+            raise TypeError(f"groups must be integer group ids, got {g.dtype}")
+        n = self._n_rows()
+        if int(g.shape[0]) != n:
+            raise ValueError(f"groups holds {int(g.shape[0])} entries, the index has {n} documents")
+        if n and int(g.min()) < 0:
+            raise ValueError(f"group ids must be >= 0, got {int(g.min())}")
+        if n and int(g.max()) > 0x7FFFFFFF:
+            raise ValueError(f"group id {int(g.max())} does not fit 31 bits")
+        gpu = torch.device("cuda", self._explain_target()[1])
+        self._groups = g.to(torch.int32).to(gpu).contiguous()
+
+    @property
+    def groups(self):
+        """the group id of every document (int32 tensor on the index's GPU), None when no groups are set"""
+        return getattr(self, "_groups", None)
+
+    def groups_from_samples(self, key: str = "title"):
+        """Factorise field `key` of the data file into group ids (documents with equal values share a group, ids in order of first
+        appearance) and set them -> the list of distinct values, indexed by group id.  Host work over the text store."""
+        n = len(self)
+        if n == 0:
+            raise ValueError("the index has no data file to read groups from")
+        if n != self._n_rows():
+            raise ValueError(f"the data file holds {n} documents, the index {self._n_rows()}")
+        seen, out = {}, np.empty(n, dtype=np.int32)
+        for i in range(n):
+            sample = self.get_sample(i)
+            if not isinstance(sample, dict):
+                raise TypeError(f"document {i} is a {type(sample).__name__}, not a record with fields: pass the group ids to set_groups()")
+            if key not in sample:
+                raise KeyError(f"document {i} has no field {key!r}")
+            v = sample[key]
+            out[i] = seen.setdefault(v if isinstance(v, (str, int, float, bool, tuple, type(None))) else json.dumps(v, sort_keys=True), len(seen))
+        self.set_groups(out)
+        return list(seen)
+
+    def search_grouped(self, q_embs, k: int, per_group: int = 1, filter=None, depth: Optional[int] = None) -> GroupedResults:
+        """The top k GROUPS per query (``set_groups``), each shown by its best `per_group` documents: the collapse of the complete
+        ranking, exact -- not "de-duplicate whatever top-k' held".  -> GroupedResults(groups [B, k], ids [B, k, per_group], scores
+        [B, k, per_group]); groups come in the order of their best document, unused slots hold group -1 / id -1 / score -inf.  Deleted
+        documents and `filter` (as ``search``) apply.  depth: the first search's depth (default 2 k per_group); the result does not
+        depend on it.  k <= 1024, per_group <= 64, k * per_group <= 8192.  Works on a row-sharded index as well."""
+        _grouped_args(k, per_group, depth)
+        if self.groups is None:
+            raise RuntimeError("the index has no groups: set_groups(groups) or groups_from_samples(key) first")
+        if isinstance(q_embs, np.ndarray):
+            q_embs = torch.from_numpy(q_embs)
+        target, gpu_ord = self._explain_target()
+        gpu = torch.device("cuda", gpu_ord)
+        if self._groups.device != gpu:
+            self._groups = self._groups.to(gpu)
+        q = q_embs.detach().to(gpu)
+        q = q.to(self._dtype) if self._dtype in (torch.float16, torch.float32) else q.float()
+        if q.dim() == 1:
+            q = q.unsqueeze(0)
+        res = target.search_grouped(q.contiguous(), int(k), self._groups, per_group=int(per_group), filter=filter, depth=depth)
+        return GroupedResults(self._to_api(res.groups), self._to_api(res.ids), self._to_api(res.scores.to(self._dtype)))
+
+    def _added_groups(self, groups, n_add):
+        """groups= of add() / update() -> int32 CPU tensor [n_add], or None for an index without groups"""
+        if self.groups is None:
+            if groups is not None:
+                raise ValueError("the index has no groups: set_groups() first, then add(..., groups=)")
+            return None
+        if groups is None:
+            raise ValueError("the index has groups: add(..., groups=) must give one group id per added document")
+        g = groups.detach().cpu() if isinstance(groups, torch.Tensor) else torch.from_numpy(np.atleast_1d(np.asarray(groups)))
+        if g.is_floating_point() or g.dtype == torch.bool:
+            raise TypeError(f"groups must be integer group ids, got {g.dtype}")
+        if g.dim() != 1 or int(g.shape[0]) != n_add:
+            raise ValueError(f"groups holds {tuple(g.shape)} entries for {n_add} added documents")
+        if n_add and (int(g.min()) < 0 or int(g.max()) > 0x7FFFFFFF):
+            raise ValueError("group ids must be in [0, 2^31)")
+        return g.to(torch.int32)
+
     # ---- term constraints (not in the reference: must / must-not / should filters from the index's own columns) --------------------
     def term_filter(self, must=None, must_not=None, should=None, min_should=None, thr=None):
         """A DocFilter of the documents that have every `must` term, no `must_not` term and at least `min_should` of the `should` terms
@@ -445,6 +532,9 @@ class Index:
         self._vector = None                                         # re-exported from the new rows on demand
         if self._shape is not None:
             self._shape = (int(old.shape[0]), self._shape[1])
+        if self.groups is not None:                                 # new document j keeps the group of old_ids[j]
+            g = self._groups
+            self._groups = g.index_select(0, torch.from_numpy(old).to(g.device)).to(torch.device("cuda", self._explain_target()[1]))
         return old
 
     def compact(self):
@@ -467,13 +557,15 @@ class Index:
         indptr, indices, data, shape = SparseIndex._csr_parts(vectors)
         return indptr, indices, data, shape
 
-    def add(self, vectors, samples=None):
+    def add(self, vectors, samples=None, groups=None):
         """Append documents -> their new ids (int64 tensor).  vectors: a sparse CSR tensor / scipy CSR (or a dense [n, V] tensor) whose
         columns match the index.  When the index has no spare capacity it is compacted with room to grow (at least the rows asked for, at
         least a quarter of its size); that moves ids if rows are deleted, so then add() raises and asks for compact().  samples: the
-        documents' texts, appended to `data`."""
+        documents' texts, appended to `data`.  groups: their group ids -- required when the index has groups (set_groups), refused
+        when it has none."""
         indptr, indices, data, shape = self._add_csr(vectors)
         n_add = int(indptr.shape[0]) - 1
+        new_groups = self._added_groups(groups, n_add)
         target = self._shards[-1] if getattr(self, "_shards", None) else self._device_index()
         info = target.info()
         if info.kind != nat.VS_KIND_CSR and not (info.kind == nat.VS_KIND_DENSE and info.n_packets > 0):
@@ -516,12 +608,16 @@ class Index:
             self._shape = (n0 + n_add, self._shape[1])
         if samples is not None:
             self.data = (self.data or []) + list(samples)
+        if new_groups is not None:
+            self._groups = torch.cat([self._groups, new_groups.to(self._groups.device)])
         return torch.arange(n0, n0 + n_add, dtype=torch.int64)
 
-    def update(self, ids, vectors, samples=None):
-        """delete(ids) + add(vectors, samples) -> the new ids of the replacements"""
+    def update(self, ids, vectors, samples=None, groups=None):
+        """delete(ids) + add(vectors, samples, groups) -> the new ids of the replacements"""
+        if (self.groups is None) != (groups is None):               # (before anything is deleted)
+            self._added_groups(groups, 0)
         self.delete(ids)
-        return self.add(vectors, samples)
+        return self.add(vectors, samples, groups)
 
     # ---- persistence -------------------------------------------------------------------------------
     def save(self, path):

@@ -22,7 +22,7 @@ from torch import Tensor as T
 from ... import _native as nat
 from ..biencoder.biencoder import BiEncoder, BiEncoderConfig
 from ..utils import sparse as sp
-from .index import BoTIndex, Index, IndexType, SearchResults, SparseIndex
+from .index import BoTIndex, GroupedResults, Index, IndexType, SearchResults, SparseIndex
 
 logger = logging.getLogger(__name__)
 
@@ -82,6 +82,26 @@ class Retriever(BiEncoder):
         if rerank and index.index_type == IndexType.BAG_OF_TOKEN:
             results = self._rerank(index, q_emb, results, k, batch_size)
         return results
+
+    def retrieve_grouped(self, queries: Union[List[str], np.ndarray, T], k: int = 5, per_group: int = 1, dropout: float = 0, a: int = None,
+                         index: Index = None, batch_size: int = 32, filter=None, must=None, must_not=None, should=None,
+                         min_should: int = None, depth: int = None) -> GroupedResults:
+        """The top k GROUPS of documents per query (``index.set_groups`` / ``groups_from_samples``: the articles of a passage index),
+        each with its best `per_group` documents -- ``Index.search_grouped`` behind the query encoder.  Exact: the collapse of the complete
+        ranking, not of a deeper top-k.  `filter` and the term constraints as in ``retrieve``."""
+        index = index or self.index
+        if index is None:
+            raise RuntimeError("no index: call build_index / load_index first")
+        if must is not None or must_not is not None or should is not None or min_should is not None:
+            terms = self.term_filter(must=must, must_not=must_not, should=should, min_should=min_should, index=index)
+            if filter is not None:
+                from ...doc_filter import as_doc_filter
+                filter = as_doc_filter(filter, terms.n_rows, device=terms.device) & terms
+            else:
+                filter = terms
+        a = a or self.encoder_q.config.topk
+        q_emb = self.process_query(queries, dropout, a, batch_size=batch_size)
+        return index.search_grouped(q_emb, k=k, per_group=per_group, filter=filter, depth=depth)
 
     def term_filter(self, must=None, must_not=None, should=None, min_should: int = None, thr=None, index: Index = None):
         """Index.term_filter with terms given as column ids or as vocabulary tokens (strings): a string is looked up in the passage
