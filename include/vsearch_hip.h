@@ -346,6 +346,32 @@ VS_API int vs_group_filter(const int32_t* groups, int64_t n_rows, int32_t Bp, co
                            const int32_t* state_group, const int32_t* state_count, const int64_t* state_ids, const uint32_t* filter,
                            int64_t filter_ld, uint32_t* out_words, int64_t ld_words, int device, void* stream);
 
+/* ---- diversified search: Maximal Marginal Relevance over a hit list (Carbonell & Goldstein 1998; no reference counterpart) -----------------
+ * vs_mmr_select_csr picks k of each query's kk candidates greedily, every pick trading relevance against similarity to the picks before it.
+ * Query b's candidates are ids / scores [b * ld, b * ld + kk) in the search's canonical order; candidate j's stored row is row b * kk + j of
+ * the compact CSR (rowptr [B * kk + 1] int64, cols int32, vals fp32 -- what vs_index_get_rows / vs_shard_group_get_rows write for the
+ * flattened ids; columns of a row distinct).  The n candidates of a query are the entries before its first id -1; the rest is ignored.
+ *   g(i, j) = fl32(sum over shared columns of fp64(fl32(v_i[c] * v_j[c])))      (the library's score numerics; the sum's order is free)
+ *   VS_MMR_COSINE: rel_j = fl32(s_j / s_0) when s_0 > 0, else s_j;  sim(i, j) = fl32(fp64(g(i, j)) / sqrt(fp64(g(i, i)) * fp64(g(j, j)))),
+ *                  sqrt and division in fp64; 0 when either diagonal is 0
+ *   VS_MMR_DOT:    rel_j = s_j;  sim(i, j) = g(i, j)
+ *   pen_j = 0; after a pick p every unpicked j takes pen_j = sim(p, j) where that is larger; an unpicked j is worth
+ *   val_j = fl32(fl32(lam_b * rel_j) - fl32(mu_b * pen_j)), mu_b = fl32(1 - lam_b), no fused multiply-add; the largest val is picked, the lower
+ *   list position on a tie; min(k, n) picks.  Scores are expected finite (no NaN).
+ * Outputs, all [B, k]: out_ids int64, out_scores fp32 (the list's own score bits), out_pos int32 (position in the list), out_mmr fp32 (val at
+ * pick time), out_pen fp32 (pen at pick time); unused slots: id -1, score -inf, pos -1, mmr -inf, pen 0.  Every slot is written.  lam [B] fp32.
+ * Limits: kk and k in 1..VS_MMR_MAX_DEPTH (else VS_EINVAL); n_cols <= 32768, the LDS image (VS_EUNSUPPORTED beyond it: no column tiles).
+ * All buffers host pointers, or all device pointers on `device` (VS_EINVAL for a mix).  Host arrays are checked (rowptr monotone, columns
+ * in [0, n_cols), lam in [0, 1]: VS_EINVAL, nothing written), staged, and the call blocks.  Device arrays are not read on the host: rowptr is
+ * trusted, a column outside [0, n_cols) is skipped as if the cell were absent; with a non-NULL stream the call only enqueues.
+ * One workgroup per query: an fp32 LDS image of the last pick's row, one wave per candidate; no float atomics, so results are deterministic. */
+#define VS_MMR_COSINE 0
+#define VS_MMR_DOT    1
+#define VS_MMR_MAX_DEPTH 1024
+VS_API int vs_mmr_select_csr(const int64_t* rowptr, const int32_t* cols, const float* vals, const int64_t* ids, const float* scores, int32_t B,
+                             int32_t kk, int64_t ld, int32_t n_cols, const float* lam, int32_t k, int mode, int64_t* out_ids, float* out_scores,
+                             int32_t* out_pos, float* out_mmr, float* out_pen, int device, void* stream);
+
 /* Dense score matrix [B, n_rows] fp32 -- the intermediate index.py:91 materialises.  Used by the
  * parity tests to check every score, not just the top-k.                                         */
 VS_API int vs_index_scores(vs_index* index, const void* q, int q_dtype, int64_t ldq, int32_t B,

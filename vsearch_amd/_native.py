@@ -19,6 +19,8 @@ VS_F32, VS_F16, VS_I32, VS_I64, VS_U16, VS_U8, VS_NONE = 0, 1, 2, 3, 4, 5, -1
 VS_KIND_DENSE, VS_KIND_CSR = 0, 1
 # term filters (VS_TERM_FILTER_*): distinct terms a pass of the scan serves, terms a call takes, entries of a must / must_not / should list
 TERM_FILTER_SLOTS, TERM_FILTER_TERMS, TERM_FILTER_LIST = 255, 4096, 64
+# diversified search (VS_MMR_*): similarity modes, the deepest candidate list / most picks, the widest vocabulary of vs_mmr_select_csr
+MMR_COSINE, MMR_DOT, MMR_MAX_DEPTH, MMR_MAX_COLS = 0, 1, 1024, 32768
 
 
 class VsearchNativeError(RuntimeError):
@@ -86,6 +88,7 @@ _SIGNATURES = {
     "vs_topk_exclude": ([_vp, _vp, _i32, _i32, _i64, _vp, _i32, _i64, _i32, _vp, _vp, _int, _vp], _int),
     "vs_topk_collapse": ([_vp, _vp, _i32, _i32, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _vp], _int),
     "vs_group_filter": ([_vp, _i64, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _int, _vp], _int),
+    "vs_mmr_select_csr": ([_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i64, _i32, _vp, _i32, _int, _vp, _vp, _vp, _vp, _vp, _int, _vp], _int),
     "vs_topk_mask": ([_vp, _i32, _i32, _i64, _i32, _vp, _int, _vp], _int),
     "vs_bow_mask": ([_vp, _i32, _i32, _i32, _i32, _int, _vp, _int, _vp], _int),
     "vs_embed_mask": ([_vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _int, _int, _int, _vp], _int),

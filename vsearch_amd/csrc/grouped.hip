@@ -13,6 +13,7 @@
 //     kept.  A workgroup owns a run of rows and a tile of queries; a lane loads its row's group id once and probes every query's LDS table;
 //     a wave ballot is two bitmap words.  Kept rows of open, non-full groups are cleared by id afterwards (atomicAnd, as the tombstones).
 #include "common.h"
+#include "staging.h"
 
 #include <algorithm>
 
@@ -28,15 +29,6 @@ constexpr int kFiltThreads = 256;
 constexpr int kFiltChunks = 8;            // 64-row steps a wave of the filter kernel takes
 constexpr int kFiltMaxTile = 16;          // queries a workgroup of the filter kernel serves
 constexpr int kFiltLds = 48 * 1024;
-
-int need_device() {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        (void)hipGetLastError();
-        return fail(VS_ENODEVICE, "no HIP device visible: libvsearch_hip has no CPU fallback");
-    }
-    return VS_OK;
-}
 
 __device__ __forceinline__ uint32_t table_hash(int32_t g, int shift) { return ((uint32_t)g * 2654435761u) >> shift; }
 
@@ -289,48 +281,6 @@ __global__ __launch_bounds__(256) void group_filter_kept_kernel(GroupFilterArgs 
 }
 
 // ---- host helpers ------------------------------------------------------------------------------------------------------------------
-int device_ok(const void* p, int device, const char* what) {
-    hipPointerAttribute_t attr;
-    VS_HIP(hipPointerGetAttributes(&attr, p));
-    if (attr.device != device) return fail(VS_EINVAL, "%s lives on device %d, the call runs on device %d", what, attr.device, device);
-    return VS_OK;
-}
-
-// the buffers of a call are all host or all device pointers (NULL ones aside) -> *dev; device ones must live on `device`
-int pointers_kind(const void* const* ptrs, const char* const* names, int n, int device, bool* dev) {
-    const void* first = nullptr;
-    for (int i = 0; i < n && !first; ++i) first = ptrs[i];
-    *dev = is_device_ptr(first);
-    for (int i = 0; i < n; ++i) {
-        if (!ptrs[i]) continue;
-        if (is_device_ptr(ptrs[i]) != *dev) return fail(VS_EINVAL, "%s: the buffers of a call must all be host or all be device pointers", names[i]);
-        if (*dev) VS_TRY(device_ok(ptrs[i], device, names[i]));
-    }
-    return VS_OK;
-}
-
-// a host buffer's copy on the device (the pointer itself for a device buffer)
-struct Staged {
-    DevBuf buf;
-    void* host = nullptr;
-    size_t bytes = 0;
-    template <class T>
-    int in(const T* src, size_t n, bool dev, bool copy, hipStream_t s, T** out) {
-        *out = const_cast<T*>(src);
-        if (dev || !src) return VS_OK;
-        bytes = n * sizeof(T);
-        host = const_cast<T*>(src);
-        VS_TRY(buf.alloc(std::max<size_t>(bytes, 4)));
-        if (copy && bytes) VS_HIP(hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, s));
-        *out = buf.as<T>();
-        return VS_OK;
-    }
-    int back(hipStream_t s) {
-        if (host && bytes) VS_HIP(hipMemcpyAsync(host, buf.p, bytes, hipMemcpyDeviceToHost, s));
-        return VS_OK;
-    }
-};
-
 int table_cells(int k) { return (int)pow2_ceil((uint32_t)std::max(2 * k, 64)); }
 int log2_of(uint32_t p) {
     int l = 0;

@@ -418,6 +418,202 @@ def _search_grouped(obj, q, k, per_group, groups, filter, depth, rounds_out=None
     return GroupedResults(st.group, st.ids, st.scores)
 
 
+class DiverseResults(NamedTuple):
+    """Per query: the k hits Maximal Marginal Relevance picked from the candidate list, in pick order -- their ids, the search's own scores,
+    their positions in the candidate list and the MMR value each was picked at (id -1 / score -inf / pos -1 / mmr -inf in unused slots)."""
+    ids: Any           # int64 [B, k]
+    scores: Any        # float32 [B, k]
+    pos: Any           # int32 [B, k]
+    mmr: Any           # float32 [B, k]
+
+
+MAX_MMR_DEPTH = nat.MMR_MAX_DEPTH
+DEFAULT_MMR_ROW_BYTES = 1 << 30          # candidate rows held at a time by search_diverse / diversify: a starting point, not a measured optimum
+_MMR_MODES = {"cosine": nat.MMR_COSINE, "dot": nat.MMR_DOT}
+
+
+def _lam_array(lam, B):
+    """lam of search_diverse / mmr_select: one number or one per query -> float32 numpy [B], every value in [0, 1]"""
+    if _is_torch(lam):
+        lam = lam.detach().cpu().numpy()
+    a = np.asarray(lam)
+    if a.dtype == np.bool_ or not (np.issubdtype(a.dtype, np.floating) or np.issubdtype(a.dtype, np.integer)):
+        raise TypeError(f"lam must be a number or one number per query, got {a.dtype}")
+    if a.ndim == 0:
+        a = np.full(B, a, dtype=np.float32)
+    elif a.shape != (B,):
+        raise ValueError(f"lam must be one number or one per query ({B}), got shape {a.shape}")
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    if not bool(((a >= 0) & (a <= 1)).all()):
+        raise ValueError("lam must lie in [0, 1]")
+    return a
+
+
+def _diverse_args(k, depth=None, sim="cosine"):
+    """Argument checks of search_diverse() / diversify() that need no device -> (k, depth or None, mode)"""
+    for name, v in (("k", k),) + ((("depth", depth),) if depth is not None else ()):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise TypeError(f"{name} must be an int, got {type(v).__name__}")
+        if v < 1:
+            raise ValueError(f"{name} must be >= 1, got {v}")
+    if sim not in _MMR_MODES:
+        raise ValueError(f"sim must be one of {sorted(_MMR_MODES)}, got {sim!r}")
+    if depth is not None:
+        if depth < k:
+            raise ValueError(f"depth = {depth} is smaller than k = {k}: the picks come out of the depth candidates")
+        if depth > MAX_MMR_DEPTH:
+            raise ValueError(f"depth must be at most {MAX_MMR_DEPTH} candidates, got {depth}")
+    return int(k), (None if depth is None else int(depth)), _MMR_MODES[sim]
+
+
+def mmr_select(indptr, indices, values, ids, scores, k: int, lam, mode: str, n_cols: int, device: int = 0, out=None):
+    """Maximal Marginal Relevance over hit lists (vs_mmr_select_csr): per query b pick k of the candidates ids / scores [B, kk] (the
+    entries before the first id -1), whose stored rows are rows b * kk + j of the compact CSR indptr / indices / values (what get_rows
+    returns for ids.reshape(-1)).  lam: one number or one per query; mode: "cosine" | "dot"; n_cols: the rows' column count (<= 32 768).
+    -> (ids int64, scores float32, pos int32, mmr float32, pen float32), all [B, k]; out: five such arrays to write instead.  All numpy,
+    or all torch CUDA tensors on `device` (enqueued on torch's current stream)."""
+    nat.require_device()
+    if mode not in _MMR_MODES:
+        raise ValueError(f"mode must be one of {sorted(_MMR_MODES)}, got {mode!r}")
+    if not hasattr(ids, "ndim") or ids.ndim != 2 or tuple(scores.shape) != tuple(ids.shape):
+        raise ValueError("ids and scores must be [B, kk] arrays of one shape")
+    B, kk, k = int(ids.shape[0]), int(ids.shape[1]), int(k)
+    if int(indptr.shape[0]) != B * kk + 1:
+        raise ValueError(f"indptr must hold {B * kk + 1} entries (one row per candidate), got {int(indptr.shape[0])}")
+    lam_h = _lam_array(lam, B)
+    on_dev = _is_torch(ids) and ids.is_cuda
+    if on_dev:
+        import torch
+        tens = [x.contiguous() for x in (indptr, indices, values, ids, scores)]
+        for t, dt, name in zip(tens, (torch.int64, torch.int32, torch.float32, torch.int64, torch.float32), ("indptr", "indices", "values", "ids", "scores")):
+            if t.dtype != dt:
+                raise TypeError(f"{name} must be {dt}, got {t.dtype}")
+        lam_a = torch.from_numpy(lam_h).to(ids.device)
+        if out is None:
+            out = tuple(torch.empty((B, max(k, 0)), dtype=dt, device=ids.device)
+                        for dt in (torch.int64, torch.float32, torch.int32, torch.float32, torch.float32))
+        stream = current_stream(int(device))
+    else:
+        tens = [np.ascontiguousarray(_host(x), dtype=dt) for x, dt in zip((indptr, indices, values, ids, scores),
+                                                                           (np.int64, np.int32, np.float32, np.int64, np.float32))]
+        lam_a = lam_h
+        if out is None:
+            out = tuple(np.empty((B, max(k, 0)), dtype=dt) for dt in (np.int64, np.float32, np.int32, np.float32, np.float32))
+        stream = None
+    nat.check(nat.lib().vs_mmr_select_csr(*[_ptr(t) if _numel(t) else None for t in tens[:3]], _ptr(tens[3]), _ptr(tens[4]), B, kk, kk,
+                                          int(n_cols), _ptr(lam_a), k, _MMR_MODES[mode], *[_ptr(o) for o in out], int(device), stream))
+    return tuple(out)
+
+
+def _host(x):
+    return x.detach().numpy() if _is_torch(x) else x
+
+
+def _numel(x):
+    return int(x.numel()) if _is_torch(x) else int(x.size)
+
+
+def _n_cols_of(obj) -> int:
+    return obj._n_cols() if isinstance(obj, DeviceIndex) else int(obj._shards[0].info().n_cols)
+
+
+def _candidate_row_ends(obj, flat_ids):
+    """indptr int64 [n + 1] (on the device) of the compact rows of flat_ids: the sizing pass of get_rows alone"""
+    import torch
+    n = int(flat_ids.shape[0])
+    indptr = torch.empty(n + 1, dtype=torch.int64, device=flat_ids.device)
+    if isinstance(obj, ShardGroup):
+        nat.check(nat.lib().vs_shard_group_get_rows(obj._h, _ptr(flat_ids), n, _ptr(indptr), None, None))
+    else:
+        nat.check(nat.lib().vs_index_get_rows(obj._h, _ptr(flat_ids), n, 0, _ptr(indptr), None, None, current_stream(obj.device)))
+    return indptr
+
+
+def _diversify(obj, ids, scores, k, lam, sim, max_row_bytes=None, chunks_out=None):
+    """MMR over the hit lists ids / scores [B, kk] with the rows obj stores: the batch is cut into runs of queries whose
+    candidate rows (8 bytes a non-zero, sized by the first pass of get_rows) stay under max_row_bytes -- a run is never shorter than one
+    query --, and every run is get_rows -> vs_mmr_select_csr.  obj: a DeviceIndex or a ShardGroup.  chunks_out: a list that receives the
+    number of runs (tests, tools/probe_mmr.py)."""
+    import torch
+    k, _, mode = _diverse_args(k, None, sim)
+    if not hasattr(ids, "ndim") or ids.ndim != 2 or tuple(scores.shape) != tuple(ids.shape):
+        raise ValueError("ids and scores must be [B, kk] arrays of one shape")
+    B, kk = int(ids.shape[0]), int(ids.shape[1])
+    if not 1 <= kk <= MAX_MMR_DEPTH:
+        raise ValueError(f"a hit list must hold 1..{MAX_MMR_DEPTH} candidates, got {kk}")
+    if k > MAX_MMR_DEPTH:
+        raise ValueError(f"k must be at most {MAX_MMR_DEPTH}, got {k}")
+    _int64_ids(ids, 2)
+    lam_h = _lam_array(lam, B)
+    max_row_bytes = DEFAULT_MMR_ROW_BYTES if max_row_bytes is None else int(max_row_bytes)
+    if max_row_bytes < 1:
+        raise ValueError(f"max_row_bytes must be positive, got {max_row_bytes}")
+    nat.require_device()
+    device = int(obj.device)
+    dev = torch.device("cuda", device)
+    V = _n_cols_of(obj)
+    if V > nat.MMR_MAX_COLS:
+        raise NotImplementedError(f"the index has {V} columns, diversified search serves at most {nat.MMR_MAX_COLS}")
+    sharded = isinstance(obj, ShardGroup)
+    host_kind = None if (_is_torch(ids) and ids.is_cuda) else ("torch" if _is_torch(ids) else "numpy")
+    as_t = lambda x: x if _is_torch(x) else torch.from_numpy(np.ascontiguousarray(x))
+    ids_d = as_t(ids).to(dev).contiguous()
+    sc_d = as_t(scores).to(dev).to(torch.float32).contiguous()
+    out = tuple(torch.empty((B, k), dtype=dt, device=dev) for dt in (torch.int64, torch.float32, torch.int32, torch.float32, torch.float32))
+    flat = ids_d.reshape(-1)
+    sync = torch.cuda.current_stream(device).synchronize
+    if sharded:
+        sync()                                                           # (the group runs on its own streams)
+    ends = _candidate_row_ends(obj, flat)
+    per_query = ((ends[kk::kk] - ends[:-1:kk]) * 8).tolist()             # bytes of each query's candidate rows (synchronises)
+    runs, b0, held = [], 0, 0
+    for b, nbytes in enumerate(per_query):
+        if b > b0 and held + nbytes > max_row_bytes:
+            runs.append((b0, b))
+            b0, held = b, 0
+        held += nbytes
+    runs.append((b0, B))
+    for b0, b1 in runs:
+        if sharded:
+            sync()
+        indptr, indices, values = obj.get_rows(flat[b0 * kk:b1 * kk])
+        mmr_select(indptr, indices, values, ids_d[b0:b1], sc_d[b0:b1], k, lam_h[b0:b1], sim, V, device, out=tuple(o[b0:b1] for o in out))
+    if chunks_out is not None:
+        chunks_out.append(len(runs))
+    res = DiverseResults(*out[:4])
+    if host_kind is not None:
+        sync()
+        res = DiverseResults(*(t.cpu() if host_kind == "torch" else t.cpu().numpy() for t in res))
+    return res
+
+
+def _search_diverse(obj, q, k, lam=0.5, depth=None, sim="cosine", filter=None, max_row_bytes=None, chunks_out=None):
+    """search(q, depth, filter=) -> _diversify of its lists.  depth defaults to min(n_rows, 1024, max(4 k, k + 16)): a starting point, not
+    a measured optimum.  Deleted rows and the filter act through the search.  obj: a DeviceIndex or a ShardGroup."""
+    import torch
+    k, depth, _ = _diverse_args(k, depth, sim)
+    if q.ndim != 2:
+        raise ValueError("queries must be [B, V]")
+    _lam_array(lam, int(q.shape[0]))                                     # (argument errors before any device work)
+    if depth is None:
+        depth = max(k, min(int(obj.n_rows), MAX_MMR_DEPTH, max(4 * k, k + 16)))      # (k > n_rows: the search raises as it does for any query)
+        if depth > MAX_MMR_DEPTH:
+            raise ValueError(f"k must be at most {MAX_MMR_DEPTH} (the deepest candidate list), got {k}")
+    nat.require_device()
+    device = int(obj.device)
+    as_numpy = not _is_torch(q)
+    on_host = as_numpy or not q.is_cuda
+    qd = (torch.from_numpy(np.ascontiguousarray(q)) if as_numpy else q).to(torch.device("cuda", device))
+    if isinstance(obj, ShardGroup):
+        torch.cuda.current_stream(device).synchronize()
+    ids, sc = obj.search(qd, depth, filter=filter)
+    res = _diversify(obj, ids, sc, k, lam, sim, max_row_bytes, chunks_out)
+    if on_host:
+        torch.cuda.current_stream(device).synchronize()
+        res = DiverseResults(*(t.cpu().numpy() if as_numpy else t.cpu() for t in res))
+    return res
+
+
 def _queries_from_rows(call, ids, weights, q, alpha, B, m, V, device, stream):
     """the shared body of DeviceIndex / ShardGroup .queries_from_rows: call(ids, B, m, ld_ids, w, ldw, q, q_dtype, ldq, alpha, out, ldo[, stream])"""
     p_ids, _, k1 = as_arg(ids, (nat.VS_I64,))
@@ -852,6 +1048,21 @@ class DeviceIndex:
         tensors on the index's device, on torch's current stream."""
         return _search_grouped(self, q, k, per_group, groups, filter, depth)
 
+    def search_diverse(self, q, k: int, lam=0.5, depth=None, sim: str = "cosine", filter=None, max_row_bytes=None) -> DiverseResults:
+        """Diversified top k: Maximal Marginal Relevance over the top `depth` of search(q, depth, filter=) -- each pick is the candidate
+        with the largest lam * relevance - (1 - lam) * (largest similarity to a hit already picked), similarities taken between the stored
+        rows on the GPU (vs_mmr_select_csr; the exact numerics: include/vsearch_hip.h).  lam in [0, 1], one number or one per query: 1 is
+        the plain top k, 0 ranks by novelty alone.  sim: "cosine" (relevance = score / best score) | "dot" (raw scores and dot products).
+        depth: candidates per query, k <= depth <= 1024 (default min(n_rows, 1024, max(4 k, k + 16)), a starting point).  The candidate
+        rows pass through HBM at most max_row_bytes at a time (default 1 GiB).  n_cols <= 32 768.  numpy queries -> numpy results; CUDA
+        tensors -> tensors on the index's device, on torch's current stream."""
+        return _search_diverse(self, q, k, lam, depth, sim, filter, max_row_bytes)
+
+    def diversify(self, ids, scores, k: int, lam=0.5, sim: str = "cosine", max_row_bytes=None) -> DiverseResults:
+        """search_diverse's selection over hit lists the caller already has (ids int64 / scores [B, kk], kk <= 1024; a reranked or a
+        filtered list: anything after a list's first id -1 is ignored).  Rows are read as stored, deleted ones included."""
+        return _diversify(self, ids, scores, k, lam, sim, max_row_bytes)
+
     def scores(self, q):
         """Dense [B, n_rows] fp32 score matrix (what index.py:91 materialises). numpy out."""
         info = self.info()
@@ -1054,6 +1265,15 @@ class ShardGroup:
         """DeviceIndex.search_grouped over the group's rows: `groups` and the rounds' bitmaps are global and live on the first shard's GPU;
         every round is a search(filter=) of the group.  Equal to the unsharded index bit for bit."""
         return _search_grouped(self, q, k, per_group, groups, filter, depth)
+
+    def search_diverse(self, q, k: int, lam=0.5, depth=None, sim: str = "cosine", filter=None, max_row_bytes=None) -> DiverseResults:
+        """DeviceIndex.search_diverse over the group's rows: the group's search, the candidates' rows stitched from their owners on the first
+        shard's GPU (get_rows), the selection there.  Equal to the unsharded index bit for bit."""
+        return _search_diverse(self, q, k, lam, depth, sim, filter, max_row_bytes)
+
+    def diversify(self, ids, scores, k: int, lam=0.5, sim: str = "cosine", max_row_bytes=None) -> DiverseResults:
+        """DeviceIndex.diversify with global ids."""
+        return _diversify(self, ids, scores, k, lam, sim, max_row_bytes)
 
     def close(self):
         if self._h:

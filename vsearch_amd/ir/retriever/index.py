@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from ... import _native as nat
-from ...device_index import DeviceIndex, Explanation, GroupedResults, NotBinaryError, ShardGroup, _grouped_args, _by_example_args, _explain_args, _int64_ids, _k_a_args, resparsify, topk_exclude
+from ...device_index import DeviceIndex, DiverseResults, Explanation, GroupedResults, NotBinaryError, ShardGroup, _diverse_args, _grouped_args, _by_example_args, _explain_args, _int64_ids, _k_a_args, resparsify, topk_exclude
 
 logger = logging.getLogger(__name__)
 
@@ -456,6 +456,39 @@ class Index:
             q = q.unsqueeze(0)
         res = target.search_grouped(q.contiguous(), int(k), self._groups, per_group=int(per_group), filter=filter, depth=depth)
         return GroupedResults(self._to_api(res.groups), self._to_api(res.ids), self._to_api(res.scores.to(self._dtype)))
+
+    # ---- diversified search (not in the reference: Maximal Marginal Relevance over the top hits, similarities from the stored rows) -------
+    def _diverse_out(self, res) -> DiverseResults:
+        return DiverseResults(self._to_api(res.ids), self._to_api(res.scores.to(self._dtype)), self._to_api(res.pos), self._to_api(res.mmr))
+
+    def search_diverse(self, q_embs, k: int, lam=0.5, depth: Optional[int] = None, sim: str = "cosine", filter=None) -> DiverseResults:
+        """The top k with near-duplicates pushed down: Maximal Marginal Relevance over the top `depth` hits of ``search`` -- every pick
+        maximises lam * relevance - (1 - lam) * (its largest similarity to a hit already picked), the similarities taken between the stored
+        rows on the GPU.  -> DiverseResults(ids, scores, pos, mmr), all [B, k] in pick order: scores are the search's own, pos the hit's
+        rank in the plain search, mmr the value it was picked at; unused slots hold id -1 / score -inf / pos -1 / mmr -inf.  lam in [0, 1],
+        one number or one per query (1: exactly ``search(q, k)``); sim: "cosine" | "dot"; depth: k <= depth <= 1024 (default
+        min(N, 1024, max(4 k, k + 16))).  Deleted documents and `filter` (as ``search``) apply.  Works on a row-sharded index as well."""
+        _diverse_args(k, depth, sim)
+        if isinstance(q_embs, np.ndarray):
+            q_embs = torch.from_numpy(q_embs)
+        target, gpu_ord = self._explain_target()
+        q = q_embs.detach().to(torch.device("cuda", gpu_ord))
+        q = q.to(self._dtype) if self._dtype in (torch.float16, torch.float32) else q.float()
+        if q.dim() == 1:
+            q = q.unsqueeze(0)
+        return self._diverse_out(target.search_diverse(q.contiguous(), int(k), lam=lam, depth=depth, sim=sim, filter=filter))
+
+    def diversify(self, results, k: int, lam=0.5, sim: str = "cosine") -> DiverseResults:
+        """``search_diverse``'s selection over hit lists already at hand: `results` is a SearchResults (or any (ids [B, kk], scores) pair,
+        kk <= 1024) -- a reranked list, a filtered search's list with its trailing padding.  Rows are read as stored."""
+        _diverse_args(k, None, sim)
+        ids = self._example_ids(results[0], 2)
+        scores = results[1] if isinstance(results[1], torch.Tensor) else torch.as_tensor(np.asarray(results[1]))
+        if scores.dim() == 1:
+            scores = scores.unsqueeze(0)
+        target, gpu_ord = self._explain_target()
+        gpu = torch.device("cuda", gpu_ord)
+        return self._diverse_out(target.diversify(ids.to(gpu).contiguous(), scores.detach().to(gpu).float().contiguous(), int(k), lam=lam, sim=sim))
 
     def _added_groups(self, groups, n_add):
         """groups= of add() / update() -> int32 CPU tensor [n_add], or None for an index without groups"""

@@ -22,7 +22,7 @@ from torch import Tensor as T
 from ... import _native as nat
 from ..biencoder.biencoder import BiEncoder, BiEncoderConfig
 from ..utils import sparse as sp
-from .index import BoTIndex, GroupedResults, Index, IndexType, SearchResults, SparseIndex
+from .index import BoTIndex, DiverseResults, GroupedResults, Index, IndexType, SearchResults, SparseIndex
 
 logger = logging.getLogger(__name__)
 
@@ -102,6 +102,26 @@ class Retriever(BiEncoder):
         a = a or self.encoder_q.config.topk
         q_emb = self.process_query(queries, dropout, a, batch_size=batch_size)
         return index.search_grouped(q_emb, k=k, per_group=per_group, filter=filter, depth=depth)
+
+    def retrieve_diverse(self, queries: Union[List[str], np.ndarray, T], k: int = 5, lam: float = 0.5, depth: int = None, sim: str = "cosine",
+                         dropout: float = 0, a: int = None, index: Index = None, batch_size: int = 32, filter=None, must=None, must_not=None,
+                         should=None, min_should: int = None) -> DiverseResults:
+        """The top k documents per query with near-duplicates pushed down -- ``Index.search_diverse`` (Maximal Marginal Relevance over the
+        top `depth` hits, similarities between the stored rows) behind the query encoder.  lam = 1 is ``retrieve``; `filter` and the term
+        constraints as in ``retrieve``."""
+        index = index or self.index
+        if index is None:
+            raise RuntimeError("no index: call build_index / load_index first")
+        if must is not None or must_not is not None or should is not None or min_should is not None:
+            terms = self.term_filter(must=must, must_not=must_not, should=should, min_should=min_should, index=index)
+            if filter is not None:
+                from ...doc_filter import as_doc_filter
+                filter = as_doc_filter(filter, terms.n_rows, device=terms.device) & terms
+            else:
+                filter = terms
+        a = a or self.encoder_q.config.topk
+        q_emb = self.process_query(queries, dropout, a, batch_size=batch_size)
+        return index.search_diverse(q_emb, k=k, lam=lam, depth=depth, sim=sim, filter=filter)
 
     def term_filter(self, must=None, must_not=None, should=None, min_should: int = None, thr=None, index: Index = None):
         """Index.term_filter with terms given as column ids or as vocabulary tokens (strings): a string is looked up in the passage
