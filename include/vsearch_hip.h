@@ -191,6 +191,36 @@ VS_API int vs_index_search_filtered(vs_index* index, const void* q, int q_dtype,
                                     const uint32_t* filter, int64_t filter_bit0, int64_t filter_ld,
                                     int64_t id_offset, int64_t* out_ids, float* out_scores, void* stream);
 
+/* Range search (no reference counterpart: the reference only has topk): every document scoring at least a threshold, counted.
+ * For query b a row r MATCHES iff it is live (not deleted), the filter allows it, and score(b, r) >= thr[b] compared as fp32 floats (-0.0 and
+ * +0.0 are equal).  score is the library's exact numerics and nothing else, whichever kernel serves the call: q rounded to the index dtype
+ * as in vs_index_search, score = fl32(sum over the row's columns of fp64(fl32(q[c] * v[c]))), v = 1 on a binary index -- bit-identical to
+ * vs_index_explain's score of the pair and independent of the summation order; an empty row scores +0.0 (it matches thr <= 0).  A dense
+ * index on the matrix cores uses its own fp32 search score instead (what vs_index_search returns for the pair).
+ *   thr [B] fp32.  -inf matches every live, allowed row; +inf none.  NaN: VS_EINVAL for a host array; on the device it matches no row.
+ *   out_count [B] int64 (may be NULL): the number of matching rows -- exact whatever max_hits is.
+ *   out_ids / out_scores [B, max_hits]: the first max_hits matches in the canonical order (score descending, id ascending; ids + id_offset):
+ *     the complete match set when count <= max_hits, else its top max_hits; id -1 / score -inf behind the matches; every slot is written.
+ *     max_hits in 0..VS_RANGE_MAX_HITS (VS_EINVAL beyond); max_hits > n_rows is allowed (this is no top-k: no VS_ERANGE); max_hits = 0 is
+ *     count-only / bitmap-only, and the two pointers may then be NULL.
+ *   out_words [B, ld_words] uint32 (may be NULL): the match bitmap in the layout of vs_index_search_filtered -- bit r of query b's row is set
+ *     iff row r matches; words [0, (n_rows + 31) / 32) of each row are written whole, bits past n_rows are 0, ld_words >= that many words.
+ *     The uncapped result: it can be passed back as a filter.
+ *   filter / filter_bit0 / filter_ld: as vs_index_search_filtered; NULL = every live row.
+ * Pointers: all host (staged; the call blocks), or all device on the index's device (VS_EINVAL for a mix).  With device pointers and a
+ * non-NULL stream the one-query scan and the dense index only enqueue; the tile scan reads its tile plan back first, as vs_index_search does.
+ * A CSR-packet index is served by the 8-queries-a-pass tile scan when the batch qualifies for tiles (as in vs_index_search; option
+ * queries_per_pass = 1 turns it off) and max_hits <= 512, else by a one-query scan, one wave per row; both give identical bits.  The blocked
+ * postings are never used.  A CSR-packet index wider than the LDS query image (n_cols > 32763): VS_EUNSUPPORTED.                          */
+#define VS_RANGE_MAX_HITS 2048
+VS_API int vs_index_search_range(vs_index* index, const void* q, int q_dtype, int64_t ldq, int32_t B, const float* thr, int32_t max_hits,
+                                 const uint32_t* filter, int64_t filter_bit0, int64_t filter_ld, int64_t id_offset, int64_t* out_ids,
+                                 float* out_scores, int64_t* out_count, uint32_t* out_words, int64_t ld_words, void* stream);
+
+/* The scan plan the most recent vs_index_search_range took on this handle (its last sub-batch): the row chunks a query's (or a tile's)
+ * scan was cut into and the rows of a chunk -- the last chunk holds the rest.  0 / 0 before the first range search; 1 chunk on a dense index. */
+VS_API int vs_index_last_range_plan(const vs_index* index, int32_t* out_chunks, int64_t* out_rows_per_chunk);
+
 /* bool / uint8 mask [B, n] (row stride ld_mask bytes; non-zero = allowed) -> the bitmap words [B, ld_words] vs_index_search_filtered
  * reads (bits past n of a row's last word are 0).  mask and words: host pointers or device pointers on `device` (VS_EINVAL otherwise).  stream as in
  * vs_index_search (host buffers block).                                                                                          */

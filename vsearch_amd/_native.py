@@ -21,6 +21,8 @@ VS_KIND_DENSE, VS_KIND_CSR = 0, 1
 TERM_FILTER_SLOTS, TERM_FILTER_TERMS, TERM_FILTER_LIST = 255, 4096, 64
 # diversified search (VS_MMR_*): similarity modes, the deepest candidate list / most picks, the widest vocabulary of vs_mmr_select_csr
 MMR_COSINE, MMR_DOT, MMR_MAX_DEPTH, MMR_MAX_COLS = 0, 1, 1024, 32768
+# range search (VS_RANGE_MAX_HITS): the most hits vs_index_search_range lists per query
+RANGE_MAX_HITS = 2048
 
 
 class VsearchNativeError(RuntimeError):
@@ -55,6 +57,8 @@ _SIGNATURES = {
     "vs_index_create_synthetic": ([C.c_uint64, _i64, _i64, _i32, _i32, _int, _int, _int, _int, C.POINTER(_vp)], _int),
     "vs_index_search": ([_vp, _vp, _int, _i64, _i32, _i32, _i64, _vp, _vp, _vp], _int),
     "vs_index_search_filtered": ([_vp, _vp, _int, _i64, _i32, _i32, _vp, _i64, _i64, _i64, _vp, _vp, _vp], _int),
+    "vs_index_search_range": ([_vp, _vp, _int, _i64, _i32, _vp, _i32, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp], _int),
+    "vs_index_last_range_plan": ([_vp, C.POINTER(_i32), C.POINTER(_i64)], _int),
     "vs_filter_pack": ([_vp, _i32, _i64, _i64, _vp, _i64, _int, _vp], _int),
     "vs_index_scores": ([_vp, _vp, _int, _i64, _i32, _vp, _vp], _int),
     "vs_index_explain": ([_vp, _vp, _int, _i64, _i32, _vp, _i64, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp], _int),

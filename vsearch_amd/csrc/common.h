@@ -299,6 +299,7 @@ struct vs_index {
     int bp_state = 0;    // vs_index_info_t.postings_state: 0 not attempted, 1 ready, 2 no HBM room, 3 directory overflow, 4 not wanted (small index / option)
     int64_t last_scan_bytes = 0;   // bytes the scan kernels of the most recent search had to read (algorithmic, per path)
     int last_path = 0;             // 0 = one query per pass, 1 = 8-query CSR scan, 2 = blocked postings
+    int last_chunks = 0;           // row chunks of the most recent range search's scan (vs_index_last_range_plan; its last sub-batch)
     int bp_pref = -1;    // option "blocked_postings": -1 auto, 0 never, 1 always
     int bp_rows_pref = 0;// option "postings_rows": 0 = auto, else documents per block (multiple of 64, 256..2048); applies at the next build
     int bp_chunks = 0;   // option "postings_chunks": 0 = auto, else block runs per tile on the postings path

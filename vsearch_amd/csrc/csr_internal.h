@@ -76,6 +76,28 @@ int bp_exact_walk(const vs_index* idx, const BpArgs& a, int grid, int ent_cap, h
 
 
 // ---- mq_search.hip ------------------------------------------------------------------------------------------------------------
+// A query batch in the form the tile scans and the fp64 walk read: CSR over the batch + the greedy tile plan (device pointers into the
+// handle's scratch), and the plan's figures on the host (mq_plan_kernel: [0] tiles, [1] non-zeros of the densest query, [2] all non-zeros,
+// [3] column-overlap sum; [4], [5] the walk's records / postings when walk_df was asked for).
+struct MqBatch {
+    int64_t* qptr;
+    int32_t* qcols;
+    float* qvals;
+    int2* tiles;
+    int n_tiles;
+    int64_t qnnz;
+    int64_t hplan[6];
+};
+// Sparsifies dq [B, n_cols] into tiles of <= qt queries and <= vals_cap non-zeros (synchronises the stream to read the plan back).
+// *fits = false -- and nothing filled -- when a query is denser than vals_cap: the batch does not qualify for tiles.
+int mq_sparsify(vs_index* idx, const float* dq, int32_t B, int qt, int vals_cap, bool walk_df, hipStream_t s, MqBatch* out, bool* fits);
+// the CSR tile scan's arguments for a sparsified batch, and its launch shape
+void mq_fill_args(const vs_index* idx, const MqBatch& b, int k, int nchunk, int vals_cap, MqArgs* a);
+inline size_t mq_lds_bytes(const vs_index* idx, int vals_cap) { return mq_fixed_lds_bytes<kQT>(idx->n_cols, mq_acc_rows(idx)) + (size_t)vals_cap * 4; }
+inline int mq_packets_per_trip(const vs_index* idx) {       // enough to cover an average row in one trip, at most 3
+    const double ppr = idx->n_rows > 0 ? (double)idx->n_packets / (double)idx->n_rows : 1.0;
+    return std::max(1, std::min(3, (int)((ppr + mq_lanes(idx) - 1) / mq_lanes(idx))));
+}
 int mq_search(vs_index* idx, const float* dq, int32_t B, int32_t k, int64_t id_offset, int64_t* d_ids, float* d_scores,
               const ScanPlan& plan, hipStream_t s, bool* done, int32_t out_ld, int32_t col0, uint64_t* upper);
 

@@ -401,6 +401,12 @@ __global__ __launch_bounds__(kScanThreads) void exact_scan_topk_kernel(KArg<Scan
     }
 }
 
+// ---- range search (range.hip): the floor key of a threshold ------------------------------------------------------------------------
+// A row matches threshold t iff score >= t as floats (-0.0 == +0.0): iff its key is at or above the lowest key that carries t.  A NaN
+// threshold matches no row.
+constexpr uint64_t kRangeNoMatch = ~0ull;
+__device__ __forceinline__ uint64_t range_floor_key(float thr) { return thr != thr ? kRangeNoMatch : make_key(canon_zero(thr), 0xFFFFFFFFu); }
+
 // ---- merge: per query, [n_lists * k] keys (each list sorted or not) -> top-k ids + scores --------
 struct MergeArgs {
     const uint64_t* cand;     // [B, n_cand]

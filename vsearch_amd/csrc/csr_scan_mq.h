@@ -101,6 +101,18 @@ struct MqArgs {
     const uint64_t* upper;    // optional [B]: only keys < upper[b] take part ("search after": passes beyond the first when k > kMaxKMq)
 };
 
+// Range search (range.hip): the RG = 1 instantiation takes these behind MqArgs.  A row MATCHES query b iff its key is at or above the floor
+// key of thr[b] (range_floor_key, csr_scan.h) and the filter allows it; every match is counted and its bit set, whether or not it then
+// enters the candidate buffer (k = max_hits; k = 0 keeps no candidates).
+struct MqRangeArgs : MqArgs {
+    const float* thr;                 // [B]
+    unsigned long long* count;        // [B], zeroed by the caller: one atomicAdd per (work item, query)
+    uint32_t* words;                  // optional [B, ld_words] match bitmaps, zeroed by the caller
+    int64_t ld_words;
+};
+template <int RG>
+using MqKernelArgs = typename std::conditional<RG != 0, MqRangeArgs, MqArgs>::type;
+
 template <int QT>
 __host__ __device__ inline size_t mq_fixed_lds_bytes(int32_t n_cols, int rows_in_flight) {
     const size_t tab = (((size_t)n_cols + 1) * 4 + 15) & ~(size_t)15;
@@ -112,9 +124,10 @@ __host__ __device__ inline size_t mq_fixed_lds_bytes(int32_t n_cols, int rows_in
 // queries (T as low as the LDS slack allows, >= 3) are stored as zero-padded 8-float rows; a hit on such a
 // column costs two ds_read_b128 + 8 multiply-adds into per-lane fp64 registers (flushed once per row)
 // instead of up to 8 trips through the one-hit-at-a-time remainder loop.
-template <int G, int VM, int QT, int U, int DN, int FL = 0>          // FL = 1: a filtered search (KArg, common.h)
-__global__ __launch_bounds__(kScanThreads) void csr_scan_topk_mq(KArg<MqArgs, FL> a) {
+template <int G, int VM, int QT, int U, int DN, int FL = 0, int RG = 0>          // FL = 1: a filtered search (KArg, common.h); RG = 1: range search
+__global__ __launch_bounds__(kScanThreads) void csr_scan_topk_mq(KArg<MqKernelArgs<RG>, FL> a) {
     static_assert(QT == 8 && G >= 8, "the packed hit word assumes 8 query slots per tile; lanes 0..7 of a row group finish them");
+    static_assert(RG == 0 || DN == 0, "the range variant keeps its match counters where the shared-column variant keeps its histogram");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int RPW = 64 / G;
     constexpr int RPI = kScanWaves * RPW;
@@ -127,6 +140,7 @@ __global__ __launch_bounds__(kScanThreads) void csr_scan_topk_mq(KArg<MqArgs, FL
     unsigned long long* tau = reinterpret_cast<unsigned long long*>(acc + RPI * S * QT);   // [QT]
     int* scratch = reinterpret_cast<int*>(tau + QT);                            // [48]
     unsigned int* ccnt = reinterpret_cast<unsigned int*>(scratch + 48);         // [QT] candidate counts (keys live in global memory)
+    unsigned int* mcnt = reinterpret_cast<unsigned int*>(scratch + 56);         // [QT] RG: matches of the work item (DN: the histogram)
     float* qv = reinterpret_cast<float*>(scratch + 64);                         // [vals_cap]
 
     const uint32_t qv_addr = (uint32_t)(reinterpret_cast<char*>(qv) - smem);    // LDS byte address of qv (smem starts at 0)
@@ -145,11 +159,14 @@ __global__ __launch_bounds__(kScanThreads) void csr_scan_topk_mq(KArg<MqArgs, FL
         const int64_t r0 = (int64_t)c * a.rows_per_chunk;
         const int64_t r1 = min(a.n_rows, r0 + a.rows_per_chunk);
         const uint64_t my_upper = (a.upper && lg < nq) ? a.upper[q0 + lg] : ~0ull;
+        uint64_t my_floor = 0ull;
+        if constexpr (RG != 0) my_floor = lg < nq ? range_floor_key(a.thr[q0 + lg]) : kRangeNoMatch;
         __syncthreads();
         // ---- build the tile tables ----
         for (int i = tid; i <= a.n_cols; i += kScanThreads) tab[i] = 0;
         for (int i = tid; i < RPI * S * QT; i += kScanThreads) acc[i] = 0.0;
         if (tid < QT) { tau[tid] = 0ull; ccnt[tid] = 0u; }
+        if constexpr (RG != 0) { if (tid < QT) mcnt[tid] = 0u; }
         __syncthreads();
         const int64_t e0 = a.qptr[q0], e1 = a.qptr[q0 + nq];
         for (int64_t e = e0 + tid; e < e1; e += kScanThreads) {
@@ -385,7 +402,18 @@ __global__ __launch_bounds__(kScanThreads) void csr_scan_topk_mq(KArg<MqArgs, FL
                     }
                     const uint64_t key = make_key((float)sum, (uint32_t)row);
                     bool pass = key > tau[lg] && key < my_upper;
-                    if constexpr (FL != 0) pass = pass && filter_ok(a, q0 + lg, row);
+                    if constexpr (RG != 0) {
+                        // the floor and the filter decide the match; the count and the bit come before the tau test (a prune loses none)
+                        bool match = key >= my_floor && my_floor != kRangeNoMatch;
+                        if constexpr (FL != 0) match = match && filter_ok(a, q0 + lg, row);
+                        if (match) {
+                            atomicAdd(&mcnt[lg], 1u);
+                            if (a.words) atomicOr(&a.words[(size_t)(q0 + lg) * (size_t)a.ld_words + (size_t)(row >> 5)], 1u << (row & 31));
+                        }
+                        pass = pass && match && K > 0;
+                    } else {
+                        if constexpr (FL != 0) pass = pass && filter_ok(a, q0 + lg, row);
+                    }
                     if (pass) {
                         const uint32_t pos = atomicAdd(&ccnt[lg], 1u);
                         my_gcand[(size_t)lg * kMqCap + pos] = key;
@@ -394,7 +422,7 @@ __global__ __launch_bounds__(kScanThreads) void csr_scan_topk_mq(KArg<MqArgs, FL
             }
             __syncthreads();
             const bool last = it1 >= iters;
-            for (int qs = 0; qs < nq; ++qs) {
+            for (int qs = 0; qs < (RG != 0 && K == 0 ? 0 : nq); ++qs) {        // (a count-only range scan keeps no candidates: nothing to sort or write)
                 const uint32_t cnt = ccnt[qs];
                 if (last || cnt > (uint32_t)(kMqCap - kMqSuperRows)) {
                     for (int i = tid; i < kMqCap; i += kScanThreads) sortbuf[i] = (uint32_t)i < cnt ? my_gcand[(size_t)qs * kMqCap + i] : 0ull;
@@ -413,6 +441,9 @@ __global__ __launch_bounds__(kScanThreads) void csr_scan_topk_mq(KArg<MqArgs, FL
                 }
             }
             __syncthreads();
+            if constexpr (RG != 0) {
+                if (last && tid < nq && mcnt[tid]) atomicAdd(&a.count[q0 + tid], (unsigned long long)mcnt[tid]);
+            }
             if (last) break;
         }
     }

@@ -41,6 +41,66 @@ constexpr double kMqSharedOverlap = 40.0;   // columns shared by two queries abo
 
 }  // namespace
 
+// The sparse form of a batch and its tile plan (csr_internal.h), for mq_search and for the range search's tile scan (range.hip)
+int mq_sparsify(vs_index* idx, const float* dq, int32_t B, int qt, int vals_cap, bool walk_df, hipStream_t s, MqBatch* out, bool* fits) {
+    *fits = false;
+    const int V = idx->n_cols;
+    const size_t off_counts = 0, off_qptr = off_counts + (size_t)B * 8, off_plan = off_qptr + (size_t)(B + 1) * 8,
+                 off_tiles = off_plan + 64, off_freq = off_tiles + (((size_t)B * sizeof(int2) + 15) & ~(size_t)15);
+    VS_TRY(idx->ws_mq_meta.reserve(off_freq + (size_t)(V + 4) * 4 + 8));
+    char* meta = idx->ws_mq_meta.as<char>();
+    int64_t* counts = (int64_t*)(meta + off_counts);
+    int64_t* qptr = (int64_t*)(meta + off_qptr);
+    int64_t* dplan = (int64_t*)(meta + off_plan);
+    int2* tiles = (int2*)(meta + off_tiles);
+    uint32_t* colfreq = (uint32_t*)(meta + off_freq);
+    VS_HIP(hipMemsetAsync(colfreq, 0, (size_t)(V + 4) * 4 + 8, s));          // counts + the 64-bit overlap sum behind them
+    hipLaunchKernelGGL(count_nz_kernel<0>, dim3(std::min(B, 2048)), dim3(kSpThreads), 0, s, dq, (int64_t)V, B, V, counts);
+    hipLaunchKernelGGL(mq_colfreq_kernel<0>, dim3(std::min(B, 2048)), dim3(kSpThreads), 0, s, dq, (int64_t)V, B, V, colfreq);
+    hipLaunchKernelGGL(mq_plan_kernel<0>, dim3(1), dim3(64), 0, s, counts, B, qt, vals_cap, qptr, tiles, dplan, colfreq, V);
+    VS_HIP(hipGetLastError());
+    if (walk_df)
+        hipLaunchKernelGGL(bp_walk_kernel<0>, dim3(1), dim3(kScanThreads), 0, s, colfreq, idx->bp_df.as<unsigned long long>(),
+                           idx->bp_df.as<unsigned long long>() + V, V, dplan + 4);
+    for (int64_t& h : out->hplan) h = 0;
+    VS_HIP(hipMemcpyAsync(out->hplan, dplan, sizeof(out->hplan), hipMemcpyDeviceToHost, s));
+    VS_HIP(hipStreamSynchronize(s));
+    if (out->hplan[1] > vals_cap) return VS_OK;                  // some query is too dense for the tile tables
+    out->n_tiles = (int)out->hplan[0];
+    out->qnnz = out->hplan[2];
+    VS_TRY(idx->ws_mq_q.reserve(std::max<size_t>((size_t)out->qnnz * 8, 16)));
+    out->qptr = qptr;
+    out->tiles = tiles;
+    out->qcols = idx->ws_mq_q.as<int32_t>();
+    out->qvals = reinterpret_cast<float*>(out->qcols + out->qnnz);
+    hipLaunchKernelGGL(fill_csr_kernel<0>, dim3(std::min(B, 2048)), dim3(kSpThreads), 0, s, dq, (int64_t)V, B, V, qptr, out->qcols, out->qvals, out->qnnz);
+    VS_HIP(hipGetLastError());
+    VS_STAGE("sparsify", s);
+    if (debug_sync_on()) fprintf(stderr, "[vsearch_hip] plan: tiles %d qnnz %lld max %lld cap %d\n", out->n_tiles, (long long)out->qnnz, (long long)out->hplan[1], vals_cap);
+    *fits = true;
+    return VS_OK;
+}
+
+void mq_fill_args(const vs_index* idx, const MqBatch& b, int k, int nchunk, int vals_cap, MqArgs* a) {
+    a->pk_ptr = idx->pk_ptr.as<uint32_t>();
+    a->cols = idx->cols.as<uint4>();
+    a->vals = idx->vals.p;
+    a->n_rows = idx->n_rows;
+    a->n_cols = idx->n_cols;
+    a->k = k;
+    a->nchunk = nchunk;
+    a->rows_per_chunk = ceil_div64(idx->n_rows, nchunk);
+    a->qptr = b.qptr;
+    a->qcols = b.qcols;
+    a->qvals = b.qvals;
+    a->tiles = b.tiles;
+    a->n_tiles = b.n_tiles;
+    a->vals_cap = vals_cap;
+    a->cand = idx->ws_cand.as<uint64_t>();
+    a->gcand = idx->ws_mq_cand.as<uint64_t>();
+    a->upper = nullptr;
+}
+
 // Multi-query pass (Qt = kQT).  Returns VS_OK and sets *done = false when the batch does not qualify
 // (a query denser than the LDS weight capacity): the caller then takes the dense-image path.
 // One pass delivers ranks [col0, col0 + k) of every query into columns col0.. of the [B, out_ld] outputs; `upper`
@@ -60,36 +120,17 @@ int mq_search(vs_index* idx, const float* dq, int32_t B, int32_t k, int64_t id_o
     if (vals_cap <= 0 || k > (use_bp ? kBpMaxK : kMaxKMq)) return VS_OK;     // (callers split larger k into passes)
     const int V = idx->n_cols;
     // 1. sparsify the batch: counts -> (qptr, tiles, plan) -> (qcols, qvals)
-    const size_t off_counts = 0, off_qptr = off_counts + (size_t)B * 8, off_plan = off_qptr + (size_t)(B + 1) * 8,
-                 off_tiles = off_plan + 64, off_freq = off_tiles + (((size_t)B * sizeof(int2) + 15) & ~(size_t)15);
-    VS_TRY(idx->ws_mq_meta.reserve(off_freq + (size_t)(V + 4) * 4 + 8));
-    char* meta = idx->ws_mq_meta.as<char>();
-    int64_t* counts = (int64_t*)(meta + off_counts);
-    int64_t* qptr = (int64_t*)(meta + off_qptr);
-    int64_t* dplan = (int64_t*)(meta + off_plan);
-    int2* tiles = (int2*)(meta + off_tiles);
-    uint32_t* colfreq = (uint32_t*)(meta + off_freq);
-    VS_HIP(hipMemsetAsync(colfreq, 0, (size_t)(V + 4) * 4 + 8, s));          // counts + the 64-bit overlap sum behind them
-    hipLaunchKernelGGL(count_nz_kernel<0>, dim3(std::min(B, 2048)), dim3(kSpThreads), 0, s, dq, (int64_t)V, B, V, counts);
-    hipLaunchKernelGGL(mq_colfreq_kernel<0>, dim3(std::min(B, 2048)), dim3(kSpThreads), 0, s, dq, (int64_t)V, B, V, colfreq);
-    hipLaunchKernelGGL(mq_plan_kernel<0>, dim3(1), dim3(64), 0, s, counts, B, qt_plan, vals_cap, qptr, tiles, dplan, colfreq, V);
-    VS_HIP(hipGetLastError());
-    if (use_bp && idx->bp_df.p)
-        hipLaunchKernelGGL(bp_walk_kernel<0>, dim3(1), dim3(kScanThreads), 0, s, colfreq, idx->bp_df.as<unsigned long long>(),
-                           idx->bp_df.as<unsigned long long>() + V, V, dplan + 4);
-    int64_t hplan[6] = {0, 0, 0, 0, 0, 0};
-    VS_HIP(hipMemcpyAsync(hplan, dplan, sizeof(hplan), hipMemcpyDeviceToHost, s));
-    VS_HIP(hipStreamSynchronize(s));
-    if (hplan[1] > vals_cap) return VS_OK;                       // some query is too dense for the tile tables
-    const int n_tiles = (int)hplan[0];
-    const int64_t qnnz = hplan[2];
-    VS_TRY(idx->ws_mq_q.reserve(std::max<size_t>((size_t)qnnz * 8, 16)));
-    int32_t* qcols = idx->ws_mq_q.as<int32_t>();
-    float* qvals = reinterpret_cast<float*>(qcols + qnnz);
-    hipLaunchKernelGGL(fill_csr_kernel<0>, dim3(std::min(B, 2048)), dim3(kSpThreads), 0, s, dq, (int64_t)V, B, V, qptr, qcols, qvals, qnnz);
-    VS_HIP(hipGetLastError());
-    VS_STAGE("sparsify", s);
-    if (debug_sync_on()) fprintf(stderr, "[vsearch_hip] plan: tiles %d qnnz %lld max %lld cap %d\n", n_tiles, (long long)qnnz, (long long)hplan[1], vals_cap);
+    MqBatch mb{};
+    bool fits = false;
+    VS_TRY(mq_sparsify(idx, dq, B, qt_plan, vals_cap, use_bp && idx->bp_df.p, s, &mb, &fits));
+    if (!fits) return VS_OK;                                     // some query is too dense for the tile tables
+    const int n_tiles = mb.n_tiles;
+    const int64_t qnnz = mb.qnnz;
+    const int64_t* hplan = mb.hplan;
+    int64_t* qptr = mb.qptr;
+    int32_t* qcols = mb.qcols;
+    float* qvals = mb.qvals;
+    int2* tiles = mb.tiles;
     // 2. scan.  Work items = (tile, row chunk)
     int nchunk = choose_chunks(idx, n_tiles, plan.nchunk);
     if (use_bp) {
@@ -131,37 +172,19 @@ int mq_search(vs_index* idx, const float* dq, int32_t B, int32_t k, int64_t id_o
         VS_TRY(bp_exact_walk(idx, a, grid, vals_cap, s));
         VS_STAGE("fp64 walk", s);
     } else {
-    const int64_t rows_per_chunk = ceil_div64(idx->n_rows, nchunk);
     const int64_t items = (int64_t)n_tiles * nchunk;
     const int grid = (int)std::min<int64_t>(items, idx->cu_count);
     VS_TRY(idx->ws_mq_cand.reserve((size_t)grid * kQT * kMqCap * 8));
     VS_TRY(idx->ws_cand.reserve((size_t)B * nchunk * k * 8));
     MqArgs a{};
-    a.pk_ptr = idx->pk_ptr.as<uint32_t>();
-    a.cols = idx->cols.as<uint4>();
-    a.vals = idx->vals.p;
-    a.n_rows = idx->n_rows;
-    a.n_cols = V;
-    a.k = k;
-    a.nchunk = nchunk;
-    a.rows_per_chunk = rows_per_chunk;
-    a.qptr = qptr;
-    a.qcols = qcols;
-    a.qvals = qvals;
-    a.tiles = tiles;
-    a.n_tiles = n_tiles;
-    a.vals_cap = vals_cap;
-    a.cand = idx->ws_cand.as<uint64_t>();
-    a.gcand = idx->ws_mq_cand.as<uint64_t>();
+    mq_fill_args(idx, mb, k, nchunk, vals_cap, &a);
     a.upper = col0 > 0 ? upper : nullptr;
-    const size_t lds = mq_fixed_lds_bytes<kQT>(V, mq_acc_rows(idx)) + (size_t)vals_cap * 4;
+    const size_t lds = mq_lds_bytes(idx, vals_cap);
     idx->last_scan_bytes += (int64_t)n_tiles * csr_bytes_per_pass(idx);
     idx->last_path = 1;
     {
         ProfScope prof("csr_scan_topk", s);
-        // packets per lane per trip: enough to cover an average row in one trip, at most 3
-        const double ppr = idx->n_rows > 0 ? (double)idx->n_packets / (double)idx->n_rows : 1.0;
-        const int u = std::max(1, std::min(3, (int)((ppr + mq_lanes(idx) - 1) / mq_lanes(idx))));
+        const int u = mq_packets_per_trip(idx);
         // expected number of columns two queries of the batch share; uniform 776-nnz queries: ~20
         const double overlap = B > 1 ? (double)hplan[3] / ((double)B * (double)(B - 1)) : 0.0;
         const bool shared_cols = idx->mq_variant >= 0 ? idx->mq_variant == 1 : overlap > kMqSharedOverlap;

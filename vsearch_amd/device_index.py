@@ -505,6 +505,98 @@ def mmr_select(indptr, indices, values, ids, scores, k: int, lam, mode: str, n_c
     return tuple(out)
 
 
+class RangeResults(NamedTuple):
+    """search_range: per query the number of matching documents (exact, whatever max_hits is) and the first max_hits of them in the
+    canonical order (score descending, id ascending): all of them when counts[b] <= max_hits, else the top max_hits; id -1 / score
+    -inf behind the matches."""
+    ids: Any           # int64 [B, max_hits]
+    scores: Any        # float32 [B, max_hits]
+    counts: Any        # int64 [B]
+
+
+MAX_RANGE_HITS = nat.RANGE_MAX_HITS
+
+
+def _range_args(q, min_score, max_hits):
+    """Argument checks of a range search that need no device -> (B, thresholds float32 ndarray [B], max_hits)"""
+    if isinstance(max_hits, bool) or not isinstance(max_hits, (int, np.integer)):
+        raise TypeError(f"max_hits must be an int, got {type(max_hits).__name__}")
+    max_hits = int(max_hits)
+    if not 0 <= max_hits <= MAX_RANGE_HITS:
+        raise ValueError(f"max_hits must be in 0..{MAX_RANGE_HITS}, got {max_hits}")
+    if not hasattr(q, "ndim") or q.ndim != 2:
+        raise ValueError("queries must be [B, V]")
+    B = int(q.shape[0])
+    if _is_torch(min_score):
+        min_score = min_score.detach().cpu().numpy()
+    thr = np.asarray(min_score, dtype=np.float32)
+    if thr.ndim == 0:
+        thr = np.full(B, thr, dtype=np.float32)
+    if thr.ndim != 1 or thr.shape[0] != B:
+        raise ValueError(f"min_score: one number, or one per query ({B}); got shape {tuple(thr.shape)}")
+    if np.isnan(thr).any():
+        raise ValueError("min_score is NaN")
+    return B, np.ascontiguousarray(thr), max_hits
+
+
+def _words_to_int32(words_i64):
+    """uint32 values held in int64 -> the int32 words of a DocFilter"""
+    import torch
+    return (words_i64 - ((words_i64 >> 31) << 32)).to(torch.int32)
+
+
+def _range_shards(group, q, min_score, max_hits, filter, want_words):
+    """Range search of a ShardGroup: every shard with its id_offset (and its bit range of the filter); lists merged with vs_merge_topk on
+    the first shard's GPU, counts summed, bitmaps placed at their bit offsets -> (ids, scores, counts, words | None) on that GPU."""
+    import torch
+    B, thr, K = _range_args(q, min_score, max_hits)
+    nat.require_device()
+    dev0 = torch.device("cuda", group.device)
+    qt = q if _is_torch(q) else torch.from_numpy(np.ascontiguousarray(q))
+    n_total = group.n_rows
+    f = None
+    if filter is not None:
+        from .doc_filter import as_doc_filter
+        f = as_doc_filter(filter, n_total, device=dev0, batch=B)
+    W = (n_total + 31) // 32
+    words = torch.zeros((B, W + 1), dtype=torch.int64, device=dev0) if want_words else None
+    counts = torch.zeros(B, dtype=torch.int64, device=dev0)
+    lists, row0 = [], 0
+    for sh in group._shards:
+        dev = torch.device("cuda", sh.device)
+        n = int(sh.info().n_rows)
+        fs = f.to(dev) if f is not None else None
+        ids, sc, cnt, w = sh._range_call(qt.to(dev), thr, K, fs, row0, want_words, filter_bit0=row0)
+        counts += cnt.to(dev0)
+        if K:
+            lists.append((ids.to(dev0), sc.to(dev0)))
+        if want_words:
+            w = w.to(dev0).to(torch.int64) & 0xFFFFFFFF
+            w0, sft, wn = row0 >> 5, row0 & 31, int(w.shape[1])
+            words[:, w0:w0 + wn] |= (w << sft) & 0xFFFFFFFF
+            if sft:
+                words[:, w0 + 1:w0 + 1 + wn] |= w >> (32 - sft)
+        row0 += n
+    if K:
+        ids, sc = merge_topk(torch.cat([l[0] for l in lists], dim=1).contiguous(), torch.cat([l[1] for l in lists], dim=1).contiguous(), K,
+                             device=group.device)
+    else:
+        ids = torch.empty((B, 0), dtype=torch.int64, device=dev0)
+        sc = torch.empty((B, 0), dtype=torch.float32, device=dev0)
+    if want_words:
+        words = _words_to_int32(words[:, :W]).contiguous()
+    return ids, sc, counts, words
+
+
+def _range_out(q, *tensors):
+    """results in the kind of the query: torch CUDA in -> as they are, torch CPU in -> CPU tensors, numpy in -> ndarrays"""
+    if _is_torch(q) and q.is_cuda:
+        return tensors
+    if _is_torch(q):
+        return tuple(t.cpu() for t in tensors)
+    return tuple(t.cpu().numpy() for t in tensors)
+
+
 def _host(x):
     return x.detach().numpy() if _is_torch(x) else x
 
@@ -1063,6 +1155,85 @@ class DeviceIndex:
         filtered list: anything after a list's first id -1 is ignored).  Rows are read as stored, deleted ones included."""
         return _diversify(self, ids, scores, k, lam, sim, max_row_bytes)
 
+    # ---- range search: every document scoring at least a threshold (vs_index_search_range) -------------------------------------------
+    def _range_call(self, q, thr, max_hits, filter, id_offset, want_words, filter_bit0=0):
+        """One vs_index_search_range call -> (ids, scores, counts, words | None).  A torch CUDA q runs on device buffers and torch's current
+        stream; anything else on host buffers (blocking).  thr: float32 ndarray [B]; filter: None or a DocFilter on this index's device."""
+        p, dt, keep, B, ldq = self._q_args(q)
+        n = int(self.info().n_rows)
+        W = (n + 31) // 32
+        K = int(max_hits)
+        fn = nat.lib().vs_index_search_range
+        if _is_torch(q) and q.is_cuda:
+            import torch
+            dev = torch.device("cuda", self.device)
+            t_thr = torch.from_numpy(thr).to(dev)
+            ids = torch.empty((B, K), dtype=torch.int64, device=dev)
+            scores = torch.empty((B, K), dtype=torch.float32, device=dev)
+            counts = torch.empty(B, dtype=torch.int64, device=dev)
+            words = torch.empty((B, W), dtype=torch.int32, device=dev) if want_words else None
+            fp = C.c_void_p(filter.words.data_ptr()) if filter is not None else None
+            nat.check(fn(self._h, p, dt, ldq, B, C.c_void_p(t_thr.data_ptr()), K, fp, int(filter_bit0), filter.ld if filter is not None else 0,
+                         int(id_offset), _ptr(ids) if K else None, _ptr(scores) if K else None, _ptr(counts), _ptr(words) if want_words else None, W,
+                         current_stream(self.device)))
+            return ids, scores, counts, words
+        if filter is not None:
+            # the filter's words live on the GPU and the call takes all-host or all-device buffers: run on the device, bring the results back
+            import torch
+            qd = (q if _is_torch(q) else torch.from_numpy(np.ascontiguousarray(q))).to(torch.device("cuda", self.device))
+            out = self._range_call(qd, thr, K, filter, id_offset, want_words, filter_bit0)
+            out = tuple(t.cpu() if t is not None else None for t in out)
+            return out if _is_torch(q) else tuple(t.numpy() if t is not None else None for t in out)
+        ids = np.empty((B, K), dtype=np.int64)
+        scores = np.empty((B, K), dtype=np.float32)
+        counts = np.empty(B, dtype=np.int64)
+        words = np.empty((B, W), dtype=np.int32) if want_words else None
+        ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None and a.size else None
+        nat.check(fn(self._h, p, dt, ldq, B, ptr(thr), K, None, 0, 0, int(id_offset), ptr(ids), ptr(scores), ptr(counts), ptr(words), W, None))
+        if _is_torch(q):
+            import torch
+            return (torch.from_numpy(ids), torch.from_numpy(scores), torch.from_numpy(counts), torch.from_numpy(words) if want_words else None)
+        return ids, scores, counts, words
+
+    def _range(self, q, min_score, max_hits, filter, id_offset, want_words):
+        B, thr, K = _range_args(q, min_score, max_hits)
+        nat.require_device()
+        f = None
+        if filter is not None:
+            from .doc_filter import as_doc_filter
+            f = as_doc_filter(filter, int(self.info().n_rows), device=self.device, batch=B)
+        return self._range_call(q, thr, K, f, id_offset, want_words)
+
+    def last_range_plan(self):
+        """(row chunks, rows a chunk) of the scan the most recent range search on this index took (vs_index_last_range_plan)"""
+        chunks, rpc = C.c_int32(0), C.c_int64(0)
+        nat.check(nat.lib().vs_index_last_range_plan(self._h, C.byref(chunks), C.byref(rpc)))
+        return chunks.value, rpc.value
+
+    def search_range(self, q, min_score, max_hits: int = 100, filter=None, id_offset: int = 0) -> RangeResults:
+        """Every live, allowed document scoring at least min_score (one number, or one per query), counted -> RangeResults(ids, scores,
+        counts): counts [B] is exact whatever max_hits is; ids / scores [B, max_hits] hold the matches in the canonical order -- all of
+        them when counts[b] <= max_hits, else the top max_hits -- with id -1 / score -inf behind them.  The score is the library's exact
+        numerics on every path (what explain() reports for the pair), so membership does not depend on the kernel that served the call.
+        max_hits in 0..2048; filter as in search().  numpy in -> numpy out; torch CUDA in -> tensors on the index's device."""
+        ids, scores, counts, _ = self._range(q, min_score, max_hits, filter, id_offset, False)
+        return RangeResults(ids, scores, counts)
+
+    def count_matches(self, q, min_score, filter=None):
+        """The number of live, allowed documents scoring at least min_score, per query: int64 [B] (search_range with max_hits = 0)."""
+        return self._range(q, min_score, 0, filter, 0, False)[2]
+
+    def match_filter(self, q, min_score, filter=None):
+        """The documents search_range matches, as a per-query DocFilter [B, W] on the index's device: the uncapped result, ready for
+        ``search(filter=)`` and for ``&``, ``|``, ``~`` with any other filter."""
+        from .doc_filter import DocFilter
+        import torch
+        _range_args(q, min_score, 0)
+        dev = torch.device("cuda", self.device)
+        qd = q.to(dev) if _is_torch(q) else torch.from_numpy(np.ascontiguousarray(q)).to(dev)
+        words = self._range(qd, min_score, 0, filter, 0, True)[3]
+        return DocFilter(words, int(self.info().n_rows))
+
     def scores(self, q):
         """Dense [B, n_rows] fp32 score matrix (what index.py:91 materialises). numpy out."""
         info = self.info()
@@ -1274,6 +1445,21 @@ class ShardGroup:
     def diversify(self, ids, scores, k: int, lam=0.5, sim: str = "cosine", max_row_bytes=None) -> DiverseResults:
         """DeviceIndex.diversify with global ids."""
         return _diversify(self, ids, scores, k, lam, sim, max_row_bytes)
+
+    def search_range(self, q, min_score, max_hits: int = 100, filter=None) -> RangeResults:
+        """DeviceIndex.search_range over the group's rows (global ids): every shard runs with its id_offset, the lists are merged on the
+        first shard's GPU and the counts summed.  Equal to the unsharded index bit for bit."""
+        ids, sc, counts, _ = _range_shards(self, q, min_score, max_hits, filter, False)
+        return RangeResults(*_range_out(q, ids, sc, counts))
+
+    def count_matches(self, q, min_score, filter=None):
+        """DeviceIndex.count_matches over the group's rows: the shards' counts summed."""
+        return _range_out(q, _range_shards(self, q, min_score, 0, filter, False)[2])[0]
+
+    def match_filter(self, q, min_score, filter=None):
+        """DeviceIndex.match_filter over the group's rows: the shards' bitmaps at their bit offsets, on the first shard's GPU."""
+        from .doc_filter import DocFilter
+        return DocFilter(_range_shards(self, q, min_score, 0, filter, True)[3], self.n_rows)
 
     def close(self):
         if self._h:

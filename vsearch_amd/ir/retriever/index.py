@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from ... import _native as nat
-from ...device_index import DeviceIndex, DiverseResults, Explanation, GroupedResults, NotBinaryError, ShardGroup, _diverse_args, _grouped_args, _by_example_args, _explain_args, _int64_ids, _k_a_args, resparsify, topk_exclude
+from ...device_index import DeviceIndex, DiverseResults, Explanation, GroupedResults, NotBinaryError, RangeResults, ShardGroup, _diverse_args, _range_args, _grouped_args, _by_example_args, _explain_args, _int64_ids, _k_a_args, resparsify, topk_exclude
 
 logger = logging.getLogger(__name__)
 
@@ -456,6 +456,41 @@ class Index:
             q = q.unsqueeze(0)
         res = target.search_grouped(q.contiguous(), int(k), self._groups, per_group=int(per_group), filter=filter, depth=depth)
         return GroupedResults(self._to_api(res.groups), self._to_api(res.ids), self._to_api(res.scores.to(self._dtype)))
+
+    # ---- range search (not in the reference: every document scoring at least a threshold, counted) ------------------------------------------
+    def _range_queries(self, q_embs, min_score, max_hits):
+        """the argument checks (before any device call), then (search target, queries on its GPU in the index dtype)"""
+        if isinstance(q_embs, np.ndarray):
+            q_embs = torch.from_numpy(q_embs)
+        q = q_embs.detach()
+        if q.dim() == 1:
+            q = q.unsqueeze(0)
+        _range_args(q, min_score, max_hits)
+        target, gpu_ord = self._explain_target()
+        q = q.to(torch.device("cuda", gpu_ord))
+        q = q.to(self._dtype) if self._dtype in (torch.float16, torch.float32) else q.float()
+        return target, q.contiguous()
+
+    def search_range(self, q_embs, min_score, max_hits: int = 100, filter=None) -> RangeResults:
+        """Every document scoring at least `min_score` (one number, or one per query) -> RangeResults(ids, scores, counts): counts [B] is
+        the exact number of matches whatever max_hits is; ids / scores [B, max_hits] hold them in the canonical order -- all of them when
+        counts[b] <= max_hits, else the top max_hits -- with id -1 / score -inf behind.  One numerics decides membership on every path
+        (the score ``explain`` reports).  max_hits in 0..2048.  Deleted documents and `filter` (as ``search``) apply.  Works on a
+        row-sharded index as well."""
+        target, q = self._range_queries(q_embs, min_score, max_hits)
+        res = target.search_range(q, min_score, max_hits=int(max_hits), filter=filter)
+        return RangeResults(self._to_api(res.ids), self._to_api(res.scores.to(self._dtype)), self._to_api(res.counts))
+
+    def count_matches(self, q_embs, min_score, filter=None):
+        """The number of documents scoring at least `min_score`, per query: int64 [B]."""
+        target, q = self._range_queries(q_embs, min_score, 0)
+        return self._to_api(target.count_matches(q, min_score, filter=filter))
+
+    def match_filter(self, q_embs, min_score, filter=None):
+        """The documents ``search_range`` matches, as a per-query DocFilter on the index's GPU: pass it to ``search(filter=)``, or combine it
+        with other filters through ``&``, ``|``, ``~``."""
+        target, q = self._range_queries(q_embs, min_score, 0)
+        return target.match_filter(q, min_score, filter=filter)
 
     # ---- diversified search (not in the reference: Maximal Marginal Relevance over the top hits, similarities from the stored rows) -------
     def _diverse_out(self, res) -> DiverseResults:

@@ -22,7 +22,7 @@ from torch import Tensor as T
 from ... import _native as nat
 from ..biencoder.biencoder import BiEncoder, BiEncoderConfig
 from ..utils import sparse as sp
-from .index import BoTIndex, DiverseResults, GroupedResults, Index, IndexType, SearchResults, SparseIndex
+from .index import BoTIndex, DiverseResults, GroupedResults, Index, IndexType, RangeResults, SearchResults, SparseIndex
 
 logger = logging.getLogger(__name__)
 
@@ -102,6 +102,25 @@ class Retriever(BiEncoder):
         a = a or self.encoder_q.config.topk
         q_emb = self.process_query(queries, dropout, a, batch_size=batch_size)
         return index.search_grouped(q_emb, k=k, per_group=per_group, filter=filter, depth=depth)
+
+    def retrieve_range(self, queries: Union[List[str], np.ndarray, T], min_score, max_hits: int = 100, dropout: float = 0, a: int = None,
+                       index: Index = None, batch_size: int = 32, filter=None, must=None, must_not=None, should=None,
+                       min_should: int = None) -> RangeResults:
+        """Every document scoring at least `min_score` per query, counted -- ``Index.search_range`` behind the query encoder: the exact
+        number of matches and the first `max_hits` of them in the canonical order.  `filter` and the term constraints as in ``retrieve``."""
+        index = index or self.index
+        if index is None:
+            raise RuntimeError("no index: call build_index / load_index first")
+        if must is not None or must_not is not None or should is not None or min_should is not None:
+            terms = self.term_filter(must=must, must_not=must_not, should=should, min_should=min_should, index=index)
+            if filter is not None:
+                from ...doc_filter import as_doc_filter
+                filter = as_doc_filter(filter, terms.n_rows, device=terms.device) & terms
+            else:
+                filter = terms
+        a = a or self.encoder_q.config.topk
+        q_emb = self.process_query(queries, dropout, a, batch_size=batch_size)
+        return index.search_range(q_emb, min_score, max_hits=max_hits, filter=filter)
 
     def retrieve_diverse(self, queries: Union[List[str], np.ndarray, T], k: int = 5, lam: float = 0.5, depth: int = None, sim: str = "cosine",
                          dropout: float = 0, a: int = None, index: Index = None, batch_size: int = 32, filter=None, must=None, must_not=None,
