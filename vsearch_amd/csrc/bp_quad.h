@@ -28,6 +28,12 @@
 #ifndef VS_QUAD_EPI
 #define VS_QUAD_EPI 2          // how the epilogue reads and zeroes a document's sums: 0 = 8 reads + 8 writes, 1 = 8 ds_wrxchg_rtn_b32, 2 = 4 ds_wrxchg2_rtn_b32
 #endif
+#ifndef VS_QUAD_HARVEST
+#define VS_QUAD_HARVEST 1      // the epilogue's rounds a block: 1 = ONE pass over a thread's two documents, one barrier and one cut decision a block, pushes without
+#endif                         // room stay pending in their thread (the walk, below); 2 = two rounds of 1024 documents, a cut decision behind each (two-field counters)
+#if VS_QUAD_HARVEST == 1 && VS_QUAD_EPI != 2
+#error "the one-pass harvest reads a thread's sixteen sums with ds_wrxchg2_rtn_b32 (VS_QUAD_EPI=2)"
+#endif
 
 namespace vs {
 
@@ -278,7 +284,7 @@ __global__ __launch_bounds__(kScanThreads) void bp_quad_topk(KArg<BpArgs, FL> a)
     unsigned long long* upper_sh = tau + QT;                                                // [QT]
     int* scratch = reinterpret_cast<int*>(upper_sh + QT);                                   // [48]
     unsigned int* ccnt = reinterpret_cast<unsigned int*>(scratch + 48);                     // [QT]
-    unsigned int* chi = ccnt + QT;                                                          // [QT] the counters' high halves at the end of the previous block (epilogue)
+    [[maybe_unused]] unsigned int* chi = ccnt + QT;                                         // [QT] two-round epilogue: the counters' high halves at the end of the previous block
     uint2* desc = reinterpret_cast<uint2*>(scratch + 64);                                   // [n_static + 64 * kQuadOverRead]
     const uint32_t desc_lds = (uint32_t)quad_fixed_lds();                                   // its LDS byte address
     uint32_t* cut_hist = reinterpret_cast<uint32_t*>(smem + quad_cut_lds());                // [kCutHistWords]
@@ -294,6 +300,11 @@ __global__ __launch_bounds__(kScanThreads) void bp_quad_topk(KArg<BpArgs, FL> a)
     // the wave's two link lists
     const uint32_t list_a = (uint32_t)kQuadAccBytes + (uint32_t)wv * 2u * kQuadListBytes, list_b = list_a + kQuadListBytes;
     const uint32_t g8 = (uint32_t)(lane >> 4) * 8u, s16 = (uint32_t)(lane & 15) * 16u;
+    // the epilogue's: LDS byte address of the sums of the thread's first document of a block (document tid; the accumulators start at 0),
+    // and how far behind it those of its second (document tid + 1024) lie
+    const uint32_t pa_doc = quad_acc_index((uint32_t)tid) * 4u;
+    constexpr uint32_t kSecondDoc = quad_acc_index((uint32_t)kScanThreads) * 4u;
+    static_assert(kScanThreads % 16 == 0, "document tid + 1024 is in the same place of its group of 16");
 
     // Cooperative prefetch (below, behind the walk's barrier): with ONE item per workgroup and a chunk count that divides the XCD count
     // (BpArgs::pf_xcds, set by the host only then) the workgroups of an XCD -- blockIdx.x % pf_xcds, the mapping bp_choose_chunks relies
@@ -349,7 +360,7 @@ __global__ __launch_bounds__(kScanThreads) void bp_quad_topk(KArg<BpArgs, FL> a)
             __syncthreads();
         }
         for (int i = tid; i < (int)(kQuadAccBytes / 4); i += kScanThreads) acc[i] = 0;
-        if (tid < QT) { tau[tid] = 0ull; ccnt[tid] = 0u; chi[tid] = 0u; }
+        if (tid < QT) { tau[tid] = tid < nq ? 0ull : ~0ull; ccnt[tid] = 0u; chi[tid] = 0u; }      // (a slot without a query: a threshold no sum reaches, the epilogue)
         if (tid < QT) upper_sh[tid] = (a.upper && tid < nq) ? a.upper[q0 + tid] : ~0ull;
         __syncthreads();
         const uint32_t trips = (uint32_t)(n_static / 64);
@@ -489,6 +500,149 @@ __global__ __launch_bounds__(kScanThreads) void bp_quad_topk(KArg<BpArgs, FL> a)
                 }
             }
             lap(2);
+#if VS_QUAD_HARVEST == 1
+            // epilogue, ONE pass a block: a thread harvests BOTH of its documents (tid and tid + 1024), their 2 x QT sums are tested, the few that
+            // reach a threshold become order keys -> candidates; then one barrier and one cut decision of the workgroup.
+            // (LDS instructions and vector issue are what the epilogue costs -- 16 waves a block, a vector instruction ~ 16 cycles of the
+            //  workgroup (4 waves a SIMD, 4 cycles each): the 8 threshold halves in four ds_read2_b32, a thread's 16 sums read AND zeroed by
+            //  eight ds_wrxchg2_rtn_b32 behind ONE wait, 16 compares folded into one wave-uniform branch -- a block-tile holds ~ 1.6 candidates
+            //  among its 16 384 sums in steady state, so 15 waves in 16 take nothing but that branch --, the 8 counters in two 16-byte reads)
+            {
+                // ONE LDS statement: the thresholds' score halves (the odd dwords of tau[], two a read) and the thread's 16 sums, read AND zeroed,
+                // behind one wait.  (documents at and beyond rows_b of a short block are harvested too: their accumulators exist and hold 0 -- a
+                // null posting adds 0 to one of the first 32 -- and the exchange leaves 0 there; `allow` below keeps them out of the candidates)
+                int32_t thr[QT], sums[2][QT];
+                {
+                    const uint32_t pa1 = pa_doc + kSecondDoc, zero = 0u, tau_lds = (uint32_t)(kQuadAccBytes + (size_t)kBpCap * 8);
+                    unsigned long long t0, t1, t2, t3, s0, s1, s2, s3, s4, s5, s6, s7;
+                    asm volatile("ds_read2_b32 %0, %12 offset0:1 offset1:3\n\tds_read2_b32 %1, %12 offset0:5 offset1:7\n\t"
+                                 "ds_read2_b32 %2, %12 offset0:9 offset1:11\n\tds_read2_b32 %3, %12 offset0:13 offset1:15\n\t"
+                                 "ds_wrxchg2_rtn_b32 %4, %13, %15, %15 offset0:0 offset1:16\n\tds_wrxchg2_rtn_b32 %5, %13, %15, %15 offset0:32 offset1:48\n\t"
+                                 "ds_wrxchg2_rtn_b32 %6, %13, %15, %15 offset0:64 offset1:80\n\tds_wrxchg2_rtn_b32 %7, %13, %15, %15 offset0:96 offset1:112\n\t"
+                                 "ds_wrxchg2_rtn_b32 %8, %14, %15, %15 offset0:0 offset1:16\n\tds_wrxchg2_rtn_b32 %9, %14, %15, %15 offset0:32 offset1:48\n\t"
+                                 "ds_wrxchg2_rtn_b32 %10, %14, %15, %15 offset0:64 offset1:80\n\tds_wrxchg2_rtn_b32 %11, %14, %15, %15 offset0:96 offset1:112\n\ts_waitcnt lgkmcnt(0)"
+                                 : "=&v"(t0), "=&v"(t1), "=&v"(t2), "=&v"(t3), "=&v"(s0), "=&v"(s1), "=&v"(s2), "=&v"(s3), "=&v"(s4), "=&v"(s5), "=&v"(s6), "=&v"(s7)
+                                 : "v"(tau_lds), "v"(pa_doc), "v"(pa1), "v"(zero) : "memory");
+                    const unsigned long long tv[QT / 2] = {t0, t1, t2, t3}, sv[2][QT / 2] = {{s0, s1, s2, s3}, {s4, s5, s6, s7}};
+#pragma unroll
+                    for (int i = 0; i < QT / 2; ++i) {
+                        // as SIGNED numbers a sum compares with directly (a slot without a query has tau = ~0: 0x7FFFFFFF, no sum reaches it)
+                        thr[2 * i] = (int32_t)((uint32_t)tv[i] ^ 0x80000000u);
+                        thr[2 * i + 1] = (int32_t)((uint32_t)(tv[i] >> 32) ^ 0x80000000u);
+#pragma unroll
+                        for (int r = 0; r < 2; ++r) { sums[r][2 * i] = (int32_t)(uint32_t)sv[r][i]; sums[r][2 * i + 1] = (int32_t)(uint32_t)(sv[r][i] >> 32); }
+                    }
+                }
+                // ONE test a wave: does any of its 64 x 16 sums reach its slot's threshold?  (the compares' lane masks are OR-ed by the scalar unit)
+                bool hit = false;
+#pragma unroll
+                for (int r = 0; r < 2; ++r)
+#pragma unroll
+                    for (int q = 0; q < QT; ++q) hit = hit | (sums[r][q] >= thr[q]);
+                // pend: bit r * QT + q = the sum of document tid + r * 1024 for slot q is a candidate that is not in the buffer yet
+                uint32_t pend = 0u;
+                if (__builtin_amdgcn_ballot_w64(hit) != 0ull) {
+                    // which (document, slot) pairs may be pushed at all: the filter's bits (rows_b is in them), or the documents the block has
+                    uint32_t allow;
+                    if constexpr (FL != 0) allow = fbits;
+                    else allow = (tid < rows_b ? 0xFFu : 0u) | (tid + kScanThreads < rows_b ? 0xFF00u : 0u);
+                    // (from the top bit down, a shift and an OR each: no bit's mask is a constant that has to wait in a register)
+#pragma unroll
+                    for (int i = 2 * QT - 1; i >= 0; --i) pend = (pend << 1) | (uint32_t)(sums[i / QT][i % QT] >= thr[i % QT]);
+                    pend &= allow;
+                }
+                const bool last = b + 1 >= b1;
+                // Pushes, the block's barrier, the cut decision -- again while a push found no room.  A slot's buffer holds kBpCap keys and a block
+                // may bring 2048 more (a work item's first blocks, where nearly every document passes): a push whose place is at or beyond kBpCap
+                // is NOT stored -- its bit stays up in `pend`, the sums stay in the thread's registers -- and the counter it raised, standing above
+                // kBpCap, is the slot's flag that somebody waits.  The cut below lowers such a slot to K <= kBpCap - 1024 keys and raises its
+                // threshold, the pending sums are tested against that and pushed again: every turn accepts at least kBpCap - K >= 1024 keys a slot
+                // of at most 2048, so the loop ends after three turns at the most; in steady state it is left at its first `break`.
+                for (;;) {
+                    if (__builtin_amdgcn_ballot_w64(pend != 0u) != 0ull) {
+                        // (the empty statements: what follows them is computed HERE, under the branch -- the loop's invariants otherwise move in
+                        //  front of it, 16 keys built a block for nothing)
+                        uint32_t row_lo = (uint32_t)tid;
+                        asm volatile("" : "+v"(row_lo));
+                        row_lo = ~((uint32_t)(b * a.rows) + row_lo);                     // (a key's low half: ~row; ~(row + 1024) = ~row - 1024)
+#pragma unroll
+                        for (int r = 0; r < 2; ++r)
+#pragma unroll
+                            for (int q = 0; q < QT; ++q) {
+                                const uint32_t bit = 1u << (r * QT + q);
+                                if (pend & bit) {
+                                    uint32_t hi = (uint32_t)sums[r][q];
+                                    asm volatile("" : "+v"(hi));
+                                    const uint64_t key = ((uint64_t)(hi ^ 0x80000000u) << 32) | (uint32_t)(row_lo - (uint32_t)(r * kScanThreads));
+                                    bool keep = false;
+                                    if (key > tau[q] && key < upper_sh[q]) {
+                                        const uint32_t old = atomicAdd(&ccnt[q], 1u);
+                                        if (old < (uint32_t)kBpCap) my_gcand[(size_t)q * kBpCap + old] = key;
+                                        else keep = true;                    // no room: again behind the cut
+                                    }
+                                    if (!keep) pend &= ~bit;
+                                }
+                            }
+                    }
+                    // Whether a buffer has to be cut is ONE decision of the workgroup (barriers sit behind it), read by every thread from the
+                    // counters behind this barrier -- so what a thread reads there must not depend on WHEN it reads.  It does not: every push
+                    // of this turn is in front of the barrier, and the next write to a counter is either a cut's (thread 0, behind the
+                    // __syncthreads() below, which no wave passes before every wave has read) or the next turn's or block's pushes -- behind
+                    // that same __syncthreads() and the cut's own, or, when nothing is cut, behind the NEXT walk's barrier, which no wave
+                    // passes before every wave has read either.  One counter field a slot is therefore enough.
+                    // (Until round 6 a round's counters were read while waves already in the block's second round pushed: with a counter
+                    //  exactly at the limit the late reader went into the cut's barriers alone -- whole blocks of candidates lost once other
+                    //  processes' waves on the CU stretched the window.  docs/EXPERIMENTS.md round 6, profiles/r06_prune_decision_race.txt.)
+                    lds_barrier();                                          // (the counters and sums are LDS; candidates other threads stored are read only when a cut follows)
+                    // (VS_BP_KNOB = 128 + 4096 n, tests: one wave reads the counters n x 512 cycles late -- the others are in the next block's walk
+                    //  by then, or wait in the cut's barrier.  A SCALAR branch: s_sleep does not care about exec -- behind a vector condition every wave slept)
+                    if ((a.knob & 128) && __builtin_amdgcn_readfirstlane(wv) == 5)
+                        for (int i = 0; i < (a.knob >> 12); ++i) __builtin_amdgcn_s_sleep(8);
+                    uint32_t cmax;
+                    {
+                        const uint4* c4 = reinterpret_cast<const uint4*>(ccnt);
+                        const uint4 c0 = c4[0], c1 = c4[1];
+                        cmax = max(max(max(c0.x, c0.y), max(c0.z, c0.w)), max(max(c1.x, c1.y), max(c1.z, c1.w)));
+                    }
+                    const bool over = cmax > (uint32_t)kBpCap;                  // a push is pending somewhere in the workgroup
+                    if (!(last || cmax > (uint32_t)(kBpCap - kScanThreads))) break;
+                    [[maybe_unused]] long long t_cut = 0;
+                    if constexpr (TM != 0) t_cut = (long long)__builtin_readcyclecounter();
+                    __syncthreads();                                        // the candidates stored above become visible to the workgroup
+                    for (int qs = 0; qs < nq; ++qs) {
+                        // (a slot's count as the decision above took it: nobody has written a counter since, but a cut of an earlier slot its own)
+                        const uint32_t cw = ccnt[qs], cnt = min(cw, (uint32_t)kBpCap);          // (the keys in the buffer: the pushes beyond it are pending)
+                        if (last || cw > (uint32_t)(kBpCap - kScanThreads)) {
+                            for (int i = tid; i < kBpCap; i += kScanThreads) sortbuf[i] = (uint32_t)i < cnt ? my_gcand[(size_t)qs * kBpCap + i] : 0ull;
+                            if (last && !over) {
+                                // the item's result: its K best, sorted.  K <= 256 (k = 100: 128): cut to K by radix select, then ONE wave sorts
+                                // them in registers (no barrier stages); else the workgroup's bitonic sort of the whole buffer
+                                uint64_t* out = a.cand + ((size_t)(q0 + qs) * a.nchunk + c) * (size_t)K;
+                                if (K <= 256) {
+                                    wg_final_topk256<kScanThreads>(sortbuf, cnt, K, my_gcand + (size_t)qs * kBpCap, out, cut_hist, tid);
+                                } else {
+                                    wg_sort_desc<kScanThreads>(sortbuf, kBpCap, tid);
+                                    for (int i = tid; i < K; i += kScanThreads) out[i] = sortbuf[i];
+                                }
+                            } else if (cnt > (uint32_t)K) {
+                                // (a cut needs the K best as a SET and the K-th key, not an order: radix select instead of the 66-stage sort)
+                                const unsigned long long kth_sel = wg_cut_topk<kScanThreads>(sortbuf, K, my_gcand + (size_t)qs * kBpCap, cut_hist, tid);
+                                if (tid == 0) {
+                                    const unsigned long long kth = kth_sel;
+                                    if (kth > tau[qs]) tau[qs] = kth;
+                                    if (a.gtau && kth != 0ull) atomicMax(a.gtau + q0 + qs, kth);
+                                    ccnt[qs] = (uint32_t)K;
+                                }
+                            }
+                            // (else: the last block's turn with a pending push in ANOTHER slot and no more than K keys here -- the counter is the count, nothing to do)
+                            __syncthreads();
+                        }
+                    }
+                    if constexpr (TM != 0) tacc[3] += (uint32_t)((long long)__builtin_readcyclecounter() - t_cut);      // (phase clocks: "dense" = inside the cuts)
+                    if (!over) break;
+                }
+            }
+#else
             // epilogue: 1024 documents at a time, one per thread: its QT sums -> order keys -> candidates; prune when a buffer could overflow
             int32_t thr[QT];
             bool thr_stale = true;
@@ -514,14 +668,14 @@ __global__ __launch_bounds__(kScanThreads) void bp_quad_topk(KArg<BpArgs, FL> a)
                     const int64_t row = b * a.rows + d;
                     int32_t sums[QT];
 #if VS_QUAD_EPI == 0
-                    int32_t* pa = acc + quad_acc_index((uint32_t)d);
+                    int32_t* pa = acc + (pa_doc + (d0 ? kSecondDoc : 0u)) / 4u;
 #pragma unroll
                     for (int q = 0; q < QT; ++q) sums[q] = pa[q * 16];
 #pragma unroll
                     for (int q = 0; q < QT; ++q) pa[q * 16] = 0;
 #elif VS_QUAD_EPI == 1
                     {
-                        const uint32_t pa = quad_acc_index((uint32_t)d) * 4u, zero = 0u;      // LDS byte address (the accumulators start at 0)
+                        const uint32_t pa = pa_doc + (d0 ? kSecondDoc : 0u), zero = 0u;      // LDS byte address (the accumulators start at 0)
                         asm volatile("ds_wrxchg_rtn_b32 %0, %8, %9\n\tds_wrxchg_rtn_b32 %1, %8, %9 offset:64\n\tds_wrxchg_rtn_b32 %2, %8, %9 offset:128\n\t"
                                      "ds_wrxchg_rtn_b32 %3, %8, %9 offset:192\n\tds_wrxchg_rtn_b32 %4, %8, %9 offset:256\n\tds_wrxchg_rtn_b32 %5, %8, %9 offset:320\n\t"
                                      "ds_wrxchg_rtn_b32 %6, %8, %9 offset:384\n\tds_wrxchg_rtn_b32 %7, %8, %9 offset:448\n\ts_waitcnt lgkmcnt(0)"
@@ -530,7 +684,7 @@ __global__ __launch_bounds__(kScanThreads) void bp_quad_topk(KArg<BpArgs, FL> a)
                     }
 #else
                     {
-                        const uint32_t pa = quad_acc_index((uint32_t)d) * 4u, zero = 0u;
+                        const uint32_t pa = pa_doc + (d0 ? kSecondDoc : 0u), zero = 0u;
                         unsigned long long s01, s23, s45, s67;
                         asm volatile("ds_wrxchg2_rtn_b32 %0, %4, %5, %5 offset0:0 offset1:16\n\tds_wrxchg2_rtn_b32 %1, %4, %5, %5 offset0:32 offset1:48\n\t"
                                      "ds_wrxchg2_rtn_b32 %2, %4, %5, %5 offset0:64 offset1:80\n\tds_wrxchg2_rtn_b32 %3, %4, %5, %5 offset0:96 offset1:112\n\ts_waitcnt lgkmcnt(0)"
@@ -539,16 +693,25 @@ __global__ __launch_bounds__(kScanThreads) void bp_quad_topk(KArg<BpArgs, FL> a)
                         sums[4] = (int32_t)(uint32_t)s45; sums[5] = (int32_t)(uint32_t)(s45 >> 32); sums[6] = (int32_t)(uint32_t)s67; sums[7] = (int32_t)(uint32_t)(s67 >> 32);
                     }
 #endif
+                    // ONE test a wave first: does any of its 64 x 8 sums reach its slot's threshold?  (the compares' lane masks are OR-ed by the
+                    // scalar unit; 699 rounds in 700 end here)
+                    bool hit = false;
+#pragma unroll
+                    for (int q = 0; q < QT; ++q) hit = hit | (sums[q] >= thr[q]);
+                    if (__builtin_amdgcn_ballot_w64(hit) != 0ull) {
+                    [[maybe_unused]] const uint32_t fb = d0 ? fbits >> QT : fbits;
+                    const uint32_t row_lo = ~(uint32_t)row;
 #pragma unroll
                     for (int q = 0; q < QT; ++q) {
-                        if (sums[q] >= thr[q] && (FL == 0 || ((fbits >> ((d0 >= kScanThreads ? QT : 0) + q)) & 1u) != 0u)) {
+                        if (sums[q] >= thr[q] && (FL == 0 || ((fb >> q) & 1u) != 0u)) {
                             const uint32_t hi = (uint32_t)sums[q] ^ 0x80000000u;
-                            const uint64_t key = ((uint64_t)hi << 32) | (uint32_t)(~(uint32_t)row);
+                            const uint64_t key = ((uint64_t)hi << 32) | row_lo;
                             if (key > tau[q] && key < upper_sh[q]) {
                                 const uint32_t old = atomicAdd(&ccnt[q], inc);                 // (low half: first rounds, high half: last rounds -- below)
                                 my_gcand[(size_t)q * kBpCap + (old & 0xFFFFu) + (old >> 16)] = key;
                             }
                         }
+                    }
                     }
                 }
                 // Whether a buffer has to be cut is ONE decision of the workgroup (barriers sit behind it), read by every thread from the
@@ -627,6 +790,7 @@ __global__ __launch_bounds__(kScanThreads) void bp_quad_topk(KArg<BpArgs, FL> a)
                 }
                 if constexpr (TM != 0) { if (any) tacc[3] += (uint32_t)((long long)__builtin_readcyclecounter() - t_cut); }      // (phase clocks: "dense" = inside the cuts)
             }
+#endif
             asm volatile("s_waitcnt vmcnt(0)" : "+v"(pf) : : "memory");   // (the prefetch above has landed -- long ago)
             lap(4);
             if constexpr (TM != 0) tacc[5] += 1u;
