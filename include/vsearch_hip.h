@@ -221,6 +221,48 @@ VS_API int vs_index_search_range(vs_index* index, const void* q, int q_dtype, in
  * scan was cut into and the rows of a chunk -- the last chunk holds the rest.  0 / 0 before the first range search; 1 chunk on a dense index. */
 VS_API int vs_index_last_range_plan(const vs_index* index, int32_t* out_chunks, int64_t* out_rows_per_chunk);
 
+/* ---- facet counts: how a document set spreads over per-row integer labels (no reference counterpart: the reference only has topk) ----------
+ * The set of query b is a bitmap in the layout of vs_index_search_filtered: bit bit0 + r of the bitmap at words + b * ld_words stands for row
+ * r (ld_words = 0: one bitmap for all queries, and then B must be 1; else ld_words >= the (bit0 + n_rows + 31) / 32 words a bitmap spans).
+ * words == NULL: every row is set (B must be 1).  and_words (may be NULL): a second bitmap shared by all queries, at the same bit0.  Row r is
+ * IN for query b iff its bit is set in words and in and_words; bits at or past bit0 + n_rows are ignored, whatever they hold.
+ *   labels [n_rows] int32, n_labels >= 1.  total [b] = rows in; counts [b, l] = rows in with labels[r] == l, 0 <= l < n_labels; other [b] =
+ *   rows in whose label is outside [0, n_labels) (-1 = "no label", anything too large): no label value causes an out-of-range access, and
+ *   sum over l of counts [b, l] + other [b] == total [b] always.  counts [B, ld_counts] (ld_counts >= n_labels; elements [b, 0 .. n_labels)
+ *   are written), total [B], other [B]: int64, every element written.  n_rows in 1 .. 2^32 - 1 (a count fits 32 bits).
+ * A workgroup owns a chunk of rows and a tile of qt queries; it reads the bitmap words coalesced, skips all-zero spans without touching the
+ * labels and loads a row's label once for the tile.  Two regimes (vs_facet_plan): qt x n_labels <= VS_FACET_LDS_BINS -- one uint32 histogram
+ * per query of the tile in LDS, non-zero bins added to counts at the end of the chunk (qt the largest of 8, 4, 2, 1 that fits; 1 for a
+ * shared bitmap); n_labels > VS_FACET_LDS_BINS -- 64-bit atomic adds straight into counts (qt = 8, or 1 for a shared bitmap).
+ * vs_facet_plan: the launch of vs_facet_counts for these arguments -- pure host arithmetic, no device needed.  regime 0 = LDS, 1 = global;
+ *   chunks x rows_per_chunk >= n_rows > (chunks - 1) x rows_per_chunk.  rows_per_chunk = 0: automatic; any other value must be a positive
+ *   multiple of 64 and is taken as given (a tuning knob; the result does not depend on it).  vs_facet_counts / vs_index_facet_counts take the
+ *   same argument and launch exactly this plan.
+ * vs_index_facet_counts: vs_facet_counts over the index's rows with its tombstones as and_words: deleted rows never count.  words == NULL: the
+ *   label distribution of the live index.
+ * vs_facet_topn: per query the n labels with the largest counts [B, ld_counts] -- count descending, then label ascending; only labels with
+ *   count >= max(min_count, 1); unused slots hold label -1 / count 0, every slot of out_labels int32 [B, n] / out_counts int64 [B, n] is
+ *   written.  n in 1..VS_FACET_MAX_TOPN, n > n_labels is allowed; counts are below 2^32 (what vs_facet_counts writes).  One workgroup per query.
+ * Errors: NULL labels or outputs, n_labels < 1, n out of range, rows_per_chunk no multiple of 64, B > 1 with ld_words = 0, ld_words too short:
+ * VS_EINVAL -- checked before the device is touched (without a GPU a bad argument is VS_EINVAL, a good one VS_ENODEVICE).  Pointers: all
+ * host (staged; the call blocks), or all device pointers on `device` / the index's device (VS_EINVAL for a mix); device pointers and a
+ * non-NULL stream only enqueue.
+ * Not covered: no index file stores labels, and a shard group has no entry point of its own (every shard counts its rows with its slice of
+ * the labels and its bit range of the bitmap; the counts are summed, and the top-n taken after the sum); the one-process-per-GPU RCCL path
+ * has none.                                                                                                                              */
+#define VS_FACET_LDS_BINS 16384      /* uint32 bins of a workgroup's LDS histograms (64 KiB: two workgroups a CU) */
+#define VS_FACET_MAX_TOPN 1024       /* labels vs_facet_topn lists per query at most */
+VS_API int vs_facet_plan(int64_t n_rows, int32_t B, int32_t n_labels, int per_query, int64_t rows_per_chunk, int32_t* out_regime,
+                         int32_t* out_qt, int64_t* out_chunks, int64_t* out_rows_per_chunk);
+VS_API int vs_facet_counts(const uint32_t* words, int64_t bit0, int64_t ld_words, const uint32_t* and_words, int32_t B, const int32_t* labels,
+                           int64_t n_rows, int32_t n_labels, int64_t rows_per_chunk, int64_t* counts, int64_t ld_counts, int64_t* total,
+                           int64_t* other, int device, void* stream);
+VS_API int vs_index_facet_counts(vs_index* index, const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B, const int32_t* labels,
+                                 int32_t n_labels, int64_t rows_per_chunk, int64_t* counts, int64_t ld_counts, int64_t* total, int64_t* other,
+                                 void* stream);
+VS_API int vs_facet_topn(const int64_t* counts, int64_t ld_counts, int32_t B, int32_t n_labels, int32_t n, int64_t min_count,
+                         int32_t* out_labels, int64_t* out_counts, int device, void* stream);
+
 /* bool / uint8 mask [B, n] (row stride ld_mask bytes; non-zero = allowed) -> the bitmap words [B, ld_words] vs_index_search_filtered
  * reads (bits past n of a row's last word are 0).  mask and words: host pointers or device pointers on `device` (VS_EINVAL otherwise).  stream as in
  * vs_index_search (host buffers block).                                                                                          */

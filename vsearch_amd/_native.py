@@ -23,6 +23,8 @@ TERM_FILTER_SLOTS, TERM_FILTER_TERMS, TERM_FILTER_LIST = 255, 4096, 64
 MMR_COSINE, MMR_DOT, MMR_MAX_DEPTH, MMR_MAX_COLS = 0, 1, 1024, 32768
 # range search (VS_RANGE_MAX_HITS): the most hits vs_index_search_range lists per query
 RANGE_MAX_HITS = 2048
+# facet counts (VS_FACET_LDS_BINS, VS_FACET_MAX_TOPN): uint32 bins of a workgroup's LDS histograms, the most labels vs_facet_topn lists
+FACET_LDS_BINS, FACET_MAX_TOPN = 16384, 1024
 
 
 class VsearchNativeError(RuntimeError):
@@ -59,6 +61,10 @@ _SIGNATURES = {
     "vs_index_search_filtered": ([_vp, _vp, _int, _i64, _i32, _i32, _vp, _i64, _i64, _i64, _vp, _vp, _vp], _int),
     "vs_index_search_range": ([_vp, _vp, _int, _i64, _i32, _vp, _i32, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp], _int),
     "vs_index_last_range_plan": ([_vp, C.POINTER(_i32), C.POINTER(_i64)], _int),
+    "vs_facet_plan": ([_i64, _i32, _i32, _int, _i64, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i64)], _int),
+    "vs_facet_counts": ([_vp, _i64, _i64, _vp, _i32, _vp, _i64, _i32, _i64, _vp, _i64, _vp, _vp, _int, _vp], _int),
+    "vs_index_facet_counts": ([_vp, _vp, _i64, _i64, _i32, _vp, _i32, _i64, _vp, _i64, _vp, _vp, _vp], _int),
+    "vs_facet_topn": ([_vp, _i64, _i32, _i32, _i32, _i64, _vp, _vp, _int, _vp], _int),
     "vs_filter_pack": ([_vp, _i32, _i64, _i64, _vp, _i64, _int, _vp], _int),
     "vs_index_scores": ([_vp, _vp, _int, _i64, _i32, _vp, _vp], _int),
     "vs_index_explain": ([_vp, _vp, _int, _i64, _i32, _vp, _i64, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp], _int),

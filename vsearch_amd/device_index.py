@@ -597,6 +597,100 @@ def _range_out(q, *tensors):
     return tuple(t.cpu().numpy() for t in tensors)
 
 
+# ---- facet counts: how a document set spreads over per-row labels (vs_facet_counts, vs_index_facet_counts, vs_facet_topn) ----------------
+class FacetCounts(NamedTuple):
+    """facet_counts: per query the documents of the set per label (counts [B, n_labels]), the size of the set (total [B]) and its documents
+    whose label is outside [0, n_labels) -- -1 = "no label" -- (other [B]); counts.sum(1) + other == total.  All int64."""
+    counts: Any
+    total: Any
+    other: Any
+
+
+class TopFacets(NamedTuple):
+    """top_facets: per query the `topn` labels with the most documents of the set, count descending then label ascending (labels int32
+    [B, topn], counts int64 [B, topn]; unused slots label -1 / count 0), with the set's total and other as in FacetCounts."""
+    labels: Any
+    counts: Any
+    total: Any
+    other: Any
+
+
+MAX_FACET_TOPN = nat.FACET_MAX_TOPN
+
+
+def facet_plan(n_rows: int, B: int, n_labels: int, per_query: bool, rows_per_chunk: int = 0):
+    """The launch vs_facet_counts takes for these arguments (vs_facet_plan; pure host arithmetic, no GPU needed) -> (regime, qt, chunks,
+    rows_per_chunk): regime 0 = LDS histograms, 1 = global atomics; qt = queries a workgroup serves."""
+    regime, qt, chunks, rpc = C.c_int32(0), C.c_int32(0), C.c_int64(0), C.c_int64(0)
+    nat.check(nat.lib().vs_facet_plan(int(n_rows), int(B), int(n_labels), 1 if per_query else 0, int(rows_per_chunk), C.byref(regime), C.byref(qt),
+                                      C.byref(chunks), C.byref(rpc)))
+    return regime.value, qt.value, chunks.value, rpc.value
+
+
+def _facet_args(labels, n_labels, n_rows, rows_per_chunk=0):
+    """Argument checks of a facet count that need no device -> (n_labels, rows_per_chunk)"""
+    for name, v in (("n_labels", n_labels), ("rows_per_chunk", rows_per_chunk)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise TypeError(f"{name} must be an int, got {type(v).__name__}")
+    n_labels, rows_per_chunk = int(n_labels), int(rows_per_chunk)
+    if not 1 <= n_labels <= 0x7FFFFFFF:
+        raise ValueError(f"n_labels must be in 1..2^31 - 1, got {n_labels}")
+    if rows_per_chunk < 0 or rows_per_chunk % 64:
+        raise ValueError(f"rows_per_chunk must be 0 (automatic) or a positive multiple of 64, got {rows_per_chunk}")
+    if not hasattr(labels, "shape") or labels.ndim != 1 or int(labels.shape[0]) != int(n_rows):
+        raise ValueError(f"labels must hold one entry per row ({int(n_rows)}), got shape {tuple(getattr(labels, 'shape', ()))}")
+    dt = str(labels.dtype)
+    if "float" in dt or "bool" in dt or "complex" in dt:
+        raise TypeError(f"labels must be integer codes, got {labels.dtype}")
+    return n_labels, rows_per_chunk
+
+
+def _topn_args(topn, min_count):
+    for name, v in (("topn", topn), ("min_count", min_count)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise TypeError(f"{name} must be an int, got {type(v).__name__}")
+    if not 1 <= int(topn) <= MAX_FACET_TOPN:
+        raise ValueError(f"topn must be in 1..{MAX_FACET_TOPN}, got {int(topn)}")
+    return int(topn), int(min_count)
+
+
+def _labels_on(labels, device: int):
+    """labels (numpy / torch, any integer dtype) -> contiguous int32 tensor on GPU `device` (the tensor itself when it is one already)"""
+    import torch
+    t = labels if _is_torch(labels) else torch.from_numpy(np.ascontiguousarray(labels))
+    if t.dtype != torch.int32:
+        t = t.clamp(-1, 0x7FFFFFFF).to(torch.int32)              # (anything negative is "no label"; too large stays outside n_labels)
+    return t.to(torch.device("cuda", device)).contiguous()
+
+
+def facet_topn(counts, topn: int, min_count: int = 1, device: int = 0):
+    """Per query the `topn` labels with the largest counts [B, n_labels] (vs_facet_topn) -> (labels int32 [B, topn], counts int64 [B, topn]):
+    count descending, then label ascending; only labels with count >= max(min_count, 1); unused slots label -1 / count 0.  numpy in ->
+    numpy out; torch CUDA in -> tensors on `device`, enqueued on torch's current stream."""
+    topn, min_count = _topn_args(topn, min_count)
+    if not hasattr(counts, "shape") or counts.ndim != 2:
+        raise ValueError("counts must be [B, n_labels]")
+    B, L = int(counts.shape[0]), int(counts.shape[1])
+    nat.require_device()
+    if _is_torch(counts) and counts.is_cuda:
+        import torch
+        c = counts.to(torch.int64).contiguous()
+        labels = torch.empty((B, topn), dtype=torch.int32, device=c.device)
+        out = torch.empty((B, topn), dtype=torch.int64, device=c.device)
+        nat.check(nat.lib().vs_facet_topn(_ptr(c), L, B, L, topn, min_count, _ptr(labels), _ptr(out), int(device), current_stream(int(device))))
+        return labels, out
+    c = np.ascontiguousarray(_host(counts), dtype=np.int64)
+    labels = np.empty((B, topn), dtype=np.int32)
+    out = np.empty((B, topn), dtype=np.int64)
+    nat.check(nat.lib().vs_facet_topn(_ptr(c), L, B, L, topn, min_count, _ptr(labels), _ptr(out), int(device), None))
+    return labels, out
+
+
+def _facet_out(labels, *tensors):
+    """results in the kind of the labels: torch in -> CUDA tensors as they are, numpy in -> ndarrays"""
+    return tensors if _is_torch(labels) else tuple(t.cpu().numpy() for t in tensors)
+
+
 def _host(x):
     return x.detach().numpy() if _is_torch(x) else x
 
@@ -1234,6 +1328,48 @@ class DeviceIndex:
         words = self._range(qd, min_score, 0, filter, 0, True)[3]
         return DocFilter(words, int(self.info().n_rows))
 
+    # ---- facet counts: how a document set spreads over per-row labels (vs_index_facet_counts) ---------------------------------------------
+    def _facet_call(self, labels_dev, n_labels, f, bit0, rows_per_chunk):
+        """One vs_index_facet_counts call on device buffers and torch's current stream -> (counts [B, L], total [B], other [B]) int64 CUDA
+        tensors.  labels_dev: int32 CUDA tensor [n_rows] on this index's device; f: None or a DocFilter there, read from bit `bit0` on."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        B = f.n_queries if (f is not None and f.per_query) else 1
+        counts = torch.empty((B, n_labels), dtype=torch.int64, device=dev)
+        total = torch.empty(B, dtype=torch.int64, device=dev)
+        other = torch.empty(B, dtype=torch.int64, device=dev)
+        nat.check(nat.lib().vs_index_facet_counts(self._h, _ptr(f.words) if f is not None else None, int(bit0), f.ld if f is not None else 0, B,
+                                                  _ptr(labels_dev), n_labels, rows_per_chunk, _ptr(counts), n_labels, _ptr(total), _ptr(other),
+                                                  current_stream(self.device)))
+        return counts, total, other
+
+    def _facets(self, labels, n_labels, filter, rows_per_chunk):
+        n = self.n_rows
+        n_labels, rows_per_chunk = _facet_args(labels, n_labels, n, rows_per_chunk)
+        nat.require_device()
+        f = None
+        if filter is not None:
+            from .doc_filter import as_doc_filter
+            f = as_doc_filter(filter, n, device=self.device)
+        return self._facet_call(_labels_on(labels, self.device), n_labels, f, 0, rows_per_chunk)
+
+    def facet_counts(self, labels, n_labels: int, filter=None, rows_per_chunk: int = 0) -> FacetCounts:
+        """How a document set spreads over per-document labels -> FacetCounts(counts [B, n_labels], total [B], other [B]), int64.  labels:
+        integer codes [n_rows] (numpy, or a tensor -- an int32 tensor on the index's GPU is read in place); a label outside [0, n_labels),
+        -1 = "no label" included, counts into `other`.  filter: what search(filter=) accepts -- a per-query DocFilter (match_filter's result)
+        gives one row per query, a shared one B = 1, None every live document.  Deleted documents never count.  rows_per_chunk: 0 =
+        automatic, else a multiple of 64 (a tuning knob: the result does not depend on it).  numpy labels -> numpy out; tensor labels ->
+        tensors on the index's device, enqueued on torch's current stream."""
+        return FacetCounts(*_facet_out(labels, *self._facets(labels, n_labels, filter, rows_per_chunk)))
+
+    def top_facets(self, labels, n_labels: int, topn: int, filter=None, min_count: int = 1) -> TopFacets:
+        """facet_counts, then per query the `topn` labels with the most documents (vs_facet_topn): count descending, label ascending, only
+        labels with at least max(min_count, 1) documents; unused slots label -1 / count 0.  topn in 1..1024."""
+        topn, min_count = _topn_args(topn, min_count)
+        counts, total, other = self._facets(labels, n_labels, filter, 0)
+        top_l, top_c = facet_topn(counts, topn, min_count, device=self.device)
+        return TopFacets(*_facet_out(labels, top_l, top_c, total, other))
+
     def scores(self, q):
         """Dense [B, n_rows] fp32 score matrix (what index.py:91 materialises). numpy out."""
         info = self.info()
@@ -1460,6 +1596,53 @@ class ShardGroup:
         """DeviceIndex.match_filter over the group's rows: the shards' bitmaps at their bit offsets, on the first shard's GPU."""
         from .doc_filter import DocFilter
         return DocFilter(_range_shards(self, q, min_score, 0, filter, True)[3], self.n_rows)
+
+    # ---- facet counts -----------------------------------------------------------------------------------------------------------------------
+    def _facet_slices(self, labels):
+        """every shard's slice of the labels as an int32 tensor on its GPU, cached per label tensor (and its version: an in-place edit drops it)"""
+        key = (id(labels), getattr(labels, "_version", None), tuple(labels.shape))
+        cached = getattr(self, "_facet_cache", None)
+        if cached is not None and cached[0] == key and cached[1] is labels:
+            return cached[2]
+        slices, row0 = [], 0
+        for sh in self._shards:
+            n = sh.n_rows
+            slices.append(_labels_on(labels[row0:row0 + n], sh.device))
+            row0 += n
+        if _is_torch(labels):                                    # (a numpy array has no version to tell an in-place edit by)
+            self._facet_cache = (key, labels, slices)
+        return slices
+
+    def _facets(self, labels, n_labels, filter, rows_per_chunk):
+        import torch
+        n_total = self.n_rows
+        n_labels, rows_per_chunk = _facet_args(labels, n_labels, n_total, rows_per_chunk)
+        nat.require_device()
+        dev0 = torch.device("cuda", self.device)
+        f = None
+        if filter is not None:
+            from .doc_filter import as_doc_filter
+            f = as_doc_filter(filter, n_total, device=dev0)
+        out, row0 = None, 0
+        for sh, lab in zip(self._shards, self._facet_slices(labels)):
+            fs = f.to(torch.device("cuda", sh.device)) if f is not None else None
+            part = sh._facet_call(lab, n_labels, fs, row0, rows_per_chunk)          # its rows are bits [row0, row0 + n) of the filter
+            part = tuple(t.to(dev0) for t in part)
+            out = part if out is None else tuple(a + b for a, b in zip(out, part))
+            row0 += sh.n_rows
+        return out
+
+    def facet_counts(self, labels, n_labels: int, filter=None, rows_per_chunk: int = 0) -> FacetCounts:
+        """DeviceIndex.facet_counts over the group's rows: labels and filter are global; every shard counts its own rows with its slice of
+        the labels on its own GPU, the counts are summed on the first shard's GPU.  Equal to the unsharded index exactly."""
+        return FacetCounts(*_facet_out(labels, *self._facets(labels, n_labels, filter, rows_per_chunk)))
+
+    def top_facets(self, labels, n_labels: int, topn: int, filter=None, min_count: int = 1) -> TopFacets:
+        """DeviceIndex.top_facets over the group's rows: the top-n is taken after the shards' counts are summed, never per shard."""
+        topn, min_count = _topn_args(topn, min_count)
+        counts, total, other = self._facets(labels, n_labels, filter, 0)
+        top_l, top_c = facet_topn(counts, topn, min_count, device=self.device)
+        return TopFacets(*_facet_out(labels, top_l, top_c, total, other))
 
     def close(self):
         if self._h:

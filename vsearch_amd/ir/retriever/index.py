@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from ... import _native as nat
-from ...device_index import DeviceIndex, DiverseResults, Explanation, GroupedResults, NotBinaryError, RangeResults, ShardGroup, _diverse_args, _range_args, _grouped_args, _by_example_args, _explain_args, _int64_ids, _k_a_args, resparsify, topk_exclude
+from ...device_index import DeviceIndex, DiverseResults, Explanation, FacetCounts, GroupedResults, TopFacets, _topn_args, NotBinaryError, RangeResults, ShardGroup, _diverse_args, _range_args, _grouped_args, _by_example_args, _explain_args, _int64_ids, _k_a_args, resparsify, topk_exclude
 
 logger = logging.getLogger(__name__)
 
@@ -492,6 +492,148 @@ class Index:
         target, q = self._range_queries(q_embs, min_score, 0)
         return target.match_filter(q, min_score, filter=filter)
 
+    # ---- facets (not in the reference: per-label counts of a document set, the summary beside a result list) ------------------------------
+    def _facet_store(self):
+        if getattr(self, "_facets", None) is None:
+            self._facets = {}                                       # name -> (int32 codes on the index's GPU, n_labels, names | None)
+        return self._facets
+
+    @staticmethod
+    def _facet_codes(codes, n, what="codes"):
+        """codes of set_facet / add(facets=) -> int32 CPU tensor [n]; values >= 0 are labels, -1 = none"""
+        c = codes.detach().cpu() if isinstance(codes, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.atleast_1d(np.asarray(codes))))
+        if c.dim() != 1:
+            raise ValueError(f"{what} must be 1-D (one code per document), got {c.dim()} dimensions")
+        if c.is_floating_point() or c.is_complex() or c.dtype == torch.bool:
+            raise TypeError(f"{what} must be integer codes, got {c.dtype}")
+        if int(c.shape[0]) != n:
+            raise ValueError(f"{what} holds {int(c.shape[0])} entries for {n} documents")
+        if n and int(c.min()) < -1:
+            raise ValueError(f"{what} must be >= -1 (-1 = no label), got {int(c.min())}")
+        if n and int(c.max()) >= 0x7FFFFFFF:
+            raise ValueError(f"code {int(c.max())} does not fit 31 bits")
+        return c.to(torch.int32)
+
+    def set_facet(self, name: str, codes, names=None):
+        """Give every document a label of facet field `name` (a category, a language, a year, an article): int array / tensor [N], values
+        >= 0 are labels, -1 means none.  n_labels = max + 1, or len(names) when `names` (label -> display name) is given; a code >=
+        len(names) raises.  Kept as an int32 tensor on the index's GPU for ``facets``; codes=None removes the field.  Facet fields follow
+        compact() and add(facets=); they are NOT written by save() -- call set_facet again after a load."""
+        if not isinstance(name, str) or not name:
+            raise TypeError("a facet field is named by a non-empty string")
+        if name == "groups":
+            raise ValueError('"groups" names the group ids (set_groups): pick another field name')
+        store = self._facet_store()
+        if codes is None:
+            store.pop(name, None)
+            return
+        c = self._facet_codes(codes, self._n_rows())
+        top = int(c.max()) if c.numel() else -1
+        if names is not None:
+            names = list(names)
+            if not names:
+                raise ValueError("names is empty")
+            if top >= len(names):
+                raise ValueError(f"code {top} has no name: names holds {len(names)}")
+            n_labels = len(names)
+        else:
+            n_labels = max(top + 1, 1)
+        store[name] = (c.to(torch.device("cuda", self._explain_target()[1])).contiguous(), n_labels, names)
+
+    @property
+    def facet_fields(self):
+        """the names of the facet fields set on this index"""
+        return list(getattr(self, "_facets", None) or {})
+
+    def facet_from_samples(self, key: str, name: Optional[str] = None):
+        """Build facet field `name` (default: `key`) from field `key` of the data file: names are the sorted distinct values, a document
+        without the key gets -1 -> the names.  Host work over the text store."""
+        n = len(self)
+        if n == 0:
+            raise ValueError("the index has no data file to read facets from")
+        if n != self._n_rows():
+            raise ValueError(f"the data file holds {n} documents, the index {self._n_rows()}")
+        vals = []
+        for i in range(n):
+            sample = self.get_sample(i)
+            if not isinstance(sample, dict):
+                raise TypeError(f"document {i} is a {type(sample).__name__}, not a record with fields: pass the codes to set_facet()")
+            if key not in sample or sample[key] is None:
+                vals.append(None)
+                continue
+            v = sample[key]
+            vals.append(v if isinstance(v, (str, int, float, bool, tuple)) else json.dumps(v, sort_keys=True))
+        names = sorted({v for v in vals if v is not None}, key=lambda v: (type(v).__name__, v))
+        if not names:
+            raise KeyError(f"no document has a field {key!r}")
+        code = {(type(v).__name__, v): i for i, v in enumerate(names)}      # (1, 1.0 and True are different labels)
+        codes = np.array([-1 if v is None else code[(type(v).__name__, v)] for v in vals], dtype=np.int32)
+        self.set_facet(name or key, codes, names)
+        return names
+
+    def _facet_field(self, field):
+        """-> (codes on the search target's GPU, n_labels, names | None)"""
+        gpu = torch.device("cuda", self._explain_target()[1])
+        if field == "groups":
+            if self.groups is None:
+                raise RuntimeError("the index has no groups: set_groups(groups) or groups_from_samples(key) first")
+            if self._groups.device != gpu:
+                self._groups = self._groups.to(gpu)
+            return self._groups, int(self._groups.max()) + 1 if self._groups.numel() else 1, None
+        store = self._facet_store()
+        if field not in store:
+            raise KeyError(f"no facet field {field!r}: set_facet() or facet_from_samples() first (fields: {list(store)})")
+        codes, n_labels, names = store[field]
+        if codes.device != gpu:
+            codes = codes.to(gpu)
+            store[field] = (codes, n_labels, names)
+        return codes, n_labels, names
+
+    def facet_names(self, field):
+        """label -> display name of a facet field (None when it has none)"""
+        return self._facet_field(field)[2]
+
+    def facets(self, field: str, q_embs=None, min_score=None, filter=None, topn: Optional[int] = 10, min_count: int = 1):
+        """How a document set spreads over the labels of facet field `field` (``set_facet`` / ``facet_from_samples``; "groups" = the group
+        ids).  The set: with q_embs and min_score, per query the documents ``match_filter(q_embs, min_score, filter)`` matches; without
+        them, `filter` alone (as in ``search``; None = every document).  Deleted documents never count.  -> TopFacets(labels [B, topn],
+        counts [B, topn], total [B], other [B]): the topn labels with the most documents of the set (count descending, label ascending, at
+        least max(min_count, 1) documents; unused slots label -1 / count 0), total = the size of the set, other = its documents without a
+        label; topn=None: the dense FacetCounts(counts [B, n_labels], total, other).  Works on a row-sharded index as well (not on the
+        one-process-per-GPU path of ``vsearch_amd.distributed``)."""
+        if (q_embs is None) != (min_score is None):
+            raise ValueError("q_embs and min_score go together: the set is match_filter(q_embs, min_score, filter), or the filter alone")
+        if topn is not None:
+            topn, min_count = _topn_args(topn, min_count)
+        codes, n_labels, _ = self._facet_field(field)
+        target = self._explain_target()[0]
+        if q_embs is not None:
+            filter = self.match_filter(q_embs, min_score, filter=filter)
+        if topn is None:
+            return FacetCounts(*(self._to_api(t) for t in target.facet_counts(codes, n_labels, filter=filter)))
+        return TopFacets(*(self._to_api(t) for t in target.top_facets(codes, n_labels, topn, filter=filter, min_count=min_count)))
+
+    def _added_facets(self, facets, n_add):
+        """facets= of add() / update() -> {name: int32 CPU codes [n_add]}, or None for an index without facet fields.  Raises before
+        anything changes: a missing or an extra field, a code without a name."""
+        have = getattr(self, "_facets", None) or {}
+        given = dict(facets) if facets is not None else {}
+        if not have:
+            if given:
+                raise ValueError("the index has no facet fields: set_facet() first, then add(..., facets=)")
+            return None
+        missing, extra = sorted(set(have) - set(given)), sorted(set(given) - set(have))
+        if missing or extra:
+            raise ValueError(f"the index has facet fields {sorted(have)}: add(..., facets=) must give codes for exactly these"
+                             f" (missing {missing}, unknown {extra})")
+        out = {}
+        for name, codes in given.items():
+            c = self._facet_codes(codes, n_add, f"facets[{name!r}]")
+            if have[name][2] is not None and n_add and int(c.max()) >= len(have[name][2]):
+                raise ValueError(f"facets[{name!r}]: code {int(c.max())} has no name (the field has {len(have[name][2])})")
+            out[name] = c
+        return out
+
     # ---- diversified search (not in the reference: Maximal Marginal Relevance over the top hits, similarities from the stored rows) -------
     def _diverse_out(self, res) -> DiverseResults:
         return DiverseResults(self._to_api(res.ids), self._to_api(res.scores.to(self._dtype)), self._to_api(res.pos), self._to_api(res.mmr))
@@ -603,6 +745,9 @@ class Index:
         if self.groups is not None:                                 # new document j keeps the group of old_ids[j]
             g = self._groups
             self._groups = g.index_select(0, torch.from_numpy(old).to(g.device)).to(torch.device("cuda", self._explain_target()[1]))
+        for name, (c, n_labels, names) in list((getattr(self, "_facets", None) or {}).items()):     # and the label of old_ids[j]
+            c = c.index_select(0, torch.from_numpy(old).to(c.device)).to(torch.device("cuda", self._explain_target()[1]))
+            self._facets[name] = (c, n_labels, names)
         return old
 
     def compact(self):
@@ -625,15 +770,17 @@ class Index:
         indptr, indices, data, shape = SparseIndex._csr_parts(vectors)
         return indptr, indices, data, shape
 
-    def add(self, vectors, samples=None, groups=None):
+    def add(self, vectors, samples=None, groups=None, facets=None):
         """Append documents -> their new ids (int64 tensor).  vectors: a sparse CSR tensor / scipy CSR (or a dense [n, V] tensor) whose
         columns match the index.  When the index has no spare capacity it is compacted with room to grow (at least the rows asked for, at
         least a quarter of its size); that moves ids if rows are deleted, so then add() raises and asks for compact().  samples: the
         documents' texts, appended to `data`.  groups: their group ids -- required when the index has groups (set_groups), refused
-        when it has none."""
+        when it has none.  facets: {field: codes} for every facet field of the index (set_facet), under the same rule; a field without
+        names grows its n_labels with the new codes."""
         indptr, indices, data, shape = self._add_csr(vectors)
         n_add = int(indptr.shape[0]) - 1
         new_groups = self._added_groups(groups, n_add)
+        new_facets = self._added_facets(facets, n_add)
         target = self._shards[-1] if getattr(self, "_shards", None) else self._device_index()
         info = target.info()
         if info.kind != nat.VS_KIND_CSR and not (info.kind == nat.VS_KIND_DENSE and info.n_packets > 0):
@@ -678,18 +825,27 @@ class Index:
             self.data = (self.data or []) + list(samples)
         if new_groups is not None:
             self._groups = torch.cat([self._groups, new_groups.to(self._groups.device)])
+        for name, c_new in (new_facets or {}).items():
+            c, n_labels, names = self._facets[name]
+            if names is None and n_add:
+                n_labels = max(n_labels, int(c_new.max()) + 1)
+            self._facets[name] = (torch.cat([c, c_new.to(c.device)]), n_labels, names)
         return torch.arange(n0, n0 + n_add, dtype=torch.int64)
 
-    def update(self, ids, vectors, samples=None, groups=None):
-        """delete(ids) + add(vectors, samples, groups) -> the new ids of the replacements"""
+    def update(self, ids, vectors, samples=None, groups=None, facets=None):
+        """delete(ids) + add(vectors, samples, groups, facets) -> the new ids of the replacements"""
         if (self.groups is None) != (groups is None):               # (before anything is deleted)
             self._added_groups(groups, 0)
+        have = getattr(self, "_facets", None) or {}
+        if set(have) != set(facets or {}):
+            self._added_facets(facets, 0)
         self.delete(ids)
-        return self.add(vectors, samples, groups)
+        return self.add(vectors, samples, groups, facets)
 
     # ---- persistence -------------------------------------------------------------------------------
     def save(self, path):
-        """Dense index -> ``.pt`` (torch.save of the CPU tensor), like index.py:96-109."""
+        """Dense index -> ``.pt`` (torch.save of the CPU tensor), like index.py:96-109.  Groups and facet fields (set_groups, set_facet)
+        are not written: set them again after a load."""
         self._check_no_deletions("a .pt file")
         try:
             torch.save(self.vector.cpu(), path)
@@ -1106,7 +1262,8 @@ class SparseIndex(Index):
 
     # -- persistence (index.py:181-202) --------------------------------------------------------------
     def save(self, path):
-        """CSR index -> scipy ``.npz`` (keys indices, indptr, data, shape, format; int64 indices)."""
+        """CSR index -> scipy ``.npz`` (keys indices, indptr, data, shape, format; int64 indices).  Groups and facet fields (set_groups,
+        set_facet) are not written: set them again after a load."""
         from scipy.sparse import csr_array, save_npz
         if str(path).endswith(".vsx"):                              # native shard file (loads without a CSR round trip)
             if self._shards:

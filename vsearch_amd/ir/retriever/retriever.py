@@ -122,6 +122,31 @@ class Retriever(BiEncoder):
         q_emb = self.process_query(queries, dropout, a, batch_size=batch_size)
         return index.search_range(q_emb, min_score, max_hits=max_hits, filter=filter)
 
+    def retrieve_facets(self, queries: Union[List[str], np.ndarray, T], field: str, min_score, topn: int = 10, min_count: int = 1,
+                        dropout: float = 0, a: int = None, index: Index = None, batch_size: int = 32, filter=None, must=None, must_not=None,
+                        should=None, min_should: int = None):
+        """How each query's matches spread over facet field `field` (``index.set_facet`` / ``facet_from_samples``) -- ``Index.facets`` behind
+        the query encoder: the matches are the documents scoring at least `min_score`, exactly as in ``retrieve_range``; `filter` and the
+        term constraints act through that match set.  -> (facets, totals): facets[b] is the list of (name, count) of query b's `topn`
+        labels with the most matches (the label's code where the field has no names), count descending; totals[b] the number of matches."""
+        index = index or self.index
+        if index is None:
+            raise RuntimeError("no index: call build_index / load_index first")
+        if must is not None or must_not is not None or should is not None or min_should is not None:
+            terms = self.term_filter(must=must, must_not=must_not, should=should, min_should=min_should, index=index)
+            if filter is not None:
+                from ...doc_filter import as_doc_filter
+                filter = as_doc_filter(filter, terms.n_rows, device=terms.device) & terms
+            else:
+                filter = terms
+        a = a or self.encoder_q.config.topk
+        q_emb = self.process_query(queries, dropout, a, batch_size=batch_size)
+        top = index.facets(field, q_emb, min_score, filter=filter, topn=topn, min_count=min_count)
+        names = index.facet_names(field)
+        labels, counts, totals = top.labels.cpu().tolist(), top.counts.cpu().tolist(), top.total.cpu().tolist()
+        facets = [[(names[l] if names is not None else l, c) for l, c in zip(ls, cs) if l >= 0] for ls, cs in zip(labels, counts)]
+        return facets, totals
+
     def retrieve_diverse(self, queries: Union[List[str], np.ndarray, T], k: int = 5, lam: float = 0.5, depth: int = None, sim: str = "cosine",
                          dropout: float = 0, a: int = None, index: Index = None, batch_size: int = 32, filter=None, must=None, must_not=None,
                          should=None, min_should: int = None) -> DiverseResults:
