@@ -444,6 +444,48 @@ VS_API int vs_mmr_select_csr(const int64_t* rowptr, const int32_t* cols, const f
                              int32_t kk, int64_t ld, int32_t n_cols, const float* lam, int32_t k, int mode, int64_t* out_ids, float* out_scores,
                              int32_t* out_pos, float* out_mmr, float* out_pen, int device, void* stream);
 
+/* ---- fused search: rank and score fusion of hit lists (reciprocal rank fusion: Cormack, Clarke & Buettcher 2009; CombSUM / CombMNZ: Fox &
+ * Shaw 1994; no reference counterpart) ---------------------------------------------------------------------------------------------------
+ * vs_fuse_topk merges L hit lists per query into one: the union of their ids, every id given a fused value from its rank or score in each
+ * list, the top k of them.  List l of query b is ids / scores [l * list_stride + b * ld, + kk) (int64 / fp32).  A list ends at its first id -1
+ * (a filtered search's padding); what stands behind it is ignored.  An id may stand in several lists; an id twice in ONE list counts at its
+ * lowest position, the later entries are ignored (they still take part in mx_l / mn_l below).
+ * Contribution c_l of list l to document d at 0-based position r with score s (fl32 = rounded to fp32, never a fused multiply-add):
+ *   VS_FUSE_RRF: fl32(w_l / fl32(rrf_c + (float)(r + 1))); scores are not read for it (NaN / inf scores are harmless); absent from l: +0
+ *   VS_FUSE_SUM: fl32(w_l * n), n = fl32(fl32(s - mn_l) / fl32(mx_l - mn_l)), mx_l / mn_l the largest / smallest score among the entries of
+ *                list l of this query (-0.0 ordered below +0.0), n = 1 when mx_l == mn_l (weighted CombSUM, min-max normalised); absent: +0
+ *   VS_FUSE_MNZ: as VS_FUSE_SUM
+ *   VS_FUSE_RAW: fl32(w_l * s); absent: fl32(w_l * fill[b * ldf + l]), 0 without fill (fill is read in this mode only)
+ *   fused(d) = fl32(...fl32(fl32(c_0 + c_1) + c_2)... + c_{L-1}), in list order; VS_FUSE_MNZ then multiplies once: fl32(fused * (float)m), m the
+ *   number of lists holding d.  The lists need not be sorted for the score modes; RRF reads the position as the rank, so its callers pass
+ *   lists in the search's canonical order.  Scores are expected finite in the three score modes.
+ * weights fp32: ldw == 0 -> [L] for the batch, else [B, ldw] (w_l of query b = weights[b * ldw + l]); NULL = all 1.
+ * Result: fused descending, compared as floats (-0.0 and +0.0 tie), then id ascending; min(k, out_n[b]) results.  out_ids [B, k] int64,
+ * out_fused [B, k] fp32, out_ranks [B, k, L] int32 (0-based position in list l, -1 = not in it), out_scores [B, k, L] fp32 (list l's own score
+ * bits, -inf where absent), out_n [B] int32 (the size of the union, whatever k is).  Unused slots: id -1, fused -inf, ranks -1, scores -inf.
+ * Every slot is written.
+ * Limits (VS_EINVAL beyond them): L in 1..VS_FUSE_MAX_LISTS, kk and k in 1..VS_FUSE_MAX_DEPTH, L * kk <= VS_FUSE_MAX_ENTRIES, ld >= kk,
+ * list_stride >= (B - 1) * ld + kk when L > 1, ldw 0 or >= L, ldf >= L, a valid mode, finite rrf_c >= 0 (conventionally 60), ids in
+ * [-1, 2^32 - 1): the keys hold 32-bit ids, as in vs_merge_topk.
+ * All buffers host pointers, or all device pointers on `device` (VS_EINVAL for a mix).  Host arrays are checked (ids in range in front of a
+ * list's first -1, weights and fill finite: VS_EINVAL, nothing written), staged, and the call blocks.  Device arrays are not read on the host:
+ * an id outside the range ends its list there, as in vs_topk_collapse; with a non-NULL stream the call only enqueues.
+ * One workgroup per query: the L * kk entries sorted once as 64-bit keys (id : list : position) in LDS, so that a document's entries are
+ * adjacent and its first entry of a list is its lowest position; the documents ranked by a second sort of (fused, position of the run).  No
+ * float atomics, so results are deterministic.
+ * Not covered: z-score normalisation; more than 8 lists or L * kk > 4096; the one-process-per-GPU RCCL path has no entry of its own (its
+ * lists after vs_merge_topk are ordinary lists).                                                                                       */
+#define VS_FUSE_RRF 0
+#define VS_FUSE_SUM 1
+#define VS_FUSE_MNZ 2
+#define VS_FUSE_RAW 3
+#define VS_FUSE_MAX_LISTS   8
+#define VS_FUSE_MAX_DEPTH   1024
+#define VS_FUSE_MAX_ENTRIES 4096
+VS_API int vs_fuse_topk(const int64_t* ids, const float* scores, int32_t L, int32_t B, int32_t kk, int64_t ld, int64_t list_stride,
+                        const float* weights, int64_t ldw, const float* fill, int64_t ldf, int mode, float rrf_c, int32_t k, int64_t* out_ids,
+                        float* out_fused, int32_t* out_ranks, float* out_scores, int32_t* out_n, int device, void* stream);
+
 /* Dense score matrix [B, n_rows] fp32 -- the intermediate index.py:91 materialises.  Used by the
  * parity tests to check every score, not just the top-k.                                         */
 VS_API int vs_index_scores(vs_index* index, const void* q, int q_dtype, int64_t ldq, int32_t B,

@@ -21,6 +21,8 @@ VS_KIND_DENSE, VS_KIND_CSR = 0, 1
 TERM_FILTER_SLOTS, TERM_FILTER_TERMS, TERM_FILTER_LIST = 255, 4096, 64
 # diversified search (VS_MMR_*): similarity modes, the deepest candidate list / most picks, the widest vocabulary of vs_mmr_select_csr
 MMR_COSINE, MMR_DOT, MMR_MAX_DEPTH, MMR_MAX_COLS = 0, 1, 1024, 32768
+# fused search (VS_FUSE_*): fusion modes, the most lists, the deepest list / most results, the most entries (L * kk) of vs_fuse_topk
+FUSE_RRF, FUSE_SUM, FUSE_MNZ, FUSE_RAW, FUSE_MAX_LISTS, FUSE_MAX_DEPTH, FUSE_MAX_ENTRIES = 0, 1, 2, 3, 8, 1024, 4096
 # range search (VS_RANGE_MAX_HITS): the most hits vs_index_search_range lists per query
 RANGE_MAX_HITS = 2048
 # facet counts (VS_FACET_LDS_BINS, VS_FACET_MAX_TOPN): uint32 bins of a workgroup's LDS histograms, the most labels vs_facet_topn lists
@@ -99,6 +101,7 @@ _SIGNATURES = {
     "vs_topk_collapse": ([_vp, _vp, _i32, _i32, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _int, _vp], _int),
     "vs_group_filter": ([_vp, _i64, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _int, _vp], _int),
     "vs_mmr_select_csr": ([_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i64, _i32, _vp, _i32, _int, _vp, _vp, _vp, _vp, _vp, _int, _vp], _int),
+    "vs_fuse_topk": ([_vp, _vp, _i32, _i32, _i32, _i64, _i64, _vp, _i64, _vp, _i64, _int, C.c_float, _i32, _vp, _vp, _vp, _vp, _vp, _int, _vp], _int),
     "vs_topk_mask": ([_vp, _i32, _i32, _i64, _i32, _vp, _int, _vp], _int),
     "vs_bow_mask": ([_vp, _i32, _i32, _i32, _i32, _int, _vp, _int, _vp], _int),
     "vs_embed_mask": ([_vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _int, _int, _int, _vp], _int),

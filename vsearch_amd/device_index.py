@@ -505,6 +505,155 @@ def mmr_select(indptr, indices, values, ids, scores, k: int, lam, mode: str, n_c
     return tuple(out)
 
 
+class FusedResults(NamedTuple):
+    """Per query: the k documents with the largest fused value over L hit lists (fused descending, then id ascending) -- their ids, the fused
+    values, and per list the document's 0-based position (-1: not in it) and the list's own score (-inf: not in it); n is the size of the
+    union of the lists, whatever k is.  Unused slots hold id -1 / fused -inf / ranks -1 / scores -inf."""
+    ids: Any           # int64 [B, k]
+    fused: Any         # float32 [B, k]
+    ranks: Any         # int32 [B, k, L]
+    scores: Any        # float32 [B, k, L]
+    n: Any             # int32 [B]
+
+
+MAX_FUSE_LISTS, MAX_FUSE_DEPTH, MAX_FUSE_ENTRIES = nat.FUSE_MAX_LISTS, nat.FUSE_MAX_DEPTH, nat.FUSE_MAX_ENTRIES
+_FUSE_MODES = {"rrf": nat.FUSE_RRF, "sum": nat.FUSE_SUM, "mnz": nat.FUSE_MNZ, "raw": nat.FUSE_RAW}
+
+
+def _fuse_args(k, mode="rrf", c=60.0, depth=None, L=None):
+    """Argument checks of fuse_topk() / search_fused() that need no device -> (k, mode code, c, depth or None)"""
+    for name, v in (("k", k),) + ((("depth", depth),) if depth is not None else ()):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise TypeError(f"{name} must be an int, got {type(v).__name__}")
+        if not 1 <= v <= MAX_FUSE_DEPTH:
+            raise ValueError(f"{name} must be in 1..{MAX_FUSE_DEPTH}, got {v}")
+    if mode not in _FUSE_MODES:
+        raise ValueError(f"the fusion method must be one of {sorted(_FUSE_MODES)}, got {mode!r}")
+    c = float(c)
+    if not (c >= 0 and c != float("inf")):
+        raise ValueError(f"c must be finite and >= 0, got {c}")
+    if L is not None:
+        if not 1 <= L <= MAX_FUSE_LISTS:
+            raise ValueError(f"1..{MAX_FUSE_LISTS} lists can be fused, got {L}")
+        if depth is not None and L * depth > MAX_FUSE_ENTRIES:
+            raise ValueError(f"{L} lists of depth {depth} hold more than {MAX_FUSE_ENTRIES} entries a query")
+    return int(k), _FUSE_MODES[mode], c, (None if depth is None else int(depth))
+
+
+def _fuse_rows(x, B, L, name):
+    """weights / fill of fuse_topk: None | [L] (the batch's) | [B, >= L] (one row a query) -> (float32 numpy array or None, its row stride)"""
+    if x is None:
+        return None, 0
+    if _is_torch(x):
+        x = x.detach().cpu().numpy()
+    a = np.ascontiguousarray(x, dtype=np.float32)
+    if a.ndim == 1 and a.shape[0] == L:
+        return a, 0
+    if a.ndim == 2 and a.shape[0] == B and a.shape[1] >= L:
+        return a, int(a.shape[1])
+    raise ValueError(f"{name} must be [L = {L}] for the batch or [B = {B}, >= L] per query, got shape {a.shape}")
+
+
+def _stack_lists(lists):
+    """A sequence of L (ids [B, kk_l], scores [B, kk_l]) pairs -> ids int64 / scores float32 [L, B, max kk_l], the shorter lists padded with
+    id -1 / score -inf.  On the device when the first pair is; numpy otherwise."""
+    lists = [tuple(p) for p in lists]
+    if not lists or any(len(p) != 2 for p in lists):
+        raise ValueError("the lists must be a non-empty sequence of (ids, scores) pairs")
+    for i, s in lists:
+        if not hasattr(i, "ndim") or i.ndim != 2 or tuple(s.shape) != tuple(i.shape) or int(i.shape[0]) != int(lists[0][0].shape[0]):
+            raise ValueError("every list must be a pair of [B, kk] arrays of one shape, with one B for all lists")
+    L, B, kk = len(lists), int(lists[0][0].shape[0]), max(int(i.shape[1]) for i, _ in lists)
+    first = lists[0][0]
+    if _is_torch(first) and first.is_cuda:
+        import torch
+        ids = torch.full((L, B, kk), -1, dtype=torch.int64, device=first.device)
+        sc = torch.full((L, B, kk), float("-inf"), dtype=torch.float32, device=first.device)
+        as_t = lambda x: x if _is_torch(x) else torch.from_numpy(np.ascontiguousarray(x))
+        for l, (i, s) in enumerate(lists):
+            ids[l, :, :i.shape[1]] = as_t(i).to(first.device)
+            sc[l, :, :i.shape[1]] = as_t(s).to(first.device)
+        return ids, sc
+    ids = np.full((L, B, kk), -1, dtype=np.int64)
+    sc = np.full((L, B, kk), -np.inf, dtype=np.float32)
+    as_n = lambda x: x.detach().cpu().numpy() if _is_torch(x) else np.asarray(x)
+    for l, (i, s) in enumerate(lists):
+        ids[l, :, :i.shape[1]] = as_n(i)
+        sc[l, :, :i.shape[1]] = as_n(s)
+    return ids, sc
+
+
+def fuse_topk(ids, scores, k: int, mode: str = "rrf", weights=None, c: float = 60.0, fill=None, device: int = 0, out=None) -> FusedResults:
+    """Rank / score fusion of L hit lists per query (vs_fuse_topk; the exact numerics: include/vsearch_hip.h): the union of the lists' ids,
+    each given a fused value, the top k by (fused descending, id ascending).  ids int64 / scores float32 [L, B, kk]; or ids a sequence of L
+    (ids [B, kk_l], scores) pairs and scores None: shorter lists are padded with id -1 / score -inf.  A list ends at its first id -1.
+    mode: "rrf" (sum of w_l / (c + rank), ranks from 1; scores are not read) | "sum" (weighted sum of min-max normalised scores) | "mnz"
+    ("sum" times the number of lists holding the document) | "raw" (weighted sum of the raw scores; a list that lacks the document adds
+    w_l * fill).  weights / fill: None, [L] for the batch or [B, >= L] per query.  L <= 8, kk and k <= 1024, L * kk <= 4096.  All numpy,
+    or all torch CUDA tensors on `device` (enqueued on torch's current stream); out: the five arrays of a FusedResults to write instead."""
+    nat.require_device()
+    if scores is None:
+        ids, scores = _stack_lists(ids)
+    if not hasattr(ids, "ndim") or ids.ndim != 3 or tuple(scores.shape) != tuple(ids.shape):
+        raise ValueError("ids and scores must be [L, B, kk] arrays of one shape")
+    L, B, kk = (int(x) for x in ids.shape)
+    k, mode_code, c, _ = _fuse_args(k, mode, c)
+    w, ldw = _fuse_rows(weights, B, L, "weights")
+    f, ldf = _fuse_rows(fill, B, L, "fill")
+    if f is not None and ldf == 0:
+        f, ldf = np.ascontiguousarray(np.broadcast_to(f, (B, L))), L
+    on_dev = _is_torch(ids) and ids.is_cuda
+    if on_dev:
+        import torch
+        ids, scores = ids.contiguous(), scores.contiguous()
+        if ids.dtype != torch.int64 or scores.dtype != torch.float32:
+            raise TypeError(f"ids must be int64 and scores float32, got {ids.dtype} and {scores.dtype}")
+        w, f = (None if x is None else torch.from_numpy(x).to(ids.device) for x in (w, f))
+        if out is None:
+            out = tuple(torch.empty(shape, dtype=dt, device=ids.device) for shape, dt in
+                        (((B, k), torch.int64), ((B, k), torch.float32), ((B, k, L), torch.int32), ((B, k, L), torch.float32), ((B,), torch.int32)))
+        stream = current_stream(int(device))
+    else:
+        ids, scores = np.ascontiguousarray(_host(ids), dtype=np.int64), np.ascontiguousarray(_host(scores), dtype=np.float32)
+        if out is None:
+            out = tuple(np.empty(shape, dtype=dt) for shape, dt in
+                        (((B, k), np.int64), ((B, k), np.float32), ((B, k, L), np.int32), ((B, k, L), np.float32), ((B,), np.int32)))
+        stream = None
+    nat.check(nat.lib().vs_fuse_topk(_ptr(ids), _ptr(scores), L, B, kk, kk, B * kk, _ptr(w), ldw, _ptr(f), ldf, mode_code, c, k,
+                                     *[_ptr(o) for o in out], int(device), stream))
+    return FusedResults(*out)
+
+
+def _search_fused(obj, qs, k, mode="rrf", weights=None, c=60.0, depth=None, filter=None):
+    """search(q_l, depth, filter=) for each of the L query batches -> fuse_topk of the L lists.  depth defaults to min(n_rows, 1024,
+    4096 / L, max(4 k, k + 16)): a starting point, not a measured optimum.  Deleted rows and the filter act through the searches.
+    obj: a DeviceIndex or a ShardGroup."""
+    import torch
+    qs = list(qs) if isinstance(qs, (list, tuple)) else [qs[l] for l in range(int(qs.shape[0]))] if getattr(qs, "ndim", 0) == 3 else None
+    if not qs or any(getattr(q, "ndim", 0) != 2 or int(q.shape[0]) != int(qs[0].shape[0]) for q in qs):
+        raise ValueError("the queries must be [L, B, V] or a non-empty list of L batches [B, V] of one B")
+    L = len(qs)
+    k, _, c, depth = _fuse_args(k, mode, c, depth, L)
+    if depth is None:
+        depth = max(1, min(int(obj.n_rows), MAX_FUSE_DEPTH, MAX_FUSE_ENTRIES // L, max(4 * k, k + 16)))
+    nat.require_device()
+    device = int(obj.device)
+    as_numpy = not _is_torch(qs[0])
+    on_host = as_numpy or not qs[0].is_cuda
+    dev = torch.device("cuda", device)
+    lists = []
+    for q in qs:
+        qd = (torch.from_numpy(np.ascontiguousarray(q)) if not _is_torch(q) else q).to(dev)
+        if isinstance(obj, ShardGroup):
+            torch.cuda.current_stream(device).synchronize()                   # (the group runs on its own streams)
+        lists.append(obj.search(qd, depth, filter=filter))
+    res = fuse_topk(lists, None, k, mode, weights, c, None, device)
+    if on_host:
+        torch.cuda.current_stream(device).synchronize()
+        res = FusedResults(*(t.cpu().numpy() if as_numpy else t.cpu() for t in res))
+    return res
+
+
 class RangeResults(NamedTuple):
     """search_range: per query the number of matching documents (exact, whatever max_hits is) and the first max_hits of them in the
     canonical order (score descending, id ascending): all of them when counts[b] <= max_hits, else the top max_hits; id -1 / score
@@ -1244,6 +1393,15 @@ class DeviceIndex:
         tensors -> tensors on the index's device, on torch's current stream."""
         return _search_diverse(self, q, k, lam, depth, sim, filter, max_row_bytes)
 
+    def search_fused(self, qs, k: int, mode: str = "rrf", weights=None, c: float = 60.0, depth=None, filter=None) -> FusedResults:
+        """Several queries for one answer: every query batch of qs ([L, B, V], or a list of L batches [B, V]: paraphrases, a feedback query
+        next to the original) is searched at depth `depth`, and the L hit lists of a query are fused on the GPU (fuse_topk / vs_fuse_topk:
+        "rrf" reciprocal rank fusion, "sum" / "mnz" min-max normalised CombSUM / CombMNZ, "raw" the weighted sum of the scores).  depth:
+        default min(n_rows, 1024, 4096 / L, max(4 k, k + 16)), a starting point.  filter: as search(), applied to every search.  A fusion
+        of the lists' candidates, not a proven top k of a summed score over all rows.  numpy queries -> numpy results; CUDA tensors ->
+        tensors on the index's device, on torch's current stream."""
+        return _search_fused(self, qs, k, mode, weights, c, depth, filter)
+
     def diversify(self, ids, scores, k: int, lam=0.5, sim: str = "cosine", max_row_bytes=None) -> DiverseResults:
         """search_diverse's selection over hit lists the caller already has (ids int64 / scores [B, kk], kk <= 1024; a reranked or a
         filtered list: anything after a list's first id -1 is ignored).  Rows are read as stored, deleted ones included."""
@@ -1577,6 +1735,11 @@ class ShardGroup:
         """DeviceIndex.search_diverse over the group's rows: the group's search, the candidates' rows stitched from their owners on the first
         shard's GPU (get_rows), the selection there.  Equal to the unsharded index bit for bit."""
         return _search_diverse(self, q, k, lam, depth, sim, filter, max_row_bytes)
+
+    def search_fused(self, qs, k: int, mode: str = "rrf", weights=None, c: float = 60.0, depth=None, filter=None) -> FusedResults:
+        """DeviceIndex.search_fused over the group's rows: the group's searches, fused on the first shard's GPU.  Equal to the unsharded
+        index bit for bit."""
+        return _search_fused(self, qs, k, mode, weights, c, depth, filter)
 
     def diversify(self, ids, scores, k: int, lam=0.5, sim: str = "cosine", max_row_bytes=None) -> DiverseResults:
         """DeviceIndex.diversify with global ids."""

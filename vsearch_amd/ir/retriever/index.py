@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from ... import _native as nat
-from ...device_index import DeviceIndex, DiverseResults, Explanation, FacetCounts, GroupedResults, TopFacets, _topn_args, NotBinaryError, RangeResults, ShardGroup, _diverse_args, _range_args, _grouped_args, _by_example_args, _explain_args, _int64_ids, _k_a_args, resparsify, topk_exclude
+from ...device_index import DeviceIndex, DiverseResults, Explanation, FacetCounts, FusedResults, GroupedResults, TopFacets, fuse_topk, _fuse_args, MAX_FUSE_DEPTH, MAX_FUSE_ENTRIES, _topn_args, NotBinaryError, RangeResults, ShardGroup, _diverse_args, _range_args, _grouped_args, _by_example_args, _explain_args, _int64_ids, _k_a_args, resparsify, topk_exclude
 
 logger = logging.getLogger(__name__)
 
@@ -73,6 +73,21 @@ def _packets_of(indptr) -> int:
     """8-nnz packets the CSR rows of `indptr` take in the device format"""
     ip = indptr.cpu().numpy() if isinstance(indptr, torch.Tensor) else np.asarray(indptr)
     return int(((np.diff(ip.astype(np.int64)) + 7) // 8).sum())
+
+
+def fuse_results(results_list, k: int, method: str = "rrf", weights=None, c: float = 60.0) -> FusedResults:
+    """``Index.search_fused``'s fusion over hit lists already at hand: `results_list` holds L SearchResults (or (ids [B, kk_l], scores)
+    pairs, kk_l <= 1024 and their sum <= 4096 a query) -- a reranked list next to the first-stage one, lists of different indexes.  Shorter
+    lists are padded; a list ends at its first id -1.  The result lives where the first list lives (host lists: numpy arrays)."""
+    lists = [(r[0], r[1]) for r in results_list]
+    _fuse_args(k, method, c, None, len(lists))
+    first = lists[0][0]
+    on_dev = isinstance(first, torch.Tensor) and first.is_cuda
+    if on_dev:
+        lists = [(i, s.float()) for i, s in lists]
+    else:
+        lists = [(i.cpu() if isinstance(i, torch.Tensor) else i, s.float().cpu() if isinstance(s, torch.Tensor) else s) for i, s in lists]
+    return fuse_topk(lists, None, int(k), method, weights, c, device=first.device.index or 0 if on_dev else 0)
 
 
 class Index:
@@ -666,6 +681,71 @@ class Index:
         target, gpu_ord = self._explain_target()
         gpu = torch.device("cuda", gpu_ord)
         return self._diverse_out(target.diversify(ids.to(gpu).contiguous(), scores.detach().to(gpu).float().contiguous(), int(k), lam=lam, sim=sim))
+
+    # ---- fused search (not in the reference: several hit lists of a query merged by rank or score on the GPU, vs_fuse_topk) ---------------
+    def _fused_out(self, res) -> FusedResults:
+        return FusedResults(*(self._to_api(t) for t in res))
+
+    def _query_batch(self, q_embs, gpu):
+        """queries as search() takes them -> a contiguous [B, V] tensor of the index's dtype on `gpu`"""
+        if isinstance(q_embs, np.ndarray):
+            q_embs = torch.from_numpy(q_embs)
+        q = q_embs.detach().to(gpu)
+        q = q.to(self._dtype) if self._dtype in (torch.float16, torch.float32) else q.float()
+        if q.dim() == 1:
+            q = q.unsqueeze(0)
+        return q.contiguous()
+
+    def search_fused(self, q_embs_list, k: int, method: str = "rrf", weights=None, c: float = 60.0, depth: Optional[int] = None,
+                     filter=None) -> FusedResults:
+        """One answer to several queries: every batch of `q_embs_list` (a list of L batches [B, V], or [L, B, V]: paraphrases, sub-questions,
+        a feedback query next to the original) is searched at depth `depth` and the L hit lists of a query are fused on the GPU.  method:
+        "rrf" reciprocal rank fusion sum_l w_l / (c + rank_l) | "sum" weighted CombSUM of min-max normalised scores | "mnz" that times the
+        number of lists holding the document | "raw" the weighted sum of the raw scores.  weights: None, [L] or [B, L].  -> FusedResults(ids,
+        fused, ranks, scores, n): per hit its 0-based rank and score in every list (-1 / -inf where absent), n the size of the union.  depth:
+        default min(N, 1024, 4096 / L, max(4 k, k + 16)).  Deleted documents and `filter` (as ``search``) apply to every search.  Works on a
+        row-sharded index as well.  A fusion of the lists' candidates, not a proven top k of a summed score over the whole corpus."""
+        qs = list(q_embs_list) if isinstance(q_embs_list, (list, tuple)) else [q_embs_list[l] for l in range(int(q_embs_list.shape[0]))]
+        _fuse_args(k, method, c, depth, len(qs))
+        target, gpu_ord = self._explain_target()
+        gpu = torch.device("cuda", gpu_ord)
+        return self._fused_out(target.search_fused([self._query_batch(q, gpu) for q in qs], int(k), method, weights, c, depth, filter))
+
+    def search_hybrid(self, q_embs, others, k: int, method: str = "rrf", weights=None, c: float = 60.0, depth: Optional[int] = None, filter=None,
+                      missing: str = "zero") -> FusedResults:
+        """This index and others over the SAME rows searched together: the valued index next to the bag-of-token index, a sparse index next
+        to a dense one.  `others`: a list of (index, queries for it | None = the same `q_embs`); list 0 is this index.  Every index is
+        searched at depth `depth` (`filter` applies to each) and the lists are fused as in ``search_fused``.  missing="zero": the lists as
+        they are -- a document outside an index's top `depth` gets nothing from it.  missing="score" (method "raw" only): the union of the
+        lists (at most 1024 documents a query, ValueError beyond) is scored on EVERY index from its stored rows (``explain``: on a sparse
+        index the search's own score bit for bit) and those complete lists are fused: every returned document carries its true weighted sum.
+        Still a fusion of candidates, not a proven top k of the summed score over the corpus."""
+        pairs = [(self, q_embs)] + [(idx, q_embs if q is None else q) for idx, q in others]
+        L = len(pairs)
+        _fuse_args(k, method, c, depth, L)
+        if missing not in ("zero", "score"):
+            raise ValueError(f"missing must be 'zero' or 'score', got {missing!r}")
+        if missing == "score" and method != "raw":
+            raise ValueError("missing='score' sums true scores: it goes with method='raw' only")
+        rows = [idx._n_rows() for idx, _ in pairs]
+        if len(set(rows)) != 1:
+            raise ValueError(f"hybrid search needs indexes over the same rows, got row counts {rows}")
+        if depth is None:
+            depth = max(1, min(rows[0], MAX_FUSE_DEPTH, MAX_FUSE_ENTRIES // L, max(4 * int(k), int(k) + 16)))
+        gpu_ord = self._explain_target()[1]
+        gpu = torch.device("cuda", gpu_ord)
+        lists = []
+        for idx, q in pairs:
+            r = idx.search(q, int(depth), filter=filter)
+            lists.append((r.ids.to(gpu), r.scores.to(gpu).float()))
+        if missing == "zero":
+            return self._fused_out(fuse_topk(lists, None, int(k), method, weights, c, device=gpu_ord))
+        union = fuse_topk(lists, None, min(MAX_FUSE_DEPTH, L * int(depth)), "rrf", device=gpu_ord)
+        n_max = int(union.n.max())
+        if n_max > MAX_FUSE_DEPTH:
+            raise ValueError(f"the lists of a query hold {n_max} different documents, missing='score' scores at most {MAX_FUSE_DEPTH}: lower depth")
+        full = [(union.ids, idx.explain(q, union.ids, topn=0).scores.to(gpu).float()) for idx, q in pairs]
+        return self._fused_out(fuse_topk(full, None, int(k), "raw", weights, c, device=gpu_ord))
 
     def _added_groups(self, groups, n_add):
         """groups= of add() / update() -> int32 CPU tensor [n_add], or None for an index without groups"""

@@ -22,7 +22,7 @@ from torch import Tensor as T
 from ... import _native as nat
 from ..biencoder.biencoder import BiEncoder, BiEncoderConfig
 from ..utils import sparse as sp
-from .index import BoTIndex, DiverseResults, GroupedResults, Index, IndexType, RangeResults, SearchResults, SparseIndex
+from .index import BoTIndex, DiverseResults, FusedResults, GroupedResults, Index, IndexType, RangeResults, SearchResults, SparseIndex
 
 logger = logging.getLogger(__name__)
 
@@ -166,6 +166,50 @@ class Retriever(BiEncoder):
         a = a or self.encoder_q.config.topk
         q_emb = self.process_query(queries, dropout, a, batch_size=batch_size)
         return index.search_diverse(q_emb, k=k, lam=lam, depth=depth, sim=sim, filter=filter)
+
+    def retrieve_fused(self, query_variants, k: int = 5, method: str = "rrf", weights=None, c: float = 60.0, depth: int = None,
+                       dropout: float = 0, a: int = None, index: Index = None, batch_size: int = 32, filter=None, must=None, must_not=None,
+                       should=None, min_should: int = None) -> SearchResults:
+        """One answer to several phrasings: `query_variants` is a list of L query lists (or embedding tensors), each of length B -- variant l
+        of query b is query_variants[l][b].  Every variant batch is searched and the L hit lists of a query are fused on the GPU
+        (``Index.search_fused``: "rrf" by default).  -> SearchResults(ids, scores), the fused value as the score.  `filter` and the term
+        constraints as in ``retrieve``: they apply to every variant's search."""
+        index = index or self.index
+        if index is None:
+            raise RuntimeError("no index: call build_index / load_index first")
+        if must is not None or must_not is not None or should is not None or min_should is not None:
+            terms = self.term_filter(must=must, must_not=must_not, should=should, min_should=min_should, index=index)
+            if filter is not None:
+                from ...doc_filter import as_doc_filter
+                filter = as_doc_filter(filter, terms.n_rows, device=terms.device) & terms
+            else:
+                filter = terms
+        a = a or self.encoder_q.config.topk
+        q_embs = [self.process_query(q, dropout, a, batch_size=batch_size) for q in query_variants]
+        res = index.search_fused(q_embs, k=k, method=method, weights=weights, c=c, depth=depth, filter=filter)
+        return SearchResults(res.ids, res.fused)
+
+    def retrieve_hybrid(self, queries: Union[List[str], np.ndarray, T], k: int = 5, indexes: List[Index] = None, weights=None, method: str = "rrf",
+                        c: float = 60.0, depth: int = None, missing: str = "zero", dropout: float = 0, a: int = None, batch_size: int = 32,
+                        filter=None, must=None, must_not=None, should=None, min_should: int = None) -> FusedResults:
+        """The same queries against several indexes over the same documents (`indexes`: the valued index and the bag-of-token index of a
+        corpus; default: the retriever's own alone), fused on the GPU -- ``Index.search_hybrid`` behind the query encoder.  `missing`:
+        "zero" | "score" (method "raw": every hit carries its true weighted sum).  `filter` and the term constraints as in ``retrieve``."""
+        indexes = list(indexes) if indexes else [self.index]
+        if indexes[0] is None:
+            raise RuntimeError("no index: call build_index / load_index first")
+        first = indexes[0]
+        if must is not None or must_not is not None or should is not None or min_should is not None:
+            terms = self.term_filter(must=must, must_not=must_not, should=should, min_should=min_should, index=first)
+            if filter is not None:
+                from ...doc_filter import as_doc_filter
+                filter = as_doc_filter(filter, terms.n_rows, device=terms.device) & terms
+            else:
+                filter = terms
+        a = a or self.encoder_q.config.topk
+        q_emb = self.process_query(queries, dropout, a, batch_size=batch_size)
+        return first.search_hybrid(q_emb, [(idx, None) for idx in indexes[1:]], k, method=method, weights=weights, c=c, depth=depth, filter=filter,
+                                   missing=missing)
 
     def term_filter(self, must=None, must_not=None, should=None, min_should: int = None, thr=None, index: Index = None):
         """Index.term_filter with terms given as column ids or as vocabulary tokens (strings): a string is looked up in the passage
