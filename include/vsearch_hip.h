@@ -263,6 +263,61 @@ VS_API int vs_index_facet_counts(vs_index* index, const uint32_t* words, int64_t
 VS_API int vs_facet_topn(const int64_t* counts, int64_t ld_counts, int32_t B, int32_t n_labels, int32_t n, int64_t min_count,
                          int32_t* out_labels, int64_t* out_counts, int device, void* stream);
 
+/* ---- term aggregations: what a document set is about (no reference counterpart: the reference only has topk) ---------------------------------
+ * For any set of rows of a CSR-packet index: how many of them HAVE each vocabulary column (vs_index_term_counts, vs_index_term_counts_ids), and
+ * which columns are over-represented in the set against a background (vs_term_topn: "significant terms").
+ * A row has column c under the definition of the term constraints (vs_index_term_bitmaps): it stores c with a non-zero value.  An fp16 store widens exactly; a
+ * binary index stores 1, so every stored cell counts; a stored +0.0 or -0.0 does not count; the packets' padding column n_cols never counts.
+ *   counts [B, ld_counts] int64, ld_counts >= n_cols: counts [b, c] = rows of query b's set that have column c.  Every element of
+ *   counts [:, 0 .. n_cols) is written, columns [n_cols, ld_counts) are not touched.  total [B] int64: the rows of the set, every element written.
+ * vs_index_term_counts (bitmap driven): row membership is exactly that of vs_index_facet_counts -- bit bit0 + r of the bitmap at words + b *
+ *   ld_words stands for row r; ld_words = 0: one shared bitmap, and then B must be 1 (else ld_words >= the (bit0 + n_rows + 31) / 32 words a
+ *   bitmap spans); words == NULL: every row is set (B must be 1); the handle's live bitmap is ANDed in at bit 0 whatever bit0 is (deleted rows
+ *   never count); bits at or past bit0 + n_rows are ignored whatever they hold.  words == NULL is the document frequency of all columns over the
+ *   live index in one pass.
+ * vs_index_term_counts_ids (id-list driven): ids [B, ld] int64 with m entries a query (ld >= m), row = id - id_offset: the terms of a hit list
+ *   without a bitmap.  Id -1 is skipped; a deleted row is skipped; AN ID LISTED TWICE COUNTS TWICE; total [b] = the entries counted.  An id
+ *   outside the index (row outside [0, n_rows)): strict = 1 -- VS_EINVAL for a host list, the entry is skipped for a device list (device ids
+ *   are not read on the host); strict = 0 -- skipped silently (what a shard passes for ids it does not own).
+ * A workgroup owns a chunk of rows (a slice of a list) and one query; it walks the bitmap in 2048-row spans, leaves an all-zero span at once,
+ * skips a 64-row step with no bit set, and streams the packets of the set rows: a lane takes one 16-byte packet of 8 column ids and reads the
+ * values only where the store has them.  Two regimes (vs_term_plan): n_cols <= VS_TERM_LDS_COLS -- one uint32 histogram of all columns in the
+ * workgroup's LDS (the 29 523 columns of the BERT vocabulary are 118 KB of a CU's 160 KiB), non-zero bins added to counts at the end of the chunk;
+ * wider (up to the 65 535 columns a packet can name) -- 64-bit atomic adds straight into counts.
+ * vs_term_plan: the launch of the two calls for these arguments -- pure host arithmetic, no device needed.  n_rows: the index's rows (for the
+ *   id-list call: the m entries of a query, with per_query = 1 and rows_per_chunk = 0).  regime 0 = LDS, 1 = global; chunks x rows_per_chunk >=
+ *   n_rows > (chunks - 1) x rows_per_chunk.  rows_per_chunk = 0: automatic (B x chunks ~ 4 workgroups a CU, a chunk at least 2048 rows); any
+ *   other value must be a positive multiple of 64 and is taken as given (a tuning knob: the result never depends on the plan).
+ * vs_term_topn: per query the n most significant columns of counts [B, ld_counts] / total [B] against the background bg [n_cols] int64 (shared
+ *   by the batch) / bg_total.  Column c is a candidate iff fg = counts [b, c] >= max(min_count, 1), bg [c] > 0, total [b] > 0 and bg_total > 0.
+ *   In fp64, each operation rounded once (no contraction): fgp = double(fg) / double(total [b]), bgp = double(bg [c]) / double(bg_total);
+ *     VS_TERM_LIFT: s = fgp / bgp;     VS_TERM_JLH: a candidate only if fgp > bgp, s = (fgp - bgp) * (fgp / bgp).
+ *   Order: float(s) descending, then column ascending -- two columns whose scores round to the same fp32 are ordered by the column.  out_cols
+ *   int32 / out_score fp32 / out_fg int64 / out_bg int64, all [B, n], every slot written: -1 / -inf / 0 / 0 behind the last candidate.  n in
+ *   1..VS_TERM_MAX_TOPN, n > n_cols is allowed.  One workgroup per query.  Ordering by the raw count is no method here (an fp32 score cannot
+ *   order counts above 2^24 exactly): vs_facet_topn over counts does that on the exact integers.
+ * Errors: NULL handle or outputs, B < 1, rows_per_chunk no multiple of 64, B > 1 with ld_words = 0, ld_words / ld / ld_counts too short, m < 1,
+ * n or method out of range, chunks x B beyond 2^31 - 1 work items: VS_EINVAL -- checked before the device is touched (without a GPU a bad argument is VS_EINVAL, a good one
+ * VS_ENODEVICE).  Pointers: all host (staged; the call blocks), or all device pointers on the index's device / `device` (VS_EINVAL for a mix);
+ * device pointers and a non-NULL stream only enqueue.  A dense index on the matrix cores keeps no packets: VS_EUNSUPPORTED.
+ * Not covered: weight sums or centroids per column (a 64-bit image of the vocabulary does not fit the LDS: it needs column tiles); the dense
+ * matrix kind; a shard group has no entry point of its own (every shard counts its bit range of the bitmap, or the ids with strict = 0 and its
+ * id_offset; counts and total are summed, and the top-n taken after the sum) and the one-process-per-GPU RCCL path has none; a cached
+ * background; scores that need a logarithm (PMI, tf-idf): they would not be bit-reproducible.                                               */
+#define VS_TERM_LDS_COLS 36864       /* columns of a workgroup's LDS histogram (144 KiB of uint32 bins; the rest of the 160 KiB: counters) */
+#define VS_TERM_MAX_TOPN 1024        /* columns vs_term_topn lists per query at most */
+#define VS_TERM_LIFT 0
+#define VS_TERM_JLH 1
+VS_API int vs_term_plan(int64_t n_rows, int32_t B, int32_t n_cols, int per_query, int64_t rows_per_chunk, int32_t* out_regime,
+                        int64_t* out_chunks, int64_t* out_rows_per_chunk);
+VS_API int vs_index_term_counts(vs_index* index, const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B, int64_t rows_per_chunk,
+                                int64_t* counts, int64_t ld_counts, int64_t* total, void* stream);
+VS_API int vs_index_term_counts_ids(vs_index* index, const int64_t* ids, int32_t B, int64_t m, int64_t ld, int64_t id_offset, int strict,
+                                    int64_t* counts, int64_t ld_counts, int64_t* total, void* stream);
+VS_API int vs_term_topn(const int64_t* counts, int64_t ld_counts, const int64_t* total, int32_t B, int32_t n_cols, const int64_t* bg,
+                        int64_t bg_total, int method, int32_t n, int64_t min_count, int32_t* out_cols, float* out_score, int64_t* out_fg,
+                        int64_t* out_bg, int device, void* stream);
+
 /* bool / uint8 mask [B, n] (row stride ld_mask bytes; non-zero = allowed) -> the bitmap words [B, ld_words] vs_index_search_filtered
  * reads (bits past n of a row's last word are 0).  mask and words: host pointers or device pointers on `device` (VS_EINVAL otherwise).  stream as in
  * vs_index_search (host buffers block).                                                                                          */

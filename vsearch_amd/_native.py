@@ -27,6 +27,8 @@ FUSE_RRF, FUSE_SUM, FUSE_MNZ, FUSE_RAW, FUSE_MAX_LISTS, FUSE_MAX_DEPTH, FUSE_MAX
 RANGE_MAX_HITS = 2048
 # facet counts (VS_FACET_LDS_BINS, VS_FACET_MAX_TOPN): uint32 bins of a workgroup's LDS histograms, the most labels vs_facet_topn lists
 FACET_LDS_BINS, FACET_MAX_TOPN = 16384, 1024
+# term aggregations (VS_TERM_*): columns of a workgroup's LDS histogram, the most columns vs_term_topn lists, its scoring methods
+TERM_LDS_COLS, TERM_MAX_TOPN, TERM_LIFT, TERM_JLH = 36864, 1024, 0, 1
 
 
 class VsearchNativeError(RuntimeError):
@@ -67,6 +69,10 @@ _SIGNATURES = {
     "vs_facet_counts": ([_vp, _i64, _i64, _vp, _i32, _vp, _i64, _i32, _i64, _vp, _i64, _vp, _vp, _int, _vp], _int),
     "vs_index_facet_counts": ([_vp, _vp, _i64, _i64, _i32, _vp, _i32, _i64, _vp, _i64, _vp, _vp, _vp], _int),
     "vs_facet_topn": ([_vp, _i64, _i32, _i32, _i32, _i64, _vp, _vp, _int, _vp], _int),
+    "vs_term_plan": ([_i64, _i32, _i32, _int, _i64, C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i64)], _int),
+    "vs_index_term_counts": ([_vp, _vp, _i64, _i64, _i32, _i64, _vp, _i64, _vp, _vp], _int),
+    "vs_index_term_counts_ids": ([_vp, _vp, _i32, _i64, _i64, _i64, _int, _vp, _i64, _vp, _vp], _int),
+    "vs_term_topn": ([_vp, _i64, _vp, _i32, _i32, _vp, _i64, _int, _i32, _i64, _vp, _vp, _vp, _vp, _int, _vp], _int),
     "vs_filter_pack": ([_vp, _i32, _i64, _i64, _vp, _i64, _int, _vp], _int),
     "vs_index_scores": ([_vp, _vp, _int, _i64, _i32, _vp, _vp], _int),
     "vs_index_explain": ([_vp, _vp, _int, _i64, _i32, _vp, _i64, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp], _int),

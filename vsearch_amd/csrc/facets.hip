@@ -14,6 +14,7 @@
 // (b) Top-n: one workgroup per query streams the counts as keys (count << 32) | (0xFFFFFFFF - label) -- larger key = larger count, then
 //     smaller label -- through the 4096-key LDS buffer of the scans, pruned to n by wg_sort_desc when more than 2048 are in.
 #include "common.h"
+#include "bitmap_span.h"
 #include "staging.h"
 #include "topk_keys.h"
 
@@ -46,27 +47,6 @@ struct FacetArgs {
     unsigned long long* total;        // [B], zeroed by the caller
     unsigned long long* other;        // [B], zeroed by the caller
 };
-
-// lane l holds words w0 + l and w0 + l + 1 of a bitmap (0 past its last word)
-struct Span {
-    uint32_t lo, hi;
-};
-__device__ __forceinline__ Span load_span(const uint32_t* w, int64_t w0, int64_t n_words, int lane) {
-    const int64_t i = w0 + lane;
-    Span s;
-    s.lo = i < n_words ? w[i] : 0u;
-    s.hi = i + 1 < n_words ? w[i + 1] : 0u;
-    return s;
-}
-// bits [64 s + sh, 64 s + sh + 64) of the span (s uniform, sh in 0..31): words 2 s, 2 s + 1 and 2 s + 2
-__device__ __forceinline__ uint64_t window64(const Span& sp, int s, int sh) {
-    const uint32_t a = (uint32_t)__builtin_amdgcn_readlane((int)sp.lo, 2 * s);
-    const uint32_t b = (uint32_t)__builtin_amdgcn_readlane((int)sp.hi, 2 * s);
-    const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)sp.hi, 2 * s + 1);
-    uint64_t v = (((uint64_t)b << 32) | a) >> sh;
-    if (sh) v |= (uint64_t)c << (64 - sh);
-    return v;
-}
 
 template <int QT, int GLOBAL>
 __global__ __launch_bounds__(kFacetThreads) void facet_counts_kernel(FacetArgs a) {

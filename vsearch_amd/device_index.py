@@ -840,6 +840,123 @@ def _facet_out(labels, *tensors):
     return tensors if _is_torch(labels) else tuple(t.cpu().numpy() for t in tensors)
 
 
+# ---- term aggregations: what a document set is about (vs_index_term_counts, vs_index_term_counts_ids, vs_term_topn) -------------------------
+class TermCounts(NamedTuple):
+    """term_counts: per query the documents of the set that have each vocabulary column (counts [B, n_cols]) and the size of the set
+    (total [B]).  All int64."""
+    counts: Any
+    total: Any
+
+
+class TopTerms(NamedTuple):
+    """top_terms / significant_terms: per query the `topn` most significant columns of the set (cols int32 [B, topn], scores float32
+    [B, topn]), with the documents of the set that have the column (df int64 [B, topn]), the documents of the background that have it
+    (bg int64 [B, topn]) and the size of the set (total int64 [B]).  Unused slots: col -1 / score -inf / df 0 / bg 0."""
+    cols: Any
+    scores: Any
+    df: Any
+    bg: Any
+    total: Any
+
+
+MAX_TERM_TOPN = nat.TERM_MAX_TOPN
+_TERM_METHODS = {"lift": nat.TERM_LIFT, "jlh": nat.TERM_JLH}
+
+
+def term_plan(n_rows: int, B: int, n_cols: int, per_query: bool, rows_per_chunk: int = 0):
+    """The launch vs_index_term_counts takes for these arguments (vs_term_plan; pure host arithmetic, no GPU needed) -> (regime, chunks,
+    rows_per_chunk): regime 0 = one LDS histogram of all columns per workgroup, 1 = global atomics."""
+    regime, chunks, rpc = C.c_int32(0), C.c_int64(0), C.c_int64(0)
+    nat.check(nat.lib().vs_term_plan(int(n_rows), int(B), int(n_cols), 1 if per_query else 0, int(rows_per_chunk), C.byref(regime),
+                                     C.byref(chunks), C.byref(rpc)))
+    return regime.value, chunks.value, rpc.value
+
+
+def _term_topn_args(topn, method, min_count):
+    """Argument checks of a term top-n that need no device -> (topn, method name, min_count); "count" orders by the raw count"""
+    for name, v in (("topn", topn), ("min_count", min_count)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise TypeError(f"{name} must be an int, got {type(v).__name__}")
+    if not 1 <= int(topn) <= MAX_TERM_TOPN:
+        raise ValueError(f"topn must be in 1..{MAX_TERM_TOPN}, got {int(topn)}")
+    if method not in _TERM_METHODS and method != "count":
+        raise ValueError(f'method must be "jlh", "lift" or "count", got {method!r}')
+    return int(topn), method, int(min_count)
+
+
+def term_topn(counts, total, bg, bg_total: int, topn: int = 20, method: str = "jlh", min_count: int = 1, device: int = 0):
+    """Per query the `topn` most significant columns of counts [B, n_cols] / total [B] against the background bg [n_cols] / bg_total
+    (vs_term_topn) -> (cols int32, scores float32, fg int64, bg int64), all [B, topn].  With fgp = fg / total and bgp = bg / bg_total in
+    fp64: "lift" scores fgp / bgp; "jlh" (fgp - bgp) * (fgp / bgp) and lists only columns with fgp > bgp.  A candidate has fg >=
+    max(min_count, 1) and bg > 0.  Score (rounded to fp32) descending, then column ascending; unused slots -1 / -inf / 0 / 0.  numpy in ->
+    numpy out; torch CUDA in -> tensors on `device`, enqueued on torch's current stream."""
+    topn, method, min_count = _term_topn_args(topn, method, min_count)
+    if method == "count":
+        raise ValueError('method "count" orders by the exact integers: use facet_topn(counts, topn, min_count)')
+    if not hasattr(counts, "shape") or counts.ndim != 2:
+        raise ValueError("counts must be [B, n_cols]")
+    B, V = int(counts.shape[0]), int(counts.shape[1])
+    if tuple(total.shape) != (B,) or tuple(bg.shape) != (V,):
+        raise ValueError(f"total must be [{B}] and bg [{V}], got {tuple(total.shape)} and {tuple(bg.shape)}")
+    nat.require_device()
+    code = _TERM_METHODS[method]
+    if _is_torch(counts) and counts.is_cuda:
+        import torch
+        dev = counts.device
+        c, t, g = (x.to(dev).to(torch.int64).contiguous() for x in (counts, total, bg))
+        outs = (torch.empty((B, topn), dtype=torch.int32, device=dev), torch.empty((B, topn), dtype=torch.float32, device=dev),
+                torch.empty((B, topn), dtype=torch.int64, device=dev), torch.empty((B, topn), dtype=torch.int64, device=dev))
+        nat.check(nat.lib().vs_term_topn(_ptr(c), V, _ptr(t), B, V, _ptr(g), int(bg_total), code, topn, min_count, *(_ptr(o) for o in outs),
+                                         int(device), current_stream(int(device))))
+        return outs
+    c, t, g = (np.ascontiguousarray(_host(x), dtype=np.int64) for x in (counts, total, bg))
+    outs = (np.empty((B, topn), dtype=np.int32), np.empty((B, topn), dtype=np.float32), np.empty((B, topn), dtype=np.int64),
+            np.empty((B, topn), dtype=np.int64))
+    nat.check(nat.lib().vs_term_topn(_ptr(c), V, _ptr(t), B, V, _ptr(g), int(bg_total), code, topn, min_count, *(_ptr(o) for o in outs),
+                                     int(device), None))
+    return outs
+
+
+def _term_ids(ids):
+    """ids of a term count -> int64 [B, m] (a 1-D list is one query), numpy or tensor as given"""
+    if isinstance(ids, (list, tuple)):
+        ids = np.asarray(ids, dtype=np.int64)
+    if not hasattr(ids, "shape") or ids.ndim not in (1, 2):
+        raise ValueError("ids must be int64 [B, m] (or [m]: one query)")
+    if "int64" not in str(ids.dtype):
+        raise TypeError(f"ids must be int64, got {ids.dtype}")
+    if ids.ndim == 1:
+        ids = ids[None, :]
+    if int(ids.shape[1]) < 1:
+        raise ValueError("ids must hold at least one entry a query (pad with -1)")
+    return ids
+
+
+def _top_terms(obj, filter, ids, topn, method, min_count, background):
+    """term_counts of the set, the background (given, or every live document: one more pass), then the top-n on the object's first GPU"""
+    import torch
+    topn, method, min_count = _term_topn_args(topn, method, min_count)
+    if background is not None and (not isinstance(background, tuple) or len(background) != 2):
+        raise TypeError("background must be a TermCounts (what term_counts() returns)")
+    fg = obj.term_counts(filter=filter, ids=ids)
+    dev = fg.counts.device
+    if background is None and method != "count":
+        background = obj.term_counts()
+    bgc = bgt = None
+    if background is not None:
+        bgc = torch.as_tensor(background.counts).to(dev).to(torch.int64).reshape(-1)
+        bgt = int(torch.as_tensor(background.total).reshape(-1)[0])
+        if int(bgc.shape[0]) != int(fg.counts.shape[1]):
+            raise ValueError(f"background.counts holds {int(bgc.shape[0])} columns, the index {int(fg.counts.shape[1])}")
+    if method == "count":                                          # the exact integers: vs_facet_topn over the counts
+        cols, df = facet_topn(fg.counts, topn, min_count, device=obj.device)
+        bg = torch.zeros_like(df) if bgc is None else torch.where(cols >= 0, bgc[cols.clamp(min=0).long()], torch.zeros_like(df))
+        scores = torch.where(cols >= 0, df.to(torch.float32), torch.full_like(df, float("-inf"), dtype=torch.float32))
+        return TopTerms(cols, scores, df, bg, fg.total)
+    cols, scores, df, bg = term_topn(fg.counts, fg.total, bgc, bgt, topn, method, min_count, device=obj.device)
+    return TopTerms(cols, scores, df, bg, fg.total)
+
+
 def _host(x):
     return x.detach().numpy() if _is_torch(x) else x
 
@@ -1528,6 +1645,69 @@ class DeviceIndex:
         top_l, top_c = facet_topn(counts, topn, min_count, device=self.device)
         return TopFacets(*_facet_out(labels, top_l, top_c, total, other))
 
+    # ---- term aggregations: what a document set is about (vs_index_term_counts, vs_index_term_counts_ids) ---------------------------------
+    def _term_counts_call(self, f, bit0, rows_per_chunk):
+        """One vs_index_term_counts call on device buffers and torch's current stream -> (counts [B, V], total [B]) int64 CUDA tensors.
+        f: None or a DocFilter on this index's device, read from bit `bit0` on."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        B, V = (f.n_queries if (f is not None and f.per_query) else 1), self._n_cols()
+        counts = torch.empty((B, V), dtype=torch.int64, device=dev)
+        total = torch.empty(B, dtype=torch.int64, device=dev)
+        nat.check(nat.lib().vs_index_term_counts(self._h, _ptr(f.words) if f is not None else None, int(bit0), f.ld if f is not None else 0, B,
+                                                 int(rows_per_chunk), _ptr(counts), V, _ptr(total), current_stream(self.device)))
+        return counts, total
+
+    def _term_counts_ids_call(self, ids_dev, id_offset, strict):
+        """One vs_index_term_counts_ids call: ids_dev int64 CUDA tensor [B, m] on this index's device"""
+        import torch
+        B, m, V = int(ids_dev.shape[0]), int(ids_dev.shape[1]), self._n_cols()
+        counts = torch.empty((B, V), dtype=torch.int64, device=ids_dev.device)
+        total = torch.empty(B, dtype=torch.int64, device=ids_dev.device)
+        nat.check(nat.lib().vs_index_term_counts_ids(self._h, _ptr(ids_dev), B, m, int(ids_dev.stride(0)), int(id_offset), 1 if strict else 0,
+                                                     _ptr(counts), V, _ptr(total), current_stream(self.device)))
+        return counts, total
+
+    def term_counts(self, filter=None, ids=None, rows_per_chunk: int = 0) -> TermCounts:
+        """For a document set, how many of its documents have each vocabulary column -> TermCounts(counts [B, V], total [B]), int64 tensors
+        on the index's device, enqueued on torch's current stream.  A document has a column iff it stores it with a non-zero value (the
+        term constraints' definition).  The set: `filter` -- what search(filter=) accepts: a per-query DocFilter (match_filter's result)
+        gives one row per query, a shared one B = 1 -- or `ids`, int64 [B, m] hit lists (``search``'s ids: -1 is skipped, an id listed
+        twice counts twice, an id outside the index raises ValueError when the list is on the host and is skipped when it is on the
+        device); neither: every live document (the document frequency of all columns in one pass).  Deleted documents never count.
+        rows_per_chunk: 0 = automatic, else a multiple of 64 (a tuning knob: the result does not depend on it)."""
+        import torch
+        if filter is not None and ids is not None:
+            raise ValueError("the set is given by `filter` or by `ids`, not both")
+        if isinstance(rows_per_chunk, bool) or not isinstance(rows_per_chunk, (int, np.integer)) or rows_per_chunk < 0 or rows_per_chunk % 64:
+            raise ValueError(f"rows_per_chunk must be 0 (automatic) or a positive multiple of 64, got {rows_per_chunk!r}")
+        if ids is not None:
+            ids = _term_ids(ids)
+            nat.require_device()
+            dev = torch.device("cuda", self.device)
+            if _is_torch(ids) and ids.is_cuda:
+                t = ids.to(dev)
+                rows_ok = t.stride(1) == 1 and t.stride(0) >= t.shape[1]       # (a column slice of a wider hit list is read in place)
+                return TermCounts(*self._term_counts_ids_call(t if rows_ok else t.contiguous(), 0, True))
+            h = np.ascontiguousarray(_host(ids))                        # a host list: checked by the library before it is staged
+            B, m, V = h.shape[0], h.shape[1], self._n_cols()
+            counts, total = np.empty((B, V), dtype=np.int64), np.empty(B, dtype=np.int64)
+            nat.check(nat.lib().vs_index_term_counts_ids(self._h, _ptr(h), B, m, m, 0, 1, _ptr(counts), V, _ptr(total), None))
+            return TermCounts(torch.from_numpy(counts).to(dev), torch.from_numpy(total).to(dev))
+        nat.require_device()
+        f = None
+        if filter is not None:
+            from .doc_filter import as_doc_filter
+            f = as_doc_filter(filter, self.n_rows, device=self.device)
+        return TermCounts(*self._term_counts_call(f, 0, int(rows_per_chunk)))
+
+    def top_terms(self, filter=None, ids=None, topn: int = 20, method: str = "jlh", min_count: int = 1, background=None) -> TopTerms:
+        """term_counts of the set, then per query its `topn` most significant columns against a background (vs_term_topn; see
+        ``term_topn``): method "jlh" | "lift", or "count" -- the columns most documents of the set have, ordered by the exact integers
+        (vs_facet_topn; scores are the counts, bg is 0 unless a background is given).  background: a TermCounts with one row (e.g. a kept
+        ``term_counts()``); None counts every live document in this call.  topn in 1..1024."""
+        return _top_terms(self, filter, ids, topn, method, min_count, background)
+
     def scores(self, q):
         """Dense [B, n_rows] fp32 score matrix (what index.py:91 materialises). numpy out."""
         info = self.info()
@@ -1806,6 +1986,45 @@ class ShardGroup:
         counts, total, other = self._facets(labels, n_labels, filter, 0)
         top_l, top_c = facet_topn(counts, topn, min_count, device=self.device)
         return TopFacets(*_facet_out(labels, top_l, top_c, total, other))
+
+    # ---- term aggregations ------------------------------------------------------------------------------------------------------------------
+    def term_counts(self, filter=None, ids=None, rows_per_chunk: int = 0) -> TermCounts:
+        """DeviceIndex.term_counts over the group's rows: filter and ids are global.  Every shard counts on its own GPU -- its bit range of
+        the filter, or the ids with its first row as the id offset (ids it does not own are skipped) -- and counts and total are summed on
+        the first shard's GPU.  Equal to the unsharded index exactly.  An id outside the group raises ValueError (host lists)."""
+        import torch
+        if filter is not None and ids is not None:
+            raise ValueError("the set is given by `filter` or by `ids`, not both")
+        if isinstance(rows_per_chunk, bool) or not isinstance(rows_per_chunk, (int, np.integer)) or rows_per_chunk < 0 or rows_per_chunk % 64:
+            raise ValueError(f"rows_per_chunk must be 0 (automatic) or a positive multiple of 64, got {rows_per_chunk!r}")
+        n_total = self.n_rows
+        dev0 = torch.device("cuda", self.device)
+        f = t = None
+        if ids is not None:
+            ids = _term_ids(ids)
+            on_dev = _is_torch(ids) and ids.is_cuda
+            t = ids if _is_torch(ids) else torch.from_numpy(np.ascontiguousarray(ids))
+            if not on_dev and t.numel() and (int(t.min()) < -1 or int(t.max()) >= n_total):
+                raise ValueError(f"an id lies outside [-1, {n_total})")
+        nat.require_device()
+        if filter is not None:
+            from .doc_filter import as_doc_filter
+            f = as_doc_filter(filter, n_total, device=dev0)
+        out, row0 = None, 0
+        for sh in self._shards:
+            sdev = torch.device("cuda", sh.device)
+            if t is not None:
+                part = sh._term_counts_ids_call(t.to(sdev).contiguous(), row0, False)
+            else:
+                part = sh._term_counts_call(f.to(sdev) if f is not None else None, row0, int(rows_per_chunk))   # its rows: bits [row0, row0 + n)
+            part = tuple(x.to(dev0) for x in part)
+            out = part if out is None else tuple(a + b for a, b in zip(out, part))
+            row0 += sh.n_rows
+        return TermCounts(*out)
+
+    def top_terms(self, filter=None, ids=None, topn: int = 20, method: str = "jlh", min_count: int = 1, background=None) -> TopTerms:
+        """DeviceIndex.top_terms over the group's rows: the top-n is taken after the shards' counts are summed, never per shard."""
+        return _top_terms(self, filter, ids, topn, method, min_count, background)
 
     def close(self):
         if self._h:

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from ... import _native as nat
-from ...device_index import DeviceIndex, DiverseResults, Explanation, FacetCounts, FusedResults, GroupedResults, TopFacets, fuse_topk, _fuse_args, MAX_FUSE_DEPTH, MAX_FUSE_ENTRIES, _topn_args, NotBinaryError, RangeResults, ShardGroup, _diverse_args, _range_args, _grouped_args, _by_example_args, _explain_args, _int64_ids, _k_a_args, resparsify, topk_exclude
+from ...device_index import DeviceIndex, DiverseResults, Explanation, FacetCounts, FusedResults, GroupedResults, TermCounts, TopFacets, TopTerms, _term_topn_args, fuse_topk, _fuse_args, MAX_FUSE_DEPTH, MAX_FUSE_ENTRIES, _topn_args, NotBinaryError, RangeResults, ShardGroup, _diverse_args, _range_args, _grouped_args, _by_example_args, _explain_args, _int64_ids, _k_a_args, resparsify, topk_exclude
 
 logger = logging.getLogger(__name__)
 
@@ -627,6 +627,48 @@ class Index:
         if topn is None:
             return FacetCounts(*(self._to_api(t) for t in target.facet_counts(codes, n_labels, filter=filter)))
         return TopFacets(*(self._to_api(t) for t in target.top_facets(codes, n_labels, topn, filter=filter, min_count=min_count)))
+
+    # ---- term aggregations (not in the reference: what a document set is about, in the vocabulary's own columns) --------------------------
+    def _term_set(self, q_embs, min_score, filter, ids):
+        """the set of a term aggregation -> (search target, filter, ids), argument errors before any device work"""
+        if (q_embs is None) != (min_score is None):
+            raise ValueError("q_embs and min_score go together: the set is match_filter(q_embs, min_score, filter), the filter alone, or ids")
+        if ids is not None and (q_embs is not None or filter is not None):
+            raise ValueError("ids name the set themselves: give them without q_embs / min_score / filter")
+        if ids is not None:
+            ids = self._example_ids(ids, 2)
+        target, gpu_ord = self._explain_target()
+        if q_embs is not None:
+            filter = self.match_filter(q_embs, min_score, filter=filter)
+        if ids is not None:
+            ids = ids.to(torch.device("cuda", gpu_ord)).contiguous()
+        return target, filter, ids
+
+    def term_counts(self, q_embs=None, min_score=None, filter=None, ids=None) -> TermCounts:
+        """For a document set, how many of its documents have each vocabulary column -> TermCounts(counts [B, V], total [B]), int64; columns
+        in the vector's space (no shift).  The set: with q_embs and min_score, per query the documents ``match_filter(q_embs, min_score,
+        filter)`` matches; `filter` alone (as in ``search``); or `ids`, int64 [B, m] hit lists (``search(...).ids``; -1 is skipped, an id
+        listed twice counts twice, an id outside [-1, N) raises IndexError).  None of them: every live document -- the document frequency
+        of the whole vocabulary in one pass.  Deleted documents never count.  Works on a row-sharded index as well (not on the
+        one-process-per-GPU path of ``vsearch_amd.distributed``, and not on a dense index)."""
+        target, filter, ids = self._term_set(q_embs, min_score, filter, ids)
+        return TermCounts(*(self._to_api(t) for t in target.term_counts(filter=filter, ids=ids)))
+
+    def significant_terms(self, q_embs=None, min_score=None, filter=None, ids=None, topn: int = 20, method: str = "jlh", min_count: int = 1,
+                          background=None) -> TopTerms:
+        """The columns over-represented in a document set (``term_counts``'s set) against a background -> TopTerms(cols [B, topn], scores
+        [B, topn], df [B, topn], bg [B, topn], total [B]); cols in the index file's column space (+ ``shift``), as ``explain`` reports
+        them.  With fgp = df / total and bgp = bg / background total: method "jlh" scores (fgp - bgp) * (fgp / bgp) over the columns with
+        fgp > bgp, "lift" fgp / bgp, "count" lists the columns most documents of the set have (exact integer order).  Only columns at
+        least max(min_count, 1) documents of the set have; score descending, then column ascending; unused slots -1 / -inf / 0 / 0.
+        background=None counts every live document in the same call (one more pass; nothing is cached, so it is never stale); a caller
+        who wants to pay once passes ``background=index.term_counts()``."""
+        _term_topn_args(topn, method, min_count)
+        target, filter, ids = self._term_set(q_embs, min_score, filter, ids)
+        top = target.top_terms(filter=filter, ids=ids, topn=int(topn), method=method, min_count=int(min_count), background=background)
+        shift = int(getattr(self, "shift", 0) or 0)
+        cols = torch.where(top.cols >= 0, top.cols + shift, top.cols) if shift else top.cols
+        return TopTerms(*(self._to_api(t) for t in (cols, top.scores, top.df, top.bg, top.total)))
 
     def _added_facets(self, facets, n_add):
         """facets= of add() / update() -> {name: int32 CPU codes [n_add]}, or None for an index without facet fields.  Raises before

@@ -147,6 +147,45 @@ class Retriever(BiEncoder):
         facets = [[(names[l] if names is not None else l, c) for l, c in zip(ls, cs) if l >= 0] for ls, cs in zip(labels, counts)]
         return facets, totals
 
+    def significant_terms(self, queries: Union[List[str], np.ndarray, T], min_score=None, k: int = None, topn: int = 20, method: str = "jlh",
+                          min_count: int = 1, background=None, dropout: float = 0, a: int = None, index: Index = None, batch_size: int = 32,
+                          filter=None, must=None, must_not=None, should=None, min_should: int = None):
+        """What each query's results are about -- ``Index.significant_terms`` behind the query encoder: the vocabulary tokens
+        over-represented in the result set against the whole index.  Exactly one of `min_score` (the set is every document scoring at
+        least it, as in ``retrieve_range``) and `k` (the set is ``retrieve``'s top k hits) must be given.  -> per query the list of
+        (token, score, df, bg), most significant first: df documents of the set and bg documents of the background have the token.
+        `method`, `min_count`, `background` as in ``Index.significant_terms``; `filter` and the term constraints as in ``retrieve_facets``."""
+        if (min_score is None) == (k is None):
+            raise ValueError("exactly one of min_score (the match set) and k (the top-k hits) must be given")
+        if method not in ("jlh", "lift", "count"):
+            raise ValueError(f'method must be "jlh", "lift" or "count", got {method!r}')
+        index = index or self.index
+        if index is None:
+            raise RuntimeError("no index: call build_index / load_index first")
+        if must is not None or must_not is not None or should is not None or min_should is not None:
+            terms = self.term_filter(must=must, must_not=must_not, should=should, min_should=min_should, index=index)
+            if filter is not None:
+                from ...doc_filter import as_doc_filter
+                filter = as_doc_filter(filter, terms.n_rows, device=terms.device) & terms
+            else:
+                filter = terms
+        a = a or self.encoder_q.config.topk
+        q_emb = self.process_query(queries, dropout, a, batch_size=batch_size)
+        if k is not None:
+            hits = index.search(q_emb, k=k, filter=filter) if filter is not None else index.search(q_emb, k=k)
+            top = index.significant_terms(ids=hits.ids, topn=topn, method=method, min_count=min_count, background=background)
+        else:
+            top = index.significant_terms(q_emb, min_score, filter=filter, topn=topn, method=method, min_count=min_count, background=background)
+        shift = int(self.encoder_p.config.shift_vocab_num)
+        tok = self.encoder_p.tokenizer
+        cols, scores, df, bg = (t.cpu().numpy() for t in (top.cols, top.scores, top.df, top.bg))
+        out = []
+        for b in range(cols.shape[0]):
+            live = cols[b] >= 0
+            names = tok.convert_ids_to_tokens([int(x) + shift for x in cols[b][live]])
+            out.append([(name, float(s), int(d), int(g)) for name, s, d, g in zip(names, scores[b][live], df[b][live], bg[b][live])])
+        return out
+
     def retrieve_diverse(self, queries: Union[List[str], np.ndarray, T], k: int = 5, lam: float = 0.5, depth: int = None, sim: str = "cosine",
                          dropout: float = 0, a: int = None, index: Index = None, batch_size: int = 32, filter=None, must=None, must_not=None,
                          should=None, min_should: int = None) -> DiverseResults:
