@@ -300,7 +300,7 @@ VS_API int vs_facet_topn(const int64_t* counts, int64_t ld_counts, int32_t B, in
  * n or method out of range, chunks x B beyond 2^31 - 1 work items: VS_EINVAL -- checked before the device is touched (without a GPU a bad argument is VS_EINVAL, a good one
  * VS_ENODEVICE).  Pointers: all host (staged; the call blocks), or all device pointers on the index's device / `device` (VS_EINVAL for a mix);
  * device pointers and a non-NULL stream only enqueue.  A dense index on the matrix cores keeps no packets: VS_EUNSUPPORTED.
- * Not covered: weight sums or centroids per column (a 64-bit image of the vocabulary does not fit the LDS: it needs column tiles); the dense
+ * Weight sums and centroids per column: vs_index_term_sums below (column tiles of 64-bit bins).  Not covered: the dense
  * matrix kind; a shard group has no entry point of its own (every shard counts its bit range of the bitmap, or the ids with strict = 0 and its
  * id_offset; counts and total are summed, and the top-n taken after the sum) and the one-process-per-GPU RCCL path has none; a cached
  * background; scores that need a logarithm (PMI, tf-idf): they would not be bit-reproducible.                                               */
@@ -317,6 +317,67 @@ VS_API int vs_index_term_counts_ids(vs_index* index, const int64_t* ids, int32_t
 VS_API int vs_term_topn(const int64_t* counts, int64_t ld_counts, const int64_t* total, int32_t B, int32_t n_cols, const int64_t* bg,
                         int64_t bg_total, int method, int32_t n, int64_t min_count, int32_t* out_cols, float* out_score, int64_t* out_fg,
                         int64_t* out_bg, int device, void* stream);
+
+/* ---- term sums: how much weight a document set puts on each column -- its centroid in vocabulary space (no reference counterpart) ----------------
+ * For any set of rows of a CSR-packet index: the sum of the stored values of each vocabulary column over the set (vs_index_term_sums,
+ * vs_index_term_sums_ids), and the columns with the largest mean weight (vs_term_sum_topn).  Integers throughout, so that a sum spread over many
+ * workgroups does not depend on the order of its additions and every result compares exactly.
+ * Per cell: a stored cell of value v (fp16 widened exactly; a binary index stores 1) contributes
+ *     fx(v) = llrint(double(clamp(v, -2^VS_TERM_FX_CLAMP_LOG2, +2^VS_TERM_FX_CLAMP_LOG2)) * 2^VS_TERM_FX_SHIFT)
+ *   rounded to nearest even; NaN contributes 0; +-inf clamp like any large value.  Every fp16 value, subnormals included, is a multiple of 2^-24:
+ *   fp16 and binary stores are summed exactly, an fp32 value is rounded to 2^-24 absolute.  A cell is at most 2^44 in magnitude, so at least 2^19
+ *   saturated rows fit before an int64 wraps; SUMS WRAP MODULO 2^64 (two's complement, as numpy's int64 does).
+ *   sums [B, ld_sums] int64, ld_sums >= n_cols: sums [b, c] = the sum of fx(v) over the stored cells (r, c) of the rows r of query b's set.  The
+ *   packets' padding column n_cols never contributes; a stored +0.0 or -0.0 contributes 0.  Every element of sums [:, 0 .. n_cols) is written,
+ *   columns [n_cols, ld_sums) are not touched.  total [B] int64: the rows of the set, every element written.  sums * 2^-24 / total is the centroid.
+ * vs_index_term_sums (bitmap driven): row membership is exactly that of vs_index_term_counts -- bit bit0 + r of the bitmap at words + b *
+ *   ld_words stands for row r; ld_words = 0: one shared bitmap, and then B must be 1 (else ld_words >= the (bit0 + n_rows + 31) / 32 words a
+ *   bitmap spans); words == NULL: every row is set (B must be 1); the handle's live bitmap is ANDed in at bit 0 whatever bit0 is (deleted rows
+ *   never contribute); bits at or past bit0 + n_rows are ignored whatever they hold.
+ * vs_index_term_sums_ids (id-list driven): ids [B, ld] int64 with m entries a query (ld >= m), row = id - id_offset.  Id -1 is skipped; a deleted
+ *   row is skipped; AN ID LISTED TWICE COUNTS TWICE; total [b] = the entries counted.  An id outside the index (row outside [0, n_rows)): strict = 1
+ *   -- VS_EINVAL for a host list, the entry is skipped for a device list (device ids are not read on the host); strict = 0 -- skipped silently
+ *   (what a shard passes for ids it does not own).
+ * A 64-bit image of the vocabulary does not fit a CU's LDS, so the columns are cut into tiles: a workgroup owns a chunk of rows (a slice of a
+ * list), one query and one column tile of at most VS_TERM_SUM_TILE_COLS 64-bit bins.  It walks the bitmap as vs_index_term_counts does, streams the
+ * packets of the set rows, and for a cell of column c adds fx(v) to bin c - tile0 when that is inside the tile -- one unsigned compare, which also
+ * drops the padding id; a lane whose 8 column ids all miss the tile does not read the packet's values.  Non-zero bins are added to sums at the end
+ * of the chunk (64-bit atomic adds); only the workgroups of tile 0 add to total.
+ * vs_term_sum_plan: the launch of the two calls for these arguments -- pure host arithmetic, no device needed.  n_rows: the index's rows (for the
+ *   id-list call: the m entries of a query, with per_query = 1 and rows_per_chunk = 0).  tile_cols = 0: automatic -- tiles = ceil(n_cols /
+ *   VS_TERM_SUM_TILE_COLS), tile_cols = ceil(n_cols / tiles) (29 523 columns: two tiles of 14 762); any other value must lie in
+ *   1..VS_TERM_SUM_TILE_COLS and is taken as given, tiles = ceil(n_cols / tile_cols).  rows_per_chunk = 0: automatic (chunks x B x tiles ~ 4
+ *   workgroups a CU, a chunk at least 2048 rows); any other value must be a positive multiple of 64 and is taken as given.  chunks x rows_per_chunk
+ *   >= n_rows > (chunks - 1) x rows_per_chunk.  Work item i: tile i % tiles of query (i / tiles) % B of chunk i / (tiles x B).  Both are tuning
+ *   knobs: THE RESULT NEVER DEPENDS ON THE PLAN.
+ * vs_term_sum_topn: per query the n columns with the largest mean weight, from sums [B, ld_sums] / total [B] and, when counts != NULL, counts
+ *   [B, ld_counts] (vs_index_term_counts of the same set).  Column c is a candidate iff sums [b, c] > 0, total [b] > 0 and (counts == NULL or
+ *   counts [b, c] >= min_count); without counts min_count is not looked at.  In fp64, each operation rounded once (no contraction):
+ *     s = (double(sums [b, c]) * 2^-24) / double(total [b]),  score = float(s).
+ *   Order: score descending, then column ascending -- two columns whose scores round to the same fp32 are ordered by the column.  out_cols int32 /
+ *   out_score fp32 / out_sums int64, all [B, n], every slot written: -1 / -inf / 0 behind the last candidate.  n in 1..VS_TERM_MAX_TOPN, n > n_cols
+ *   is allowed.  One workgroup per query; the order is that of the fp32 score, not of a saturating integer key (sums above 2^32 order correctly).
+ * Errors: NULL handle or outputs, B < 1, rows_per_chunk no multiple of 64, tile_cols outside 0..VS_TERM_SUM_TILE_COLS, B > 1 with ld_words = 0,
+ * ld_words / ld / ld_sums / ld_counts too short, m < 1, n out of range, chunks x B x tiles beyond 2^31 - 1 work items: VS_EINVAL -- checked before
+ * the device is touched (without a GPU a bad argument is VS_EINVAL, a good one VS_ENODEVICE).  Pointers: all host (staged; the call blocks), or all
+ * device pointers on the index's device / `device` (VS_EINVAL for a mix); device pointers and a non-NULL stream only enqueue.  A dense index on the
+ * matrix cores keeps no packets: VS_EUNSUPPORTED.
+ * Not covered: per-entry weights on id lists (fixed point would no longer be exact); the dense matrix kind; a shard group has no entry point of its
+ * own (every shard sums its bit range of the bitmap, or the ids with strict = 0 and its id_offset; sums and total are added -- integers, so the
+ * result is exactly the unsharded one -- and the top-n taken after the sum) and the one-process-per-GPU RCCL path has none; k-means itself; a
+ * combined counts + sums pass.                                                                                                                  */
+#define VS_TERM_FX_SHIFT 24          /* a cell contributes its value times 2^24, rounded to nearest even */
+#define VS_TERM_FX_CLAMP_LOG2 20     /* ... after a clamp to +-2^20 */
+#define VS_TERM_SUM_TILE_COLS 18432  /* columns of a workgroup's tile (144 KiB of 64-bit bins; the rest of the 160 KiB: counters) */
+VS_API int vs_term_sum_plan(int64_t n_rows, int32_t B, int32_t n_cols, int per_query, int64_t rows_per_chunk, int32_t tile_cols,
+                            int32_t* out_tiles, int32_t* out_tile_cols, int64_t* out_chunks, int64_t* out_rows_per_chunk);
+VS_API int vs_index_term_sums(vs_index* index, const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B, int64_t rows_per_chunk,
+                              int32_t tile_cols, int64_t* sums, int64_t ld_sums, int64_t* total, void* stream);
+VS_API int vs_index_term_sums_ids(vs_index* index, const int64_t* ids, int32_t B, int64_t m, int64_t ld, int64_t id_offset, int strict,
+                                  int32_t tile_cols, int64_t* sums, int64_t ld_sums, int64_t* total, void* stream);
+VS_API int vs_term_sum_topn(const int64_t* sums, int64_t ld_sums, const int64_t* total, const int64_t* counts, int64_t ld_counts, int32_t B,
+                            int32_t n_cols, int32_t n, int64_t min_count, int32_t* out_cols, float* out_score, int64_t* out_sums, int device,
+                            void* stream);
 
 /* bool / uint8 mask [B, n] (row stride ld_mask bytes; non-zero = allowed) -> the bitmap words [B, ld_words] vs_index_search_filtered
  * reads (bits past n of a row's last word are 0).  mask and words: host pointers or device pointers on `device` (VS_EINVAL otherwise).  stream as in

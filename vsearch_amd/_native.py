@@ -29,6 +29,8 @@ RANGE_MAX_HITS = 2048
 FACET_LDS_BINS, FACET_MAX_TOPN = 16384, 1024
 # term aggregations (VS_TERM_*): columns of a workgroup's LDS histogram, the most columns vs_term_topn lists, its scoring methods
 TERM_LDS_COLS, TERM_MAX_TOPN, TERM_LIFT, TERM_JLH = 36864, 1024, 0, 1
+# term sums (VS_TERM_FX_*, VS_TERM_SUM_TILE_COLS): a cell adds its value clamped to +-2^20 times 2^24; the columns of a workgroup's tile of 64-bit bins
+TERM_FX_SHIFT, TERM_FX_CLAMP_LOG2, TERM_SUM_TILE_COLS = 24, 20, 18432
 
 
 class VsearchNativeError(RuntimeError):
@@ -73,6 +75,10 @@ _SIGNATURES = {
     "vs_index_term_counts": ([_vp, _vp, _i64, _i64, _i32, _i64, _vp, _i64, _vp, _vp], _int),
     "vs_index_term_counts_ids": ([_vp, _vp, _i32, _i64, _i64, _i64, _int, _vp, _i64, _vp, _vp], _int),
     "vs_term_topn": ([_vp, _i64, _vp, _i32, _i32, _vp, _i64, _int, _i32, _i64, _vp, _vp, _vp, _vp, _int, _vp], _int),
+    "vs_term_sum_plan": ([_i64, _i32, _i32, _int, _i64, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i64)], _int),
+    "vs_index_term_sums": ([_vp, _vp, _i64, _i64, _i32, _i64, _i32, _vp, _i64, _vp, _vp], _int),
+    "vs_index_term_sums_ids": ([_vp, _vp, _i32, _i64, _i64, _i64, _int, _i32, _vp, _i64, _vp, _vp], _int),
+    "vs_term_sum_topn": ([_vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _int, _vp], _int),
     "vs_filter_pack": ([_vp, _i32, _i64, _i64, _vp, _i64, _int, _vp], _int),
     "vs_index_scores": ([_vp, _vp, _int, _i64, _i32, _vp, _vp], _int),
     "vs_index_explain": ([_vp, _vp, _int, _i64, _i32, _vp, _i64, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp], _int),

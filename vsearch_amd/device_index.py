@@ -957,6 +957,117 @@ def _top_terms(obj, filter, ids, topn, method, min_count, background):
     return TopTerms(cols, scores, df, bg, fg.total)
 
 
+# ---- term sums: how much weight a document set puts on each column (vs_index_term_sums, vs_index_term_sums_ids, vs_term_sum_topn) ---------------
+TERM_FX_ONE = 1 << nat.TERM_FX_SHIFT                   # the fixed-point image of the value 1.0
+MAX_TERM_TILE_COLS = nat.TERM_SUM_TILE_COLS
+
+
+class TermSums(NamedTuple):
+    """term_sums: per query the fixed-point weight the set puts on each vocabulary column (sums int64 [B, n_cols]: every stored cell adds its
+    value, clamped to +-2^20, times 2^24, rounded to nearest even) and the size of the set (total int64 [B]).  Integers: the result does
+    not depend on the order of the additions, shards add exactly."""
+    sums: Any
+    total: Any
+
+    def values(self):
+        """the sums as float64 [B, n_cols]: sums * 2^-24"""
+        if _is_torch(self.sums):
+            import torch
+            return self.sums.to(torch.float64) * (1.0 / TERM_FX_ONE)
+        return np.asarray(self.sums).astype(np.float64) * (1.0 / TERM_FX_ONE)
+
+    def mean(self):
+        """the set's centroid, float32 [B, n_cols]: (double(sums) * 2^-24) / double(total) rounded once to fp32 -- the chain of the top-n's
+        score; a query whose set is empty (total = 0) gets an all-zero row"""
+        if _is_torch(self.sums):
+            import torch
+            t = self.total.to(torch.float64).reshape(-1, 1)
+            m = (self.values() / torch.where(t > 0, t, torch.ones_like(t))).to(torch.float32)
+            return torch.where(t > 0, m, torch.zeros_like(m))
+        t = np.asarray(self.total).astype(np.float64).reshape(-1, 1)
+        m = (self.values() / np.where(t > 0, t, 1.0)).astype(np.float32)
+        return np.where(t > 0, m, np.float32(0))
+
+
+class TopWeights(NamedTuple):
+    """top_weight_terms / centroid_terms: per query the `topn` columns with the largest mean weight over the set (cols int32 [B, topn],
+    scores float32 [B, topn] = the mean weight), their fixed-point sums (sums int64 [B, topn]) and the size of the set (total int64
+    [B]).  Unused slots: col -1 / score -inf / sum 0."""
+    cols: Any
+    scores: Any
+    sums: Any
+    total: Any
+
+
+def term_sum_plan(n_rows: int, B: int, n_cols: int, per_query: bool, rows_per_chunk: int = 0, tile_cols: int = 0):
+    """The launch vs_index_term_sums takes for these arguments (vs_term_sum_plan; pure host arithmetic, no GPU needed) -> (tiles, tile_cols,
+    chunks, rows_per_chunk): the columns are cut into `tiles` tiles of `tile_cols`, a workgroup owns one tile of one query's chunk."""
+    tiles, tc, chunks, rpc = C.c_int32(0), C.c_int32(0), C.c_int64(0), C.c_int64(0)
+    nat.check(nat.lib().vs_term_sum_plan(int(n_rows), int(B), int(n_cols), 1 if per_query else 0, int(rows_per_chunk), int(tile_cols),
+                                         C.byref(tiles), C.byref(tc), C.byref(chunks), C.byref(rpc)))
+    return tiles.value, tc.value, chunks.value, rpc.value
+
+
+def _term_sum_args(rows_per_chunk, tile_cols):
+    """Argument checks of a term sum's tuning knobs that need no device -> (rows_per_chunk, tile_cols)"""
+    if isinstance(rows_per_chunk, bool) or not isinstance(rows_per_chunk, (int, np.integer)) or rows_per_chunk < 0 or rows_per_chunk % 64:
+        raise ValueError(f"rows_per_chunk must be 0 (automatic) or a positive multiple of 64, got {rows_per_chunk!r}")
+    if isinstance(tile_cols, bool) or not isinstance(tile_cols, (int, np.integer)) or not 0 <= tile_cols <= MAX_TERM_TILE_COLS:
+        raise ValueError(f"tile_cols must be 0 (automatic) or in 1..{MAX_TERM_TILE_COLS}, got {tile_cols!r}")
+    return int(rows_per_chunk), int(tile_cols)
+
+
+def _weight_topn_args(topn, min_count):
+    """Argument checks of a weight top-n that need no device -> (topn, min_count)"""
+    for name, v in (("topn", topn), ("min_count", min_count)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise TypeError(f"{name} must be an int, got {type(v).__name__}")
+    if not 1 <= int(topn) <= MAX_TERM_TOPN:
+        raise ValueError(f"topn must be in 1..{MAX_TERM_TOPN}, got {int(topn)}")
+    return int(topn), int(min_count)
+
+
+def term_sum_topn(sums, total, topn: int = 20, counts=None, min_count: int = 0, device: int = 0):
+    """Per query the `topn` columns with the largest mean weight, from sums [B, n_cols] / total [B] (vs_term_sum_topn) -> (cols int32, scores
+    float32, sums int64), all [B, topn].  A candidate has sum > 0 and, when `counts` [B, n_cols] (``term_counts`` of the same set) is
+    given, counts >= min_count.  score = float32((double(sum) * 2^-24) / double(total)); score descending, then column ascending; unused
+    slots -1 / -inf / 0.  numpy in -> numpy out; torch CUDA in -> tensors on `device`, enqueued on torch's current stream."""
+    topn, min_count = _weight_topn_args(topn, min_count)
+    if not hasattr(sums, "shape") or sums.ndim != 2:
+        raise ValueError("sums must be [B, n_cols]")
+    B, V = int(sums.shape[0]), int(sums.shape[1])
+    if tuple(total.shape) != (B,):
+        raise ValueError(f"total must be [{B}], got {tuple(total.shape)}")
+    if counts is not None and tuple(counts.shape) != (B, V):
+        raise ValueError(f"counts must be [{B}, {V}] as sums, got {tuple(counts.shape)}")
+    nat.require_device()
+    if _is_torch(sums) and sums.is_cuda:
+        import torch
+        dev = sums.device
+        s, t = (x.to(dev).to(torch.int64).contiguous() for x in (sums, total))
+        c = counts.to(dev).to(torch.int64).contiguous() if counts is not None else None
+        outs = (torch.empty((B, topn), dtype=torch.int32, device=dev), torch.empty((B, topn), dtype=torch.float32, device=dev),
+                torch.empty((B, topn), dtype=torch.int64, device=dev))
+        nat.check(nat.lib().vs_term_sum_topn(_ptr(s), V, _ptr(t), _ptr(c) if c is not None else None, V, B, V, topn, min_count,
+                                             *(_ptr(o) for o in outs), int(device), current_stream(int(device))))
+        return outs
+    s, t = (np.ascontiguousarray(_host(x), dtype=np.int64) for x in (sums, total))
+    c = np.ascontiguousarray(_host(counts), dtype=np.int64) if counts is not None else None
+    outs = (np.empty((B, topn), dtype=np.int32), np.empty((B, topn), dtype=np.float32), np.empty((B, topn), dtype=np.int64))
+    nat.check(nat.lib().vs_term_sum_topn(_ptr(s), V, _ptr(t), _ptr(c) if c is not None else None, V, B, V, topn, min_count,
+                                         *(_ptr(o) for o in outs), int(device), None))
+    return outs
+
+
+def _top_weights(obj, filter, ids, topn, min_count):
+    """term_sums of the set (and its term_counts when min_count asks for them), then the top-n on the object's first GPU"""
+    topn, min_count = _weight_topn_args(topn, min_count)
+    res = obj.term_sums(filter=filter, ids=ids)
+    counts = obj.term_counts(filter=filter, ids=ids).counts if min_count > 0 else None
+    cols, scores, sums = term_sum_topn(res.sums, res.total, topn, counts=counts, min_count=min_count, device=obj.device)
+    return TopWeights(cols, scores, sums, res.total)
+
+
 def _host(x):
     return x.detach().numpy() if _is_torch(x) else x
 
@@ -1708,6 +1819,68 @@ class DeviceIndex:
         ``term_counts()``); None counts every live document in this call.  topn in 1..1024."""
         return _top_terms(self, filter, ids, topn, method, min_count, background)
 
+    # ---- term sums: the weight a document set puts on each column (vs_index_term_sums, vs_index_term_sums_ids) ----------------------------------
+    def _term_sums_call(self, f, bit0, rows_per_chunk, tile_cols):
+        """One vs_index_term_sums call on device buffers and torch's current stream -> (sums [B, V], total [B]) int64 CUDA tensors.
+        f: None or a DocFilter on this index's device, read from bit `bit0` on."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        B, V = (f.n_queries if (f is not None and f.per_query) else 1), self._n_cols()
+        sums = torch.empty((B, V), dtype=torch.int64, device=dev)
+        total = torch.empty(B, dtype=torch.int64, device=dev)
+        nat.check(nat.lib().vs_index_term_sums(self._h, _ptr(f.words) if f is not None else None, int(bit0), f.ld if f is not None else 0, B,
+                                               int(rows_per_chunk), int(tile_cols), _ptr(sums), V, _ptr(total), current_stream(self.device)))
+        return sums, total
+
+    def _term_sums_ids_call(self, ids_dev, id_offset, strict, tile_cols):
+        """One vs_index_term_sums_ids call: ids_dev int64 CUDA tensor [B, m] on this index's device"""
+        import torch
+        B, m, V = int(ids_dev.shape[0]), int(ids_dev.shape[1]), self._n_cols()
+        sums = torch.empty((B, V), dtype=torch.int64, device=ids_dev.device)
+        total = torch.empty(B, dtype=torch.int64, device=ids_dev.device)
+        nat.check(nat.lib().vs_index_term_sums_ids(self._h, _ptr(ids_dev), B, m, int(ids_dev.stride(0)), int(id_offset), 1 if strict else 0,
+                                                   int(tile_cols), _ptr(sums), V, _ptr(total), current_stream(self.device)))
+        return sums, total
+
+    def term_sums(self, filter=None, ids=None, rows_per_chunk: int = 0, tile_cols: int = 0) -> TermSums:
+        """For a document set, how much weight it puts on each vocabulary column -> TermSums(sums [B, V], total [B]), int64 tensors on the
+        index's device, enqueued on torch's current stream.  sums are fixed point: every stored cell adds its value (clamped to +-2^20)
+        times 2^24, rounded to nearest even -- exact for fp16 and binary stores, and independent of the order of the additions;
+        ``.values()`` gives them as float64, ``.mean()`` the set's centroid as float32.  The set is ``term_counts``'s: `filter`, or `ids`
+        (int64 [B, m] hit lists: -1 is skipped, an id listed twice counts twice, an id outside the index raises ValueError when the list is
+        on the host and is skipped when it is on the device), or neither: every live document.  Deleted documents never contribute.
+        rows_per_chunk: 0 = automatic, else a multiple of 64; tile_cols: 0 = automatic, else the columns of a workgroup's tile, at most
+        18 432 (tuning knobs: the result does not depend on them)."""
+        import torch
+        if filter is not None and ids is not None:
+            raise ValueError("the set is given by `filter` or by `ids`, not both")
+        rows_per_chunk, tile_cols = _term_sum_args(rows_per_chunk, tile_cols)
+        if ids is not None:
+            ids = _term_ids(ids)
+            nat.require_device()
+            dev = torch.device("cuda", self.device)
+            if _is_torch(ids) and ids.is_cuda:
+                t = ids.to(dev)
+                rows_ok = t.stride(1) == 1 and t.stride(0) >= t.shape[1]       # (a column slice of a wider hit list is read in place)
+                return TermSums(*self._term_sums_ids_call(t if rows_ok else t.contiguous(), 0, True, tile_cols))
+            h = np.ascontiguousarray(_host(ids))                        # a host list: checked by the library before it is staged
+            B, m, V = h.shape[0], h.shape[1], self._n_cols()
+            sums, total = np.empty((B, V), dtype=np.int64), np.empty(B, dtype=np.int64)
+            nat.check(nat.lib().vs_index_term_sums_ids(self._h, _ptr(h), B, m, m, 0, 1, tile_cols, _ptr(sums), V, _ptr(total), None))
+            return TermSums(torch.from_numpy(sums).to(dev), torch.from_numpy(total).to(dev))
+        nat.require_device()
+        f = None
+        if filter is not None:
+            from .doc_filter import as_doc_filter
+            f = as_doc_filter(filter, self.n_rows, device=self.device)
+        return TermSums(*self._term_sums_call(f, 0, rows_per_chunk, tile_cols))
+
+    def top_weight_terms(self, filter=None, ids=None, topn: int = 20, min_count: int = 0) -> TopWeights:
+        """term_sums of the set, then per query the `topn` columns with the largest mean weight (vs_term_sum_topn; see ``term_sum_topn``):
+        only columns with a positive sum; min_count > 0 also takes ``term_counts`` of the set and lists only columns at least min_count of
+        its documents have.  topn in 1..1024."""
+        return _top_weights(self, filter, ids, topn, min_count)
+
     def scores(self, q):
         """Dense [B, n_rows] fp32 score matrix (what index.py:91 materialises). numpy out."""
         info = self.info()
@@ -2025,6 +2198,44 @@ class ShardGroup:
     def top_terms(self, filter=None, ids=None, topn: int = 20, method: str = "jlh", min_count: int = 1, background=None) -> TopTerms:
         """DeviceIndex.top_terms over the group's rows: the top-n is taken after the shards' counts are summed, never per shard."""
         return _top_terms(self, filter, ids, topn, method, min_count, background)
+
+    def term_sums(self, filter=None, ids=None, rows_per_chunk: int = 0, tile_cols: int = 0) -> TermSums:
+        """DeviceIndex.term_sums over the group's rows: filter and ids are global.  Every shard sums on its own GPU -- its bit range of the
+        filter, or the ids with its first row as the id offset (ids it does not own are skipped) -- and sums and total are added on the
+        first shard's GPU.  The additions are integer: equal to the unsharded index exactly.  An id outside the group raises ValueError
+        (host lists)."""
+        import torch
+        if filter is not None and ids is not None:
+            raise ValueError("the set is given by `filter` or by `ids`, not both")
+        rows_per_chunk, tile_cols = _term_sum_args(rows_per_chunk, tile_cols)
+        n_total = self.n_rows
+        dev0 = torch.device("cuda", self.device)
+        f = t = None
+        if ids is not None:
+            ids = _term_ids(ids)
+            on_dev = _is_torch(ids) and ids.is_cuda
+            t = ids if _is_torch(ids) else torch.from_numpy(np.ascontiguousarray(ids))
+            if not on_dev and t.numel() and (int(t.min()) < -1 or int(t.max()) >= n_total):
+                raise ValueError(f"an id lies outside [-1, {n_total})")
+        nat.require_device()
+        if filter is not None:
+            from .doc_filter import as_doc_filter
+            f = as_doc_filter(filter, n_total, device=dev0)
+        out, row0 = None, 0
+        for sh in self._shards:
+            sdev = torch.device("cuda", sh.device)
+            if t is not None:
+                part = sh._term_sums_ids_call(t.to(sdev).contiguous(), row0, False, tile_cols)
+            else:
+                part = sh._term_sums_call(f.to(sdev) if f is not None else None, row0, rows_per_chunk, tile_cols)   # its rows: bits [row0, row0 + n)
+            part = tuple(x.to(dev0) for x in part)
+            out = part if out is None else tuple(a + b for a, b in zip(out, part))
+            row0 += sh.n_rows
+        return TermSums(*out)
+
+    def top_weight_terms(self, filter=None, ids=None, topn: int = 20, min_count: int = 0) -> TopWeights:
+        """DeviceIndex.top_weight_terms over the group's rows: the top-n is taken after the shards' sums are added, never per shard."""
+        return _top_weights(self, filter, ids, topn, min_count)
 
     def close(self):
         if self._h:

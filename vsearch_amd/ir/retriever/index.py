@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from ... import _native as nat
-from ...device_index import DeviceIndex, DiverseResults, Explanation, FacetCounts, FusedResults, GroupedResults, TermCounts, TopFacets, TopTerms, _term_topn_args, fuse_topk, _fuse_args, MAX_FUSE_DEPTH, MAX_FUSE_ENTRIES, _topn_args, NotBinaryError, RangeResults, ShardGroup, _diverse_args, _range_args, _grouped_args, _by_example_args, _explain_args, _int64_ids, _k_a_args, resparsify, topk_exclude
+from ...device_index import DeviceIndex, DiverseResults, Explanation, FacetCounts, FusedResults, GroupedResults, TermCounts, TermSums, TopFacets, TopTerms, TopWeights, _term_topn_args, _weight_topn_args, fuse_topk, _fuse_args, MAX_FUSE_DEPTH, MAX_FUSE_ENTRIES, _topn_args, NotBinaryError, RangeResults, ShardGroup, _diverse_args, _range_args, _grouped_args, _by_example_args, _explain_args, _int64_ids, _k_a_args, resparsify, topk_exclude
 
 logger = logging.getLogger(__name__)
 
@@ -669,6 +669,34 @@ class Index:
         shift = int(getattr(self, "shift", 0) or 0)
         cols = torch.where(top.cols >= 0, top.cols + shift, top.cols) if shift else top.cols
         return TopTerms(*(self._to_api(t) for t in (cols, top.scores, top.df, top.bg, top.total)))
+
+    def term_sums(self, q_embs=None, min_score=None, filter=None, ids=None) -> TermSums:
+        """For a document set (``term_counts``'s: q_embs + min_score, `filter`, `ids`, or every live document), how much weight it puts on
+        each vocabulary column -> TermSums(sums [B, V], total [B]), int64; columns in the vector's space (no shift).  sums are fixed
+        point -- every stored value (clamped to +-2^20) times 2^24, rounded to nearest even, added as integers: exact for an fp16 or a
+        binary index, the same whatever the order and however the index is sharded.  ``.values()`` gives float64 sums, ``.mean()`` the
+        centroid.  Deleted documents never contribute.  Not on the one-process-per-GPU path of ``vsearch_amd.distributed``, not on a
+        dense index."""
+        target, filter, ids = self._term_set(q_embs, min_score, filter, ids)
+        return TermSums(*(self._to_api(t) for t in target.term_sums(filter=filter, ids=ids)))
+
+    def centroid(self, q_embs=None, min_score=None, filter=None, ids=None) -> torch.Tensor:
+        """The mean vector of a document set (``term_sums``'s set) -> float32 [B, V] in the vector's space: a query like any other,
+        ``index.search(index.centroid(filter=f), k)``.  A query whose set is empty gets an all-zero row."""
+        return self.term_sums(q_embs, min_score, filter=filter, ids=ids).mean()
+
+    def centroid_terms(self, q_embs=None, min_score=None, filter=None, ids=None, topn: int = 20, min_count: int = 0) -> TopWeights:
+        """The columns a document set (``term_sums``'s set) puts the most weight on -> TopWeights(cols [B, topn], scores [B, topn], sums
+        [B, topn], total [B]); cols in the index file's column space (+ ``shift``), as ``explain`` reports them.  score = the column's mean
+        weight over the set, float32((double(sum) * 2^-24) / double(total)); only columns with a positive sum; score descending, then
+        column ascending; unused slots -1 / -inf / 0.  min_count > 0 takes ``term_counts`` of the same set as well and lists only columns
+        at least min_count of its documents have."""
+        _weight_topn_args(topn, min_count)
+        target, filter, ids = self._term_set(q_embs, min_score, filter, ids)
+        top = target.top_weight_terms(filter=filter, ids=ids, topn=int(topn), min_count=int(min_count))
+        shift = int(getattr(self, "shift", 0) or 0)
+        cols = torch.where(top.cols >= 0, top.cols + shift, top.cols) if shift else top.cols
+        return TopWeights(*(self._to_api(t) for t in (cols, top.scores, top.sums, top.total)))
 
     def _added_facets(self, facets, n_add):
         """facets= of add() / update() -> {name: int32 CPU codes [n_add]}, or None for an index without facet fields.  Raises before

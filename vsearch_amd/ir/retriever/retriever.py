@@ -186,6 +186,43 @@ class Retriever(BiEncoder):
             out.append([(name, float(s), int(d), int(g)) for name, s, d, g in zip(names, scores[b][live], df[b][live], bg[b][live])])
         return out
 
+    def centroid_terms(self, queries: Union[List[str], np.ndarray, T], min_score=None, k: int = None, topn: int = 20, min_count: int = 0,
+                       dropout: float = 0, a: int = None, index: Index = None, batch_size: int = 32, filter=None, must=None, must_not=None,
+                       should=None, min_should: int = None):
+        """What each query's results weigh most -- ``Index.centroid_terms`` behind the query encoder: the vocabulary tokens with the
+        largest mean weight over the result set (its centroid's largest coordinates).  Exactly one of `min_score` (the set is every
+        document scoring at least it, as in ``retrieve_range``) and `k` (the set is ``retrieve``'s top k hits) must be given.  -> per query
+        the list of (token, mean_weight, sum), heaviest first: sum is the fixed-point column sum (weights times 2^24).  `min_count` as in
+        ``Index.centroid_terms``; `filter` and the term constraints as in ``retrieve_facets``."""
+        if (min_score is None) == (k is None):
+            raise ValueError("exactly one of min_score (the match set) and k (the top-k hits) must be given")
+        index = index or self.index
+        if index is None:
+            raise RuntimeError("no index: call build_index / load_index first")
+        if must is not None or must_not is not None or should is not None or min_should is not None:
+            terms = self.term_filter(must=must, must_not=must_not, should=should, min_should=min_should, index=index)
+            if filter is not None:
+                from ...doc_filter import as_doc_filter
+                filter = as_doc_filter(filter, terms.n_rows, device=terms.device) & terms
+            else:
+                filter = terms
+        a = a or self.encoder_q.config.topk
+        q_emb = self.process_query(queries, dropout, a, batch_size=batch_size)
+        if k is not None:
+            hits = index.search(q_emb, k=k, filter=filter) if filter is not None else index.search(q_emb, k=k)
+            top = index.centroid_terms(ids=hits.ids, topn=topn, min_count=min_count)
+        else:
+            top = index.centroid_terms(q_emb, min_score, filter=filter, topn=topn, min_count=min_count)
+        shift = int(self.encoder_p.config.shift_vocab_num)
+        tok = self.encoder_p.tokenizer
+        cols, scores, sums = (t.cpu().numpy() for t in (top.cols, top.scores, top.sums))
+        out = []
+        for b in range(cols.shape[0]):
+            live = cols[b] >= 0
+            names = tok.convert_ids_to_tokens([int(x) + shift for x in cols[b][live]])
+            out.append([(name, float(s), int(d)) for name, s, d in zip(names, scores[b][live], sums[b][live])])
+        return out
+
     def retrieve_diverse(self, queries: Union[List[str], np.ndarray, T], k: int = 5, lam: float = 0.5, depth: int = None, sim: str = "cosine",
                          dropout: float = 0, a: int = None, index: Index = None, batch_size: int = 32, filter=None, must=None, must_not=None,
                          should=None, min_should: int = None) -> DiverseResults:
