@@ -379,6 +379,53 @@ VS_API int vs_term_sum_topn(const int64_t* sums, int64_t ld_sums, const int64_t*
                             int32_t n_cols, int32_t n, int64_t min_count, int32_t* out_cols, float* out_score, int64_t* out_sums, int device,
                             void* stream);
 
+/* ---- clustering: the nearest of K centroids for every row (no reference counterpart: the reference only has topk) ----------------------------
+ * The transposed question of a search: not "the best rows for this query" but "the best of these K queries for every row", without a [K, N]
+ * score matrix.  centroids fp32 [K, ldc] (ldc >= n_cols), c'_j = centroid j rounded to the index dtype as vs_index_search rounds a query (fp16
+ * store: to fp16, nearest even, widened again; fp32 and binary stores: as given).  For a row r with stored cells (col_t, v_t) in STORED order (v =
+ * 1 on a binary index; cells carrying the padding id n_cols are skipped):
+ *     S(j, r)     = the fp64 sum, starting at +0.0, taken in the row's stored cell order, of double(float(c'_j[col_t] * v_t))   (no fma)
+ *     value(j, r) = float(S)  when bias == NULL,  float(S + double(bias[j]))  otherwise;  a NaN value counts -- and is reported -- as -inf
+ *     label(r)    = the lowest j whose value is largest, values compared as floats (-0.0 == +0.0)
+ * The order is fixed -- one lane owns a centroid and adds its products one after the other -- so a plain loop over the cells reproduces the sum bit
+ * for bit; where every product and partial sum is exact, value equals vs_index_explain's score of (centroid label(r), row r).  A row that is deleted
+ * or not allowed by the filter gets label -1 / value -inf; an empty row has S = +0.0 (label 0 without a bias, the argmax of the bias with one).
+ * out_labels int32 [n_rows] and out_values fp32 [n_rows] (may be NULL): slots [0, n_rows) are all written, nothing behind them.
+ * filter: ONE bitmap in the layout of vs_index_search_filtered, read from bit filter_bit0 on (bit filter_bit0 + r = row r: a shard passes the
+ * group's bitmap and its first row); NULL = every live row.  Tombstones are ANDed in at bit 0.
+ *
+ * vs_centroid_half_norms: hn[j] = float(0.5 * T_j) for centroids c fp32 [K, ldc], rounded to fp16 first when round_f16 != 0:
+ *     x[t] = fp64 sum over columns c = t, t + 256, t + 512, ... (ascending) of double(float(c'_j[c] * c'_j[c])),   t in 0..255
+ *     for h = 128, 64, ..., 1:  x[t] += x[t + h] for t < h;   T_j = x[0]
+ * With bias = -hn, the argmax of value is the argmin of ||x_r - c'_j||^2: the assignment step of Lloyd's k-means.
+ *
+ * vs_label_bitmaps: labels int32 [n_rows] and B values -> B bitmaps, bit bit0 + r of row b set iff labels[r] == values[b].  Words [0, (bit0 +
+ * n_rows + 31) / 32) of each row of out_words [B, ld_words] are written whole (bits below bit0 and past the rows: 0).  The per-label filters of a
+ * drill-down, and the K cluster sets vs_index_term_sums takes.  B in 1..VS_LABEL_MAX_VALUES.
+ *
+ * Kernels (assign.hip): a prep kernel transposes and rounds the centroids into a slab Ct [n_cols + 1][Kp] (Kp = K rounded up to the slice width W;
+ * row n_cols -- the padding id -- and slots j >= K are zero; device scratch of slab_bytes, freed before the call returns).  The assign kernel gives
+ * a wave a row: lane l holds packet p0 + l in registers, the cells are broadcast in stored order and every lane loads its W / 64 centroids' weights of
+ * the cell's column -- one coalesced read of W * 4 bytes -- and adds the product to its fp64 accumulators; K > W takes Kp / W slices over the same
+ * registers.  vs_assign_plan is the launch for these arguments -- pure host arithmetic, no device needed: W = 64 (K <= 64), 128 (K <= 128) or 256;
+ * rows_per_chunk = 0: automatic, else a positive multiple of 64 taken as given (a tuning knob: the result does not depend on it).
+ * Errors: NULL handle / centroids / out_labels, K outside 1..VS_ASSIGN_MAX_K, ldc < n_cols, filter_bit0 < 0, rows_per_chunk no multiple of 64,
+ * host centroids or bias that are not finite: VS_EINVAL -- checked before the device is touched.  Pointers: all host (staged; the call blocks) or all
+ * device pointers on the index's device / `device` (VS_EINVAL for a mix); device pointers and a non-NULL stream only enqueue (the slab is freed
+ * behind a stream synchronisation either way).  A dense index on the matrix cores keeps no packets: VS_EUNSUPPORTED.
+ * Not covered: the top-m nearest centroids and soft assignment; the dense matrix kind; a shard group has no entry point of its own (every shard
+ * assigns its rows with its bit range of the filter: a row's value depends on nothing but the row) and the one-process-per-GPU RCCL path has none; a
+ * fused per-label sums kernel (the k-means update goes through vs_label_bitmaps and vs_index_term_sums, 64 clusters a call).                    */
+#define VS_ASSIGN_MAX_K 4096         /* centroids of one vs_index_assign call */
+#define VS_LABEL_MAX_VALUES 4096     /* bitmaps of one vs_label_bitmaps call */
+VS_API int vs_assign_plan(int64_t n_rows, int32_t K, int32_t n_cols, int64_t rows_per_chunk, int32_t* out_slice_w, int32_t* out_slices,
+                          int64_t* out_chunks, int64_t* out_rows_per_chunk, int64_t* out_slab_bytes);
+VS_API int vs_centroid_half_norms(const float* c, int64_t ldc, int32_t K, int32_t n_cols, int round_f16, float* out, int device, void* stream);
+VS_API int vs_index_assign(vs_index* index, const float* centroids, int64_t ldc, int32_t K, const float* bias, const uint32_t* filter,
+                           int64_t filter_bit0, int64_t rows_per_chunk, int32_t* out_labels, float* out_values, void* stream);
+VS_API int vs_label_bitmaps(const int32_t* labels, int64_t n_rows, const int32_t* values, int32_t B, int64_t bit0, uint32_t* out_words,
+                            int64_t ld_words, int device, void* stream);
+
 /* bool / uint8 mask [B, n] (row stride ld_mask bytes; non-zero = allowed) -> the bitmap words [B, ld_words] vs_index_search_filtered
  * reads (bits past n of a row's last word are 0).  mask and words: host pointers or device pointers on `device` (VS_EINVAL otherwise).  stream as in
  * vs_index_search (host buffers block).                                                                                          */

@@ -31,6 +31,8 @@ FACET_LDS_BINS, FACET_MAX_TOPN = 16384, 1024
 TERM_LDS_COLS, TERM_MAX_TOPN, TERM_LIFT, TERM_JLH = 36864, 1024, 0, 1
 # term sums (VS_TERM_FX_*, VS_TERM_SUM_TILE_COLS): a cell adds its value clamped to +-2^20 times 2^24; the columns of a workgroup's tile of 64-bit bins
 TERM_FX_SHIFT, TERM_FX_CLAMP_LOG2, TERM_SUM_TILE_COLS = 24, 20, 18432
+# clustering (VS_ASSIGN_MAX_K, VS_LABEL_MAX_VALUES): the most centroids of vs_index_assign, the most bitmaps of vs_label_bitmaps
+ASSIGN_MAX_K, LABEL_MAX_VALUES = 4096, 4096
 
 
 class VsearchNativeError(RuntimeError):
@@ -79,6 +81,10 @@ _SIGNATURES = {
     "vs_index_term_sums": ([_vp, _vp, _i64, _i64, _i32, _i64, _i32, _vp, _i64, _vp, _vp], _int),
     "vs_index_term_sums_ids": ([_vp, _vp, _i32, _i64, _i64, _i64, _int, _i32, _vp, _i64, _vp, _vp], _int),
     "vs_term_sum_topn": ([_vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _int, _vp], _int),
+    "vs_assign_plan": ([_i64, _i32, _i32, _i64, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)], _int),
+    "vs_centroid_half_norms": ([_vp, _i64, _i32, _i32, _int, _vp, _int, _vp], _int),
+    "vs_index_assign": ([_vp, _vp, _i64, _i32, _vp, _vp, _i64, _i64, _vp, _vp, _vp], _int),
+    "vs_label_bitmaps": ([_vp, _i64, _vp, _i32, _i64, _vp, _i64, _int, _vp], _int),
     "vs_filter_pack": ([_vp, _i32, _i64, _i64, _vp, _i64, _int, _vp], _int),
     "vs_index_scores": ([_vp, _vp, _int, _i64, _i32, _vp, _vp], _int),
     "vs_index_explain": ([_vp, _vp, _int, _i64, _i32, _vp, _i64, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp], _int),

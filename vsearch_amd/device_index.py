@@ -1068,6 +1068,212 @@ def _top_weights(obj, filter, ids, topn, min_count):
     return TopWeights(cols, scores, sums, res.total)
 
 
+# ---- clustering: the nearest of K centroids for every row (vs_assign_plan, vs_index_assign, vs_centroid_half_norms, vs_label_bitmaps) -----------
+MAX_ASSIGN_K = nat.ASSIGN_MAX_K
+MAX_LABEL_VALUES = nat.LABEL_MAX_VALUES
+
+
+class Assignment(NamedTuple):
+    """assign: per row the centroid with the largest value (labels int32 [N]; the lowest index among equals) and that value (values
+    float32 [N]).  A row that is deleted or not allowed by the filter has label -1 / value -inf."""
+    labels: Any
+    values: Any
+
+
+def assign_plan(n_rows: int, K: int, n_cols: int, rows_per_chunk: int = 0):
+    """The launch vs_index_assign takes for these arguments (vs_assign_plan; pure host arithmetic, no GPU needed) -> (slice_w, slices, chunks,
+    rows_per_chunk, slab_bytes): a lane owns slice_w / 64 centroids of each of the `slices` slices, a workgroup a chunk of rows; the
+    transposed centroids take slab_bytes of device scratch."""
+    w, s, chunks, rpc, slab = C.c_int32(0), C.c_int32(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    nat.check(nat.lib().vs_assign_plan(int(n_rows), int(K), int(n_cols), int(rows_per_chunk), C.byref(w), C.byref(s), C.byref(chunks),
+                                       C.byref(rpc), C.byref(slab)))
+    return w.value, s.value, chunks.value, rpc.value, slab.value
+
+
+def _assign_args(centroids, bias, n_cols, rows_per_chunk=0):
+    """Argument checks of an assignment that need no device -> (centroids float32 [K, V] tensor, bias float32 [K] tensor | None,
+    rows_per_chunk).  A tensor on a GPU is not read here: the finiteness of device centroids is the caller's."""
+    import torch
+    if isinstance(rows_per_chunk, bool) or not isinstance(rows_per_chunk, (int, np.integer)) or rows_per_chunk < 0 or rows_per_chunk % 64:
+        raise ValueError(f"rows_per_chunk must be 0 (automatic) or a positive multiple of 64, got {rows_per_chunk!r}")
+    c = centroids if _is_torch(centroids) else torch.from_numpy(np.ascontiguousarray(np.asarray(centroids)))
+    c = c.detach()
+    if c.dim() != 2:
+        raise ValueError(f"centroids must be [K, n_cols], got {c.dim()} dimensions")
+    if not c.is_floating_point():
+        raise TypeError(f"centroids must be floating point, got {c.dtype}")
+    K, V = int(c.shape[0]), int(c.shape[1])
+    if not 1 <= K <= MAX_ASSIGN_K:
+        raise ValueError(f"the number of centroids must be in 1..{MAX_ASSIGN_K}, got {K}")
+    if V != int(n_cols):
+        raise ValueError(f"centroids have {V} columns, the index has {int(n_cols)}")
+    c = c.to(torch.float32)
+    if not c.is_cuda and not bool(torch.isfinite(c).all()):
+        raise ValueError("centroids must be finite")
+    b = None
+    if bias is not None:
+        b = bias if _is_torch(bias) else torch.from_numpy(np.ascontiguousarray(np.asarray(bias)))
+        b = b.detach()
+        if tuple(b.shape) != (K,):
+            raise ValueError(f"bias must be [{K}], got {tuple(b.shape)}")
+        if not b.is_floating_point():
+            raise TypeError(f"bias must be floating point, got {b.dtype}")
+        b = b.to(torch.float32)
+        if not b.is_cuda and not bool(torch.isfinite(b).all()):
+            raise ValueError("bias must be finite")
+    return c, b, int(rows_per_chunk)
+
+
+def centroid_half_norms(centroids, round_f16: bool = False, device: int = 0):
+    """hn[j] = float32(0.5 * ||c'_j||^2) in the fixed order of vs_centroid_half_norms (256 strided fp64 partial sums of the fp32 squares, then a
+    halving tree); round_f16: the centroids are rounded to fp16 first, as an fp16 index rounds them.  With bias = -hn, ``assign`` picks the
+    nearest centroid in the Euclidean sense.  numpy in -> numpy out; torch CUDA in -> a tensor on `device`, on torch's current stream."""
+    if not hasattr(centroids, "shape") or len(centroids.shape) != 2:
+        raise ValueError("centroids must be [K, n_cols]")
+    K, V = int(centroids.shape[0]), int(centroids.shape[1])
+    if not 1 <= K <= MAX_ASSIGN_K:
+        raise ValueError(f"the number of centroids must be in 1..{MAX_ASSIGN_K}, got {K}")
+    nat.require_device()
+    if _is_torch(centroids) and centroids.is_cuda:
+        import torch
+        c = centroids.detach().to(torch.float32).contiguous()
+        out = torch.empty(K, dtype=torch.float32, device=c.device)
+        nat.check(nat.lib().vs_centroid_half_norms(_ptr(c), V, K, V, 1 if round_f16 else 0, _ptr(out), int(device), current_stream(int(device))))
+        return out
+    c = np.ascontiguousarray(_host(centroids), dtype=np.float32)
+    out = np.empty(K, dtype=np.float32)
+    nat.check(nat.lib().vs_centroid_half_norms(_ptr(c), V, K, V, 1 if round_f16 else 0, _ptr(out), int(device), None))
+    return out
+
+
+def _label_values(values):
+    """values of a label-bitmap call -> (int32 ndarray [B], scalar?)"""
+    scalar = isinstance(values, (int, np.integer)) and not isinstance(values, bool)
+    v = np.atleast_1d(np.asarray(_host(values.detach().cpu()) if _is_torch(values) else values))
+    if v.ndim != 1:
+        raise TypeError("values: an int, or a 1-D sequence of ints")
+    if not 1 <= v.shape[0] <= MAX_LABEL_VALUES:
+        raise ValueError(f"the number of values must be in 1..{MAX_LABEL_VALUES}, got {v.shape[0]}")
+    if v.dtype == np.bool_ or not np.issubdtype(v.dtype, np.integer):
+        raise TypeError("values: an int, or a 1-D sequence of ints")
+    if v.size and (int(v.min()) < -0x80000000 or int(v.max()) > 0x7FFFFFFF):
+        raise ValueError("a value does not fit an int32 label")
+    return np.ascontiguousarray(v, dtype=np.int32), scalar
+
+
+def label_bitmaps(labels, values, bit0: int = 0, ld_words=None, device: int = 0):
+    """Per value the bitmap of the rows that carry it (vs_label_bitmaps) -> words int32 [B, ld_words]: bit bit0 + r of row b is set iff
+    labels[r] == values[b]; ld_words defaults to the (bit0 + n_rows + 31) // 32 words a bitmap spans.  labels: int32 [n_rows]; numpy in ->
+    numpy out (words behind the span are zero), torch CUDA in -> a tensor on `device`, on torch's current stream."""
+    vals, _ = _label_values(values)
+    if not hasattr(labels, "shape") or len(labels.shape) != 1 or int(labels.shape[0]) < 1:
+        raise ValueError("labels must be a non-empty 1-D array")
+    n, B = int(labels.shape[0]), int(vals.shape[0])
+    if isinstance(bit0, bool) or not isinstance(bit0, (int, np.integer)) or bit0 < 0:
+        raise ValueError(f"bit0 must be an int >= 0, got {bit0!r}")
+    span = (int(bit0) + n + 31) // 32
+    ld = span if ld_words is None else int(ld_words)
+    if ld < span:
+        raise ValueError(f"ld_words = {ld} is shorter than the {span} words a bitmap spans")
+    nat.require_device()
+    if _is_torch(labels) and labels.is_cuda:
+        import torch
+        l = labels.detach().to(torch.int32).contiguous()
+        v = torch.from_numpy(vals).to(l.device)
+        out = torch.zeros((B, ld), dtype=torch.int32, device=l.device) if ld > span else torch.empty((B, ld), dtype=torch.int32, device=l.device)
+        nat.check(nat.lib().vs_label_bitmaps(_ptr(l), n, _ptr(v), B, int(bit0), _ptr(out), ld, int(device), current_stream(int(device))))
+        return out
+    l = np.ascontiguousarray(_host(labels), dtype=np.int32)
+    out = np.zeros((B, ld), dtype=np.int32)
+    nat.check(nat.lib().vs_label_bitmaps(_ptr(l), n, _ptr(vals), B, int(bit0), _ptr(out), ld, int(device), None))
+    return out
+
+
+KMEANS_UPDATE_BATCH = 64                                 # clusters whose sums one term_sums call of the update takes
+KMEANS_METRICS = ("dot", "l2")
+
+
+class KMeansResult(NamedTuple):
+    """kmeans / cluster: centroids float32 [K, V]; labels int32 [N] and values float32 [N], the assignment UNDER these centroids (-1 / -inf
+    for a deleted or filtered-out document); counts int64 [K], the documents of each cluster; n_iter, the iterations run; changed, per
+    iteration the documents whose label differed from the previous assignment (the first entry: the documents assigned)."""
+    centroids: Any
+    labels: Any
+    values: Any
+    counts: Any
+    n_iter: int
+    changed: list
+
+
+def _kmeans_args(n_clusters, iters, metric, init=None, n_cols=None):
+    """Argument checks of kmeans that need no device -> (K, iters).  init: None, int64 row ids [K] or float32 centroids [K, V]."""
+    for name, v in (("n_clusters", n_clusters), ("iters", iters)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise TypeError(f"{name} must be an int, got {type(v).__name__}")
+    K, iters = int(n_clusters), int(iters)
+    if not 1 <= K <= MAX_ASSIGN_K:
+        raise ValueError(f"n_clusters must be in 1..{MAX_ASSIGN_K}, got {K}")
+    if iters < 0:
+        raise ValueError(f"iters must be >= 0, got {iters}")
+    if metric not in KMEANS_METRICS:
+        raise ValueError(f'metric must be "dot" or "l2", got {metric!r}')
+    if init is not None:
+        if not hasattr(init, "shape") or len(init.shape) not in (1, 2) or int(init.shape[0]) != K:
+            raise ValueError(f"init must be {K} row ids [K] or {K} centroids [K, V]")
+        floating = init.is_floating_point() if _is_torch(init) else np.issubdtype(np.asarray(init).dtype, np.floating)
+        if len(init.shape) == 1 and floating:
+            raise TypeError("init row ids must be integers")
+        if len(init.shape) == 2:
+            if not floating:
+                raise TypeError("init centroids must be floating point")
+            if n_cols is not None and int(init.shape[1]) != int(n_cols):
+                raise ValueError(f"init centroids have {int(init.shape[1])} columns, the index has {int(n_cols)}")
+            on_gpu = _is_torch(init) and init.is_cuda
+            if not on_gpu and not bool(np.isfinite(_host(init) if _is_torch(init) else np.asarray(init)).all()):
+                raise ValueError("init centroids must be finite")
+    return K, iters
+
+
+def kmeans_loop(target, centroids, iters: int, metric: str = "l2", filter=None):
+    """Lloyd's iteration over the rows of `target` (a DeviceIndex or a ShardGroup) from float32 start centroids [K, V] on its GPU ->
+    (centroids, labels, values, n_iter, changed).  Per iteration: bias = -half_norms(C) under "l2" (none under "dot"); labels, values =
+    assign(C, bias, filter); changed = the rows whose label differs from the previous assignment (first: the rows assigned); stop when
+    nothing changed; else, for the clusters in batches of 64, C[j] = term_sums(filter=from_labels(labels, batch) & filter).mean() where the
+    cluster has rows -- an empty cluster keeps its centroid.  The labels returned are the assignment under the centroids returned (one
+    closing assign when the loop ends on `iters`).  Deterministic: every step is pinned bit for bit."""
+    import torch
+    from .doc_filter import DocFilter
+    dev = torch.device("cuda", target.device)
+    C_ = centroids.detach().to(dev).to(torch.float32).contiguous().clone()
+    K = int(C_.shape[0])
+
+    def step():
+        bias = -target.half_norms(C_) if metric == "l2" else None
+        return target.assign(C_, bias=bias, filter=filter)
+
+    prev, changed, stale = None, [], True
+    for _ in range(int(iters)):
+        cur = step()
+        stale = False
+        n_changed = int((cur.labels >= 0).sum()) if prev is None else int((cur.labels != prev.labels).sum())
+        changed.append(n_changed)
+        prev = cur
+        if n_changed == 0:
+            break
+        for b0 in range(0, K, KMEANS_UPDATE_BATCH):
+            batch = np.arange(b0, min(K, b0 + KMEANS_UPDATE_BATCH), dtype=np.int32)
+            sets = DocFilter.from_labels(cur.labels, batch, device=dev)
+            if filter is not None:
+                sets = sets & filter
+            ts = target.term_sums(filter=sets)
+            has = (ts.total > 0).reshape(-1, 1)
+            C_[b0:b0 + batch.size] = torch.where(has, ts.mean(), C_[b0:b0 + batch.size])
+        stale = True
+    if stale:
+        prev = step()
+    return C_, prev.labels, prev.values, len(changed), changed
+
+
 def _host(x):
     return x.detach().numpy() if _is_torch(x) else x
 
@@ -1881,6 +2087,50 @@ class DeviceIndex:
         its documents have.  topn in 1..1024."""
         return _top_weights(self, filter, ids, topn, min_count)
 
+    # ---- clustering: the nearest of K centroids for every row (vs_index_assign) ------------------------------------------------------------------
+    def _round_f16(self) -> bool:
+        return int(self.info().store_dtype) == nat.VS_F16
+
+    def _assign_call(self, c_dev, b_dev, f, bit0, rows_per_chunk, want_values=True):
+        """One vs_index_assign call on device buffers and torch's current stream -> (labels int32 [n_rows], values float32 [n_rows] | None).
+        c_dev [K, V] / b_dev [K] | None: float32 CUDA tensors on this index's device; f: None or a shared DocFilter there, read from bit
+        `bit0` on."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        n = self.n_rows
+        labels = torch.empty(n, dtype=torch.int32, device=dev)
+        values = torch.empty(n, dtype=torch.float32, device=dev) if want_values else None
+        nat.check(nat.lib().vs_index_assign(self._h, _ptr(c_dev), int(c_dev.stride(0)), int(c_dev.shape[0]), _ptr(b_dev),
+                                            _ptr(f.words) if f is not None else None, int(bit0), int(rows_per_chunk), _ptr(labels), _ptr(values),
+                                            current_stream(self.device)))
+        return labels, values
+
+    def assign(self, centroids, bias=None, filter=None, rows_per_chunk: int = 0) -> Assignment:
+        """For every live, allowed document the centroid with the largest value -> Assignment(labels int32 [N], values float32 [N]) on the
+        index's device, on torch's current stream.  centroids: float32 [K, V], K <= 4096, rounded to the index dtype as a query is; value(j,
+        r) = the fp64 sum, in the row's stored cell order, of the fp32 products centroid[j, col] * v, plus bias[j] when a bias [K] is given,
+        rounded once to fp32; ties go to the lowest j.  bias = -``half_norms(centroids)`` makes it the nearest centroid in the Euclidean
+        sense.  A deleted or filtered-out document gets -1 / -inf.  filter: ONE set (a DocFilter, a bool mask [N] or ids).  One pass over the
+        index: no [K, N] matrix is formed.  rows_per_chunk: 0 = automatic, else a multiple of 64 (a tuning knob)."""
+        c, b, rows_per_chunk = _assign_args(centroids, bias, self._n_cols(), rows_per_chunk)
+        import torch
+        nat.require_device()
+        dev = torch.device("cuda", self.device)
+        f = None
+        if filter is not None:
+            from .doc_filter import as_doc_filter
+            f = as_doc_filter(filter, self.n_rows, device=self.device)
+            if f.per_query:
+                raise ValueError("assign takes ONE document set, not a per-query filter")
+        return Assignment(*self._assign_call(c.to(dev).contiguous(), b.to(dev).contiguous() if b is not None else None, f, 0, rows_per_chunk))
+
+    def half_norms(self, centroids):
+        """float32(0.5 * ||c'_j||^2) per centroid, c' rounded to the index dtype (``centroid_half_norms``) -> float32 [K] on the index's device"""
+        import torch
+        c, _, _ = _assign_args(centroids, None, self._n_cols())
+        nat.require_device()
+        return centroid_half_norms(c.to(torch.device("cuda", self.device)), round_f16=self._round_f16(), device=self.device)
+
     def scores(self, q):
         """Dense [B, n_rows] fp32 score matrix (what index.py:91 materialises). numpy out."""
         info = self.info()
@@ -2236,6 +2486,35 @@ class ShardGroup:
     def top_weight_terms(self, filter=None, ids=None, topn: int = 20, min_count: int = 0) -> TopWeights:
         """DeviceIndex.top_weight_terms over the group's rows: the top-n is taken after the shards' sums are added, never per shard."""
         return _top_weights(self, filter, ids, topn, min_count)
+
+    def assign(self, centroids, bias=None, filter=None, rows_per_chunk: int = 0) -> Assignment:
+        """DeviceIndex.assign over the group's rows: the centroids and the bias are copied to every shard's GPU, every shard assigns its rows
+        under its bit range of the filter, and the answers are concatenated on the first shard's GPU.  A row's value depends on nothing
+        but the row: equal to the unsharded index bit for bit."""
+        c, b, rows_per_chunk = _assign_args(centroids, bias, _n_cols_of(self), rows_per_chunk)
+        import torch
+        nat.require_device()
+        dev0 = torch.device("cuda", self.device)
+        f = None
+        if filter is not None:
+            from .doc_filter import as_doc_filter
+            f = as_doc_filter(filter, self.n_rows, device=dev0)
+            if f.per_query:
+                raise ValueError("assign takes ONE document set, not a per-query filter")
+        labels, values, row0 = [], [], 0
+        for sh in self._shards:
+            sdev = torch.device("cuda", sh.device)
+            with torch.cuda.device(sdev):
+                l, v = sh._assign_call(c.to(sdev).contiguous(), b.to(sdev).contiguous() if b is not None else None,
+                                       f.to(sdev) if f is not None else None, row0, rows_per_chunk)       # its rows: bits [row0, row0 + n)
+            labels.append(l.to(dev0))
+            values.append(v.to(dev0))
+            row0 += sh.n_rows
+        return Assignment(torch.cat(labels), torch.cat(values))
+
+    def half_norms(self, centroids):
+        """DeviceIndex.half_norms, on the first shard's GPU (the shards share the store dtype)"""
+        return self._shards[0].half_norms(centroids)
 
     def close(self):
         if self._h:

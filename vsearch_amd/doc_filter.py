@@ -296,6 +296,39 @@ class DocFilter:
                                                    current_stream(dev.index)))
         return cls(words if prog.per_query else words[0], n)
 
+    @classmethod
+    def from_labels(cls, labels, values, device=None) -> "DocFilter":
+        """The rows whose label equals a value: `labels` an int array / tensor [N] (facet codes, cluster labels of ``assign``), `values` an
+        int (one set for the batch) or a sequence of B ints (one set per query, at most 4096) -> row r is allowed for query b iff
+        labels[r] == values[b].  Built in one pass over the labels on the GPU (vs_label_bitmaps); a value no row carries gives an empty
+        set.  The drill-down filter of a facet field, and the K cluster sets ``term_sums`` takes."""
+        torch = _torch()
+        from .device_index import _label_values, current_stream
+        vals, scalar = _label_values(values)
+        if isinstance(labels, (np.ndarray, list, tuple)):
+            labels = torch.from_numpy(np.ascontiguousarray(np.asarray(labels)))
+        if not isinstance(labels, torch.Tensor) or labels.dim() != 1:
+            raise TypeError("DocFilter.from_labels takes an integer tensor / ndarray [N]")
+        if labels.dtype.is_floating_point or labels.dtype.is_complex or labels.dtype == torch.bool:
+            raise TypeError(f"DocFilter.from_labels takes integer labels, not {labels.dtype}")
+        n = int(labels.shape[0])
+        if n <= 0:
+            raise ValueError("no labels: the index has rows")
+        dev = _device_of(device if device is not None else (labels.device if labels.is_cuda else None))
+        nat.require_device()
+        lab = labels.detach().to(dev)
+        if lab.dtype != torch.int32:
+            if lab.dtype == torch.int64 and n and (int(lab.min()) < -0x80000000 or int(lab.max()) > 0x7FFFFFFF):
+                raise ValueError("a label does not fit 32 bits")
+            lab = lab.to(torch.int32)
+        lab = lab.contiguous()
+        B, nw = int(vals.shape[0]), (n + 31) // 32
+        v = torch.from_numpy(vals).to(dev)
+        words = torch.empty((B, nw), dtype=torch.int32, device=dev)
+        nat.check(nat.lib().vs_label_bitmaps(C.c_void_p(lab.data_ptr()), n, C.c_void_p(v.data_ptr()), B, 0, C.c_void_p(words.data_ptr()), nw,
+                                             dev.index, current_stream(dev.index)))
+        return cls(words[0] if scalar else words, n)
+
     # ---- set algebra on the packed words --------------------------------------------------------------
     def _pair(self, other):
         if not isinstance(other, DocFilter):

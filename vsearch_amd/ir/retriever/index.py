@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from ... import _native as nat
-from ...device_index import DeviceIndex, DiverseResults, Explanation, FacetCounts, FusedResults, GroupedResults, TermCounts, TermSums, TopFacets, TopTerms, TopWeights, _term_topn_args, _weight_topn_args, fuse_topk, _fuse_args, MAX_FUSE_DEPTH, MAX_FUSE_ENTRIES, _topn_args, NotBinaryError, RangeResults, ShardGroup, _diverse_args, _range_args, _grouped_args, _by_example_args, _explain_args, _int64_ids, _k_a_args, resparsify, topk_exclude
+from ...device_index import Assignment, KMeansResult, KMEANS_UPDATE_BATCH, kmeans_loop, term_sum_topn, _assign_args, _kmeans_args, DeviceIndex, DiverseResults, Explanation, FacetCounts, FusedResults, GroupedResults, TermCounts, TermSums, TopFacets, TopTerms, TopWeights, _term_topn_args, _weight_topn_args, fuse_topk, _fuse_args, MAX_FUSE_DEPTH, MAX_FUSE_ENTRIES, _topn_args, NotBinaryError, RangeResults, ShardGroup, _diverse_args, _range_args, _grouped_args, _by_example_args, _explain_args, _int64_ids, _k_a_args, resparsify, topk_exclude
 
 logger = logging.getLogger(__name__)
 
@@ -697,6 +697,109 @@ class Index:
         shift = int(getattr(self, "shift", 0) or 0)
         cols = torch.where(top.cols >= 0, top.cols + shift, top.cols) if shift else top.cols
         return TopWeights(*(self._to_api(t) for t in (cols, top.scores, top.sums, top.total)))
+
+    # ---- clustering (not in the reference: the nearest of K centroids for every document, and Lloyd's k-means around it) --------------------------
+    def _cluster_target(self, filter):
+        """-> (search target, its GPU, one shared DocFilter there | None); a dense index raises NotImplementedError before any device work"""
+        if self.index_type == IndexType.DENSE:
+            raise NotImplementedError("clustering reads the sparse rows: a dense Index is not covered")
+        target, gpu_ord = self._explain_target()
+        gpu = torch.device("cuda", gpu_ord)
+        f = None
+        if filter is not None:
+            from ...doc_filter import as_doc_filter
+            f = as_doc_filter(filter, self._n_rows(), device=gpu)
+            if f.per_query:
+                raise ValueError("clustering takes ONE document set, not a per-query filter")
+        return target, gpu, f
+
+    def _n_cols(self) -> int:
+        return int(self._vector_meta()[0][1])
+
+    def assign(self, centroids, metric: str = "dot", filter=None) -> Assignment:
+        """For every live document (allowed by `filter`, as in ``search``: one set) the nearest of the K centroids [K, V] (float32, columns
+        in the vector's space) -> Assignment(labels int32 [N], values float32 [N]).  metric "dot": the largest dot product, in the
+        library's numerics (``explain``'s score where the sums are exact); "l2": the smallest Euclidean distance -- value = dot - ||c||^2 /
+        2, so ||x||^2 - 2 value is the squared distance.  Ties go to the lowest centroid; a deleted or filtered-out document gets -1 /
+        -inf.  One pass over the index on the GPU, no [K, N] matrix.  K <= 4096.  Works on a row-sharded index as well (not on the
+        one-process-per-GPU path of ``vsearch_amd.distributed``, and not on a dense index)."""
+        if metric not in ("dot", "l2"):
+            raise ValueError(f'metric must be "dot" or "l2", got {metric!r}')
+        if self.index_type == IndexType.DENSE:
+            raise NotImplementedError("clustering reads the sparse rows: a dense Index is not covered")
+        c, _, _ = _assign_args(centroids, None, self._n_cols())
+        target, gpu, f = self._cluster_target(filter)
+        c = c.to(gpu).contiguous()
+        res = target.assign(c, bias=-target.half_norms(c) if metric == "l2" else None, filter=f)
+        return Assignment(self._to_api(res.labels), self._to_api(res.values))
+
+    def kmeans(self, n_clusters: int, iters: int = 10, metric: str = "l2", init=None, seed: int = 0, filter=None) -> KMeansResult:
+        """Lloyd's k-means over the live documents (allowed by `filter`) -> KMeansResult(centroids float32 [K, V], labels int32 [N], values
+        float32 [N], counts int64 [K], n_iter, changed).  init: int64 row ids [K] (those documents are the start centroids), float32
+        centroids [K, V], or None: K distinct live, allowed documents drawn with ``torch.randperm`` under a CPU generator seeded with
+        `seed`.  Each iteration assigns (``assign``) and, unless nothing changed, moves every centroid to the mean of its documents
+        (``term_sums`` of the K label sets, 64 clusters a pass); an empty cluster keeps its centroid.  The labels and values returned are
+        the assignment under the centroids returned.  Deterministic, bit for bit: two runs are identical.  metric "l2" (Euclidean) or "dot"
+        (the largest dot product: spherical k-means without the normalisation).  The centroids are queries for ``search``; the labels feed
+        ``set_facet``, ``set_groups`` (see ``cluster``) and ``DocFilter.from_labels``."""
+        K, iters = _kmeans_args(n_clusters, iters, metric)
+        if self.index_type == IndexType.DENSE:
+            raise NotImplementedError("clustering reads the sparse rows: a dense Index is not covered")
+        V = self._n_cols()
+        _kmeans_args(K, iters, metric, init, V)
+        target, gpu, f = self._cluster_target(filter)
+        n = self._n_rows()
+        rows = None
+        if init is not None and len(init.shape) == 1:
+            rows = (init.detach().cpu() if isinstance(init, torch.Tensor) else torch.from_numpy(np.asarray(init))).to(torch.int64)
+            if int(rows.min()) < 0 or int(rows.max()) >= n:
+                raise IndexError(f"an init row lies outside [0, {n})")
+        cand = None
+        if init is None or f is not None:                               # the live, allowed documents: one pass against a single zero centroid
+            ok = target.assign(torch.zeros((1, V), dtype=torch.float32, device=gpu), filter=f).labels >= 0
+            cand = ok.nonzero().reshape(-1).cpu()
+        n_ok = int(cand.numel()) if cand is not None else self.n_live
+        if K > n_ok:
+            raise ValueError(f"n_clusters = {K} exceeds the {n_ok} live, allowed documents")
+        if init is None:
+            g = torch.Generator(device="cpu")
+            g.manual_seed(int(seed))
+            rows = cand[torch.randperm(n_ok, generator=g)[:K]]
+        if rows is not None:
+            start = target.queries_from_rows(rows.to(gpu).unsqueeze(1).contiguous())        # (0 + 1 * v: the stored values, exactly)
+        else:
+            start = _assign_args(init, None, V)[0].to(gpu)
+        C_, labels, values, n_iter, changed = kmeans_loop(target, start.to(torch.float32), iters, metric, f)
+        counts = target.facet_counts(labels, K, filter=f).counts[0]
+        return KMeansResult(self._to_api(C_), self._to_api(labels), self._to_api(values), self._to_api(counts), n_iter, changed)
+
+    def cluster(self, n_clusters: int, field: str = "cluster", set_groups: bool = False, **kmeans_args) -> KMeansResult:
+        """``kmeans``, with the labels stored as facet field `field` (``facets(field, q, min_score)`` then counts a result set per cluster;
+        unassigned documents carry -1 = no label) and, with set_groups=True, as the group ids of ``search_grouped`` (one hit per cluster;
+        documents without a cluster share the group id K, since group ids are >= 0) -> the KMeansResult."""
+        res = self.kmeans(n_clusters, **kmeans_args)
+        K = int(res.centroids.shape[0])
+        self.set_facet(field, res.labels, names=[str(j) for j in range(K)])
+        if set_groups:
+            self.set_groups(torch.where(res.labels < 0, torch.full_like(res.labels, K), res.labels))
+        return res
+
+    def cluster_terms(self, labels, n_clusters: int, topn: int = 10) -> TopWeights:
+        """Per cluster the columns its documents put the most weight on -> TopWeights(cols [K, topn], scores, sums, total [K]); cols in the
+        index file's column space (+ ``shift``), scores the mean weight, total the cluster's size.  labels: ``kmeans(...).labels``."""
+        _weight_topn_args(topn, 0)
+        from ...doc_filter import DocFilter
+        target, gpu, _ = self._cluster_target(None)
+        lab = (labels if isinstance(labels, torch.Tensor) else torch.from_numpy(np.asarray(labels))).to(gpu)
+        K = _kmeans_args(n_clusters, 0, "l2")[0]
+        parts = []
+        for b0 in range(0, K, KMEANS_UPDATE_BATCH):
+            ts = target.term_sums(filter=DocFilter.from_labels(lab, np.arange(b0, min(K, b0 + KMEANS_UPDATE_BATCH), dtype=np.int32), device=gpu))
+            parts.append(term_sum_topn(ts.sums, ts.total, int(topn), device=gpu.index) + (ts.total,))
+        cols, scores, sums, total = (torch.cat([p[i] for p in parts]) for i in range(4))
+        shift = int(getattr(self, "shift", 0) or 0)
+        cols = torch.where(cols >= 0, cols + shift, cols) if shift else cols
+        return TopWeights(*(self._to_api(t) for t in (cols, scores, sums, total)))
 
     def _added_facets(self, facets, n_add):
         """facets= of add() / update() -> {name: int32 CPU codes [n_add]}, or None for an index without facet fields.  Raises before

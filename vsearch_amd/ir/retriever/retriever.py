@@ -223,6 +223,26 @@ class Retriever(BiEncoder):
             out.append([(name, float(s), int(d)) for name, s, d in zip(names, scores[b][live], sums[b][live])])
         return out
 
+    def cluster_documents(self, n_clusters: int, topn: int = 10, index: Index = None, **args):
+        """Partition the indexed documents into `n_clusters` clusters (``Index.cluster``: Lloyd's k-means on the GPU, the labels stored as
+        facet field "cluster") and name every cluster by its tokens -> per cluster (size, [(token, mean weight), ...]), the vocabulary
+        tokens its documents put the most weight on, heaviest first.  **args go to ``Index.cluster`` (iters, metric, init, seed, filter,
+        field, set_groups)."""
+        index = index or self.index
+        if index is None:
+            raise RuntimeError("no index: call build_index / load_index first")
+        res = index.cluster(n_clusters, **args)
+        top = index.cluster_terms(res.labels, n_clusters, topn=topn)
+        shift = int(self.encoder_p.config.shift_vocab_num)
+        tok = self.encoder_p.tokenizer
+        cols, scores, total = (t.cpu().numpy() for t in (top.cols, top.scores, top.total))
+        out = []
+        for j in range(cols.shape[0]):
+            live = cols[j] >= 0
+            names = tok.convert_ids_to_tokens([int(x) + shift for x in cols[j][live]])
+            out.append((int(total[j]), [(name, float(s)) for name, s in zip(names, scores[j][live])]))
+        return out
+
     def retrieve_diverse(self, queries: Union[List[str], np.ndarray, T], k: int = 5, lam: float = 0.5, depth: int = None, sim: str = "cosine",
                          dropout: float = 0, a: int = None, index: Index = None, batch_size: int = 32, filter=None, must=None, must_not=None,
                          should=None, min_should: int = None) -> DiverseResults:
