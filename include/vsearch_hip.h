@@ -426,6 +426,85 @@ VS_API int vs_index_assign(vs_index* index, const float* centroids, int64_t ldc,
 VS_API int vs_label_bitmaps(const int32_t* labels, int64_t n_rows, const int32_t* values, int32_t B, int64_t bit0, uint32_t* out_words,
                             int64_t ld_words, int device, void* stream);
 
+/* ---- numeric fields: range filters, stats, histograms and sort by value over a per-row quantity (no reference counterpart) ------------------
+ * A field is one 32-bit value per row: values [n_rows] of dtype VS_VAL_F32 (fp32) or VS_VAL_I32 (int32).  A row may have NO value: the missing
+ * sentinel is NaN (any NaN pattern) for fp32 and INT32_MIN for int32.  Everything is decided on one ORDER KEY, a uint32:
+ *     fp32:  key = flip(canon_zero(v)) -- -0.0 and +0.0 share a key, -inf < finite < +inf, the smallest key is -inf's, 0x007FFFFF;
+ *     int32: key = uint32(v) ^ 0x80000000;       missing: key 0 (no value of either type has it).
+ * All comparisons are unsigned compares of keys, so every result is exact and bit-reproducible whatever the launch.
+ * A set of rows is given exactly as for vs_facet_counts: bit bit0 + r of the bitmap at words + b * ld_words stands for row r (ld_words = 0: one
+ * bitmap, and then B must be 1; else ld_words >= the (bit0 + n_rows + 31) / 32 words a bitmap spans); words == NULL: every row (B must be 1);
+ * and_words (may be NULL): a second bitmap shared by all queries, at the same bit0; bits at or past bit0 + n_rows are ignored whatever they hold.
+ * The vs_index_* variants run over the index's rows with its tombstones ANDed in (at bit 0 whatever bit0 is): deleted rows never count.
+ *
+ * vs_value_range_bitmaps: lo / hi [B] in the field's type -> B bitmaps; bit bit0 + r of row b is set iff row r has a value and lo[b] <= v <= hi[b],
+ *   both ends inclusive (compared on keys: a bound of -0.0 is +0.0).  lo > hi is the empty set; fp32 bounds may be +-inf (an open end; for int32
+ *   INT32_MIN + 1 and INT32_MAX).  A missing bound (NaN / INT32_MIN): VS_EINVAL for host arrays; on the device it matches nothing.  Words [0,
+ *   (bit0 + n_rows + 31) / 32) of each row of out_words [B, ld_words] are written whole, bits below bit0 and past the rows 0 -- the convention of
+ *   vs_label_bitmaps.  B in 1..VS_VALUE_MAX_RANGES.  A wave owns 64 bits of every bitmap: it loads its rows' keys once and forms each word pair
+ *   with a ballot; plain stores, no atomics.
+ * vs_value_plan: the launch of vs_value_stats / vs_value_histogram for these arguments -- pure host arithmetic, no device needed, the rule of
+ *   vs_facet_plan: qt = queries a workgroup serves (8 for per-query bitmaps, 1 for a shared one); chunks x rows_per_chunk >= n_rows > (chunks - 1)
+ *   x rows_per_chunk.  n_bins: the LDS bins a query takes (n_edges + 2 for a histogram, 0 for stats; 0..VS_VALUE_MAX_EDGES + 2).  rows_per_chunk
+ *   = 0: automatic; any other value must be a positive multiple of 64 and is taken as given (a tuning knob: no result depends on it).
+ *   vs_value_topk cuts its chunks by the same rule with per_query = 1 and n_bins = 0, one query a workgroup.
+ * vs_value_stats: per query b, count [b] = set rows that have a value, missing [b] = set rows without one (count + missing = the size of the set,
+ *   vs_facet_counts' total); out_min [b] / out_max [b]: raw 32-bit values of the field's type (of -0.0 and +0.0 the answer is +0.0; count = 0:
+ *   the missing sentinel, NaN 0x7FC00000 / INT32_MIN); sum [b] int64: int32 field -- the exact integer sum; fp32 field -- the sum of fx(v) of
+ *   the term sums above (clamped to +-2^VS_TERM_FX_CLAMP_LOG2, times 2^VS_TERM_FX_SHIFT, rounded to nearest even); sums wrap modulo 2^64.
+ *   count, missing, sum int64 [B]; every element of the five outputs is written.
+ * vs_value_histogram: edges [n_edges] in the field's type, strictly ascending (on keys: -0.0 next to +0.0 is not), none missing, n_edges in
+ *   2..VS_VALUE_MAX_EDGES -- a host array that breaks this is VS_EINVAL, a device array is not read on the host (the bin sum identity still
+ *   holds, the bins are whatever the search gives).  Bin i holds edges[i] <= v < edges[i + 1]; below [b]: v < edges[0]; above [b]: v >=
+ *   edges[n_edges - 1]; missing [b] as above.  counts [B, ld_counts] int64, ld_counts >= n_edges - 1; columns [n_edges - 1, ld_counts) are not
+ *   touched; below / above / missing int64 [B].  counts [b].sum() + below [b] + above [b] + missing [b] == the size of the set, always.
+ * vs_value_topk: per query the k set rows that have a value, in value order: descending != 0 -- value descending, else ascending; then id
+ *   ascending (-0.0 and +0.0 tie).  out_ids int64 [B, k] (row + id_offset), out_values [B, k] the rows' 32-bit values as stored (a -0.0 stays -0.0); unused slots hold id
+ *   -1 and the missing sentinel; every slot is written.  k in 1..VS_VALUE_MAX_TOPK, k > n_rows is allowed.
+ * Kernels (values.hip).  Stats and histogram: a workgroup owns a chunk of rows and a tile of qt queries; it walks the bitmaps in 2048-row spans,
+ * leaves a span whose words are all zero without touching the values, and loads a row's value once for the tile.  Histogram: the edges sit in LDS
+ * as keys, the bin is a branch-free binary search (<= 11 steps), one uint32 LDS histogram of n_edges + 2 bins per query of the tile (33 KB at 8
+ * queries and 1025 edges: one regime); non-zero bins are added to the outputs with 64-bit atomics at the end of the chunk.  Stats: min / max key
+ * and sum per lane, reduced per wave, then per workgroup in LDS, then one atomic per (workgroup, query) on keys / int64; a finishing kernel
+ * turns keys into raw values.  Top-k: a workgroup owns a chunk and one query and streams (key or ~key) << 32 | ~row through a 4096-key LDS
+ * buffer, sorted and cut to k when more than 2048 are in -- afterwards only keys above the k-th are admitted; per-chunk lists go to device
+ * scratch (freed behind a stream synchronisation before the call returns) and one workgroup per query merges them.
+ * Errors: NULL values or outputs, dtype not VS_VAL_*, n_rows outside 1..2^32 - 1, B < 1 (B > VS_VALUE_MAX_RANGES for the range bitmaps), bit0 < 0,
+ * B > 1 with ld_words = 0, ld_words / ld_counts too short, rows_per_chunk no multiple of 64, n_edges or k out of range, chunks x B x k beyond
+ * 2^27 scratch keys, host edges / bounds as above: VS_EINVAL -- checked before the device is touched (without a GPU a bad argument is VS_EINVAL,
+ * a good one VS_ENODEVICE).  Pointers: all host (staged; the call blocks), or all device pointers on `device` / the index's device (VS_EINVAL
+ * for a mix); device pointers and a non-NULL stream only enqueue (vs_value_topk synchronises either way).
+ * Not covered: no index file stores values; 64-bit and fp64 values; histograms of scores; percentiles; sort by several keys; k > 1024; a shard
+ * group has no entry point of its own (every shard works on its slice of the values and its bit range of the bitmap: counts, sums and bins are
+ * added, min / max combined on keys, the top-k lists merged by (key, id)) and the one-process-per-GPU RCCL path has none.                       */
+#define VS_VAL_F32 0
+#define VS_VAL_I32 1
+#define VS_VALUE_MAX_RANGES 4096     /* bitmaps of one vs_value_range_bitmaps call */
+#define VS_VALUE_MAX_EDGES 1025      /* edges of a histogram: up to 1024 bins */
+#define VS_VALUE_MAX_TOPK 1024       /* rows vs_value_topk lists per query at most */
+VS_API int vs_value_range_bitmaps(const void* values, int dtype, int64_t n_rows, const void* lo, const void* hi, int32_t B, int64_t bit0,
+                                  uint32_t* out_words, int64_t ld_words, int device, void* stream);
+VS_API int vs_value_plan(int64_t n_rows, int32_t B, int32_t n_bins, int per_query, int64_t rows_per_chunk, int32_t* out_qt, int64_t* out_chunks,
+                         int64_t* out_rows_per_chunk);
+VS_API int vs_value_stats(const uint32_t* words, int64_t bit0, int64_t ld_words, const uint32_t* and_words, int32_t B, const void* values,
+                          int dtype, int64_t n_rows, int64_t rows_per_chunk, int64_t* count, int64_t* missing, void* out_min, void* out_max,
+                          int64_t* sum, int device, void* stream);
+VS_API int vs_index_value_stats(vs_index* index, const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B, const void* values, int dtype,
+                                int64_t rows_per_chunk, int64_t* count, int64_t* missing, void* out_min, void* out_max, int64_t* sum,
+                                void* stream);
+VS_API int vs_value_histogram(const uint32_t* words, int64_t bit0, int64_t ld_words, const uint32_t* and_words, int32_t B, const void* values,
+                              int dtype, int64_t n_rows, const void* edges, int32_t n_edges, int64_t rows_per_chunk, int64_t* counts,
+                              int64_t ld_counts, int64_t* below, int64_t* above, int64_t* missing, int device, void* stream);
+VS_API int vs_index_value_histogram(vs_index* index, const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B, const void* values,
+                                    int dtype, const void* edges, int32_t n_edges, int64_t rows_per_chunk, int64_t* counts, int64_t ld_counts,
+                                    int64_t* below, int64_t* above, int64_t* missing, void* stream);
+VS_API int vs_value_topk(const uint32_t* words, int64_t bit0, int64_t ld_words, const uint32_t* and_words, int32_t B, const void* values,
+                         int dtype, int64_t n_rows, int32_t k, int descending, int64_t id_offset, int64_t rows_per_chunk, int64_t* out_ids,
+                         void* out_values, int device, void* stream);
+VS_API int vs_index_value_topk(vs_index* index, const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B, const void* values, int dtype,
+                               int32_t k, int descending, int64_t id_offset, int64_t rows_per_chunk, int64_t* out_ids, void* out_values,
+                               void* stream);
+
 /* bool / uint8 mask [B, n] (row stride ld_mask bytes; non-zero = allowed) -> the bitmap words [B, ld_words] vs_index_search_filtered
  * reads (bits past n of a row's last word are 0).  mask and words: host pointers or device pointers on `device` (VS_EINVAL otherwise).  stream as in
  * vs_index_search (host buffers block).                                                                                          */

@@ -1,0 +1,779 @@
+// values.hip -- numeric fields (vs_value_range_bitmaps, vs_value_plan, vs_value_stats, vs_value_histogram, vs_value_topk and their vs_index_*
+// variants): range filters, stats, histograms and sort by value over one 32-bit quantity per row.  No reference counterpart
+// (the reference only has topk, index.py:92).  Nothing here touches a search kernel: a set arrives as a packed bitmap in the layout of
+// vs_index_search_filtered, the values as fp32 or int32 [n_rows].  Everything is decided on the uint32 order keys of value_check.h (0 = the
+// row has no value), so every result is exact and independent of the launch.
+//
+// (a) Range bitmaps: a wave owns 64 bits of every bitmap.  It loads its rows' keys once and, per range, forms the two words with one ballot;
+//     lane b of a batch of 64 ranges keeps the ballot of range b and stores it: plain stores, every word written exactly once.
+// (b) Stats / histogram: a workgroup owns a chunk of rows and a tile of QT queries and walks the bitmaps as facets.hip does (2048-row spans,
+//     all-zero spans left at once, a row's value loaded once for the tile).
+//       histogram: the edge keys in LDS, bin = value_bin (branch-free, 11 steps), one uint32 histogram of n_edges + 2 slots per query in LDS
+//                  (slot 0 below, 1 .. n_edges - 1 the bins, n_edges above, n_edges + 1 missing), flushed with 64-bit atomicAdd.
+//       stats:     min key, max key and sum per lane and query; wave reduction by shuffles, workgroup reduction by LDS atomics, one global
+//                  atomic per (workgroup, query) and output.  The min / max outputs hold KEYS until value_finish_kernel turns them into values.
+// (c) Top-k: a workgroup owns a chunk and one query.  All four waves walk the same span, each a quarter of its 64-row steps, and push
+//     (key or ~key) << 32 | ~row above the threshold into a 4096-key LDS buffer; after a span with more than 2048 keys in, the buffer is
+//     sorted (wg_sort_desc), cut to k, and the k-th key becomes the threshold.  Per-chunk lists go to scratch; value_topk_merge_kernel, one
+//     workgroup per query, streams them through the same buffer and writes ids and the rows' stored values.
+#include "common.h"
+#include "bitmap_span.h"
+#include "staging.h"
+#include "term_sum_check.h"
+#include "topk_keys.h"
+#include "value_check.h"
+
+using namespace vs;
+
+namespace {
+
+constexpr int kValThreads = 256;
+constexpr int kValWaves = kValThreads / 64;
+constexpr int kTopCap = 4096;                         // keys of the top-k candidate buffer
+constexpr int kTopKeep = 2048;                        // sorted and cut when more are in
+static_assert(kValueSpanRows == 2048 && kTopCap - kTopKeep >= kValueSpanRows, "a span adds up to 2048 candidates");
+
+int plan_or_fail(int rc, const char* msg) { return rc == VS_OK ? VS_OK : fail(rc, "%s", msg); }
+
+int device_in_range(int device) {
+    VS_TRY(need_device());
+    int ndev = 0;
+    VS_HIP(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) return fail(VS_EINVAL, "device %d out of range", device);
+    return VS_OK;
+}
+
+// ---- (a) range bitmaps -----------------------------------------------------------------------------------------------------------------------
+struct RangeArgs {
+    const uint32_t* values;           // [n_rows] raw
+    int dtype;
+    int64_t n_rows;
+    const uint32_t *lo, *hi;          // [B] raw
+    int32_t B;
+    int64_t bit0, n_words;            // n_words = (bit0 + n_rows + 31) / 32 words of a row are written
+    uint32_t* out;                    // [B, ld]
+    int64_t ld;
+};
+
+__global__ __launch_bounds__(kValThreads) void value_range_kernel(RangeArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int64_t g = (int64_t)blockIdx.x * kValWaves + (threadIdx.x >> 6);          // this wave owns words 2 g and 2 g + 1 of every row
+    const int64_t w0 = 2 * g;
+    if (w0 >= a.n_words) return;                                                     // (wave-uniform)
+    const int64_t r = 64 * g + lane - a.bit0;                                         // the row behind bit 64 g + lane
+    const bool valid = r >= 0 && r < a.n_rows;
+    const uint32_t key = valid ? value_key(a.values[r], a.dtype) : 0u;                // 0: no value, in no range
+    const bool two = w0 + 1 < a.n_words;
+    for (int32_t b0 = 0; b0 < a.B; b0 += 64) {
+        const int n = min(64, a.B - b0);
+        uint32_t klo = 1u, khi = 0u;                                                  // (empty)
+        if (lane < n) {
+            klo = value_key(a.lo[b0 + lane], a.dtype);
+            khi = value_key(a.hi[b0 + lane], a.dtype);
+            if (klo == 0u || khi == 0u) {                                             // a missing bound matches nothing
+                klo = 1u;
+                khi = 0u;
+            }
+        }
+        uint64_t bits = 0ull;
+        for (int k = 0; k < n; ++k) {
+            const uint32_t l = (uint32_t)__builtin_amdgcn_readlane((int)klo, k);
+            const uint32_t h = (uint32_t)__builtin_amdgcn_readlane((int)khi, k);
+            const uint64_t m = __builtin_amdgcn_ballot_w64(key != 0u && l <= key && key <= h);
+            if (lane == k) bits = m;
+        }
+        if (lane < n) {                                                               // range b0 + lane: its two words
+            uint32_t* dst = a.out + (size_t)(b0 + lane) * (size_t)a.ld + w0;
+            dst[0] = (uint32_t)bits;
+            if (two) dst[1] = (uint32_t)(bits >> 32);
+        }
+    }
+}
+
+// ---- (b) stats and histogram -------------------------------------------------------------------------------------------------------------------
+struct SetArgs {
+    const uint32_t* words;            // [B, ld_words] or null (every row set)
+    int64_t bit0, ld_words;
+    const uint32_t* and_words;        // shared by the queries, or null
+    int64_t and_bit0;
+    const uint32_t* values;           // [n_rows] raw
+    int dtype;
+    int64_t n_rows;
+    int32_t B;
+    int64_t rows_per_chunk;
+};
+
+struct StatsArgs {
+    SetArgs s;
+    unsigned long long *count, *missing, *sum;     // [B], zeroed by the caller
+    uint32_t *min_key, *max_key;                   // [B], 0xFFFFFFFF / 0 set by the caller
+};
+
+struct HistArgs {
+    SetArgs s;
+    const uint32_t* edges;            // [n_edges] raw
+    int32_t n_edges;
+    unsigned long long* counts;       // [B, ld_counts], columns [0, n_edges - 1) zeroed by the caller
+    int64_t ld_counts;
+    unsigned long long *below, *above, *missing;   // [B], zeroed by the caller
+};
+
+// One wave's walk over its spans of the chunk: body(row0, raw, key, sp, s, sh, live) is called for every 64-row step with a set row -- raw /
+// key: this lane's row's value and its key where some query has the row (else 0); query q's rows of the step are window64(sp[q], s, sh) & live.
+template <int QT, class Body>
+__device__ __forceinline__ void walk_set(const SetArgs& a, int q0, int nq, int64_t r0, int64_t r1, int w, int lane, Body body) {
+    const int64_t n_w = (a.bit0 + a.n_rows + 31) >> 5, n_aw = (a.and_bit0 + a.n_rows + 31) >> 5;
+    for (int64_t rb = r0 + (int64_t)w * kValueSpanRows; rb < r1; rb += (int64_t)kValWaves * kValueSpanRows) {
+        const int nsub = (int)((min(r1, rb + kValueSpanRows) - rb + 63) >> 6);
+        Span an{~0u, ~0u};
+        int sha = 0;
+        if (a.and_words) {
+            const int64_t p = a.and_bit0 + rb;
+            an = load_span(a.and_words, p >> 5, n_aw, lane);
+            sha = (int)(p & 31);
+            if (__builtin_amdgcn_ballot_w64((an.lo | an.hi) != 0u) == 0ull) continue;
+        }
+        Span sp[QT];
+        Span u{~0u, ~0u};
+        int sh = 0;
+        if (a.words) {
+            const int64_t p = a.bit0 + rb;
+            sh = (int)(p & 31);
+            u.lo = u.hi = 0u;
+#pragma unroll
+            for (int q = 0; q < QT; ++q) {
+                sp[q] = Span{0u, 0u};
+                if (q < nq) sp[q] = load_span(a.words + (size_t)(q0 + q) * (size_t)a.ld_words, p >> 5, n_w, lane);
+                u.lo |= sp[q].lo;
+                u.hi |= sp[q].hi;
+            }
+            if (__builtin_amdgcn_ballot_w64((u.lo | u.hi) != 0u) == 0ull) continue;      // no value of the span is touched
+        } else {
+#pragma unroll
+            for (int q = 0; q < QT; ++q) sp[q] = u;
+        }
+        for (int s = 0; s < nsub; ++s) {
+            const int64_t row0 = rb + (int64_t)s * 64;
+            const int64_t nvalid = r1 - row0;                                        // >= 1
+            const uint64_t vm = nvalid >= 64 ? ~0ull : ((1ull << nvalid) - 1ull);    // bits at or past the last row are ignored
+            const uint64_t live = window64(an, s, sha) & vm;
+            const uint64_t many = window64(u, s, sh) & live;
+            if (many == 0ull) continue;                                              // (uniform)
+            uint32_t raw = 0u, key = 0u;
+            if ((many >> lane) & 1ull) {                                             // once for the tile
+                raw = a.values[row0 + lane];
+                key = value_key(raw, a.dtype);
+            }
+            body(row0, raw, key, sp, s, sh, live);
+        }
+    }
+}
+
+template <int QT>
+__global__ __launch_bounds__(kValThreads) void value_stats_kernel(StatsArgs a) {
+    __shared__ uint32_t s_cnt[QT], s_mis[QT], s_min[QT], s_max[QT];
+    __shared__ unsigned long long s_sum[QT];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int q0 = (int)blockIdx.y * QT;
+    const int nq = min(QT, a.s.B - q0);
+    const int64_t r0 = (int64_t)blockIdx.x * a.s.rows_per_chunk;
+    const int64_t r1 = min(a.s.n_rows, r0 + a.s.rows_per_chunk);
+    if (tid < QT) {
+        s_cnt[tid] = s_mis[tid] = 0u;
+        s_min[tid] = 0xFFFFFFFFu;
+        s_max[tid] = 0u;
+        s_sum[tid] = 0ull;
+    }
+    __syncthreads();
+    uint32_t cnt[QT], mis[QT];                                   // wave-uniform: a chunk holds fewer than 2^32 rows
+    uint32_t kmin[QT], kmax[QT];                                 // per lane
+    uint64_t sum[QT];
+#pragma unroll
+    for (int q = 0; q < QT; ++q) {
+        cnt[q] = mis[q] = 0u;
+        kmin[q] = 0xFFFFFFFFu;
+        kmax[q] = 0u;
+        sum[q] = 0ull;
+    }
+    const bool f32 = a.s.dtype == VS_VAL_F32;
+    walk_set<QT>(a.s, q0, nq, r0, r1, w, lane, [&](int64_t, uint32_t raw, uint32_t key, const Span* sp, int s, int sh, uint64_t live) {
+        // what the row adds to a sum: fx(v) of the term sums for fp32, the integer itself for int32; nothing without a value
+        uint64_t add = 0ull;
+        if (key != 0u) add = f32 ? term_fx(__uint_as_float(raw)) : (uint64_t)(int64_t)(int32_t)raw;
+#pragma unroll
+        for (int q = 0; q < QT; ++q) {
+            if (q >= nq) continue;
+            const uint64_t m = window64(sp[q], s, sh) & live;
+            if (m == 0ull) continue;
+            const bool in = (m >> lane) & 1ull;
+            const bool has = in && key != 0u;
+            const uint32_t c = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(has));
+            cnt[q] += c;
+            mis[q] += (uint32_t)__popcll(m) - c;
+            if (has) {
+                kmin[q] = min(kmin[q], key);
+                kmax[q] = max(kmax[q], key);
+                sum[q] += add;
+            }
+        }
+    });
+#pragma unroll
+    for (int q = 0; q < QT; ++q) {
+        if (q >= nq) continue;
+        uint32_t lo = kmin[q], hi = kmax[q];
+        uint64_t sm = sum[q];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            lo = min(lo, (uint32_t)__shfl_xor((int)lo, o, 64));
+            hi = max(hi, (uint32_t)__shfl_xor((int)hi, o, 64));
+            sm += (uint64_t)__shfl_xor((unsigned long long)sm, o, 64);
+        }
+        if (lane == 0 && (cnt[q] | mis[q])) {
+            atomicAdd(&s_cnt[q], cnt[q]);
+            atomicAdd(&s_mis[q], mis[q]);
+            atomicMin(&s_min[q], lo);
+            atomicMax(&s_max[q], hi);
+            atomicAdd(&s_sum[q], (unsigned long long)sm);
+        }
+    }
+    __syncthreads();
+    if (tid < nq) {
+        const int b = q0 + tid;
+        if (s_cnt[tid]) {
+            atomicAdd(&a.count[b], (unsigned long long)s_cnt[tid]);
+            atomicMin(&a.min_key[b], s_min[tid]);
+            atomicMax(&a.max_key[b], s_max[tid]);
+            if (s_sum[tid]) atomicAdd(&a.sum[b], s_sum[tid]);
+        }
+        if (s_mis[tid]) atomicAdd(&a.missing[b], (unsigned long long)s_mis[tid]);
+    }
+}
+
+// keys -> raw values, in place; no row with a value: the missing sentinel
+__global__ void value_finish_kernel(uint32_t* min_key, uint32_t* max_key, const unsigned long long* count, int32_t B, int dtype) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const bool any = count[b] != 0ull;
+    min_key[b] = value_unkey(any ? min_key[b] : 0u, dtype);
+    max_key[b] = value_unkey(any ? max_key[b] : 0u, dtype);
+}
+
+template <int QT>
+__global__ __launch_bounds__(kValThreads) void value_hist_kernel(HistArgs a) {
+    extern __shared__ uint32_t val_lds[];                        // edge keys [n_edges], then the histograms [nq][n_edges + 2]
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int q0 = (int)blockIdx.y * QT;
+    const int nq = min(QT, a.s.B - q0);
+    const int64_t r0 = (int64_t)blockIdx.x * a.s.rows_per_chunk;
+    const int64_t r1 = min(a.s.n_rows, r0 + a.s.rows_per_chunk);
+    const int E = a.n_edges;
+    const uint32_t S = (uint32_t)E + 2u;                         // slots of a query
+    uint32_t* ekeys = val_lds;
+    uint32_t* hist = val_lds + E;
+    for (int i = tid; i < E; i += kValThreads) ekeys[i] = value_key(a.edges[i], a.s.dtype);
+    for (uint32_t i = tid; i < (uint32_t)nq * S; i += kValThreads) hist[i] = 0u;
+    __syncthreads();
+    walk_set<QT>(a.s, q0, nq, r0, r1, w, lane, [&](int64_t, uint32_t, uint32_t key, const Span* sp, int s, int sh, uint64_t live) {
+        const uint32_t slot = key == 0u ? (uint32_t)E + 1u : (uint32_t)value_bin(ekeys, E, key);      // once for the tile
+#pragma unroll
+        for (int q = 0; q < QT; ++q) {
+            if (q >= nq) continue;
+            const uint64_t m = window64(sp[q], s, sh) & live;
+            if (m == 0ull) continue;
+            const bool in = (m >> lane) & 1ull;
+            const int first = __builtin_ctzll(m);
+            const uint32_t s0 = (uint32_t)__builtin_amdgcn_readlane((int)slot, first);
+            const bool one = __builtin_amdgcn_ballot_w64(in && slot == s0) == m;      // every row of the step in one slot: add once
+            uint32_t* dst = hist + (size_t)q * S;
+            if (one) {
+                if (lane == first) atomicAdd(dst + s0, (uint32_t)__popcll(m));
+            } else if (in) {
+                atomicAdd(dst + slot, 1u);
+            }
+        }
+    });
+    __syncthreads();
+    for (int q = 0; q < nq; ++q) {
+        const size_t b = (size_t)(q0 + q);
+        unsigned long long* dst = a.counts + b * (size_t)a.ld_counts;
+        for (uint32_t i = tid; i < S; i += kValThreads) {
+            const uint32_t v = hist[(size_t)q * S + i];
+            if (!v) continue;
+            unsigned long long* p = i == 0u ? a.below + b : i == (uint32_t)E ? a.above + b : i == (uint32_t)E + 1u ? a.missing + b : dst + (i - 1u);
+            atomicAdd(p, (unsigned long long)v);
+        }
+    }
+}
+
+// ---- (c) top-k ------------------------------------------------------------------------------------------------------------------------------------
+struct TopArgs {
+    SetArgs s;
+    int32_t k;
+    uint32_t flip;                    // 0: descending (key as it is), 0xFFFFFFFF: ascending (~key)
+    int64_t chunks;
+    uint64_t* scratch;                // [B, chunks, k]
+    int64_t id_offset;
+    int64_t* out_ids;                 // [B, k]
+    uint32_t* out_values;             // [B, k] raw
+};
+
+// push the lanes' keys that pass into the buffer (cnt_sh: its fill); the caller guarantees the room
+__device__ __forceinline__ void top_push(uint64_t* cand, int* cnt_sh, bool pass, uint64_t key, int lane) {
+    const unsigned long long m = __builtin_amdgcn_ballot_w64(pass);
+    if (m == 0ull) return;
+    int base = 0;
+    if (lane == 0) base = atomicAdd(cnt_sh, __popcll(m));
+    base = __shfl(base, 0, 64);
+    if (pass) cand[base + __popcll(m & ((1ull << lane) - 1ull))] = key;
+}
+
+// after a barrier: sort the buffer when it is more than half full (or at the end) and cut it to K -> the new threshold.  Only the power of two
+// that holds the keys (and the K slots the caller reads) is sorted: a sparse set's last sort is a few hundred keys, not 4096.
+__device__ __forceinline__ uint64_t top_cut(uint64_t* cand, int* cnt_sh, int K, bool last, uint64_t tau, int tid) {
+    const int cnt = *cnt_sh;                                     // (uniform: read after the caller's barrier)
+    if (last || cnt > kTopKeep) {
+        int n = 2;
+        while (n < cnt || n < K) n <<= 1;                        // <= kTopCap: cnt <= kTopCap, K <= 1024
+        for (int i = cnt + tid; i < n; i += kValThreads) cand[i] = 0ull;
+        wg_sort_desc<kValThreads>(cand, n, tid);
+        if (!last && cnt > K) {
+            tau = cand[K - 1];
+            __syncthreads();
+            if (tid == 0) *cnt_sh = K;
+        }
+    }
+    __syncthreads();
+    return tau;
+}
+
+__global__ __launch_bounds__(kValThreads) void value_topk_chunk_kernel(TopArgs a) {
+    __shared__ uint64_t cand[kTopCap];
+    __shared__ int cnt_sh;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int64_t c = blockIdx.x;
+    const size_t b = blockIdx.y;
+    const int K = a.k;
+    const int64_t r0 = c * a.s.rows_per_chunk;
+    const int64_t r1 = min(a.s.n_rows, r0 + a.s.rows_per_chunk);
+    const int64_t n_w = (a.s.bit0 + a.s.n_rows + 31) >> 5, n_aw = (a.s.and_bit0 + a.s.n_rows + 31) >> 5;
+    const uint32_t* words = a.s.words ? a.s.words + b * (size_t)a.s.ld_words : nullptr;
+    if (tid == 0) cnt_sh = 0;
+    __syncthreads();
+    uint64_t tau = 0ull;
+    // every wave loads the words of the same span (so that the decisions below are uniform over the workgroup) and takes a quarter of its steps
+    for (int64_t rb = r0; rb < r1; rb += kValueSpanRows) {
+        const int nsub = (int)((min(r1, rb + kValueSpanRows) - rb + 63) >> 6);
+        Span an{~0u, ~0u}, sp{~0u, ~0u};
+        int sha = 0, sh = 0;
+        if (a.s.and_words) {
+            const int64_t p = a.s.and_bit0 + rb;
+            an = load_span(a.s.and_words, p >> 5, n_aw, lane);
+            sha = (int)(p & 31);
+            if (__builtin_amdgcn_ballot_w64((an.lo | an.hi) != 0u) == 0ull) continue;
+        }
+        if (words) {
+            const int64_t p = a.s.bit0 + rb;
+            sp = load_span(words, p >> 5, n_w, lane);
+            sh = (int)(p & 31);
+            if (__builtin_amdgcn_ballot_w64((sp.lo | sp.hi) != 0u) == 0ull) continue;
+        }
+        for (int s = w; s < nsub; s += kValWaves) {
+            const int64_t row0 = rb + (int64_t)s * 64;
+            const int64_t nvalid = r1 - row0;
+            const uint64_t vm = nvalid >= 64 ? ~0ull : ((1ull << nvalid) - 1ull);
+            const uint64_t m = window64(sp, s, sh) & window64(an, s, sha) & vm;
+            if (m == 0ull) continue;
+            uint64_t key = 0ull;
+            if ((m >> lane) & 1ull) {
+                const uint32_t k32 = value_key(a.s.values[row0 + lane], a.s.dtype);
+                if (k32 != 0u) key = ((uint64_t)(k32 ^ a.flip) << 32) | (uint32_t)~(uint32_t)(row0 + lane);      // never 0: row < 2^32 - 1
+            }
+            top_push(cand, &cnt_sh, key > tau, key, lane);
+        }
+        __syncthreads();
+        tau = top_cut(cand, &cnt_sh, K, false, tau, tid);
+    }
+    __syncthreads();
+    (void)top_cut(cand, &cnt_sh, K, true, tau, tid);
+    uint64_t* dst = a.scratch + (b * (size_t)a.chunks + (size_t)c) * (size_t)K;
+    for (int i = tid; i < K; i += kValThreads) dst[i] = cand[i];                     // sorted, zeros behind the last
+}
+
+__global__ __launch_bounds__(kValThreads) void value_topk_merge_kernel(TopArgs a) {
+    __shared__ uint64_t cand[kTopCap];
+    __shared__ int cnt_sh;
+    const int tid = threadIdx.x, lane = tid & 63;
+    constexpr int SB = (kTopCap - kTopKeep) / kValThreads;       // steps between cuts
+    const int K = a.k;
+    const size_t b = blockIdx.x;
+    const uint64_t* src = a.scratch + b * (size_t)a.chunks * (size_t)K;
+    const int64_t n = a.chunks * K;
+    if (tid == 0) cnt_sh = 0;
+    __syncthreads();
+    uint64_t tau = 0ull;
+    const int64_t iters = (n + kValThreads - 1) / kValThreads;
+    for (int64_t it0 = 0; it0 < iters; it0 += SB) {
+        const int64_t it1 = min(iters, it0 + SB);
+        for (int64_t it = it0; it < it1; ++it) {
+            const int64_t i = it * kValThreads + tid;
+            const uint64_t key = i < n ? src[i] : 0ull;
+            top_push(cand, &cnt_sh, key > tau, key, lane);
+        }
+        __syncthreads();
+        tau = top_cut(cand, &cnt_sh, K, it1 >= iters, tau, tid);
+    }
+    const uint32_t miss = a.s.dtype == VS_VAL_F32 ? kValueNanF32 : kValueMissI32;
+    for (int i = tid; i < K; i += kValThreads) {                  // every slot is written: id -1 / the missing sentinel behind the last
+        const uint64_t key = cand[i];
+        const uint32_t row = ~(uint32_t)key;
+        a.out_ids[b * (size_t)K + i] = key ? (int64_t)row + a.id_offset : -1;
+        a.out_values[b * (size_t)K + i] = key ? a.s.values[row] : miss;
+    }
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------------------------------------
+// the staged inputs of a set: bitmap words, a caller's and-bitmap, the values
+struct SetStage {
+    Staged w, a, v;
+    int in(const uint32_t* words, int64_t bit0, int64_t ld_words, const uint32_t* and_user, const uint32_t* and_dev, int32_t B, const void* values,
+           int dtype, int64_t n_rows, const ValuePlan& plan, bool dev, hipStream_t s, SetArgs* out) {
+        const int64_t span = (bit0 + n_rows + 31) >> 5;
+        uint32_t *d_w, *d_a, *d_v;
+        VS_TRY(w.in(words, (size_t)((B - 1) * ld_words + span), dev, true, s, &d_w));
+        VS_TRY(a.in(and_user, (size_t)span, dev, true, s, &d_a));
+        VS_TRY(v.in(static_cast<const uint32_t*>(values), (size_t)n_rows, dev, true, s, &d_v));
+        out->words = d_w;
+        out->bit0 = bit0;
+        out->ld_words = words ? ld_words : 0;
+        out->and_words = and_user ? d_a : and_dev;
+        out->and_bit0 = and_user ? bit0 : 0;
+        out->values = d_v;
+        out->dtype = dtype;
+        out->n_rows = n_rows;
+        out->B = B;
+        out->rows_per_chunk = plan.rows_per_chunk;
+        return VS_OK;
+    }
+};
+
+int finish_call(bool dev, void* stream, hipStream_t s) {
+    if (!stream || !dev) VS_HIP(hipStreamSynchronize(s));
+    if (Profiler::get().on) Profiler::get().drain();
+    return VS_OK;
+}
+
+// One stats call on `device`.  and_user: a caller's second bitmap (of the kind of the other pointers, at bit0); and_dev: a device bitmap at
+// bit 0 (an index's live rows).  At most one of the two.
+int stats_call(int device, const uint32_t* words, int64_t bit0, int64_t ld_words, const uint32_t* and_user, const uint32_t* and_dev, int32_t B,
+               const void* values, int dtype, int64_t n_rows, const ValuePlan& plan, int64_t* count, int64_t* missing, void* out_min, void* out_max,
+               int64_t* sum, void* stream) {
+    const void* ptrs[8] = {words, and_user, values, count, missing, out_min, out_max, sum};
+    const char* names[8] = {"words", "and_words", "values", "count", "missing", "out_min", "out_max", "sum"};
+    bool dev = false;
+    VS_TRY(pointers_kind(ptrs, names, 8, device, &dev));
+    VS_HIP(hipSetDevice(device));
+    hipStream_t s = (hipStream_t)stream;
+    SetStage st;
+    StatsArgs a{};
+    VS_TRY(st.in(words, bit0, ld_words, and_user, and_dev, B, values, dtype, n_rows, plan, dev, s, &a.s));
+    DevBuf out;                                                   // host outputs: count, missing, sum [B] x 8 bytes, then min, max [B] x 4
+    if (dev) {
+        a.count = reinterpret_cast<unsigned long long*>(count);
+        a.missing = reinterpret_cast<unsigned long long*>(missing);
+        a.sum = reinterpret_cast<unsigned long long*>(sum);
+        a.min_key = static_cast<uint32_t*>(out_min);
+        a.max_key = static_cast<uint32_t*>(out_max);
+    } else {
+        VS_TRY(out.alloc((size_t)B * 32));
+        a.count = out.as<unsigned long long>();
+        a.missing = a.count + B;
+        a.sum = a.missing + B;
+        a.min_key = reinterpret_cast<uint32_t*>(a.sum + B);
+        a.max_key = a.min_key + B;
+    }
+    VS_HIP(hipMemsetAsync(a.count, 0, (size_t)B * 8, s));
+    VS_HIP(hipMemsetAsync(a.missing, 0, (size_t)B * 8, s));
+    VS_HIP(hipMemsetAsync(a.sum, 0, (size_t)B * 8, s));
+    VS_HIP(hipMemsetAsync(a.min_key, 0xFF, (size_t)B * 4, s));
+    VS_HIP(hipMemsetAsync(a.max_key, 0, (size_t)B * 4, s));
+    {
+        ProfScope prof("value_stats", s);
+        const dim3 grid((unsigned)plan.chunks, (unsigned)ceil_div64(B, plan.qt));
+        if (plan.qt == 8) hipLaunchKernelGGL(value_stats_kernel<8>, grid, dim3(kValThreads), 0, s, a);
+        else hipLaunchKernelGGL(value_stats_kernel<1>, grid, dim3(kValThreads), 0, s, a);
+        hipLaunchKernelGGL(value_finish_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, a.min_key, a.max_key, a.count, B, dtype);
+    }
+    const hipError_t le = hipGetLastError();
+    if (le != hipSuccess) {
+        (void)hipStreamSynchronize(s);                              // staging buffers die here
+        return fail(VS_EHIP, "value_stats launch failed: %s", hipGetErrorString(le));
+    }
+    VS_STAGE("value_stats", s);
+    if (!dev) {
+        VS_HIP(hipMemcpyAsync(count, a.count, (size_t)B * 8, hipMemcpyDeviceToHost, s));
+        VS_HIP(hipMemcpyAsync(missing, a.missing, (size_t)B * 8, hipMemcpyDeviceToHost, s));
+        VS_HIP(hipMemcpyAsync(sum, a.sum, (size_t)B * 8, hipMemcpyDeviceToHost, s));
+        VS_HIP(hipMemcpyAsync(out_min, a.min_key, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+        VS_HIP(hipMemcpyAsync(out_max, a.max_key, (size_t)B * 4, hipMemcpyDeviceToHost, s));
+    }
+    return finish_call(dev, stream, s);
+}
+
+int hist_call(int device, const uint32_t* words, int64_t bit0, int64_t ld_words, const uint32_t* and_user, const uint32_t* and_dev, int32_t B,
+              const void* values, int dtype, int64_t n_rows, const void* edges, int32_t n_edges, const ValuePlan& plan, int64_t* counts,
+              int64_t ld_counts, int64_t* below, int64_t* above, int64_t* missing, void* stream) {
+    const void* ptrs[8] = {words, and_user, values, edges, counts, below, above, missing};
+    const char* names[8] = {"words", "and_words", "values", "edges", "counts", "below", "above", "missing"};
+    bool dev = false;
+    VS_TRY(pointers_kind(ptrs, names, 8, device, &dev));
+    VS_HIP(hipSetDevice(device));
+    hipStream_t s = (hipStream_t)stream;
+    SetStage st;
+    Staged st_e;
+    HistArgs a{};
+    VS_TRY(st.in(words, bit0, ld_words, and_user, and_dev, B, values, dtype, n_rows, plan, dev, s, &a.s));
+    uint32_t* d_e;
+    VS_TRY(st_e.in(static_cast<const uint32_t*>(edges), (size_t)n_edges, dev, true, s, &d_e));
+    a.edges = d_e;
+    a.n_edges = n_edges;
+    const int32_t n_bins = n_edges - 1;
+    const size_t n_cnt = (size_t)B * (size_t)n_bins;
+    DevBuf out;
+    if (dev) {
+        a.counts = reinterpret_cast<unsigned long long*>(counts);
+        a.ld_counts = ld_counts;
+        a.below = reinterpret_cast<unsigned long long*>(below);
+        a.above = reinterpret_cast<unsigned long long*>(above);
+        a.missing = reinterpret_cast<unsigned long long*>(missing);
+        if (ld_counts == n_bins || B == 1) VS_HIP(hipMemsetAsync(a.counts, 0, n_cnt * 8, s));
+        else VS_HIP(hipMemset2DAsync(a.counts, (size_t)ld_counts * 8, 0, (size_t)n_bins * 8, (size_t)B, s));
+        VS_HIP(hipMemsetAsync(a.below, 0, (size_t)B * 8, s));
+        VS_HIP(hipMemsetAsync(a.above, 0, (size_t)B * 8, s));
+        VS_HIP(hipMemsetAsync(a.missing, 0, (size_t)B * 8, s));
+    } else {
+        VS_TRY(out.alloc((n_cnt + 3 * (size_t)B) * 8));
+        a.counts = out.as<unsigned long long>();
+        a.ld_counts = n_bins;
+        a.below = a.counts + n_cnt;
+        a.above = a.below + B;
+        a.missing = a.above + B;
+        VS_HIP(hipMemsetAsync(out.p, 0, out.bytes, s));
+    }
+    {
+        ProfScope prof("value_histogram", s);
+        const dim3 grid((unsigned)plan.chunks, (unsigned)ceil_div64(B, plan.qt));
+        const size_t lds = ((size_t)n_edges + (size_t)plan.qt * ((size_t)n_edges + 2)) * 4;      // at most 37 KB
+        if (plan.qt == 8) hipLaunchKernelGGL(value_hist_kernel<8>, grid, dim3(kValThreads), lds, s, a);
+        else hipLaunchKernelGGL(value_hist_kernel<1>, grid, dim3(kValThreads), lds, s, a);
+    }
+    const hipError_t le = hipGetLastError();
+    if (le != hipSuccess) {
+        (void)hipStreamSynchronize(s);                              // staging buffers die here
+        return fail(VS_EHIP, "value_histogram launch failed: %s", hipGetErrorString(le));
+    }
+    VS_STAGE("value_histogram", s);
+    if (!dev) {
+        VS_HIP(hipMemcpy2DAsync(counts, (size_t)ld_counts * 8, a.counts, (size_t)n_bins * 8, (size_t)n_bins * 8, (size_t)B, hipMemcpyDeviceToHost, s));
+        VS_HIP(hipMemcpyAsync(below, a.below, (size_t)B * 8, hipMemcpyDeviceToHost, s));
+        VS_HIP(hipMemcpyAsync(above, a.above, (size_t)B * 8, hipMemcpyDeviceToHost, s));
+        VS_HIP(hipMemcpyAsync(missing, a.missing, (size_t)B * 8, hipMemcpyDeviceToHost, s));
+    }
+    return finish_call(dev, stream, s);
+}
+
+int topk_call(int device, const uint32_t* words, int64_t bit0, int64_t ld_words, const uint32_t* and_user, const uint32_t* and_dev, int32_t B,
+              const void* values, int dtype, int64_t n_rows, int32_t k, int descending, int64_t id_offset, const ValuePlan& plan, int64_t* out_ids,
+              void* out_values, void* stream) {
+    const void* ptrs[5] = {words, and_user, values, out_ids, out_values};
+    const char* names[5] = {"words", "and_words", "values", "out_ids", "out_values"};
+    bool dev = false;
+    VS_TRY(pointers_kind(ptrs, names, 5, device, &dev));
+    VS_HIP(hipSetDevice(device));
+    hipStream_t s = (hipStream_t)stream;
+    SetStage st;
+    Staged st_i, st_v;
+    DevBuf scratch;
+    TopArgs a{};
+    VS_TRY(st.in(words, bit0, ld_words, and_user, and_dev, B, values, dtype, n_rows, plan, dev, s, &a.s));
+    VS_TRY(st_i.in(out_ids, (size_t)B * k, dev, false, s, &a.out_ids));
+    VS_TRY(st_v.in(static_cast<uint32_t*>(out_values), (size_t)B * k, dev, false, s, &a.out_values));
+    VS_TRY(scratch.alloc((size_t)B * (size_t)plan.chunks * (size_t)k * 8));
+    a.k = k;
+    a.flip = descending ? 0u : 0xFFFFFFFFu;
+    a.chunks = plan.chunks;
+    a.scratch = scratch.as<uint64_t>();
+    a.id_offset = id_offset;
+    {
+        ProfScope prof("value_topk", s);
+        hipLaunchKernelGGL(value_topk_chunk_kernel, dim3((unsigned)plan.chunks, (unsigned)B), dim3(kValThreads), 0, s, a);
+        hipLaunchKernelGGL(value_topk_merge_kernel, dim3((unsigned)B), dim3(kValThreads), 0, s, a);
+    }
+    const hipError_t le = hipGetLastError();
+    if (le != hipSuccess) {
+        (void)hipStreamSynchronize(s);                              // staging buffers and the scratch die here
+        return fail(VS_EHIP, "value_topk launch failed: %s", hipGetErrorString(le));
+    }
+    VS_STAGE("value_topk", s);
+    if (!dev) {
+        VS_TRY(st_i.back(s));
+        VS_TRY(st_v.back(s));
+    }
+    VS_HIP(hipStreamSynchronize(s));                                // the scratch is freed before the call returns
+    if (Profiler::get().on) Profiler::get().drain();
+    return VS_OK;
+}
+
+// host arrays are looked at before the device is (a pointer the runtime does not know, or no runtime at all: a host pointer)
+int check_edges(const void* edges, int32_t n_edges, int dtype) {
+    if (is_device_ptr(edges)) return VS_OK;
+    char msg[256];
+    return plan_or_fail(value_check_edges_host(static_cast<const uint32_t*>(edges), n_edges, dtype, msg, sizeof msg), msg);
+}
+
+int check_stats(const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B, const void* values, int dtype, int64_t n_rows, int64_t rows_per_chunk,
+                bool have_outputs, ValuePlan* plan) {
+    char msg[256];
+    return plan_or_fail(value_check_set(values && have_outputs, words != nullptr, bit0, ld_words, B, dtype, n_rows, 0, rows_per_chunk, 8, plan, msg,
+                                        sizeof msg), msg);
+}
+
+int check_hist(const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B, const void* values, int dtype, int64_t n_rows, const void* edges,
+               int32_t n_edges, int64_t rows_per_chunk, int64_t ld_counts, bool have_outputs, ValuePlan* plan) {
+    char msg[256];
+    if (!values || !edges || !have_outputs) return fail(VS_EINVAL, "NULL argument");
+    VS_TRY(plan_or_fail(value_check_hist(n_edges, ld_counts, msg, sizeof msg), msg));
+    VS_TRY(plan_or_fail(value_check_set(true, words != nullptr, bit0, ld_words, B, dtype, n_rows, n_edges + 2, rows_per_chunk, 8, plan, msg, sizeof msg),
+                        msg));
+    return check_edges(edges, n_edges, dtype);
+}
+
+int check_topk(const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B, const void* values, int dtype, int64_t n_rows, int32_t k,
+               int64_t rows_per_chunk, bool have_outputs, ValuePlan* plan) {
+    char msg[256];
+    VS_TRY(plan_or_fail(value_check_set(values && have_outputs, words != nullptr, bit0, ld_words, B, dtype, n_rows, 0, rows_per_chunk, 1, plan, msg,
+                                        sizeof msg), msg));
+    return plan_or_fail(value_check_topk(k, B, *plan, msg, sizeof msg), msg);
+}
+
+const uint32_t* live_words(vs_index* idx) { return idx->has_tomb ? idx->live.as<uint32_t>() : nullptr; }
+
+}  // namespace
+
+extern "C" int vs_value_plan(int64_t n_rows, int32_t B, int32_t n_bins, int per_query, int64_t rows_per_chunk, int32_t* out_qt, int64_t* out_chunks,
+                             int64_t* out_rows_per_chunk) {
+    if (!out_qt || !out_chunks || !out_rows_per_chunk) return fail(VS_EINVAL, "NULL argument");
+    ValuePlan p;
+    char msg[256];
+    VS_TRY(plan_or_fail(value_plan(n_rows, B, n_bins, per_query != 0, rows_per_chunk, 8, &p, msg, sizeof msg), msg));
+    *out_qt = p.qt;
+    *out_chunks = p.chunks;
+    *out_rows_per_chunk = p.rows_per_chunk;
+    return VS_OK;
+}
+
+extern "C" int vs_value_range_bitmaps(const void* values, int dtype, int64_t n_rows, const void* lo, const void* hi, int32_t B, int64_t bit0,
+                                      uint32_t* out_words, int64_t ld_words, int device, void* stream) {
+    char msg[256];
+    VS_TRY(plan_or_fail(value_check_ranges(values && lo && hi && out_words, dtype, n_rows, B, bit0, ld_words, msg, sizeof msg), msg));
+    if (!is_device_ptr(lo) && !is_device_ptr(hi))
+        VS_TRY(plan_or_fail(value_check_bounds_host(static_cast<const uint32_t*>(lo), static_cast<const uint32_t*>(hi), B, dtype, msg, sizeof msg), msg));
+    VS_TRY(device_in_range(device));
+    const void* ptrs[4] = {values, lo, hi, out_words};
+    const char* names[4] = {"values", "lo", "hi", "out_words"};
+    bool dev = false;
+    VS_TRY(pointers_kind(ptrs, names, 4, device, &dev));
+    VS_HIP(hipSetDevice(device));
+    hipStream_t s = (hipStream_t)stream;
+    RangeArgs a{};
+    a.dtype = dtype;
+    a.n_rows = n_rows;
+    a.B = B;
+    a.bit0 = bit0;
+    a.n_words = (bit0 + n_rows + 31) >> 5;
+    Staged st_v, st_l, st_h, st_o;
+    uint32_t *d_v, *d_l, *d_h;
+    VS_TRY(st_v.in(static_cast<const uint32_t*>(values), (size_t)n_rows, dev, true, s, &d_v));
+    VS_TRY(st_l.in(static_cast<const uint32_t*>(lo), (size_t)B, dev, true, s, &d_l));
+    VS_TRY(st_h.in(static_cast<const uint32_t*>(hi), (size_t)B, dev, true, s, &d_h));
+    // (a host buffer's gaps between the rows come back as they went in: the staged copy starts from the caller's words)
+    VS_TRY(st_o.in(out_words, (size_t)(B - 1) * (size_t)ld_words + (size_t)a.n_words, dev, true, s, &a.out));
+    a.values = d_v;
+    a.lo = d_l;
+    a.hi = d_h;
+    a.ld = ld_words;
+    {
+        ProfScope prof("value_range_bitmaps", s);
+        const int64_t waves = (a.n_words + 1) / 2;
+        hipLaunchKernelGGL(value_range_kernel, dim3((unsigned)((waves + kValWaves - 1) / kValWaves)), dim3(kValThreads), 0, s, a);
+    }
+    const hipError_t le = hipGetLastError();
+    if (le != hipSuccess) {
+        (void)hipStreamSynchronize(s);
+        return fail(VS_EHIP, "value_range_bitmaps launch failed: %s", hipGetErrorString(le));
+    }
+    VS_STAGE("value_range_bitmaps", s);
+    if (!dev) VS_TRY(st_o.back(s));
+    return finish_call(dev, stream, s);
+}
+
+extern "C" int vs_value_stats(const uint32_t* words, int64_t bit0, int64_t ld_words, const uint32_t* and_words, int32_t B, const void* values,
+                              int dtype, int64_t n_rows, int64_t rows_per_chunk, int64_t* count, int64_t* missing, void* out_min, void* out_max,
+                              int64_t* sum, int device, void* stream) {
+    ValuePlan plan;
+    VS_TRY(check_stats(words, bit0, ld_words, B, values, dtype, n_rows, rows_per_chunk, count && missing && out_min && out_max && sum, &plan));
+    VS_TRY(device_in_range(device));
+    return stats_call(device, words, bit0, ld_words, and_words, nullptr, B, values, dtype, n_rows, plan, count, missing, out_min, out_max, sum, stream);
+}
+
+extern "C" int vs_index_value_stats(vs_index* idx, const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B, const void* values, int dtype,
+                                    int64_t rows_per_chunk, int64_t* count, int64_t* missing, void* out_min, void* out_max, int64_t* sum,
+                                    void* stream) {
+    if (!idx) return fail(VS_EINVAL, "NULL argument");
+    ValuePlan plan;
+    VS_TRY(check_stats(words, bit0, ld_words, B, values, dtype, idx->n_rows, rows_per_chunk, count && missing && out_min && out_max && sum, &plan));
+    // tombstones are ANDed in, as every search does (the live bitmap starts at bit 0 whatever bit0 is)
+    return stats_call(idx->device, words, bit0, ld_words, nullptr, live_words(idx), B, values, dtype, idx->n_rows, plan, count, missing, out_min, out_max,
+                      sum, stream);
+}
+
+extern "C" int vs_value_histogram(const uint32_t* words, int64_t bit0, int64_t ld_words, const uint32_t* and_words, int32_t B, const void* values,
+                                  int dtype, int64_t n_rows, const void* edges, int32_t n_edges, int64_t rows_per_chunk, int64_t* counts,
+                                  int64_t ld_counts, int64_t* below, int64_t* above, int64_t* missing, int device, void* stream) {
+    ValuePlan plan;
+    VS_TRY(check_hist(words, bit0, ld_words, B, values, dtype, n_rows, edges, n_edges, rows_per_chunk, ld_counts, counts && below && above && missing,
+                      &plan));
+    VS_TRY(device_in_range(device));
+    return hist_call(device, words, bit0, ld_words, and_words, nullptr, B, values, dtype, n_rows, edges, n_edges, plan, counts, ld_counts, below, above,
+                     missing, stream);
+}
+
+extern "C" int vs_index_value_histogram(vs_index* idx, const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B, const void* values,
+                                        int dtype, const void* edges, int32_t n_edges, int64_t rows_per_chunk, int64_t* counts, int64_t ld_counts,
+                                        int64_t* below, int64_t* above, int64_t* missing, void* stream) {
+    if (!idx) return fail(VS_EINVAL, "NULL argument");
+    ValuePlan plan;
+    VS_TRY(check_hist(words, bit0, ld_words, B, values, dtype, idx->n_rows, edges, n_edges, rows_per_chunk, ld_counts,
+                      counts && below && above && missing, &plan));
+    return hist_call(idx->device, words, bit0, ld_words, nullptr, live_words(idx), B, values, dtype, idx->n_rows, edges, n_edges, plan, counts, ld_counts,
+                     below, above, missing, stream);
+}
+
+extern "C" int vs_value_topk(const uint32_t* words, int64_t bit0, int64_t ld_words, const uint32_t* and_words, int32_t B, const void* values,
+                             int dtype, int64_t n_rows, int32_t k, int descending, int64_t id_offset, int64_t rows_per_chunk, int64_t* out_ids,
+                             void* out_values, int device, void* stream) {
+    ValuePlan plan;
+    VS_TRY(check_topk(words, bit0, ld_words, B, values, dtype, n_rows, k, rows_per_chunk, out_ids && out_values, &plan));
+    VS_TRY(device_in_range(device));
+    return topk_call(device, words, bit0, ld_words, and_words, nullptr, B, values, dtype, n_rows, k, descending, id_offset, plan, out_ids, out_values,
+                     stream);
+}
+
+extern "C" int vs_index_value_topk(vs_index* idx, const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B, const void* values, int dtype,
+                                   int32_t k, int descending, int64_t id_offset, int64_t rows_per_chunk, int64_t* out_ids, void* out_values,
+                                   void* stream) {
+    if (!idx) return fail(VS_EINVAL, "NULL argument");
+    ValuePlan plan;
+    VS_TRY(check_topk(words, bit0, ld_words, B, values, dtype, idx->n_rows, k, rows_per_chunk, out_ids && out_values, &plan));
+    return topk_call(idx->device, words, bit0, ld_words, nullptr, live_words(idx), B, values, dtype, idx->n_rows, k, descending, id_offset, plan, out_ids,
+                     out_values, stream);
+}

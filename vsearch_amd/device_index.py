@@ -1189,6 +1189,235 @@ def label_bitmaps(labels, values, bit0: int = 0, ld_words=None, device: int = 0)
     return out
 
 
+# ---- numeric fields: range filters, stats, histograms and sort by value (vs_value_range_bitmaps, vs_value_stats, vs_value_histogram, vs_value_topk)
+MAX_VALUE_RANGES, MAX_VALUE_EDGES, MAX_VALUE_TOPK = nat.VALUE_MAX_RANGES, nat.VALUE_MAX_EDGES, nat.VALUE_MAX_TOPK
+INT32_MISSING = -0x80000000                              # the missing sentinel of an int32 field (a float field's is NaN)
+
+
+class ValueStats(NamedTuple):
+    """value_stats: per query, count = the documents of the set that have a value, missing = those without one (count + missing = the size
+    of the set); min / max in the field's type (the missing sentinel -- NaN / INT32_MIN -- when count is 0); sum int64: the exact sum of an
+    int32 field, the sum of round(clamp(v, +-2^20) * 2^24) of a float field (the fixed point of the term sums), modulo 2^64."""
+    count: Any
+    missing: Any
+    min: Any
+    max: Any
+    sum: Any
+
+    def mean(self):
+        """the mean value per query in fp64 (NaN for a set without values)"""
+        is_t = _is_torch(self.sum)
+        s, c = (self.sum.cpu().numpy(), self.count.cpu().numpy()) if is_t else (np.asarray(self.sum), np.asarray(self.count))
+        mn = self.min.cpu().numpy() if is_t else np.asarray(self.min)
+        scale = 2.0 ** -nat.TERM_FX_SHIFT if mn.dtype.kind == "f" else 1.0
+        with np.errstate(divide="ignore", invalid="ignore"):
+            m = np.where(c > 0, s.astype(np.float64) * scale / c.astype(np.float64), np.nan)
+        if is_t:
+            import torch
+            return torch.from_numpy(m).to(self.sum.device)
+        return m
+
+
+class ValueHistogram(NamedTuple):
+    """histogram: counts int64 [B, E - 1] -- bin i holds edges[i] <= v < edges[i + 1]; below: v < edges[0]; above: v >= edges[E - 1]; missing:
+    documents of the set without a value; total = counts.sum(1) + below + above + missing, the size of the set."""
+    counts: Any
+    below: Any
+    above: Any
+    missing: Any
+    total: Any
+
+
+class SortedResults(NamedTuple):
+    """top_by_value / value_topk: per query the k documents of the set with the largest (descending) or smallest values, ties by id
+    ascending: ids int64 [B, k], values [B, k] in the field's type; id -1 / the missing sentinel behind the last."""
+    ids: Any
+    values: Any
+
+
+def value_plan(n_rows: int, B: int, n_bins: int, per_query: bool, rows_per_chunk: int = 0):
+    """The launch vs_value_stats / vs_value_histogram take for these arguments (vs_value_plan; pure host arithmetic, no GPU needed) ->
+    (qt, chunks, rows_per_chunk): qt = queries a workgroup serves; n_bins = n_edges + 2 for a histogram, 0 for stats."""
+    qt, chunks, rpc = C.c_int32(0), C.c_int64(0), C.c_int64(0)
+    nat.check(nat.lib().vs_value_plan(int(n_rows), int(B), int(n_bins), 1 if per_query else 0, int(rows_per_chunk), C.byref(qt), C.byref(chunks),
+                                      C.byref(rpc)))
+    return qt.value, chunks.value, rpc.value
+
+
+def value_column(values, missing=None, what="values"):
+    """The values of a numeric field -> a contiguous 1-D ndarray, int32 or float32, with the missing sentinel written in.  Integer input
+    becomes int32: a value outside [-2^31 + 1, 2^31 - 1] raises (INT32_MIN is the sentinel: say missing=).  Floating input becomes float32
+    and NaN means missing.  missing: optional bool mask [n] of the documents without a value.  Host logic only."""
+    v = values.detach().cpu().numpy() if _is_torch(values) else np.asarray(values)
+    v = np.atleast_1d(v)
+    if v.ndim != 1:
+        raise ValueError(f"{what} must be 1-D (one value per document), got {v.ndim} dimensions")
+    if v.dtype == np.bool_ or v.dtype.kind not in "iuf":
+        raise TypeError(f"{what} must be integers or floats, got {v.dtype}")
+    m = None
+    if missing is not None:
+        m = missing.detach().cpu().numpy() if _is_torch(missing) else np.asarray(missing)
+        if m.dtype != np.bool_ or m.shape != v.shape:
+            raise ValueError(f"missing must be a bool mask of shape {v.shape}, got {m.dtype} {m.shape}")
+        v = np.where(m, v.dtype.type(0), v)                       # (what a masked entry holds is not looked at)
+    if v.dtype.kind in "iu":
+        if v.size and (int(v.min()) <= INT32_MISSING or int(v.max()) > 0x7FFFFFFF):
+            raise ValueError(f"{what}: an integer field holds [-2^31 + 1, 2^31 - 1] (-2^31 marks a missing value: pass missing=)")
+        out = v.astype(np.int32)
+    else:
+        with np.errstate(over="ignore"):
+            out = v.astype(np.float32)
+    if m is not None:
+        out[m] = INT32_MISSING if out.dtype == np.int32 else np.nan
+    return np.ascontiguousarray(out)
+
+
+def _value_dtype(values):
+    """numpy / torch values -> VS_VAL_F32 or VS_VAL_I32 (TypeError for anything else: value_column converts)"""
+    dt = str(values.dtype).replace("torch.", "")
+    if dt == "float32":
+        return nat.VAL_F32
+    if dt == "int32":
+        return nat.VAL_I32
+    raise TypeError(f"a value column is float32 or int32 (value_column() converts), got {values.dtype}")
+
+
+def _value_args(values, n_rows, rows_per_chunk=0):
+    """Argument checks of a value call that need no device -> (vs dtype, rows_per_chunk)"""
+    if isinstance(rows_per_chunk, bool) or not isinstance(rows_per_chunk, (int, np.integer)):
+        raise TypeError(f"rows_per_chunk must be an int, got {type(rows_per_chunk).__name__}")
+    if rows_per_chunk < 0 or rows_per_chunk % 64:
+        raise ValueError(f"rows_per_chunk must be 0 (automatic) or a positive multiple of 64, got {rows_per_chunk}")
+    if not hasattr(values, "shape") or len(values.shape) != 1 or int(values.shape[0]) != int(n_rows):
+        raise ValueError(f"values must hold one entry per row ({int(n_rows)}), got shape {tuple(getattr(values, 'shape', ()))}")
+    return _value_dtype(values), int(rows_per_chunk)
+
+
+def _np_value_dtype(dt):
+    return np.float32 if dt == nat.VAL_F32 else np.int32
+
+
+def _value_bounds(lo, hi, dt):
+    """lo / hi of a range (None = an open end; scalars, or sequences of B) -> (lo [B], hi [B] in the field's type, scalar?).  A bound that is
+    missing (NaN), or an integer bound outside the field's range, raises."""
+    npdt = _np_value_dtype(dt)
+    open_lo, open_hi = (-np.inf, np.inf) if dt == nat.VAL_F32 else (INT32_MISSING + 1, 0x7FFFFFFF)
+    def one(x, opened, name):
+        if x is None:
+            return np.asarray([opened]), True
+        a = x.detach().cpu().numpy() if _is_torch(x) else np.asarray([opened if e is None else e for e in x] if isinstance(x, (list, tuple)) else x)
+        scalar = a.ndim == 0
+        a = np.atleast_1d(a)
+        if a.ndim != 1 or a.dtype == np.bool_ or a.dtype.kind not in "iuf":
+            raise TypeError(f"{name}: a number, None, or a 1-D sequence of them")
+        if a.dtype.kind == "f" and np.isnan(a).any():
+            raise ValueError(f"{name}: NaN is no bound (None is an open end)")
+        if dt == nat.VAL_I32:
+            if a.dtype.kind == "f":                               # lo <= v over integers v: round the bound inwards
+                a = np.ceil(a) if name == "lo" else np.floor(a)
+                a = np.where(np.isinf(a), np.where(a < 0, open_lo, open_hi), a)      # (+-inf: an open end)
+            if (a < open_lo).any() or (a > open_hi).any():
+                raise ValueError(f"{name}: a bound of an integer field lies in [-2^31 + 1, 2^31 - 1] (None is an open end)")
+            a = a.astype(np.int64)
+        return a, scalar
+    l, sl = one(lo, open_lo, "lo")
+    h, sh = one(hi, open_hi, "hi")
+    B = max(l.shape[0], h.shape[0])
+    if l.shape[0] not in (1, B) or h.shape[0] not in (1, B):
+        raise ValueError(f"lo holds {l.shape[0]} bounds, hi {h.shape[0]}")
+    if not 1 <= B <= MAX_VALUE_RANGES:
+        raise ValueError(f"the number of ranges must be in 1..{MAX_VALUE_RANGES}, got {B}")
+    with np.errstate(over="ignore"):
+        l, h = np.broadcast_to(l, (B,)).astype(npdt), np.broadcast_to(h, (B,)).astype(npdt)
+    return np.ascontiguousarray(l), np.ascontiguousarray(h), sl and sh
+
+
+def _value_edges(edges, dt):
+    """edges of a histogram -> ndarray [E] in the field's type: 2..1025 of them, strictly ascending, none missing"""
+    e = edges.detach().cpu().numpy() if _is_torch(edges) else np.asarray(edges)
+    if e.ndim != 1 or e.dtype == np.bool_ or e.dtype.kind not in "iuf":
+        raise TypeError("edges: a 1-D sequence of numbers")
+    if not 2 <= e.shape[0] <= MAX_VALUE_EDGES:
+        raise ValueError(f"a histogram takes 2..{MAX_VALUE_EDGES} edges, got {e.shape[0]}")
+    if e.dtype.kind == "f" and np.isnan(e).any():
+        raise ValueError("edges: NaN is no edge")
+    if dt == nat.VAL_I32:
+        if e.dtype.kind == "f" and (e != np.floor(e)).any():
+            raise ValueError("edges of an integer field must be integers")
+        if int(e.min()) <= INT32_MISSING or int(e.max()) > 0x7FFFFFFF:
+            raise ValueError("edges of an integer field lie in [-2^31 + 1, 2^31 - 1]")
+    with np.errstate(over="ignore"):
+        out = np.ascontiguousarray(e.astype(_np_value_dtype(dt)))
+    if not (out[1:] > out[:-1]).all():
+        raise ValueError("edges must be strictly ascending (in the field's type)")
+    return out
+
+
+def _value_topk_args(k, descending=True):
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+        raise TypeError(f"k must be an int, got {type(k).__name__}")
+    if not 1 <= int(k) <= MAX_VALUE_TOPK:
+        raise ValueError(f"k must be in 1..{MAX_VALUE_TOPK}, got {int(k)}")
+    return int(k), 1 if descending else 0
+
+
+def _values_on(values, device: int):
+    """values (numpy / torch, float32 or int32) -> contiguous tensor on GPU `device` (the tensor itself when it is one already)"""
+    import torch
+    t = values.detach() if _is_torch(values) else torch.from_numpy(np.ascontiguousarray(values))
+    return t.to(torch.device("cuda", device)).contiguous()
+
+
+def _value_keys(t):
+    """The uint32 order keys of a float32 / int32 tensor, as int64 (0 = missing): the rule of value_check.h, for merging shard results"""
+    import torch
+    u = t.contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    if t.dtype == torch.int32:
+        return u ^ 0x80000000
+    mag = u & 0x7FFFFFFF
+    u = torch.where(mag == 0, torch.zeros_like(u), u)
+    key = torch.where((u & 0x80000000) != 0, ~u & 0xFFFFFFFF, u | 0x80000000)
+    return torch.where(mag > 0x7F800000, torch.zeros_like(key), key)
+
+
+def value_range_bitmaps(values, lo, hi, bit0: int = 0, ld_words=None, device: int = 0):
+    """Per range the bitmap of the rows whose value lies in it (vs_value_range_bitmaps) -> words int32 [B, ld_words]: bit bit0 + r of row b
+    is set iff row r has a value and lo[b] <= v <= hi[b]; None is an open end.  values: float32 / int32 [n_rows]; numpy in -> numpy out
+    (words behind the span are zero), torch CUDA in -> a tensor on `device`, on torch's current stream."""
+    if not hasattr(values, "shape") or len(values.shape) != 1 or int(values.shape[0]) < 1:
+        raise ValueError("values must be a non-empty 1-D array")
+    dt = _value_dtype(values)
+    l, h, _ = _value_bounds(lo, hi, dt)
+    n, B = int(values.shape[0]), int(l.shape[0])
+    if isinstance(bit0, bool) or not isinstance(bit0, (int, np.integer)) or bit0 < 0:
+        raise ValueError(f"bit0 must be an int >= 0, got {bit0!r}")
+    span = (int(bit0) + n + 31) // 32
+    ld = span if ld_words is None else int(ld_words)
+    if ld < span:
+        raise ValueError(f"ld_words = {ld} is shorter than the {span} words a bitmap spans")
+    nat.require_device()
+    if _is_torch(values) and values.is_cuda:
+        import torch
+        v = values.detach().contiguous()
+        ld_, hd_ = torch.from_numpy(np.stack([l, h])).to(v.device)                  # (one upload for both bounds)
+        out = torch.zeros((B, ld), dtype=torch.int32, device=v.device) if ld > span else torch.empty((B, ld), dtype=torch.int32, device=v.device)
+        nat.check(nat.lib().vs_value_range_bitmaps(_ptr(v), dt, n, _ptr(ld_), _ptr(hd_), B, int(bit0), _ptr(out), ld, int(device),
+                                                   current_stream(int(device))))
+        return out
+    v = np.ascontiguousarray(_host(values))
+    out = np.zeros((B, ld), dtype=np.int32)
+    nat.check(nat.lib().vs_value_range_bitmaps(_ptr(v), dt, n, _ptr(l), _ptr(h), B, int(bit0), _ptr(out), ld, int(device), None))
+    return out
+
+
+def _value_set(filter, n_rows, device):
+    """filter= of a value call -> None or a DocFilter on `device`"""
+    if filter is None:
+        return None
+    from .doc_filter import as_doc_filter
+    return as_doc_filter(filter, n_rows, device=device)
+
+
 KMEANS_UPDATE_BATCH = 64                                 # clusters whose sums one term_sums call of the update takes
 KMEANS_METRICS = ("dot", "l2")
 
@@ -1962,6 +2191,92 @@ class DeviceIndex:
         top_l, top_c = facet_topn(counts, topn, min_count, device=self.device)
         return TopFacets(*_facet_out(labels, top_l, top_c, total, other))
 
+    # ---- numeric fields: range filters, stats, histograms and sort by value (vs_index_value_stats / _histogram / _topk) --------------------
+    def _value_set_args(self, f, bit0):
+        B = f.n_queries if (f is not None and f.per_query) else 1
+        return B, (_ptr(f.words) if f is not None else None, int(bit0), f.ld if f is not None else 0, B)
+
+    def _value_stats_call(self, vals_dev, dt, f, bit0, rows_per_chunk):
+        """One vs_index_value_stats call on device buffers and torch's current stream -> (count, missing, min, max, sum) CUDA tensors [B].
+        vals_dev: float32 / int32 CUDA tensor [n_rows] on this index's device; f: None or a DocFilter there, read from bit `bit0` on."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        B, set_args = self._value_set_args(f, bit0)
+        count, missing, total = (torch.empty(B, dtype=torch.int64, device=dev) for _ in range(3))
+        lo, hi = (torch.empty(B, dtype=vals_dev.dtype, device=dev) for _ in range(2))
+        nat.check(nat.lib().vs_index_value_stats(self._h, *set_args, _ptr(vals_dev), dt, rows_per_chunk, _ptr(count), _ptr(missing), _ptr(lo),
+                                                 _ptr(hi), _ptr(total), current_stream(self.device)))
+        return count, missing, lo, hi, total
+
+    def _value_hist_call(self, vals_dev, dt, edges_dev, f, bit0, rows_per_chunk):
+        """One vs_index_value_histogram call -> (counts [B, E - 1], below, above, missing [B]) int64 CUDA tensors"""
+        import torch
+        dev = torch.device("cuda", self.device)
+        B, set_args = self._value_set_args(f, bit0)
+        E = int(edges_dev.shape[0])
+        counts = torch.empty((B, E - 1), dtype=torch.int64, device=dev)
+        below, above, missing = (torch.empty(B, dtype=torch.int64, device=dev) for _ in range(3))
+        nat.check(nat.lib().vs_index_value_histogram(self._h, *set_args, _ptr(vals_dev), dt, _ptr(edges_dev), E, rows_per_chunk, _ptr(counts), E - 1,
+                                                     _ptr(below), _ptr(above), _ptr(missing), current_stream(self.device)))
+        return counts, below, above, missing
+
+    def _value_topk_call(self, vals_dev, dt, k, descending, id_offset, f, bit0, rows_per_chunk):
+        """One vs_index_value_topk call -> (ids int64 [B, k], values [B, k]) CUDA tensors"""
+        import torch
+        dev = torch.device("cuda", self.device)
+        B, set_args = self._value_set_args(f, bit0)
+        ids = torch.empty((B, k), dtype=torch.int64, device=dev)
+        vals = torch.empty((B, k), dtype=vals_dev.dtype, device=dev)
+        nat.check(nat.lib().vs_index_value_topk(self._h, *set_args, _ptr(vals_dev), dt, k, descending, int(id_offset), rows_per_chunk, _ptr(ids),
+                                                _ptr(vals), current_stream(self.device)))
+        return ids, vals
+
+    def value_range_filter(self, values, lo=None, hi=None):
+        """The documents whose value lies in [lo, hi], both ends inclusive, as a DocFilter on the index's device (vs_value_range_bitmaps): for
+        ``search(filter=)`` and for ``&``, ``|``, ``~`` with any other filter.  values: float32 / int32 [n_rows] (``value_column`` converts);
+        None is an open end; sequences of B bounds give a per-query filter.  A document without a value never matches."""
+        from .doc_filter import DocFilter
+        n = self.n_rows
+        dt, _ = _value_args(values, n)
+        _, _, scalar = _value_bounds(lo, hi, dt)
+        nat.require_device()
+        words = value_range_bitmaps(_values_on(values, self.device), lo, hi, device=self.device)
+        return DocFilter(words[0] if scalar else words, n)
+
+    def value_stats(self, values, filter=None, rows_per_chunk: int = 0) -> ValueStats:
+        """Count, missing, min, max and sum of a numeric field over a document set -> ValueStats, one entry per query.  values: float32 /
+        int32 [n_rows] (numpy, or a tensor -- one on the index's GPU is read in place).  filter: what search(filter=) accepts -- a per-query
+        DocFilter gives one entry per query, a shared one B = 1, None every live document.  Deleted documents never count.  numpy values ->
+        numpy out; tensor values -> tensors on the index's device, enqueued on torch's current stream."""
+        n = self.n_rows
+        dt, rows_per_chunk = _value_args(values, n, rows_per_chunk)
+        nat.require_device()
+        f = _value_set(filter, n, self.device)
+        return ValueStats(*_facet_out(values, *self._value_stats_call(_values_on(values, self.device), dt, f, 0, rows_per_chunk)))
+
+    def value_histogram(self, values, edges, filter=None, rows_per_chunk: int = 0) -> ValueHistogram:
+        """How a document set spreads over the bins [edges[i], edges[i + 1]) of a numeric field -> ValueHistogram(counts [B, E - 1], below,
+        above, missing, total), int64.  edges: 2..1025 strictly ascending numbers.  values, filter, outputs as in ``value_stats``."""
+        n = self.n_rows
+        dt, rows_per_chunk = _value_args(values, n, rows_per_chunk)
+        e = _value_edges(edges, dt)
+        nat.require_device()
+        f = _value_set(filter, n, self.device)
+        c, below, above, missing = self._value_hist_call(_values_on(values, self.device), dt, _values_on(e, self.device), f, 0, rows_per_chunk)
+        return ValueHistogram(*_facet_out(values, c, below, above, missing, c.sum(1) + below + above + missing))
+
+    def value_topk(self, values, k: int, descending: bool = True, filter=None, id_offset: int = 0, rows_per_chunk: int = 0) -> SortedResults:
+        """Per query the k documents of the set with the largest (descending) or smallest values of a numeric field, ties by id ascending ->
+        SortedResults(ids [B, k], values [B, k]); documents without a value are never listed; id -1 / the missing sentinel behind the last.
+        k in 1..1024.  values, filter, outputs as in ``value_stats``."""
+        n = self.n_rows
+        dt, rows_per_chunk = _value_args(values, n, rows_per_chunk)
+        k, descending = _value_topk_args(k, descending)
+        nat.require_device()
+        f = _value_set(filter, n, self.device)
+        return SortedResults(*_facet_out(values, *self._value_topk_call(_values_on(values, self.device), dt, k, descending, id_offset, f, 0,
+                                                                        rows_per_chunk)))
+
     # ---- term aggregations: what a document set is about (vs_index_term_counts, vs_index_term_counts_ids) ---------------------------------
     def _term_counts_call(self, f, bit0, rows_per_chunk):
         """One vs_index_term_counts call on device buffers and torch's current stream -> (counts [B, V], total [B]) int64 CUDA tensors.
@@ -2409,6 +2724,95 @@ class ShardGroup:
         counts, total, other = self._facets(labels, n_labels, filter, 0)
         top_l, top_c = facet_topn(counts, topn, min_count, device=self.device)
         return TopFacets(*_facet_out(labels, top_l, top_c, total, other))
+
+    # ---- numeric fields -----------------------------------------------------------------------------------------------------------------------
+    def _value_slices(self, values):
+        """every shard's slice of the values as a tensor on its GPU, cached per value tensor (and its version: an in-place edit drops it)"""
+        key = (id(values), getattr(values, "_version", None), tuple(values.shape))
+        cached = getattr(self, "_value_cache", None)
+        if cached is not None and cached[0] == key and cached[1] is values:
+            return cached[2]
+        slices, row0 = [], 0
+        for sh in self._shards:
+            n = sh.n_rows
+            slices.append(_values_on(values[row0:row0 + n], sh.device))
+            row0 += n
+        if _is_torch(values):                                    # (a numpy array has no version to tell an in-place edit by)
+            self._value_cache = (key, values, slices)
+        return slices
+
+    def _value_parts(self, values, filter, call):
+        """call(shard, its slice of the values, its filter, its first row) for every shard -> the results, moved to the first shard's GPU"""
+        import torch
+        dev0 = torch.device("cuda", self.device)
+        f = _value_set(filter, self.n_rows, dev0)
+        parts, row0 = [], 0
+        for sh, vals in zip(self._shards, self._value_slices(values)):
+            fs = f.to(torch.device("cuda", sh.device)) if f is not None else None
+            parts.append(tuple(t.to(dev0) for t in call(sh, vals, fs, row0)))      # its rows are bits [row0, row0 + n) of the filter
+            row0 += sh.n_rows
+        return parts
+
+    def value_range_filter(self, values, lo=None, hi=None):
+        """DeviceIndex.value_range_filter over the group's rows: every shard writes the bits of its slice of the values at its bit offset of
+        one bitmap on the first shard's GPU."""
+        import torch
+        from .doc_filter import DocFilter
+        n = self.n_rows
+        dt, _ = _value_args(values, n)
+        l, h, scalar = _value_bounds(lo, hi, dt)
+        nat.require_device()
+        dev0 = torch.device("cuda", self.device)
+        W = (n + 31) // 32
+        words, row0 = torch.zeros((int(l.shape[0]), W), dtype=torch.int32, device=dev0), 0
+        for sh, vals in zip(self._shards, self._value_slices(values)):
+            part = value_range_bitmaps(vals, l, h, bit0=row0 & 31, device=sh.device).to(dev0)      # zero below its first bit and past its last
+            w0 = row0 >> 5
+            words[:, w0:w0 + part.shape[1]] |= part
+            row0 += sh.n_rows
+        return DocFilter(words[0] if scalar else words, n)
+
+    def value_stats(self, values, filter=None, rows_per_chunk: int = 0) -> ValueStats:
+        """DeviceIndex.value_stats over the group's rows: values and filter are global; counts and sums are added, min and max combined on
+        the order keys (an int32 value never passes through a float).  Equal to the unsharded index exactly."""
+        import torch
+        dt, rows_per_chunk = _value_args(values, self.n_rows, rows_per_chunk)
+        nat.require_device()
+        parts = self._value_parts(values, filter, lambda sh, v, f, row0: sh._value_stats_call(v, dt, f, row0, rows_per_chunk))
+        count, missing, lo, hi, total = (torch.stack(x) for x in zip(*parts))      # [S, B]
+        has = count > 0
+        klo = torch.where(has, _value_keys(lo), torch.full_like(count, 1 << 32))
+        khi = torch.where(has, _value_keys(hi), torch.zeros_like(count))
+        lo = lo.gather(0, klo.argmin(0, keepdim=True))[0]
+        hi = hi.gather(0, khi.argmax(0, keepdim=True))[0]
+        return ValueStats(*_facet_out(values, count.sum(0), missing.sum(0), lo, hi, total.sum(0)))
+
+    def value_histogram(self, values, edges, filter=None, rows_per_chunk: int = 0) -> ValueHistogram:
+        """DeviceIndex.value_histogram over the group's rows: the shards' bins are added on the first shard's GPU."""
+        dt, rows_per_chunk = _value_args(values, self.n_rows, rows_per_chunk)
+        e = _value_edges(edges, dt)
+        nat.require_device()
+        parts = self._value_parts(values, filter,
+                                  lambda sh, v, f, row0: sh._value_hist_call(v, dt, _values_on(e, sh.device), f, row0, rows_per_chunk))
+        c, below, above, missing = (sum(x[1:], x[0]) for x in zip(*parts))
+        return ValueHistogram(*_facet_out(values, c, below, above, missing, c.sum(1) + below + above + missing))
+
+    def value_topk(self, values, k: int, descending: bool = True, filter=None, rows_per_chunk: int = 0) -> SortedResults:
+        """DeviceIndex.value_topk over the group's rows (global ids): every shard lists its k best with its id offset; the lists are merged by
+        (order key, id) on the first shard's GPU."""
+        import torch
+        dt, rows_per_chunk = _value_args(values, self.n_rows, rows_per_chunk)
+        k, descending = _value_topk_args(k, descending)
+        nat.require_device()
+        parts = self._value_parts(values, filter,
+                                  lambda sh, v, f, row0: sh._value_topk_call(v, dt, k, descending, row0, f, row0, rows_per_chunk))
+        ids, vals = (torch.cat(x, dim=1) for x in zip(*parts))                      # [B, S * k]: ids ascend from shard to shard
+        key = _value_keys(vals)
+        key = torch.where(ids < 0, torch.full_like(key, -1), key if descending else 0xFFFFFFFF - key)
+        # a shard's list is in (key descending, id ascending) order and the shards' id ranges ascend: order by id first, then -- stably -- by key
+        by_id = torch.where(ids < 0, torch.full_like(ids, 1 << 62), ids).argsort(dim=1, stable=True)
+        order = by_id.gather(1, key.gather(1, by_id).argsort(dim=1, descending=True, stable=True))[:, :k]
+        return SortedResults(*_facet_out(values, ids.gather(1, order), vals.gather(1, order)))
 
     # ---- term aggregations ------------------------------------------------------------------------------------------------------------------
     def term_counts(self, filter=None, ids=None, rows_per_chunk: int = 0) -> TermCounts:

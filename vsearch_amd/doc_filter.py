@@ -329,6 +329,24 @@ class DocFilter:
                                              dev.index, current_stream(dev.index)))
         return cls(words[0] if scalar else words, n)
 
+    @classmethod
+    def from_values(cls, values, lo=None, hi=None, device=None) -> "DocFilter":
+        """The rows whose value lies in a range: `values` a float32 / int32 array / tensor [N] (NaN / INT32_MIN = the row has no value;
+        ``device_index.value_column`` converts other types), `lo` / `hi` numbers (one set for the batch) or sequences of B of them (one set
+        per query, at most 4096); None is an open end -> row r is allowed for query b iff it has a value and lo[b] <= values[r] <= hi[b].
+        Built in one pass over the values on the GPU (vs_value_range_bitmaps); lo > hi gives an empty set."""
+        torch = _torch()
+        from .device_index import _value_bounds, _value_dtype, value_range_bitmaps
+        if isinstance(values, np.ndarray):
+            values = torch.from_numpy(np.ascontiguousarray(values))
+        if not isinstance(values, torch.Tensor) or values.dim() != 1 or int(values.shape[0]) < 1:
+            raise TypeError("DocFilter.from_values takes a non-empty float32 / int32 tensor / ndarray [N]")
+        _, _, scalar = _value_bounds(lo, hi, _value_dtype(values))
+        dev = _device_of(device if device is not None else (values.device if values.is_cuda else None))
+        nat.require_device()
+        words = value_range_bitmaps(values.detach().to(dev).contiguous(), lo, hi, device=dev.index)
+        return cls(words[0] if scalar else words, int(values.shape[0]))
+
     # ---- set algebra on the packed words --------------------------------------------------------------
     def _pair(self, other):
         if not isinstance(other, DocFilter):

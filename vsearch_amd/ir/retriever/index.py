@@ -23,6 +23,7 @@ import torch
 
 from ... import _native as nat
 from ...device_index import Assignment, KMeansResult, KMEANS_UPDATE_BATCH, kmeans_loop, term_sum_topn, _assign_args, _kmeans_args, DeviceIndex, DiverseResults, Explanation, FacetCounts, FusedResults, GroupedResults, TermCounts, TermSums, TopFacets, TopTerms, TopWeights, _term_topn_args, _weight_topn_args, fuse_topk, _fuse_args, MAX_FUSE_DEPTH, MAX_FUSE_ENTRIES, _topn_args, NotBinaryError, RangeResults, ShardGroup, _diverse_args, _range_args, _grouped_args, _by_example_args, _explain_args, _int64_ids, _k_a_args, resparsify, topk_exclude
+from ...device_index import SortedResults, ValueHistogram, ValueStats, value_column, _value_bounds, _value_dtype, _value_edges, _value_topk_args
 
 logger = logging.getLogger(__name__)
 
@@ -628,6 +629,145 @@ class Index:
             return FacetCounts(*(self._to_api(t) for t in target.facet_counts(codes, n_labels, filter=filter)))
         return TopFacets(*(self._to_api(t) for t in target.top_facets(codes, n_labels, topn, filter=filter, min_count=min_count)))
 
+    # ---- numeric fields (not in the reference: a quantity per document -- a year, a timestamp, a length, a price -- to filter, describe and sort by)
+    def _value_store(self):
+        if getattr(self, "_values", None) is None:
+            self._values = {}                                       # name -> float32 / int32 values on the index's GPU, the missing sentinel inside
+        return self._values
+
+    def set_values(self, name: str, values, missing=None):
+        """Give every document a value of numeric field `name`: array / tensor [N].  Integer input becomes int32 (a value outside
+        [-2^31 + 1, 2^31 - 1] raises); floating input becomes float32, and NaN means "no value".  missing: optional bool mask [N] of the
+        documents without a value.  Kept on the index's GPU for ``value_filter``, ``value_stats``, ``histogram`` and ``top_by_value``;
+        values=None removes the field.  A name of a facet field, or "groups", raises.  Value fields follow compact() and
+        add(values=); they are NOT written by save() -- call set_values again after a load."""
+        if not isinstance(name, str) or not name:
+            raise TypeError("a value field is named by a non-empty string")
+        if name == "groups":
+            raise ValueError('"groups" names the group ids (set_groups): pick another field name')
+        if name in (getattr(self, "_facets", None) or {}):
+            raise ValueError(f"{name!r} is a facet field of this index: pick another field name")
+        store = self._value_store()
+        if values is None:
+            store.pop(name, None)
+            return
+        v = value_column(values, missing)
+        if int(v.shape[0]) != self._n_rows():
+            raise ValueError(f"values holds {int(v.shape[0])} entries for {self._n_rows()} documents")
+        store[name] = torch.from_numpy(v).to(torch.device("cuda", self._explain_target()[1])).contiguous()
+
+    @property
+    def value_fields(self):
+        """the names of the value fields set on this index"""
+        return list(getattr(self, "_values", None) or {})
+
+    def values_from_samples(self, key: str, name: Optional[str] = None):
+        """Build value field `name` (default: `key`) from field `key` of the data file: numbers only; all integers give an int32 field, else
+        float32; a document without the key (or with None) has no value.  Host work over the text store."""
+        n = len(self)
+        if n == 0:
+            raise ValueError("the index has no data file to read values from")
+        if n != self._n_rows():
+            raise ValueError(f"the data file holds {n} documents, the index {self._n_rows()}")
+        vals, missing = [], np.zeros(n, dtype=bool)
+        for i in range(n):
+            sample = self.get_sample(i)
+            if not isinstance(sample, dict):
+                raise TypeError(f"document {i} is a {type(sample).__name__}, not a record with fields: pass the values to set_values()")
+            v = sample.get(key)
+            if v is None:
+                missing[i] = True
+                v = 0
+            elif isinstance(v, bool) or not isinstance(v, (int, float)):
+                raise TypeError(f"document {i}: field {key!r} holds {type(v).__name__} {v!r}, not a number")
+            vals.append(v)
+        if missing.all():
+            raise KeyError(f"no document has a field {key!r}")
+        ints = all(isinstance(v, int) for v in vals)
+        self.set_values(name or key, np.asarray(vals, dtype=np.int64 if ints else np.float64), missing)
+
+    def _value_check(self, field, q_embs=None, min_score=None):
+        """the argument errors of a value call that need no device -> the field's vs dtype"""
+        store = self._value_store()
+        if field not in store:
+            raise KeyError(f"no value field {field!r}: set_values() or values_from_samples() first (fields: {list(store)})")
+        if (q_embs is None) != (min_score is None):
+            raise ValueError("q_embs and min_score go together: the set is match_filter(q_embs, min_score, filter), or the filter alone")
+        return _value_dtype(store[field])
+
+    def _value_field(self, field):
+        """-> the field's values on the search target's GPU"""
+        store = self._value_store()
+        self._value_check(field)
+        gpu = torch.device("cuda", self._explain_target()[1])
+        if store[field].device != gpu:
+            store[field] = store[field].to(gpu)
+        return store[field]
+
+    def get_values(self, name: str):
+        """the values of field `name` [N], float32 or int32, documents without a value as NaN / INT32_MIN"""
+        return self._to_api(self._value_field(name))
+
+    def value_filter(self, field: str, lo=None, hi=None):
+        """A DocFilter of the documents with lo <= value <= hi of value field `field`, both ends inclusive; None is an open end; lists of B
+        bounds give a per-query filter.  A document without a value never matches.  Built on the GPU in one pass over the values; for
+        ``search(filter=)`` and ``&``, ``|``, ``~`` with any other filter (term_filter, match_filter, from_labels)."""
+        v = self._value_field(field)
+        return self._explain_target()[0].value_range_filter(v, lo, hi)
+
+    def _value_set(self, q_embs, min_score, filter):
+        return self.match_filter(q_embs, min_score, filter=filter) if q_embs is not None else filter
+
+    def value_stats(self, field: str, q_embs=None, min_score=None, filter=None) -> ValueStats:
+        """Count, missing, min, max and sum of value field `field` over a document set -> ValueStats, one entry per query; ``.mean()`` in
+        fp64.  The set as in ``facets``: with q_embs and min_score the documents ``match_filter(q_embs, min_score, filter)`` matches per
+        query, else `filter` alone (None = every document).  Deleted documents never count."""
+        self._value_check(field, q_embs, min_score)
+        v = self._value_field(field)
+        filter = self._value_set(q_embs, min_score, filter)
+        return ValueStats(*(self._to_api(t) for t in self._explain_target()[0].value_stats(v, filter=filter)))
+
+    def histogram(self, field: str, edges, q_embs=None, min_score=None, filter=None) -> ValueHistogram:
+        """How a document set spreads over the bins [edges[i], edges[i + 1]) of value field `field` -> ValueHistogram(counts [B, E - 1],
+        below, above, missing, total).  edges: 2..1025 strictly ascending numbers.  The set as in ``value_stats``."""
+        _value_edges(edges, self._value_check(field, q_embs, min_score))
+        v = self._value_field(field)
+        filter = self._value_set(q_embs, min_score, filter)
+        return ValueHistogram(*(self._to_api(t) for t in self._explain_target()[0].value_histogram(v, edges, filter=filter)))
+
+    def top_by_value(self, field: str, k: int, descending: bool = True, q_embs=None, min_score=None, filter=None) -> SortedResults:
+        """The k documents of a set with the largest (descending) or smallest values of `field`, ties by id ascending -- sort by a field
+        instead of by score -> SortedResults(ids [B, k], values [B, k]); documents without a value are never listed, id -1 behind the last.
+        k in 1..1024.  The set as in ``value_stats``."""
+        self._value_check(field, q_embs, min_score)
+        _value_topk_args(k, descending)
+        v = self._value_field(field)
+        filter = self._value_set(q_embs, min_score, filter)
+        return SortedResults(*(self._to_api(t) for t in self._explain_target()[0].value_topk(v, k, descending=descending, filter=filter)))
+
+    def _added_values(self, values, n_add):
+        """values= of add() / update() -> {name: ndarray [n_add] in the field's type}, or None for an index without value fields.  Raises
+        before anything changes: a missing or an extra field, a wrong length, a value the field's type does not hold."""
+        have = getattr(self, "_values", None) or {}
+        given = dict(values) if values is not None else {}
+        if not have:
+            if given:
+                raise ValueError("the index has no value fields: set_values() first, then add(..., values=)")
+            return None
+        missing, extra = sorted(set(have) - set(given)), sorted(set(given) - set(have))
+        if missing or extra:
+            raise ValueError(f"the index has value fields {sorted(have)}: add(..., values=) must give values for exactly these"
+                             f" (missing {missing}, unknown {extra})")
+        out = {}
+        for name, vals in given.items():
+            v = value_column(vals, what=f"values[{name!r}]")
+            if int(v.shape[0]) != n_add:
+                raise ValueError(f"values[{name!r}] holds {int(v.shape[0])} entries for {n_add} added documents")
+            if have[name].dtype == torch.int32 and v.dtype != np.int32:
+                raise TypeError(f"values[{name!r}]: the field holds integers, got {v.dtype}")
+            out[name] = v.astype(np.float32 if have[name].dtype == torch.float32 else np.int32)
+        return out
+
     # ---- term aggregations (not in the reference: what a document set is about, in the vocabulary's own columns) --------------------------
     def _term_set(self, q_embs, min_score, filter, ids):
         """the set of a term aggregation -> (search target, filter, ids), argument errors before any device work"""
@@ -1001,6 +1141,8 @@ class Index:
         for name, (c, n_labels, names) in list((getattr(self, "_facets", None) or {}).items()):     # and the label of old_ids[j]
             c = c.index_select(0, torch.from_numpy(old).to(c.device)).to(torch.device("cuda", self._explain_target()[1]))
             self._facets[name] = (c, n_labels, names)
+        for name, v in list((getattr(self, "_values", None) or {}).items()):                        # and the value
+            self._values[name] = v.index_select(0, torch.from_numpy(old).to(v.device)).to(torch.device("cuda", self._explain_target()[1]))
         return old
 
     def compact(self):
@@ -1023,17 +1165,19 @@ class Index:
         indptr, indices, data, shape = SparseIndex._csr_parts(vectors)
         return indptr, indices, data, shape
 
-    def add(self, vectors, samples=None, groups=None, facets=None):
+    def add(self, vectors, samples=None, groups=None, facets=None, values=None):
         """Append documents -> their new ids (int64 tensor).  vectors: a sparse CSR tensor / scipy CSR (or a dense [n, V] tensor) whose
         columns match the index.  When the index has no spare capacity it is compacted with room to grow (at least the rows asked for, at
         least a quarter of its size); that moves ids if rows are deleted, so then add() raises and asks for compact().  samples: the
         documents' texts, appended to `data`.  groups: their group ids -- required when the index has groups (set_groups), refused
         when it has none.  facets: {field: codes} for every facet field of the index (set_facet), under the same rule; a field without
-        names grows its n_labels with the new codes."""
+        names grows its n_labels with the new codes.  values: {field: values} for every value field of the index (set_values), under the
+        same rule; NaN (a float field) marks a document without a value."""
         indptr, indices, data, shape = self._add_csr(vectors)
         n_add = int(indptr.shape[0]) - 1
         new_groups = self._added_groups(groups, n_add)
         new_facets = self._added_facets(facets, n_add)
+        new_values = self._added_values(values, n_add)
         target = self._shards[-1] if getattr(self, "_shards", None) else self._device_index()
         info = target.info()
         if info.kind != nat.VS_KIND_CSR and not (info.kind == nat.VS_KIND_DENSE and info.n_packets > 0):
@@ -1083,22 +1227,27 @@ class Index:
             if names is None and n_add:
                 n_labels = max(n_labels, int(c_new.max()) + 1)
             self._facets[name] = (torch.cat([c, c_new.to(c.device)]), n_labels, names)
+        for name, v_new in (new_values or {}).items():
+            v = self._values[name]
+            self._values[name] = torch.cat([v, torch.from_numpy(v_new).to(v.device)])
         return torch.arange(n0, n0 + n_add, dtype=torch.int64)
 
-    def update(self, ids, vectors, samples=None, groups=None, facets=None):
-        """delete(ids) + add(vectors, samples, groups, facets) -> the new ids of the replacements"""
+    def update(self, ids, vectors, samples=None, groups=None, facets=None, values=None):
+        """delete(ids) + add(vectors, samples, groups, facets, values) -> the new ids of the replacements"""
         if (self.groups is None) != (groups is None):               # (before anything is deleted)
             self._added_groups(groups, 0)
         have = getattr(self, "_facets", None) or {}
         if set(have) != set(facets or {}):
             self._added_facets(facets, 0)
+        if set(getattr(self, "_values", None) or {}) != set(values or {}):
+            self._added_values(values, 0)
         self.delete(ids)
-        return self.add(vectors, samples, groups, facets)
+        return self.add(vectors, samples, groups, facets, values)
 
     # ---- persistence -------------------------------------------------------------------------------
     def save(self, path):
-        """Dense index -> ``.pt`` (torch.save of the CPU tensor), like index.py:96-109.  Groups and facet fields (set_groups, set_facet)
-        are not written: set them again after a load."""
+        """Dense index -> ``.pt`` (torch.save of the CPU tensor), like index.py:96-109.  Groups, facet fields and value
+        fields (set_groups, set_facet, set_values) are not written: set them again after a load."""
         self._check_no_deletions("a .pt file")
         try:
             torch.save(self.vector.cpu(), path)
@@ -1515,8 +1664,8 @@ class SparseIndex(Index):
 
     # -- persistence (index.py:181-202) --------------------------------------------------------------
     def save(self, path):
-        """CSR index -> scipy ``.npz`` (keys indices, indptr, data, shape, format; int64 indices).  Groups and facet fields (set_groups,
-        set_facet) are not written: set them again after a load."""
+        """CSR index -> scipy ``.npz`` (keys indices, indptr, data, shape, format; int64 indices).  Groups, facet fields and value fields
+        (set_groups, set_facet, set_values) are not written: set them again after a load."""
         from scipy.sparse import csr_array, save_npz
         if str(path).endswith(".vsx"):                              # native shard file (loads without a CSR round trip)
             if self._shards:

@@ -147,6 +147,46 @@ class Retriever(BiEncoder):
         facets = [[(names[l] if names is not None else l, c) for l, c in zip(ls, cs) if l >= 0] for ls, cs in zip(labels, counts)]
         return facets, totals
 
+    def _match_set(self, queries, index, filter, must, must_not, should, min_should, dropout, a, batch_size):
+        """the index, the query embeddings and the filter (term constraints ANDed in) of a retrieve_* call over the match set"""
+        index = index or self.index
+        if index is None:
+            raise RuntimeError("no index: call build_index / load_index first")
+        if must is not None or must_not is not None or should is not None or min_should is not None:
+            terms = self.term_filter(must=must, must_not=must_not, should=should, min_should=min_should, index=index)
+            if filter is not None:
+                from ...doc_filter import as_doc_filter
+                filter = as_doc_filter(filter, terms.n_rows, device=terms.device) & terms
+            else:
+                filter = terms
+        a = a or self.encoder_q.config.topk
+        return index, self.process_query(queries, dropout, a, batch_size=batch_size), filter
+
+    def value_filter(self, field: str, lo=None, hi=None, index: Index = None):
+        """``Index.value_filter``: the documents with lo <= value <= hi of value field `field` (None: an open end) as a DocFilter, to be passed
+        as ``filter=`` to any retrieve_* call; it composes with ``term_filter`` through ``&``."""
+        index = index or self.index
+        if index is None:
+            raise RuntimeError("no index: call build_index / load_index first")
+        return index.value_filter(field, lo, hi)
+
+    def retrieve_sorted(self, queries: Union[List[str], np.ndarray, T], field: str, k: int = 5, min_score=0.0, descending: bool = True,
+                        dropout: float = 0, a: int = None, index: Index = None, batch_size: int = 32, filter=None, must=None, must_not=None,
+                        should=None, min_should: int = None):
+        """The k matches of each query with the largest (descending) or smallest values of value field `field` -- sort by a field instead
+        of by score, ``Index.top_by_value`` behind the query encoder: the matches are the documents scoring at least `min_score`, exactly
+        as in ``retrieve_range``; `filter` and the term constraints as in ``retrieve``.  -> SortedResults(ids [B, k], values [B, k])."""
+        index, q_emb, filter = self._match_set(queries, index, filter, must, must_not, should, min_should, dropout, a, batch_size)
+        return index.top_by_value(field, k, descending=descending, q_embs=q_emb, min_score=min_score, filter=filter)
+
+    def retrieve_histogram(self, queries: Union[List[str], np.ndarray, T], field: str, edges, min_score=0.0, dropout: float = 0, a: int = None,
+                           index: Index = None, batch_size: int = 32, filter=None, must=None, must_not=None, should=None,
+                           min_should: int = None):
+        """How each query's matches spread over the bins of value field `field` -- ``Index.histogram`` behind the query encoder, the match
+        set as in ``retrieve_sorted`` -> ValueHistogram(counts [B, E - 1], below, above, missing, total)."""
+        index, q_emb, filter = self._match_set(queries, index, filter, must, must_not, should, min_should, dropout, a, batch_size)
+        return index.histogram(field, edges, q_embs=q_emb, min_score=min_score, filter=filter)
+
     def significant_terms(self, queries: Union[List[str], np.ndarray, T], min_score=None, k: int = None, topn: int = 20, method: str = "jlh",
                           min_count: int = 1, background=None, dropout: float = 0, a: int = None, index: Index = None, batch_size: int = 32,
                           filter=None, must=None, must_not=None, should=None, min_should: int = None):
