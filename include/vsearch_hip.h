@@ -474,7 +474,7 @@ VS_API int vs_label_bitmaps(const int32_t* labels, int64_t n_rows, const int32_t
  * 2^27 scratch keys, host edges / bounds as above: VS_EINVAL -- checked before the device is touched (without a GPU a bad argument is VS_EINVAL,
  * a good one VS_ENODEVICE).  Pointers: all host (staged; the call blocks), or all device pointers on `device` / the index's device (VS_EINVAL
  * for a mix); device pointers and a non-NULL stream only enqueue (vs_value_topk synchronises either way).
- * Not covered: no index file stores values; 64-bit and fp64 values; histograms of scores; percentiles; sort by several keys; k > 1024; a shard
+ * Not covered: no index file stores values; 64-bit and fp64 values; histograms of scores; sort by several keys; k > 1024; a shard
  * group has no entry point of its own (every shard works on its slice of the values and its bit range of the bitmap: counts, sums and bins are
  * added, min / max combined on keys, the top-k lists merged by (key, id)) and the one-process-per-GPU RCCL path has none.                       */
 #define VS_VAL_F32 0
@@ -504,6 +504,74 @@ VS_API int vs_value_topk(const uint32_t* words, int64_t bit0, int64_t ld_words, 
 VS_API int vs_index_value_topk(vs_index* index, const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B, const void* values, int dtype,
                                int32_t k, int descending, int64_t id_offset, int64_t rows_per_chunk, int64_t* out_ids, void* out_values,
                                void* stream);
+
+/* ---- percentiles: exact order statistics of a numeric field over any document set (no reference counterpart) ---------------------------------
+ * For query b let K_b be the ascending multiset of the order keys (above) of the rows that are in the set (bitmap bit set, and_words bit set,
+ * live for the vs_index_* variant) and carry a value (key != 0): count [b] = |K_b|, missing [b] = the set rows with key 0.  The ORDER STATISTIC
+ * of rank r (0-based, ascending) is value_unkey(K_b[r]): a raw 32-bit value of the field's type, +0.0 of -0.0 / +0.0 as vs_value_stats' min and
+ * max.  A rank outside 0..count - 1 (any rank when count = 0) gives the missing sentinel (NaN 0x7FC00000 / INT32_MIN) and a resolved rank of -1.
+ * QUANTILE -> RANK: pos = q * double(count - 1), ONE fp64 multiplication, q in [0, 1]; VS_QUANTILE_LOWER: floor(pos), VS_QUANTILE_HIGHER:
+ * ceil(pos), VS_QUANTILE_NEAREST: rint(pos), half to even.  No call interpolates (the Python facade's "linear" selects floor and ceil exactly).
+ * The selection is a most-significant-digit radix select on the keys, VS_VALUE_RADIX_LEVELS = 3 levels: level 0 = bits 31..21, level 1 = bits
+ * 20..10 (VS_VALUE_RADIX_BINS = 2048 bins each), level 2 = bits 9..0 (1024 bins): three passes over bitmaps and values.  Every count is an
+ * integer, so shards ADD their counts between the levels and a row-sharded index gives the unsharded answer bit for bit.
+ *
+ * vs_value_quantiles / vs_index_value_quantiles: all three levels on one device.  The set arguments are vs_value_stats'.  R in
+ *   1..VS_VALUE_MAX_RANKS ranks per query, given either as q double [R] (shared by the queries) with `method`, or -- q == NULL -- as ranks
+ *   int64 [B, R].  out_values [B, R] raw 32-bit, out_ranks int64 [B, R] the resolved ranks (-1: no answer), count / missing int64 [B]; every
+ *   element is written.  The call is the composition of the level calls below, bit for bit, and synchronises either way (its counts are device
+ *   scratch, B x R x 2048 int64, at most 2^27 of them).
+ * vs_value_radix_counts / vs_index_value_radix_counts: one level's digit counts.  counts int64 [B, S, bins], S = 1 at level 0 and R at levels 1
+ *   and 2, bins = 2048 / 2048 / 1024, written whole.  Level 0 counts the top digit of every set row with a value and writes missing [B]; levels
+ *   1 and 2 read the step's state -- slot_prefix uint32 [B, R], n_slots int32 [B] -- and count, for slot s < n_slots[b], the level's digit of the
+ *   rows whose higher digits equal slot_prefix [b, s]; rows of no slot cost no atomic; slots >= n_slots[b] stay 0.  missing / slot_prefix /
+ *   n_slots may be NULL where the level does not use them.  Pointers all host or all device, as vs_value_stats.
+ * vs_value_radix_step: the step between two levels, on DEVICE buffers only (one workgroup a query).  State arrays, all [B, R] but n_slots [B]:
+ *     rank_res    int64   in (levels 1, 2) / out: each rank's residual rank inside its slot; -1 = no answer
+ *     rank_slot   int32   in (levels 1, 2) / out: the slot of the NEXT level the rank fell into; -1 = no answer
+ *     rank_prefix uint32  out: the rank's digits so far, right-aligned (11, 22, 32 bits: after level 2 the key itself)
+ *     slot_prefix uint32  in (levels 1, 2) / out: the next level's slots: the distinct rank_prefix values, ascending; 0xFFFFFFFF behind the last
+ *     n_slots     int32   out: how many; equal ranks, and ranks that fell into one bin, share a slot
+ *   Level 0 reads counts [B, 1, 2048] and q [R] with method or ranks [B, R] (device arrays; a q outside [0, 1] or NaN, or a rank outside
+ *   0..count - 1, resolves to -1), and also writes count [B] = the sum of the bins and out_ranks [B, R].  Levels 1 and 2 read counts [B, R,
+ *   bins]: per slot a prefix scan of the bins, per rank the bin d with cum <= r < cum + counts[d]; the residual becomes r - cum.  Level 2 also
+ *   writes out_values [B, R] = value_unkey(rank_prefix) (the sentinel for -1); out_values may be NULL at the other levels, q / ranks / count /
+ *   out_ranks at levels 1 and 2.
+ * vs_value_quantile_plan: the launch of the counting kernel -- pure host arithmetic on R: per-query bitmaps R = 1..2 -> qt = 8, 3..4 -> 4, 5..8
+ *   -> 2, 9..16 -> 1; a shared bitmap qt = 1; chunks and rows_per_chunk by vs_value_plan's rule with n_bins = 0.  LDS = qt x S x bins x 4 bytes,
+ *   128 KiB at most.
+ * Kernels (quantiles.hip).  Counting: the shape of the histogram kernel above -- a workgroup owns a chunk and a tile of qt queries, walks the
+ * bitmaps in 2048-row spans, loads a row's value once for the tile; a row's slot is found by a branch-free search (4 steps and a compare) over the
+ * query's sorted slot prefixes in LDS; when every row of a 64-row step falls into one bin one lane adds the popcount; non-zero bins are flushed
+ * with 64-bit atomics.  Integer arithmetic throughout.
+ * Errors (VS_EINVAL before the device is touched; a good call without a GPU is VS_ENODEVICE): everything vs_value_stats refuses, R outside
+ * 1..VS_VALUE_MAX_RANKS, an unknown method or level, a host q outside [0, 1] or NaN, a negative host rank, B x R x 2048 beyond 2^27, a NULL
+ * array the level needs, host pointers to vs_value_radix_step.
+ * Not covered: weighted quantiles; quantiles of scores; per-label quantiles in one pass; skipping levels by the set's common key prefix; 64-bit
+ * values; the one-process-per-GPU RCCL path.                                                                                                     */
+#define VS_VALUE_RADIX_BINS 2048
+#define VS_VALUE_RADIX_LEVELS 3
+#define VS_VALUE_MAX_RANKS 16
+#define VS_QUANTILE_LOWER 0
+#define VS_QUANTILE_HIGHER 1
+#define VS_QUANTILE_NEAREST 2
+VS_API int vs_value_quantile_plan(int64_t n_rows, int32_t B, int32_t R, int per_query, int64_t rows_per_chunk, int32_t* out_qt, int64_t* out_chunks,
+                                  int64_t* out_rows_per_chunk);
+VS_API int vs_value_quantiles(const uint32_t* words, int64_t bit0, int64_t ld_words, const uint32_t* and_words, int32_t B, const void* values,
+                              int dtype, int64_t n_rows, const double* q, int method, const int64_t* ranks, int32_t R, int64_t rows_per_chunk,
+                              void* out_values, int64_t* out_ranks, int64_t* count, int64_t* missing, int device, void* stream);
+VS_API int vs_index_value_quantiles(vs_index* index, const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B, const void* values, int dtype,
+                                    const double* q, int method, const int64_t* ranks, int32_t R, int64_t rows_per_chunk, void* out_values,
+                                    int64_t* out_ranks, int64_t* count, int64_t* missing, void* stream);
+VS_API int vs_value_radix_counts(const uint32_t* words, int64_t bit0, int64_t ld_words, const uint32_t* and_words, int32_t B, const void* values,
+                                 int dtype, int64_t n_rows, int level, int32_t R, const uint32_t* slot_prefix, const int32_t* n_slots,
+                                 int64_t rows_per_chunk, int64_t* counts, int64_t* missing, int device, void* stream);
+VS_API int vs_index_value_radix_counts(vs_index* index, const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B, const void* values,
+                                       int dtype, int level, int32_t R, const uint32_t* slot_prefix, const int32_t* n_slots, int64_t rows_per_chunk,
+                                       int64_t* counts, int64_t* missing, void* stream);
+VS_API int vs_value_radix_step(int level, const int64_t* counts, int32_t B, int32_t R, const double* q, int method, const int64_t* ranks,
+                               int64_t* rank_res, int32_t* rank_slot, uint32_t* rank_prefix, uint32_t* slot_prefix, int32_t* n_slots,
+                               int64_t* count, int64_t* out_ranks, void* out_values, int dtype, int device, void* stream);
 
 /* bool / uint8 mask [B, n] (row stride ld_mask bytes; non-zero = allowed) -> the bitmap words [B, ld_words] vs_index_search_filtered
  * reads (bits past n of a row's last word are 0).  mask and words: host pointers or device pointers on `device` (VS_EINVAL otherwise).  stream as in

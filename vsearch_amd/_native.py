@@ -35,6 +35,9 @@ TERM_FX_SHIFT, TERM_FX_CLAMP_LOG2, TERM_SUM_TILE_COLS = 24, 20, 18432
 ASSIGN_MAX_K, LABEL_MAX_VALUES = 4096, 4096
 # numeric fields (VS_VAL_*, VS_VALUE_MAX_*): the value types, the most ranges of vs_value_range_bitmaps, edges of a histogram, rows of vs_value_topk
 VAL_F32, VAL_I32, VALUE_MAX_RANGES, VALUE_MAX_EDGES, VALUE_MAX_TOPK = 0, 1, 4096, 1025, 1024
+# percentiles (VS_VALUE_RADIX_*, VS_VALUE_MAX_RANKS, VS_QUANTILE_*): bins of a radix level, the levels, the most ranks of a call, the rank rules
+VALUE_RADIX_BINS, VALUE_RADIX_LEVELS, VALUE_MAX_RANKS = 2048, 3, 16
+QUANTILE_LOWER, QUANTILE_HIGHER, QUANTILE_NEAREST = 0, 1, 2
 
 
 class VsearchNativeError(RuntimeError):
@@ -95,6 +98,12 @@ _SIGNATURES = {
     "vs_index_value_histogram": ([_vp, _vp, _i64, _i64, _i32, _vp, _int, _vp, _i32, _i64, _vp, _i64, _vp, _vp, _vp, _vp], _int),
     "vs_value_topk": ([_vp, _i64, _i64, _vp, _i32, _vp, _int, _i64, _i32, _int, _i64, _i64, _vp, _vp, _int, _vp], _int),
     "vs_index_value_topk": ([_vp, _vp, _i64, _i64, _i32, _vp, _int, _i32, _int, _i64, _i64, _vp, _vp, _vp], _int),
+    "vs_value_quantile_plan": ([_i64, _i32, _i32, _int, _i64, C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i64)], _int),
+    "vs_value_quantiles": ([_vp, _i64, _i64, _vp, _i32, _vp, _int, _i64, _vp, _int, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _int, _vp], _int),
+    "vs_index_value_quantiles": ([_vp, _vp, _i64, _i64, _i32, _vp, _int, _vp, _int, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp], _int),
+    "vs_value_radix_counts": ([_vp, _i64, _i64, _vp, _i32, _vp, _int, _i64, _int, _i32, _vp, _vp, _i64, _vp, _vp, _int, _vp], _int),
+    "vs_index_value_radix_counts": ([_vp, _vp, _i64, _i64, _i32, _vp, _int, _int, _i32, _vp, _vp, _i64, _vp, _vp, _vp], _int),
+    "vs_value_radix_step": ([_int, _vp, _i32, _i32, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _vp], _int),
     "vs_filter_pack": ([_vp, _i32, _i64, _i64, _vp, _i64, _int, _vp], _int),
     "vs_index_scores": ([_vp, _vp, _int, _i64, _i32, _vp, _vp], _int),
     "vs_index_explain": ([_vp, _vp, _int, _i64, _i32, _vp, _i64, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp], _int),

@@ -1418,7 +1418,137 @@ def _value_set(filter, n_rows, device):
     return as_doc_filter(filter, n_rows, device=device)
 
 
-KMEANS_UPDATE_BATCH = 64                                 # clusters whose sums one term_sums call of the update takes
+# ---- percentiles: exact order statistics of a numeric field (vs_value_quantiles, vs_value_radix_counts, vs_value_radix_step) ----------------
+MAX_VALUE_RANKS = nat.VALUE_MAX_RANKS
+QUANTILE_METHODS = {"lower": nat.QUANTILE_LOWER, "higher": nat.QUANTILE_HIGHER, "nearest": nat.QUANTILE_NEAREST}
+
+
+class ValueQuantiles(NamedTuple):
+    """value_quantiles: per query and rank the order statistic of the set's values -- values [B, R] in the field's type (the missing
+    sentinel, NaN / INT32_MIN, where there is no answer), ranks int64 [B, R] the 0-based ascending ranks they stand at (-1: no answer);
+    count / missing int64 [B]: the documents of the set with / without a value."""
+    values: Any
+    ranks: Any
+    count: Any
+    missing: Any
+
+
+class ValuePercentiles(NamedTuple):
+    """percentiles / median: values [B, P] -- float64 for method "linear" (NaN where there is no answer), else the field's type (the missing
+    sentinel there); count / missing int64 [B]: the documents of the set with / without a value."""
+    values: Any
+    count: Any
+    missing: Any
+
+
+PERCENTILE_METHODS = ("linear", "lower", "higher", "nearest")
+
+
+def _percentile_args(pcts, method):
+    """pcts of percentiles() -> the quantiles q = pcts / 100, float64 [P]; a percentile outside 0..100 or NaN raises"""
+    if method not in PERCENTILE_METHODS:
+        raise ValueError(f'method must be one of {PERCENTILE_METHODS}, got {method!r}')
+    p = np.asarray(pcts.detach().cpu().numpy() if _is_torch(pcts) else pcts)
+    if p.dtype == np.bool_ or p.dtype.kind not in "iuf":
+        raise TypeError("pcts: a number or a 1-D sequence of numbers in 0..100")
+    p = np.atleast_1d(p).astype(np.float64)
+    if p.ndim != 1 or p.shape[0] < 1:
+        raise ValueError("pcts: a number or a non-empty 1-D sequence of numbers")
+    if not ((p >= 0.0) & (p <= 100.0)).all():
+        raise ValueError("pcts must lie in 0..100")
+    return np.ascontiguousarray(p / 100.0)
+
+
+def value_quantile_plan(n_rows: int, B: int, R: int, per_query: bool, rows_per_chunk: int = 0):
+    """The launch of the counting kernel of vs_value_quantiles for these arguments (vs_value_quantile_plan; pure host arithmetic, no GPU
+    needed) -> (qt, chunks, rows_per_chunk): qt = queries a workgroup serves, by the number of ranks R."""
+    qt, chunks, rpc = C.c_int32(0), C.c_int64(0), C.c_int64(0)
+    nat.check(nat.lib().vs_value_quantile_plan(int(n_rows), int(B), int(R), 1 if per_query else 0, int(rows_per_chunk), C.byref(qt), C.byref(chunks),
+                                               C.byref(rpc)))
+    return qt.value, chunks.value, rpc.value
+
+
+def _quantile_args(q, method, ranks):
+    """Argument checks of a quantile call that need no device -> (q float64 [R] | None, method code, ranks int64 [R] or [B, R] | None)"""
+    if (q is None) == (ranks is None):
+        raise ValueError("exactly one of q (quantiles in [0, 1]) and ranks (0-based ascending ranks) must be given")
+    if method not in QUANTILE_METHODS:
+        raise ValueError(f'method must be "lower", "higher" or "nearest", got {method!r}')
+    if q is not None:
+        a = np.atleast_1d(np.asarray(q.detach().cpu().numpy() if _is_torch(q) else q, dtype=np.float64))
+        if a.ndim != 1 or a.shape[0] < 1:
+            raise ValueError("q must be a number or a non-empty 1-D sequence of numbers")
+        if not ((a >= 0.0) & (a <= 1.0)).all():
+            raise ValueError("q must lie in [0, 1]")
+        return np.ascontiguousarray(a), QUANTILE_METHODS[method], None
+    r = np.asarray(ranks.detach().cpu().numpy() if _is_torch(ranks) else ranks)
+    if r.dtype == np.bool_ or r.dtype.kind not in "iu":
+        raise TypeError(f"ranks must be integers, got {r.dtype}")
+    r = np.atleast_1d(r).astype(np.int64)
+    if r.ndim not in (1, 2) or r.shape[-1] < 1:
+        raise ValueError("ranks must be a non-empty [R] or [B, R] array")
+    if (r < 0).any():
+        raise ValueError("ranks must be >= 0 (0-based, ascending)")
+    return None, QUANTILE_METHODS[method], np.ascontiguousarray(r)
+
+
+def _quantile_ranks_for(ranks, B):
+    """ranks [R] or [B, R] -> int64 [B, R]"""
+    if ranks.ndim == 1:
+        return np.ascontiguousarray(np.broadcast_to(ranks[None, :], (B, ranks.shape[0])))
+    if ranks.shape[0] != B:
+        raise ValueError(f"ranks holds {ranks.shape[0]} rows for {B} queries")
+    return ranks
+
+
+def quantile_lerp(lo, hi, frac):
+    """The linear interpolation of ``percentiles(method="linear")`` in fp64: lo + (hi - lo) * frac, and exactly lo where lo == hi (so that
+    +-inf does not give NaN).  numpy arrays in, float64 out; a missing end (NaN) gives NaN."""
+    lo, hi, frac = np.asarray(lo, np.float64), np.asarray(hi, np.float64), np.asarray(frac, np.float64)
+    with np.errstate(invalid="ignore"):
+        return np.where(lo == hi, lo, lo + (hi - lo) * frac)
+
+
+def value_radix_step(level: int, counts, R: int, state=None, q=None, method: int = 0, ranks=None, dtype=None, device: int = 0):
+    """One step of the radix select on a level's counts (vs_value_radix_step; CUDA tensors on `device`, torch's current stream).  counts:
+    int64 [B, S, bins], summed over the shards; state: the dict the step of the level above returned (None at level 0); q float64 [R] with
+    the method code, or ranks int64 [B, R], at level 0 -> dict(rank_res, rank_slot, rank_prefix, slot_prefix, n_slots) and, from level 0 on,
+    count [B] and ranks [B, R]; after level 2, values [B, R] of `dtype`."""
+    import torch
+    dev = torch.device("cuda", device)
+    B = int(counts.shape[0])
+    if state is None:
+        state = dict(rank_res=torch.empty((B, R), dtype=torch.int64, device=dev), rank_slot=torch.empty((B, R), dtype=torch.int32, device=dev),
+                     rank_prefix=torch.empty((B, R), dtype=torch.int32, device=dev), slot_prefix=torch.empty((B, R), dtype=torch.int32, device=dev),
+                     n_slots=torch.empty(B, dtype=torch.int32, device=dev), count=torch.empty(B, dtype=torch.int64, device=dev),
+                     ranks=torch.empty((B, R), dtype=torch.int64, device=dev))
+    last = level == nat.VALUE_RADIX_LEVELS - 1
+    if last:
+        state["values"] = torch.empty((B, R), dtype=dtype, device=dev)
+    counts = counts.contiguous()
+    nat.check(nat.lib().vs_value_radix_step(int(level), _ptr(counts), B, int(R), _ptr(q) if q is not None else None, int(method),
+                                            _ptr(ranks) if ranks is not None else None, _ptr(state["rank_res"]), _ptr(state["rank_slot"]),
+                                            _ptr(state["rank_prefix"]), _ptr(state["slot_prefix"]), _ptr(state["n_slots"]), _ptr(state["count"]),
+                                            _ptr(state["ranks"]), _ptr(state["values"]) if last else None,
+                                            nat.VAL_F32 if dtype == torch.float32 else nat.VAL_I32, int(device), current_stream(int(device))))
+    return state
+
+
+def _quantile_batches(q, ranks, B, call):
+    """more than 16 ranks are served in batches of 16: call(q batch | None, ranks batch | None, R) -> (values, ranks, count, missing)"""
+    import torch
+    P = q.shape[0] if q is not None else ranks.shape[1]
+    parts = []
+    for j0 in range(0, P, MAX_VALUE_RANKS):
+        j1 = min(P, j0 + MAX_VALUE_RANKS)
+        parts.append(call(np.ascontiguousarray(q[j0:j1]) if q is not None else None,
+                          np.ascontiguousarray(ranks[:, j0:j1]) if ranks is not None else None, j1 - j0))
+    if len(parts) == 1:
+        return parts[0]
+    return torch.cat([p[0] for p in parts], dim=1), torch.cat([p[1] for p in parts], dim=1), parts[0][2], parts[0][3]
+
+
+KMEANS_UPDATE_BATCH = 64                               # clusters whose sums one term_sums call of the update takes
 KMEANS_METRICS = ("dot", "l2")
 
 
@@ -2277,6 +2407,56 @@ class DeviceIndex:
         return SortedResults(*_facet_out(values, *self._value_topk_call(_values_on(values, self.device), dt, k, descending, id_offset, f, 0,
                                                                         rows_per_chunk)))
 
+    # ---- percentiles (vs_index_value_quantiles, vs_index_value_radix_counts) ------------------------------------------------------------------
+    def _value_quantiles_call(self, vals_dev, dt, q_dev, method, ranks_dev, R, f, bit0, rows_per_chunk):
+        """One vs_index_value_quantiles call on device buffers -> (values [B, R], ranks int64 [B, R], count, missing int64 [B]) CUDA tensors.
+        q_dev: float64 [R] or None; ranks_dev: int64 [B, R] or None."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        B, set_args = self._value_set_args(f, bit0)
+        vals = torch.empty((B, R), dtype=vals_dev.dtype, device=dev)
+        ranks = torch.empty((B, R), dtype=torch.int64, device=dev)
+        count, missing = (torch.empty(B, dtype=torch.int64, device=dev) for _ in range(2))
+        nat.check(nat.lib().vs_index_value_quantiles(self._h, *set_args, _ptr(vals_dev), dt, _ptr(q_dev) if q_dev is not None else None, method,
+                                                     _ptr(ranks_dev) if ranks_dev is not None else None, R, rows_per_chunk, _ptr(vals), _ptr(ranks),
+                                                     _ptr(count), _ptr(missing), current_stream(self.device)))
+        return vals, ranks, count, missing
+
+    def _value_radix_counts_call(self, vals_dev, dt, level, R, slot_prefix, n_slots, f, bit0, rows_per_chunk):
+        """One vs_index_value_radix_counts call -> (counts int64 [B, S, bins], missing int64 [B]) CUDA tensors; missing only at level 0.
+        slot_prefix int32 [B, R] / n_slots int32 [B]: the state of the step above, on this index's device (None at level 0)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        B, set_args = self._value_set_args(f, bit0)
+        bins = nat.VALUE_RADIX_BINS if level < 2 else nat.VALUE_RADIX_BINS // 2
+        counts = torch.empty((B, 1 if level == 0 else R, bins), dtype=torch.int64, device=dev)
+        missing = torch.empty(B, dtype=torch.int64, device=dev) if level == 0 else None
+        nat.check(nat.lib().vs_index_value_radix_counts(self._h, *set_args, _ptr(vals_dev), dt, level, R,
+                                                        _ptr(slot_prefix) if level else None, _ptr(n_slots) if level else None, rows_per_chunk,
+                                                        _ptr(counts), _ptr(missing) if level == 0 else None, current_stream(self.device)))
+        return (counts, missing) if level == 0 else (counts,)
+
+    def value_quantiles(self, values, q=None, method: str = "lower", ranks=None, filter=None, rows_per_chunk: int = 0) -> ValueQuantiles:
+        """Exact order statistics of a numeric field over a document set -> ValueQuantiles(values [B, R], ranks [B, R], count, missing).
+        q: quantiles in [0, 1] shared by the queries, turned into ranks by pos = q * (count - 1) and method "lower" (floor), "higher" (ceil)
+        or "nearest" (half to even); or ranks: 0-based ascending ranks, [R] or [B, R].  A rank outside the set's values gives the missing
+        sentinel and rank -1.  No interpolation, no sort: three counting passes over the set.  More than 16 ranks are served in batches of
+        16.  values, filter, outputs as in ``value_stats``."""
+        import torch
+        n = self.n_rows
+        dt, rows_per_chunk = _value_args(values, n, rows_per_chunk)
+        qa, method, ra = _quantile_args(q, method, ranks)
+        nat.require_device()
+        f = _value_set(filter, n, self.device)
+        B = f.n_queries if (f is not None and f.per_query) else 1
+        if ra is not None:
+            ra = _quantile_ranks_for(ra, B)
+        v = _values_on(values, self.device)
+        dev = torch.device("cuda", self.device)
+        call = lambda qb, rb, R: self._value_quantiles_call(v, dt, torch.from_numpy(qb).to(dev) if qb is not None else None, method,
+                                                            torch.from_numpy(rb).to(dev) if rb is not None else None, R, f, 0, rows_per_chunk)
+        return ValueQuantiles(*_facet_out(values, *_quantile_batches(qa, ra, B, call)))
+
     # ---- term aggregations: what a document set is about (vs_index_term_counts, vs_index_term_counts_ids) ---------------------------------
     def _term_counts_call(self, f, bit0, rows_per_chunk):
         """One vs_index_term_counts call on device buffers and torch's current stream -> (counts [B, V], total [B]) int64 CUDA tensors.
@@ -2813,6 +2993,39 @@ class ShardGroup:
         by_id = torch.where(ids < 0, torch.full_like(ids, 1 << 62), ids).argsort(dim=1, stable=True)
         order = by_id.gather(1, key.gather(1, by_id).argsort(dim=1, descending=True, stable=True))[:, :k]
         return SortedResults(*_facet_out(values, ids.gather(1, order), vals.gather(1, order)))
+
+    def value_quantiles(self, values, q=None, method: str = "lower", ranks=None, filter=None, rows_per_chunk: int = 0) -> ValueQuantiles:
+        """DeviceIndex.value_quantiles over the group's rows: three rounds of level calls -- every shard counts the level's digits of its
+        slice of the values and its bit range of the filter, the counts are added on the first shard's GPU, one step there picks each rank's
+        bin and names the next level's slots.  Integer counts: equal to the unsharded index bit for bit."""
+        import torch
+        n = self.n_rows
+        dt, rows_per_chunk = _value_args(values, n, rows_per_chunk)
+        qa, method, ra = _quantile_args(q, method, ranks)
+        nat.require_device()
+        dev0 = torch.device("cuda", self.device)
+        f = _value_set(filter, n, dev0)
+        B = f.n_queries if (f is not None and f.per_query) else 1
+        if ra is not None:
+            ra = _quantile_ranks_for(ra, B)
+        tdt = torch.float32 if dt == nat.VAL_F32 else torch.int32
+
+        def batch(qb, rb, R):
+            q_dev = torch.from_numpy(qb).to(dev0) if qb is not None else None
+            r_dev = torch.from_numpy(rb).to(dev0) if rb is not None else None
+            state = missing = None
+            for level in range(nat.VALUE_RADIX_LEVELS):
+                def one(sh, v, fs, row0):
+                    d = torch.device("cuda", sh.device)
+                    sp, ns = (state["slot_prefix"].to(d), state["n_slots"].to(d)) if level else (None, None)
+                    return sh._value_radix_counts_call(v, dt, level, R, sp, ns, fs, row0, rows_per_chunk)
+                parts = self._value_parts(values, f, one)
+                counts = sum((p[0] for p in parts[1:]), parts[0][0])
+                if level == 0:
+                    missing = sum((p[1] for p in parts[1:]), parts[0][1])
+                state = value_radix_step(level, counts, R, state, q_dev, method, r_dev, tdt, self.device)
+            return state["values"], state["ranks"], state["count"], missing
+        return ValueQuantiles(*_facet_out(values, *_quantile_batches(qa, ra, B, batch)))
 
     # ---- term aggregations ------------------------------------------------------------------------------------------------------------------
     def term_counts(self, filter=None, ids=None, rows_per_chunk: int = 0) -> TermCounts:

@@ -24,6 +24,7 @@ import torch
 from ... import _native as nat
 from ...device_index import Assignment, KMeansResult, KMEANS_UPDATE_BATCH, kmeans_loop, term_sum_topn, _assign_args, _kmeans_args, DeviceIndex, DiverseResults, Explanation, FacetCounts, FusedResults, GroupedResults, TermCounts, TermSums, TopFacets, TopTerms, TopWeights, _term_topn_args, _weight_topn_args, fuse_topk, _fuse_args, MAX_FUSE_DEPTH, MAX_FUSE_ENTRIES, _topn_args, NotBinaryError, RangeResults, ShardGroup, _diverse_args, _range_args, _grouped_args, _by_example_args, _explain_args, _int64_ids, _k_a_args, resparsify, topk_exclude
 from ...device_index import SortedResults, ValueHistogram, ValueStats, value_column, _value_bounds, _value_dtype, _value_edges, _value_topk_args
+from ...device_index import ValuePercentiles, _percentile_args, quantile_lerp
 
 logger = logging.getLogger(__name__)
 
@@ -744,6 +745,31 @@ class Index:
         v = self._value_field(field)
         filter = self._value_set(q_embs, min_score, filter)
         return SortedResults(*(self._to_api(t) for t in self._explain_target()[0].value_topk(v, k, descending=descending, filter=filter)))
+
+    def percentiles(self, field: str, pcts, q_embs=None, min_score=None, filter=None, method: str = "linear") -> ValuePercentiles:
+        """Exact percentiles of value field `field` over a document set -> ValuePercentiles(values [B, P], count, missing).  pcts: numbers
+        in 0..100.  With q = pct / 100 and pos = q * (count - 1): method "lower" gives the value at rank floor(pos), "higher" at ceil(pos),
+        "nearest" at rint(pos) (half to even), in the field's type; "linear" (the default, numpy's) selects the values at floor(pos) and
+        ceil(pos) exactly and interpolates lo + (hi - lo) * (pos - floor(pos)) in float64 (exactly lo where lo == hi).  A set without values
+        gives NaN / the missing sentinel.  The set as in ``value_stats``; any number of percentiles (16 a pass)."""
+        self._value_check(field, q_embs, min_score)
+        q = _percentile_args(pcts, method)
+        v = self._value_field(field)
+        filter = self._value_set(q_embs, min_score, filter)
+        target = self._explain_target()[0]
+        if method != "linear":
+            res = target.value_quantiles(v, q=q, method=method, filter=filter)
+            return ValuePercentiles(self._to_api(res.values), self._to_api(res.count), self._to_api(res.missing))
+        lo, hi = target.value_quantiles(v, q=q, method="lower", filter=filter), target.value_quantiles(v, q=q, method="higher", filter=filter)
+        pos = q[None, :] * (lo.count.cpu().numpy().astype(np.float64) - 1.0)[:, None]
+        vals = quantile_lerp(lo.values.cpu().numpy(), hi.values.cpu().numpy(), pos - np.floor(pos))
+        if v.dtype == torch.int32:                                  # (an int32 field's sentinel is a number: no answer is NaN here)
+            vals = np.where(lo.ranks.cpu().numpy() < 0, np.nan, vals)
+        return ValuePercentiles(self._to_api(torch.from_numpy(vals).to(lo.count.device)), self._to_api(lo.count), self._to_api(lo.missing))
+
+    def median(self, field: str, q_embs=None, min_score=None, filter=None, method: str = "linear") -> ValuePercentiles:
+        """``percentiles(field, [50], ...)``: the median of value field `field` over a document set, values [B, 1]."""
+        return self.percentiles(field, [50], q_embs=q_embs, min_score=min_score, filter=filter, method=method)
 
     def _added_values(self, values, n_add):
         """values= of add() / update() -> {name: ndarray [n_add] in the field's type}, or None for an index without value fields.  Raises

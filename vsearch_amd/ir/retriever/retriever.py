@@ -187,6 +187,14 @@ class Retriever(BiEncoder):
         index, q_emb, filter = self._match_set(queries, index, filter, must, must_not, should, min_should, dropout, a, batch_size)
         return index.histogram(field, edges, q_embs=q_emb, min_score=min_score, filter=filter)
 
+    def retrieve_percentiles(self, queries: Union[List[str], np.ndarray, T], field: str, pcts, min_score=0.0, method: str = "linear",
+                             dropout: float = 0, a: int = None, index: Index = None, batch_size: int = 32, filter=None, must=None, must_not=None,
+                             should=None, min_should: int = None):
+        """Exact percentiles of value field `field` over each query's matches -- ``Index.percentiles`` behind the query encoder, the match
+        set as in ``retrieve_sorted`` -> ValuePercentiles(values [B, P], count, missing); pcts in 0..100."""
+        index, q_emb, filter = self._match_set(queries, index, filter, must, must_not, should, min_should, dropout, a, batch_size)
+        return index.percentiles(field, pcts, q_embs=q_emb, min_score=min_score, filter=filter, method=method)
+
     def significant_terms(self, queries: Union[List[str], np.ndarray, T], min_score=None, k: int = None, topn: int = 20, method: str = "jlh",
                           min_count: int = 1, background=None, dropout: float = 0, a: int = None, index: Index = None, batch_size: int = 32,
                           filter=None, must=None, must_not=None, should=None, min_should: int = None):
