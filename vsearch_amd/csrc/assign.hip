@@ -18,8 +18,7 @@
 // (c) Half norms: one workgroup of 256 threads per centroid, strided partial sums and a halving tree in LDS.
 // (d) Label bitmaps: a wave owns two output words, reads the 64 labels behind them (shifted by bit0), takes one ballot per value and writes the
 //     two words of 64 values with one store each.
-#include "common.h"
-#include "staging.h"
+#include "agg_call.h"
 #include "assign_check.h"
 #include "topk_keys.h"
 
@@ -87,22 +86,11 @@ __device__ __forceinline__ uint64_t uniform64(uint64_t v) {
     return ((uint64_t)hi << 32) | lo;
 }
 
-// packet p: its 8 column ids and its 8 values widened to fp32 (nothing for a binary index)
+// packet p: its 8 column ids and its 8 values widened to fp32 (packets.h)
 template <int SD>
 __device__ __forceinline__ void load_packet(const AssignArgs& a, uint64_t p, uint4& c, float (&v)[8]) {
     c = a.cols[p];
-    if constexpr (SD == VS_F32) {
-        const float4 x = reinterpret_cast<const float4*>(a.vals)[2 * p], y = reinterpret_cast<const float4*>(a.vals)[2 * p + 1];
-        v[0] = x.x, v[1] = x.y, v[2] = x.z, v[3] = x.w, v[4] = y.x, v[5] = y.y, v[6] = y.z, v[7] = y.w;
-    } else if constexpr (SD == VS_F16) {
-        const uint4 x = reinterpret_cast<const uint4*>(a.vals)[p];
-        const uint32_t h[4] = {x.x, x.y, x.z, x.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            v[2 * j] = __half2float(__ushort_as_half((unsigned short)(h[j] & 0xFFFFu)));
-            v[2 * j + 1] = __half2float(__ushort_as_half((unsigned short)(h[j] >> 16)));
-        }
-    }
+    load_vals<SD>(a.vals, p, v);
 }
 
 template <int CPL> struct SlabVec;
@@ -291,16 +279,6 @@ __global__ __launch_bounds__(kBitmapThreads) void label_bitmaps_kernel(BitmapArg
     }
 }
 
-int plan_or_fail(int rc, const char* msg) { return rc == VS_OK ? VS_OK : fail(rc, "%s", msg); }
-
-int device_in_range(int device) {
-    VS_TRY(need_device());
-    int ndev = 0;
-    VS_HIP(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(VS_EINVAL, "device %d out of range", device);
-    return VS_OK;
-}
-
 }  // namespace
 
 extern "C" int vs_assign_plan(int64_t n_rows, int32_t K, int32_t n_cols, int64_t rows_per_chunk, int32_t* out_slice_w, int32_t* out_slices,
@@ -338,9 +316,7 @@ extern "C" int vs_centroid_half_norms(const float* c, int64_t ldc, int32_t K, in
     }
     VS_STAGE("half_norms", s);
     if (!dev) VS_TRY(st_o.back(s));
-    if (!stream || !dev) VS_HIP(hipStreamSynchronize(s));
-    if (Profiler::get().on) Profiler::get().drain();
-    return VS_OK;
+    return finish_call(dev, stream, s);
 }
 
 extern "C" int vs_index_assign(vs_index* idx, const float* centroids, int64_t ldc, int32_t K, const float* bias, const uint32_t* filter,
@@ -377,7 +353,7 @@ extern "C" int vs_index_assign(vs_index* idx, const float* centroids, int64_t ld
     a.vals = idx->vals.p;
     a.n_cols = V;
     a.n_rows = idx->n_rows;
-    a.live = idx->has_tomb ? idx->live.as<uint32_t>() : nullptr;     // tombstones are ANDed in at bit 0 whatever filter_bit0 is
+    a.live = live_words(idx);                                       // tombstones are ANDed in at bit 0 whatever filter_bit0 is
     a.filt = d_f;
     a.bit0 = filter_bit0;
     a.rows_per_chunk = plan.rows_per_chunk;
@@ -448,7 +424,5 @@ extern "C" int vs_label_bitmaps(const int32_t* labels, int64_t n_rows, const int
     }
     VS_STAGE("label_bitmaps", s);
     if (!dev) VS_TRY(st_o.back(s));
-    if (!stream || !dev) VS_HIP(hipStreamSynchronize(s));
-    if (Profiler::get().on) Profiler::get().drain();
-    return VS_OK;
+    return finish_call(dev, stream, s);
 }

@@ -1,5 +1,5 @@
-// bitmap_span.h -- how a wave walks a packed row bitmap (the layout of vs_index_search_filtered) in spans of 2048 rows, whatever bit the rows
-// start at: what facets.hip and term_agg.hip share.
+// bitmap_span.h -- how a wave reads a packed row bitmap (the layout of vs_index_search_filtered) in spans of 2048 rows, whatever bit the rows
+// start at: the two primitives under the walks of set_walk.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -2,21 +2,17 @@
 // No reference counterpart (the reference only has topk, index.py:92).  Nothing here touches a search kernel: the set arrives as a packed
 // bitmap in the layout of vs_index_search_filtered (a match_filter result, a DocFilter), the labels as int32 [n_rows].
 //
-// (a) Counts: a workgroup owns a chunk of rows and a tile of QT queries.  A wave takes spans of 2048 rows: lane l loads words l and l + 1 of
-//     every query's bitmap (two coalesced 256-byte reads a query), so the 64 bits of any 64-row step -- whatever bit0 is -- come out of three
-//     lane reads.  A span whose words are all zero is left at once, a 64-row step whose bits are all zero is skipped, and only lanes whose row
-//     is in SOME query's set load their label: once for the whole tile.
+// (a) Counts: a workgroup owns a chunk of rows and a tile of QT queries and walks the bitmaps with walk_tile (set_walk.h): a wave per 2048-row
+//     span, all-zero spans and steps left at once, and only lanes whose row is in SOME query's set load their label: once for the whole tile.
 //       LDS regime    (QT x n_labels <= VS_FACET_LDS_BINS): one uint32 histogram per query of the tile in LDS, filled with LDS atomics and
 //                     flushed at the end of the chunk -- one 64-bit vector atomicAdd per non-zero bin into counts (zeroed on the stream first).
 //       global regime (n_labels > VS_FACET_LDS_BINS): 64-bit vector atomicAdd straight into counts.
 //     A wave whose rows of a step all carry one label adds once (the popcount): the one-label worst case costs an add a step, not 64
 //     serialised ones.  total / other are summed per wave in scalar registers, per workgroup in LDS, and added to global memory once.
 // (b) Top-n: one workgroup per query streams the counts as keys (count << 32) | (0xFFFFFFFF - label) -- larger key = larger count, then
-//     smaller label -- through the 4096-key LDS buffer of the scans, pruned to n by wg_sort_desc when more than 2048 are in.
-#include "common.h"
-#include "bitmap_span.h"
-#include "staging.h"
-#include "topk_keys.h"
+//     smaller label -- through stream_topn (topn_stream.h).
+#include "agg_call.h"
+#include "topn_stream.h"
 
 #include <algorithm>
 
@@ -26,22 +22,13 @@ namespace {
 
 constexpr int kFacetThreads = 256;
 constexpr int kFacetWaves = kFacetThreads / 64;
-constexpr int kSpanRows = 2048;                       // rows a wave loads the bitmap words of at a time: 64 lanes x 32 bits
-constexpr int64_t kFacetMaxRows = 0xFFFFFFFFll;       // a count fits 32 bits (the LDS bins, the top-n keys)
 constexpr int kFacetAutoItems = 1024;                 // workgroups the automatic plan aims at (4 a CU)
 constexpr int64_t kFacetMinChunk = 8192;              // rows of an automatic chunk at least
-constexpr int kTopnCap = 4096;                        // keys of the top-n candidate buffer
-constexpr int kTopnKeep = 2048;                       // pruned when more are in
 
 struct FacetArgs {
-    const uint32_t* words;            // [B, ld_words] or null (every row set)
-    int64_t bit0, ld_words;
-    const uint32_t* and_words;        // shared by the queries, or null
-    int64_t and_bit0;
+    RowSet set;
     const int32_t* labels;            // [n_rows]
-    int64_t n_rows;
-    int32_t n_labels, B;
-    int64_t rows_per_chunk;
+    int32_t n_labels;
     unsigned long long* counts;       // [B, ld_counts], zeroed by the caller
     int64_t ld_counts;
     unsigned long long* total;        // [B], zeroed by the caller
@@ -54,9 +41,9 @@ __global__ __launch_bounds__(kFacetThreads) void facet_counts_kernel(FacetArgs a
     __shared__ uint32_t s_tot[QT], s_oth[QT];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int q0 = (int)blockIdx.y * QT;
-    const int nq = min(QT, a.B - q0);
-    const int64_t r0 = (int64_t)blockIdx.x * a.rows_per_chunk;
-    const int64_t r1 = min(a.n_rows, r0 + a.rows_per_chunk);
+    const int nq = min(QT, a.set.B - q0);
+    const int64_t r0 = (int64_t)blockIdx.x * a.set.rows_per_chunk;
+    const int64_t r1 = min(a.set.n_rows, r0 + a.set.rows_per_chunk);
     const uint32_t L = (uint32_t)a.n_labels;
     if constexpr (!GLOBAL)
         for (uint32_t i = tid; i < (uint32_t)nq * L; i += kFacetThreads) facet_hist[i] = 0u;
@@ -68,77 +55,40 @@ __global__ __launch_bounds__(kFacetThreads) void facet_counts_kernel(FacetArgs a
     uint32_t tot[QT], oth[QT];                                   // wave-uniform: a chunk holds fewer than 2^32 rows
 #pragma unroll
     for (int q = 0; q < QT; ++q) tot[q] = oth[q] = 0u;
-    const int64_t n_w = (a.bit0 + a.n_rows + 31) >> 5, n_aw = (a.and_bit0 + a.n_rows + 31) >> 5;
-    for (int64_t rb = r0 + (int64_t)w * kSpanRows; rb < r1; rb += (int64_t)kFacetWaves * kSpanRows) {
-        const int nsub = (int)((min(r1, rb + kSpanRows) - rb + 63) >> 6);
-        Span an{~0u, ~0u};
-        int sha = 0;
-        if (a.and_words) {
-            const int64_t p = a.and_bit0 + rb;
-            an = load_span(a.and_words, p >> 5, n_aw, lane);
-            sha = (int)(p & 31);
-            if (__builtin_amdgcn_ballot_w64((an.lo | an.hi) != 0u) == 0ull) continue;
-        }
-        Span sp[QT];
-        Span u{~0u, ~0u};
-        int sh = 0;
-        if (a.words) {
-            const int64_t p = a.bit0 + rb;
-            sh = (int)(p & 31);
-            u.lo = u.hi = 0u;
+    walk_tile<QT, kFacetWaves>(a.set, q0, nq, r0, r1, w, lane, [&](int64_t row0, uint64_t many, const Span* sp, int s, int sh, uint64_t live) {
+        int32_t label = -1;
+        if ((many >> lane) & 1ull) label = a.labels[row0 + lane];                    // once for the tile
+        const bool in_range = (uint32_t)label < L;                                   // -1 and anything too large: `other`
 #pragma unroll
-            for (int q = 0; q < QT; ++q) {
-                sp[q] = Span{0u, 0u};
-                if (q < nq) sp[q] = load_span(a.words + (size_t)(q0 + q) * (size_t)a.ld_words, p >> 5, n_w, lane);
-                u.lo |= sp[q].lo;
-                u.hi |= sp[q].hi;
-            }
-            if (__builtin_amdgcn_ballot_w64((u.lo | u.hi) != 0u) == 0ull) continue;
-        } else {
-#pragma unroll
-            for (int q = 0; q < QT; ++q) sp[q] = u;
-        }
-        for (int s = 0; s < nsub; ++s) {
-            const int64_t row0 = rb + (int64_t)s * 64;
-            const int64_t nvalid = r1 - row0;                                        // >= 1
-            const uint64_t vm = nvalid >= 64 ? ~0ull : ((1ull << nvalid) - 1ull);    // bits at or past the last row are ignored
-            const uint64_t live = window64(an, s, sha) & vm;
-            const uint64_t many = window64(u, s, sh) & live;
-            if (many == 0ull) continue;                                              // (uniform) no label is touched
-            int32_t label = -1;
-            if ((many >> lane) & 1ull) label = a.labels[row0 + lane];                // once for the tile
-            const bool in_range = (uint32_t)label < L;                               // -1 and anything too large: `other`
-#pragma unroll
-            for (int q = 0; q < QT; ++q) {
-                if (q >= nq) continue;
-                const uint64_t m = window64(sp[q], s, sh) & live;
-                if (m == 0ull) continue;
-                const bool ok = ((m >> lane) & 1ull) && in_range;
-                const unsigned long long okm = __builtin_amdgcn_ballot_w64(ok);
-                tot[q] += (uint32_t)__popcll(m);
-                oth[q] += (uint32_t)(__popcll(m) - __popcll(okm));
-                if (okm == 0ull) continue;
-                const int first = __builtin_ctzll(okm);
-                const int32_t l0 = __builtin_amdgcn_readlane(label, first);
-                const bool one = __builtin_amdgcn_ballot_w64(ok && label == l0) == okm;     // every row of the step on one label: add once
-                if constexpr (GLOBAL) {
-                    unsigned long long* dst = a.counts + (size_t)(q0 + q) * (size_t)a.ld_counts;
-                    if (one) {
-                        if (lane == first) atomicAdd(dst + l0, (unsigned long long)__popcll(okm));
-                    } else if (ok) {
-                        atomicAdd(dst + label, 1ull);
-                    }
-                } else {
-                    uint32_t* dst = facet_hist + (size_t)q * L;
-                    if (one) {
-                        if (lane == first) atomicAdd(dst + l0, (uint32_t)__popcll(okm));
-                    } else if (ok) {
-                        atomicAdd(dst + label, 1u);
-                    }
+        for (int q = 0; q < QT; ++q) {
+            if (q >= nq) continue;
+            const uint64_t m = window64(sp[q], s, sh) & live;
+            if (m == 0ull) continue;
+            const bool ok = ((m >> lane) & 1ull) && in_range;
+            const unsigned long long okm = __builtin_amdgcn_ballot_w64(ok);
+            tot[q] += (uint32_t)__popcll(m);
+            oth[q] += (uint32_t)(__popcll(m) - __popcll(okm));
+            if (okm == 0ull) continue;
+            const int first = __builtin_ctzll(okm);
+            const int32_t l0 = __builtin_amdgcn_readlane(label, first);
+            const bool one = __builtin_amdgcn_ballot_w64(ok && label == l0) == okm;     // every row of the step on one label: add once
+            if constexpr (GLOBAL) {
+                unsigned long long* dst = a.counts + (size_t)(q0 + q) * (size_t)a.ld_counts;
+                if (one) {
+                    if (lane == first) atomicAdd(dst + l0, (unsigned long long)__popcll(okm));
+                } else if (ok) {
+                    atomicAdd(dst + label, 1ull);
+                }
+            } else {
+                uint32_t* dst = facet_hist + (size_t)q * L;
+                if (one) {
+                    if (lane == first) atomicAdd(dst + l0, (uint32_t)__popcll(okm));
+                } else if (ok) {
+                    atomicAdd(dst + label, 1u);
                 }
             }
         }
-    }
+    });
     if (lane == 0) {
 #pragma unroll
         for (int q = 0; q < QT; ++q) {
@@ -169,12 +119,11 @@ struct FacetPlan {
 
 // the plan rule: pure host arithmetic
 int facet_plan(int64_t n_rows, int32_t B, int32_t n_labels, bool per_query, int64_t rows_per_chunk, FacetPlan* out) {
-    if (n_rows < 1 || n_rows > kFacetMaxRows) return fail(VS_EINVAL, "n_rows must be in 1..2^32 - 1 (got %lld)", (long long)n_rows);
+    char msg[256];
+    VS_TRY(plan_or_fail(check_n_rows(n_rows, msg, sizeof msg), msg));
     if (B < 1) return fail(VS_EINVAL, "B must be positive");
     if (n_labels < 1) return fail(VS_EINVAL, "n_labels must be at least 1 (got %d)", n_labels);
-    if (!per_query && B > 1) return fail(VS_EINVAL, "one bitmap for all queries (ld_words = 0) takes B = 1, got B = %d", B);
-    if (rows_per_chunk < 0 || rows_per_chunk % 64 != 0 || rows_per_chunk > kFacetMaxRows)
-        return fail(VS_EINVAL, "rows_per_chunk must be 0 (automatic) or a positive multiple of 64 below 2^32 (got %lld)", (long long)rows_per_chunk);
+    VS_TRY(plan_or_fail(check_chunking(per_query, B, rows_per_chunk, "bitmap", msg, sizeof msg), msg));
     FacetPlan p;
     p.regime = n_labels > VS_FACET_LDS_BINS ? 1 : 0;
     p.qt = 1;
@@ -215,19 +164,16 @@ int facet_check(const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B
                 int64_t rows_per_chunk, const int64_t* counts, int64_t ld_counts, const int64_t* total, const int64_t* other, FacetPlan* plan) {
     if (!labels || !counts || !total || !other) return fail(VS_EINVAL, "NULL argument");
     if (bit0 < 0) return fail(VS_EINVAL, "bit0 must be >= 0");
-    const bool per_query = words && ld_words != 0;
-    VS_TRY(facet_plan(n_rows, B, n_labels, per_query, rows_per_chunk, plan));
-    const int64_t span = (bit0 + n_rows + 31) >> 5;
-    if (words && (ld_words < 0 || (ld_words > 0 && ld_words < span)))
-        return fail(VS_EINVAL, "ld_words = %lld is shorter than the %lld words a query's bitmap spans", (long long)ld_words, (long long)span);
+    VS_TRY(facet_plan(n_rows, B, n_labels, words && ld_words != 0, rows_per_chunk, plan));
+    char msg[256];
+    VS_TRY(plan_or_fail(check_ld_words(words != nullptr, bit0, ld_words, n_rows, msg, sizeof msg), msg));
     if (ld_counts < n_labels) return fail(VS_EINVAL, "ld_counts = %lld is shorter than n_labels = %d", (long long)ld_counts, n_labels);
     if (plan->chunks > 0x7FFFFFFF || ceil_div64(B, plan->qt) > 65535)
         return fail(VS_EINVAL, "%lld chunks x %d queries are too many for one call", (long long)plan->chunks, B);
     return VS_OK;
 }
 
-// One call on `device`.  and_user: a caller's second bitmap (of the kind of the other pointers, at bit0); and_dev: a device bitmap at bit 0
-// (an index's live rows).  At most one of the two.
+// One call on `device`.  and_user / and_dev: BitmapStage's (agg_call.h).
 int facet_call(int device, const uint32_t* words, int64_t bit0, int64_t ld_words, const uint32_t* and_user, const uint32_t* and_dev, int32_t B,
                const int32_t* labels, int64_t n_rows, int32_t n_labels, const FacetPlan& plan, int64_t* counts, int64_t ld_counts, int64_t* total,
                int64_t* other, void* stream) {
@@ -237,64 +183,31 @@ int facet_call(int device, const uint32_t* words, int64_t bit0, int64_t ld_words
     VS_TRY(pointers_kind(ptrs, names, 6, device, &dev));
     VS_HIP(hipSetDevice(device));
     hipStream_t s = (hipStream_t)stream;
-    const int64_t span = (bit0 + n_rows + 31) >> 5;
-    Staged st_w, st_a, st_l;
-    DevBuf out;
+    BitmapStage st;
+    Staged st_l;
+    CountsOut out;
     FacetArgs a{};
-    uint32_t *d_w, *d_a;
     int32_t* d_l;
-    VS_TRY(st_w.in(words, (size_t)((B - 1) * ld_words + span), dev, true, s, &d_w));
-    VS_TRY(st_a.in(and_user, (size_t)span, dev, true, s, &d_a));
+    VS_TRY(st.in(words, bit0, ld_words, and_user, and_dev, B, n_rows, plan.rows_per_chunk, dev, s, &a.set));
     VS_TRY(st_l.in(labels, (size_t)n_rows, dev, true, s, &d_l));
-    a.words = d_w;
-    a.bit0 = bit0;
-    a.ld_words = words ? ld_words : 0;
-    a.and_words = and_user ? d_a : and_dev;
-    a.and_bit0 = and_user ? bit0 : 0;
     a.labels = d_l;
-    a.n_rows = n_rows;
     a.n_labels = n_labels;
-    a.B = B;
-    a.rows_per_chunk = plan.rows_per_chunk;
-    const size_t n_cnt = (size_t)B * (size_t)n_labels;
-    if (dev) {
-        a.counts = reinterpret_cast<unsigned long long*>(counts);
-        a.ld_counts = ld_counts;
-        a.total = reinterpret_cast<unsigned long long*>(total);
-        a.other = reinterpret_cast<unsigned long long*>(other);
-        if (ld_counts == n_labels || B == 1) VS_HIP(hipMemsetAsync(a.counts, 0, n_cnt * 8, s));
-        else VS_HIP(hipMemset2DAsync(a.counts, (size_t)ld_counts * 8, 0, (size_t)n_labels * 8, (size_t)B, s));
-        VS_HIP(hipMemsetAsync(a.total, 0, (size_t)B * 8, s));
-        VS_HIP(hipMemsetAsync(a.other, 0, (size_t)B * 8, s));
-    } else {
-        VS_TRY(out.alloc((n_cnt + 2 * (size_t)B) * 8));
-        a.counts = out.as<unsigned long long>();
-        a.ld_counts = n_labels;
-        a.total = a.counts + n_cnt;
-        a.other = a.total + B;
-        VS_HIP(hipMemsetAsync(out.p, 0, out.bytes, s));
-    }
+    VS_TRY(out.bind(dev, counts, ld_counts, n_labels, B, {total, other}, s));
+    a.counts = out.mat;
+    a.ld_counts = out.ld;
+    a.total = out.vec[0];
+    a.other = out.vec[1];
     {
         ProfScope prof("facet_counts", s);
         const dim3 grid((unsigned)plan.chunks, (unsigned)ceil_div64(B, plan.qt));
-        const int rc = plan.qt == 8 ? facet_launch_qt<8>(plan, a, grid, s)
-                     : plan.qt == 4 ? facet_launch_qt<4>(plan, a, grid, s)
-                     : plan.qt == 2 ? facet_launch_qt<2>(plan, a, grid, s)
-                                    : facet_launch_qt<1>(plan, a, grid, s);
-        if (rc != VS_OK) {
-            (void)hipStreamSynchronize(s);                          // staging buffers die here
-            return rc;
-        }
+        VS_TRY(launch_rc(plan.qt == 8 ? facet_launch_qt<8>(plan, a, grid, s)
+                         : plan.qt == 4 ? facet_launch_qt<4>(plan, a, grid, s)
+                         : plan.qt == 2 ? facet_launch_qt<2>(plan, a, grid, s)
+                                        : facet_launch_qt<1>(plan, a, grid, s), s));
     }
     VS_STAGE("facet_counts", s);
-    if (!dev) {
-        VS_HIP(hipMemcpy2DAsync(counts, (size_t)ld_counts * 8, a.counts, (size_t)n_labels * 8, (size_t)n_labels * 8, (size_t)B, hipMemcpyDeviceToHost, s));
-        VS_HIP(hipMemcpyAsync(total, a.total, (size_t)B * 8, hipMemcpyDeviceToHost, s));
-        VS_HIP(hipMemcpyAsync(other, a.other, (size_t)B * 8, hipMemcpyDeviceToHost, s));
-    }
-    if (!stream || !dev) VS_HIP(hipStreamSynchronize(s));
-    if (Profiler::get().on) Profiler::get().drain();
-    return VS_OK;
+    if (!dev) VS_TRY(out.back(s));
+    return finish_call(dev, stream, s);
 }
 
 // ---- top-n ---------------------------------------------------------------------------------------------------------------------------
@@ -308,51 +221,17 @@ struct TopnArgs {
 };
 
 __global__ __launch_bounds__(kFacetThreads) void facet_topn_kernel(TopnArgs a) {
-    __shared__ uint64_t cand[kTopnCap];
+    __shared__ uint64_t cand[kTopCap];
     __shared__ int cnt_sh;
-    const int tid = threadIdx.x, lane = tid & 63;
-    constexpr int SB = (kTopnCap - kTopnKeep) / kFacetThreads;   // steps between prune checks
-    static_assert(SB >= 1, "a step adds up to kFacetThreads candidates");
     const int K = a.n;
     const size_t b = blockIdx.x;
     const int64_t* src = a.counts + b * (size_t)a.ld_counts;
-    if (tid == 0) cnt_sh = 0;
-    __syncthreads();
-    uint64_t tau = 0;
-    const int iters = (a.n_labels + kFacetThreads - 1) / kFacetThreads;
-    for (int it0 = 0; it0 < iters; it0 += SB) {
-        const int it1 = min(iters, it0 + SB);
-        for (int it = it0; it < it1; ++it) {
-            const int l = it * kFacetThreads + tid;
-            uint64_t key = 0ull;
-            if (l < a.n_labels) {
-                const int64_t c = src[l];
-                if (c >= a.min_count) key = ((uint64_t)(c < 0xFFFFFFFFll ? c : 0xFFFFFFFFll) << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)l);
-            }
-            const bool pass = key > tau;                          // (key 0: no candidate)
-            const unsigned long long m = __builtin_amdgcn_ballot_w64(pass);
-            if (m) {
-                int base = 0;
-                if (lane == 0) base = atomicAdd(&cnt_sh, __popcll(m));
-                base = __shfl(base, 0, 64);
-                if (pass) cand[base + __popcll(m & ((1ull << lane) - 1ull))] = key;
-            }
-        }
-        __syncthreads();
-        const int cnt = cnt_sh;
-        const bool last = it1 >= iters;
-        if (last || cnt > kTopnKeep) {                           // uniform: cnt read after the barrier
-            for (int i = cnt + tid; i < kTopnCap; i += kFacetThreads) cand[i] = 0ull;
-            wg_sort_desc<kFacetThreads>(cand, kTopnCap, tid);
-            if (!last && cnt > K) {
-                tau = cand[K - 1];
-                __syncthreads();
-                if (tid == 0) cnt_sh = K;
-            }
-        }
-        __syncthreads();
-    }
-    for (int i = tid; i < K; i += kFacetThreads) {                // every slot is written: label -1 / count 0 behind the last
+    stream_topn<kFacetThreads>(a.n_labels, K, [&](int64_t l) -> uint64_t {
+        const int64_t c = src[l];
+        if (c < a.min_count) return 0ull;
+        return ((uint64_t)(c < 0xFFFFFFFFll ? c : 0xFFFFFFFFll) << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)l);
+    }, cand, &cnt_sh);
+    for (int i = threadIdx.x; i < K; i += kFacetThreads) {        // every slot is written: label -1 / count 0 behind the last
         const uint64_t key = cand[i];
         a.out_labels[b * (size_t)K + i] = key ? (int32_t)(0xFFFFFFFFu - (uint32_t)key) : -1;
         a.out_counts[b * (size_t)K + i] = (int64_t)(key >> 32);
@@ -378,10 +257,7 @@ extern "C" int vs_facet_counts(const uint32_t* words, int64_t bit0, int64_t ld_w
                                int64_t* other, int device, void* stream) {
     FacetPlan plan;
     VS_TRY(facet_check(words, bit0, ld_words, B, labels, n_rows, n_labels, rows_per_chunk, counts, ld_counts, total, other, &plan));
-    VS_TRY(need_device());
-    int ndev = 0;
-    VS_HIP(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(VS_EINVAL, "device %d out of range", device);
+    VS_TRY(device_in_range(device));
     return facet_call(device, words, bit0, ld_words, and_words, nullptr, B, labels, n_rows, n_labels, plan, counts, ld_counts, total, other, stream);
 }
 
@@ -391,9 +267,8 @@ extern "C" int vs_index_facet_counts(vs_index* idx, const uint32_t* words, int64
     if (!idx) return fail(VS_EINVAL, "NULL argument");
     FacetPlan plan;
     VS_TRY(facet_check(words, bit0, ld_words, B, labels, idx->n_rows, n_labels, rows_per_chunk, counts, ld_counts, total, other, &plan));
-    // tombstones are ANDed in, as every search does (the live bitmap starts at bit 0 whatever bit0 is)
-    const uint32_t* live = idx->has_tomb ? idx->live.as<uint32_t>() : nullptr;
-    return facet_call(idx->device, words, bit0, ld_words, nullptr, live, B, labels, idx->n_rows, n_labels, plan, counts, ld_counts, total, other, stream);
+    return facet_call(idx->device, words, bit0, ld_words, nullptr, live_words(idx), B, labels, idx->n_rows, n_labels, plan, counts, ld_counts, total,
+                      other, stream);
 }
 
 extern "C" int vs_facet_topn(const int64_t* counts, int64_t ld_counts, int32_t B, int32_t n_labels, int32_t n, int64_t min_count,
@@ -403,10 +278,7 @@ extern "C" int vs_facet_topn(const int64_t* counts, int64_t ld_counts, int32_t B
     if (n_labels < 1) return fail(VS_EINVAL, "n_labels must be at least 1 (got %d)", n_labels);
     if (n < 1 || n > VS_FACET_MAX_TOPN) return fail(VS_EINVAL, "n must be in 1..%d (got %d)", VS_FACET_MAX_TOPN, n);
     if (ld_counts < n_labels) return fail(VS_EINVAL, "ld_counts = %lld is shorter than n_labels = %d", (long long)ld_counts, n_labels);
-    VS_TRY(need_device());
-    int ndev = 0;
-    VS_HIP(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(VS_EINVAL, "device %d out of range", device);
+    VS_TRY(device_in_range(device));
     const void* ptrs[3] = {counts, out_labels, out_counts};
     const char* names[3] = {"counts", "out_labels", "out_counts"};
     bool dev = false;
@@ -434,7 +306,5 @@ extern "C" int vs_facet_topn(const int64_t* counts, int64_t ld_counts, int32_t B
         VS_TRY(st[1].back(s));
         VS_TRY(st[2].back(s));
     }
-    if (!stream || !dev) VS_HIP(hipStreamSynchronize(s));
-    if (Profiler::get().on) Profiler::get().drain();
-    return VS_OK;
+    return finish_call(dev, stream, s);
 }

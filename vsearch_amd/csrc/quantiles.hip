@@ -3,7 +3,7 @@
 // digit radix select on the uint32 order keys of value_check.h, three levels (bits 31..21, 20..10, 9..0: quantile_check.h), every level one
 // counting pass over bitmaps and values and one tiny step.  All integer: shards add their counts between the levels.
 //
-// (a) Counting (value_radix_kernel): a workgroup owns a chunk of rows and a tile of QT queries and walks the bitmaps with walk_set as the
+// (a) Counting (value_radix_kernel): a workgroup owns a chunk of rows and a tile of QT queries and walks the bitmaps with walk_tile (set_walk.h) as the
 //     histogram of values.hip does.  LDS: one uint32 histogram of `bins` per (query, slot).  Level 0 has one slot a query and counts the missing
 //     rows; at levels 1 and 2 a query's slots are the sorted distinct key prefixes its ranks resolved to (padded to 16 in LDS), a row's slot is
 //     radix_find_slot (branch-free, 4 steps and a compare), a row of no slot costs no atomic.  When every counted row of a 64-row step falls
@@ -12,12 +12,9 @@
 // (b) Step (value_radix_step_kernel): one workgroup a query.  Per slot a block prefix scan of its bins into LDS, per rank radix_find_bin; then
 //     the ranks' extended prefixes are deduplicated and sorted into the next level's slots (R <= 16: counted, not sorted).  Level 0 forms count
 //     and the ranks (quantile_rank), level 2 writes the values.
-#include "common.h"
-#include "bitmap_span.h"
-#include "staging.h"
+#include "agg_call.h"
 #include "value_check.h"
 #include "quantile_check.h"
-#include "value_set.h"
 
 using namespace vs;
 
@@ -61,9 +58,9 @@ __global__ __launch_bounds__(kValThreads) void value_radix_kernel(RadixArgs a) {
     __shared__ int s_ns[QT];                                     // slots in use
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int q0 = (int)blockIdx.y * QT;
-    const int nq = min(QT, a.s.B - q0);
-    const int64_t r0 = (int64_t)blockIdx.x * a.s.rows_per_chunk;
-    const int64_t r1 = min(a.s.n_rows, r0 + a.s.rows_per_chunk);
+    const int nq = min(QT, a.s.set.B - q0);
+    const int64_t r0 = (int64_t)blockIdx.x * a.s.set.rows_per_chunk;
+    const int64_t r1 = min(a.s.set.n_rows, r0 + a.s.set.rows_per_chunk);
     const int level = TOP ? 0 : a.level;
     const uint32_t bins = (uint32_t)radix_bins(level);
     const uint32_t qstride = (TOP ? 1u : (uint32_t)a.R) * bins;  // uint32 words of a query's histograms
@@ -89,7 +86,8 @@ __global__ __launch_bounds__(kValThreads) void value_radix_kernel(RadixArgs a) {
 #pragma unroll
     for (int q = 0; q < QT; ++q) mis[q] = 0u;
     const int shift = radix_shift(level);
-    walk_set<QT>(a.s, q0, nq, r0, r1, w, lane, [&](int64_t, uint32_t, uint32_t key, const Span* sp, int s, int sh, uint64_t live) {
+    walk_tile<QT, kValWaves>(a.s.set, q0, nq, r0, r1, w, lane, [&](int64_t row0, uint64_t many, const Span* sp, int s, int sh, uint64_t live) {
+        const uint32_t key = (many >> lane) & 1ull ? value_key(a.s.values[row0 + lane], a.s.dtype) : 0u;      // once for the tile
         const uint32_t dig = (key >> shift) & (bins - 1u);                            // once for the tile
         const uint32_t pre = TOP ? 0u : radix_prefix(key, level);
 #pragma unroll
@@ -261,7 +259,7 @@ int radix_launch_top(const RadixArgs& a, int32_t qt, dim3 grid, size_t lds, hipS
 
 // zero a level's counts (and missing at level 0) and count; everything on the device
 int radix_counts_launch(const RadixArgs& a, const ValuePlan& plan, hipStream_t s) {
-    const int32_t B = a.s.B;
+    const int32_t B = a.s.set.B;
     VS_HIP(hipMemsetAsync(a.counts, 0, level_counts(B, a.R, a.level) * 8, s));
     if (a.level == 0) VS_HIP(hipMemsetAsync(a.missing, 0, (size_t)B * 8, s));
     ProfScope prof("value_radix_counts", s);
@@ -320,7 +318,7 @@ int counts_call(int device, const uint32_t* words, int64_t bit0, int64_t ld_word
     SetStage st;
     Staged st_p, st_n, st_c, st_m;
     RadixArgs a{};
-    VS_TRY(st.in(words, bit0, ld_words, and_user, and_dev, B, values, dtype, n_rows, plan, dev, s, &a.s));
+    VS_TRY(st.in(words, bit0, ld_words, and_user, and_dev, B, values, dtype, n_rows, plan.rows_per_chunk, dev, s, &a.s));
     uint32_t* d_p;
     int32_t* d_n;
     int64_t *d_c, *d_m;
@@ -358,7 +356,7 @@ int quantiles_call(int device, const uint32_t* words, int64_t bit0, int64_t ld_w
     Staged st_q, st_r, st_v, st_o, st_c, st_m;
     RadixArgs ca{};
     StepArgs sa{};
-    VS_TRY(st.in(words, bit0, ld_words, and_user, and_dev, B, values, dtype, n_rows, plan, dev, s, &ca.s));
+    VS_TRY(st.in(words, bit0, ld_words, and_user, and_dev, B, values, dtype, n_rows, plan.rows_per_chunk, dev, s, &ca.s));
     double* d_q;
     int64_t *d_r, *d_m;
     VS_TRY(st_q.in(q, (size_t)R, dev, true, s, &d_q));

@@ -2,6 +2,7 @@
 // vs_term_sum_topn) that need no device: column tiles, chunks, sizes and strides -- and term_fx, the fixed-point image of a value, which the kernel and
 // the stand-alone check share.  A host id list is checked by term_check_ids_host of
 // term_agg_check.h, whose limits (rows, columns, span, the automatic plan's aim) hold here as well.
+// What every aggregation over a row set checks alike (rows, batch, chunking, bitmap and id-list geometry, auto_chunk) is set_check.h's.
 // Plain C++ with no HIP in it, so that a stand-alone program can run them under a host sanitizer (tests/test_term_sum_cpu.py builds one).
 #pragma once
 
@@ -32,19 +33,14 @@ VS_TERM_HD inline uint64_t term_fx(float v) {
 
 struct TermSumPlan {
     int32_t tiles = 1, tile_cols = 1;  // column tile t holds columns [t * tile_cols, min(n_cols, (t + 1) * tile_cols)): never empty
-    int64_t chunks = 1, rows_per_chunk = kTermSpanRows;
+    int64_t chunks = 1, rows_per_chunk = kSpanRows;
 };
 
 // The plan rule: pure host arithmetic.  n_rows: the rows of the index (bitmap driven) or the entries of a query's id list (id-list driven).
 inline int term_sum_plan(int64_t n_rows, int32_t B, int32_t n_cols, bool per_query, int64_t rows_per_chunk, int32_t tile_cols, TermSumPlan* out,
                          char* msg, size_t cap) {
-    if (n_rows < 1 || n_rows > kTermMaxRows) return snprintf(msg, cap, "n_rows must be in 1..2^32 - 1 (got %lld)", (long long)n_rows), VS_EINVAL;
-    if (B < 1) return snprintf(msg, cap, "B must be positive (got %d)", B), VS_EINVAL;
-    if (n_cols < 1 || n_cols > kTermMaxCols) return snprintf(msg, cap, "n_cols must be in 1..%d (got %d)", kTermMaxCols, n_cols), VS_EINVAL;
-    if (!per_query && B > 1) return snprintf(msg, cap, "one set for all queries (ld_words = 0) takes B = 1, got B = %d", B), VS_EINVAL;
-    if (rows_per_chunk < 0 || rows_per_chunk % 64 != 0 || rows_per_chunk > kTermMaxRows)
-        return snprintf(msg, cap, "rows_per_chunk must be 0 (automatic) or a positive multiple of 64 below 2^32 (got %lld)", (long long)rows_per_chunk),
-               VS_EINVAL;
+    const int rc = check_term_set(n_rows, B, n_cols, per_query, rows_per_chunk, msg, cap);
+    if (rc != VS_OK) return rc;
     if (tile_cols < 0 || tile_cols > VS_TERM_SUM_TILE_COLS)
         return snprintf(msg, cap, "tile_cols must be 0 (automatic) or in 1..%d (got %d)", VS_TERM_SUM_TILE_COLS, tile_cols), VS_EINVAL;
     TermSumPlan p;
@@ -56,14 +52,8 @@ inline int term_sum_plan(int64_t n_rows, int32_t B, int32_t n_cols, bool per_que
         p.tiles = (n_cols + tile_cols - 1) / tile_cols;
     }
     const int64_t items = (int64_t)B * p.tiles;                                   // work items a chunk
-    if (rows_per_chunk == 0) {
-        // the rule of the term counts over B x tiles work items a chunk: a few workgroups per CU, a chunk at least one span
-        const int64_t want = std::max<int64_t>(1, kTermAutoItems / items);
-        rows_per_chunk = std::max<int64_t>((n_rows + want - 1) / want, kTermSpanRows);
-        rows_per_chunk = (rows_per_chunk + kTermSpanRows - 1) / kTermSpanRows * kTermSpanRows;
-    }
-    p.rows_per_chunk = rows_per_chunk;
-    p.chunks = (n_rows + rows_per_chunk - 1) / rows_per_chunk;
+    p.rows_per_chunk = rows_per_chunk ? rows_per_chunk : auto_chunk(n_rows, items);
+    p.chunks = (n_rows + p.rows_per_chunk - 1) / p.rows_per_chunk;
     if (p.chunks > 0x7FFFFFFF / items)                                            // (one work item a chunk, query and tile: a 1-D grid of 31 bits)
         return snprintf(msg, cap, "%lld chunks x %d queries x %d column tiles are too many for one call", (long long)p.chunks, B, p.tiles), VS_EINVAL;
     *out = p;
@@ -73,41 +63,25 @@ inline int term_sum_plan(int64_t n_rows, int32_t B, int32_t n_cols, bool per_que
 // vs_index_term_sums: the bitmap's geometry and the outputs (n_rows, n_cols: the index's)
 inline int term_sum_check_sums(bool have_words, int64_t bit0, int64_t ld_words, int32_t B, int64_t n_rows, int32_t n_cols, int64_t rows_per_chunk,
                                int32_t tile_cols, bool have_outputs, int64_t ld_sums, TermSumPlan* plan, char* msg, size_t cap) {
-    if (!have_outputs) return snprintf(msg, cap, "NULL argument"), VS_EINVAL;
-    if (bit0 < 0) return snprintf(msg, cap, "bit0 must be >= 0 (got %lld)", (long long)bit0), VS_EINVAL;
-    const bool per_query = have_words && ld_words != 0;
-    const int rc = term_sum_plan(n_rows, B, n_cols, per_query, rows_per_chunk, tile_cols, plan, msg, cap);
-    if (rc != VS_OK) return rc;
-    const int64_t span = (bit0 + n_rows + 31) >> 5;
-    if (have_words && (ld_words < 0 || (ld_words > 0 && ld_words < span)))
-        return snprintf(msg, cap, "ld_words = %lld is shorter than the %lld words a query's bitmap spans", (long long)ld_words, (long long)span), VS_EINVAL;
-    if (ld_sums < n_cols) return snprintf(msg, cap, "ld_sums = %lld is shorter than n_cols = %d", (long long)ld_sums, n_cols), VS_EINVAL;
-    return VS_OK;
+    return check_bitmap_call(have_words, bit0, ld_words, n_rows, n_cols, have_outputs, ld_sums, "sums",
+                             [&](bool per_query) { return term_sum_plan(n_rows, B, n_cols, per_query, rows_per_chunk, tile_cols, plan, msg, cap); },
+                             msg, cap);
 }
 
 // vs_index_term_sums_ids: the list's geometry and the outputs; the plan is taken over the m entries of a query
 inline int term_sum_check_ids(bool have_ids, int32_t B, int64_t m, int64_t ld, int32_t n_cols, int32_t tile_cols, bool have_outputs, int64_t ld_sums,
                               TermSumPlan* plan, char* msg, size_t cap) {
-    if (!have_ids || !have_outputs) return snprintf(msg, cap, "NULL argument"), VS_EINVAL;
-    if (m < 1 || m > kTermMaxRows) return snprintf(msg, cap, "m must be in 1..2^32 - 1 entries a query (got %lld)", (long long)m), VS_EINVAL;
-    if (ld < m) return snprintf(msg, cap, "ld = %lld is shorter than m = %lld", (long long)ld, (long long)m), VS_EINVAL;
-    const int rc = term_sum_plan(m, B, n_cols, true, 0, tile_cols, plan, msg, cap);
-    if (rc != VS_OK) return rc;
-    if (ld_sums < n_cols) return snprintf(msg, cap, "ld_sums = %lld is shorter than n_cols = %d", (long long)ld_sums, n_cols), VS_EINVAL;
-    return VS_OK;
+    return check_ids_call(have_ids, m, ld, n_cols, have_outputs, ld_sums, "sums",
+                          [&] { return term_sum_plan(m, B, n_cols, true, 0, tile_cols, plan, msg, cap); }, msg, cap);
 }
 
 // vs_term_sum_topn (counts may be absent: then ld_counts is not looked at)
 inline int term_sum_check_topn(bool have_pointers, bool have_counts, int32_t B, int32_t n_cols, int64_t ld_sums, int64_t ld_counts, int32_t n,
                                char* msg, size_t cap) {
-    if (!have_pointers) return snprintf(msg, cap, "NULL argument"), VS_EINVAL;
-    if (B < 1) return snprintf(msg, cap, "B must be positive (got %d)", B), VS_EINVAL;
-    if (n_cols < 1 || n_cols > kTermMaxCols) return snprintf(msg, cap, "n_cols must be in 1..%d (got %d)", kTermMaxCols, n_cols), VS_EINVAL;
-    if (n < 1 || n > VS_TERM_MAX_TOPN) return snprintf(msg, cap, "n must be in 1..%d (got %d)", VS_TERM_MAX_TOPN, n), VS_EINVAL;
-    if (ld_sums < n_cols) return snprintf(msg, cap, "ld_sums = %lld is shorter than n_cols = %d", (long long)ld_sums, n_cols), VS_EINVAL;
-    if (have_counts && ld_counts < n_cols)
-        return snprintf(msg, cap, "ld_counts = %lld is shorter than n_cols = %d", (long long)ld_counts, n_cols), VS_EINVAL;
-    return VS_OK;
+    int rc = check_term_topn(have_pointers, B, n_cols, n, msg, cap);
+    if (rc == VS_OK) rc = check_ld_out(ld_sums, n_cols, "sums", msg, cap);
+    if (rc == VS_OK && have_counts) rc = check_ld_out(ld_counts, n_cols, "counts", msg, cap);
+    return rc;
 }
 
 }  // namespace vs

@@ -4,12 +4,7 @@
 // Plain C++ with no HIP in it, so that a stand-alone program can run them under a host sanitizer (tests/test_value_cpu.py builds one).
 #pragma once
 
-#include <algorithm>
-#include <cstddef>
-#include <cstdint>
-#include <cstdio>
-
-#include "vsearch_hip.h"
+#include "set_check.h"
 
 namespace vs {
 
@@ -20,7 +15,8 @@ namespace vs {
 #endif
 
 constexpr int64_t kValueMaxRows = 0xFFFFFFFFll;       // a chunk's count fits a uint32 bin, a row fits the low half of a top-k key
-constexpr int kValueSpanRows = 2048;                  // rows a wave loads the bitmap words of at a time: 64 lanes x 32 bits
+constexpr int kValThreads = 256;                      // threads of the workgroups that walk a set of values (values.hip, quantiles.hip)
+constexpr int kValWaves = kValThreads / 64;
 constexpr int kValueAutoItems = 1024;                 // workgroups the automatic plan aims at (4 a CU)
 constexpr int64_t kValueMinChunk = 8192;              // rows of an automatic chunk at least
 constexpr int64_t kValueMaxScratchKeys = 1ll << 27;   // keys of vs_value_topk's per-chunk lists (1 GiB)
@@ -64,20 +60,19 @@ static_assert(VS_VALUE_MAX_EDGES <= 2047, "value_bin starts at a step of 1024");
 // ---- the plan rule: pure host arithmetic ----------------------------------------------------------------------------------------------------
 struct ValuePlan {
     int32_t qt = 1;                   // queries a workgroup serves
-    int64_t chunks = 1, rows_per_chunk = kValueSpanRows;
+    int64_t chunks = 1, rows_per_chunk = kSpanRows;
 };
 
 // qt_max: 8 for stats and histograms, 1 for the top-k (one query a workgroup)
 inline int value_plan(int64_t n_rows, int32_t B, int32_t n_bins, bool per_query, int64_t rows_per_chunk, int32_t qt_max, ValuePlan* out, char* msg,
                       size_t cap) {
-    if (n_rows < 1 || n_rows > kValueMaxRows) return snprintf(msg, cap, "n_rows must be in 1..2^32 - 1 (got %lld)", (long long)n_rows), VS_EINVAL;
-    if (B < 1) return snprintf(msg, cap, "B must be positive (got %d)", B), VS_EINVAL;
+    int rc = check_n_rows(n_rows, msg, cap);
+    if (rc == VS_OK) rc = check_batch(B, msg, cap);
+    if (rc != VS_OK) return rc;
     if (n_bins < 0 || n_bins > VS_VALUE_MAX_EDGES + 2)
         return snprintf(msg, cap, "n_bins must be in 0..%d (got %d)", VS_VALUE_MAX_EDGES + 2, n_bins), VS_EINVAL;
-    if (!per_query && B > 1) return snprintf(msg, cap, "one bitmap for all queries (ld_words = 0) takes B = 1, got B = %d", B), VS_EINVAL;
-    if (rows_per_chunk < 0 || rows_per_chunk % 64 != 0 || rows_per_chunk > kValueMaxRows)
-        return snprintf(msg, cap, "rows_per_chunk must be 0 (automatic) or a positive multiple of 64 below 2^32 (got %lld)", (long long)rows_per_chunk),
-               VS_EINVAL;
+    rc = check_chunking(per_query, B, rows_per_chunk, "bitmap", msg, cap);
+    if (rc != VS_OK) return rc;
     ValuePlan p;
     p.qt = per_query ? qt_max : 1;
     const int64_t tiles = (B + p.qt - 1) / p.qt;
@@ -86,7 +81,7 @@ inline int value_plan(int64_t n_rows, int32_t B, int32_t n_bins, bool per_query,
         const int64_t want = std::max<int64_t>(1, kValueAutoItems / tiles);
         const int64_t floor_rows = std::max<int64_t>(kValueMinChunk, (int64_t)16 * n_bins);
         rows_per_chunk = std::max<int64_t>((n_rows + want - 1) / want, floor_rows);
-        rows_per_chunk = (rows_per_chunk + kValueSpanRows - 1) / kValueSpanRows * kValueSpanRows;
+        rows_per_chunk = (rows_per_chunk + kSpanRows - 1) / kSpanRows * kSpanRows;
     }
     p.rows_per_chunk = rows_per_chunk;
     p.chunks = (n_rows + rows_per_chunk - 1) / rows_per_chunk;
@@ -108,14 +103,10 @@ inline int value_check_set(bool have_pointers, bool have_words, int64_t bit0, in
     if (!have_pointers) return snprintf(msg, cap, "NULL argument"), VS_EINVAL;
     int rc = value_check_dtype(dtype, msg, cap);
     if (rc != VS_OK) return rc;
-    if (bit0 < 0) return snprintf(msg, cap, "bit0 must be >= 0 (got %lld)", (long long)bit0), VS_EINVAL;
-    const bool per_query = have_words && ld_words != 0;
-    rc = value_plan(n_rows, B, n_bins, per_query, rows_per_chunk, qt_max, plan, msg, cap);
-    if (rc != VS_OK) return rc;
-    const int64_t span = (bit0 + n_rows + 31) >> 5;
-    if (have_words && (ld_words < 0 || (ld_words > 0 && ld_words < span)))
-        return snprintf(msg, cap, "ld_words = %lld is shorter than the %lld words a query's bitmap spans", (long long)ld_words, (long long)span), VS_EINVAL;
-    return VS_OK;
+    rc = check_bit0(bit0, msg, cap);
+    if (rc == VS_OK) rc = value_plan(n_rows, B, n_bins, have_words && ld_words != 0, rows_per_chunk, qt_max, plan, msg, cap);
+    if (rc == VS_OK) rc = check_ld_words(have_words, bit0, ld_words, n_rows, msg, cap);
+    return rc;
 }
 
 // vs_value_histogram: the edge count and the stride of counts

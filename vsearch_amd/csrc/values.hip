@@ -6,31 +6,26 @@
 //
 // (a) Range bitmaps: a wave owns 64 bits of every bitmap.  It loads its rows' keys once and, per range, forms the two words with one ballot;
 //     lane b of a batch of 64 ranges keeps the ballot of range b and stores it: plain stores, every word written exactly once.
-// (b) Stats / histogram: a workgroup owns a chunk of rows and a tile of QT queries and walks the bitmaps as facets.hip does (2048-row spans,
-//     all-zero spans left at once, a row's value loaded once for the tile).
+// (b) Stats / histogram: a workgroup owns a chunk of rows and a tile of QT queries and walks the bitmaps with walk_tile (set_walk.h: 2048-row
+//     spans, all-zero spans left at once); a row's value is loaded once for the tile.
 //       histogram: the edge keys in LDS, bin = value_bin (branch-free, 11 steps), one uint32 histogram of n_edges + 2 slots per query in LDS
 //                  (slot 0 below, 1 .. n_edges - 1 the bins, n_edges above, n_edges + 1 missing), flushed with 64-bit atomicAdd.
 //       stats:     min key, max key and sum per lane and query; wave reduction by shuffles, workgroup reduction by LDS atomics, one global
 //                  atomic per (workgroup, query) and output.  The min / max outputs hold KEYS until value_finish_kernel turns them into values.
-// (c) Top-k: a workgroup owns a chunk and one query.  All four waves walk the same span, each a quarter of its 64-row steps, and push
-//     (key or ~key) << 32 | ~row above the threshold into a 4096-key LDS buffer; after a span with more than 2048 keys in, the buffer is
-//     sorted (wg_sort_desc), cut to k, and the k-th key becomes the threshold.  Per-chunk lists go to scratch; value_topk_merge_kernel, one
-//     workgroup per query, streams them through the same buffer and writes ids and the rows' stored values.
-#include "common.h"
-#include "bitmap_span.h"
-#include "staging.h"
+// (c) Top-k: a workgroup owns a chunk and one query.  All four waves walk the same span (walk_rows), each a quarter of its 64-row steps, and
+//     push (key or ~key) << 32 | ~row above the threshold into the buffer of topn_stream.h; after a span with more than 2048 keys in, the
+//     buffer is sorted, cut to k, and the k-th key becomes the threshold.  Per-chunk lists go to scratch; value_topk_merge_kernel, one
+//     workgroup per query, streams them through the same buffer (stream_topn) and writes ids and the rows' stored values.
+#include "agg_call.h"
 #include "term_sum_check.h"
-#include "topk_keys.h"
+#include "topn_stream.h"
 #include "value_check.h"
-#include "value_set.h"
 
 using namespace vs;
 
 namespace {
 
-constexpr int kTopCap = 4096;                         // keys of the top-k candidate buffer
-constexpr int kTopKeep = 2048;                        // sorted and cut when more are in
-static_assert(kValueSpanRows == 2048 && kTopCap - kTopKeep >= kValueSpanRows, "a span adds up to 2048 candidates");
+static_assert(kTopCap - kTopKeep >= kSpanRows, "a span adds up to kSpanRows candidates");
 
 // ---- (a) range bitmaps -----------------------------------------------------------------------------------------------------------------------
 struct RangeArgs {
@@ -101,9 +96,9 @@ __global__ __launch_bounds__(kValThreads) void value_stats_kernel(StatsArgs a) {
     __shared__ unsigned long long s_sum[QT];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int q0 = (int)blockIdx.y * QT;
-    const int nq = min(QT, a.s.B - q0);
-    const int64_t r0 = (int64_t)blockIdx.x * a.s.rows_per_chunk;
-    const int64_t r1 = min(a.s.n_rows, r0 + a.s.rows_per_chunk);
+    const int nq = min(QT, a.s.set.B - q0);
+    const int64_t r0 = (int64_t)blockIdx.x * a.s.set.rows_per_chunk;
+    const int64_t r1 = min(a.s.set.n_rows, r0 + a.s.set.rows_per_chunk);
     if (tid < QT) {
         s_cnt[tid] = s_mis[tid] = 0u;
         s_min[tid] = 0xFFFFFFFFu;
@@ -122,7 +117,9 @@ __global__ __launch_bounds__(kValThreads) void value_stats_kernel(StatsArgs a) {
         sum[q] = 0ull;
     }
     const bool f32 = a.s.dtype == VS_VAL_F32;
-    walk_set<QT>(a.s, q0, nq, r0, r1, w, lane, [&](int64_t, uint32_t raw, uint32_t key, const Span* sp, int s, int sh, uint64_t live) {
+    walk_tile<QT, kValWaves>(a.s.set, q0, nq, r0, r1, w, lane, [&](int64_t row0, uint64_t many, const Span* sp, int s, int sh, uint64_t live) {
+        const uint32_t raw = (many >> lane) & 1ull ? a.s.values[row0 + lane] : 0u;   // once for the tile
+        const uint32_t key = (many >> lane) & 1ull ? value_key(raw, a.s.dtype) : 0u;
         // what the row adds to a sum: fx(v) of the term sums for fp32, the integer itself for int32; nothing without a value
         uint64_t add = 0ull;
         if (key != 0u) add = f32 ? term_fx(__uint_as_float(raw)) : (uint64_t)(int64_t)(int32_t)raw;
@@ -189,9 +186,9 @@ __global__ __launch_bounds__(kValThreads) void value_hist_kernel(HistArgs a) {
     extern __shared__ uint32_t val_lds[];                        // edge keys [n_edges], then the histograms [nq][n_edges + 2]
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int q0 = (int)blockIdx.y * QT;
-    const int nq = min(QT, a.s.B - q0);
-    const int64_t r0 = (int64_t)blockIdx.x * a.s.rows_per_chunk;
-    const int64_t r1 = min(a.s.n_rows, r0 + a.s.rows_per_chunk);
+    const int nq = min(QT, a.s.set.B - q0);
+    const int64_t r0 = (int64_t)blockIdx.x * a.s.set.rows_per_chunk;
+    const int64_t r1 = min(a.s.set.n_rows, r0 + a.s.set.rows_per_chunk);
     const int E = a.n_edges;
     const uint32_t S = (uint32_t)E + 2u;                         // slots of a query
     uint32_t* ekeys = val_lds;
@@ -199,7 +196,8 @@ __global__ __launch_bounds__(kValThreads) void value_hist_kernel(HistArgs a) {
     for (int i = tid; i < E; i += kValThreads) ekeys[i] = value_key(a.edges[i], a.s.dtype);
     for (uint32_t i = tid; i < (uint32_t)nq * S; i += kValThreads) hist[i] = 0u;
     __syncthreads();
-    walk_set<QT>(a.s, q0, nq, r0, r1, w, lane, [&](int64_t, uint32_t, uint32_t key, const Span* sp, int s, int sh, uint64_t live) {
+    walk_tile<QT, kValWaves>(a.s.set, q0, nq, r0, r1, w, lane, [&](int64_t row0, uint64_t many, const Span* sp, int s, int sh, uint64_t live) {
+        const uint32_t key = (many >> lane) & 1ull ? value_key(a.s.values[row0 + lane], a.s.dtype) : 0u;
         const uint32_t slot = key == 0u ? (uint32_t)E + 1u : (uint32_t)value_bin(ekeys, E, key);      // once for the tile
 #pragma unroll
         for (int q = 0; q < QT; ++q) {
@@ -243,35 +241,6 @@ struct TopArgs {
     uint32_t* out_values;             // [B, k] raw
 };
 
-// push the lanes' keys that pass into the buffer (cnt_sh: its fill); the caller guarantees the room
-__device__ __forceinline__ void top_push(uint64_t* cand, int* cnt_sh, bool pass, uint64_t key, int lane) {
-    const unsigned long long m = __builtin_amdgcn_ballot_w64(pass);
-    if (m == 0ull) return;
-    int base = 0;
-    if (lane == 0) base = atomicAdd(cnt_sh, __popcll(m));
-    base = __shfl(base, 0, 64);
-    if (pass) cand[base + __popcll(m & ((1ull << lane) - 1ull))] = key;
-}
-
-// after a barrier: sort the buffer when it is more than half full (or at the end) and cut it to K -> the new threshold.  Only the power of two
-// that holds the keys (and the K slots the caller reads) is sorted: a sparse set's last sort is a few hundred keys, not 4096.
-__device__ __forceinline__ uint64_t top_cut(uint64_t* cand, int* cnt_sh, int K, bool last, uint64_t tau, int tid) {
-    const int cnt = *cnt_sh;                                     // (uniform: read after the caller's barrier)
-    if (last || cnt > kTopKeep) {
-        int n = 2;
-        while (n < cnt || n < K) n <<= 1;                        // <= kTopCap: cnt <= kTopCap, K <= 1024
-        for (int i = cnt + tid; i < n; i += kValThreads) cand[i] = 0ull;
-        wg_sort_desc<kValThreads>(cand, n, tid);
-        if (!last && cnt > K) {
-            tau = cand[K - 1];
-            __syncthreads();
-            if (tid == 0) *cnt_sh = K;
-        }
-    }
-    __syncthreads();
-    return tau;
-}
-
 __global__ __launch_bounds__(kValThreads) void value_topk_chunk_kernel(TopArgs a) {
     __shared__ uint64_t cand[kTopCap];
     __shared__ int cnt_sh;
@@ -279,48 +248,24 @@ __global__ __launch_bounds__(kValThreads) void value_topk_chunk_kernel(TopArgs a
     const int64_t c = blockIdx.x;
     const size_t b = blockIdx.y;
     const int K = a.k;
-    const int64_t r0 = c * a.s.rows_per_chunk;
-    const int64_t r1 = min(a.s.n_rows, r0 + a.s.rows_per_chunk);
-    const int64_t n_w = (a.s.bit0 + a.s.n_rows + 31) >> 5, n_aw = (a.s.and_bit0 + a.s.n_rows + 31) >> 5;
-    const uint32_t* words = a.s.words ? a.s.words + b * (size_t)a.s.ld_words : nullptr;
+    const int64_t r0 = c * a.s.set.rows_per_chunk;
+    const int64_t r1 = min(a.s.set.n_rows, r0 + a.s.set.rows_per_chunk);
     if (tid == 0) cnt_sh = 0;
     __syncthreads();
     uint64_t tau = 0ull;
-    // every wave loads the words of the same span (so that the decisions below are uniform over the workgroup) and takes a quarter of its steps
-    for (int64_t rb = r0; rb < r1; rb += kValueSpanRows) {
-        const int nsub = (int)((min(r1, rb + kValueSpanRows) - rb + 63) >> 6);
-        Span an{~0u, ~0u}, sp{~0u, ~0u};
-        int sha = 0, sh = 0;
-        if (a.s.and_words) {
-            const int64_t p = a.s.and_bit0 + rb;
-            an = load_span(a.s.and_words, p >> 5, n_aw, lane);
-            sha = (int)(p & 31);
-            if (__builtin_amdgcn_ballot_w64((an.lo | an.hi) != 0u) == 0ull) continue;
+    walk_rows<kValWaves>(a.s.set, b, r0, r1, w, lane, [&](int64_t row0, uint64_t m, int64_t) {
+        uint64_t key = 0ull;
+        if ((m >> lane) & 1ull) {
+            const uint32_t k32 = value_key(a.s.values[row0 + lane], a.s.dtype);
+            if (k32 != 0u) key = ((uint64_t)(k32 ^ a.flip) << 32) | (uint32_t)~(uint32_t)(row0 + lane);      // never 0: row < 2^32 - 1
         }
-        if (words) {
-            const int64_t p = a.s.bit0 + rb;
-            sp = load_span(words, p >> 5, n_w, lane);
-            sh = (int)(p & 31);
-            if (__builtin_amdgcn_ballot_w64((sp.lo | sp.hi) != 0u) == 0ull) continue;
-        }
-        for (int s = w; s < nsub; s += kValWaves) {
-            const int64_t row0 = rb + (int64_t)s * 64;
-            const int64_t nvalid = r1 - row0;
-            const uint64_t vm = nvalid >= 64 ? ~0ull : ((1ull << nvalid) - 1ull);
-            const uint64_t m = window64(sp, s, sh) & window64(an, s, sha) & vm;
-            if (m == 0ull) continue;
-            uint64_t key = 0ull;
-            if ((m >> lane) & 1ull) {
-                const uint32_t k32 = value_key(a.s.values[row0 + lane], a.s.dtype);
-                if (k32 != 0u) key = ((uint64_t)(k32 ^ a.flip) << 32) | (uint32_t)~(uint32_t)(row0 + lane);      // never 0: row < 2^32 - 1
-            }
-            top_push(cand, &cnt_sh, key > tau, key, lane);
-        }
+        top_push(cand, &cnt_sh, key > tau, key, lane);
+    }, [&] {                                                     // (the walk leaves a span for the whole workgroup or not at all)
         __syncthreads();
-        tau = top_cut(cand, &cnt_sh, K, false, tau, tid);
-    }
+        tau = top_cut<kValThreads>(cand, &cnt_sh, K, false, tau, tid);
+    });
     __syncthreads();
-    (void)top_cut(cand, &cnt_sh, K, true, tau, tid);
+    (void)top_cut<kValThreads>(cand, &cnt_sh, K, true, tau, tid);
     uint64_t* dst = a.scratch + (b * (size_t)a.chunks + (size_t)c) * (size_t)K;
     for (int i = tid; i < K; i += kValThreads) dst[i] = cand[i];                     // sorted, zeros behind the last
 }
@@ -328,26 +273,11 @@ __global__ __launch_bounds__(kValThreads) void value_topk_chunk_kernel(TopArgs a
 __global__ __launch_bounds__(kValThreads) void value_topk_merge_kernel(TopArgs a) {
     __shared__ uint64_t cand[kTopCap];
     __shared__ int cnt_sh;
-    const int tid = threadIdx.x, lane = tid & 63;
-    constexpr int SB = (kTopCap - kTopKeep) / kValThreads;       // steps between cuts
+    const int tid = threadIdx.x;
     const int K = a.k;
     const size_t b = blockIdx.x;
     const uint64_t* src = a.scratch + b * (size_t)a.chunks * (size_t)K;
-    const int64_t n = a.chunks * K;
-    if (tid == 0) cnt_sh = 0;
-    __syncthreads();
-    uint64_t tau = 0ull;
-    const int64_t iters = (n + kValThreads - 1) / kValThreads;
-    for (int64_t it0 = 0; it0 < iters; it0 += SB) {
-        const int64_t it1 = min(iters, it0 + SB);
-        for (int64_t it = it0; it < it1; ++it) {
-            const int64_t i = it * kValThreads + tid;
-            const uint64_t key = i < n ? src[i] : 0ull;
-            top_push(cand, &cnt_sh, key > tau, key, lane);
-        }
-        __syncthreads();
-        tau = top_cut(cand, &cnt_sh, K, it1 >= iters, tau, tid);
-    }
+    stream_topn<kValThreads>(a.chunks * K, K, [&](int64_t i) { return src[i]; }, cand, &cnt_sh);
     const uint32_t miss = a.s.dtype == VS_VAL_F32 ? kValueNanF32 : kValueMissI32;
     for (int i = tid; i < K; i += kValThreads) {                  // every slot is written: id -1 / the missing sentinel behind the last
         const uint64_t key = cand[i];
@@ -371,7 +301,7 @@ int stats_call(int device, const uint32_t* words, int64_t bit0, int64_t ld_words
     hipStream_t s = (hipStream_t)stream;
     SetStage st;
     StatsArgs a{};
-    VS_TRY(st.in(words, bit0, ld_words, and_user, and_dev, B, values, dtype, n_rows, plan, dev, s, &a.s));
+    VS_TRY(st.in(words, bit0, ld_words, and_user, and_dev, B, values, dtype, n_rows, plan.rows_per_chunk, dev, s, &a.s));
     DevBuf out;                                                   // host outputs: count, missing, sum [B] x 8 bytes, then min, max [B] x 4
     if (dev) {
         a.count = reinterpret_cast<unsigned long long*>(count);
@@ -427,34 +357,18 @@ int hist_call(int device, const uint32_t* words, int64_t bit0, int64_t ld_words,
     SetStage st;
     Staged st_e;
     HistArgs a{};
-    VS_TRY(st.in(words, bit0, ld_words, and_user, and_dev, B, values, dtype, n_rows, plan, dev, s, &a.s));
+    VS_TRY(st.in(words, bit0, ld_words, and_user, and_dev, B, values, dtype, n_rows, plan.rows_per_chunk, dev, s, &a.s));
     uint32_t* d_e;
     VS_TRY(st_e.in(static_cast<const uint32_t*>(edges), (size_t)n_edges, dev, true, s, &d_e));
     a.edges = d_e;
     a.n_edges = n_edges;
-    const int32_t n_bins = n_edges - 1;
-    const size_t n_cnt = (size_t)B * (size_t)n_bins;
-    DevBuf out;
-    if (dev) {
-        a.counts = reinterpret_cast<unsigned long long*>(counts);
-        a.ld_counts = ld_counts;
-        a.below = reinterpret_cast<unsigned long long*>(below);
-        a.above = reinterpret_cast<unsigned long long*>(above);
-        a.missing = reinterpret_cast<unsigned long long*>(missing);
-        if (ld_counts == n_bins || B == 1) VS_HIP(hipMemsetAsync(a.counts, 0, n_cnt * 8, s));
-        else VS_HIP(hipMemset2DAsync(a.counts, (size_t)ld_counts * 8, 0, (size_t)n_bins * 8, (size_t)B, s));
-        VS_HIP(hipMemsetAsync(a.below, 0, (size_t)B * 8, s));
-        VS_HIP(hipMemsetAsync(a.above, 0, (size_t)B * 8, s));
-        VS_HIP(hipMemsetAsync(a.missing, 0, (size_t)B * 8, s));
-    } else {
-        VS_TRY(out.alloc((n_cnt + 3 * (size_t)B) * 8));
-        a.counts = out.as<unsigned long long>();
-        a.ld_counts = n_bins;
-        a.below = a.counts + n_cnt;
-        a.above = a.below + B;
-        a.missing = a.above + B;
-        VS_HIP(hipMemsetAsync(out.p, 0, out.bytes, s));
-    }
+    CountsOut out;
+    VS_TRY(out.bind(dev, counts, ld_counts, n_edges - 1, B, {below, above, missing}, s));
+    a.counts = out.mat;
+    a.ld_counts = out.ld;
+    a.below = out.vec[0];
+    a.above = out.vec[1];
+    a.missing = out.vec[2];
     {
         ProfScope prof("value_histogram", s);
         const dim3 grid((unsigned)plan.chunks, (unsigned)ceil_div64(B, plan.qt));
@@ -468,12 +382,7 @@ int hist_call(int device, const uint32_t* words, int64_t bit0, int64_t ld_words,
         return fail(VS_EHIP, "value_histogram launch failed: %s", hipGetErrorString(le));
     }
     VS_STAGE("value_histogram", s);
-    if (!dev) {
-        VS_HIP(hipMemcpy2DAsync(counts, (size_t)ld_counts * 8, a.counts, (size_t)n_bins * 8, (size_t)n_bins * 8, (size_t)B, hipMemcpyDeviceToHost, s));
-        VS_HIP(hipMemcpyAsync(below, a.below, (size_t)B * 8, hipMemcpyDeviceToHost, s));
-        VS_HIP(hipMemcpyAsync(above, a.above, (size_t)B * 8, hipMemcpyDeviceToHost, s));
-        VS_HIP(hipMemcpyAsync(missing, a.missing, (size_t)B * 8, hipMemcpyDeviceToHost, s));
-    }
+    if (!dev) VS_TRY(out.back(s));
     return finish_call(dev, stream, s);
 }
 
@@ -490,7 +399,7 @@ int topk_call(int device, const uint32_t* words, int64_t bit0, int64_t ld_words,
     Staged st_i, st_v;
     DevBuf scratch;
     TopArgs a{};
-    VS_TRY(st.in(words, bit0, ld_words, and_user, and_dev, B, values, dtype, n_rows, plan, dev, s, &a.s));
+    VS_TRY(st.in(words, bit0, ld_words, and_user, and_dev, B, values, dtype, n_rows, plan.rows_per_chunk, dev, s, &a.s));
     VS_TRY(st_i.in(out_ids, (size_t)B * k, dev, false, s, &a.out_ids));
     VS_TRY(st_v.in(static_cast<uint32_t*>(out_values), (size_t)B * k, dev, false, s, &a.out_values));
     VS_TRY(scratch.alloc((size_t)B * (size_t)plan.chunks * (size_t)k * 8));

@@ -1008,13 +1008,30 @@ def term_sum_plan(n_rows: int, B: int, n_cols: int, per_query: bool, rows_per_ch
     return tiles.value, tc.value, chunks.value, rpc.value
 
 
-def _term_sum_args(rows_per_chunk, tile_cols):
-    """Argument checks of a term sum's tuning knobs that need no device -> (rows_per_chunk, tile_cols)"""
+def _rows_per_chunk_arg(rows_per_chunk) -> int:
+    """The tuning knob of the chunked walks: 0 (automatic) or a positive multiple of 64"""
     if isinstance(rows_per_chunk, bool) or not isinstance(rows_per_chunk, (int, np.integer)) or rows_per_chunk < 0 or rows_per_chunk % 64:
         raise ValueError(f"rows_per_chunk must be 0 (automatic) or a positive multiple of 64, got {rows_per_chunk!r}")
+    return int(rows_per_chunk)
+
+
+class _TermAgg(NamedTuple):
+    """A term aggregation over a document set: its two entry points (bitmap driven, id-list driven) and its result tuple"""
+    bitmap: str
+    ids: str
+    result: Any
+
+
+_TERM_COUNTS = _TermAgg("vs_index_term_counts", "vs_index_term_counts_ids", TermCounts)
+_TERM_SUMS = _TermAgg("vs_index_term_sums", "vs_index_term_sums_ids", TermSums)
+
+
+def _term_sum_args(rows_per_chunk, tile_cols):
+    """Argument checks of a term sum's tuning knobs that need no device -> (rows_per_chunk, tile_cols)"""
+    rows_per_chunk = _rows_per_chunk_arg(rows_per_chunk)
     if isinstance(tile_cols, bool) or not isinstance(tile_cols, (int, np.integer)) or not 0 <= tile_cols <= MAX_TERM_TILE_COLS:
         raise ValueError(f"tile_cols must be 0 (automatic) or in 1..{MAX_TERM_TILE_COLS}, got {tile_cols!r}")
-    return int(rows_per_chunk), int(tile_cols)
+    return rows_per_chunk, int(tile_cols)
 
 
 def _weight_topn_args(topn, min_count):
@@ -1094,8 +1111,7 @@ def _assign_args(centroids, bias, n_cols, rows_per_chunk=0):
     """Argument checks of an assignment that need no device -> (centroids float32 [K, V] tensor, bias float32 [K] tensor | None,
     rows_per_chunk).  A tensor on a GPU is not read here: the finiteness of device centroids is the caller's."""
     import torch
-    if isinstance(rows_per_chunk, bool) or not isinstance(rows_per_chunk, (int, np.integer)) or rows_per_chunk < 0 or rows_per_chunk % 64:
-        raise ValueError(f"rows_per_chunk must be 0 (automatic) or a positive multiple of 64, got {rows_per_chunk!r}")
+    rows_per_chunk = _rows_per_chunk_arg(rows_per_chunk)
     c = centroids if _is_torch(centroids) else torch.from_numpy(np.ascontiguousarray(np.asarray(centroids)))
     c = c.detach()
     if c.dim() != 2:
@@ -2458,27 +2474,63 @@ class DeviceIndex:
         return ValueQuantiles(*_facet_out(values, *_quantile_batches(qa, ra, B, call)))
 
     # ---- term aggregations: what a document set is about (vs_index_term_counts, vs_index_term_counts_ids) ---------------------------------
-    def _term_counts_call(self, f, bit0, rows_per_chunk):
-        """One vs_index_term_counts call on device buffers and torch's current stream -> (counts [B, V], total [B]) int64 CUDA tensors.
-        f: None or a DocFilter on this index's device, read from bit `bit0` on."""
+    def _term_set_call(self, spec, f, bit0, rows_per_chunk, extra=()):
+        """One bitmap-driven call of a term aggregation (spec.bitmap) on device buffers and torch's current stream -> ([B, V], total [B]) int64
+        CUDA tensors.  f: None or a DocFilter on this index's device, read from bit `bit0` on; extra: the arguments behind rows_per_chunk."""
         import torch
         dev = torch.device("cuda", self.device)
         B, V = (f.n_queries if (f is not None and f.per_query) else 1), self._n_cols()
-        counts = torch.empty((B, V), dtype=torch.int64, device=dev)
+        out = torch.empty((B, V), dtype=torch.int64, device=dev)
         total = torch.empty(B, dtype=torch.int64, device=dev)
-        nat.check(nat.lib().vs_index_term_counts(self._h, _ptr(f.words) if f is not None else None, int(bit0), f.ld if f is not None else 0, B,
-                                                 int(rows_per_chunk), _ptr(counts), V, _ptr(total), current_stream(self.device)))
-        return counts, total
+        nat.check(getattr(nat.lib(), spec.bitmap)(self._h, _ptr(f.words) if f is not None else None, int(bit0), f.ld if f is not None else 0, B,
+                                                  int(rows_per_chunk), *extra, _ptr(out), V, _ptr(total), current_stream(self.device)))
+        return out, total
 
-    def _term_counts_ids_call(self, ids_dev, id_offset, strict):
-        """One vs_index_term_counts_ids call: ids_dev int64 CUDA tensor [B, m] on this index's device"""
+    def _term_ids_call(self, spec, ids_dev, id_offset, strict, extra=()):
+        """One id-list-driven call of a term aggregation (spec.ids): ids_dev int64 CUDA tensor [B, m] on this index's device"""
         import torch
         B, m, V = int(ids_dev.shape[0]), int(ids_dev.shape[1]), self._n_cols()
-        counts = torch.empty((B, V), dtype=torch.int64, device=ids_dev.device)
+        out = torch.empty((B, V), dtype=torch.int64, device=ids_dev.device)
         total = torch.empty(B, dtype=torch.int64, device=ids_dev.device)
-        nat.check(nat.lib().vs_index_term_counts_ids(self._h, _ptr(ids_dev), B, m, int(ids_dev.stride(0)), int(id_offset), 1 if strict else 0,
-                                                     _ptr(counts), V, _ptr(total), current_stream(self.device)))
-        return counts, total
+        nat.check(getattr(nat.lib(), spec.ids)(self._h, _ptr(ids_dev), B, m, int(ids_dev.stride(0)), int(id_offset), 1 if strict else 0, *extra,
+                                               _ptr(out), V, _ptr(total), current_stream(self.device)))
+        return out, total
+
+    def _term_counts_call(self, f, bit0, rows_per_chunk):
+        return self._term_set_call(_TERM_COUNTS, f, bit0, rows_per_chunk)
+
+    def _term_counts_ids_call(self, ids_dev, id_offset, strict):
+        return self._term_ids_call(_TERM_COUNTS, ids_dev, id_offset, strict)
+
+    def _term_sums_call(self, f, bit0, rows_per_chunk, tile_cols):
+        return self._term_set_call(_TERM_SUMS, f, bit0, rows_per_chunk, (int(tile_cols),))
+
+    def _term_sums_ids_call(self, ids_dev, id_offset, strict, tile_cols):
+        return self._term_ids_call(_TERM_SUMS, ids_dev, id_offset, strict, (int(tile_cols),))
+
+    def _term_agg(self, spec, filter, ids, rows_per_chunk, extra=()):
+        """term_counts / term_sums: the set from `filter`, from `ids` (a host list is checked by the library before it is staged) or every live
+        document -> spec.result on the index's device.  extra: the arguments behind rows_per_chunk (term sums: tile_cols)."""
+        import torch
+        if ids is not None:
+            ids = _term_ids(ids)
+            nat.require_device()
+            dev = torch.device("cuda", self.device)
+            if _is_torch(ids) and ids.is_cuda:
+                t = ids.to(dev)
+                rows_ok = t.stride(1) == 1 and t.stride(0) >= t.shape[1]       # (a column slice of a wider hit list is read in place)
+                return spec.result(*self._term_ids_call(spec, t if rows_ok else t.contiguous(), 0, True, extra))
+            h = np.ascontiguousarray(_host(ids))
+            B, m, V = h.shape[0], h.shape[1], self._n_cols()
+            out, total = np.empty((B, V), dtype=np.int64), np.empty(B, dtype=np.int64)
+            nat.check(getattr(nat.lib(), spec.ids)(self._h, _ptr(h), B, m, m, 0, 1, *extra, _ptr(out), V, _ptr(total), None))
+            return spec.result(torch.from_numpy(out).to(dev), torch.from_numpy(total).to(dev))
+        nat.require_device()
+        f = None
+        if filter is not None:
+            from .doc_filter import as_doc_filter
+            f = as_doc_filter(filter, self.n_rows, device=self.device)
+        return spec.result(*self._term_set_call(spec, f, 0, rows_per_chunk, extra))
 
     def term_counts(self, filter=None, ids=None, rows_per_chunk: int = 0) -> TermCounts:
         """For a document set, how many of its documents have each vocabulary column -> TermCounts(counts [B, V], total [B]), int64 tensors
@@ -2488,30 +2540,9 @@ class DeviceIndex:
         twice counts twice, an id outside the index raises ValueError when the list is on the host and is skipped when it is on the
         device); neither: every live document (the document frequency of all columns in one pass).  Deleted documents never count.
         rows_per_chunk: 0 = automatic, else a multiple of 64 (a tuning knob: the result does not depend on it)."""
-        import torch
         if filter is not None and ids is not None:
             raise ValueError("the set is given by `filter` or by `ids`, not both")
-        if isinstance(rows_per_chunk, bool) or not isinstance(rows_per_chunk, (int, np.integer)) or rows_per_chunk < 0 or rows_per_chunk % 64:
-            raise ValueError(f"rows_per_chunk must be 0 (automatic) or a positive multiple of 64, got {rows_per_chunk!r}")
-        if ids is not None:
-            ids = _term_ids(ids)
-            nat.require_device()
-            dev = torch.device("cuda", self.device)
-            if _is_torch(ids) and ids.is_cuda:
-                t = ids.to(dev)
-                rows_ok = t.stride(1) == 1 and t.stride(0) >= t.shape[1]       # (a column slice of a wider hit list is read in place)
-                return TermCounts(*self._term_counts_ids_call(t if rows_ok else t.contiguous(), 0, True))
-            h = np.ascontiguousarray(_host(ids))                        # a host list: checked by the library before it is staged
-            B, m, V = h.shape[0], h.shape[1], self._n_cols()
-            counts, total = np.empty((B, V), dtype=np.int64), np.empty(B, dtype=np.int64)
-            nat.check(nat.lib().vs_index_term_counts_ids(self._h, _ptr(h), B, m, m, 0, 1, _ptr(counts), V, _ptr(total), None))
-            return TermCounts(torch.from_numpy(counts).to(dev), torch.from_numpy(total).to(dev))
-        nat.require_device()
-        f = None
-        if filter is not None:
-            from .doc_filter import as_doc_filter
-            f = as_doc_filter(filter, self.n_rows, device=self.device)
-        return TermCounts(*self._term_counts_call(f, 0, int(rows_per_chunk)))
+        return self._term_agg(_TERM_COUNTS, filter, ids, _rows_per_chunk_arg(rows_per_chunk))
 
     def top_terms(self, filter=None, ids=None, topn: int = 20, method: str = "jlh", min_count: int = 1, background=None) -> TopTerms:
         """term_counts of the set, then per query its `topn` most significant columns against a background (vs_term_topn; see
@@ -2521,28 +2552,6 @@ class DeviceIndex:
         return _top_terms(self, filter, ids, topn, method, min_count, background)
 
     # ---- term sums: the weight a document set puts on each column (vs_index_term_sums, vs_index_term_sums_ids) ----------------------------------
-    def _term_sums_call(self, f, bit0, rows_per_chunk, tile_cols):
-        """One vs_index_term_sums call on device buffers and torch's current stream -> (sums [B, V], total [B]) int64 CUDA tensors.
-        f: None or a DocFilter on this index's device, read from bit `bit0` on."""
-        import torch
-        dev = torch.device("cuda", self.device)
-        B, V = (f.n_queries if (f is not None and f.per_query) else 1), self._n_cols()
-        sums = torch.empty((B, V), dtype=torch.int64, device=dev)
-        total = torch.empty(B, dtype=torch.int64, device=dev)
-        nat.check(nat.lib().vs_index_term_sums(self._h, _ptr(f.words) if f is not None else None, int(bit0), f.ld if f is not None else 0, B,
-                                               int(rows_per_chunk), int(tile_cols), _ptr(sums), V, _ptr(total), current_stream(self.device)))
-        return sums, total
-
-    def _term_sums_ids_call(self, ids_dev, id_offset, strict, tile_cols):
-        """One vs_index_term_sums_ids call: ids_dev int64 CUDA tensor [B, m] on this index's device"""
-        import torch
-        B, m, V = int(ids_dev.shape[0]), int(ids_dev.shape[1]), self._n_cols()
-        sums = torch.empty((B, V), dtype=torch.int64, device=ids_dev.device)
-        total = torch.empty(B, dtype=torch.int64, device=ids_dev.device)
-        nat.check(nat.lib().vs_index_term_sums_ids(self._h, _ptr(ids_dev), B, m, int(ids_dev.stride(0)), int(id_offset), 1 if strict else 0,
-                                                   int(tile_cols), _ptr(sums), V, _ptr(total), current_stream(self.device)))
-        return sums, total
-
     def term_sums(self, filter=None, ids=None, rows_per_chunk: int = 0, tile_cols: int = 0) -> TermSums:
         """For a document set, how much weight it puts on each vocabulary column -> TermSums(sums [B, V], total [B]), int64 tensors on the
         index's device, enqueued on torch's current stream.  sums are fixed point: every stored cell adds its value (clamped to +-2^20)
@@ -2552,29 +2561,10 @@ class DeviceIndex:
         on the host and is skipped when it is on the device), or neither: every live document.  Deleted documents never contribute.
         rows_per_chunk: 0 = automatic, else a multiple of 64; tile_cols: 0 = automatic, else the columns of a workgroup's tile, at most
         18 432 (tuning knobs: the result does not depend on them)."""
-        import torch
         if filter is not None and ids is not None:
             raise ValueError("the set is given by `filter` or by `ids`, not both")
         rows_per_chunk, tile_cols = _term_sum_args(rows_per_chunk, tile_cols)
-        if ids is not None:
-            ids = _term_ids(ids)
-            nat.require_device()
-            dev = torch.device("cuda", self.device)
-            if _is_torch(ids) and ids.is_cuda:
-                t = ids.to(dev)
-                rows_ok = t.stride(1) == 1 and t.stride(0) >= t.shape[1]       # (a column slice of a wider hit list is read in place)
-                return TermSums(*self._term_sums_ids_call(t if rows_ok else t.contiguous(), 0, True, tile_cols))
-            h = np.ascontiguousarray(_host(ids))                        # a host list: checked by the library before it is staged
-            B, m, V = h.shape[0], h.shape[1], self._n_cols()
-            sums, total = np.empty((B, V), dtype=np.int64), np.empty(B, dtype=np.int64)
-            nat.check(nat.lib().vs_index_term_sums_ids(self._h, _ptr(h), B, m, m, 0, 1, tile_cols, _ptr(sums), V, _ptr(total), None))
-            return TermSums(torch.from_numpy(sums).to(dev), torch.from_numpy(total).to(dev))
-        nat.require_device()
-        f = None
-        if filter is not None:
-            from .doc_filter import as_doc_filter
-            f = as_doc_filter(filter, self.n_rows, device=self.device)
-        return TermSums(*self._term_sums_call(f, 0, rows_per_chunk, tile_cols))
+        return self._term_agg(_TERM_SUMS, filter, ids, rows_per_chunk, (tile_cols,))
 
     def top_weight_terms(self, filter=None, ids=None, topn: int = 20, min_count: int = 0) -> TopWeights:
         """term_sums of the set, then per query the `topn` columns with the largest mean weight (vs_term_sum_topn; see ``term_sum_topn``):
@@ -3028,15 +3018,10 @@ class ShardGroup:
         return ValueQuantiles(*_facet_out(values, *_quantile_batches(qa, ra, B, batch)))
 
     # ---- term aggregations ------------------------------------------------------------------------------------------------------------------
-    def term_counts(self, filter=None, ids=None, rows_per_chunk: int = 0) -> TermCounts:
-        """DeviceIndex.term_counts over the group's rows: filter and ids are global.  Every shard counts on its own GPU -- its bit range of
-        the filter, or the ids with its first row as the id offset (ids it does not own are skipped) -- and counts and total are summed on
-        the first shard's GPU.  Equal to the unsharded index exactly.  An id outside the group raises ValueError (host lists)."""
+    def _term_agg(self, spec, filter, ids, rows_per_chunk, extra=()):
+        """term_counts / term_sums over the group's rows: every shard takes its bit range of the global filter, or the global ids with its
+        first row as the id offset, and the integer parts are added on the first shard's GPU -> spec.result"""
         import torch
-        if filter is not None and ids is not None:
-            raise ValueError("the set is given by `filter` or by `ids`, not both")
-        if isinstance(rows_per_chunk, bool) or not isinstance(rows_per_chunk, (int, np.integer)) or rows_per_chunk < 0 or rows_per_chunk % 64:
-            raise ValueError(f"rows_per_chunk must be 0 (automatic) or a positive multiple of 64, got {rows_per_chunk!r}")
         n_total = self.n_rows
         dev0 = torch.device("cuda", self.device)
         f = t = None
@@ -3054,13 +3039,21 @@ class ShardGroup:
         for sh in self._shards:
             sdev = torch.device("cuda", sh.device)
             if t is not None:
-                part = sh._term_counts_ids_call(t.to(sdev).contiguous(), row0, False)
+                part = sh._term_ids_call(spec, t.to(sdev).contiguous(), row0, False, extra)
             else:
-                part = sh._term_counts_call(f.to(sdev) if f is not None else None, row0, int(rows_per_chunk))   # its rows: bits [row0, row0 + n)
+                part = sh._term_set_call(spec, f.to(sdev) if f is not None else None, row0, rows_per_chunk, extra)   # its rows: bits [row0, row0 + n)
             part = tuple(x.to(dev0) for x in part)
             out = part if out is None else tuple(a + b for a, b in zip(out, part))
             row0 += sh.n_rows
-        return TermCounts(*out)
+        return spec.result(*out)
+
+    def term_counts(self, filter=None, ids=None, rows_per_chunk: int = 0) -> TermCounts:
+        """DeviceIndex.term_counts over the group's rows: filter and ids are global.  Every shard counts on its own GPU -- its bit range of
+        the filter, or the ids with its first row as the id offset (ids it does not own are skipped) -- and counts and total are summed on
+        the first shard's GPU.  Equal to the unsharded index exactly.  An id outside the group raises ValueError (host lists)."""
+        if filter is not None and ids is not None:
+            raise ValueError("the set is given by `filter` or by `ids`, not both")
+        return self._term_agg(_TERM_COUNTS, filter, ids, _rows_per_chunk_arg(rows_per_chunk))
 
     def top_terms(self, filter=None, ids=None, topn: int = 20, method: str = "jlh", min_count: int = 1, background=None) -> TopTerms:
         """DeviceIndex.top_terms over the group's rows: the top-n is taken after the shards' counts are summed, never per shard."""
@@ -3071,34 +3064,10 @@ class ShardGroup:
         filter, or the ids with its first row as the id offset (ids it does not own are skipped) -- and sums and total are added on the
         first shard's GPU.  The additions are integer: equal to the unsharded index exactly.  An id outside the group raises ValueError
         (host lists)."""
-        import torch
         if filter is not None and ids is not None:
             raise ValueError("the set is given by `filter` or by `ids`, not both")
         rows_per_chunk, tile_cols = _term_sum_args(rows_per_chunk, tile_cols)
-        n_total = self.n_rows
-        dev0 = torch.device("cuda", self.device)
-        f = t = None
-        if ids is not None:
-            ids = _term_ids(ids)
-            on_dev = _is_torch(ids) and ids.is_cuda
-            t = ids if _is_torch(ids) else torch.from_numpy(np.ascontiguousarray(ids))
-            if not on_dev and t.numel() and (int(t.min()) < -1 or int(t.max()) >= n_total):
-                raise ValueError(f"an id lies outside [-1, {n_total})")
-        nat.require_device()
-        if filter is not None:
-            from .doc_filter import as_doc_filter
-            f = as_doc_filter(filter, n_total, device=dev0)
-        out, row0 = None, 0
-        for sh in self._shards:
-            sdev = torch.device("cuda", sh.device)
-            if t is not None:
-                part = sh._term_sums_ids_call(t.to(sdev).contiguous(), row0, False, tile_cols)
-            else:
-                part = sh._term_sums_call(f.to(sdev) if f is not None else None, row0, rows_per_chunk, tile_cols)   # its rows: bits [row0, row0 + n)
-            part = tuple(x.to(dev0) for x in part)
-            out = part if out is None else tuple(a + b for a, b in zip(out, part))
-            row0 += sh.n_rows
-        return TermSums(*out)
+        return self._term_agg(_TERM_SUMS, filter, ids, rows_per_chunk, (tile_cols,))
 
     def top_weight_terms(self, filter=None, ids=None, topn: int = 20, min_count: int = 0) -> TopWeights:
         """DeviceIndex.top_weight_terms over the group's rows: the top-n is taken after the shards' sums are added, never per shard."""
