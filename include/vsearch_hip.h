@@ -573,6 +573,58 @@ VS_API int vs_value_radix_step(int level, const int64_t* counts, int32_t B, int3
                                int64_t* rank_res, int32_t* rank_slot, uint32_t* rank_prefix, uint32_t* slot_prefix, int32_t* n_slots,
                                int64_t* count, int64_t* out_ranks, void* out_values, int dtype, int device, void* stream);
 
+/* ---- breakdowns: a numeric field's stats and histogram per facet label, in one pass (no reference counterpart) -------------------------------
+ * The product of the facet counts and the numeric fields above: labels int32 [n_rows] as for vs_facet_counts, values [n_rows] of dtype
+ * VS_VAL_F32 / VS_VAL_I32 as for vs_value_stats, the set of rows given exactly as there (words, bit0, ld_words, and_words; the vs_index_*
+ * variants AND the index's tombstones in at bit 0).  Everything is decided on the order keys above: every output is an integer or a 32-bit
+ * pattern, exact, independent of the launch, and bit-identical on a row-sharded index.  For a row of query b's set:
+ *   its label is outside [0, n_labels), -1 included: other [b] += 1 and nothing else, whether or not it has a value;
+ *   its label is l and it has a value (key != 0): count [b, l] += 1, min / max [b, l] are taken on the key, sum [b, l] adds what vs_value_stats
+ *     adds (the integer itself for int32, fx(v) of the term sums for fp32; int64 wrapping modulo 2^64);
+ *   its label is l and it has no value (NaN, INT32_MIN): missing [b, l] += 1;
+ *   total [b] is the size of the set: count [b].sum() + missing [b].sum() + other [b] == total [b], and count + missing is vs_facet_counts'
+ *   counts [b, l].
+ * vs_facet_value_plan: the launch of either call -- pure host arithmetic, no device needed.  n_slots = 0: stats, a query takes n_labels
+ *   24-byte records; n_slots = n_edges + 2: histogram, a query takes n_labels x n_slots uint32 bins.  regime 0: the records / bins of qt
+ *   queries sit in a workgroup's LDS (qt x records <= VS_FACET_VALUE_LDS_RECORDS, qt x bins <= VS_FACET_LDS_BINS; per-query bitmaps start at
+ *   qt = 8 and halve until that holds, a shared bitmap has qt = 1); regime 1: atomics straight into the outputs (qt = 8 or 1: the tile only
+ *   shares the loads).  chunks and rows_per_chunk by vs_value_plan's rule with a floor of 16 x the LDS records / bins of a query.
+ * vs_facet_value_stats: count, missing, sum int64 [B, ld_out]; out_min / out_max [B, ld_out] raw 32-bit values of the field's type (a cell with
+ *   count = 0: the missing sentinel, NaN 0x7FC00000 / INT32_MIN; of -0.0 and +0.0 the answer is +0.0); total, other int64 [B].  ld_out >=
+ *   n_labels; columns [n_labels, ld_out) of the five matrices are never written, every other element is.
+ * vs_facet_value_histogram: edges as for vs_value_histogram (checked the same way); counts int64 [B, n_labels, ld_counts]: bin i of (b, l)
+ *   holds the rows with label l and edges[i] <= v < edges[i + 1]; below / above / missing int64 [B, n_labels]; total, other int64 [B].
+ *   ld_counts >= n_edges - 1; columns [n_edges - 1, ld_counts) are never written.  counts [b].sum() + below [b].sum() + above [b].sum() +
+ *   missing [b].sum() + other [b] == total [b], always; the slots of (b, l) add up to vs_facet_counts' counts [b, l].
+ * Kernels (facet_values.hip): a workgroup owns a chunk of rows and a tile of qt queries and walks the bitmaps as the kernels above do; a lane
+ * whose row is in some query's set loads its label and its value once for the tile.  A step whose in-range rows of a query all carry one label
+ * (32 of them at least; one slot, for the histogram, any number) is reduced across the wave and added by one lane; otherwise every lane adds for itself.  Stats keep the min /
+ * max KEYS in out_min / out_max (preset to 0xFFFFFFFF / 0) until a finishing kernel turns them into values.
+ * Errors: as for vs_value_stats / vs_value_histogram, and n_labels < 1, n_labels x (n_edges + 2) > VS_FACET_VALUE_MAX_CELLS, B x n_labels >
+ * 2^31 - 1, ld_out < n_labels: VS_EINVAL, checked before the device is touched.  Pointers: all host (staged; the call blocks) or all device.
+ * Not covered: per-label percentiles; top-n labels by a statistic; two facet fields crossed; 64-bit values; the one-process-per-GPU RCCL path. */
+/* (query, label) records of a workgroup's LDS in the stats kernel: 24 bytes each, 48 KiB, so three workgroups fit a CU's 160 KiB.  A design
+ * choice: the occupancy it leaves has not been measured against a smaller or a larger cap. */
+#define VS_FACET_VALUE_LDS_RECORDS 2048
+#define VS_FACET_VALUE_MAX_CELLS 4194304 /* n_labels x (n_edges + 2) of a histogram call: 2^22 cells a query */
+VS_API int vs_facet_value_plan(int64_t n_rows, int32_t B, int32_t n_labels, int32_t n_slots, int per_query, int64_t rows_per_chunk,
+                               int32_t* out_regime, int32_t* out_qt, int64_t* out_chunks, int64_t* out_rows_per_chunk);
+VS_API int vs_facet_value_stats(const uint32_t* words, int64_t bit0, int64_t ld_words, const uint32_t* and_words, int32_t B, const int32_t* labels,
+                                int32_t n_labels, const void* values, int dtype, int64_t n_rows, int64_t rows_per_chunk, int64_t* count,
+                                int64_t* missing, void* out_min, void* out_max, int64_t* sum, int64_t ld_out, int64_t* total, int64_t* other,
+                                int device, void* stream);
+VS_API int vs_index_facet_value_stats(vs_index* index, const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B, const int32_t* labels,
+                                      int32_t n_labels, const void* values, int dtype, int64_t rows_per_chunk, int64_t* count, int64_t* missing,
+                                      void* out_min, void* out_max, int64_t* sum, int64_t ld_out, int64_t* total, int64_t* other, void* stream);
+VS_API int vs_facet_value_histogram(const uint32_t* words, int64_t bit0, int64_t ld_words, const uint32_t* and_words, int32_t B,
+                                    const int32_t* labels, int32_t n_labels, const void* values, int dtype, int64_t n_rows, const void* edges,
+                                    int32_t n_edges, int64_t rows_per_chunk, int64_t* counts, int64_t ld_counts, int64_t* below, int64_t* above,
+                                    int64_t* missing, int64_t* total, int64_t* other, int device, void* stream);
+VS_API int vs_index_facet_value_histogram(vs_index* index, const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B, const int32_t* labels,
+                                          int32_t n_labels, const void* values, int dtype, const void* edges, int32_t n_edges,
+                                          int64_t rows_per_chunk, int64_t* counts, int64_t ld_counts, int64_t* below, int64_t* above,
+                                          int64_t* missing, int64_t* total, int64_t* other, void* stream);
+
 /* bool / uint8 mask [B, n] (row stride ld_mask bytes; non-zero = allowed) -> the bitmap words [B, ld_words] vs_index_search_filtered
  * reads (bits past n of a row's last word are 0).  mask and words: host pointers or device pointers on `device` (VS_EINVAL otherwise).  stream as in
  * vs_index_search (host buffers block).                                                                                          */

@@ -38,6 +38,8 @@ VAL_F32, VAL_I32, VALUE_MAX_RANGES, VALUE_MAX_EDGES, VALUE_MAX_TOPK = 0, 1, 4096
 # percentiles (VS_VALUE_RADIX_*, VS_VALUE_MAX_RANKS, VS_QUANTILE_*): bins of a radix level, the levels, the most ranks of a call, the rank rules
 VALUE_RADIX_BINS, VALUE_RADIX_LEVELS, VALUE_MAX_RANKS = 2048, 3, 16
 QUANTILE_LOWER, QUANTILE_HIGHER, QUANTILE_NEAREST = 0, 1, 2
+# breakdowns (VS_FACET_VALUE_*): (query, label) records of a workgroup's LDS in the stats kernel, n_labels x (n_edges + 2) cells a query at most
+FACET_VALUE_LDS_RECORDS, FACET_VALUE_MAX_CELLS = 2048, 1 << 22
 
 
 class VsearchNativeError(RuntimeError):
@@ -104,6 +106,13 @@ _SIGNATURES = {
     "vs_value_radix_counts": ([_vp, _i64, _i64, _vp, _i32, _vp, _int, _i64, _int, _i32, _vp, _vp, _i64, _vp, _vp, _int, _vp], _int),
     "vs_index_value_radix_counts": ([_vp, _vp, _i64, _i64, _i32, _vp, _int, _int, _i32, _vp, _vp, _i64, _vp, _vp, _vp], _int),
     "vs_value_radix_step": ([_int, _vp, _i32, _i32, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _vp], _int),
+    "vs_facet_value_plan": ([_i64, _i32, _i32, _i32, _int, _i64, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i64)], _int),
+    "vs_facet_value_stats": ([_vp, _i64, _i64, _vp, _i32, _vp, _i32, _vp, _int, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _int, _vp], _int),
+    "vs_index_facet_value_stats": ([_vp, _vp, _i64, _i64, _i32, _vp, _i32, _vp, _int, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp], _int),
+    "vs_facet_value_histogram": ([_vp, _i64, _i64, _vp, _i32, _vp, _i32, _vp, _int, _i64, _vp, _i32, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _int,
+                                  _vp], _int),
+    "vs_index_facet_value_histogram": ([_vp, _vp, _i64, _i64, _i32, _vp, _i32, _vp, _int, _vp, _i32, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
+                                       _int),
     "vs_filter_pack": ([_vp, _i32, _i64, _i64, _vp, _i64, _int, _vp], _int),
     "vs_index_scores": ([_vp, _vp, _int, _i64, _i32, _vp, _vp], _int),
     "vs_index_explain": ([_vp, _vp, _int, _i64, _i32, _vp, _i64, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp], _int),

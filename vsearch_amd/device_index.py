@@ -1434,6 +1434,58 @@ def _value_set(filter, n_rows, device):
     return as_doc_filter(filter, n_rows, device=device)
 
 
+# ---- breakdowns: a numeric field's stats and histogram per facet label (vs_facet_value_stats, vs_facet_value_histogram) ---------------------
+class FacetValueStats(NamedTuple):
+    """facet_value_stats: per (query, label) the ValueStats of the set's documents with that label -- count, missing, sum int64 [B, L], min /
+    max [B, L] in the field's type (the missing sentinel where count is 0) -- with the size of the set (total [B]) and its documents whose
+    label is outside [0, L) (other [B]): count.sum(1) + missing.sum(1) + other == total, and count + missing is facet_counts' counts."""
+    count: Any
+    missing: Any
+    min: Any
+    max: Any
+    sum: Any
+    total: Any
+    other: Any
+
+    def mean(self):
+        """the mean value per (query, label) in fp64 (NaN for a cell without values)"""
+        return ValueStats(self.count, self.missing, self.min, self.max, self.sum).mean()
+
+
+class FacetValueHistogram(NamedTuple):
+    """facet_value_histogram: counts int64 [B, L, E - 1] -- bin i of (b, l) holds the set's documents with label l and edges[i] <= v <
+    edges[i + 1]; below / above / missing int64 [B, L] as in ValueHistogram; total / other int64 [B] as in FacetCounts: counts.sum((1, 2)) +
+    below.sum(1) + above.sum(1) + missing.sum(1) + other == total."""
+    counts: Any
+    below: Any
+    above: Any
+    missing: Any
+    total: Any
+    other: Any
+
+
+def facet_value_plan(n_rows: int, B: int, n_labels: int, n_slots: int, per_query: bool, rows_per_chunk: int = 0):
+    """The launch vs_facet_value_stats (n_slots = 0) / vs_facet_value_histogram (n_slots = n_edges + 2) take for these arguments
+    (vs_facet_value_plan; pure host arithmetic, no GPU needed) -> (regime, qt, chunks, rows_per_chunk): regime 0 = LDS records / bins, 1 =
+    global atomics; qt = queries a workgroup serves."""
+    regime, qt, chunks, rpc = C.c_int32(0), C.c_int32(0), C.c_int64(0), C.c_int64(0)
+    nat.check(nat.lib().vs_facet_value_plan(int(n_rows), int(B), int(n_labels), int(n_slots), 1 if per_query else 0, int(rows_per_chunk),
+                                            C.byref(regime), C.byref(qt), C.byref(chunks), C.byref(rpc)))
+    return regime.value, qt.value, chunks.value, rpc.value
+
+
+def _facet_value_args(labels, n_labels, values, n_rows, rows_per_chunk=0, edges=None):
+    """Argument checks of a breakdown that need no device -> (n_labels, vs dtype, rows_per_chunk, edges in the field's type | None)"""
+    n_labels, rows_per_chunk = _facet_args(labels, n_labels, n_rows, rows_per_chunk)
+    dt, _ = _value_args(values, n_rows, rows_per_chunk)
+    e = None
+    if edges is not None:
+        e = _value_edges(edges, dt)
+        if n_labels * (int(e.shape[0]) + 2) > nat.FACET_VALUE_MAX_CELLS:
+            raise ValueError(f"n_labels x (n_edges + 2) = {n_labels * (int(e.shape[0]) + 2)} is more than the {nat.FACET_VALUE_MAX_CELLS} cells a query takes")
+    return n_labels, dt, rows_per_chunk, e
+
+
 # ---- percentiles: exact order statistics of a numeric field (vs_value_quantiles, vs_value_radix_counts, vs_value_radix_step) ----------------
 MAX_VALUE_RANKS = nat.VALUE_MAX_RANKS
 QUANTILE_METHODS = {"lower": nat.QUANTILE_LOWER, "higher": nat.QUANTILE_HIGHER, "nearest": nat.QUANTILE_NEAREST}
@@ -2423,6 +2475,60 @@ class DeviceIndex:
         return SortedResults(*_facet_out(values, *self._value_topk_call(_values_on(values, self.device), dt, k, descending, id_offset, f, 0,
                                                                         rows_per_chunk)))
 
+    # ---- breakdowns: a numeric field by facet label (vs_index_facet_value_stats / _histogram) --------------------------------------------------
+    def _facet_value_stats_call(self, labels_dev, n_labels, vals_dev, dt, f, bit0, rows_per_chunk):
+        """One vs_index_facet_value_stats call on device buffers and torch's current stream -> (count, missing, min, max, sum [B, L], total,
+        other [B]) CUDA tensors.  labels_dev / vals_dev: int32 and float32 / int32 CUDA tensors [n_rows] on this index's device; f: None or a
+        DocFilter there, read from bit `bit0` on."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        B, set_args = self._value_set_args(f, bit0)
+        count, missing, total_sum = (torch.empty((B, n_labels), dtype=torch.int64, device=dev) for _ in range(3))
+        lo, hi = (torch.empty((B, n_labels), dtype=vals_dev.dtype, device=dev) for _ in range(2))
+        total, other = (torch.empty(B, dtype=torch.int64, device=dev) for _ in range(2))
+        nat.check(nat.lib().vs_index_facet_value_stats(self._h, *set_args, _ptr(labels_dev), n_labels, _ptr(vals_dev), dt, rows_per_chunk,
+                                                       _ptr(count), _ptr(missing), _ptr(lo), _ptr(hi), _ptr(total_sum), n_labels, _ptr(total),
+                                                       _ptr(other), current_stream(self.device)))
+        return count, missing, lo, hi, total_sum, total, other
+
+    def _facet_value_hist_call(self, labels_dev, n_labels, vals_dev, dt, edges_dev, f, bit0, rows_per_chunk):
+        """One vs_index_facet_value_histogram call -> (counts [B, L, E - 1], below, above, missing [B, L], total, other [B]) int64 CUDA tensors"""
+        import torch
+        dev = torch.device("cuda", self.device)
+        B, set_args = self._value_set_args(f, bit0)
+        E = int(edges_dev.shape[0])
+        counts = torch.empty((B, n_labels, E - 1), dtype=torch.int64, device=dev)
+        below, above, missing = (torch.empty((B, n_labels), dtype=torch.int64, device=dev) for _ in range(3))
+        total, other = (torch.empty(B, dtype=torch.int64, device=dev) for _ in range(2))
+        nat.check(nat.lib().vs_index_facet_value_histogram(self._h, *set_args, _ptr(labels_dev), n_labels, _ptr(vals_dev), dt, _ptr(edges_dev), E,
+                                                           rows_per_chunk, _ptr(counts), E - 1, _ptr(below), _ptr(above), _ptr(missing),
+                                                           _ptr(total), _ptr(other), current_stream(self.device)))
+        return counts, below, above, missing, total, other
+
+    def facet_value_stats(self, labels, n_labels: int, values, filter=None, rows_per_chunk: int = 0) -> FacetValueStats:
+        """Count, missing, min, max and sum of a numeric field per facet label over a document set, in one pass -> FacetValueStats (matrices
+        [B, n_labels], total / other [B]); ``.mean()`` in fp64.  labels as in ``facet_counts`` (a label outside [0, n_labels) counts into
+        `other` and nothing else), values as in ``value_stats``; filter: what search(filter=) accepts.  Deleted documents never count.
+        numpy in -> numpy out; tensors in -> tensors on the index's device, enqueued on torch's current stream."""
+        n = self.n_rows
+        n_labels, dt, rows_per_chunk, _ = _facet_value_args(labels, n_labels, values, n, rows_per_chunk)
+        nat.require_device()
+        f = _value_set(filter, n, self.device)
+        return FacetValueStats(*_facet_out(labels, *self._facet_value_stats_call(_labels_on(labels, self.device), n_labels,
+                                                                                 _values_on(values, self.device), dt, f, 0, rows_per_chunk)))
+
+    def facet_value_histogram(self, labels, n_labels: int, values, edges, filter=None, rows_per_chunk: int = 0) -> FacetValueHistogram:
+        """How the documents of each facet label spread over the bins [edges[i], edges[i + 1]) of a numeric field, over a document set, in one
+        pass (a cross-tab) -> FacetValueHistogram(counts [B, n_labels, E - 1], below, above, missing [B, n_labels], total, other [B]).
+        edges: 2..1025 strictly ascending numbers, n_labels x (E + 2) <= 2^22.  labels, values, filter, outputs as in ``facet_value_stats``."""
+        n = self.n_rows
+        n_labels, dt, rows_per_chunk, e = _facet_value_args(labels, n_labels, values, n, rows_per_chunk, edges)
+        nat.require_device()
+        f = _value_set(filter, n, self.device)
+        return FacetValueHistogram(*_facet_out(labels, *self._facet_value_hist_call(_labels_on(labels, self.device), n_labels,
+                                                                                    _values_on(values, self.device), dt, _values_on(e, self.device),
+                                                                                    f, 0, rows_per_chunk)))
+
     # ---- percentiles (vs_index_value_quantiles, vs_index_value_radix_counts) ------------------------------------------------------------------
     def _value_quantiles_call(self, vals_dev, dt, q_dev, method, ranks_dev, R, f, bit0, rows_per_chunk):
         """One vs_index_value_quantiles call on device buffers -> (values [B, R], ranks int64 [B, R], count, missing int64 [B]) CUDA tensors.
@@ -2966,6 +3072,44 @@ class ShardGroup:
                                   lambda sh, v, f, row0: sh._value_hist_call(v, dt, _values_on(e, sh.device), f, row0, rows_per_chunk))
         c, below, above, missing = (sum(x[1:], x[0]) for x in zip(*parts))
         return ValueHistogram(*_facet_out(values, c, below, above, missing, c.sum(1) + below + above + missing))
+
+    # ---- breakdowns -----------------------------------------------------------------------------------------------------------------------------
+    def _facet_value_parts(self, labels, values, filter, call):
+        """call(shard, its labels, its values, its filter, its first row) for every shard -> the results, moved to the first shard's GPU"""
+        import torch
+        dev0 = torch.device("cuda", self.device)
+        f = _value_set(filter, self.n_rows, dev0)
+        parts, row0 = [], 0
+        for sh, lab, vals in zip(self._shards, self._facet_slices(labels), self._value_slices(values)):
+            fs = f.to(torch.device("cuda", sh.device)) if f is not None else None
+            parts.append(tuple(t.to(dev0) for t in call(sh, lab, vals, fs, row0)))  # its rows are bits [row0, row0 + n) of the filter
+            row0 += sh.n_rows
+        return parts
+
+    def facet_value_stats(self, labels, n_labels: int, values, filter=None, rows_per_chunk: int = 0) -> FacetValueStats:
+        """DeviceIndex.facet_value_stats over the group's rows: labels, values and filter are global; counts and sums are added on the first
+        shard's GPU, min and max combined on the order keys over [S, B, L].  Equal to the unsharded index exactly."""
+        import torch
+        n_labels, dt, rows_per_chunk, _ = _facet_value_args(labels, n_labels, values, self.n_rows, rows_per_chunk)
+        nat.require_device()
+        parts = self._facet_value_parts(labels, values, filter,
+                                        lambda sh, l, v, f, row0: sh._facet_value_stats_call(l, n_labels, v, dt, f, row0, rows_per_chunk))
+        count, missing, lo, hi, total_sum, total, other = (torch.stack(x) for x in zip(*parts))      # [S, B, L] / [S, B]
+        has = count > 0
+        klo = torch.where(has, _value_keys(lo), torch.full_like(count, 1 << 32))
+        khi = torch.where(has, _value_keys(hi), torch.zeros_like(count))
+        lo = lo.gather(0, klo.argmin(0, keepdim=True))[0]
+        hi = hi.gather(0, khi.argmax(0, keepdim=True))[0]
+        return FacetValueStats(*_facet_out(labels, count.sum(0), missing.sum(0), lo, hi, total_sum.sum(0), total.sum(0), other.sum(0)))
+
+    def facet_value_histogram(self, labels, n_labels: int, values, edges, filter=None, rows_per_chunk: int = 0) -> FacetValueHistogram:
+        """DeviceIndex.facet_value_histogram over the group's rows: the shards' bins are added on the first shard's GPU."""
+        n_labels, dt, rows_per_chunk, e = _facet_value_args(labels, n_labels, values, self.n_rows, rows_per_chunk, edges)
+        nat.require_device()
+        parts = self._facet_value_parts(labels, values, filter,
+                                        lambda sh, l, v, f, row0: sh._facet_value_hist_call(l, n_labels, v, dt, _values_on(e, sh.device), f, row0,
+                                                                                            rows_per_chunk))
+        return FacetValueHistogram(*_facet_out(labels, *(sum(x[1:], x[0]) for x in zip(*parts))))
 
     def value_topk(self, values, k: int, descending: bool = True, filter=None, rows_per_chunk: int = 0) -> SortedResults:
         """DeviceIndex.value_topk over the group's rows (global ids): every shard lists its k best with its id offset; the lists are merged by

@@ -25,6 +25,7 @@ from ... import _native as nat
 from ...device_index import Assignment, KMeansResult, KMEANS_UPDATE_BATCH, kmeans_loop, term_sum_topn, _assign_args, _kmeans_args, DeviceIndex, DiverseResults, Explanation, FacetCounts, FusedResults, GroupedResults, TermCounts, TermSums, TopFacets, TopTerms, TopWeights, _term_topn_args, _weight_topn_args, fuse_topk, _fuse_args, MAX_FUSE_DEPTH, MAX_FUSE_ENTRIES, _topn_args, NotBinaryError, RangeResults, ShardGroup, _diverse_args, _range_args, _grouped_args, _by_example_args, _explain_args, _int64_ids, _k_a_args, resparsify, topk_exclude
 from ...device_index import SortedResults, ValueHistogram, ValueStats, value_column, _value_bounds, _value_dtype, _value_edges, _value_topk_args
 from ...device_index import ValuePercentiles, _percentile_args, quantile_lerp
+from ...device_index import FacetValueHistogram, FacetValueStats
 
 logger = logging.getLogger(__name__)
 
@@ -735,6 +736,37 @@ class Index:
         v = self._value_field(field)
         filter = self._value_set(q_embs, min_score, filter)
         return ValueHistogram(*(self._to_api(t) for t in self._explain_target()[0].value_histogram(v, edges, filter=filter)))
+
+    def _facet_check(self, field):
+        """the argument errors of naming a facet field, before any device work"""
+        if field == "groups":
+            if self.groups is None:
+                raise RuntimeError("the index has no groups: set_groups(groups) or groups_from_samples(key) first")
+        elif field not in self._facet_store():
+            raise KeyError(f"no facet field {field!r}: set_facet() or facet_from_samples() first (fields: {list(self._facet_store())})")
+
+    def stats_by_facet(self, value_field: str, facet_field: str, q_embs=None, min_score=None, filter=None) -> FacetValueStats:
+        """Count, missing, min, max and sum of value field `value_field` per label of facet field `facet_field` ("groups" = the group ids) over
+        a document set, in one pass over the index -> FacetValueStats(count, missing, min, max, sum [B, n_labels], total, other [B]);
+        ``.mean()`` in fp64 -- "mean price per category of the matches".  A document without a label counts into `other` only.  The set as in
+        ``value_stats``.  Works on a row-sharded index as well."""
+        self._value_check(value_field, q_embs, min_score)
+        self._facet_check(facet_field)
+        v = self._value_field(value_field)
+        codes, n_labels, _ = self._facet_field(facet_field)
+        filter = self._value_set(q_embs, min_score, filter)
+        return FacetValueStats(*(self._to_api(t) for t in self._explain_target()[0].facet_value_stats(codes, n_labels, v, filter=filter)))
+
+    def histogram_by_facet(self, value_field: str, facet_field: str, edges, q_embs=None, min_score=None, filter=None) -> FacetValueHistogram:
+        """How the documents of each label of `facet_field` spread over the bins [edges[i], edges[i + 1]) of `value_field`, over a document
+        set (a cross-tab) -> FacetValueHistogram(counts [B, n_labels, E - 1], below, above, missing [B, n_labels], total, other [B]).
+        edges: 2..1025 strictly ascending numbers.  The set as in ``value_stats``."""
+        _value_edges(edges, self._value_check(value_field, q_embs, min_score))
+        self._facet_check(facet_field)
+        v = self._value_field(value_field)
+        codes, n_labels, _ = self._facet_field(facet_field)
+        filter = self._value_set(q_embs, min_score, filter)
+        return FacetValueHistogram(*(self._to_api(t) for t in self._explain_target()[0].facet_value_histogram(codes, n_labels, v, edges, filter=filter)))
 
     def top_by_value(self, field: str, k: int, descending: bool = True, q_embs=None, min_score=None, filter=None) -> SortedResults:
         """The k documents of a set with the largest (descending) or smallest values of `field`, ties by id ascending -- sort by a field

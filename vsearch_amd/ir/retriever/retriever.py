@@ -187,6 +187,44 @@ class Retriever(BiEncoder):
         index, q_emb, filter = self._match_set(queries, index, filter, must, must_not, should, min_should, dropout, a, batch_size)
         return index.histogram(field, edges, q_embs=q_emb, min_score=min_score, filter=filter)
 
+    def retrieve_stats_by_facet(self, queries: Union[List[str], np.ndarray, T], value_field: str, facet_field: str, min_score=0.0, topn: int = 10,
+                                min_count: int = 1, dropout: float = 0, a: int = None, index: Index = None, batch_size: int = 32, filter=None,
+                                must=None, must_not=None, should=None, min_should: int = None):
+        """The stats of value field `value_field` per label of `facet_field` over each query's matches -- ``Index.stats_by_facet`` behind the
+        query encoder, the match set as in ``retrieve_histogram`` -> (rows, totals): rows[b] lists (name, docs, count, min, max, mean) for the
+        `topn` labels with the most documents of the set (docs = count + missing, at least max(min_count, 1)), docs descending then label
+        ascending; name is the label's code where the field has no names; min / max are None and mean is NaN where no document of the label
+        has a value; totals[b] is the number of matches."""
+        from ...device_index import facet_topn, _topn_args
+        topn, min_count = _topn_args(topn, min_count)
+        index, q_emb, filter = self._match_set(queries, index, filter, must, must_not, should, min_should, dropout, a, batch_size)
+        st = index.stats_by_facet(value_field, facet_field, q_embs=q_emb, min_score=min_score, filter=filter)
+        docs = st.count + st.missing
+        top_l, top_c = facet_topn(docs if docs.is_cuda else docs.numpy(), topn, min_count, device=index._explain_target()[1])
+        top_l, top_c = (x.cpu().numpy() if isinstance(x, torch.Tensor) else x for x in (top_l, top_c))
+        names = index.facet_names(facet_field)
+        count, lo, hi, mean = st.count.cpu().numpy(), st.min.cpu().numpy(), st.max.cpu().numpy(), st.mean().cpu().numpy()
+        rows = []
+        for b in range(top_l.shape[0]):
+            out = []
+            for l, d in zip(top_l[b].tolist(), top_c[b].tolist()):
+                if l < 0:
+                    continue
+                c = int(count[b, l])
+                out.append((names[l] if names is not None else l, d, c, lo[b, l].item() if c else None, hi[b, l].item() if c else None,
+                            float(mean[b, l])))
+            rows.append(out)
+        return rows, st.total.cpu().tolist()
+
+    def retrieve_histogram_by_facet(self, queries: Union[List[str], np.ndarray, T], value_field: str, facet_field: str, edges, min_score=0.0,
+                                    dropout: float = 0, a: int = None, index: Index = None, batch_size: int = 32, filter=None, must=None,
+                                    must_not=None, should=None, min_should: int = None):
+        """How each query's matches spread over (label of `facet_field`, bin of `value_field`) -- ``Index.histogram_by_facet`` behind the query
+        encoder, the match set as in ``retrieve_histogram`` -> FacetValueHistogram(counts [B, n_labels, E - 1], below, above, missing, total,
+        other)."""
+        index, q_emb, filter = self._match_set(queries, index, filter, must, must_not, should, min_should, dropout, a, batch_size)
+        return index.histogram_by_facet(value_field, facet_field, edges, q_embs=q_emb, min_score=min_score, filter=filter)
+
     def retrieve_percentiles(self, queries: Union[List[str], np.ndarray, T], field: str, pcts, min_score=0.0, method: str = "linear",
                              dropout: float = 0, a: int = None, index: Index = None, batch_size: int = 32, filter=None, must=None, must_not=None,
                              should=None, min_should: int = None):
