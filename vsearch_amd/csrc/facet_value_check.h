@@ -1,6 +1,6 @@
 // facet_value_check.h -- the plan rule, the limits and the argument checks of the breakdowns (vs_facet_value_plan, vs_facet_value_stats,
 // vs_facet_value_histogram and their vs_index_* variants) that need no device.  A breakdown is a numeric field's stats or
-// histogram per facet label: the set and the chunking are checked by set_check.h, the dtype, the edges and the automatic chunk's constants are
+// histogram per facet label: the set and the chunking are checked by set_check.h, the automatic chunk included; the dtype and the edges are
 // value_check.h's.
 // Plain C++ with no HIP in it, so that a stand-alone program can run them under a host sanitizer (tests/test_facet_value_cpu.py builds one).
 #pragma once
@@ -44,13 +44,8 @@ inline int facet_value_plan(int64_t n_rows, int32_t B, int32_t n_labels, int32_t
         while (p.qt > 1 && (int64_t)p.qt * cells > lds_cap) p.qt >>= 1;
     p.lds_slots = p.regime ? 0 : cells;
     const int64_t tiles = (B + p.qt - 1) / p.qt;
-    if (rows_per_chunk == 0) {
-        // value_plan's rule: enough workgroups to fill the chip, chunks long enough that zeroing and flushing the LDS stays a sixteenth of the walk
-        const int64_t want = std::max<int64_t>(1, kValueAutoItems / tiles);
-        const int64_t floor_rows = std::max<int64_t>(kValueMinChunk, (int64_t)16 * p.lds_slots);
-        rows_per_chunk = std::max<int64_t>((n_rows + want - 1) / want, floor_rows);
-        rows_per_chunk = (rows_per_chunk + kSpanRows - 1) / kSpanRows * kSpanRows;
-    }
+    // value_plan's rule: enough workgroups to fill the chip, chunks long enough that zeroing and flushing the LDS stays a sixteenth of the walk
+    if (rows_per_chunk == 0) rows_per_chunk = auto_chunk(n_rows, tiles, std::max<int64_t>(kMinChunk, (int64_t)16 * p.lds_slots));
     p.rows_per_chunk = rows_per_chunk;
     p.chunks = (n_rows + rows_per_chunk - 1) / rows_per_chunk;
     if (p.chunks > 0x7FFFFFFF || tiles > 65535)

@@ -60,7 +60,7 @@ int main() {
 
     // ---- the automatic chunk: value_plan's rule with a floor of 16 x the LDS slots of a query ----------------------------------------------------
     expect("auto small", plan(1000, 1, 12, 0, false, 0), VS_OK, msg, "");
-    expect_true("auto small: one chunk of the floor", p.chunks == 1 && p.rows_per_chunk == kValueMinChunk);
+    expect_true("auto small: one chunk of the floor", p.chunks == 1 && p.rows_per_chunk == kMinChunk);
     expect("auto 21M", plan(21015324, 8, 12, 0, true, 0), VS_OK, msg, "");
     expect_true("auto 21M: <= 1024 chunks of whole spans",
                 p.rows_per_chunk % kSpanRows == 0 && p.chunks <= 1024 && p.chunks * p.rows_per_chunk >= 21015324 && (p.chunks - 1) * p.rows_per_chunk < 21015324);
@@ -69,7 +69,7 @@ int main() {
     expect("auto floor hist", plan(1 << 20, 1, 1000, 16, true, 0), VS_OK, msg, "");
     expect_true("auto floor hist: 16 rows a bin", p.rows_per_chunk == 16 * 16000 && p.rows_per_chunk % kSpanRows == 0);
     expect("auto global", plan(1 << 20, 1, 70000, 0, true, 0), VS_OK, msg, "");
-    expect_true("auto global: no LDS, the plain floor", p.rows_per_chunk == kValueMinChunk && p.chunks == 128);
+    expect_true("auto global: no LDS, the plain floor", p.rows_per_chunk == kMinChunk && p.chunks == 128);
     expect("given", plan(3 * 2048 + 1, 17, 7, 0, true, 64), VS_OK, msg, "");
     expect_true("given: taken as it is", p.rows_per_chunk == 64 && p.chunks == 97 && p.qt == 8);
 

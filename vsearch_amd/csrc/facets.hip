@@ -22,8 +22,6 @@ namespace {
 
 constexpr int kFacetThreads = 256;
 constexpr int kFacetWaves = kFacetThreads / 64;
-constexpr int kFacetAutoItems = 1024;                 // workgroups the automatic plan aims at (4 a CU)
-constexpr int64_t kFacetMinChunk = 8192;              // rows of an automatic chunk at least
 
 struct FacetArgs {
     RowSet set;
@@ -132,14 +130,9 @@ int facet_plan(int64_t n_rows, int32_t B, int32_t n_labels, bool per_query, int6
         if (!p.regime)
             while (p.qt > 1 && (int64_t)p.qt * n_labels > VS_FACET_LDS_BINS) p.qt >>= 1;
     }
-    if (rows_per_chunk == 0) {
-        // enough workgroups to fill the chip, chunks long enough that zeroing and flushing a histogram stays a sixteenth of the bit tests
-        const int64_t tiles = ceil_div64(B, p.qt);
-        const int64_t want = std::max<int64_t>(1, kFacetAutoItems / tiles);
-        const int64_t floor_rows = p.regime ? kFacetMinChunk : std::max<int64_t>(kFacetMinChunk, (int64_t)16 * n_labels);
-        rows_per_chunk = std::max(ceil_div64(n_rows, want), floor_rows);
-        rows_per_chunk = ceil_div64(rows_per_chunk, kSpanRows) * kSpanRows;
-    }
+    // enough workgroups to fill the chip, chunks long enough that zeroing and flushing a histogram stays a sixteenth of the bit tests
+    if (rows_per_chunk == 0)
+        rows_per_chunk = auto_chunk(n_rows, ceil_div64(B, p.qt), p.regime ? kMinChunk : std::max<int64_t>(kMinChunk, (int64_t)16 * n_labels));
     p.rows_per_chunk = rows_per_chunk;
     p.chunks = ceil_div64(n_rows, rows_per_chunk);
     *out = p;

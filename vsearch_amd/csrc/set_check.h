@@ -1,6 +1,6 @@
 // set_check.h -- the argument checks every aggregation over a row set repeats (facets, term counts, term sums, numeric fields): the rows and the
 // batch, one set or one per query, the chunking, the geometry of a bitmap or of id lists, the stride of an output -- and the automatic-chunk rule
-// of the term aggregations.  Every function writes its message into msg and returns a VS_* code.
+// of them all.  Every function writes its message into msg and returns a VS_* code.
 // Plain C++ with no HIP in it, so that the stand-alone check programs build with a host compiler.
 #pragma once
 
@@ -16,7 +16,8 @@ namespace vs {
 constexpr int kSpanRows = 2048;                       // rows a wave loads the bitmap words of at a time: 64 lanes x 32 bits (set_walk.h)
 constexpr int64_t kSetMaxRows = 0xFFFFFFFFll;         // a chunk's count fits a uint32 bin
 constexpr int32_t kTermMaxCols = 65535;               // the packets hold uint16 column ids; n_cols itself is the padding id
-constexpr int kTermAutoItems = 1024;                  // workgroups the automatic plan of the term aggregations aims at (4 a CU)
+constexpr int kAutoItems = 1024;                      // workgroups an automatic plan aims at (4 a CU)
+constexpr int64_t kMinChunk = 8192;                   // rows of an automatic chunk at least, where a workgroup keeps bins per label or per value
 
 inline int check_n_rows(int64_t n_rows, char* msg, size_t cap) {
     if (n_rows < 1 || n_rows > kSetMaxRows) return snprintf(msg, cap, "n_rows must be in 1..2^32 - 1 (got %lld)", (long long)n_rows), VS_EINVAL;
@@ -47,11 +48,12 @@ inline int check_term_set(int64_t n_rows, int32_t B, int32_t n_cols, bool per_qu
     return rc;
 }
 
-// The automatic chunk of the term aggregations over `items` work items a chunk: a few workgroups per CU over the batch; a chunk is at least one
-// span, so zeroing and flushing a workgroup's bins stays small against the cells of the chunk's rows.
-inline int64_t auto_chunk(int64_t n_rows, int64_t items) {
-    const int64_t want = std::max<int64_t>(1, kTermAutoItems / items);
-    const int64_t rows = std::max<int64_t>((n_rows + want - 1) / want, kSpanRows);
+// The automatic chunk over `items` work items a chunk: a few workgroups per CU over the batch; a chunk is at least floor_rows rows (the term
+// aggregations: one span; the others: kMinChunk, or 16 rows a bin a workgroup keeps), so zeroing and flushing a workgroup's bins stays small
+// against the work of the chunk's rows; whole spans.
+inline int64_t auto_chunk(int64_t n_rows, int64_t items, int64_t floor_rows = kSpanRows) {
+    const int64_t want = std::max<int64_t>(1, kAutoItems / items);
+    const int64_t rows = std::max<int64_t>((n_rows + want - 1) / want, floor_rows);
     return (rows + kSpanRows - 1) / kSpanRows * kSpanRows;
 }
 

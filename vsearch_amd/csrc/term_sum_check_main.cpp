@@ -73,7 +73,7 @@ int main() {
     }
     expect("tile_cols = -1", plan(100, 1, 40, true, 0, -1), VS_EINVAL, msg, "tile_cols must");
     expect("tile_cols too wide", plan(100, 1, 40, true, 0, T + 1), VS_EINVAL, msg, "tile_cols must");
-    // chunks cover the rows; an explicit chunk is taken as given; the automatic one aims at kTermAutoItems work items
+    // chunks cover the rows; an explicit chunk is taken as given; the automatic one aims at kAutoItems work items
     const int64_t rows[] = {1, 63, 64, 65, 2047, 2048, 2049, 1000000, 21000000, kTermMaxRows};
     const int64_t rpcs[] = {0, 64, 2048, 1 << 20};
     for (const int64_t n : rows)
@@ -91,7 +91,7 @@ int main() {
                                                              (rpc == 0 || p.rows_per_chunk == rpc));
                     if (rpc == 0)
                         expect_true("automatic chunks", p.rows_per_chunk % kTermSpanRows == 0 &&
-                                                            p.chunks * B * tiles <= std::max<int64_t>(kTermAutoItems, B * tiles));
+                                                            p.chunks * B * tiles <= std::max<int64_t>(kAutoItems, B * tiles));
                 }
     expect("n_rows = 0", plan(0, 1, 8, true, 0, 0), VS_EINVAL, msg, "n_rows must");
     expect("n_rows = 2^32", plan(kTermMaxRows + 1, 1, 8, true, 0, 0), VS_EINVAL, msg, "n_rows must");

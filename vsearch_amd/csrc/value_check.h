@@ -17,8 +17,6 @@ namespace vs {
 constexpr int64_t kValueMaxRows = 0xFFFFFFFFll;       // a chunk's count fits a uint32 bin, a row fits the low half of a top-k key
 constexpr int kValThreads = 256;                      // threads of the workgroups that walk a set of values (values.hip, quantiles.hip)
 constexpr int kValWaves = kValThreads / 64;
-constexpr int kValueAutoItems = 1024;                 // workgroups the automatic plan aims at (4 a CU)
-constexpr int64_t kValueMinChunk = 8192;              // rows of an automatic chunk at least
 constexpr int64_t kValueMaxScratchKeys = 1ll << 27;   // keys of vs_value_topk's per-chunk lists (1 GiB)
 constexpr uint32_t kValueNanF32 = 0x7FC00000u;        // the missing sentinels the calls WRITE (any NaN is read as missing)
 constexpr uint32_t kValueMissI32 = 0x80000000u;
@@ -76,13 +74,8 @@ inline int value_plan(int64_t n_rows, int32_t B, int32_t n_bins, bool per_query,
     ValuePlan p;
     p.qt = per_query ? qt_max : 1;
     const int64_t tiles = (B + p.qt - 1) / p.qt;
-    if (rows_per_chunk == 0) {
-        // enough workgroups to fill the chip, chunks long enough that zeroing and flushing the histograms stays a sixteenth of the bit tests
-        const int64_t want = std::max<int64_t>(1, kValueAutoItems / tiles);
-        const int64_t floor_rows = std::max<int64_t>(kValueMinChunk, (int64_t)16 * n_bins);
-        rows_per_chunk = std::max<int64_t>((n_rows + want - 1) / want, floor_rows);
-        rows_per_chunk = (rows_per_chunk + kSpanRows - 1) / kSpanRows * kSpanRows;
-    }
+    // enough workgroups to fill the chip, chunks long enough that zeroing and flushing the histograms stays a sixteenth of the bit tests
+    if (rows_per_chunk == 0) rows_per_chunk = auto_chunk(n_rows, tiles, std::max<int64_t>(kMinChunk, (int64_t)16 * n_bins));
     p.rows_per_chunk = rows_per_chunk;
     p.chunks = (n_rows + rows_per_chunk - 1) / rows_per_chunk;
     if (p.chunks > 0x7FFFFFFF || tiles > 65535)

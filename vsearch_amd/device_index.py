@@ -1426,12 +1426,21 @@ def value_range_bitmaps(values, lo, hi, bit0: int = 0, ld_words=None, device: in
     return out
 
 
-def _value_set(filter, n_rows, device):
-    """filter= of a value call -> None or a DocFilter on `device`"""
+def _doc_set(filter, n_rows, device):
+    """filter= of an aggregation -> None or a DocFilter on `device`"""
     if filter is None:
         return None
     from .doc_filter import as_doc_filter
     return as_doc_filter(filter, n_rows, device=device)
+
+
+_value_set = _doc_set                                  # (its name before every aggregation used it)
+
+
+def _set_args(f, bit0):
+    """the set of a raw call -> (B, (words, bit0, ld_words, B)): f None (every live row) or a DocFilter on the call's GPU, read from bit `bit0` on"""
+    B = f.n_queries if (f is not None and f.per_query) else 1
+    return B, (_ptr(f.words) if f is not None else None, int(bit0), f.ld if f is not None else 0, B)
 
 
 # ---- breakdowns: a numeric field's stats and histogram per facet label (vs_facet_value_stats, vs_facet_value_histogram) ---------------------
@@ -1883,6 +1892,240 @@ def _term_bitmaps(call, n_rows, n_cols, device, cols, thr, want_df=False, live_o
         nat.check(call(*args))
     return words, df
 
+
+# ---- aggregations, each written once over the parts of obj: a DeviceIndex is one part at row 0, a ShardGroup one part a shard ---------------------
+# A feature is a raw call (DeviceIndex._*_call), a merge rule (_add_parts, _merge_stats, torch.cat, _merge_value_topk) and a function below.
+def _lab(labels):
+    """a label column of _shard_parts: (conversion, kind, array)"""
+    return _labels_on, "labels", labels
+
+
+def _val(values):
+    """a value column of _shard_parts"""
+    return _values_on, "values", values
+
+
+def _shard_parts(obj, filter, columns, call, n_rows=None):
+    """call(shard, *its slices of the per-row columns, its filter, its first row) for every part of obj -> the parts' tuples on obj's GPU.
+    filter: filter= as given (resolved once, on obj's GPU; n_rows: obj.n_rows where the caller has it) -- a part's rows are bits [row0,
+    row0 + n) of it; columns: (conversion, kind, array) each (``_lab``, ``_val``).  A part on obj's GPU is returned as the call made it."""
+    dev = obj.device
+    f = None if filter is None else _doc_set(filter, obj.n_rows if n_rows is None else n_rows, dev)
+    out = []
+    for (sh, row0), *xs in zip(obj._parts, *[obj._slices(*c) for c in columns]):
+        part = call(sh, *xs, f if f is None else f.to(sh.device), row0)
+        out.append(part if sh.device == dev else tuple(t.to(f"cuda:{dev}") for t in part))
+    return out
+
+
+def _add_parts(parts):
+    """the parts' integer tensors (counts, sums, histograms) added field by field; one part is returned as it is"""
+    return parts[0] if len(parts) == 1 else tuple(sum(x[1:], x[0]) for x in zip(*parts))
+
+
+def _merge_stats(parts):
+    """the parts' (count, missing, min, max, *sums), [B] or [B, L] alike -> one: the integers added, min and max taken on the order keys (an
+    int32 value never passes through a float) among the parts whose count is not 0; one part is returned as it is"""
+    if len(parts) == 1:
+        return parts[0]
+    import torch
+    count, lo, hi = (torch.stack([p[i] for p in parts]) for i in (0, 2, 3))
+    has = count > 0
+    klo = torch.where(has, _value_keys(lo), torch.full_like(count, 1 << 32))
+    khi = torch.where(has, _value_keys(hi), torch.zeros_like(count))
+    added = _add_parts([p[:2] + p[4:] for p in parts])
+    return added[:2] + (lo.gather(0, klo.argmin(0, keepdim=True))[0], hi.gather(0, khi.argmax(0, keepdim=True))[0]) + added[2:]
+
+
+def _merge_value_topk(parts, k, descending):
+    """the shards' (ids, values) lists [B, k], each with its id offset -> the k best by (order key, id)"""
+    import torch
+    ids, vals = (torch.cat(x, dim=1) for x in zip(*parts))                          # [B, S * k]: ids ascend from shard to shard
+    key = _value_keys(vals)
+    key = torch.where(ids < 0, torch.full_like(key, -1), key if descending else 0xFFFFFFFF - key)
+    # a shard's list is in (key descending, id ascending) order and the shards' id ranges ascend: order by id first, then -- stably -- by key
+    by_id = torch.where(ids < 0, torch.full_like(ids, 1 << 62), ids).argsort(dim=1, stable=True)
+    order = by_id.gather(1, key.gather(1, by_id).argsort(dim=1, descending=True, stable=True))[:, :k]
+    return ids.gather(1, order), vals.gather(1, order)
+
+
+def _facet_sums(obj, labels, n_labels, filter, rows_per_chunk):
+    n = obj.n_rows
+    n_labels, rows_per_chunk = _facet_args(labels, n_labels, n, rows_per_chunk)
+    nat.require_device()
+    return _add_parts(_shard_parts(obj, filter, (_lab(labels),), lambda sh, l, f, row0: sh._facet_call(l, n_labels, f, row0, rows_per_chunk), n))
+
+
+def _facet_counts(obj, labels, n_labels, filter, rows_per_chunk):
+    return FacetCounts(*_facet_out(labels, *_facet_sums(obj, labels, n_labels, filter, rows_per_chunk)))
+
+
+def _top_facets(obj, labels, n_labels, topn, filter, min_count):
+    topn, min_count = _topn_args(topn, min_count)
+    counts, total, other = _facet_sums(obj, labels, n_labels, filter, 0)
+    top_l, top_c = facet_topn(counts, topn, min_count, device=obj.device)
+    return TopFacets(*_facet_out(labels, top_l, top_c, total, other))
+
+
+def _value_range_filter(obj, values, lo, hi):
+    import torch
+    from .doc_filter import DocFilter
+    n = obj.n_rows
+    dt, _ = _value_args(values, n)
+    l, _, scalar = _value_bounds(lo, hi, dt)
+    nat.require_device()
+    parts = _shard_parts(obj, None, (_val(values),), lambda sh, v, f, row0: (value_range_bitmaps(v, lo, hi, bit0=row0 & 31, device=sh.device),))
+    words = parts[0][0]
+    if len(parts) > 1:                                             # a part's words are zero below its first bit and past its last
+        words = torch.zeros((int(l.shape[0]), (n + 31) // 32), dtype=torch.int32, device=words.device)
+        for (part,), (_, row0) in zip(parts, obj._parts):
+            words[:, (row0 >> 5):(row0 >> 5) + part.shape[1]] |= part
+    return DocFilter(words[0] if scalar else words, n)
+
+
+def _value_stats(obj, values, filter, rows_per_chunk):
+    n = obj.n_rows
+    dt, rows_per_chunk = _value_args(values, n, rows_per_chunk)
+    nat.require_device()
+    parts = _shard_parts(obj, filter, (_val(values),), lambda sh, v, f, row0: sh._value_stats_call(v, dt, f, row0, rows_per_chunk), n)
+    return ValueStats(*_facet_out(values, *_merge_stats(parts)))
+
+
+def _value_histogram(obj, values, edges, filter, rows_per_chunk):
+    n = obj.n_rows
+    dt, rows_per_chunk = _value_args(values, n, rows_per_chunk)
+    e = _value_edges(edges, dt)
+    nat.require_device()
+    parts = _shard_parts(obj, filter, (_val(values),),
+                         lambda sh, v, f, row0: sh._value_hist_call(v, dt, _values_on(e, sh.device), f, row0, rows_per_chunk), n)
+    c, below, above, missing = _add_parts(parts)
+    return ValueHistogram(*_facet_out(values, c, below, above, missing, c.sum(1) + below + above + missing))
+
+
+def _value_topk(obj, values, k, descending, filter, id_offset, rows_per_chunk):
+    n = obj.n_rows
+    dt, rows_per_chunk = _value_args(values, n, rows_per_chunk)
+    k, descending = _value_topk_args(k, descending)
+    nat.require_device()
+    parts = _shard_parts(obj, filter, (_val(values),),
+                         lambda sh, v, f, row0: sh._value_topk_call(v, dt, k, descending, id_offset + row0, f, row0, rows_per_chunk), n)
+    return SortedResults(*_facet_out(values, *(parts[0] if len(parts) == 1 else _merge_value_topk(parts, k, descending))))
+
+
+def _facet_value_stats(obj, labels, n_labels, values, filter, rows_per_chunk):
+    n = obj.n_rows
+    n_labels, dt, rows_per_chunk, _ = _facet_value_args(labels, n_labels, values, n, rows_per_chunk)
+    nat.require_device()
+    parts = _shard_parts(obj, filter, (_lab(labels), _val(values)),
+                         lambda sh, l, v, f, row0: sh._facet_value_stats_call(l, n_labels, v, dt, f, row0, rows_per_chunk), n)
+    return FacetValueStats(*_facet_out(labels, *_merge_stats(parts)))
+
+
+def _facet_value_histogram(obj, labels, n_labels, values, edges, filter, rows_per_chunk):
+    n = obj.n_rows
+    n_labels, dt, rows_per_chunk, e = _facet_value_args(labels, n_labels, values, n, rows_per_chunk, edges)
+    nat.require_device()
+    parts = _shard_parts(obj, filter, (_lab(labels), _val(values)),
+                         lambda sh, l, v, f, row0: sh._facet_value_hist_call(l, n_labels, v, dt, _values_on(e, sh.device), f, row0, rows_per_chunk), n)
+    return FacetValueHistogram(*_facet_out(labels, *_add_parts(parts)))
+
+
+def _value_quantiles(obj, values, q, method, ranks, filter, rows_per_chunk):
+    """One part: the one call that runs the three levels on its GPU.  More: three rounds of level calls -- the parts' digit counts added on obj's
+    GPU, one step there picks each rank's bin and names the next level's slots."""
+    import torch
+    n = obj.n_rows
+    dt, rows_per_chunk = _value_args(values, n, rows_per_chunk)
+    qa, method, ra = _quantile_args(q, method, ranks)
+    nat.require_device()
+    dev = torch.device("cuda", obj.device)
+    f = _doc_set(filter, n, obj.device)
+    B = _set_args(f, 0)[0]
+    if ra is not None:
+        ra = _quantile_ranks_for(ra, B)
+    tdt = torch.float32 if dt == nat.VAL_F32 else torch.int32
+    up = lambda a: torch.from_numpy(a).to(dev) if a is not None else None
+    if len(obj._parts) == 1:
+        fused = lambda sh, v, fs, row0: _quantile_batches(
+            qa, ra, B, lambda qb, rb, R: sh._value_quantiles_call(v, dt, up(qb), method, up(rb), R, fs, row0, rows_per_chunk))
+        return ValueQuantiles(*_facet_out(values, *_shard_parts(obj, f, (_val(values),), fused, n)[0]))
+
+    def batch(qb, rb, R):
+        q_dev, r_dev = up(qb), up(rb)
+        state = missing = None
+        for level in range(nat.VALUE_RADIX_LEVELS):
+            def one(sh, v, fs, row0):
+                d = torch.device("cuda", sh.device)
+                sp, ns = (state["slot_prefix"].to(d), state["n_slots"].to(d)) if level else (None, None)
+                return sh._value_radix_counts_call(v, dt, level, R, sp, ns, fs, row0, rows_per_chunk)
+            counts, *rest = _add_parts(_shard_parts(obj, f, (_val(values),), one, n))
+            if level == 0:
+                missing = rest[0]
+            state = value_radix_step(level, counts, R, state, q_dev, method, r_dev, tdt, obj.device)
+        return state["values"], state["ranks"], state["count"], missing
+    return ValueQuantiles(*_facet_out(values, *_quantile_batches(qa, ra, B, batch)))
+
+
+def _term_agg(obj, spec, filter, ids, rows_per_chunk, extra=()):
+    """term_counts / term_sums: the set from `filter`, from `ids` or every live document -> spec.result on obj's GPU.  Every part takes its bit
+    range of the filter, or the ids with its first row as the id offset.  A host id list is checked by the library before it is staged (an
+    index) or here (a group, whose shards skip the ids they do not own).  extra: the arguments behind rows_per_chunk (term sums: tile_cols)."""
+    if ids is None:
+        nat.require_device()
+        return spec.result(*_add_parts(_shard_parts(obj, filter, (), lambda sh, f, row0: sh._term_set_call(spec, f, row0, rows_per_chunk, extra))))
+    import torch
+    group = isinstance(obj, ShardGroup)
+    ids = _term_ids(ids)
+    on_dev = _is_torch(ids) and ids.is_cuda
+    t = ids if _is_torch(ids) else torch.from_numpy(np.ascontiguousarray(ids))
+    if group and not on_dev and t.numel() and (int(t.min()) < -1 or int(t.max()) >= obj.n_rows):
+        raise ValueError(f"an id lies outside [-1, {obj.n_rows})")
+    nat.require_device()
+    if not group and not on_dev:
+        h = np.ascontiguousarray(_host(ids))
+        B, m, V = h.shape[0], h.shape[1], obj._n_cols()
+        out, total = np.empty((B, V), dtype=np.int64), np.empty(B, dtype=np.int64)
+        nat.check(getattr(nat.lib(), spec.ids)(obj._h, _ptr(h), B, m, m, 0, 1, *extra, _ptr(out), V, _ptr(total), None))
+        dev = torch.device("cuda", obj.device)
+        return spec.result(torch.from_numpy(out).to(dev), torch.from_numpy(total).to(dev))
+
+    def one(sh, f, row0):
+        ts = t.to(torch.device("cuda", sh.device))
+        rows_ok = not group and ts.stride(1) == 1 and ts.stride(0) >= ts.shape[1]   # (an index reads a column slice of a wider hit list in place)
+        return sh._term_ids_call(spec, ts if rows_ok else ts.contiguous(), row0, not group, extra)
+    return spec.result(*_add_parts(_shard_parts(obj, None, (), one)))
+
+
+def _term_counts(obj, filter, ids, rows_per_chunk):
+    if filter is not None and ids is not None:
+        raise ValueError("the set is given by `filter` or by `ids`, not both")
+    return _term_agg(obj, _TERM_COUNTS, filter, ids, _rows_per_chunk_arg(rows_per_chunk))
+
+
+def _term_sums(obj, filter, ids, rows_per_chunk, tile_cols):
+    if filter is not None and ids is not None:
+        raise ValueError("the set is given by `filter` or by `ids`, not both")
+    rows_per_chunk, tile_cols = _term_sum_args(rows_per_chunk, tile_cols)
+    return _term_agg(obj, _TERM_SUMS, filter, ids, rows_per_chunk, (tile_cols,))
+
+
+def _assign(obj, centroids, bias, filter, rows_per_chunk):
+    c, b, rows_per_chunk = _assign_args(centroids, bias, _n_cols_of(obj), rows_per_chunk)
+    import torch
+    nat.require_device()
+    n = None if filter is None else obj.n_rows
+    f = _doc_set(filter, n, obj.device)
+    if f is not None and f.per_query:
+        raise ValueError("assign takes ONE document set, not a per-query filter")
+
+    def one(sh, fs, row0):
+        sdev = torch.device("cuda", sh.device)
+        with torch.cuda.device(sdev):                              # (a shard of a group runs with its GPU current)
+            return sh._assign_call(c.to(sdev).contiguous(), b.to(sdev).contiguous() if b is not None else None, fs, row0, rows_per_chunk)
+    parts = _shard_parts(obj, f, (), one, n)
+    return Assignment(*(parts[0] if len(parts) == 1 else (torch.cat(x) for x in zip(*parts))))
+
+
 class DeviceIndex:
     """Owner of one device-resident index shard (CSR packets or dense)."""
 
@@ -1895,6 +2138,15 @@ class DeviceIndex:
         if self._device is None:
             self._device = int(self.info().device)
         return self._device
+
+    @property
+    def _parts(self):
+        """(shard, its first row) of every part an aggregation runs over: an index is one part at row 0"""
+        return ((self, 0),)
+
+    def _slices(self, on, kind, x):
+        """every part's slice of a per-row column, made a tensor on its GPU by `on` (_labels_on | _values_on)"""
+        return (on(x, self.device),)
 
     # ---- constructors -------------------------------------------------------------------------
     @classmethod
@@ -2353,24 +2605,13 @@ class DeviceIndex:
         tensors.  labels_dev: int32 CUDA tensor [n_rows] on this index's device; f: None or a DocFilter there, read from bit `bit0` on."""
         import torch
         dev = torch.device("cuda", self.device)
-        B = f.n_queries if (f is not None and f.per_query) else 1
+        B, set_args = _set_args(f, bit0)
         counts = torch.empty((B, n_labels), dtype=torch.int64, device=dev)
         total = torch.empty(B, dtype=torch.int64, device=dev)
         other = torch.empty(B, dtype=torch.int64, device=dev)
-        nat.check(nat.lib().vs_index_facet_counts(self._h, _ptr(f.words) if f is not None else None, int(bit0), f.ld if f is not None else 0, B,
-                                                  _ptr(labels_dev), n_labels, rows_per_chunk, _ptr(counts), n_labels, _ptr(total), _ptr(other),
-                                                  current_stream(self.device)))
+        nat.check(nat.lib().vs_index_facet_counts(self._h, *set_args, _ptr(labels_dev), n_labels, rows_per_chunk, _ptr(counts), n_labels,
+                                                  _ptr(total), _ptr(other), current_stream(self.device)))
         return counts, total, other
-
-    def _facets(self, labels, n_labels, filter, rows_per_chunk):
-        n = self.n_rows
-        n_labels, rows_per_chunk = _facet_args(labels, n_labels, n, rows_per_chunk)
-        nat.require_device()
-        f = None
-        if filter is not None:
-            from .doc_filter import as_doc_filter
-            f = as_doc_filter(filter, n, device=self.device)
-        return self._facet_call(_labels_on(labels, self.device), n_labels, f, 0, rows_per_chunk)
 
     def facet_counts(self, labels, n_labels: int, filter=None, rows_per_chunk: int = 0) -> FacetCounts:
         """How a document set spreads over per-document labels -> FacetCounts(counts [B, n_labels], total [B], other [B]), int64.  labels:
@@ -2379,27 +2620,20 @@ class DeviceIndex:
         gives one row per query, a shared one B = 1, None every live document.  Deleted documents never count.  rows_per_chunk: 0 =
         automatic, else a multiple of 64 (a tuning knob: the result does not depend on it).  numpy labels -> numpy out; tensor labels ->
         tensors on the index's device, enqueued on torch's current stream."""
-        return FacetCounts(*_facet_out(labels, *self._facets(labels, n_labels, filter, rows_per_chunk)))
+        return _facet_counts(self, labels, n_labels, filter, rows_per_chunk)
 
     def top_facets(self, labels, n_labels: int, topn: int, filter=None, min_count: int = 1) -> TopFacets:
         """facet_counts, then per query the `topn` labels with the most documents (vs_facet_topn): count descending, label ascending, only
         labels with at least max(min_count, 1) documents; unused slots label -1 / count 0.  topn in 1..1024."""
-        topn, min_count = _topn_args(topn, min_count)
-        counts, total, other = self._facets(labels, n_labels, filter, 0)
-        top_l, top_c = facet_topn(counts, topn, min_count, device=self.device)
-        return TopFacets(*_facet_out(labels, top_l, top_c, total, other))
+        return _top_facets(self, labels, n_labels, topn, filter, min_count)
 
     # ---- numeric fields: range filters, stats, histograms and sort by value (vs_index_value_stats / _histogram / _topk) --------------------
-    def _value_set_args(self, f, bit0):
-        B = f.n_queries if (f is not None and f.per_query) else 1
-        return B, (_ptr(f.words) if f is not None else None, int(bit0), f.ld if f is not None else 0, B)
-
     def _value_stats_call(self, vals_dev, dt, f, bit0, rows_per_chunk):
         """One vs_index_value_stats call on device buffers and torch's current stream -> (count, missing, min, max, sum) CUDA tensors [B].
         vals_dev: float32 / int32 CUDA tensor [n_rows] on this index's device; f: None or a DocFilter there, read from bit `bit0` on."""
         import torch
         dev = torch.device("cuda", self.device)
-        B, set_args = self._value_set_args(f, bit0)
+        B, set_args = _set_args(f, bit0)
         count, missing, total = (torch.empty(B, dtype=torch.int64, device=dev) for _ in range(3))
         lo, hi = (torch.empty(B, dtype=vals_dev.dtype, device=dev) for _ in range(2))
         nat.check(nat.lib().vs_index_value_stats(self._h, *set_args, _ptr(vals_dev), dt, rows_per_chunk, _ptr(count), _ptr(missing), _ptr(lo),
@@ -2410,7 +2644,7 @@ class DeviceIndex:
         """One vs_index_value_histogram call -> (counts [B, E - 1], below, above, missing [B]) int64 CUDA tensors"""
         import torch
         dev = torch.device("cuda", self.device)
-        B, set_args = self._value_set_args(f, bit0)
+        B, set_args = _set_args(f, bit0)
         E = int(edges_dev.shape[0])
         counts = torch.empty((B, E - 1), dtype=torch.int64, device=dev)
         below, above, missing = (torch.empty(B, dtype=torch.int64, device=dev) for _ in range(3))
@@ -2422,7 +2656,7 @@ class DeviceIndex:
         """One vs_index_value_topk call -> (ids int64 [B, k], values [B, k]) CUDA tensors"""
         import torch
         dev = torch.device("cuda", self.device)
-        B, set_args = self._value_set_args(f, bit0)
+        B, set_args = _set_args(f, bit0)
         ids = torch.empty((B, k), dtype=torch.int64, device=dev)
         vals = torch.empty((B, k), dtype=vals_dev.dtype, device=dev)
         nat.check(nat.lib().vs_index_value_topk(self._h, *set_args, _ptr(vals_dev), dt, k, descending, int(id_offset), rows_per_chunk, _ptr(ids),
@@ -2433,47 +2667,25 @@ class DeviceIndex:
         """The documents whose value lies in [lo, hi], both ends inclusive, as a DocFilter on the index's device (vs_value_range_bitmaps): for
         ``search(filter=)`` and for ``&``, ``|``, ``~`` with any other filter.  values: float32 / int32 [n_rows] (``value_column`` converts);
         None is an open end; sequences of B bounds give a per-query filter.  A document without a value never matches."""
-        from .doc_filter import DocFilter
-        n = self.n_rows
-        dt, _ = _value_args(values, n)
-        _, _, scalar = _value_bounds(lo, hi, dt)
-        nat.require_device()
-        words = value_range_bitmaps(_values_on(values, self.device), lo, hi, device=self.device)
-        return DocFilter(words[0] if scalar else words, n)
+        return _value_range_filter(self, values, lo, hi)
 
     def value_stats(self, values, filter=None, rows_per_chunk: int = 0) -> ValueStats:
         """Count, missing, min, max and sum of a numeric field over a document set -> ValueStats, one entry per query.  values: float32 /
         int32 [n_rows] (numpy, or a tensor -- one on the index's GPU is read in place).  filter: what search(filter=) accepts -- a per-query
         DocFilter gives one entry per query, a shared one B = 1, None every live document.  Deleted documents never count.  numpy values ->
         numpy out; tensor values -> tensors on the index's device, enqueued on torch's current stream."""
-        n = self.n_rows
-        dt, rows_per_chunk = _value_args(values, n, rows_per_chunk)
-        nat.require_device()
-        f = _value_set(filter, n, self.device)
-        return ValueStats(*_facet_out(values, *self._value_stats_call(_values_on(values, self.device), dt, f, 0, rows_per_chunk)))
+        return _value_stats(self, values, filter, rows_per_chunk)
 
     def value_histogram(self, values, edges, filter=None, rows_per_chunk: int = 0) -> ValueHistogram:
         """How a document set spreads over the bins [edges[i], edges[i + 1]) of a numeric field -> ValueHistogram(counts [B, E - 1], below,
         above, missing, total), int64.  edges: 2..1025 strictly ascending numbers.  values, filter, outputs as in ``value_stats``."""
-        n = self.n_rows
-        dt, rows_per_chunk = _value_args(values, n, rows_per_chunk)
-        e = _value_edges(edges, dt)
-        nat.require_device()
-        f = _value_set(filter, n, self.device)
-        c, below, above, missing = self._value_hist_call(_values_on(values, self.device), dt, _values_on(e, self.device), f, 0, rows_per_chunk)
-        return ValueHistogram(*_facet_out(values, c, below, above, missing, c.sum(1) + below + above + missing))
+        return _value_histogram(self, values, edges, filter, rows_per_chunk)
 
     def value_topk(self, values, k: int, descending: bool = True, filter=None, id_offset: int = 0, rows_per_chunk: int = 0) -> SortedResults:
         """Per query the k documents of the set with the largest (descending) or smallest values of a numeric field, ties by id ascending ->
         SortedResults(ids [B, k], values [B, k]); documents without a value are never listed; id -1 / the missing sentinel behind the last.
         k in 1..1024.  values, filter, outputs as in ``value_stats``."""
-        n = self.n_rows
-        dt, rows_per_chunk = _value_args(values, n, rows_per_chunk)
-        k, descending = _value_topk_args(k, descending)
-        nat.require_device()
-        f = _value_set(filter, n, self.device)
-        return SortedResults(*_facet_out(values, *self._value_topk_call(_values_on(values, self.device), dt, k, descending, id_offset, f, 0,
-                                                                        rows_per_chunk)))
+        return _value_topk(self, values, k, descending, filter, id_offset, rows_per_chunk)
 
     # ---- breakdowns: a numeric field by facet label (vs_index_facet_value_stats / _histogram) --------------------------------------------------
     def _facet_value_stats_call(self, labels_dev, n_labels, vals_dev, dt, f, bit0, rows_per_chunk):
@@ -2482,7 +2694,7 @@ class DeviceIndex:
         DocFilter there, read from bit `bit0` on."""
         import torch
         dev = torch.device("cuda", self.device)
-        B, set_args = self._value_set_args(f, bit0)
+        B, set_args = _set_args(f, bit0)
         count, missing, total_sum = (torch.empty((B, n_labels), dtype=torch.int64, device=dev) for _ in range(3))
         lo, hi = (torch.empty((B, n_labels), dtype=vals_dev.dtype, device=dev) for _ in range(2))
         total, other = (torch.empty(B, dtype=torch.int64, device=dev) for _ in range(2))
@@ -2495,7 +2707,7 @@ class DeviceIndex:
         """One vs_index_facet_value_histogram call -> (counts [B, L, E - 1], below, above, missing [B, L], total, other [B]) int64 CUDA tensors"""
         import torch
         dev = torch.device("cuda", self.device)
-        B, set_args = self._value_set_args(f, bit0)
+        B, set_args = _set_args(f, bit0)
         E = int(edges_dev.shape[0])
         counts = torch.empty((B, n_labels, E - 1), dtype=torch.int64, device=dev)
         below, above, missing = (torch.empty((B, n_labels), dtype=torch.int64, device=dev) for _ in range(3))
@@ -2510,24 +2722,13 @@ class DeviceIndex:
         [B, n_labels], total / other [B]); ``.mean()`` in fp64.  labels as in ``facet_counts`` (a label outside [0, n_labels) counts into
         `other` and nothing else), values as in ``value_stats``; filter: what search(filter=) accepts.  Deleted documents never count.
         numpy in -> numpy out; tensors in -> tensors on the index's device, enqueued on torch's current stream."""
-        n = self.n_rows
-        n_labels, dt, rows_per_chunk, _ = _facet_value_args(labels, n_labels, values, n, rows_per_chunk)
-        nat.require_device()
-        f = _value_set(filter, n, self.device)
-        return FacetValueStats(*_facet_out(labels, *self._facet_value_stats_call(_labels_on(labels, self.device), n_labels,
-                                                                                 _values_on(values, self.device), dt, f, 0, rows_per_chunk)))
+        return _facet_value_stats(self, labels, n_labels, values, filter, rows_per_chunk)
 
     def facet_value_histogram(self, labels, n_labels: int, values, edges, filter=None, rows_per_chunk: int = 0) -> FacetValueHistogram:
         """How the documents of each facet label spread over the bins [edges[i], edges[i + 1]) of a numeric field, over a document set, in one
         pass (a cross-tab) -> FacetValueHistogram(counts [B, n_labels, E - 1], below, above, missing [B, n_labels], total, other [B]).
         edges: 2..1025 strictly ascending numbers, n_labels x (E + 2) <= 2^22.  labels, values, filter, outputs as in ``facet_value_stats``."""
-        n = self.n_rows
-        n_labels, dt, rows_per_chunk, e = _facet_value_args(labels, n_labels, values, n, rows_per_chunk, edges)
-        nat.require_device()
-        f = _value_set(filter, n, self.device)
-        return FacetValueHistogram(*_facet_out(labels, *self._facet_value_hist_call(_labels_on(labels, self.device), n_labels,
-                                                                                    _values_on(values, self.device), dt, _values_on(e, self.device),
-                                                                                    f, 0, rows_per_chunk)))
+        return _facet_value_histogram(self, labels, n_labels, values, edges, filter, rows_per_chunk)
 
     # ---- percentiles (vs_index_value_quantiles, vs_index_value_radix_counts) ------------------------------------------------------------------
     def _value_quantiles_call(self, vals_dev, dt, q_dev, method, ranks_dev, R, f, bit0, rows_per_chunk):
@@ -2535,7 +2736,7 @@ class DeviceIndex:
         q_dev: float64 [R] or None; ranks_dev: int64 [B, R] or None."""
         import torch
         dev = torch.device("cuda", self.device)
-        B, set_args = self._value_set_args(f, bit0)
+        B, set_args = _set_args(f, bit0)
         vals = torch.empty((B, R), dtype=vals_dev.dtype, device=dev)
         ranks = torch.empty((B, R), dtype=torch.int64, device=dev)
         count, missing = (torch.empty(B, dtype=torch.int64, device=dev) for _ in range(2))
@@ -2549,7 +2750,7 @@ class DeviceIndex:
         slot_prefix int32 [B, R] / n_slots int32 [B]: the state of the step above, on this index's device (None at level 0)."""
         import torch
         dev = torch.device("cuda", self.device)
-        B, set_args = self._value_set_args(f, bit0)
+        B, set_args = _set_args(f, bit0)
         bins = nat.VALUE_RADIX_BINS if level < 2 else nat.VALUE_RADIX_BINS // 2
         counts = torch.empty((B, 1 if level == 0 else R, bins), dtype=torch.int64, device=dev)
         missing = torch.empty(B, dtype=torch.int64, device=dev) if level == 0 else None
@@ -2564,20 +2765,7 @@ class DeviceIndex:
         or "nearest" (half to even); or ranks: 0-based ascending ranks, [R] or [B, R].  A rank outside the set's values gives the missing
         sentinel and rank -1.  No interpolation, no sort: three counting passes over the set.  More than 16 ranks are served in batches of
         16.  values, filter, outputs as in ``value_stats``."""
-        import torch
-        n = self.n_rows
-        dt, rows_per_chunk = _value_args(values, n, rows_per_chunk)
-        qa, method, ra = _quantile_args(q, method, ranks)
-        nat.require_device()
-        f = _value_set(filter, n, self.device)
-        B = f.n_queries if (f is not None and f.per_query) else 1
-        if ra is not None:
-            ra = _quantile_ranks_for(ra, B)
-        v = _values_on(values, self.device)
-        dev = torch.device("cuda", self.device)
-        call = lambda qb, rb, R: self._value_quantiles_call(v, dt, torch.from_numpy(qb).to(dev) if qb is not None else None, method,
-                                                            torch.from_numpy(rb).to(dev) if rb is not None else None, R, f, 0, rows_per_chunk)
-        return ValueQuantiles(*_facet_out(values, *_quantile_batches(qa, ra, B, call)))
+        return _value_quantiles(self, values, q, method, ranks, filter, rows_per_chunk)
 
     # ---- term aggregations: what a document set is about (vs_index_term_counts, vs_index_term_counts_ids) ---------------------------------
     def _term_set_call(self, spec, f, bit0, rows_per_chunk, extra=()):
@@ -2585,11 +2773,11 @@ class DeviceIndex:
         CUDA tensors.  f: None or a DocFilter on this index's device, read from bit `bit0` on; extra: the arguments behind rows_per_chunk."""
         import torch
         dev = torch.device("cuda", self.device)
-        B, V = (f.n_queries if (f is not None and f.per_query) else 1), self._n_cols()
+        (B, set_args), V = _set_args(f, bit0), self._n_cols()
         out = torch.empty((B, V), dtype=torch.int64, device=dev)
         total = torch.empty(B, dtype=torch.int64, device=dev)
-        nat.check(getattr(nat.lib(), spec.bitmap)(self._h, _ptr(f.words) if f is not None else None, int(bit0), f.ld if f is not None else 0, B,
-                                                  int(rows_per_chunk), *extra, _ptr(out), V, _ptr(total), current_stream(self.device)))
+        nat.check(getattr(nat.lib(), spec.bitmap)(self._h, *set_args, int(rows_per_chunk), *extra, _ptr(out), V, _ptr(total),
+                                                  current_stream(self.device)))
         return out, total
 
     def _term_ids_call(self, spec, ids_dev, id_offset, strict, extra=()):
@@ -2614,30 +2802,6 @@ class DeviceIndex:
     def _term_sums_ids_call(self, ids_dev, id_offset, strict, tile_cols):
         return self._term_ids_call(_TERM_SUMS, ids_dev, id_offset, strict, (int(tile_cols),))
 
-    def _term_agg(self, spec, filter, ids, rows_per_chunk, extra=()):
-        """term_counts / term_sums: the set from `filter`, from `ids` (a host list is checked by the library before it is staged) or every live
-        document -> spec.result on the index's device.  extra: the arguments behind rows_per_chunk (term sums: tile_cols)."""
-        import torch
-        if ids is not None:
-            ids = _term_ids(ids)
-            nat.require_device()
-            dev = torch.device("cuda", self.device)
-            if _is_torch(ids) and ids.is_cuda:
-                t = ids.to(dev)
-                rows_ok = t.stride(1) == 1 and t.stride(0) >= t.shape[1]       # (a column slice of a wider hit list is read in place)
-                return spec.result(*self._term_ids_call(spec, t if rows_ok else t.contiguous(), 0, True, extra))
-            h = np.ascontiguousarray(_host(ids))
-            B, m, V = h.shape[0], h.shape[1], self._n_cols()
-            out, total = np.empty((B, V), dtype=np.int64), np.empty(B, dtype=np.int64)
-            nat.check(getattr(nat.lib(), spec.ids)(self._h, _ptr(h), B, m, m, 0, 1, *extra, _ptr(out), V, _ptr(total), None))
-            return spec.result(torch.from_numpy(out).to(dev), torch.from_numpy(total).to(dev))
-        nat.require_device()
-        f = None
-        if filter is not None:
-            from .doc_filter import as_doc_filter
-            f = as_doc_filter(filter, self.n_rows, device=self.device)
-        return spec.result(*self._term_set_call(spec, f, 0, rows_per_chunk, extra))
-
     def term_counts(self, filter=None, ids=None, rows_per_chunk: int = 0) -> TermCounts:
         """For a document set, how many of its documents have each vocabulary column -> TermCounts(counts [B, V], total [B]), int64 tensors
         on the index's device, enqueued on torch's current stream.  A document has a column iff it stores it with a non-zero value (the
@@ -2646,9 +2810,7 @@ class DeviceIndex:
         twice counts twice, an id outside the index raises ValueError when the list is on the host and is skipped when it is on the
         device); neither: every live document (the document frequency of all columns in one pass).  Deleted documents never count.
         rows_per_chunk: 0 = automatic, else a multiple of 64 (a tuning knob: the result does not depend on it)."""
-        if filter is not None and ids is not None:
-            raise ValueError("the set is given by `filter` or by `ids`, not both")
-        return self._term_agg(_TERM_COUNTS, filter, ids, _rows_per_chunk_arg(rows_per_chunk))
+        return _term_counts(self, filter, ids, rows_per_chunk)
 
     def top_terms(self, filter=None, ids=None, topn: int = 20, method: str = "jlh", min_count: int = 1, background=None) -> TopTerms:
         """term_counts of the set, then per query its `topn` most significant columns against a background (vs_term_topn; see
@@ -2667,10 +2829,7 @@ class DeviceIndex:
         on the host and is skipped when it is on the device), or neither: every live document.  Deleted documents never contribute.
         rows_per_chunk: 0 = automatic, else a multiple of 64; tile_cols: 0 = automatic, else the columns of a workgroup's tile, at most
         18 432 (tuning knobs: the result does not depend on them)."""
-        if filter is not None and ids is not None:
-            raise ValueError("the set is given by `filter` or by `ids`, not both")
-        rows_per_chunk, tile_cols = _term_sum_args(rows_per_chunk, tile_cols)
-        return self._term_agg(_TERM_SUMS, filter, ids, rows_per_chunk, (tile_cols,))
+        return _term_sums(self, filter, ids, rows_per_chunk, tile_cols)
 
     def top_weight_terms(self, filter=None, ids=None, topn: int = 20, min_count: int = 0) -> TopWeights:
         """term_sums of the set, then per query the `topn` columns with the largest mean weight (vs_term_sum_topn; see ``term_sum_topn``):
@@ -2703,17 +2862,7 @@ class DeviceIndex:
         rounded once to fp32; ties go to the lowest j.  bias = -``half_norms(centroids)`` makes it the nearest centroid in the Euclidean
         sense.  A deleted or filtered-out document gets -1 / -inf.  filter: ONE set (a DocFilter, a bool mask [N] or ids).  One pass over the
         index: no [K, N] matrix is formed.  rows_per_chunk: 0 = automatic, else a multiple of 64 (a tuning knob)."""
-        c, b, rows_per_chunk = _assign_args(centroids, bias, self._n_cols(), rows_per_chunk)
-        import torch
-        nat.require_device()
-        dev = torch.device("cuda", self.device)
-        f = None
-        if filter is not None:
-            from .doc_filter import as_doc_filter
-            f = as_doc_filter(filter, self.n_rows, device=self.device)
-            if f.per_query:
-                raise ValueError("assign takes ONE document set, not a per-query filter")
-        return Assignment(*self._assign_call(c.to(dev).contiguous(), b.to(dev).contiguous() if b is not None else None, f, 0, rows_per_chunk))
+        return _assign(self, centroids, bias, filter, rows_per_chunk)
 
     def half_norms(self, centroids):
         """float32(0.5 * ||c'_j||^2) per centroid, c' rounded to the index dtype (``centroid_half_norms``) -> float32 [K] on the index's device"""
@@ -2773,6 +2922,30 @@ class ShardGroup:
     def device(self) -> int:
         """the first shard's GPU: where the group's results land"""
         return self._shards[0].device
+
+    @property
+    def _parts(self):
+        """(shard, its first row) of every part an aggregation runs over"""
+        parts, row0 = [], 0
+        for sh in self._shards:
+            parts.append((sh, row0))
+            row0 += sh.n_rows
+        return parts
+
+    def _slices(self, on, kind, x):
+        """every shard's slice of a per-row column (kind: "labels" | "values"), made a tensor on its GPU by `on`; cached per kind and tensor
+        (and its version: an in-place edit drops it)"""
+        key = (id(x), getattr(x, "_version", None), tuple(x.shape))
+        cache = self.__dict__.setdefault("_slice_cache", {})
+        cached = cache.get(kind)
+        if cached is not None and cached[0] == key and cached[1] is x:
+            return cached[2]
+        parts = self._parts
+        ends = [row0 for _, row0 in parts[1:]] + [None]
+        slices = [on(x[row0:end], sh.device) for (sh, row0), end in zip(parts, ends)]
+        if _is_torch(x):                                         # (a numpy array has no version to tell an in-place edit by)
+            cache[kind] = (key, x, slices)
+        return slices
 
     def search(self, q, k: int, filter=None):
         """filter: as DeviceIndex.search, over the GROUP's rows (global ids); every shard reads its own row range of it."""
@@ -2955,249 +3128,57 @@ class ShardGroup:
         return DocFilter(_range_shards(self, q, min_score, 0, filter, True)[3], self.n_rows)
 
     # ---- facet counts -----------------------------------------------------------------------------------------------------------------------
-    def _facet_slices(self, labels):
-        """every shard's slice of the labels as an int32 tensor on its GPU, cached per label tensor (and its version: an in-place edit drops it)"""
-        key = (id(labels), getattr(labels, "_version", None), tuple(labels.shape))
-        cached = getattr(self, "_facet_cache", None)
-        if cached is not None and cached[0] == key and cached[1] is labels:
-            return cached[2]
-        slices, row0 = [], 0
-        for sh in self._shards:
-            n = sh.n_rows
-            slices.append(_labels_on(labels[row0:row0 + n], sh.device))
-            row0 += n
-        if _is_torch(labels):                                    # (a numpy array has no version to tell an in-place edit by)
-            self._facet_cache = (key, labels, slices)
-        return slices
-
-    def _facets(self, labels, n_labels, filter, rows_per_chunk):
-        import torch
-        n_total = self.n_rows
-        n_labels, rows_per_chunk = _facet_args(labels, n_labels, n_total, rows_per_chunk)
-        nat.require_device()
-        dev0 = torch.device("cuda", self.device)
-        f = None
-        if filter is not None:
-            from .doc_filter import as_doc_filter
-            f = as_doc_filter(filter, n_total, device=dev0)
-        out, row0 = None, 0
-        for sh, lab in zip(self._shards, self._facet_slices(labels)):
-            fs = f.to(torch.device("cuda", sh.device)) if f is not None else None
-            part = sh._facet_call(lab, n_labels, fs, row0, rows_per_chunk)          # its rows are bits [row0, row0 + n) of the filter
-            part = tuple(t.to(dev0) for t in part)
-            out = part if out is None else tuple(a + b for a, b in zip(out, part))
-            row0 += sh.n_rows
-        return out
-
     def facet_counts(self, labels, n_labels: int, filter=None, rows_per_chunk: int = 0) -> FacetCounts:
         """DeviceIndex.facet_counts over the group's rows: labels and filter are global; every shard counts its own rows with its slice of
         the labels on its own GPU, the counts are summed on the first shard's GPU.  Equal to the unsharded index exactly."""
-        return FacetCounts(*_facet_out(labels, *self._facets(labels, n_labels, filter, rows_per_chunk)))
+        return _facet_counts(self, labels, n_labels, filter, rows_per_chunk)
 
     def top_facets(self, labels, n_labels: int, topn: int, filter=None, min_count: int = 1) -> TopFacets:
         """DeviceIndex.top_facets over the group's rows: the top-n is taken after the shards' counts are summed, never per shard."""
-        topn, min_count = _topn_args(topn, min_count)
-        counts, total, other = self._facets(labels, n_labels, filter, 0)
-        top_l, top_c = facet_topn(counts, topn, min_count, device=self.device)
-        return TopFacets(*_facet_out(labels, top_l, top_c, total, other))
+        return _top_facets(self, labels, n_labels, topn, filter, min_count)
 
     # ---- numeric fields -----------------------------------------------------------------------------------------------------------------------
-    def _value_slices(self, values):
-        """every shard's slice of the values as a tensor on its GPU, cached per value tensor (and its version: an in-place edit drops it)"""
-        key = (id(values), getattr(values, "_version", None), tuple(values.shape))
-        cached = getattr(self, "_value_cache", None)
-        if cached is not None and cached[0] == key and cached[1] is values:
-            return cached[2]
-        slices, row0 = [], 0
-        for sh in self._shards:
-            n = sh.n_rows
-            slices.append(_values_on(values[row0:row0 + n], sh.device))
-            row0 += n
-        if _is_torch(values):                                    # (a numpy array has no version to tell an in-place edit by)
-            self._value_cache = (key, values, slices)
-        return slices
-
-    def _value_parts(self, values, filter, call):
-        """call(shard, its slice of the values, its filter, its first row) for every shard -> the results, moved to the first shard's GPU"""
-        import torch
-        dev0 = torch.device("cuda", self.device)
-        f = _value_set(filter, self.n_rows, dev0)
-        parts, row0 = [], 0
-        for sh, vals in zip(self._shards, self._value_slices(values)):
-            fs = f.to(torch.device("cuda", sh.device)) if f is not None else None
-            parts.append(tuple(t.to(dev0) for t in call(sh, vals, fs, row0)))      # its rows are bits [row0, row0 + n) of the filter
-            row0 += sh.n_rows
-        return parts
-
     def value_range_filter(self, values, lo=None, hi=None):
         """DeviceIndex.value_range_filter over the group's rows: every shard writes the bits of its slice of the values at its bit offset of
         one bitmap on the first shard's GPU."""
-        import torch
-        from .doc_filter import DocFilter
-        n = self.n_rows
-        dt, _ = _value_args(values, n)
-        l, h, scalar = _value_bounds(lo, hi, dt)
-        nat.require_device()
-        dev0 = torch.device("cuda", self.device)
-        W = (n + 31) // 32
-        words, row0 = torch.zeros((int(l.shape[0]), W), dtype=torch.int32, device=dev0), 0
-        for sh, vals in zip(self._shards, self._value_slices(values)):
-            part = value_range_bitmaps(vals, l, h, bit0=row0 & 31, device=sh.device).to(dev0)      # zero below its first bit and past its last
-            w0 = row0 >> 5
-            words[:, w0:w0 + part.shape[1]] |= part
-            row0 += sh.n_rows
-        return DocFilter(words[0] if scalar else words, n)
+        return _value_range_filter(self, values, lo, hi)
 
     def value_stats(self, values, filter=None, rows_per_chunk: int = 0) -> ValueStats:
         """DeviceIndex.value_stats over the group's rows: values and filter are global; counts and sums are added, min and max combined on
         the order keys (an int32 value never passes through a float).  Equal to the unsharded index exactly."""
-        import torch
-        dt, rows_per_chunk = _value_args(values, self.n_rows, rows_per_chunk)
-        nat.require_device()
-        parts = self._value_parts(values, filter, lambda sh, v, f, row0: sh._value_stats_call(v, dt, f, row0, rows_per_chunk))
-        count, missing, lo, hi, total = (torch.stack(x) for x in zip(*parts))      # [S, B]
-        has = count > 0
-        klo = torch.where(has, _value_keys(lo), torch.full_like(count, 1 << 32))
-        khi = torch.where(has, _value_keys(hi), torch.zeros_like(count))
-        lo = lo.gather(0, klo.argmin(0, keepdim=True))[0]
-        hi = hi.gather(0, khi.argmax(0, keepdim=True))[0]
-        return ValueStats(*_facet_out(values, count.sum(0), missing.sum(0), lo, hi, total.sum(0)))
+        return _value_stats(self, values, filter, rows_per_chunk)
 
     def value_histogram(self, values, edges, filter=None, rows_per_chunk: int = 0) -> ValueHistogram:
         """DeviceIndex.value_histogram over the group's rows: the shards' bins are added on the first shard's GPU."""
-        dt, rows_per_chunk = _value_args(values, self.n_rows, rows_per_chunk)
-        e = _value_edges(edges, dt)
-        nat.require_device()
-        parts = self._value_parts(values, filter,
-                                  lambda sh, v, f, row0: sh._value_hist_call(v, dt, _values_on(e, sh.device), f, row0, rows_per_chunk))
-        c, below, above, missing = (sum(x[1:], x[0]) for x in zip(*parts))
-        return ValueHistogram(*_facet_out(values, c, below, above, missing, c.sum(1) + below + above + missing))
+        return _value_histogram(self, values, edges, filter, rows_per_chunk)
 
     # ---- breakdowns -----------------------------------------------------------------------------------------------------------------------------
-    def _facet_value_parts(self, labels, values, filter, call):
-        """call(shard, its labels, its values, its filter, its first row) for every shard -> the results, moved to the first shard's GPU"""
-        import torch
-        dev0 = torch.device("cuda", self.device)
-        f = _value_set(filter, self.n_rows, dev0)
-        parts, row0 = [], 0
-        for sh, lab, vals in zip(self._shards, self._facet_slices(labels), self._value_slices(values)):
-            fs = f.to(torch.device("cuda", sh.device)) if f is not None else None
-            parts.append(tuple(t.to(dev0) for t in call(sh, lab, vals, fs, row0)))  # its rows are bits [row0, row0 + n) of the filter
-            row0 += sh.n_rows
-        return parts
-
     def facet_value_stats(self, labels, n_labels: int, values, filter=None, rows_per_chunk: int = 0) -> FacetValueStats:
         """DeviceIndex.facet_value_stats over the group's rows: labels, values and filter are global; counts and sums are added on the first
         shard's GPU, min and max combined on the order keys over [S, B, L].  Equal to the unsharded index exactly."""
-        import torch
-        n_labels, dt, rows_per_chunk, _ = _facet_value_args(labels, n_labels, values, self.n_rows, rows_per_chunk)
-        nat.require_device()
-        parts = self._facet_value_parts(labels, values, filter,
-                                        lambda sh, l, v, f, row0: sh._facet_value_stats_call(l, n_labels, v, dt, f, row0, rows_per_chunk))
-        count, missing, lo, hi, total_sum, total, other = (torch.stack(x) for x in zip(*parts))      # [S, B, L] / [S, B]
-        has = count > 0
-        klo = torch.where(has, _value_keys(lo), torch.full_like(count, 1 << 32))
-        khi = torch.where(has, _value_keys(hi), torch.zeros_like(count))
-        lo = lo.gather(0, klo.argmin(0, keepdim=True))[0]
-        hi = hi.gather(0, khi.argmax(0, keepdim=True))[0]
-        return FacetValueStats(*_facet_out(labels, count.sum(0), missing.sum(0), lo, hi, total_sum.sum(0), total.sum(0), other.sum(0)))
+        return _facet_value_stats(self, labels, n_labels, values, filter, rows_per_chunk)
 
     def facet_value_histogram(self, labels, n_labels: int, values, edges, filter=None, rows_per_chunk: int = 0) -> FacetValueHistogram:
         """DeviceIndex.facet_value_histogram over the group's rows: the shards' bins are added on the first shard's GPU."""
-        n_labels, dt, rows_per_chunk, e = _facet_value_args(labels, n_labels, values, self.n_rows, rows_per_chunk, edges)
-        nat.require_device()
-        parts = self._facet_value_parts(labels, values, filter,
-                                        lambda sh, l, v, f, row0: sh._facet_value_hist_call(l, n_labels, v, dt, _values_on(e, sh.device), f, row0,
-                                                                                            rows_per_chunk))
-        return FacetValueHistogram(*_facet_out(labels, *(sum(x[1:], x[0]) for x in zip(*parts))))
+        return _facet_value_histogram(self, labels, n_labels, values, edges, filter, rows_per_chunk)
 
     def value_topk(self, values, k: int, descending: bool = True, filter=None, rows_per_chunk: int = 0) -> SortedResults:
         """DeviceIndex.value_topk over the group's rows (global ids): every shard lists its k best with its id offset; the lists are merged by
         (order key, id) on the first shard's GPU."""
-        import torch
-        dt, rows_per_chunk = _value_args(values, self.n_rows, rows_per_chunk)
-        k, descending = _value_topk_args(k, descending)
-        nat.require_device()
-        parts = self._value_parts(values, filter,
-                                  lambda sh, v, f, row0: sh._value_topk_call(v, dt, k, descending, row0, f, row0, rows_per_chunk))
-        ids, vals = (torch.cat(x, dim=1) for x in zip(*parts))                      # [B, S * k]: ids ascend from shard to shard
-        key = _value_keys(vals)
-        key = torch.where(ids < 0, torch.full_like(key, -1), key if descending else 0xFFFFFFFF - key)
-        # a shard's list is in (key descending, id ascending) order and the shards' id ranges ascend: order by id first, then -- stably -- by key
-        by_id = torch.where(ids < 0, torch.full_like(ids, 1 << 62), ids).argsort(dim=1, stable=True)
-        order = by_id.gather(1, key.gather(1, by_id).argsort(dim=1, descending=True, stable=True))[:, :k]
-        return SortedResults(*_facet_out(values, ids.gather(1, order), vals.gather(1, order)))
+        return _value_topk(self, values, k, descending, filter, 0, rows_per_chunk)
 
     def value_quantiles(self, values, q=None, method: str = "lower", ranks=None, filter=None, rows_per_chunk: int = 0) -> ValueQuantiles:
         """DeviceIndex.value_quantiles over the group's rows: three rounds of level calls -- every shard counts the level's digits of its
         slice of the values and its bit range of the filter, the counts are added on the first shard's GPU, one step there picks each rank's
         bin and names the next level's slots.  Integer counts: equal to the unsharded index bit for bit."""
-        import torch
-        n = self.n_rows
-        dt, rows_per_chunk = _value_args(values, n, rows_per_chunk)
-        qa, method, ra = _quantile_args(q, method, ranks)
-        nat.require_device()
-        dev0 = torch.device("cuda", self.device)
-        f = _value_set(filter, n, dev0)
-        B = f.n_queries if (f is not None and f.per_query) else 1
-        if ra is not None:
-            ra = _quantile_ranks_for(ra, B)
-        tdt = torch.float32 if dt == nat.VAL_F32 else torch.int32
-
-        def batch(qb, rb, R):
-            q_dev = torch.from_numpy(qb).to(dev0) if qb is not None else None
-            r_dev = torch.from_numpy(rb).to(dev0) if rb is not None else None
-            state = missing = None
-            for level in range(nat.VALUE_RADIX_LEVELS):
-                def one(sh, v, fs, row0):
-                    d = torch.device("cuda", sh.device)
-                    sp, ns = (state["slot_prefix"].to(d), state["n_slots"].to(d)) if level else (None, None)
-                    return sh._value_radix_counts_call(v, dt, level, R, sp, ns, fs, row0, rows_per_chunk)
-                parts = self._value_parts(values, f, one)
-                counts = sum((p[0] for p in parts[1:]), parts[0][0])
-                if level == 0:
-                    missing = sum((p[1] for p in parts[1:]), parts[0][1])
-                state = value_radix_step(level, counts, R, state, q_dev, method, r_dev, tdt, self.device)
-            return state["values"], state["ranks"], state["count"], missing
-        return ValueQuantiles(*_facet_out(values, *_quantile_batches(qa, ra, B, batch)))
+        return _value_quantiles(self, values, q, method, ranks, filter, rows_per_chunk)
 
     # ---- term aggregations ------------------------------------------------------------------------------------------------------------------
-    def _term_agg(self, spec, filter, ids, rows_per_chunk, extra=()):
-        """term_counts / term_sums over the group's rows: every shard takes its bit range of the global filter, or the global ids with its
-        first row as the id offset, and the integer parts are added on the first shard's GPU -> spec.result"""
-        import torch
-        n_total = self.n_rows
-        dev0 = torch.device("cuda", self.device)
-        f = t = None
-        if ids is not None:
-            ids = _term_ids(ids)
-            on_dev = _is_torch(ids) and ids.is_cuda
-            t = ids if _is_torch(ids) else torch.from_numpy(np.ascontiguousarray(ids))
-            if not on_dev and t.numel() and (int(t.min()) < -1 or int(t.max()) >= n_total):
-                raise ValueError(f"an id lies outside [-1, {n_total})")
-        nat.require_device()
-        if filter is not None:
-            from .doc_filter import as_doc_filter
-            f = as_doc_filter(filter, n_total, device=dev0)
-        out, row0 = None, 0
-        for sh in self._shards:
-            sdev = torch.device("cuda", sh.device)
-            if t is not None:
-                part = sh._term_ids_call(spec, t.to(sdev).contiguous(), row0, False, extra)
-            else:
-                part = sh._term_set_call(spec, f.to(sdev) if f is not None else None, row0, rows_per_chunk, extra)   # its rows: bits [row0, row0 + n)
-            part = tuple(x.to(dev0) for x in part)
-            out = part if out is None else tuple(a + b for a, b in zip(out, part))
-            row0 += sh.n_rows
-        return spec.result(*out)
-
     def term_counts(self, filter=None, ids=None, rows_per_chunk: int = 0) -> TermCounts:
         """DeviceIndex.term_counts over the group's rows: filter and ids are global.  Every shard counts on its own GPU -- its bit range of
         the filter, or the ids with its first row as the id offset (ids it does not own are skipped) -- and counts and total are summed on
         the first shard's GPU.  Equal to the unsharded index exactly.  An id outside the group raises ValueError (host lists)."""
-        if filter is not None and ids is not None:
-            raise ValueError("the set is given by `filter` or by `ids`, not both")
-        return self._term_agg(_TERM_COUNTS, filter, ids, _rows_per_chunk_arg(rows_per_chunk))
+        return _term_counts(self, filter, ids, rows_per_chunk)
 
     def top_terms(self, filter=None, ids=None, topn: int = 20, method: str = "jlh", min_count: int = 1, background=None) -> TopTerms:
         """DeviceIndex.top_terms over the group's rows: the top-n is taken after the shards' counts are summed, never per shard."""
@@ -3208,10 +3189,7 @@ class ShardGroup:
         filter, or the ids with its first row as the id offset (ids it does not own are skipped) -- and sums and total are added on the
         first shard's GPU.  The additions are integer: equal to the unsharded index exactly.  An id outside the group raises ValueError
         (host lists)."""
-        if filter is not None and ids is not None:
-            raise ValueError("the set is given by `filter` or by `ids`, not both")
-        rows_per_chunk, tile_cols = _term_sum_args(rows_per_chunk, tile_cols)
-        return self._term_agg(_TERM_SUMS, filter, ids, rows_per_chunk, (tile_cols,))
+        return _term_sums(self, filter, ids, rows_per_chunk, tile_cols)
 
     def top_weight_terms(self, filter=None, ids=None, topn: int = 20, min_count: int = 0) -> TopWeights:
         """DeviceIndex.top_weight_terms over the group's rows: the top-n is taken after the shards' sums are added, never per shard."""
@@ -3221,26 +3199,7 @@ class ShardGroup:
         """DeviceIndex.assign over the group's rows: the centroids and the bias are copied to every shard's GPU, every shard assigns its rows
         under its bit range of the filter, and the answers are concatenated on the first shard's GPU.  A row's value depends on nothing
         but the row: equal to the unsharded index bit for bit."""
-        c, b, rows_per_chunk = _assign_args(centroids, bias, _n_cols_of(self), rows_per_chunk)
-        import torch
-        nat.require_device()
-        dev0 = torch.device("cuda", self.device)
-        f = None
-        if filter is not None:
-            from .doc_filter import as_doc_filter
-            f = as_doc_filter(filter, self.n_rows, device=dev0)
-            if f.per_query:
-                raise ValueError("assign takes ONE document set, not a per-query filter")
-        labels, values, row0 = [], [], 0
-        for sh in self._shards:
-            sdev = torch.device("cuda", sh.device)
-            with torch.cuda.device(sdev):
-                l, v = sh._assign_call(c.to(sdev).contiguous(), b.to(sdev).contiguous() if b is not None else None,
-                                       f.to(sdev) if f is not None else None, row0, rows_per_chunk)       # its rows: bits [row0, row0 + n)
-            labels.append(l.to(dev0))
-            values.append(v.to(dev0))
-            row0 += sh.n_rows
-        return Assignment(torch.cat(labels), torch.cat(values))
+        return _assign(self, centroids, bias, filter, rows_per_chunk)
 
     def half_norms(self, centroids):
         """DeviceIndex.half_norms, on the first shard's GPU (the shards share the store dtype)"""
