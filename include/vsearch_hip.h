@@ -474,7 +474,7 @@ VS_API int vs_label_bitmaps(const int32_t* labels, int64_t n_rows, const int32_t
  * 2^27 scratch keys, host edges / bounds as above: VS_EINVAL -- checked before the device is touched (without a GPU a bad argument is VS_EINVAL,
  * a good one VS_ENODEVICE).  Pointers: all host (staged; the call blocks), or all device pointers on `device` / the index's device (VS_EINVAL
  * for a mix); device pointers and a non-NULL stream only enqueue (vs_value_topk synchronises either way).
- * Not covered: no index file stores values; 64-bit and fp64 values; histograms of scores; sort by several keys; k > 1024; a shard
+ * Not covered: no index file stores values; 64-bit and fp64 values; sort by several keys; k > 1024; a shard
  * group has no entry point of its own (every shard works on its slice of the values and its bit range of the bitmap: counts, sums and bins are
  * added, min / max combined on keys, the top-k lists merged by (key, id)) and the one-process-per-GPU RCCL path has none.                       */
 #define VS_VAL_F32 0
@@ -547,7 +547,7 @@ VS_API int vs_index_value_topk(vs_index* index, const uint32_t* words, int64_t b
  * Errors (VS_EINVAL before the device is touched; a good call without a GPU is VS_ENODEVICE): everything vs_value_stats refuses, R outside
  * 1..VS_VALUE_MAX_RANKS, an unknown method or level, a host q outside [0, 1] or NaN, a negative host rank, B x R x 2048 beyond 2^27, a NULL
  * array the level needs, host pointers to vs_value_radix_step.
- * Not covered: weighted quantiles; quantiles of scores; per-label quantiles in one pass; skipping levels by the set's common key prefix; 64-bit
+ * Not covered: weighted quantiles; per-label quantiles in one pass; skipping levels by the set's common key prefix; 64-bit
  * values; the one-process-per-GPU RCCL path.                                                                                                     */
 #define VS_VALUE_RADIX_BINS 2048
 #define VS_VALUE_RADIX_LEVELS 3
@@ -624,6 +624,38 @@ VS_API int vs_index_facet_value_histogram(vs_index* index, const uint32_t* words
                                           int32_t n_labels, const void* values, int dtype, const void* edges, int32_t n_edges,
                                           int64_t rows_per_chunk, int64_t* counts, int64_t ld_counts, int64_t* below, int64_t* above,
                                           int64_t* missing, int64_t* total, int64_t* other, void* stream);
+
+/* ---- scores as a field: the exact score of every row of a document set, as a value array (no reference counterpart) -----------------------------
+ * vs_index_set_scores: for query b and row r, out_scores [b * ld_scores + r] holds the library's exact score when r is live (not deleted) and in
+ *   the set, and the missing sentinel of the numeric fields, NaN 0x7FC00000, for every other row.  The result is a VS_VAL_F32 field of its own:
+ *   vs_index_value_stats / _histogram / _topk / _quantiles and the breakdowns take row b of it as `values` unchanged, which gives the stats,
+ *   histograms, percentiles and per-label breakdowns of SCORES under the very keys every other field is decided on.
+ *   The set: bit bit0 + r of the bitmap at words + b * ld_words, the layout of vs_index_value_stats -- but here ld_words = 0 is one bitmap SHARED by
+ *   the batch and words == NULL every live row, for any B (the queries differ, not the sets); else ld_words >= the (bit0 + n_rows + 31) / 32 words
+ *   a bitmap spans.  Bits at or past bit0 + n_rows are ignored.  The index's tombstones are ANDed in at bit 0 whatever bit0 is.
+ *   The score is the one of vs_index_search_range and vs_index_explain, bit for bit: q (fp32 | fp16 [B, ldq]) is rounded to the index dtype as in
+ *   vs_index_search; score = fl32(sum of fp64(fl32(q[c] * v[c])) over the row's stored cells), v = 1 on a binary index; a row without cells
+ *   scores +0.0.  A score that is itself NaN (non-finite stored data or query) cannot be told from "not in the set": it reads as missing.
+ *   Every element [b, 0 .. n_rows) is written; columns [n_rows, ld_scores) are not touched; ld_scores >= n_rows.
+ * vs_set_score_plan: the launch for these arguments -- pure host arithmetic, no device needed.  A work item is (query, chunk of rows): chunks x
+ *   rows_per_chunk >= n_rows > (chunks - 1) x rows_per_chunk.  rows_per_chunk = 0: automatic (about 1024 work items over the batch, a multiple
+ *   of 64 rows, 2048 at least); any other value must be a positive multiple of 64 and is taken as given (a tuning knob: no result depends
+ *   on it).  per_query is accepted for symmetry with the other plans; the rule does not depend on it.
+ * Kernel (set_scores.hip): 1024 threads, one workgroup a CU; the query's dense fp32 image (4 x (n_cols + 1) bytes) sits in LDS and is loaded when
+ *   a workgroup's query changes.  The set is walked in 2048-row spans, every wave on the same words; a span whose set words or live words are all
+ *   zero is left at once.  The set rows of a span are compacted through LDS into a list (8 KB) and dealt to the 16 waves, one wave a row, so a
+ *   sparse set costs its rows and the bitmap walk, not a scan.  The queries of a chunk run side by side on one XCD and share its L2.  Plain stores
+ *   only; the sentinel is a 32-bit memset on the stream ahead of the kernel.
+ * Errors: NULL q or out_scores, q_dtype not VS_F32 / VS_F16, B < 1, bit0 < 0, ld_words < 0 or too short, rows_per_chunk no multiple of 64, a NULL
+ *   index, ldq < n_cols, ld_scores < n_rows, chunks x B beyond 2^31 - 1: VS_EINVAL, checked on the host before the device is touched.  A dense index
+ *   on the matrix cores, and a CSR index wider than the LDS image (n_cols > 32763): VS_EUNSUPPORTED.  Pointers: all host (staged; the call blocks)
+ *   or all device pointers on the index's device (VS_EINVAL for a mix); device pointers and a non-NULL stream only enqueue.
+ * Not covered: a dense index; wide indexes; the one-process-per-GPU RCCL path; an 8-queries-a-pass tile variant of the scorer; a values stride in
+ *   the value calls, which would make a batch of score rows one call (today: one value call a query); weighted aggregations.                    */
+VS_API int vs_set_score_plan(int64_t n_rows, int32_t B, int32_t n_cols, int per_query, int64_t rows_per_chunk, int64_t* out_chunks,
+                             int64_t* out_rows_per_chunk);
+VS_API int vs_index_set_scores(vs_index* index, const void* q, int q_dtype, int64_t ldq, int32_t B, const uint32_t* words, int64_t bit0,
+                               int64_t ld_words, int64_t rows_per_chunk, float* out_scores, int64_t ld_scores, void* stream);
 
 /* bool / uint8 mask [B, n] (row stride ld_mask bytes; non-zero = allowed) -> the bitmap words [B, ld_words] vs_index_search_filtered
  * reads (bits past n of a row's last word are 0).  mask and words: host pointers or device pointers on `device` (VS_EINVAL otherwise).  stream as in

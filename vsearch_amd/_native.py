@@ -113,6 +113,8 @@ _SIGNATURES = {
                                   _vp], _int),
     "vs_index_facet_value_histogram": ([_vp, _vp, _i64, _i64, _i32, _vp, _i32, _vp, _int, _vp, _i32, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
                                        _int),
+    "vs_set_score_plan": ([_i64, _i32, _i32, _int, _i64, C.POINTER(_i64), C.POINTER(_i64)], _int),
+    "vs_index_set_scores": ([_vp, _vp, _int, _i64, _i32, _vp, _i64, _i64, _i64, _vp, _i64, _vp], _int),
     "vs_filter_pack": ([_vp, _i32, _i64, _i64, _vp, _i64, _int, _vp], _int),
     "vs_index_scores": ([_vp, _vp, _int, _i64, _i32, _vp, _vp], _int),
     "vs_index_explain": ([_vp, _vp, _int, _i64, _i32, _vp, _i64, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp], _int),

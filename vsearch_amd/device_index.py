@@ -2126,6 +2126,36 @@ def _assign(obj, centroids, bias, filter, rows_per_chunk):
     return Assignment(*(parts[0] if len(parts) == 1 else (torch.cat(x) for x in zip(*parts))))
 
 
+# ---- scores as a field: the exact score of every row of a document set (vs_index_set_scores) -------------------------------------------------
+def set_score_plan(n_rows: int, B: int, n_cols: int, per_query: bool = True, rows_per_chunk: int = 0):
+    """The launch vs_index_set_scores takes for these arguments (vs_set_score_plan; pure host arithmetic, no GPU needed) -> (chunks,
+    rows_per_chunk): a work item is one query's chunk of rows."""
+    chunks, rpc = C.c_int64(0), C.c_int64(0)
+    nat.check(nat.lib().vs_set_score_plan(int(n_rows), int(B), int(n_cols), 1 if per_query else 0, int(rows_per_chunk), C.byref(chunks), C.byref(rpc)))
+    return chunks.value, rpc.value
+
+
+def _set_scores(obj, q, filter, rows_per_chunk):
+    rows_per_chunk = _rows_per_chunk_arg(rows_per_chunk)
+    if not hasattr(q, "ndim") or q.ndim != 2:
+        raise ValueError("queries must be [B, V]")
+    import torch
+    nat.require_device()
+    qt = q.detach() if _is_torch(q) else torch.from_numpy(np.ascontiguousarray(q))
+    n = obj.n_rows
+    f = None
+    if filter is not None:
+        from .doc_filter import as_doc_filter
+        f = as_doc_filter(filter, n, device=obj.device, batch=int(qt.shape[0]))
+
+    def one(sh, fs, row0):
+        sdev = torch.device("cuda", sh.device)
+        with torch.cuda.device(sdev):                              # (a shard of a group runs with its GPU current)
+            return (sh._set_scores_call(qt.to(sdev).contiguous(), fs, row0, rows_per_chunk),)
+    parts = _shard_parts(obj, f, (), one, n)
+    return parts[0][0] if len(parts) == 1 else torch.cat([p[0] for p in parts], dim=1)
+
+
 class DeviceIndex:
     """Owner of one device-resident index shard (CSR packets or dense)."""
 
@@ -2871,6 +2901,29 @@ class DeviceIndex:
         nat.require_device()
         return centroid_half_norms(c.to(torch.device("cuda", self.device)), round_f16=self._round_f16(), device=self.device)
 
+    # ---- scores as a field (vs_index_set_scores) ---------------------------------------------------------------------------------------------
+    def _set_scores_call(self, q_dev, f, bit0, rows_per_chunk):
+        """One vs_index_set_scores call on device buffers and torch's current stream -> float32 CUDA tensor [B, n_rows].  q_dev: contiguous
+        float32 / float16 CUDA tensor [B, V] on this index's device; f: None or a DocFilter there, read from bit `bit0` on."""
+        import torch
+        p, dt, keep, B, ldq = self._q_args(q_dev)
+        n = self.n_rows
+        out = torch.empty((B, n), dtype=torch.float32, device=torch.device("cuda", self.device))
+        if n:
+            nat.check(nat.lib().vs_index_set_scores(self._h, p, dt, ldq, B, _ptr(f.words) if f is not None else None, int(bit0),
+                                                    f.ld if f is not None else 0, rows_per_chunk, _ptr(out), n, current_stream(self.device)))
+        return out
+
+    def set_scores(self, q, filter=None, rows_per_chunk: int = 0):
+        """The exact score of every document of a set, as a value array -> float32 [B, N] on the index's GPU: row b holds query b's score
+        (search_range's and explain's, bit for bit) of every live document of its set, and NaN -- the missing sentinel of the numeric
+        fields -- for every document OUTSIDE the set and every deleted one.  A row of it is a float32 field: ``value_stats``,
+        ``value_histogram``, ``value_topk``, ``value_quantiles`` and the breakdowns take it as `values`.  q: [B, V] float32 / float16 (numpy
+        or tensor); filter: what search(filter=) accepts -- one set shared by the queries, or one per query (match_filter's result); None:
+        every live document.  rows_per_chunk: 0 = automatic, else a multiple of 64 (a tuning knob: no result depends on it).  A dense
+        index, and one wider than 32 763 columns, raise NotImplementedError.  Enqueued on torch's current stream."""
+        return _set_scores(self, q, filter, rows_per_chunk)
+
     def scores(self, q):
         """Dense [B, n_rows] fp32 score matrix (what index.py:91 materialises). numpy out."""
         info = self.info()
@@ -3200,6 +3253,12 @@ class ShardGroup:
         under its bit range of the filter, and the answers are concatenated on the first shard's GPU.  A row's value depends on nothing
         but the row: equal to the unsharded index bit for bit."""
         return _assign(self, centroids, bias, filter, rows_per_chunk)
+
+    def set_scores(self, q, filter=None, rows_per_chunk: int = 0):
+        """DeviceIndex.set_scores over the group's rows: every shard scores its rows under its bit range of the filter on its own GPU, and
+        the slices are placed side by side on the first shard's GPU.  A row's score depends on nothing but the row and the query: equal
+        to the unsharded index bit for bit."""
+        return _set_scores(self, q, filter, rows_per_chunk)
 
     def half_norms(self, centroids):
         """DeviceIndex.half_norms, on the first shard's GPU (the shards share the store dtype)"""

@@ -30,6 +30,20 @@ from ...device_index import FacetValueHistogram, FacetValueStats
 logger = logging.getLogger(__name__)
 
 
+class _ScoreField:
+    """the type of ``SCORE``"""
+    __slots__ = ()
+
+    def __repr__(self):
+        return "SCORE"
+
+
+# Pass as `field` / `value_field` of value_stats, histogram, percentiles, median, top_by_value, stats_by_facet and histogram_by_facet to describe
+# a document set by its SCORES instead of a stored field.  An object of its own, not a reserved name: set_values("_score", ...) is a field like any.
+SCORE = _ScoreField()
+SCORE_SCRATCH_BYTES = 1 << 30                                        # the [Bt, N] float32 block of scores a SCORE call keeps at a time
+
+
 class SearchResults(NamedTuple):
     ids: List[int]
     scores: List[float]
@@ -720,18 +734,75 @@ class Index:
     def _value_set(self, q_embs, min_score, filter):
         return self.match_filter(q_embs, min_score, filter=filter) if q_embs is not None else filter
 
-    def value_stats(self, field: str, q_embs=None, min_score=None, filter=None) -> ValueStats:
+    # ---- scores as a field: SCORE in place of a field name ---------------------------------------------------------------------------------
+    @staticmethod
+    def _score_check(q_embs, score_scratch=SCORE_SCRATCH_BYTES):
+        """the argument errors of a SCORE call, before any device work"""
+        if q_embs is None:
+            raise ValueError("field=SCORE needs q_embs: the scores are a query's")
+        if isinstance(score_scratch, bool) or not isinstance(score_scratch, (int, np.integer)) or score_scratch < 1:
+            raise ValueError(f"score_scratch must be a positive number of bytes, got {score_scratch!r}")
+
+    def _score_set(self, q_embs, min_score, filter):
+        """-> (search target, queries on its GPU, None or the set as a DocFilter there)"""
+        target, q = self._range_queries(q_embs, 0.0 if min_score is None else min_score, 0)
+        if min_score is not None:
+            return target, q, target.match_filter(q, min_score, filter=filter)
+        if filter is None:
+            return target, q, None
+        from ...doc_filter import as_doc_filter
+        return target, q, as_doc_filter(filter, self._n_rows(), device=target.device, batch=int(q.shape[0]))
+
+    def set_scores(self, q_embs, min_score=None, filter=None) -> torch.Tensor:
+        """The exact score of every document of a set -> float32 [B, N] on the index's GPU: the score ``search_range`` decides by and
+        ``explain`` reports, bit for bit, and NaN for every document outside the set and every deleted one.  The set: with min_score
+        the documents ``match_filter(q_embs, min_score, filter)`` matches per query, else `filter` alone (None = every document).  A row is
+        a float32 value array like any field's (``DeviceIndex.value_stats`` and the other value calls take it).  B x N x 4 bytes: for a
+        large batch use ``histogram(SCORE, ...)`` and its siblings, which score a bounded block of queries at a time.  A dense ``Index``
+        raises NotImplementedError."""
+        self._score_check(q_embs)
+        target, q, f = self._score_set(q_embs, min_score, filter)
+        return target.set_scores(q, filter=f)
+
+    def _over_scores(self, q_embs, min_score, filter, score_scratch, one):
+        """one(search target, values [N], None or a one-set DocFilter) -> a result tuple of one query; the queries' results stacked.  The value calls take
+        ONE [N] array for all queries, so a batch is served in two levels: a block of Bt queries is scored at once, [Bt, N] float32 within
+        score_scratch bytes, then every query of it makes its own value call with its row of the scores and its bitmap."""
+        from ...doc_filter import DocFilter
+        self._score_check(q_embs, score_scratch)
+        target, q, f = self._score_set(q_embs, min_score, filter)
+        B, n = int(q.shape[0]), self._n_rows()
+        bt = int(max(1, min(B, int(score_scratch) // max(4 * n, 1))))
+        parts = []
+        for b0 in range(0, B, bt):
+            per_query = f is not None and f.per_query
+            fb = DocFilter(f.words[b0:b0 + bt], n) if per_query else f
+            block = target.set_scores(q[b0:b0 + bt], filter=fb)
+            for i in range(int(block.shape[0])):
+                parts.append(one(target, block[i], DocFilter(fb.words[i], n) if per_query else fb))
+        return type(parts[0])(*(self._to_api(torch.cat(x)) for x in zip(*parts)))
+
+    def value_stats(self, field: str, q_embs=None, min_score=None, filter=None, score_scratch: int = SCORE_SCRATCH_BYTES) -> ValueStats:
         """Count, missing, min, max and sum of value field `field` over a document set -> ValueStats, one entry per query; ``.mean()`` in
         fp64.  The set as in ``facets``: with q_embs and min_score the documents ``match_filter(q_embs, min_score, filter)`` matches per
-        query, else `filter` alone (None = every document).  Deleted documents never count."""
+        query, else `filter` alone (None = every document).  Deleted documents never count.
+        field=SCORE describes the set by each query's scores (float32; ``set_scores``): q_embs is required, min_score optional -- without
+        it the set is `filter` alone; score_scratch: bytes of the block of scores kept at a time (the queries are served in blocks)."""
+        if field is SCORE:
+            return self._over_scores(q_embs, min_score, filter, score_scratch, lambda t, v, f: ValueStats(*t.value_stats(v, filter=f)))
         self._value_check(field, q_embs, min_score)
         v = self._value_field(field)
         filter = self._value_set(q_embs, min_score, filter)
         return ValueStats(*(self._to_api(t) for t in self._explain_target()[0].value_stats(v, filter=filter)))
 
-    def histogram(self, field: str, edges, q_embs=None, min_score=None, filter=None) -> ValueHistogram:
+    def histogram(self, field: str, edges, q_embs=None, min_score=None, filter=None, score_scratch: int = SCORE_SCRATCH_BYTES) -> ValueHistogram:
         """How a document set spreads over the bins [edges[i], edges[i + 1]) of value field `field` -> ValueHistogram(counts [B, E - 1],
-        below, above, missing, total).  edges: 2..1025 strictly ascending numbers.  The set as in ``value_stats``."""
+        below, above, missing, total).  edges: 2..1025 strictly ascending numbers.  The set as in ``value_stats``.  field=SCORE: the
+        histogram of each query's scores -- counts[b, i] == count_matches(edges[i]) - count_matches(edges[i + 1]) over the same set."""
+        if field is SCORE:
+            self._score_check(q_embs, score_scratch)
+            _value_edges(edges, nat.VAL_F32)
+            return self._over_scores(q_embs, min_score, filter, score_scratch, lambda t, v, f: ValueHistogram(*t.value_histogram(v, edges, filter=f)))
         _value_edges(edges, self._value_check(field, q_embs, min_score))
         v = self._value_field(field)
         filter = self._value_set(q_embs, min_score, filter)
@@ -745,11 +816,18 @@ class Index:
         elif field not in self._facet_store():
             raise KeyError(f"no facet field {field!r}: set_facet() or facet_from_samples() first (fields: {list(self._facet_store())})")
 
-    def stats_by_facet(self, value_field: str, facet_field: str, q_embs=None, min_score=None, filter=None) -> FacetValueStats:
+    def stats_by_facet(self, value_field: str, facet_field: str, q_embs=None, min_score=None, filter=None,
+                       score_scratch: int = SCORE_SCRATCH_BYTES) -> FacetValueStats:
         """Count, missing, min, max and sum of value field `value_field` per label of facet field `facet_field` ("groups" = the group ids) over
         a document set, in one pass over the index -> FacetValueStats(count, missing, min, max, sum [B, n_labels], total, other [B]);
         ``.mean()`` in fp64 -- "mean price per category of the matches".  A document without a label counts into `other` only.  The set as in
-        ``value_stats``.  Works on a row-sharded index as well."""
+        ``value_stats``.  Works on a row-sharded index as well.  value_field=SCORE: the mean score per label (as in ``value_stats``)."""
+        if value_field is SCORE:
+            self._score_check(q_embs, score_scratch)
+            self._facet_check(facet_field)
+            codes, n_labels, _ = self._facet_field(facet_field)
+            return self._over_scores(q_embs, min_score, filter, score_scratch,
+                                     lambda t, v, f: FacetValueStats(*t.facet_value_stats(codes, n_labels, v, filter=f)))
         self._value_check(value_field, q_embs, min_score)
         self._facet_check(facet_field)
         v = self._value_field(value_field)
@@ -757,10 +835,18 @@ class Index:
         filter = self._value_set(q_embs, min_score, filter)
         return FacetValueStats(*(self._to_api(t) for t in self._explain_target()[0].facet_value_stats(codes, n_labels, v, filter=filter)))
 
-    def histogram_by_facet(self, value_field: str, facet_field: str, edges, q_embs=None, min_score=None, filter=None) -> FacetValueHistogram:
+    def histogram_by_facet(self, value_field: str, facet_field: str, edges, q_embs=None, min_score=None, filter=None,
+                           score_scratch: int = SCORE_SCRATCH_BYTES) -> FacetValueHistogram:
         """How the documents of each label of `facet_field` spread over the bins [edges[i], edges[i + 1]) of `value_field`, over a document
         set (a cross-tab) -> FacetValueHistogram(counts [B, n_labels, E - 1], below, above, missing [B, n_labels], total, other [B]).
-        edges: 2..1025 strictly ascending numbers.  The set as in ``value_stats``."""
+        edges: 2..1025 strictly ascending numbers.  The set as in ``value_stats``.  value_field=SCORE: score bands per label."""
+        if value_field is SCORE:
+            self._score_check(q_embs, score_scratch)
+            _value_edges(edges, nat.VAL_F32)
+            self._facet_check(facet_field)
+            codes, n_labels, _ = self._facet_field(facet_field)
+            return self._over_scores(q_embs, min_score, filter, score_scratch,
+                                     lambda t, v, f: FacetValueHistogram(*t.facet_value_histogram(codes, n_labels, v, edges, filter=f)))
         _value_edges(edges, self._value_check(value_field, q_embs, min_score))
         self._facet_check(facet_field)
         v = self._value_field(value_field)
@@ -768,40 +854,57 @@ class Index:
         filter = self._value_set(q_embs, min_score, filter)
         return FacetValueHistogram(*(self._to_api(t) for t in self._explain_target()[0].facet_value_histogram(codes, n_labels, v, edges, filter=filter)))
 
-    def top_by_value(self, field: str, k: int, descending: bool = True, q_embs=None, min_score=None, filter=None) -> SortedResults:
+    def top_by_value(self, field: str, k: int, descending: bool = True, q_embs=None, min_score=None, filter=None,
+                     score_scratch: int = SCORE_SCRATCH_BYTES) -> SortedResults:
         """The k documents of a set with the largest (descending) or smallest values of `field`, ties by id ascending -- sort by a field
         instead of by score -> SortedResults(ids [B, k], values [B, k]); documents without a value are never listed, id -1 behind the last.
-        k in 1..1024.  The set as in ``value_stats``."""
+        k in 1..1024.  The set as in ``value_stats``.  field=SCORE: the best (``search_range``'s list) or the WORST k of the set by score."""
+        if field is SCORE:
+            self._score_check(q_embs, score_scratch)
+            _value_topk_args(k, descending)
+            return self._over_scores(q_embs, min_score, filter, score_scratch,
+                                     lambda t, v, f: SortedResults(*t.value_topk(v, k, descending=descending, filter=f)))
         self._value_check(field, q_embs, min_score)
         _value_topk_args(k, descending)
         v = self._value_field(field)
         filter = self._value_set(q_embs, min_score, filter)
         return SortedResults(*(self._to_api(t) for t in self._explain_target()[0].value_topk(v, k, descending=descending, filter=filter)))
 
-    def percentiles(self, field: str, pcts, q_embs=None, min_score=None, filter=None, method: str = "linear") -> ValuePercentiles:
+    def percentiles(self, field: str, pcts, q_embs=None, min_score=None, filter=None, method: str = "linear",
+                    score_scratch: int = SCORE_SCRATCH_BYTES) -> ValuePercentiles:
         """Exact percentiles of value field `field` over a document set -> ValuePercentiles(values [B, P], count, missing).  pcts: numbers
         in 0..100.  With q = pct / 100 and pos = q * (count - 1): method "lower" gives the value at rank floor(pos), "higher" at ceil(pos),
         "nearest" at rint(pos) (half to even), in the field's type; "linear" (the default, numpy's) selects the values at floor(pos) and
         ceil(pos) exactly and interpolates lo + (hi - lo) * (pos - floor(pos)) in float64 (exactly lo where lo == hi).  A set without values
-        gives NaN / the missing sentinel.  The set as in ``value_stats``; any number of percentiles (16 a pass)."""
+        gives NaN / the missing sentinel.  The set as in ``value_stats``; any number of percentiles (16 a pass).  field=SCORE: the median,
+        p90, ... of each query's scores over its set."""
+        if field is SCORE:
+            self._score_check(q_embs, score_scratch)
+            q = _percentile_args(pcts, method)
+            return self._over_scores(q_embs, min_score, filter, score_scratch, lambda t, v, f: self._percentiles_of(t, v, q, method, f))
         self._value_check(field, q_embs, min_score)
         q = _percentile_args(pcts, method)
         v = self._value_field(field)
         filter = self._value_set(q_embs, min_score, filter)
-        target = self._explain_target()[0]
+        return ValuePercentiles(*(self._to_api(t) for t in self._percentiles_of(self._explain_target()[0], v, q, method, filter)))
+
+    @staticmethod
+    def _percentiles_of(target, v, q, method, filter):
+        """the percentiles of one value array over one filter, on the target's GPU"""
         if method != "linear":
             res = target.value_quantiles(v, q=q, method=method, filter=filter)
-            return ValuePercentiles(self._to_api(res.values), self._to_api(res.count), self._to_api(res.missing))
+            return ValuePercentiles(res.values, res.count, res.missing)
         lo, hi = target.value_quantiles(v, q=q, method="lower", filter=filter), target.value_quantiles(v, q=q, method="higher", filter=filter)
         pos = q[None, :] * (lo.count.cpu().numpy().astype(np.float64) - 1.0)[:, None]
         vals = quantile_lerp(lo.values.cpu().numpy(), hi.values.cpu().numpy(), pos - np.floor(pos))
         if v.dtype == torch.int32:                                  # (an int32 field's sentinel is a number: no answer is NaN here)
             vals = np.where(lo.ranks.cpu().numpy() < 0, np.nan, vals)
-        return ValuePercentiles(self._to_api(torch.from_numpy(vals).to(lo.count.device)), self._to_api(lo.count), self._to_api(lo.missing))
+        return ValuePercentiles(torch.from_numpy(vals).to(lo.count.device), lo.count, lo.missing)
 
-    def median(self, field: str, q_embs=None, min_score=None, filter=None, method: str = "linear") -> ValuePercentiles:
-        """``percentiles(field, [50], ...)``: the median of value field `field` over a document set, values [B, 1]."""
-        return self.percentiles(field, [50], q_embs=q_embs, min_score=min_score, filter=filter, method=method)
+    def median(self, field: str, q_embs=None, min_score=None, filter=None, method: str = "linear",
+               score_scratch: int = SCORE_SCRATCH_BYTES) -> ValuePercentiles:
+        """``percentiles(field, [50], ...)``: the median of value field `field` (or of the scores: SCORE) over a document set, values [B, 1]."""
+        return self.percentiles(field, [50], q_embs=q_embs, min_score=min_score, filter=filter, method=method, score_scratch=score_scratch)
 
     def _added_values(self, values, n_add):
         """values= of add() / update() -> {name: ndarray [n_add] in the field's type}, or None for an index without value fields.  Raises

@@ -22,7 +22,7 @@ from torch import Tensor as T
 from ... import _native as nat
 from ..biencoder.biencoder import BiEncoder, BiEncoderConfig
 from ..utils import sparse as sp
-from .index import BoTIndex, DiverseResults, FusedResults, GroupedResults, Index, IndexType, RangeResults, SearchResults, SparseIndex
+from .index import BoTIndex, DiverseResults, FusedResults, GroupedResults, Index, IndexType, RangeResults, SCORE, SearchResults, SparseIndex
 
 logger = logging.getLogger(__name__)
 
@@ -186,6 +186,13 @@ class Retriever(BiEncoder):
         set as in ``retrieve_sorted`` -> ValueHistogram(counts [B, E - 1], below, above, missing, total)."""
         index, q_emb, filter = self._match_set(queries, index, filter, must, must_not, should, min_should, dropout, a, batch_size)
         return index.histogram(field, edges, q_embs=q_emb, min_score=min_score, filter=filter)
+
+    def retrieve_score_histogram(self, queries: Union[List[str], np.ndarray, T], edges, min_score=None, **filters):
+        """How each query's SCORES spread over the bins [edges[i], edges[i + 1]) -- ``retrieve_histogram(queries, SCORE, edges, ...)``: where a
+        relevance cut-off should sit, counts at every threshold from one call.  min_score=None: over every document `filters` (filter=,
+        must=, ... and the other keywords of ``retrieve_histogram``) leave; else over the matches.  ``retrieve_percentiles``,
+        ``retrieve_sorted``, ``retrieve_stats_by_facet`` and ``retrieve_histogram_by_facet`` take SCORE as their field the same way."""
+        return self.retrieve_histogram(queries, SCORE, edges, min_score=min_score, **filters)
 
     def retrieve_stats_by_facet(self, queries: Union[List[str], np.ndarray, T], value_field: str, facet_field: str, min_score=0.0, topn: int = 10,
                                 min_count: int = 1, dropout: float = 0, a: int = None, index: Index = None, batch_size: int = 32, filter=None,
