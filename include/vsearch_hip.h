@@ -657,6 +657,77 @@ VS_API int vs_set_score_plan(int64_t n_rows, int32_t B, int32_t n_cols, int per_
 VS_API int vs_index_set_scores(vs_index* index, const void* q, int q_dtype, int64_t ldq, int32_t B, const uint32_t* words, int64_t bit0,
                                int64_t ld_words, int64_t rows_per_chunk, float* out_scores, int64_t ld_scores, void* stream);
 
+/* ---- set egress: the size, the members, a page and a sample of any document set, and id lists back to bitmaps (no reference counterpart) ------
+ * The way out of a bitmap.  A set of rows is given exactly as for vs_value_stats: bit bit0 + r of the bitmap at words + b * ld_words stands for
+ * row r (ld_words = 0: one bitmap, and then B must be 1; else ld_words >= the (bit0 + n_rows + 31) / 32 words a bitmap spans); words == NULL:
+ * every row (B must be 1); and_words (may be NULL): a second bitmap shared by all queries, at the same bit0; bits below bit0 and at or past
+ * bit0 + n_rows are ignored whatever they hold.  The vs_index_* variants run over the index's rows with its tombstones ANDed in (at bit 0
+ * whatever bit0 is): deleted rows are never counted, listed or sampled.  No float and no position-deciding atomic is involved: every result is
+ * exact and independent of the launch.
+ *
+ * vs_set_list_plan: the launch for these arguments -- pure host arithmetic, no device needed.  A work item is (query, chunk of rows): chunks x
+ *   rows_per_chunk >= n_rows > (chunks - 1) x rows_per_chunk; spans = the 2048-row spans of a query, (n_rows + 2047) / 2048.  rows_per_chunk = 0:
+ *   automatic (about 1024 work items over the batch, 8192 rows at least); any other value must be a positive multiple of 64 and is rounded up
+ *   to whole spans (a tuning knob: no result depends on it).
+ * vs_set_count: out_counts int64 [B] receives the number of set rows.
+ * vs_set_ids: per query the set's rows IN ASCENDING ORDER, ranks [offsets[b], offsets[b] + limit) of that list, as row + id_offset in out_ids
+ *   int64 [B, limit]; slots behind the last member hold -1; every slot is written.  out_counts [b] is the full size of the set whatever the
+ *   window.  offsets int64 [B] or NULL (0); a negative host offset is VS_EINVAL, a negative device one reads as 0; an offset at or past the
+ *   count gives all -1.  limit = 0 is count-only (out_ids may be NULL).  B x limit <= 2^27 (VS_SET_MAX_OUT_IDS).
+ * vs_set_sample: per query the n set rows with the smallest (h, id), listed in that order -- a uniform sample without replacement, the same for
+ *   the same seed, and the same whether the rows are one index or the shards of one (id = row + id_offset, the GLOBAL id, is what is hashed).
+ *   All arithmetic modulo 2^64:
+ *       mix(z): z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31      (the splitmix64 finaliser)
+ *       k = mix(seeds[b] + 0x9E3779B97F4A7C15);   h = uint32(mix(k ^ (0x9E3779B97F4A7C15 * (id + 1))) >> 32)
+ *   (seed, id) -> h: (0, 0) 0x0397ab29, (0, 1) 0xc0737b7c, (1, 0) 0xddc1ed05, (12345, 21015323) 0xfa680e94, (2^64 - 1, 2^32 - 2) 0x29fc86af;
+ *   vs_set_sample_hash computes it on the host.  seeds uint64 [B]; out_ids int64 [B, n]; out_hash uint32 [B, n] or NULL: the members' hashes
+ *   (what a merge of shards' lists orders by); unused slots hold id -1 and hash 0xFFFFFFFF; every slot is written.  out_counts [b]: the size of
+ *   the set.  n in 1..VS_SET_MAX_SAMPLE, n > count is allowed; chunks x B x n <= 2^27 scratch keys, the rule of vs_value_topk.
+ * vs_set_from_ids: the inverse of vs_set_ids.  ids int64 [B, ld_ids], m entries a query (m = 0: ids may be NULL) -> out_words [B, ld_words]:
+ *   words [0, (bit0 + n_rows + 31) / 32) of each row are written whole, bits below bit0 and past the rows 0 -- the convention of
+ *   vs_label_bitmaps.  Bit bit0 + id is set for every listed id in [0, n_rows); ids below 0 are padding and ignored; duplicates are harmless.
+ *   An id at or above n_rows: VS_EINVAL in a host array; on the device it is ignored and never written anywhere.  allow = 0 gives the
+ *   complement within the rows.  B in 1..65535, bit0 in 0..2^32.
+ * Kernels (set_list.hip).  Count: a wave owns a 2048-row span of one query; lane s forms the 64 rows of step s from the two bitmaps' words
+ *   (shifted and masked at both ends) and the wave adds the popcounts into span_count uint32 [B, spans].  Scan: one workgroup per query turns
+ *   them into exclusive int64 bases and the total.  Write: a wave per span; a span whose ranks [base, base + count) miss the window, or that is
+ *   empty, is left WITHOUT READING THE BITMAP; otherwise a wave-exclusive scan of the steps' popcounts gives the step bases, a row's rank is
+ *   base + step base + popc(step & lanes below), and rows inside the window are stored at rank - offset with plain stores; a fourth launch
+ *   writes the -1 tail.  Sample: the shape of vs_value_topk with the key computed, not loaded -- (~h << 32 | ~row) through the 4096-key LDS
+ *   stream per (chunk, query), per-chunk lists and counts in scratch, one workgroup per query merges.  From ids: a clear, a scatter with a
+ *   32-bit atomicOr per id, and an invert pass when allow = 0.
+ * Errors: NULL outputs (or seeds), n_rows outside 1..2^32 - 1, B < 1, bit0 < 0, B > 1 with ld_words = 0, ld_words too short, rows_per_chunk no
+ *   multiple of 64, limit < 0 or B x limit > 2^27, n out of range or too many scratch keys, spans x B > 2^27, host offsets / ids as above:
+ *   VS_EINVAL -- checked before the device is touched (without a GPU a bad argument is VS_EINVAL, a good one VS_ENODEVICE).  Pointers: all
+ *   host (staged; the call blocks), or all device pointers on `device` / the index's device (VS_EINVAL for a mix).  vs_set_from_ids with device
+ *   pointers and a non-NULL stream only enqueues; the others hold device scratch and synchronise the stream before they return.
+ * Not covered: payloads gathered with the ids (scores: vs_index_set_scores; values: the caller's array); weighted, stratified or
+ *   with-replacement sampling; a rank -> row select call; more than 2^32 - 1 rows; a shard group has no entry point of its own (counts add; a
+ *   shard lists its local window [offset - C, offset - C + limit) clipped at 0, C the count of the shards before it, with id_offset = its first
+ *   row; samples merge by (h, id)) and the one-process-per-GPU RCCL path has none.                                                          */
+#define VS_SET_MAX_SAMPLE 1024        /* rows vs_set_sample lists per query at most */
+#define VS_SET_MAX_OUT_IDS 134217728  /* B x limit of one vs_set_ids call: 2^27 */
+VS_API uint32_t vs_set_sample_hash(uint64_t seed, int64_t id);
+VS_API int vs_set_list_plan(int64_t n_rows, int32_t B, int per_query, int64_t rows_per_chunk, int64_t* out_chunks, int64_t* out_rows_per_chunk,
+                            int64_t* out_spans);
+VS_API int vs_set_count(const uint32_t* words, int64_t bit0, int64_t ld_words, const uint32_t* and_words, int32_t B, int64_t n_rows,
+                        int64_t rows_per_chunk, int64_t* out_counts, int device, void* stream);
+VS_API int vs_index_set_count(vs_index* index, const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B, int64_t rows_per_chunk,
+                              int64_t* out_counts, void* stream);
+VS_API int vs_set_ids(const uint32_t* words, int64_t bit0, int64_t ld_words, const uint32_t* and_words, int32_t B, int64_t n_rows,
+                      const int64_t* offsets, int64_t limit, int64_t id_offset, int64_t rows_per_chunk, int64_t* out_ids, int64_t* out_counts,
+                      int device, void* stream);
+VS_API int vs_index_set_ids(vs_index* index, const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B, const int64_t* offsets,
+                            int64_t limit, int64_t id_offset, int64_t rows_per_chunk, int64_t* out_ids, int64_t* out_counts, void* stream);
+VS_API int vs_set_sample(const uint32_t* words, int64_t bit0, int64_t ld_words, const uint32_t* and_words, int32_t B, int64_t n_rows,
+                         const uint64_t* seeds, int32_t n, int64_t id_offset, int64_t rows_per_chunk, int64_t* out_ids, uint32_t* out_hash,
+                         int64_t* out_counts, int device, void* stream);
+VS_API int vs_index_set_sample(vs_index* index, const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B, const uint64_t* seeds, int32_t n,
+                               int64_t id_offset, int64_t rows_per_chunk, int64_t* out_ids, uint32_t* out_hash, int64_t* out_counts,
+                               void* stream);
+VS_API int vs_set_from_ids(const int64_t* ids, int32_t B, int64_t m, int64_t ld_ids, int64_t n_rows, int64_t bit0, int allow,
+                           uint32_t* out_words, int64_t ld_words, int device, void* stream);
+
 /* bool / uint8 mask [B, n] (row stride ld_mask bytes; non-zero = allowed) -> the bitmap words [B, ld_words] vs_index_search_filtered
  * reads (bits past n of a row's last word are 0).  mask and words: host pointers or device pointers on `device` (VS_EINVAL otherwise).  stream as in
  * vs_index_search (host buffers block).                                                                                          */

@@ -40,6 +40,8 @@ VALUE_RADIX_BINS, VALUE_RADIX_LEVELS, VALUE_MAX_RANKS = 2048, 3, 16
 QUANTILE_LOWER, QUANTILE_HIGHER, QUANTILE_NEAREST = 0, 1, 2
 # breakdowns (VS_FACET_VALUE_*): (query, label) records of a workgroup's LDS in the stats kernel, n_labels x (n_edges + 2) cells a query at most
 FACET_VALUE_LDS_RECORDS, FACET_VALUE_MAX_CELLS = 2048, 1 << 22
+# set egress (VS_SET_MAX_*): the most rows vs_set_sample lists per query, the most ids (B x limit) of one vs_set_ids call
+SET_MAX_SAMPLE, SET_MAX_OUT_IDS = 1024, 1 << 27
 
 
 class VsearchNativeError(RuntimeError):
@@ -115,6 +117,15 @@ _SIGNATURES = {
                                        _int),
     "vs_set_score_plan": ([_i64, _i32, _i32, _int, _i64, C.POINTER(_i64), C.POINTER(_i64)], _int),
     "vs_index_set_scores": ([_vp, _vp, _int, _i64, _i32, _vp, _i64, _i64, _i64, _vp, _i64, _vp], _int),
+    "vs_set_sample_hash": ([C.c_uint64, _i64], C.c_uint32),
+    "vs_set_list_plan": ([_i64, _i32, _int, _i64, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64)], _int),
+    "vs_set_count": ([_vp, _i64, _i64, _vp, _i32, _i64, _i64, _vp, _int, _vp], _int),
+    "vs_index_set_count": ([_vp, _vp, _i64, _i64, _i32, _i64, _vp, _vp], _int),
+    "vs_set_ids": ([_vp, _i64, _i64, _vp, _i32, _i64, _vp, _i64, _i64, _i64, _vp, _vp, _int, _vp], _int),
+    "vs_index_set_ids": ([_vp, _vp, _i64, _i64, _i32, _vp, _i64, _i64, _i64, _vp, _vp, _vp], _int),
+    "vs_set_sample": ([_vp, _i64, _i64, _vp, _i32, _i64, _vp, _i32, _i64, _i64, _vp, _vp, _vp, _int, _vp], _int),
+    "vs_index_set_sample": ([_vp, _vp, _i64, _i64, _i32, _vp, _i32, _i64, _i64, _vp, _vp, _vp, _vp], _int),
+    "vs_set_from_ids": ([_vp, _i32, _i64, _i64, _i64, _i64, _int, _vp, _i64, _int, _vp], _int),
     "vs_filter_pack": ([_vp, _i32, _i64, _i64, _vp, _i64, _int, _vp], _int),
     "vs_index_scores": ([_vp, _vp, _int, _i64, _i32, _vp, _vp], _int),
     "vs_index_explain": ([_vp, _vp, _int, _i64, _i32, _vp, _i64, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp], _int),

@@ -2156,6 +2156,243 @@ def _set_scores(obj, q, filter, rows_per_chunk):
     return parts[0][0] if len(parts) == 1 else torch.cat([p[0] for p in parts], dim=1)
 
 
+# ---- set egress: the size, the members, a page and a sample of a document set; id lists back to bitmaps (vs_set_*) ------------------------------
+class SetIds(NamedTuple):
+    """set_ids / DocFilter.ids: per query the set's documents in ascending order -- ranks [offset, offset + limit) of that list, ids int64
+    [B, limit], -1 behind the last member -- and the full size of the set, counts int64 [B], whatever the window"""
+    ids: object
+    counts: object
+
+
+class SetSample(NamedTuple):
+    """set_sample / DocFilter.sample: per query n documents of the set, uniformly and without replacement -- the n with the smallest (hash of
+    the seed and the id, id), in that order, ids int64 [B, n], -1 behind the last when the set holds fewer -- and the size of the set"""
+    ids: object
+    counts: object
+
+
+MAX_SET_SAMPLE = nat.SET_MAX_SAMPLE
+MAX_SET_IDS = nat.SET_MAX_OUT_IDS
+
+
+def set_list_plan(n_rows: int, B: int, per_query: bool = True, rows_per_chunk: int = 0):
+    """The launch vs_set_count / vs_set_ids / vs_set_sample take for these arguments (vs_set_list_plan; pure host arithmetic, no GPU needed) ->
+    (chunks, rows_per_chunk, spans): a work item is one query's chunk of rows, a wave counts and lists 2048-row spans."""
+    chunks, rpc, spans = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    nat.check(nat.lib().vs_set_list_plan(int(n_rows), int(B), 1 if per_query else 0, int(rows_per_chunk), C.byref(chunks), C.byref(rpc), C.byref(spans)))
+    return chunks.value, rpc.value, spans.value
+
+
+def set_sample_hash(seed: int, id: int) -> int:
+    """The pinned hash vs_set_sample orders a set by (vs_set_sample_hash, on the host): uint32 of (seed, global id)"""
+    return int(nat.lib().vs_set_sample_hash(int(seed) & 0xFFFFFFFFFFFFFFFF, int(id)))
+
+
+def _is_int(x) -> bool:
+    return isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_))
+
+
+def _set_window_args(offset, limit):
+    """offset: an int >= 0 or a sequence of them, one per query; limit: None (the largest count) or an int >= 0 -> (int | int64 ndarray, limit)"""
+    if _is_int(offset):
+        off = int(offset)
+        bad = off < 0
+    else:
+        off = np.asarray(offset.detach().cpu().numpy() if _is_torch(offset) else offset)
+        if off.ndim != 1 or off.shape[0] < 1 or off.dtype.kind not in "iu":
+            raise TypeError("offset: an int, or one int per query")
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        bad = bool((off < 0).any())
+    if bad:
+        raise ValueError("offset must be >= 0")
+    if limit is not None and (not _is_int(limit) or limit < 0):
+        raise ValueError(f"limit must be None or an int >= 0, got {limit!r}")
+    return off, None if limit is None else int(limit)
+
+
+def _set_sample_args(n, seed):
+    if not _is_int(n) or not 1 <= n <= MAX_SET_SAMPLE:
+        raise ValueError(f"n must be in 1..{MAX_SET_SAMPLE}, got {n!r}")
+    if not _is_int(seed):
+        raise TypeError(f"seed must be an int, got {type(seed).__name__}")
+    return int(n), int(seed)
+
+
+def _sample_seeds(seed: int, B: int):
+    """query b samples under seed + b (modulo 2^64) -> int64 ndarray [B] holding the uint64 bits"""
+    return np.array([(seed + b) & 0xFFFFFFFFFFFFFFFF for b in range(B)], dtype=np.uint64).view(np.int64)
+
+
+def _offsets_for(off, B):
+    """the offsets of a call for B queries -> None (all 0) or an int64 ndarray [B]"""
+    if isinstance(off, int):
+        return None if off == 0 else np.full(B, off, dtype=np.int64)
+    if off.shape[0] != B:
+        raise ValueError(f"{off.shape[0]} offsets, the filter is for {B} queries")
+    return off
+
+
+def _set_count_call(h, device, n_rows, f, bit0, rows_per_chunk):
+    """One vs_set_count (h None: the bitmap as it is) or vs_index_set_count (tombstones in) call on torch's current stream -> (counts int64
+    [B],) on `device`.  f: None (every row) or a DocFilter there, read from bit `bit0` on."""
+    import torch
+    B, (w, b0, ld, _) = _set_args(f, bit0)
+    counts = torch.empty(B, dtype=torch.int64, device=torch.device("cuda", device))
+    if h is None:
+        nat.check(nat.lib().vs_set_count(w, b0, ld, None, B, int(n_rows), rows_per_chunk, _ptr(counts), device, current_stream(device)))
+    else:
+        nat.check(nat.lib().vs_index_set_count(h, w, b0, ld, B, rows_per_chunk, _ptr(counts), current_stream(device)))
+    return (counts,)
+
+
+def _set_ids_call(h, device, n_rows, f, bit0, offsets_dev, limit, id_offset, rows_per_chunk):
+    """One vs_set_ids / vs_index_set_ids call -> (ids int64 [B, limit], counts int64 [B]); offsets_dev: None or an int64 tensor [B] there"""
+    import torch
+    dev = torch.device("cuda", device)
+    B, (w, b0, ld, _) = _set_args(f, bit0)
+    ids = torch.empty((B, limit), dtype=torch.int64, device=dev)
+    counts = torch.empty(B, dtype=torch.int64, device=dev)
+    if h is None:
+        nat.check(nat.lib().vs_set_ids(w, b0, ld, None, B, int(n_rows), _ptr(offsets_dev), limit, int(id_offset), rows_per_chunk, _ptr(ids),
+                                       _ptr(counts), device, current_stream(device)))
+    else:
+        nat.check(nat.lib().vs_index_set_ids(h, w, b0, ld, B, _ptr(offsets_dev), limit, int(id_offset), rows_per_chunk, _ptr(ids), _ptr(counts),
+                                             current_stream(device)))
+    return ids, counts
+
+
+def _set_sample_call(h, device, n_rows, f, bit0, seeds_dev, n, id_offset, rows_per_chunk):
+    """One vs_set_sample / vs_index_set_sample call -> (ids int64 [B, n], hashes int64 [B, n] in 0..2^32 - 1, counts int64 [B]); seeds_dev:
+    an int64 tensor [B] there holding the uint64 seeds' bits"""
+    import torch
+    dev = torch.device("cuda", device)
+    B, (w, b0, ld, _) = _set_args(f, bit0)
+    ids = torch.empty((B, n), dtype=torch.int64, device=dev)
+    hs = torch.empty((B, n), dtype=torch.int32, device=dev)
+    counts = torch.empty(B, dtype=torch.int64, device=dev)
+    if h is None:
+        nat.check(nat.lib().vs_set_sample(w, b0, ld, None, B, int(n_rows), _ptr(seeds_dev), n, int(id_offset), rows_per_chunk, _ptr(ids), _ptr(hs),
+                                          _ptr(counts), device, current_stream(device)))
+    else:
+        nat.check(nat.lib().vs_index_set_sample(h, w, b0, ld, B, _ptr(seeds_dev), n, int(id_offset), rows_per_chunk, _ptr(ids), _ptr(hs), _ptr(counts),
+                                                current_stream(device)))
+    return ids, hs.to(torch.int64) & 0xFFFFFFFF, counts
+
+
+def set_from_ids(ids, n_rows: int, bit0: int = 0, allow: bool = True, ld_words=None, device: int = 0):
+    """vs_set_from_ids on torch's current stream: ids an int64 tensor [B, m] on `device` (entries < 0 are padding; an id at or above n_rows is
+    ignored) -> int32 words [B, ld_words] there, bit bit0 + id set for every listed id -- or, allow=False, for every other row"""
+    import torch
+    B, m = int(ids.shape[0]), int(ids.shape[1])
+    nw = (int(bit0) + int(n_rows) + 31) // 32
+    ld = nw if ld_words is None else int(ld_words)
+    words = torch.empty((B, ld), dtype=torch.int32, device=torch.device("cuda", device))
+    ids = ids.contiguous()
+    nat.check(nat.lib().vs_set_from_ids(_ptr(ids) if m else None, B, m, m, int(n_rows), int(bit0), 1 if allow else 0, _ptr(words), ld, int(device),
+                                        current_stream(device)))
+    return words
+
+
+def _on(x, device: int):
+    """a small host array -> a tensor on GPU `device`"""
+    import torch
+    return None if x is None else torch.from_numpy(np.ascontiguousarray(x)).to(f"cuda:{device}")
+
+
+def _doc_filter_count(f, rows_per_chunk=0):
+    nat.require_device()
+    return _set_count_call(None, f.device.index, f.n_rows, f, 0, _rows_per_chunk_arg(rows_per_chunk))[0]
+
+
+def _doc_filter_ids(f, offset, limit, rows_per_chunk=0):
+    off, limit = _set_window_args(offset, limit)
+    rpc = _rows_per_chunk_arg(rows_per_chunk)
+    nat.require_device()
+    dev, B = f.device.index, f.n_queries or 1
+    if limit is None:                                              # one count round first
+        limit = int(_set_count_call(None, dev, f.n_rows, f, 0, rpc)[0].max())
+    return SetIds(*_set_ids_call(None, dev, f.n_rows, f, 0, _on(_offsets_for(off, B), dev), limit, 0, rpc))
+
+
+def _doc_filter_sample(f, n, seed, rows_per_chunk=0):
+    n, seed = _set_sample_args(n, seed)
+    rpc = _rows_per_chunk_arg(rows_per_chunk)
+    nat.require_device()
+    dev, B = f.device.index, f.n_queries or 1
+    ids, _, counts = _set_sample_call(None, dev, f.n_rows, f, 0, _on(_sample_seeds(seed, B), dev), n, 0, rpc)
+    return SetSample(ids, counts)
+
+
+def _set_batch(obj, filter, n):
+    """filter= resolved once on obj's GPU -> (DocFilter | None, the B of the calls)"""
+    f = _doc_set(filter, n, obj.device)
+    return f, (f.n_queries if (f is not None and f.per_query) else 1)
+
+
+def _set_count(obj, filter, rows_per_chunk):
+    n = obj.n_rows
+    rpc = _rows_per_chunk_arg(rows_per_chunk)
+    nat.require_device()
+    return _add_parts(_shard_parts(obj, filter, (), lambda sh, f, row0: sh._set_count_call(f, row0, rpc), n))[0]
+
+
+def _set_ids(obj, filter, offset, limit, rows_per_chunk):
+    """The shard rule of the list: after a count round, shard s lists its local window [offset - C_s, offset - C_s + limit) clipped at 0 -- C_s
+    the count of the shards before it -- with its first row as the id offset, and the pieces are placed one behind the other."""
+    import torch
+    n = obj.n_rows
+    off, limit = _set_window_args(offset, limit)
+    rpc = _rows_per_chunk_arg(rows_per_chunk)
+    nat.require_device()
+    f, B = _set_batch(obj, filter, n)
+    off = _offsets_for(off, B)
+    parts = obj._parts
+    if len(parts) == 1 and limit is not None:                      # one part: its window is the window
+        sh = parts[0][0]
+        return SetIds(*sh._set_ids_call(f, 0, _on(off, sh.device), limit, 0, rpc))
+    counts = torch.stack([p[0] for p in _shard_parts(obj, f, (), lambda sh, fs, row0: sh._set_count_call(fs, row0, rpc), n)])      # [S, B]
+    total = counts.sum(0)
+    if limit is None:
+        limit = int(total.max())
+    before = counts.cumsum(0) - counts                             # C_s: the exclusive prefix of the shards' counts
+    want = _on(off, obj.device) if off is not None else torch.zeros(B, dtype=torch.int64, device=total.device)
+    local = {row0: (want - before[s]).clamp_(min=0) for s, (_, row0) in enumerate(parts)}
+    pieces = _shard_parts(obj, f, (), lambda sh, fs, row0: sh._set_ids_call(fs, row0, local[row0].to(f"cuda:{sh.device}"), limit, row0, rpc), n)
+    if len(pieces) == 1:
+        return SetIds(pieces[0][0], total)
+    out = torch.full((B, limit), -1, dtype=torch.int64, device=total.device)
+    slot = torch.arange(limit, device=total.device)[None, :]
+    for s, (ids, _) in enumerate(pieces):
+        dest = slot + (before[s] - want).clamp_(min=0)[:, None]    # a shard's piece starts where the shards before it end
+        take = (ids >= 0) & (dest < limit)
+        out[take.nonzero(as_tuple=True)[0], dest[take]] = ids[take]
+    return SetIds(out, total)
+
+
+def _merge_set_samples(parts, n):
+    """the shards' (ids, hashes, counts), each sampled with its id offset -> the n smallest by (hash, id), and the counts added"""
+    import torch
+    ids, hs = (torch.cat([p[i] for p in parts], dim=1) for i in (0, 1))
+    gone = ids < 0
+    by_id = torch.where(gone, torch.full_like(ids, 1 << 62), ids).argsort(dim=1, stable=True)
+    h = torch.where(gone, torch.full_like(hs, 1 << 32), hs)
+    order = by_id.gather(1, h.gather(1, by_id).argsort(dim=1, stable=True))[:, :n]
+    return ids.gather(1, order), sum(p[2] for p in parts[1:]) + parts[0][2]
+
+
+def _set_sample(obj, filter, n, seed, rows_per_chunk):
+    n_rows = obj.n_rows
+    n, seed = _set_sample_args(n, seed)
+    rpc = _rows_per_chunk_arg(rows_per_chunk)
+    nat.require_device()
+    f, B = _set_batch(obj, filter, n_rows)
+    seeds = _sample_seeds(seed, B)
+    parts = _shard_parts(obj, f, (), lambda sh, fs, row0: sh._set_sample_call(fs, row0, _on(seeds, sh.device), n, row0, rpc), n_rows)
+    if len(parts) == 1:
+        return SetSample(parts[0][0], parts[0][2])
+    return SetSample(*_merge_set_samples(parts, n))
+
+
 class DeviceIndex:
     """Owner of one device-resident index shard (CSR packets or dense)."""
 
@@ -2924,6 +3161,38 @@ class DeviceIndex:
         index, and one wider than 32 763 columns, raise NotImplementedError.  Enqueued on torch's current stream."""
         return _set_scores(self, q, filter, rows_per_chunk)
 
+    # ---- set egress: count, list, page and sample a document set (vs_index_set_count / _set_ids / _set_sample) --------------------------------
+    def _set_count_call(self, f, bit0, rows_per_chunk):
+        """One vs_index_set_count call on torch's current stream -> (counts int64 [B],).  f: None (every live row) or a DocFilter on this
+        index's device, read from bit `bit0` on."""
+        return _set_count_call(self._h, self.device, self.n_rows, f, bit0, rows_per_chunk)
+
+    def _set_ids_call(self, f, bit0, offsets_dev, limit, id_offset, rows_per_chunk):
+        """One vs_index_set_ids call -> (ids int64 [B, limit], counts int64 [B])"""
+        return _set_ids_call(self._h, self.device, self.n_rows, f, bit0, offsets_dev, limit, id_offset, rows_per_chunk)
+
+    def _set_sample_call(self, f, bit0, seeds_dev, n, id_offset, rows_per_chunk):
+        """One vs_index_set_sample call -> (ids int64 [B, n], hashes int64 [B, n], counts int64 [B])"""
+        return _set_sample_call(self._h, self.device, self.n_rows, f, bit0, seeds_dev, n, id_offset, rows_per_chunk)
+
+    def set_count(self, filter=None, rows_per_chunk: int = 0):
+        """The number of live documents in a set -> int64 tensor [B] on the index's device.  filter: what search(filter=) accepts -- a
+        per-query DocFilter gives one entry per query, a shared one B = 1, None every live document.  Deleted documents never count."""
+        return _set_count(self, filter, rows_per_chunk)
+
+    def set_ids(self, filter=None, offset=0, limit=None, rows_per_chunk: int = 0) -> SetIds:
+        """The live documents of a set as ids in ascending order -> SetIds(ids int64 [B, limit], counts int64 [B]): ranks [offset, offset +
+        limit) of each query's list, -1 behind its last member; counts is the full size of the set whatever the window.  offset: an int or one
+        per query; limit=None takes the largest count (one count round first); B x limit <= 2^27 -- page through longer lists.  No atomic
+        decides a position: the list is sorted by construction."""
+        return _set_ids(self, filter, offset, limit, rows_per_chunk)
+
+    def set_sample(self, n: int, filter=None, seed: int = 0, rows_per_chunk: int = 0) -> SetSample:
+        """n live documents of a set, uniformly and without replacement -> SetSample(ids int64 [B, n], counts int64 [B]): the n with the
+        smallest (hash(seed + b, id), id) for query b, in that order (``set_sample_hash``); -1 behind the last when the set holds fewer.  The
+        same seed gives the same sample, on one index and on a ShardGroup of its rows alike.  n in 1..1024."""
+        return _set_sample(self, filter, n, seed, rows_per_chunk)
+
     def scores(self, q):
         """Dense [B, n_rows] fp32 score matrix (what index.py:91 materialises). numpy out."""
         info = self.info()
@@ -3259,6 +3528,22 @@ class ShardGroup:
         the slices are placed side by side on the first shard's GPU.  A row's score depends on nothing but the row and the query: equal
         to the unsharded index bit for bit."""
         return _set_scores(self, q, filter, rows_per_chunk)
+
+    # ---- set egress ---------------------------------------------------------------------------------------------------------------------------
+    def set_count(self, filter=None, rows_per_chunk: int = 0):
+        """DeviceIndex.set_count over the group's rows: every shard counts its bit range of the filter, the counts are added."""
+        return _set_count(self, filter, rows_per_chunk)
+
+    def set_ids(self, filter=None, offset=0, limit=None, rows_per_chunk: int = 0) -> SetIds:
+        """DeviceIndex.set_ids over the group's rows (global ids): after a count round shard s lists its local window [offset - C_s, offset -
+        C_s + limit) clipped at 0 -- C_s the count of the shards before it -- with its first row as the id offset, and the pieces are placed
+        one behind the other on the first shard's GPU.  Equal to the unsharded index bit for bit."""
+        return _set_ids(self, filter, offset, limit, rows_per_chunk)
+
+    def set_sample(self, n: int, filter=None, seed: int = 0, rows_per_chunk: int = 0) -> SetSample:
+        """DeviceIndex.set_sample over the group's rows: every shard samples n with its first row as the id offset -- the GLOBAL id is what
+        is hashed -- and the lists merge by (hash, id), cut to n.  Equal to the unsharded index bit for bit."""
+        return _set_sample(self, filter, n, seed, rows_per_chunk)
 
     def half_norms(self, centroids):
         """DeviceIndex.half_norms, on the first shard's GPU (the shards share the store dtype)"""

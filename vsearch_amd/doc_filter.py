@@ -241,9 +241,12 @@ class DocFilter:
     @classmethod
     def from_ids(cls, ids, n_rows: int, allow: bool = True, device=None) -> "DocFilter":
         """Row ids to allow (allow=True) or to exclude (allow=False): a 1-D tensor / ndarray / list for the whole batch, or [B, m] for one
-        set per query (entries < 0 are ignored there: ragged sets padded with -1).  The mask is built with torch on the device."""
+        set per query (entries < 0 are ignored there: ragged sets padded with -1).  The ids are scattered into the packed words on the GPU
+        (vs_set_from_ids): no [B, N] mask is formed."""
         torch = _torch()
         n_rows = int(n_rows)
+        if n_rows <= 0:
+            raise ValueError("no rows: the index has rows")
         if isinstance(ids, np.ndarray) or isinstance(ids, (list, tuple)):
             ids = torch.as_tensor(np.asarray(ids, dtype=np.int64))
         if not isinstance(ids, torch.Tensor) or ids.dtype.is_floating_point or ids.dtype == torch.bool or ids.dim() not in (1, 2):
@@ -252,16 +255,15 @@ class DocFilter:
         ids = ids.to(dev).to(torch.int64)
         if ids.numel() and int(ids.max()) >= n_rows:
             raise ValueError(f"row id {int(ids.max())} is out of range for {n_rows} rows")
-        if ids.dim() == 1:
-            if ids.numel() and int(ids.min()) < 0:
-                raise ValueError("row ids must be >= 0")
-            mask = torch.zeros(n_rows, dtype=torch.bool, device=dev)
-            mask[ids] = True
-        else:
-            mask = torch.zeros((ids.shape[0], n_rows), dtype=torch.bool, device=dev)
-            r, c = (ids >= 0).nonzero(as_tuple=True)                     # only the real entries: a -1 pad writes nothing
-            mask[r, ids[r, c]] = True
-        return cls.from_mask(mask if allow else ~mask, device=dev)
+        if ids.dim() == 1 and ids.numel() and int(ids.min()) < 0:
+            raise ValueError("row ids must be >= 0")
+        if ids.dim() == 2 and int(ids.shape[0]) < 1:
+            raise ValueError("id sets for zero queries")
+        from .device_index import set_from_ids
+        nat.require_device()
+        with torch.cuda.device(dev):
+            words = set_from_ids(ids.reshape(1, -1) if ids.dim() == 1 else ids, n_rows, allow=allow, device=dev.index)
+        return cls(words[0] if ids.dim() == 1 else words, n_rows)
 
     @classmethod
     def from_terms(cls, index, must=None, must_not=None, should=None, min_should=None, thr=None) -> "DocFilter":
@@ -374,6 +376,39 @@ class DocFilter:
     def to(self, device) -> "DocFilter":
         dev = _device_of(device)
         return self if self.words.device == dev else DocFilter(self.words.to(dev), self.n_rows)
+
+    # ---- the way out: count, list, page and sample the set (vs_set_count / vs_set_ids / vs_set_sample) ------------------------------------------
+    # These read the bitmap as it is: an index's deleted rows are taken out by DeviceIndex.set_ids / Index.list_ids, not here.
+    def count(self):
+        """The number of rows in the set -> int64 tensor [B] on the filter's GPU (B = 1 for a shared filter)."""
+        from .device_index import _doc_filter_count
+        return _doc_filter_count(self)
+
+    def ids(self, offset=0, limit=None):
+        """The rows of the set in ascending order -> SetIds(ids int64 [B, limit], counts int64 [B]): ranks [offset, offset + limit) of each
+        query's list, -1 behind its last member; counts is the full size whatever the window.  offset: an int or one per query.  limit=None
+        takes the largest count, which costs one count round first.  B x limit <= 2^27: ``pages`` walks a longer list."""
+        from .device_index import _doc_filter_ids
+        return _doc_filter_ids(self, offset, limit)
+
+    def pages(self, page_size: int):
+        """The whole list in pages of `page_size` ids: a generator of SetIds, until every query's list is exhausted (at least one page)."""
+        if isinstance(page_size, bool) or not isinstance(page_size, (int, np.integer)) or page_size < 1:
+            raise ValueError(f"page_size must be a positive int, got {page_size!r}")
+        offset = 0
+        while True:
+            page = self.ids(offset, int(page_size))
+            yield page
+            offset += int(page_size)
+            if offset >= int(page.counts.max()):
+                return
+
+    def sample(self, n: int, seed: int = 0):
+        """n rows of the set, uniformly and without replacement -> SetSample(ids int64 [B, n], counts int64 [B]): query b's n rows with the
+        smallest (hash(seed + b, row), row), in that order; -1 behind the last when the set holds fewer.  Reproducible under the seed.
+        n in 1..1024."""
+        from .device_index import _doc_filter_sample
+        return _doc_filter_sample(self, n, seed)
 
     def __repr__(self):
         kind = f"per-query x {self.n_queries}" if self.per_query else "shared"

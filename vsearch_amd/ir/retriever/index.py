@@ -26,6 +26,7 @@ from ...device_index import Assignment, KMeansResult, KMEANS_UPDATE_BATCH, kmean
 from ...device_index import SortedResults, ValueHistogram, ValueStats, value_column, _value_bounds, _value_dtype, _value_edges, _value_topk_args
 from ...device_index import ValuePercentiles, _percentile_args, quantile_lerp
 from ...device_index import FacetValueHistogram, FacetValueStats
+from ...device_index import SetIds, SetSample, _set_sample_args, _set_window_args
 
 logger = logging.getLogger(__name__)
 
@@ -644,6 +645,35 @@ class Index:
         if topn is None:
             return FacetCounts(*(self._to_api(t) for t in target.facet_counts(codes, n_labels, filter=filter)))
         return TopFacets(*(self._to_api(t) for t in target.top_facets(codes, n_labels, topn, filter=filter, min_count=min_count)))
+
+    # ---- set egress (not in the reference: the members of a document set as ids -- the whole list, a page, a uniform sample) ------------------
+    def _egress_set(self, q_embs, min_score, filter):
+        """the set of count_docs / list_ids / sample_ids, resolved exactly as ``facets`` resolves it"""
+        if (q_embs is None) != (min_score is None):
+            raise ValueError("q_embs and min_score go together: the set is match_filter(q_embs, min_score, filter), or the filter alone")
+        return self.match_filter(q_embs, min_score, filter=filter) if q_embs is not None else filter
+
+    def count_docs(self, filter=None):
+        """The number of live documents in `filter` (as in ``search``; None = every document): int64 [B], B = 1 for a shared filter."""
+        return self._to_api(self._explain_target()[0].set_count(filter=filter))
+
+    def list_ids(self, q_embs=None, min_score=None, filter=None, offset=0, limit: Optional[int] = None) -> SetIds:
+        """The documents of a set as ids in ascending order -> SetIds(ids [B, limit], counts [B]): ranks [offset, offset + limit) of each
+        query's list, -1 behind its last member; counts is the full size of the set whatever the window.  The set as in ``facets``: with
+        q_embs and min_score the documents ``match_filter`` matches, without them `filter` alone, None = every document; deleted documents
+        are never listed.  limit=None takes the largest count; B x limit <= 2^27 -- page with `offset` through a longer list.  Works on a
+        row-sharded index as well."""
+        _set_window_args(offset, limit)
+        filter = self._egress_set(q_embs, min_score, filter)
+        return SetIds(*(self._to_api(t) for t in self._explain_target()[0].set_ids(filter=filter, offset=offset, limit=limit)))
+
+    def sample_ids(self, n: int, q_embs=None, min_score=None, filter=None, seed: int = 0) -> SetSample:
+        """n documents of a set, uniformly and without replacement -> SetSample(ids [B, n], counts [B]); query b samples under seed + b, the
+        same seed gives the same documents on one GPU and on a row-sharded index alike; -1 behind the last when the set holds fewer.  The
+        set as in ``list_ids``.  n in 1..1024."""
+        _set_sample_args(n, seed)
+        filter = self._egress_set(q_embs, min_score, filter)
+        return SetSample(*(self._to_api(t) for t in self._explain_target()[0].set_sample(n, filter=filter, seed=seed)))
 
     # ---- numeric fields (not in the reference: a quantity per document -- a year, a timestamp, a length, a price -- to filter, describe and sort by)
     def _value_store(self):

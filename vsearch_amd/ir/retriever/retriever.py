@@ -179,6 +179,29 @@ class Retriever(BiEncoder):
         index, q_emb, filter = self._match_set(queries, index, filter, must, must_not, should, min_should, dropout, a, batch_size)
         return index.top_by_value(field, k, descending=descending, q_embs=q_emb, min_score=min_score, filter=filter)
 
+    def retrieve_ids(self, queries: Union[List[str], np.ndarray, T], min_score, offset=0, limit: int = None, dropout: float = 0, a: int = None,
+                     index: Index = None, batch_size: int = 32, filter=None, must=None, must_not=None, should=None, min_should: int = None):
+        """EVERY match of each query as ids in ascending order -- ``Index.list_ids`` behind the query encoder, where ``retrieve_range`` stops
+        at 2048 hits: the matches are the documents scoring at least `min_score`; `filter` and the term constraints as in ``retrieve``.
+        -> SetIds(ids [B, limit], counts [B]); limit=None: the largest count; `offset` pages through a longer list."""
+        index, q_emb, filter = self._match_set(queries, index, filter, must, must_not, should, min_should, dropout, a, batch_size)
+        return index.list_ids(q_embs=q_emb, min_score=min_score, filter=filter, offset=offset, limit=limit)
+
+    def sample_band(self, queries: Union[List[str], np.ndarray, T], lo, hi, n: int, seed: int = 0, dropout: float = 0, a: int = None,
+                    index: Index = None, batch_size: int = 32, filter=None, must=None, must_not=None, should=None, min_should: int = None,
+                    return_texts: bool = True):
+        """n documents per query scoring in [lo, hi) -- the hard-negative band as one call: match_filter(lo) & ~match_filter(hi), sampled
+        uniformly and reproducibly under `seed` (``Index.sample_ids``).  -> (SetSample(ids [B, n], counts [B]), texts): texts[b] lists the
+        samples' documents (``index.get_sample``) in the order of ids[b], without the -1 padding; None when return_texts is False or the
+        index has no data file."""
+        index, q_emb, filter = self._match_set(queries, index, filter, must, must_not, should, min_should, dropout, a, batch_size)
+        band = index.match_filter(q_emb, lo, filter=filter) & ~index.match_filter(q_emb, hi)
+        res = index.sample_ids(n, filter=band, seed=seed)
+        texts = None
+        if return_texts and len(index):
+            texts = [[index.get_sample(int(i)) for i in row if i >= 0] for row in res.ids.cpu().tolist()]
+        return res, texts
+
     def retrieve_histogram(self, queries: Union[List[str], np.ndarray, T], field: str, edges, min_score=0.0, dropout: float = 0, a: int = None,
                            index: Index = None, batch_size: int = 32, filter=None, must=None, must_not=None, should=None,
                            min_should: int = None):
