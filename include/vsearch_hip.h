@@ -547,8 +547,8 @@ VS_API int vs_index_value_topk(vs_index* index, const uint32_t* words, int64_t b
  * Errors (VS_EINVAL before the device is touched; a good call without a GPU is VS_ENODEVICE): everything vs_value_stats refuses, R outside
  * 1..VS_VALUE_MAX_RANKS, an unknown method or level, a host q outside [0, 1] or NaN, a negative host rank, B x R x 2048 beyond 2^27, a NULL
  * array the level needs, host pointers to vs_value_radix_step.
- * Not covered: weighted quantiles; per-label quantiles in one pass; skipping levels by the set's common key prefix; 64-bit
- * values; the one-process-per-GPU RCCL path.                                                                                                     */
+ * Not covered: weighted quantiles; skipping levels by the set's common key prefix; 64-bit values; the one-process-per-GPU RCCL path
+ * (per-label quantiles: vs_facet_value_quantiles below).                                                                                        */
 #define VS_VALUE_RADIX_BINS 2048
 #define VS_VALUE_RADIX_LEVELS 3
 #define VS_VALUE_MAX_RANKS 16
@@ -602,7 +602,7 @@ VS_API int vs_value_radix_step(int level, const int64_t* counts, int32_t B, int3
  * max KEYS in out_min / out_max (preset to 0xFFFFFFFF / 0) until a finishing kernel turns them into values.
  * Errors: as for vs_value_stats / vs_value_histogram, and n_labels < 1, n_labels x (n_edges + 2) > VS_FACET_VALUE_MAX_CELLS, B x n_labels >
  * 2^31 - 1, ld_out < n_labels: VS_EINVAL, checked before the device is touched.  Pointers: all host (staged; the call blocks) or all device.
- * Not covered: per-label percentiles; top-n labels by a statistic; two facet fields crossed; 64-bit values; the one-process-per-GPU RCCL path. */
+ * Not covered: top-n labels by a statistic; two facet fields crossed; 64-bit values; the one-process-per-GPU RCCL path. */
 /* (query, label) records of a workgroup's LDS in the stats kernel: 24 bytes each, 48 KiB, so three workgroups fit a CU's 160 KiB.  A design
  * choice: the occupancy it leaves has not been measured against a smaller or a larger cap. */
 #define VS_FACET_VALUE_LDS_RECORDS 2048
@@ -624,6 +624,62 @@ VS_API int vs_index_facet_value_histogram(vs_index* index, const uint32_t* words
                                           int32_t n_labels, const void* values, int dtype, const void* edges, int32_t n_edges,
                                           int64_t rows_per_chunk, int64_t* counts, int64_t ld_counts, int64_t* below, int64_t* above,
                                           int64_t* missing, int64_t* total, int64_t* other, void* stream);
+
+/* ---- per-label percentiles: exact order statistics of a numeric field per facet label, one pass a radix level (no reference counterpart) ------
+ * The product of the percentiles and the breakdowns above.  The set arguments, the dtypes, the pointer rule and the error order are
+ * vs_facet_value_stats'; the digits, the ranks and the sentinels vs_value_quantiles'.  For query b and label l in [0, n_labels) let K[b, l] be
+ * the ascending multiset of the order keys of the rows that are in the set, carry label l and have a value (key != 0): count [b, l] = |K[b, l]|,
+ * missing [b, l] = the set rows of label l with key 0; a set row whose label is outside [0, n_labels), -1 included, adds to other [b] and
+ * nothing else; total [b] is the size of the set: count [b].sum() + missing [b].sum() + other [b] == total [b], always, and count + missing is
+ * vs_facet_counts' counts [b, l].  The order statistic of rank r is value_unkey(K[b, l][r]); a rank outside 0..count - 1 gives the missing
+ * sentinel and a resolved rank of -1; quantile -> rank is the rule above applied to count [b, l].
+ *
+ * vs_facet_value_radix_counts / vs_index_facet_value_radix_counts: one level's digit counts per (query, label).  counts int64 [B, n_labels, S,
+ *   bins], S = 1 at level 0 and R at levels 1 and 2, bins = 2048 / 2048 / 1024, written whole.  Level 0 also writes missing [B, n_labels], total
+ *   [B] and other [B].  Levels 1 and 2 read slot_prefix uint32 [B, n_labels, R] and n_slots int32 [B, n_labels]: exactly the state
+ *   vs_value_radix_step produces when called with B' = B x n_labels.  A row of no slot costs no atomic; slots >= n_slots stay 0.  The arrays a
+ *   level does not use may be NULL.
+ * vs_facet_value_quantiles / vs_index_facet_value_quantiles: all three levels on one device.  Ranks as q double [R] with `method` or -- q ==
+ *   NULL -- as ranks int64 [B, n_labels, R].  out_values [B, n_labels, R] raw 32-bit, out_ranks int64 [B, n_labels, R], count, missing int64
+ *   [B, n_labels], total, other int64 [B]; every element is written.  The call is, bit for bit, the composition of the level call and
+ *   vs_value_radix_step over B x n_labels cells, and synchronises either way (its counts are device scratch).
+ * vs_facet_value_quantile_plan: the launch of the counting kernel at `level` -- pure host arithmetic.  cap = the (query, label) cells whose
+ *   histograms fit 128 KiB of LDS: 16 at level 0, 16 / R at level 1, 32 / R at level 2.  regime 0 (LDS): a workgroup serves qt queries x
+ *   tile_labels labels, qt x tile_labels <= cap, label_tiles = ceil(n_labels / tile_labels) tiles in the grid's z dimension; qt is the power of
+ *   two in 1..8 (1 for a shared bitmap) with the fewest passes ceil(B / qt) x label_tiles, tile_labels = min(n_labels, cap / qt), among those
+ *   with label_tiles <= VS_FACET_QUANTILE_MAX_LABEL_TILES; of equal ones the smallest qt.  None: regime 1 (global atomics), qt = 8 or 1,
+ *   tile_labels = n_labels, label_tiles = 1.  chunks and rows_per_chunk by vs_value_plan's rule over ceil(B / qt) x label_tiles items.
+ * Kernel (facet_quantiles.hip): the shape of the percentiles' counting kernel.  A lane whose row is in some query's set loads its label once
+ * for the tile; LDS regime: one unsigned compare label - tile0 < tile_labels picks the tile's rows, only those load their value; the tile's
+ * slot prefixes sit in LDS; only slots in use are zeroed and flushed (64-bit atomics on non-zero bins); total and other are counted by the
+ * first label tile, a label's missing rows by the tile that owns the label.  Global regime: 64-bit atomics straight into counts, a cell's slot
+ * prefixes read from global memory.  A 64-row step whose counted rows all fall into one (label, slot, bin) is added once.
+ * Errors (VS_EINVAL before the device is touched; a good call without a GPU is VS_ENODEVICE): everything vs_facet_value_stats and
+ * vs_value_quantiles refuse, n_labels < 1, R outside 1..VS_VALUE_MAX_RANKS, B x n_labels x R x 2048 beyond 2^27 counts.
+ * Not covered: weighted quantiles; more than 65536 labels through the Python facade; two facet fields crossed; the one-process-per-GPU RCCL
+ * path.                                                                                                                                         */
+/* Label tiles a level of the LDS regime takes at most.  Measured, not chosen: on builds of either regime at 21 M rows a tile pass costs 0.06
+ * ms and the regimes meet at 8 tiles a level on a uniform float32 field and at 16 on a field of years. */
+#define VS_FACET_QUANTILE_MAX_LABEL_TILES 16
+VS_API int vs_facet_value_quantile_plan(int64_t n_rows, int32_t B, int32_t n_labels, int32_t R, int level, int per_query, int64_t rows_per_chunk,
+                                        int32_t* out_regime, int32_t* out_qt, int32_t* out_tile_labels, int32_t* out_label_tiles,
+                                        int64_t* out_chunks, int64_t* out_rows_per_chunk);
+VS_API int vs_facet_value_quantiles(const uint32_t* words, int64_t bit0, int64_t ld_words, const uint32_t* and_words, int32_t B,
+                                    const int32_t* labels, int32_t n_labels, const void* values, int dtype, int64_t n_rows, const double* q,
+                                    int method, const int64_t* ranks, int32_t R, int64_t rows_per_chunk, void* out_values, int64_t* out_ranks,
+                                    int64_t* count, int64_t* missing, int64_t* total, int64_t* other, int device, void* stream);
+VS_API int vs_index_facet_value_quantiles(vs_index* index, const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B, const int32_t* labels,
+                                          int32_t n_labels, const void* values, int dtype, const double* q, int method, const int64_t* ranks,
+                                          int32_t R, int64_t rows_per_chunk, void* out_values, int64_t* out_ranks, int64_t* count,
+                                          int64_t* missing, int64_t* total, int64_t* other, void* stream);
+VS_API int vs_facet_value_radix_counts(const uint32_t* words, int64_t bit0, int64_t ld_words, const uint32_t* and_words, int32_t B,
+                                       const int32_t* labels, int32_t n_labels, const void* values, int dtype, int64_t n_rows, int level, int32_t R,
+                                       const uint32_t* slot_prefix, const int32_t* n_slots, int64_t rows_per_chunk, int64_t* counts,
+                                       int64_t* missing, int64_t* total, int64_t* other, int device, void* stream);
+VS_API int vs_index_facet_value_radix_counts(vs_index* index, const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B,
+                                             const int32_t* labels, int32_t n_labels, const void* values, int dtype, int level, int32_t R,
+                                             const uint32_t* slot_prefix, const int32_t* n_slots, int64_t rows_per_chunk, int64_t* counts,
+                                             int64_t* missing, int64_t* total, int64_t* other, void* stream);
 
 /* ---- scores as a field: the exact score of every row of a document set, as a value array (no reference counterpart) -----------------------------
  * vs_index_set_scores: for query b and row r, out_scores [b * ld_scores + r] holds the library's exact score when r is live (not deleted) and in

@@ -40,6 +40,8 @@ VALUE_RADIX_BINS, VALUE_RADIX_LEVELS, VALUE_MAX_RANKS = 2048, 3, 16
 QUANTILE_LOWER, QUANTILE_HIGHER, QUANTILE_NEAREST = 0, 1, 2
 # breakdowns (VS_FACET_VALUE_*): (query, label) records of a workgroup's LDS in the stats kernel, n_labels x (n_edges + 2) cells a query at most
 FACET_VALUE_LDS_RECORDS, FACET_VALUE_MAX_CELLS = 2048, 1 << 22
+# per-label percentiles (VS_FACET_QUANTILE_MAX_LABEL_TILES): label tiles the LDS regime of the counting kernel takes at most
+FACET_QUANTILE_MAX_LABEL_TILES = 16
 # set egress (VS_SET_MAX_*): the most rows vs_set_sample lists per query, the most ids (B x limit) of one vs_set_ids call
 SET_MAX_SAMPLE, SET_MAX_OUT_IDS = 1024, 1 << 27
 
@@ -113,6 +115,15 @@ _SIGNATURES = {
     "vs_index_facet_value_stats": ([_vp, _vp, _i64, _i64, _i32, _vp, _i32, _vp, _int, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp], _int),
     "vs_facet_value_histogram": ([_vp, _i64, _i64, _vp, _i32, _vp, _i32, _vp, _int, _i64, _vp, _i32, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _int,
                                   _vp], _int),
+    "vs_facet_value_quantile_plan": ([_i64, _i32, _i32, _i32, _int, _int, _i64, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32),
+                                      C.POINTER(_i64), C.POINTER(_i64)], _int),
+    "vs_facet_value_quantiles": ([_vp, _i64, _i64, _vp, _i32, _vp, _i32, _vp, _int, _i64, _vp, _int, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _int,
+                                  _vp], _int),
+    "vs_index_facet_value_quantiles": ([_vp, _vp, _i64, _i64, _i32, _vp, _i32, _vp, _int, _vp, _int, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+                                       _int),
+    "vs_facet_value_radix_counts": ([_vp, _i64, _i64, _vp, _i32, _vp, _i32, _vp, _int, _i64, _int, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _int, _vp],
+                                    _int),
+    "vs_index_facet_value_radix_counts": ([_vp, _vp, _i64, _i64, _i32, _vp, _i32, _vp, _int, _int, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp], _int),
     "vs_index_facet_value_histogram": ([_vp, _vp, _i64, _i64, _i32, _vp, _i32, _vp, _int, _vp, _i32, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
                                        _int),
     "vs_set_score_plan": ([_i64, _i32, _i32, _int, _i64, C.POINTER(_i64), C.POINTER(_i64)], _int),

@@ -1625,6 +1625,72 @@ def _quantile_batches(q, ranks, B, call):
     return torch.cat([p[0] for p in parts], dim=1), torch.cat([p[1] for p in parts], dim=1), parts[0][2], parts[0][3]
 
 
+# ---- per-label percentiles: order statistics of a numeric field per facet label (vs_facet_value_quantiles, vs_facet_value_radix_counts) ------
+class FacetValueQuantiles(NamedTuple):
+    """facet_value_quantiles: per (query, label, rank) the order statistic of the values of the set's documents with that label -- values
+    [B, L, R] in the field's type (the missing sentinel where there is no answer), ranks int64 [B, L, R] (-1: no answer); count / missing
+    int64 [B, L]: those documents with / without a value; total / other int64 [B] as in FacetCounts: count.sum(1) + missing.sum(1) + other ==
+    total."""
+    values: Any
+    ranks: Any
+    count: Any
+    missing: Any
+    total: Any
+    other: Any
+
+
+class FacetValuePercentiles(NamedTuple):
+    """percentiles_by_facet / median_by_facet: values [B, L, P] -- float64 for method "linear" (NaN where there is no answer), else the
+    field's type (the missing sentinel there); count / missing int64 [B, L]; total / other int64 [B]."""
+    values: Any
+    count: Any
+    missing: Any
+    total: Any
+    other: Any
+
+
+def facet_value_quantile_plan(n_rows: int, B: int, n_labels: int, R: int, level: int, per_query: bool, rows_per_chunk: int = 0):
+    """The launch of the counting kernel of vs_facet_value_quantiles at a radix level (vs_facet_value_quantile_plan; pure host arithmetic, no
+    GPU needed) -> (regime, qt, tile_labels, label_tiles, chunks, rows_per_chunk): regime 0 = LDS histograms of qt queries x tile_labels labels
+    a workgroup, label_tiles tiles; 1 = global atomics."""
+    regime, qt, tl, lt, chunks, rpc = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int64(0), C.c_int64(0)
+    nat.check(nat.lib().vs_facet_value_quantile_plan(int(n_rows), int(B), int(n_labels), int(R), int(level), 1 if per_query else 0, int(rows_per_chunk),
+                                                     C.byref(regime), C.byref(qt), C.byref(tl), C.byref(lt), C.byref(chunks), C.byref(rpc)))
+    return regime.value, qt.value, tl.value, lt.value, chunks.value, rpc.value
+
+
+def _facet_quantile_args(q, method, ranks, n_labels):
+    """Argument checks of a per-label quantile call that need no device -> (q float64 [R] | None, method code, ranks int64 [R] or [B, L, R] |
+    None)"""
+    if ranks is not None and q is None:
+        r = np.asarray(ranks.detach().cpu().numpy() if _is_torch(ranks) else ranks)
+        if r.ndim == 3:
+            if r.shape[1] != n_labels:
+                raise ValueError(f"ranks holds {r.shape[1]} labels for n_labels = {n_labels}")
+            _, m, flat = _quantile_args(None, method, r.reshape(-1, r.shape[2]))
+            return None, m, flat.reshape(r.shape)
+        if r.ndim != 1:
+            raise ValueError("ranks must be a non-empty [R] or [B, n_labels, R] array")
+        ranks = r
+    return _quantile_args(q, method, ranks)
+
+
+def _facet_quantile_batches(q, ranks, cells, call):
+    """The ranks are served in batches of min(16, 65536 // cells) -- cells = B x n_labels; 65536 x 2048 bins are the 2^27 counts of a call:
+    call(q batch | None, ranks batch [B, L, Rb] | None, Rb) -> the six tensors"""
+    import torch
+    P = q.shape[0] if q is not None else ranks.shape[2]
+    step = max(1, min(MAX_VALUE_RANKS, (1 << 16) // max(cells, 1)))
+    parts = []
+    for j0 in range(0, P, step):
+        j1 = min(P, j0 + step)
+        parts.append(call(np.ascontiguousarray(q[j0:j1]) if q is not None else None,
+                          np.ascontiguousarray(ranks[:, :, j0:j1]) if ranks is not None else None, j1 - j0))
+    if len(parts) == 1:
+        return parts[0]
+    return (torch.cat([p[0] for p in parts], dim=2), torch.cat([p[1] for p in parts], dim=2)) + tuple(parts[0][2:])
+
+
 KMEANS_UPDATE_BATCH = 64                               # clusters whose sums one term_sums call of the update takes
 KMEANS_METRICS = ("dot", "l2")
 
@@ -2064,6 +2130,48 @@ def _value_quantiles(obj, values, q, method, ranks, filter, rows_per_chunk):
             state = value_radix_step(level, counts, R, state, q_dev, method, r_dev, tdt, obj.device)
         return state["values"], state["ranks"], state["count"], missing
     return ValueQuantiles(*_facet_out(values, *_quantile_batches(qa, ra, B, batch)))
+
+
+def _facet_value_quantiles(obj, labels, n_labels, values, q, method, ranks, filter, rows_per_chunk):
+    """_value_quantiles with a (query, label) cell where that has a query: one part runs the one call; more parts count each level on their
+    GPUs, the counts are added on obj's GPU and one value_radix_step over B x n_labels cells runs there."""
+    import torch
+    n = obj.n_rows
+    n_labels, dt, rows_per_chunk, _ = _facet_value_args(labels, n_labels, values, n, rows_per_chunk)
+    qa, method, ra = _facet_quantile_args(q, method, ranks, n_labels)
+    nat.require_device()
+    dev = torch.device("cuda", obj.device)
+    f = _doc_set(filter, n, obj.device)
+    B = _set_args(f, 0)[0]
+    L = n_labels
+    if ra is not None:
+        if ra.ndim == 1:
+            ra = np.ascontiguousarray(np.broadcast_to(ra[None, None, :], (B, L, ra.shape[0])))
+        elif ra.shape[0] != B:
+            raise ValueError(f"ranks holds {ra.shape[0]} rows for {B} queries")
+    tdt = torch.float32 if dt == nat.VAL_F32 else torch.int32
+    up = lambda a: torch.from_numpy(a).to(dev) if a is not None else None
+    cols = (_lab(labels), _val(values))
+    if len(obj._parts) == 1:
+        fused = lambda sh, l, v, fs, row0: _facet_quantile_batches(
+            qa, ra, B * L, lambda qb, rb, R: sh._facet_value_quantiles_call(l, L, v, dt, up(qb), method, up(rb), R, fs, row0, rows_per_chunk))
+        return FacetValueQuantiles(*_facet_out(labels, *_shard_parts(obj, f, cols, fused, n)[0]))
+
+    def batch(qb, rb, R):
+        q_dev, r_dev = up(qb), up(rb)
+        state = tail = None
+        for level in range(nat.VALUE_RADIX_LEVELS):
+            def one(sh, l, v, fs, row0):
+                d = torch.device("cuda", sh.device)
+                sp, ns = (state["slot_prefix"].to(d), state["n_slots"].to(d)) if level else (None, None)
+                return sh._facet_value_radix_counts_call(l, L, v, dt, level, R, sp, ns, fs, row0, rows_per_chunk)
+            counts, *rest = _add_parts(_shard_parts(obj, f, cols, one, n))
+            if level == 0:
+                tail = rest                                        # missing [B, L], total, other [B]
+            state = value_radix_step(level, counts.reshape(B * L, counts.shape[2], counts.shape[3]), R, state, q_dev, method,
+                                     r_dev.reshape(B * L, R) if r_dev is not None else None, tdt, obj.device)
+        return (state["values"].reshape(B, L, R), state["ranks"].reshape(B, L, R), state["count"].reshape(B, L)) + tuple(tail)
+    return FacetValueQuantiles(*_facet_out(labels, *_facet_quantile_batches(qa, ra, B * L, batch)))
 
 
 def _term_agg(obj, spec, filter, ids, rows_per_chunk, extra=()):
@@ -3034,6 +3142,63 @@ class DeviceIndex:
         16.  values, filter, outputs as in ``value_stats``."""
         return _value_quantiles(self, values, q, method, ranks, filter, rows_per_chunk)
 
+    # ---- per-label percentiles (vs_index_facet_value_quantiles, vs_index_facet_value_radix_counts) ------------------------------------------
+    def _facet_value_quantiles_call(self, labels_dev, n_labels, vals_dev, dt, q_dev, method, ranks_dev, R, f, bit0, rows_per_chunk):
+        """One vs_index_facet_value_quantiles call on device buffers -> (values [B, L, R], ranks int64 [B, L, R], count, missing int64 [B, L],
+        total, other int64 [B]) CUDA tensors.  q_dev: float64 [R] or None; ranks_dev: int64 [B, L, R] or None."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        B, set_args = _set_args(f, bit0)
+        vals = torch.empty((B, n_labels, R), dtype=vals_dev.dtype, device=dev)
+        ranks = torch.empty((B, n_labels, R), dtype=torch.int64, device=dev)
+        count, missing = (torch.empty((B, n_labels), dtype=torch.int64, device=dev) for _ in range(2))
+        total, other = (torch.empty(B, dtype=torch.int64, device=dev) for _ in range(2))
+        nat.check(nat.lib().vs_index_facet_value_quantiles(self._h, *set_args, _ptr(labels_dev), n_labels, _ptr(vals_dev), dt,
+                                                           _ptr(q_dev) if q_dev is not None else None, method,
+                                                           _ptr(ranks_dev) if ranks_dev is not None else None, R, rows_per_chunk, _ptr(vals),
+                                                           _ptr(ranks), _ptr(count), _ptr(missing), _ptr(total), _ptr(other),
+                                                           current_stream(self.device)))
+        return vals, ranks, count, missing, total, other
+
+    def _facet_value_radix_counts_call(self, labels_dev, n_labels, vals_dev, dt, level, R, slot_prefix, n_slots, f, bit0, rows_per_chunk):
+        """One vs_index_facet_value_radix_counts call -> (counts int64 [B, L, S, bins], missing int64 [B, L], total, other int64 [B]) CUDA
+        tensors; only counts below level 0.  slot_prefix int32 [B x L, R] / n_slots int32 [B x L]: the state of the step above, on this
+        index's device (None at level 0)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        B, set_args = _set_args(f, bit0)
+        bins = nat.VALUE_RADIX_BINS if level < 2 else nat.VALUE_RADIX_BINS // 2
+        counts = torch.empty((B, n_labels, 1 if level == 0 else R, bins), dtype=torch.int64, device=dev)
+        missing = torch.empty((B, n_labels), dtype=torch.int64, device=dev) if level == 0 else None
+        total, other = (torch.empty(B, dtype=torch.int64, device=dev) if level == 0 else None for _ in range(2))
+        opt = lambda t, use: _ptr(t) if use else None
+        nat.check(nat.lib().vs_index_facet_value_radix_counts(self._h, *set_args, _ptr(labels_dev), n_labels, _ptr(vals_dev), dt, level, R,
+                                                              opt(slot_prefix, level), opt(n_slots, level), rows_per_chunk, _ptr(counts),
+                                                              opt(missing, level == 0), opt(total, level == 0), opt(other, level == 0),
+                                                              current_stream(self.device)))
+        return (counts, missing, total, other) if level == 0 else (counts,)
+
+    def facet_value_quantiles(self, labels, n_labels: int, values, q=None, method: str = "lower", ranks=None, filter=None,
+                              rows_per_chunk: int = 0) -> FacetValueQuantiles:
+        """Exact order statistics of a numeric field per facet label over a document set, three counting passes for all labels ->
+        FacetValueQuantiles(values, ranks [B, n_labels, R], count, missing [B, n_labels], total, other [B]).  q / method / ranks as in
+        ``value_quantiles`` (ranks: [R] or [B, n_labels, R]), applied to each label's count; labels, values, filter, outputs as in
+        ``facet_value_stats``.  The ranks are served in batches of min(16, 65536 // (B x n_labels)), so that the counts of a batch stay
+        within 2^27 (the percentiles' 1 GiB rule); B x n_labels itself may not pass 65536."""
+        return _facet_value_quantiles(self, labels, n_labels, values, q, method, ranks, filter, rows_per_chunk)
+
+    def facet_value_radix_counts(self, labels, n_labels: int, values, level: int, R: int, slot_prefix=None, n_slots=None, filter=None,
+                                 rows_per_chunk: int = 0):
+        """One radix level's digit counts per (query, label) (vs_index_facet_value_radix_counts) -> (counts int64 [B, n_labels, S, bins],
+        missing [B, n_labels], total, other [B]) at level 0, (counts,) below.  slot_prefix int32 [B x n_labels, R] / n_slots int32 [B x
+        n_labels]: the state ``value_radix_step`` returned for the level above, taken over B x n_labels cells."""
+        n_labels, dt, rows_per_chunk, _ = _facet_value_args(labels, n_labels, values, self.n_rows, rows_per_chunk)
+        nat.require_device()
+        to = lambda t: None if t is None else (t if _is_torch(t) else _on(t, self.device)).to(f"cuda:{self.device}").contiguous()
+        one = lambda sh, l, v, f, row0: sh._facet_value_radix_counts_call(l, n_labels, v, dt, int(level), int(R), to(slot_prefix), to(n_slots), f,
+                                                                          row0, rows_per_chunk)
+        return _facet_out(labels, *_shard_parts(self, filter, (_lab(labels), _val(values)), one, self.n_rows)[0])
+
     # ---- term aggregations: what a document set is about (vs_index_term_counts, vs_index_term_counts_ids) ---------------------------------
     def _term_set_call(self, spec, f, bit0, rows_per_chunk, extra=()):
         """One bitmap-driven call of a term aggregation (spec.bitmap) on device buffers and torch's current stream -> ([B, V], total [B]) int64
@@ -3494,6 +3659,13 @@ class ShardGroup:
         slice of the values and its bit range of the filter, the counts are added on the first shard's GPU, one step there picks each rank's
         bin and names the next level's slots.  Integer counts: equal to the unsharded index bit for bit."""
         return _value_quantiles(self, values, q, method, ranks, filter, rows_per_chunk)
+
+    def facet_value_quantiles(self, labels, n_labels: int, values, q=None, method: str = "lower", ranks=None, filter=None,
+                              rows_per_chunk: int = 0) -> FacetValueQuantiles:
+        """DeviceIndex.facet_value_quantiles over the group's rows: per level every shard counts its slice on its GPU, the counts are added on
+        the first shard's GPU, one value_radix_step over B x n_labels cells runs there and its state goes back to the shards.  Equal to the
+        unsharded index bit for bit."""
+        return _facet_value_quantiles(self, labels, n_labels, values, q, method, ranks, filter, rows_per_chunk)
 
     # ---- term aggregations ------------------------------------------------------------------------------------------------------------------
     def term_counts(self, filter=None, ids=None, rows_per_chunk: int = 0) -> TermCounts:

@@ -26,6 +26,7 @@ from ...device_index import Assignment, KMeansResult, KMEANS_UPDATE_BATCH, kmean
 from ...device_index import SortedResults, ValueHistogram, ValueStats, value_column, _value_bounds, _value_dtype, _value_edges, _value_topk_args
 from ...device_index import ValuePercentiles, _percentile_args, quantile_lerp
 from ...device_index import FacetValueHistogram, FacetValueStats
+from ...device_index import FacetValuePercentiles, MAX_VALUE_RANKS
 from ...device_index import SetIds, SetSample, _set_sample_args, _set_window_args
 
 logger = logging.getLogger(__name__)
@@ -935,6 +936,79 @@ class Index:
                score_scratch: int = SCORE_SCRATCH_BYTES) -> ValuePercentiles:
         """``percentiles(field, [50], ...)``: the median of value field `field` (or of the scores: SCORE) over a document set, values [B, 1]."""
         return self.percentiles(field, [50], q_embs=q_embs, min_score=min_score, filter=filter, method=method, score_scratch=score_scratch)
+
+    # (query, label, rank) cells a per-label percentile call may take: x 2048 bins = the 2^27 counts of the percentiles' 1 GiB rule
+    FACET_QUANTILE_CELLS = 65536
+
+    def percentiles_by_facet(self, value_field: str, facet_field: str, pcts, q_embs=None, min_score=None, filter=None, method: str = "linear",
+                             score_scratch: int = SCORE_SCRATCH_BYTES) -> FacetValuePercentiles:
+        """Exact percentiles of value field `value_field` per label of facet field `facet_field` ("groups" = the group ids) over a document
+        set, three counting passes for all labels -> FacetValuePercentiles(values [B, n_labels, P], count, missing [B, n_labels], total,
+        other [B]) -- "the median price per category of the matches".  pcts and method as in ``percentiles``, applied to each label's count;
+        a label without values gives NaN / the missing sentinel; a document without a label counts into `other` only.  The set as in
+        ``value_stats``.  The work is split so that queries x labels x ranks of a pass stay within 65536: first over the queries, then over
+        the percentiles (16 a pass at most).  More than 65536 labels are not covered and raise ValueError.  Works on a row-sharded index as
+        well.  value_field=SCORE: the median, p90, ... score per label."""
+        if value_field is SCORE:
+            self._score_check(q_embs, score_scratch)
+            q = _percentile_args(pcts, method)
+            self._facet_check(facet_field)
+            codes, n_labels, _ = self._facet_field(facet_field)
+            self._facet_quantile_check(n_labels)
+            return self._over_scores(q_embs, min_score, filter, score_scratch,
+                                     lambda t, v, f: self._percentiles_by_facet_of(t, codes, n_labels, v, q, method, f))
+        self._value_check(value_field, q_embs, min_score)
+        q = _percentile_args(pcts, method)
+        self._facet_check(facet_field)
+        v = self._value_field(value_field)
+        codes, n_labels, _ = self._facet_field(facet_field)
+        self._facet_quantile_check(n_labels)
+        filter = self._value_set(q_embs, min_score, filter)
+        target = self._explain_target()[0]
+        if filter is not None:
+            from ...doc_filter import as_doc_filter
+            filter = as_doc_filter(filter, self._n_rows(), device=target.device)
+        return FacetValuePercentiles(*(self._to_api(t) for t in self._percentiles_by_facet_of(target, codes, n_labels, v, q, method, filter)))
+
+    def _facet_quantile_check(self, n_labels):
+        if n_labels > self.FACET_QUANTILE_CELLS:
+            raise ValueError(f"percentiles_by_facet: n_labels = {n_labels} is more than {self.FACET_QUANTILE_CELLS} labels, which is not covered "
+                             f"(one query's counts of one rank would pass 2^27): break the facet field up, or filter by from_labels and use percentiles()")
+
+    def _percentiles_by_facet_of(self, target, codes, n_labels, v, q, method, f):
+        """the per-label percentiles of one value array over one DocFilter (or None), on the target's GPU, in passes within FACET_QUANTILE_CELLS"""
+        from ...doc_filter import DocFilter
+        n, P = self._n_rows(), int(q.shape[0])
+        per_query = f is not None and f.per_query
+        B = f.n_queries if per_query else 1
+        bt = max(1, min(B, self.FACET_QUANTILE_CELLS // (n_labels * min(P, MAX_VALUE_RANKS))))
+        rp = max(1, min(MAX_VALUE_RANKS, self.FACET_QUANTILE_CELLS // (bt * n_labels)))
+        blocks = []
+        for b0 in range(0, B, bt):
+            fb = DocFilter(f.words[b0:b0 + bt], n) if per_query else f
+            vals, first = [], None
+            for j0 in range(0, P, rp):
+                qj = np.ascontiguousarray(q[j0:j0 + rp])
+                if method != "linear":
+                    lo = target.facet_value_quantiles(codes, n_labels, v, q=qj, method=method, filter=fb)
+                    vals.append(lo.values)
+                else:
+                    lo = target.facet_value_quantiles(codes, n_labels, v, q=qj, method="lower", filter=fb)
+                    hi = target.facet_value_quantiles(codes, n_labels, v, q=qj, method="higher", filter=fb)
+                    pos = qj[None, None, :] * (lo.count.cpu().numpy().astype(np.float64) - 1.0)[:, :, None]
+                    x = quantile_lerp(lo.values.cpu().numpy(), hi.values.cpu().numpy(), pos - np.floor(pos))
+                    if v.dtype == torch.int32:                      # (an int32 field's sentinel is a number: no answer is NaN here)
+                        x = np.where(lo.ranks.cpu().numpy() < 0, np.nan, x)
+                    vals.append(torch.from_numpy(x).to(lo.count.device))
+                first = first or lo
+            blocks.append((torch.cat(vals, dim=2), first.count, first.missing, first.total, first.other))
+        return FacetValuePercentiles(*(torch.cat(x) for x in zip(*blocks)))
+
+    def median_by_facet(self, value_field: str, facet_field: str, q_embs=None, min_score=None, filter=None, method: str = "linear",
+                        score_scratch: int = SCORE_SCRATCH_BYTES) -> FacetValuePercentiles:
+        """``percentiles_by_facet(value_field, facet_field, [50], ...)``: the median per label, values [B, n_labels, 1]."""
+        return self.percentiles_by_facet(value_field, facet_field, [50], q_embs=q_embs, min_score=min_score, filter=filter, method=method,
+                                         score_scratch=score_scratch)
 
     def _added_values(self, values, n_add):
         """values= of add() / update() -> {name: ndarray [n_add] in the field's type}, or None for an index without value fields.  Raises

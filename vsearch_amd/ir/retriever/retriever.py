@@ -255,6 +255,34 @@ class Retriever(BiEncoder):
         index, q_emb, filter = self._match_set(queries, index, filter, must, must_not, should, min_should, dropout, a, batch_size)
         return index.histogram_by_facet(value_field, facet_field, edges, q_embs=q_emb, min_score=min_score, filter=filter)
 
+    def retrieve_percentiles_by_facet(self, queries: Union[List[str], np.ndarray, T], value_field: str, facet_field: str, pcts, min_score=0.0,
+                                      topn: int = 10, min_count: int = 1, method: str = "linear", dropout: float = 0, a: int = None,
+                                      index: Index = None, batch_size: int = 32, filter=None, must=None, must_not=None, should=None,
+                                      min_should: int = None):
+        """Exact percentiles of value field `value_field` per label of `facet_field` over each query's matches --
+        ``Index.percentiles_by_facet`` behind the query encoder, the match set as in ``retrieve_histogram`` -> (rows, totals): rows[b] lists
+        (name, docs, count, percentiles) for the `topn` labels with the most documents of the set (docs = count + missing, at least
+        max(min_count, 1)), docs descending then label ascending; name is the label's code where the field has no names; percentiles is the
+        list of the P values (NaN / the missing sentinel where no document of the label has a value); totals[b] is the number of matches."""
+        from ...device_index import facet_topn, _topn_args
+        topn, min_count = _topn_args(topn, min_count)
+        index, q_emb, filter = self._match_set(queries, index, filter, must, must_not, should, min_should, dropout, a, batch_size)
+        res = index.percentiles_by_facet(value_field, facet_field, pcts, q_embs=q_emb, min_score=min_score, filter=filter, method=method)
+        docs = res.count + res.missing
+        top_l, top_c = facet_topn(docs if docs.is_cuda else docs.numpy(), topn, min_count, device=index._explain_target()[1])
+        top_l, top_c = (x.cpu().numpy() if isinstance(x, torch.Tensor) else x for x in (top_l, top_c))
+        names = index.facet_names(facet_field)
+        count, vals = res.count.cpu().numpy(), res.values.cpu().numpy()
+        rows = []
+        for b in range(top_l.shape[0]):
+            out = []
+            for l, d in zip(top_l[b].tolist(), top_c[b].tolist()):
+                if l < 0:
+                    continue
+                out.append((names[l] if names is not None else l, d, int(count[b, l]), vals[b, l].tolist()))
+            rows.append(out)
+        return rows, res.total.cpu().tolist()
+
     def retrieve_percentiles(self, queries: Union[List[str], np.ndarray, T], field: str, pcts, min_score=0.0, method: str = "linear",
                              dropout: float = 0, a: int = None, index: Index = None, batch_size: int = 32, filter=None, must=None, must_not=None,
                              should=None, min_should: int = None):
