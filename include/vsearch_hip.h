@@ -871,6 +871,42 @@ VS_API int vs_index_live_bitmap(const vs_index* index, uint32_t* out_words, int6
  *   bytes needed) when HBM cannot hold them -- setting option "blocked_postings" to 0 on `src` releases its postings copy.  Blocking.  */
 VS_API int vs_index_compact(const vs_index* src, int64_t rows_extra, int64_t packets_extra, int device, vs_index** out, int64_t* out_old_ids);
 
+/* ---- index pruning: re-sparsify a stored index to its top-m cells (embed(..., topk = m), encoder/vdr.py:102-168: mask = bow_mask | topk_mask) -----
+ * The reference fixes a document's sparsity when it embeds it.  For m <= the topk an index was built with, the m largest entries of a row's
+ * full embedding are among its stored ones, and a lexical cell outside them is not larger than the smallest: the index built with topk = m is
+ * a function of the stored index and of the bag-of-token rows (the protect index).  vs_index_prune makes it on the GPU: a NEW index holding,
+ * for every row of a CSR index, a subset of its stored cells.  Rows keep their ids; the source is untouched.
+ * For row r with stored cells (col_t, v_t), t = 0..n-1 in STORED ORDER (the order vs_index_export_csr returns; padding cells are not cells):
+ *   - eligible_t = col_keep[col_t] and, if min_value is given (not NaN), v_t >= min_value -- compared on the fp32-widened stored value; a NaN
+ *     value is never >=.
+ *   - key_t = the order key of the numeric fields on the fp32-widened stored value (value_key_f32 of the library's value_check.h): -0.0 and
+ *     +0.0 tie, -inf < finite < +inf, a NaN has key 0 and ranks last.  fp16 -> fp32 is monotone: a fp16 store ranks as its halves do.
+ *   - rank: among eligible cells, by (key descending, t ascending); top_t = rank < topk.  topk = 0: no cut (every eligible cell is top).
+ *   - protected_t = row r of `protect` stores col_t.  protect: a binary or valued CSR index with the same n_rows and n_cols on the same
+ *     device (any stored cell counts, whatever its value), or NULL.
+ *   - kept_t = eligible_t && (top_t || protected_t): the reference's logical_or(bow_mask, topk_mask) -- the top m is taken over all eligible
+ *     cells, protected cells are added and do not count against m.
+ *   - the new row = the kept cells in stored order, 8 to a packet, the last packet padded with column id n_cols and value 0; a row with no
+ *     kept cell has 0 packets.  Values move as stored bits.
+ *   - rows are 1:1 with the source, deleted rows included; the new handle carries the source's tombstones (vs_index_restore_rows brings a
+ *     deleted row back pruned).  It has no postings copy yet (vs_index_prepare).
+ *   - a binary index (VS_NONE): topk > 0 or a min_value is VS_EINVAL (every value is 1); col_keep alone is allowed.  A dense matrix index:
+ *     VS_EUNSUPPORTED; a dense index stored as packets is pruned like any CSR index and stays reported VS_KIND_DENSE.
+ * col_keep: uint32 bitmap of n_cols bits (bit c & 31 of word c >> 5), host or device on src's device; NULL: every column.  out_kept: int32
+ * [n_rows] kept cells per row, host or device on src's device, may be NULL; col_keep and out_kept together are both host or both device
+ * pointers.  topk in 0..65535.  rows_extra / packets_extra / device as in vs_index_compact: spare capacity for vs_index_append_csr, the same
+ * 2^32 limits, VS_ENOMEM naming the bytes when HBM cannot hold source and result, the result moved to GPU `device` by peer copies.  nnz = the
+ * sum of out_kept.  Three steps on src's GPU: select (a wave a row: rows of up to reg_cells cells are read once and held in registers, longer
+ * rows are re-read every pass; an exact radix select on the 32-bit keys; one keep byte a source packet), scan, pack.  Blocking.
+ * vs_prune_plan: pure host arithmetic, no device -- reg_cells (the register path's longest row, a constant of the build), the scratch the
+ * call allocates next to both indexes (a keep byte a source packet + 4 bytes a row + the scan's block sums: 2 GB at 21 M rows x 96 packets)
+ * and the LDS of a select workgroup.  Any output may be NULL.  The shape and rule errors of vs_index_prune: n_cols > 65535 VS_EUNSUPPORTED,
+ * topk outside 0..65535 or topk > 0 on VS_NONE: VS_EINVAL.                                                                                  */
+VS_API int vs_prune_plan(int64_t n_rows, int64_t n_packets, int32_t n_cols, int store_dtype, int32_t topk, int has_protect, int32_t* out_reg_cells,
+                         int64_t* out_scratch_bytes, int32_t* out_lds_bytes);
+VS_API int vs_index_prune(const vs_index* src, int32_t topk, float min_value, const uint32_t* col_keep, const vs_index* protect, int64_t rows_extra,
+                          int64_t packets_extra, int device, vs_index** out, int32_t* out_kept);
+
 /* ---- term constraints: must / must-not / should filters built from the index's own columns (no reference counterpart) --------------------
  * A row HAS term c (a column id in [0, n_cols)) iff it stores column c with a non-zero value; under a threshold thr, iff the stored value
  * v satisfies v >= thr (an fp16 store widens exactly, as vs_index_get_rows; a binary index stores 1; a stored zero counts under thr <= 0).

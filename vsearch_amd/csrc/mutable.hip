@@ -1,6 +1,7 @@
 // mutable.hip -- the writable index: tombstones kept in the handle (delete / restore rows, applied by every search as a document filter)
 // and compaction (a new index of the live rows, with spare capacity for appends).  No reference counterpart: the reference's index is
 // a tensor that is rebuilt (index.py:163-179).  Nothing here touches a walk or scan kernel: deletion reaches them as FilterArgs.
+#include "block_scan.h"
 #include "common.h"
 
 #include <algorithm>
@@ -324,38 +325,12 @@ extern "C" int vs_index_live_bitmap(const vs_index* idx, uint32_t* out_words, in
 // =================================================================================================
 namespace {
 
-constexpr int kScanItems = 16;                       // rows per thread of a scan block: 256 x 16 = 4096 rows a block
-constexpr int kScanRows = 256 * kScanItems;
-
-__device__ __forceinline__ uint2 add2(uint2 a, uint2 b) { return make_uint2(a.x + b.x, a.y + b.y); }
-
+// (the scan: block_scan.h -- blocks of kScanRows rows, block_excl_scan inside a block, scan_block_sums_kernel over the block sums)
 // (live?, packets) of row r; a dead row and a row past the end count nothing.  pk == nullptr (dense matrix): no packets
 __device__ __forceinline__ uint2 row_stat(const uint32_t* live, const uint32_t* pk, int64_t r, int64_t n_rows) {
     if (r >= n_rows) return make_uint2(0u, 0u);
     if (live && !((live[r >> 5] >> (r & 31)) & 1u)) return make_uint2(0u, 0u);
     return make_uint2(1u, pk ? pk[r + 1] - pk[r] : 0u);
-}
-
-// exclusive scan over the NW waves of a workgroup; *total = the workgroup's sum.  sh: [NW] uint2 of LDS
-template <int NW>
-__device__ __forceinline__ uint2 block_excl_scan(uint2 v, uint2* sh, uint2* total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint2 inc = v;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t a = __shfl_up(inc.x, o, 64), b = __shfl_up(inc.y, o, 64);
-        if (lane >= o) { inc.x += a; inc.y += b; }
-    }
-    if (lane == 63) sh[w] = inc;
-    __syncthreads();
-    uint2 base = make_uint2(0u, 0u), tot = make_uint2(0u, 0u);
-#pragma unroll
-    for (int i = 0; i < NW; ++i) {
-        if (i < w) base = add2(base, sh[i]);
-        tot = add2(tot, sh[i]);
-    }
-    __syncthreads();                                  // (sh is written again by the caller's next round)
-    *total = tot;
-    return make_uint2(base.x + inc.x - v.x, base.y + inc.y - v.y);
 }
 
 // step 1a: (live rows, their packets) of every block of kScanRows rows
@@ -367,21 +342,6 @@ __global__ __launch_bounds__(256) void compact_sums_kernel(const uint32_t* live,
     uint2 tot;
     (void)block_excl_scan<4>(acc, sh, &tot);
     if (threadIdx.x == 0) sums[blockIdx.x] = tot;
-}
-
-// step 1b: exclusive scan of the block sums in place (one workgroup walks them 1024 at a time); total[0] = (live rows, packets) of the index
-__global__ __launch_bounds__(1024) void compact_scan_sums_kernel(uint2* sums, int64_t n_blocks, uint2* total) {
-    __shared__ uint2 sh[16];
-    uint2 carry = make_uint2(0u, 0u);
-    for (int64_t b0 = 0; b0 < n_blocks; b0 += 1024) {
-        const int64_t b = b0 + threadIdx.x;
-        const uint2 v = b < n_blocks ? sums[b] : make_uint2(0u, 0u);
-        uint2 tot;
-        const uint2 ex = block_excl_scan<16>(v, sh, &tot);
-        if (b < n_blocks) sums[b] = add2(carry, ex);
-        carry = add2(carry, tot);
-    }
-    if (threadIdx.x == 0) total[0] = carry;
 }
 
 // step 1c: every live row learns its new row id j and first packet: old_ids[j] = row, new_pk[j] = packets of the live rows before it
@@ -464,6 +424,10 @@ __global__ __launch_bounds__(256) void compact_nnz_kernel(const uint32_t* pk, in
     if ((threadIdx.x & 63) == 0 && nnz) atomicAdd(out, nnz);
 }
 
+}  // namespace
+
+namespace vs {
+
 int pick_lanes(int64_t n_packets, int64_t n_rows) {             // (csr_index.hip: pick_lanes_per_row)
     const double mp = n_rows > 0 ? (double)n_packets / (double)n_rows : 1.0;
     int g = 4;
@@ -490,7 +454,7 @@ int move_csr(const vs_index* a, int device, vs_index** out) {
     return VS_OK;
 }
 
-}  // namespace
+}  // namespace vs
 
 extern "C" int vs_index_compact(const vs_index* src, int64_t rows_extra, int64_t packets_extra, int device, vs_index** out, int64_t* out_old_ids) {
     VS_TRY(need_device());
@@ -515,7 +479,7 @@ extern "C" int vs_index_compact(const vs_index* src, int64_t rows_extra, int64_t
     VS_TRY(sums.alloc((size_t)(n_blocks + 1) * 8));
     uint2* d_sums = sums.as<uint2>();
     hipLaunchKernelGGL(compact_sums_kernel, dim3((unsigned)n_blocks), dim3(256), 0, 0, live, pk, n, d_sums);
-    hipLaunchKernelGGL(compact_scan_sums_kernel, dim3(1), dim3(1024), 0, 0, d_sums, n_blocks, d_sums + n_blocks);
+    hipLaunchKernelGGL(scan_block_sums_kernel<0>, dim3(1), dim3(1024), 0, 0, d_sums, n_blocks, d_sums + n_blocks);
     VS_HIP(hipGetLastError());
     uint32_t tot[2] = {0u, 0u};
     VS_HIP(hipMemcpy(tot, d_sums + n_blocks, 8, hipMemcpyDeviceToHost));

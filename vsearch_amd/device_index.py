@@ -164,6 +164,65 @@ def _compact_args(rows_extra, packets_extra):
     return int(rows_extra), int(packets_extra)
 
 
+def _prune_args(topk, min_value):
+    """The cut rules of prune() -> (topk for the library: 0 = no cut, min_value: NaN = none); checked before the library is reached."""
+    if topk is None:
+        topk = 0
+    if isinstance(topk, bool) or not isinstance(topk, (int, np.integer)):
+        raise TypeError(f"topk must be an int or None, got {type(topk).__name__}")
+    if topk < 0 or topk > 65535:
+        raise ValueError(f"topk must be in 0..65535 (0 / None: no cut), got {topk}")
+    if min_value is None:
+        return int(topk), float("nan")
+    if isinstance(min_value, bool) or not isinstance(min_value, (int, float, np.integer, np.floating)):
+        raise TypeError(f"min_value must be a number or None, got {type(min_value).__name__}")
+    if np.isnan(min_value):
+        raise ValueError("min_value must not be NaN (None: no threshold)")
+    return int(topk), float(np.float32(min_value))
+
+
+def _col_mask(cols, n_cols, name):
+    """column ids (integers, 1-D) or a bool mask [n_cols] -> bool numpy [n_cols]"""
+    if _is_torch(cols):
+        cols = cols.detach().cpu().numpy()
+    a = np.asarray(cols)
+    if a.dtype == np.bool_:
+        if a.shape != (n_cols,):
+            raise ValueError(f"a bool {name} mask must have shape ({n_cols},), got {a.shape}")
+        return a.copy()
+    if a.size == 0:
+        return np.zeros(n_cols, dtype=bool)
+    if not np.issubdtype(a.dtype, np.integer):
+        raise TypeError(f"{name} must be integer column ids or a bool mask, got {a.dtype}")
+    if a.ndim != 1:
+        raise ValueError(f"{name} must be a 1-D list of column ids, got {a.ndim} dimensions")
+    if a.min() < 0 or a.max() >= n_cols:
+        raise ValueError(f"{name} holds a column outside [0, {n_cols})")
+    m = np.zeros(n_cols, dtype=bool)
+    m[a] = True
+    return m
+
+
+def _col_keep_words(n_cols, keep_cols=None, drop_cols=None):
+    """col_keep of vs_index_prune: uint32 words, bit c = column c may stay (keep_cols minus drop_cols) -- None when every column stays"""
+    if keep_cols is None and drop_cols is None:
+        return None
+    m = np.ones(n_cols, dtype=bool) if keep_cols is None else _col_mask(keep_cols, n_cols, "keep_cols")
+    if drop_cols is not None:
+        m &= ~_col_mask(drop_cols, n_cols, "drop_cols")
+    bits = np.zeros(((n_cols + 31) // 32) * 32, dtype=np.uint8)
+    bits[:n_cols] = m
+    return np.ascontiguousarray(np.packbits(bits, bitorder="little").view(np.uint32))
+
+
+def prune_plan(n_rows, n_packets, n_cols, store_dtype, topk=0, has_protect=False):
+    """vs_prune_plan (pure host arithmetic) -> (reg_cells, scratch_bytes, lds_bytes)"""
+    reg, scratch, lds = C.c_int32(0), C.c_int64(0), C.c_int32(0)
+    nat.check(nat.lib().vs_prune_plan(int(n_rows), int(n_packets), int(n_cols), int(store_dtype), int(topk), 1 if has_protect else 0, C.byref(reg),
+                                      C.byref(scratch), C.byref(lds)))
+    return reg.value, scratch.value, lds.value
+
+
 def _by_example_args(ids, weights=None, q=None, k=None, a=None):
     """Argument checks of queries_from_rows() / search_by_example() that need no device -> (B, m, on_device)"""
     on_dev = _int64_ids(ids, 2)
@@ -2784,6 +2843,38 @@ class DeviceIndex:
             nat.check(nat.lib().vs_index_compact(*args))
         return DeviceIndex(h), old
 
+    def prune(self, topk=None, min_value=None, keep_cols=None, drop_cols=None, protect=None, rows_extra: int = 0, packets_extra: int = 0,
+              device: int = None):
+        """-> (new DeviceIndex, kept int32 numpy [n_rows]: the cells every row keeps).  The new index holds, for every row, the stored cells
+        that are eligible -- column in keep_cols (ids or a bool mask [n_cols]; None: all) and not in drop_cols, value >= min_value -- and either
+        among the row's topk largest eligible values (ties: the earlier stored cell) or stored by the same row of `protect` (a DeviceIndex of
+        the same shape on the same GPU, binary or valued: the reference's bow_mask | topk_mask); cells keep their stored order and bits
+        (vs_index_prune).  Rows keep their ids, deleted rows stay deleted; this index is untouched.  topk / min_value on a binary index raise
+        ValueError, a dense matrix index NotImplementedError.  rows_extra / packets_extra / device as in compact(), and compact()'s retry: if
+        HBM cannot hold both, this index's postings copy is dropped (prepare() rebuilds it) and the call retried once."""
+        topk, min_value = _prune_args(topk, min_value)
+        rows_extra, packets_extra = _compact_args(rows_extra, packets_extra)
+        if protect is not None and not isinstance(protect, DeviceIndex):
+            raise TypeError(f"protect must be a DeviceIndex, got {type(protect).__name__}")
+        nat.require_device()
+        info = self.info()
+        words = _col_keep_words(int(info.n_cols), keep_cols, drop_cols)
+        device = self.device if device is None else int(device)
+        kept = np.zeros(int(info.n_rows), dtype=np.int32)
+        h = C.c_void_p()
+        args = (self._h, topk, C.c_float(min_value), C.c_void_p(words.ctypes.data) if words is not None else None,
+                protect._h if protect is not None else None, rows_extra, packets_extra, device, C.byref(h),
+                C.c_void_p(kept.ctypes.data) if kept.size else None)
+        try:
+            nat.check(nat.lib().vs_index_prune(*args))
+        except MemoryError:
+            if not self.info().aux_bytes:
+                raise
+            self.set_option("blocked_postings", 0)             # releases the copy; back to auto for the next prepare()
+            self.set_option("blocked_postings", -1)
+            nat.check(nat.lib().vs_index_prune(*args))
+        return DeviceIndex(h), kept
+
     # ---- term constraints (vsearch_amd.doc_filter.DocFilter.from_terms) ------------------------------
     def _term_words(self, cols, thr=None, want_df=False, live_only=True, ld=None):
         info = self.info()
@@ -3504,6 +3595,25 @@ class ShardGroup:
             olds.append(old + row0)
             row0 += s.n_rows
         return ShardGroup(new), (np.concatenate(olds) if olds else np.zeros(0, dtype=np.int64))
+
+    def prune(self, topk=None, min_value=None, keep_cols=None, drop_cols=None, protect=None, rows_extra: int = 0, packets_extra: int = 0):
+        """DeviceIndex.prune on every shard's own GPU -> (new ShardGroup, kept int32 numpy over the group's rows).  protect: a ShardGroup cut
+        at the same rows, shard i on shard i's GPU.  The spare capacity goes to the last shard."""
+        rows_extra, packets_extra = _compact_args(rows_extra, packets_extra)
+        if protect is not None:
+            if not isinstance(protect, ShardGroup):
+                raise TypeError(f"protect must be a ShardGroup, got {type(protect).__name__}")
+            mine, theirs = [s.n_rows for s in self._shards], [s.n_rows for s in protect._shards]
+            if mine != theirs:
+                raise ValueError(f"the protect group is cut into rows {theirs}, this group into {mine}: shard i protects shard i")
+        new, kepts = [], []
+        for i, s in enumerate(self._shards):
+            last = i == len(self._shards) - 1
+            c, kept = s.prune(topk, min_value, keep_cols, drop_cols, protect._shards[i] if protect is not None else None,
+                              rows_extra if last else 0, packets_extra if last else 0)
+            new.append(c)
+            kepts.append(kept)
+        return ShardGroup(new), (np.concatenate(kepts) if kepts else np.zeros(0, dtype=np.int32))
 
     # ---- term constraints -----------------------------------------------------------------------------------
     def _term_words(self, cols, thr=None, want_df=False, live_only=True, ld=None):

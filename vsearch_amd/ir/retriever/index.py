@@ -12,6 +12,7 @@ Same names, constructor arguments and return conventions as ``src.ir.retriever.i
 """
 from __future__ import annotations
 
+import copy
 import glob
 import json
 import logging
@@ -28,6 +29,7 @@ from ...device_index import ValuePercentiles, _percentile_args, quantile_lerp
 from ...device_index import FacetValueHistogram, FacetValueStats
 from ...device_index import FacetValuePercentiles, MAX_VALUE_RANKS
 from ...device_index import SetIds, SetSample, _set_sample_args, _set_window_args
+from ...device_index import _col_mask
 
 logger = logging.getLogger(__name__)
 
@@ -1418,6 +1420,55 @@ class Index:
         if offsets is not None:
             self.offsets = offsets
         return torch.from_numpy(old)
+
+    def pruned(self, topk=None, min_value=None, drop_columns=None, keep_columns=None, max_df=None, protect=None):
+        """A NEW index of the same class holding, for every document, a subset of its stored cells (vs_index_prune on the GPU; this index is
+        left exactly as it was): the cells whose column is in keep_columns (ids or a bool mask [V]; None: all), not in drop_columns and not
+        more frequent than max_df, whose value is >= min_value, and that are among the document's `topk` largest such cells -- or that the
+        same document of `protect` stores (a BoTIndex / SparseIndex of the same rows: the reference's bow_mask | topk_mask at topk = m,
+        vdr.py:152-169, made from the index built at topk = 768).  max_df: a fraction of the live documents (float in (0, 1]) or a count
+        (int): the columns more than that many live documents have are dropped, taken from term_counts().  Ids do not move: the new index
+        shares the text store, the groups, the facet and the value fields, and carries the deletions; a row-sharded index is pruned shard by
+        shard on its GPUs (protect row-sharded the same way).  A dense index on the matrix cores raises NotImplementedError."""
+        target, gpu_ord = self._explain_target()
+        sharded = isinstance(target, ShardGroup)
+        n_cols = int((target._shards[0] if sharded else target).info().n_cols)
+        drop = None if drop_columns is None else _col_mask(drop_columns, n_cols, "drop_columns")
+        if max_df is not None:
+            if isinstance(max_df, bool) or not isinstance(max_df, (int, float, np.integer, np.floating)):
+                raise TypeError(f"max_df must be a fraction (float) or a count (int), got {type(max_df).__name__}")
+            if isinstance(max_df, (float, np.floating)):
+                if not 0.0 < max_df <= 1.0:
+                    raise ValueError(f"a fractional max_df must be in (0, 1], got {max_df}")
+                limit = float(max_df) * self.n_live
+            else:
+                if max_df < 0:
+                    raise ValueError(f"max_df must be >= 0, got {max_df}")
+                limit = int(max_df)
+            frequent = (self.term_counts().counts[0] > limit).cpu().numpy()
+            drop = frequent if drop is None else (drop | frequent)
+        p_target = None
+        if protect is not None:
+            if not isinstance(protect, Index):
+                raise TypeError(f"protect must be an index of the same rows, got {type(protect).__name__}")
+            p_target = protect._explain_target()[0]
+            if isinstance(p_target, ShardGroup) != sharded:
+                raise ValueError("protect must be row-sharded exactly as this index is (or neither)")
+        new_target, _ = target.prune(topk, min_value, keep_cols=keep_columns, drop_cols=drop, protect=p_target)
+        new = copy.copy(self)                                       # the text store (data / offsets) is shared: ids did not move
+        new._vector = None                                          # re-exported from the pruned rows on demand
+        new._dev = None
+        for name in ("_facets", "_values"):                         # the columns are shared, the registries are the new index's own
+            if getattr(self, name, None) is not None:
+                setattr(new, name, dict(getattr(self, name)))
+        if sharded:
+            new._shards, new._group = None, None
+            new._adopt_shards(list(new_target._shards))
+            new_target.close()
+        else:
+            new._dev = new_target
+            new._prepare()
+        return new
 
     def _add_csr(self, vectors):
         """vectors -> (indptr, indices, data) of the rows to append"""

@@ -721,6 +721,24 @@ class Retriever(BiEncoder):
         """Drop deleted documents for good (Index.compact) -> old_ids: document j of the index was document old_ids[j] before."""
         return (index or self.index).compact()
 
+    def prune_index(self, topk=None, min_value=None, drop_tokens=None, keep_tokens=None, max_df=None, protect_lexical: Index = None,
+                    inplace: bool = True, index: Index = None) -> Index:
+        """Index.pruned with the columns given as column ids or vocabulary tokens (resolved the way must= is: a string is one entry of the
+        passage tokenizer's vocabulary, its column is token id - shift) -> the pruned index; inplace: it replaces retriever.index (the old
+        index object stays valid for whoever holds it).  protect_lexical: the bag-of-token index of the same documents."""
+        from ...doc_filter import terms_to_columns
+        index = index or self.index
+        if index is None:
+            raise RuntimeError("no index: call build_index / load_index first")
+        vocab = self.encoder_p.tokenizer.vocab
+        shift = int(self.encoder_p.config.shift_vocab_num)
+        drop = None if drop_tokens is None else terms_to_columns(drop_tokens, vocab, shift, "drop_tokens")
+        keep = None if keep_tokens is None else terms_to_columns(keep_tokens, vocab, shift, "keep_tokens")
+        new = index.pruned(topk=topk, min_value=min_value, drop_columns=drop, keep_columns=keep, max_df=max_df, protect=protect_lexical)
+        if inplace:
+            self.index = new
+        return new
+
     def save_index(self, path):
         self.index.save(path)
 
