@@ -38,6 +38,9 @@ retriever.build_index(passages, index_type=IndexType.SPARSE)
 ids, scores = retriever.retrieve(query, k=min(3, len(passages)))
 print("top ids:", ids.tolist(), "scores:", scores.tolist())
 print("best passage:", retriever.index.get_sample(int(ids[0, 0])))
+# relevance and a numeric field together: the exact top k by score + 0.3 * recency (every passage is scored, no rescore window)
+retriever.index.set_values("recency", torch.linspace(0, 1, len(passages)))
+print("boosted by recency:", retriever.retrieve_boosted(query, k=min(3, len(passages)), boosts={"recency": 0.3}).ids.tolist())
 
 # 3. bag-of-token index (SVDR beta search) with rerank
 retriever.build_index(passages, index_type=IndexType.BAG_OF_TOKEN)

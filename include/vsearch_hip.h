@@ -221,6 +221,39 @@ VS_API int vs_index_search_range(vs_index* index, const void* q, int q_dtype, in
  * scan was cut into and the rows of a chunk -- the last chunk holds the rest.  0 / 0 before the first range search; 1 chunk on a dense index. */
 VS_API int vs_index_last_range_plan(const vs_index* index, int32_t* out_chunks, int64_t* out_rows_per_chunk);
 
+/* Boosted search (no reference counterpart: the reference only has topk): vs_index_search_range with a BOOSTED score in the place of the
+ * score -- relevance plus (or times) a weighted sum of up to VS_BOOST_MAX_FIELDS numeric fields, exact: every live, allowed row is scored, so
+ * with thr = -inf and max_hits = k the list is the exact top k by boosted score, not a rescore window of a deeper top-k.
+ * One numerics, reproducible bit for bit (csrc/boost_check.h: boost_apply).  For query b and row r:
+ *   S    = the fp64 sum vs_index_search_range holds before its rounding: sum over the row's columns of fp64(fl32(q[c] * v[c])), q rounded to the
+ *          index dtype, v = 1 on a binary index (fl32(S) is that call's score); a row without packets has S = +0.0.  A dense index on the
+ *          matrix cores: S = fp64(its own fp32 search score).
+ *   t_j  = +0.0 if weights[b, j] == 0 or row r has no value in field j (NaN / INT32_MIN), else fp64(weights[b, j]) * fp64(fields[j][r]) --
+ *          exact in fp64.
+ *   VS_BOOST_ADD: x = (((S + t_0) + t_1) + ...), fp64 additions in field order.   VS_BOOST_MUL: u = (((1.0 + t_0) + t_1) + ...), x = S * u.
+ *   boosted(b, r) = fl32(x), -0.0 read as +0.0.  x NaN (an infinite value met its opposite, or S = 0): the row matches nothing for query b.
+ * With every weight 0 the call is vs_index_search_range bit for bit in both modes, whatever the fields hold; a missing value is neutral.
+ *   fields [n_fields]: HOST table of pointers to the value arrays [n_rows] (fp32 or int32, the layout of vs_value_*); field_dtypes [n_fields]:
+ *     HOST array of VS_VAL_F32 | VS_VAL_I32; n_fields in 1..VS_BOOST_MAX_FIELDS; weights fp32 [B, n_fields]; mode VS_BOOST_ADD | VS_BOOST_MUL.
+ *   thr [B] is a floor on the boosted score (NULL: -inf, every live, allowed row whose boosted score is not NaN).  out_count, out_ids /
+ *     out_scores (the boosted scores; canonical order: boosted descending, id ascending), max_hits, out_words, filter, id_offset: as
+ *     vs_index_search_range.
+ * Pointers: q, thr, filter, the outputs, the value arrays and weights are all host or all device on the index's device.  Host weights must be
+ * finite and a host thr not NaN (VS_EINVAL); on the device a NaN weight or a NaN thr makes its query match nothing, other non-finite weights go
+ * through the arithmetic as written.  n_fields outside 1..4, an unknown mode or dtype, a NULL field pointer: VS_EINVAL before any device work;
+ * a CSR-packet index with n_cols > 32763: VS_EUNSUPPORTED.  Routing as vs_index_search_range (tile scan when the batch qualifies and max_hits
+ * <= 512, else the one-query scan; identical bits); a disallowed or deleted row loads no value.  vs_index_last_range_plan reports its plan.
+ * Not covered: the blocked postings (their filter proves a top k of q.p, not of a boosted score: every call is an exact scan, one index pass
+ * per 8 queries), boosts in the grouped / diverse / fused searches and in vs_index_set_scores, decay functions (derive the field and store
+ * it), 64-bit values, more than 4 fields.                                                                                                    */
+#define VS_BOOST_ADD 0
+#define VS_BOOST_MUL 1
+#define VS_BOOST_MAX_FIELDS 4
+VS_API int vs_index_search_boosted(vs_index* index, const void* q, int q_dtype, int64_t ldq, int32_t B, const float* thr, int32_t max_hits,
+                                   const uint32_t* filter, int64_t filter_bit0, int64_t filter_ld, int64_t id_offset, int64_t* out_ids,
+                                   float* out_scores, int64_t* out_count, uint32_t* out_words, int64_t ld_words, const void* const* fields,
+                                   const int32_t* field_dtypes, int32_t n_fields, const float* weights, int mode, void* stream);
+
 /* ---- facet counts: how a document set spreads over per-row integer labels (no reference counterpart: the reference only has topk) ----------
  * The set of query b is a bitmap in the layout of vs_index_search_filtered: bit bit0 + r of the bitmap at words + b * ld_words stands for row
  * r (ld_words = 0: one bitmap for all queries, and then B must be 1; else ld_words >= the (bit0 + n_rows + 31) / 32 words a bitmap spans).

@@ -25,6 +25,8 @@ MMR_COSINE, MMR_DOT, MMR_MAX_DEPTH, MMR_MAX_COLS = 0, 1, 1024, 32768
 FUSE_RRF, FUSE_SUM, FUSE_MNZ, FUSE_RAW, FUSE_MAX_LISTS, FUSE_MAX_DEPTH, FUSE_MAX_ENTRIES = 0, 1, 2, 3, 8, 1024, 4096
 # range search (VS_RANGE_MAX_HITS): the most hits vs_index_search_range lists per query
 RANGE_MAX_HITS = 2048
+# boosted search (VS_BOOST_*): the modes, the most numeric fields of one vs_index_search_boosted call
+BOOST_ADD, BOOST_MUL, BOOST_MAX_FIELDS = 0, 1, 4
 # facet counts (VS_FACET_LDS_BINS, VS_FACET_MAX_TOPN): uint32 bins of a workgroup's LDS histograms, the most labels vs_facet_topn lists
 FACET_LDS_BINS, FACET_MAX_TOPN = 16384, 1024
 # term aggregations (VS_TERM_*): columns of a workgroup's LDS histogram, the most columns vs_term_topn lists, its scoring methods
@@ -80,6 +82,8 @@ _SIGNATURES = {
     "vs_index_search_filtered": ([_vp, _vp, _int, _i64, _i32, _i32, _vp, _i64, _i64, _i64, _vp, _vp, _vp], _int),
     "vs_index_search_range": ([_vp, _vp, _int, _i64, _i32, _vp, _i32, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp], _int),
     "vs_index_last_range_plan": ([_vp, C.POINTER(_i32), C.POINTER(_i64)], _int),
+    "vs_index_search_boosted": ([_vp, _vp, _int, _i64, _i32, _vp, _i32, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, C.POINTER(_vp),
+                                 C.POINTER(_i32), _i32, _vp, _int, _vp], _int),
     "vs_facet_plan": ([_i64, _i32, _i32, _int, _i64, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i64)], _int),
     "vs_facet_counts": ([_vp, _i64, _i64, _vp, _i32, _vp, _i64, _i32, _i64, _vp, _i64, _vp, _vp, _int, _vp], _int),
     "vs_index_facet_counts": ([_vp, _vp, _i64, _i64, _i32, _vp, _i32, _i64, _vp, _i64, _vp, _vp, _vp], _int),

@@ -23,6 +23,7 @@
 #include <hip/hip_fp16.h>
 #include <stdint.h>
 
+#include "boost_check.h"
 #include "csr_scan.h"
 #include "dense_csr.h"
 
@@ -110,8 +111,14 @@ struct MqRangeArgs : MqArgs {
     uint32_t* words;                  // optional [B, ld_words] match bitmaps, zeroed by the caller
     int64_t ld_words;
 };
-template <int RG>
-using MqKernelArgs = typename std::conditional<RG != 0, MqRangeArgs, MqArgs>::type;
+// Boosted search (range.hip): the BO = 1 instantiations of the range variant take the boost arguments behind MqRangeArgs; boost.w is the weight
+// row of the launch's first query.  The BO = 0 ones take the structs they took.
+template <class A>
+struct WithBoost : A {
+    BoostArgs boost;
+};
+template <int RG, int BO = 0>
+using MqKernelArgs = typename std::conditional<RG != 0, typename std::conditional<BO != 0, WithBoost<MqRangeArgs>, MqRangeArgs>::type, MqArgs>::type;
 
 template <int QT>
 __host__ __device__ inline size_t mq_fixed_lds_bytes(int32_t n_cols, int rows_in_flight) {
@@ -124,8 +131,9 @@ __host__ __device__ inline size_t mq_fixed_lds_bytes(int32_t n_cols, int rows_in
 // queries (T as low as the LDS slack allows, >= 3) are stored as zero-padded 8-float rows; a hit on such a
 // column costs two ds_read_b128 + 8 multiply-adds into per-lane fp64 registers (flushed once per row)
 // instead of up to 8 trips through the one-hit-at-a-time remainder loop.
-template <int G, int VM, int QT, int U, int DN, int FL = 0, int RG = 0>          // FL = 1: a filtered search (KArg, common.h); RG = 1: range search
-__global__ __launch_bounds__(kScanThreads) void csr_scan_topk_mq(KArg<MqKernelArgs<RG>, FL> a) {
+template <int G, int VM, int QT, int U, int DN, int FL = 0, int RG = 0, int BO = 0>   // FL = 1: a filtered search (KArg, common.h); RG = 1: range search; BO = 1: boosted
+__global__ __launch_bounds__(kScanThreads) void csr_scan_topk_mq(KArg<MqKernelArgs<RG, BO>, FL> a) {
+    static_assert(BO == 0 || RG != 0, "a boost belongs to the range variant: only that scan holds one numerics for every row");
     static_assert(QT == 8 && G >= 8, "the packed hit word assumes 8 query slots per tile; lanes 0..7 of a row group finish them");
     static_assert(RG == 0 || DN == 0, "the range variant keeps its match counters where the shared-column variant keeps its histogram");
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -161,6 +169,17 @@ __global__ __launch_bounds__(kScanThreads) void csr_scan_topk_mq(KArg<MqKernelAr
         const uint64_t my_upper = (a.upper && lg < nq) ? a.upper[q0 + lg] : ~0ull;
         uint64_t my_floor = 0ull;
         if constexpr (RG != 0) my_floor = lg < nq ? range_floor_key(a.thr[q0 + lg]) : kRangeNoMatch;
+        // boosted: lane lg of a row group keeps the weights of query q0 + lg in registers for the work item (named scalars: no lane-varying index)
+        float bw0 = 0.f, bw1 = 0.f, bw2 = 0.f, bw3 = 0.f;
+        if constexpr (BO != 0) {
+            if (lg < nq) {
+                const float* wq = a.boost.w + (size_t)(q0 + lg) * (size_t)a.boost.F;
+                bw0 = wq[0];
+                if (a.boost.F > 1) bw1 = wq[1];
+                if (a.boost.F > 2) bw2 = wq[2];
+                if (a.boost.F > 3) bw3 = wq[3];
+            }
+        }
         __syncthreads();
         // ---- build the tile tables ----
         for (int i = tid; i <= a.n_cols; i += kScanThreads) tab[i] = 0;
@@ -270,6 +289,26 @@ __global__ __launch_bounds__(kScanThreads) void csr_scan_topk_mq(KArg<MqKernelAr
                     const int64_t nrow = row + RPI;
                     if (nrow < r1) { np0 = a.pk_ptr[nrow]; np1 = a.pk_ptr[nrow + 1]; }
                 }
+                // boosted: the row's values are asked for before the packets, so that their latency passes under the row's work (U = 3 holds
+                // 24 packet values a lane: there two VGPRs would spill, and the loads wait until the packets are done).  The filter first: a
+                // disallowed row loads no value.  The lanes of a row read the same value addresses (one transaction)
+                constexpr bool BOOST_AHEAD = U < 3;
+                bool allowed_b = false;
+                uint32_t raw_b[VS_BOOST_MAX_FIELDS] = {0u, 0u, 0u, 0u};
+                auto boost_fetch = [&]() {
+                    if constexpr (BO != 0) {
+                        if (row < r1 && lg < nq) {
+                            allowed_b = my_floor != kRangeNoMatch;
+                            if constexpr (FL != 0) allowed_b = allowed_b && filter_ok(a, q0 + lg, row);
+                            if (allowed_b) {
+#pragma unroll
+                                for (int j = 0; j < VS_BOOST_MAX_FIELDS; ++j)
+                                    if (j < a.boost.F) raw_b[j] = a.boost.field[j][row];
+                            }
+                        }
+                    }
+                };
+                if constexpr (BO != 0 && BOOST_AHEAD) boost_fetch();
                 if (row < r1) {
                     // U packets per lane per trip: all loads first, then the hit walks
                     const uint32_t padw = (uint32_t)a.n_cols | ((uint32_t)a.n_cols << 16);
@@ -400,9 +439,28 @@ __global__ __launch_bounds__(kScanThreads) void csr_scan_topk_mq(KArg<MqKernelAr
                         sum += *pa;
                         *pa = 0.0;
                     }
-                    const uint64_t key = make_key((float)sum, (uint32_t)row);
+                    uint64_t key_b = 0ull;
+                    bool match_b = false;
+                    if constexpr (BO != 0) {
+                        if constexpr (!BOOST_AHEAD) boost_fetch();
+                        if (allowed_b) {
+                            const float bw[VS_BOOST_MAX_FIELDS] = {bw0, bw1, bw2, bw3};
+                            float x;
+                            if (boost_apply(sum, bw, raw_b, a.boost.dtype, a.boost.F, a.boost.mode, &x)) {
+                                key_b = make_key(x, (uint32_t)row);
+                                match_b = key_b >= my_floor;
+                            }
+                        }
+                    }
+                    const uint64_t key = BO != 0 ? key_b : make_key((float)sum, (uint32_t)row);
                     bool pass = key > tau[lg] && key < my_upper;
-                    if constexpr (RG != 0) {
+                    if constexpr (BO != 0) {
+                        if (match_b) {
+                            atomicAdd(&mcnt[lg], 1u);
+                            if (a.words) atomicOr(&a.words[(size_t)(q0 + lg) * (size_t)a.ld_words + (size_t)(row >> 5)], 1u << (row & 31));
+                        }
+                        pass = pass && match_b && K > 0;
+                    } else if constexpr (RG != 0) {
                         // the floor and the filter decide the match; the count and the bit come before the tau test (a prune loses none)
                         bool match = key >= my_floor && my_floor != kRangeNoMatch;
                         if constexpr (FL != 0) match = match && filter_ok(a, q0 + lg, row);

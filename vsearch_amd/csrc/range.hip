@@ -9,7 +9,14 @@
 //   CSR packets:   the 8-queries-a-pass tile scan (RG = 1 instantiation of csr_scan_topk_mq) when the batch qualifies for tiles and
 //                  max_hits <= kMaxKMq, else range_scan_kernel: one query per pass, one wave per row.  Identical bits either way.
 //   matrix cores:  vs_dense_scores into scratch, then range_select_dense_kernel over the [Bt, N] tile (the dense search's own fp32 score).
+//
+// Boosted search (vs_index_search_boosted) is the same call with boost_apply(S, weights, the row's values) (boost_check.h) in the place of
+// fl32(S): the BO = 1 instantiations of the three kernels, one or a few 32-bit loads a row at the point where the fp64 sum is still whole.
+// Floor, count, bitmap, candidate buffers, prune cycles, merge, tombstones, filter and routing are the range search's own.
 #include "csr_internal.h"
+
+#include <limits>
+#include <vector>
 
 using namespace vs;
 
@@ -28,10 +35,25 @@ struct RangeArgs : ScanArgs {
     int64_t ld_words;
 };
 
+// Boosted search: the BO = 1 instantiations take the boost arguments behind their range arguments (WithBoost, csr_scan_mq.h), the BO = 0 ones
+// the structs they took.  The score of a row becomes boost_apply(sum, ...) (boost_check.h) at the point where the fp64 sum is still whole.
+template <class A, int BO>
+using BArg = typename std::conditional<BO != 0, WithBoost<A>, A>::type;
+template <int BO, class A>
+inline BArg<A, BO> with_boost(const A& a, const BoostArgs& b) {
+    if constexpr (BO != 0) return WithBoost<A>{a, b};
+    else return a;
+}
+// the F values of a row (a missing field's slot stays 0: boost_apply reads none past F)
+__device__ __forceinline__ void boost_load(const BoostArgs& b, int64_t row, uint32_t* raw) {
+#pragma unroll
+    for (int j = 0; j < VS_BOOST_MAX_FIELDS; ++j) raw[j] = j < b.F ? b.field[j][row] : 0u;
+}
+
 // Sibling of exact_scan_topk_kernel (csr_scan.h): the LDS query image, one wave per row, row_sum_f64, the shared 4096-key buffer pruned
 // to K = a.k.  Work item = (query, row chunk).  K = 0: count / bitmap only, no candidate is kept and no barrier taken inside the scan.
-template <int VM, int FL>
-__global__ __launch_bounds__(kScanThreads) void range_scan_kernel(KArg<RangeArgs, FL> a) {
+template <int VM, int FL, int BO = 0>
+__global__ __launch_bounds__(kScanThreads) void range_scan_kernel(KArg<BArg<RangeArgs, BO>, FL> a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* img = reinterpret_cast<float*>(smem);
     uint64_t* cand = reinterpret_cast<uint64_t*>(smem + scan_img_bytes(a.n_cols));
@@ -50,6 +72,12 @@ __global__ __launch_bounds__(kScanThreads) void range_scan_kernel(KArg<RangeArgs
         if (tid == 0) { *cnt_sh = 0; *mcnt_sh = 0u; }
         __syncthreads();
         const uint64_t floor = range_floor_key(a.thr[qi]);
+        float bw[VS_BOOST_MAX_FIELDS] = {0.f, 0.f, 0.f, 0.f};       // the query's weights, for the work item
+        if constexpr (BO != 0) {
+#pragma unroll
+            for (int j = 0; j < VS_BOOST_MAX_FIELDS; ++j)
+                if (j < a.boost.F) bw[j] = a.boost.w[(size_t)qi * (size_t)a.boost.F + j];
+        }
         uint64_t tau = 0;
         const int64_t iters = r1 > r0 ? (r1 - r0 + kScanWaves - 1) / kScanWaves : 0;
         for (int64_t it0 = 0; it0 < iters; it0 += SB) {
@@ -59,9 +87,23 @@ __global__ __launch_bounds__(kScanThreads) void range_scan_kernel(KArg<RangeArgs
                 bool live = row < r1 && floor != kRangeNoMatch;
                 if constexpr (FL != 0) live = live && filter_ok(a, qi, row);      // (one wave a row: a disallowed row is not summed)
                 if (live) {
+                    // boosted: lane 0 will hold the sum, so it loads the row's values -- ahead of the packets, their latency passes under the sum
+                    uint32_t raw[VS_BOOST_MAX_FIELDS] = {0u, 0u, 0u, 0u};
+                    if constexpr (BO != 0) { if (lane == 0) boost_load(a.boost, row, raw); }
                     const double sum = row_sum_f64<VM>(a.pk_ptr, a.cols, a.vals, (uint32_t)row, lane, [&](uint32_t col) { return img[col]; });
-                    const uint64_t key = make_key((float)sum, (uint32_t)row);
-                    if (lane == 0 && key >= floor) {
+                    uint64_t key = 0ull;
+                    bool ok = true;
+                    if constexpr (BO != 0) {
+                        ok = false;
+                        if (lane == 0) {
+                            float x;
+                            ok = boost_apply(sum, bw, raw, a.boost.dtype, a.boost.F, a.boost.mode, &x);
+                            if (ok) key = make_key(x, (uint32_t)row);
+                        }
+                    } else {
+                        key = make_key((float)sum, (uint32_t)row);
+                    }
+                    if (lane == 0 && ok && key >= floor) {
                         atomicAdd(mcnt_sh, 1u);
                         if (a.words) atomicOr(&a.words[(size_t)qi * (size_t)a.ld_words + (size_t)(row >> 5)], 1u << (row & 31));
                         if (K > 0 && key > tau) cand[atomicAdd(cnt_sh, 1)] = key;
@@ -97,45 +139,54 @@ __global__ __launch_bounds__(kScanThreads) void range_scan_kernel(KArg<RangeArgs
     }
 }
 
-template <int VM>
-int launch_range_scan_vm(const RangeArgs& a, const FilterArgs& f, int grid, size_t lds, hipStream_t s) {
+template <int VM, int BO>
+int launch_range_scan_bo(const RangeArgs& a, const BoostArgs& bo, const FilterArgs& f, int grid, size_t lds, hipStream_t s) {
     if (f.words) {
-        VS_HIP(hipFuncSetAttribute((const void*)range_scan_kernel<VM, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((range_scan_kernel<VM, 1>), dim3(grid), dim3(kScanThreads), lds, s, with_filter<1>(a, f));
+        VS_HIP(hipFuncSetAttribute((const void*)range_scan_kernel<VM, 1, BO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL((range_scan_kernel<VM, 1, BO>), dim3(grid), dim3(kScanThreads), lds, s, with_filter<1>(with_boost<BO>(a, bo), f));
     } else {
-        VS_HIP(hipFuncSetAttribute((const void*)range_scan_kernel<VM, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((range_scan_kernel<VM, 0>), dim3(grid), dim3(kScanThreads), lds, s, a);
+        VS_HIP(hipFuncSetAttribute((const void*)range_scan_kernel<VM, 0, BO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL((range_scan_kernel<VM, 0, BO>), dim3(grid), dim3(kScanThreads), lds, s, with_boost<BO>(a, bo));
     }
     VS_HIP(hipGetLastError());
     return VS_OK;
+}
+// bo: the boost of the launch's queries, or null (the plain range search)
+template <int VM>
+int launch_range_scan_vm(const RangeArgs& a, const BoostArgs* bo, const FilterArgs& f, int grid, size_t lds, hipStream_t s) {
+    return bo ? launch_range_scan_bo<VM, 1>(a, *bo, f, grid, lds, s) : launch_range_scan_bo<VM, 0>(a, BoostArgs{}, f, grid, lds, s);
 }
 
 // ---- 8 queries per pass: the RG = 1 instantiations of csr_scan_topk_mq (plain variant, DN = 0) -----------------------------------------
-template <int G, int VM, int U>
-int launch_range_mq_gu(const MqRangeArgs& a, const FilterArgs& f, int grid, size_t lds, hipStream_t s) {
+template <int G, int VM, int U, int BO>
+int launch_range_mq_bo(const MqRangeArgs& a, const BoostArgs& bo, const FilterArgs& f, int grid, size_t lds, hipStream_t s) {
     if (f.words) {
-        VS_HIP(hipFuncSetAttribute((const void*)csr_scan_topk_mq<G, VM, kQT, U, 0, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((csr_scan_topk_mq<G, VM, kQT, U, 0, 1, 1>), dim3(grid), dim3(kScanThreads), lds, s, with_filter<1>(a, f));
+        VS_HIP(hipFuncSetAttribute((const void*)csr_scan_topk_mq<G, VM, kQT, U, 0, 1, 1, BO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL((csr_scan_topk_mq<G, VM, kQT, U, 0, 1, 1, BO>), dim3(grid), dim3(kScanThreads), lds, s, with_filter<1>(with_boost<BO>(a, bo), f));
     } else {
-        VS_HIP(hipFuncSetAttribute((const void*)csr_scan_topk_mq<G, VM, kQT, U, 0, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((csr_scan_topk_mq<G, VM, kQT, U, 0, 0, 1>), dim3(grid), dim3(kScanThreads), lds, s, a);
+        VS_HIP(hipFuncSetAttribute((const void*)csr_scan_topk_mq<G, VM, kQT, U, 0, 0, 1, BO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL((csr_scan_topk_mq<G, VM, kQT, U, 0, 0, 1, BO>), dim3(grid), dim3(kScanThreads), lds, s, with_boost<BO>(a, bo));
     }
     VS_HIP(hipGetLastError());
     return VS_OK;
 }
+template <int G, int VM, int U>
+int launch_range_mq_gu(const MqRangeArgs& a, const BoostArgs* bo, const FilterArgs& f, int grid, size_t lds, hipStream_t s) {
+    return bo ? launch_range_mq_bo<G, VM, U, 1>(a, *bo, f, grid, lds, s) : launch_range_mq_bo<G, VM, U, 0>(a, BoostArgs{}, f, grid, lds, s);
+}
 template <int G, int VM>
-int launch_range_mq_g(int u, const MqRangeArgs& a, const FilterArgs& f, int grid, size_t lds, hipStream_t s) {
-    if (u <= 1) return launch_range_mq_gu<G, VM, 1>(a, f, grid, lds, s);
-    if (u == 2) return launch_range_mq_gu<G, VM, 2>(a, f, grid, lds, s);
-    return launch_range_mq_gu<G, VM, 3>(a, f, grid, lds, s);
+int launch_range_mq_g(int u, const MqRangeArgs& a, const BoostArgs* bo, const FilterArgs& f, int grid, size_t lds, hipStream_t s) {
+    if (u <= 1) return launch_range_mq_gu<G, VM, 1>(a, bo, f, grid, lds, s);
+    if (u == 2) return launch_range_mq_gu<G, VM, 2>(a, bo, f, grid, lds, s);
+    return launch_range_mq_gu<G, VM, 3>(a, bo, f, grid, lds, s);
 }
 template <int VM>
-int launch_range_mq_vm(int g, int u, const MqRangeArgs& a, const FilterArgs& f, int grid, size_t lds, hipStream_t s) {
+int launch_range_mq_vm(int g, int u, const MqRangeArgs& a, const BoostArgs* bo, const FilterArgs& f, int grid, size_t lds, hipStream_t s) {
     switch (g) {
-        case 8: return launch_range_mq_g<8, VM>(u, a, f, grid, lds, s);
-        case 16: return launch_range_mq_g<16, VM>(u, a, f, grid, lds, s);
-        case 32: return launch_range_mq_g<32, VM>(u, a, f, grid, lds, s);
-        default: return launch_range_mq_g<64, VM>(u, a, f, grid, lds, s);
+        case 8: return launch_range_mq_g<8, VM>(u, a, bo, f, grid, lds, s);
+        case 16: return launch_range_mq_g<16, VM>(u, a, bo, f, grid, lds, s);
+        case 32: return launch_range_mq_g<32, VM>(u, a, bo, f, grid, lds, s);
+        default: return launch_range_mq_g<64, VM>(u, a, bo, f, grid, lds, s);
     }
 }
 
@@ -154,8 +205,8 @@ struct RangeSelArgs {
 
 // One workgroup per query, a thread per row and step: a wave's 64 rows are two whole bitmap words (ballot), so the bitmap takes plain
 // stores here.  Candidates as in csr_scan_topk_shared: the 4096-key LDS buffer, pruned to K when more than 2048 are in.
-template <int FL>
-__global__ __launch_bounds__(kScanThreads) void range_select_dense_kernel(KArg<RangeSelArgs, FL> a) {
+template <int FL, int BO = 0>
+__global__ __launch_bounds__(kScanThreads) void range_select_dense_kernel(KArg<BArg<RangeSelArgs, BO>, FL> a) {
     __shared__ uint64_t cand[kWgCap];
     __shared__ int cnt_sh;
     __shared__ unsigned int mcnt_sh;
@@ -169,6 +220,12 @@ __global__ __launch_bounds__(kScanThreads) void range_select_dense_kernel(KArg<R
         if (tid == 0) { cnt_sh = 0; mcnt_sh = 0u; }
         __syncthreads();
         const uint64_t floor = range_floor_key(a.thr[b]);
+        float bw[VS_BOOST_MAX_FIELDS] = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (BO != 0) {
+#pragma unroll
+            for (int j = 0; j < VS_BOOST_MAX_FIELDS; ++j)
+                if (j < a.boost.F) bw[j] = a.boost.w[(size_t)b * (size_t)a.boost.F + j];
+        }
         const float* src = a.scores + (size_t)b * (size_t)a.N;
         uint64_t tau = 0;
         unsigned int mine = 0;
@@ -179,11 +236,26 @@ __global__ __launch_bounds__(kScanThreads) void range_select_dense_kernel(KArg<R
                 const int64_t n = it * kScanThreads + tid;
                 bool match = n < a.N && floor != kRangeNoMatch;
                 uint64_t key = 0ull;
-                if (match) {
-                    key = make_key(canon_zero(src[n]), (uint32_t)n);
-                    match = key >= floor;
+                if constexpr (BO != 0) {
+                    // the filter first: a disallowed row loads no value.  S = fp64(the dense search's fp32 score)
+                    if constexpr (FL != 0) { if (match) match = filter_ok(a, b, n); }
+                    if (match) {
+                        uint32_t raw[VS_BOOST_MAX_FIELDS];
+                        boost_load(a.boost, n, raw);
+                        float x;
+                        match = boost_apply((double)src[n], bw, raw, a.boost.dtype, a.boost.F, a.boost.mode, &x);
+                        if (match) {
+                            key = make_key(x, (uint32_t)n);
+                            match = key >= floor;
+                        }
+                    }
+                } else {
+                    if (match) {
+                        key = make_key(canon_zero(src[n]), (uint32_t)n);
+                        match = key >= floor;
+                    }
+                    if constexpr (FL != 0) { if (match) match = filter_ok(a, b, n); }
                 }
-                if constexpr (FL != 0) { if (match) match = filter_ok(a, b, n); }
                 const unsigned long long mm = __builtin_amdgcn_ballot_w64(match);
                 if (a.words && lane < 2) {
                     const int64_t wi = ((it * kScanThreads + (int64_t)w * 64) >> 5) + lane;
@@ -253,7 +325,15 @@ struct RangeCall {
     unsigned long long* count;        // [B]
     uint32_t* words;                  // [B, ld_words] or null
     int64_t ld_words;
+    const BoostArgs* boost;           // null: the plain range search; else the boost, w at the call's first query
 };
+
+// the boost of queries [b0, ...) of the call
+inline BoostArgs boost_from(const BoostArgs& b, int64_t b0) {
+    BoostArgs r = b;
+    r.w += (size_t)b0 * (size_t)b.F;
+    return r;
+}
 
 int range_merge(vs_index* idx, const uint64_t* cand, int64_t n_cand, int b0, int bs, const RangeCall& rc, hipStream_t s) {
     if (rc.K == 0) return VS_OK;
@@ -307,9 +387,11 @@ int range_tiles(vs_index* idx, const float* dq, int b0, int bs, const RangeCall&
         const int u = mq_packets_per_trip(idx);
         const size_t lds = mq_lds_bytes(idx, vals_cap);
         const FilterArgs f = filter_from(filt, b0);
-        const int rcode = idx->store_dtype == VS_F32 ? launch_range_mq_vm<VM_F32>(mq_lanes(idx), u, a, f, grid, lds, s)
-                        : idx->store_dtype == VS_F16 ? launch_range_mq_vm<VM_F16>(mq_lanes(idx), u, a, f, grid, lds, s)
-                                                     : launch_range_mq_vm<VM_BIN>(mq_lanes(idx), u, a, f, grid, lds, s);
+        const BoostArgs bo_sub = rc.boost ? boost_from(*rc.boost, b0) : BoostArgs{};
+        const BoostArgs* bo = rc.boost ? &bo_sub : nullptr;
+        const int rcode = idx->store_dtype == VS_F32 ? launch_range_mq_vm<VM_F32>(mq_lanes(idx), u, a, bo, f, grid, lds, s)
+                        : idx->store_dtype == VS_F16 ? launch_range_mq_vm<VM_F16>(mq_lanes(idx), u, a, bo, f, grid, lds, s)
+                                                     : launch_range_mq_vm<VM_BIN>(mq_lanes(idx), u, a, bo, f, grid, lds, s);
         VS_TRY(rcode);
     }
     VS_STAGE("range tile scan", s);
@@ -346,9 +428,11 @@ int range_one(vs_index* idx, const float* dq, int b0, int bs, const RangeCall& r
     {
         ProfScope prof("range_scan", s);
         const FilterArgs f = filter_from(filt, b0);
-        const int rcode = idx->store_dtype == VS_F32 ? launch_range_scan_vm<VM_F32>(a, f, grid, lds, s)
-                        : idx->store_dtype == VS_F16 ? launch_range_scan_vm<VM_F16>(a, f, grid, lds, s)
-                                                     : launch_range_scan_vm<VM_BIN>(a, f, grid, lds, s);
+        const BoostArgs bo_sub = rc.boost ? boost_from(*rc.boost, b0) : BoostArgs{};
+        const BoostArgs* bo = rc.boost ? &bo_sub : nullptr;
+        const int rcode = idx->store_dtype == VS_F32 ? launch_range_scan_vm<VM_F32>(a, bo, f, grid, lds, s)
+                        : idx->store_dtype == VS_F16 ? launch_range_scan_vm<VM_F16>(a, bo, f, grid, lds, s)
+                                                     : launch_range_scan_vm<VM_BIN>(a, bo, f, grid, lds, s);
         VS_TRY(rcode);
     }
     VS_STAGE("range one-query scan", s);
@@ -422,7 +506,11 @@ int range_dense(vs_index* idx, const void* q_dev, int q_dtype, int64_t ldq, int3
         {
             ProfScope prof("range_scan", s);
             const FilterArgs f = filter_from(filt, b0);
-            if (f.words) hipLaunchKernelGGL(range_select_dense_kernel<1>, dim3(grid), dim3(kScanThreads), 0, s, with_filter<1>(a, f));
+            if (rc.boost) {
+                const BoostArgs bo = boost_from(*rc.boost, b0);
+                if (f.words) hipLaunchKernelGGL((range_select_dense_kernel<1, 1>), dim3(grid), dim3(kScanThreads), 0, s, with_filter<1>(with_boost<1>(a, bo), f));
+                else hipLaunchKernelGGL((range_select_dense_kernel<0, 1>), dim3(grid), dim3(kScanThreads), 0, s, with_boost<1>(a, bo));
+            } else if (f.words) hipLaunchKernelGGL(range_select_dense_kernel<1>, dim3(grid), dim3(kScanThreads), 0, s, with_filter<1>(a, f));
             else hipLaunchKernelGGL(range_select_dense_kernel<0>, dim3(grid), dim3(kScanThreads), 0, s, a);
             VS_HIP(hipGetLastError());
         }
@@ -432,13 +520,25 @@ int range_dense(vs_index* idx, const void* q_dev, int q_dtype, int64_t ldq, int3
     return VS_OK;
 }
 
-}  // namespace
-}  // namespace vs
+// what vs_index_search_boosted adds to a range search, as the caller gave it (null: the plain range search)
+struct BoostIn {
+    const void* const* fields;
+    const int32_t* dtypes;
+    int32_t F;
+    const float* weights;
+    int mode;
+};
 
-extern "C" int vs_index_search_range(vs_index* idx, const void* q, int q_dtype, int64_t ldq, int32_t B, const float* thr, int32_t max_hits,
-                                     const uint32_t* filter, int64_t filter_bit0, int64_t filter_ld, int64_t id_offset, int64_t* out_ids,
-                                     float* out_scores, int64_t* out_count, uint32_t* out_words, int64_t ld_words, void* stream) {
-    if (!idx || !q || !thr) return fail(VS_EINVAL, "NULL argument");
+// vs_index_search_range and vs_index_search_boosted: one entry, so that checks, staging, tombstones and the stream rules are one code
+int range_entry(vs_index* idx, const void* q, int q_dtype, int64_t ldq, int32_t B, const float* thr, int32_t max_hits, const uint32_t* filter,
+                int64_t filter_bit0, int64_t filter_ld, int64_t id_offset, int64_t* out_ids, float* out_scores, int64_t* out_count,
+                uint32_t* out_words, int64_t ld_words, const BoostIn* bi, void* stream) {
+    if (!idx || !q || (!thr && !bi)) return fail(VS_EINVAL, "NULL argument");
+    if (bi) {
+        char msg[256] = {0};
+        const int rc = boost_check_fields(bi->fields, bi->dtypes, bi->F, bi->mode, bi->weights, msg, sizeof msg);
+        if (rc != VS_OK) return fail(rc, "%s", msg);
+    }
     if (B <= 0) return fail(VS_EINVAL, "B must be positive");
     if (q_dtype != VS_F32 && q_dtype != VS_F16) return fail(VS_EINVAL, "q_dtype must be VS_F32 or VS_F16");
     if (ldq < idx->n_cols) return fail(VS_EINVAL, "query has %lld columns, index has %d", (long long)ldq, idx->n_cols);
@@ -457,11 +557,15 @@ extern "C" int vs_index_search_range(vs_index* idx, const void* q, int q_dtype, 
         return fail(VS_EUNSUPPORTED, "range search needs the LDS query image: n_cols = %d is too wide (at most 32763 columns)", idx->n_cols);
     // all host, or all device on the index's device
     const bool dev = is_device_ptr(q);
-    const void* ptrs[6] = {thr, filter, max_hits > 0 ? out_ids : nullptr, max_hits > 0 ? out_scores : nullptr, out_count, out_words};
+    const void* ptrs[6 + 1 + VS_BOOST_MAX_FIELDS] = {thr, filter, max_hits > 0 ? out_ids : nullptr, max_hits > 0 ? out_scores : nullptr, out_count, out_words};
+    if (bi) {
+        ptrs[6] = bi->weights;
+        for (int j = 0; j < bi->F; ++j) ptrs[7 + j] = bi->fields[j];
+    }
     for (const void* p : ptrs)
         if (p && is_device_ptr(p) != dev) return fail(VS_EINVAL, "the buffers of a range search must all be host or all device pointers");
     if (dev) {
-        const void* all[7] = {q, ptrs[0], ptrs[1], ptrs[2], ptrs[3], ptrs[4], ptrs[5]};
+        const void* all[7 + 1 + VS_BOOST_MAX_FIELDS] = {q, ptrs[0], ptrs[1], ptrs[2], ptrs[3], ptrs[4], ptrs[5], ptrs[6], ptrs[7], ptrs[8], ptrs[9], ptrs[10]};
         for (const void* p : all) {
             if (!p) continue;
             hipPointerAttribute_t attr;
@@ -469,14 +573,23 @@ extern "C" int vs_index_search_range(vs_index* idx, const void* q, int q_dtype, 
             if (attr.device != idx->device) return fail(VS_EINVAL, "a buffer lives on device %d, the index on device %d", attr.device, idx->device);
         }
     } else {
-        for (int b = 0; b < B; ++b)
+        for (int b = 0; thr && b < B; ++b)
             if (thr[b] != thr[b]) return fail(VS_EINVAL, "thr[%d] is NaN", b);
+        if (bi) {
+            char msg[256] = {0};
+            const int rc = boost_check_weights_host(bi->weights, B, bi->F, msg, sizeof msg);
+            if (rc != VS_OK) return fail(rc, "%s", msg);
+        }
     }
     VS_HIP(hipSetDevice(idx->device));
     hipStream_t s = (hipStream_t)stream;
     const int K = max_hits;
     // staging of host buffers; a count the caller did not ask for still has a home (the kernels always count)
-    DevBuf st_in, st_out;
+    DevBuf st_in, st_out, st_boost;
+    // thr == NULL (a boosted search): a floor of -inf for every query
+    const std::vector<float> no_floor(thr ? 0 : (size_t)B, -std::numeric_limits<float>::infinity());
+    if (!thr) thr = no_floor.data();
+    const bool thr_dev = dev && no_floor.empty();
     const void* d_q = q;
     const uint32_t* d_filter = filter;
     RangeCall rc{};
@@ -486,7 +599,12 @@ extern "C" int vs_index_search_range(vs_index* idx, const void* q, int q_dtype, 
     const size_t sz_ids = (size_t)B * K * 8, sz_sc = (size_t)B * K * 4, sz_cnt = (size_t)B * 8;
     const size_t sz_words = out_words ? ((size_t)(B - 1) * (size_t)ld_words + (size_t)n_words) * 4 : 0;
     if (dev) {
-        rc.thr = thr;
+        if (thr_dev) rc.thr = thr;
+        else {
+            VS_TRY(st_in.alloc((size_t)B * 4));
+            VS_HIP(hipMemcpyAsync(st_in.p, thr, (size_t)B * 4, hipMemcpyHostToDevice, s));
+            rc.thr = st_in.as<float>();
+        }
         rc.ids = out_ids;
         rc.scores = out_scores;
         rc.words = out_words;
@@ -516,6 +634,28 @@ extern "C" int vs_index_search_range(vs_index* idx, const void* q, int q_dtype, 
         rc.scores = reinterpret_cast<float*>(p + a8);
         rc.count = reinterpret_cast<unsigned long long*>(p + a8 + a4);
         rc.words = out_words ? reinterpret_cast<uint32_t*>(p + a8 + a4 + ac) : nullptr;
+    }
+    // the boost: the value arrays and the weights as they are (device), or staged
+    BoostArgs bo{};
+    if (bi) {
+        bo.F = bi->F;
+        bo.mode = bi->mode;
+        for (int j = 0; j < bi->F; ++j) bo.dtype[j] = bi->dtypes[j];
+        if (dev) {
+            bo.w = bi->weights;
+            for (int j = 0; j < bi->F; ++j) bo.field[j] = static_cast<const uint32_t*>(bi->fields[j]);
+        } else {
+            const size_t col = (((size_t)idx->n_rows * 4) + 15) & ~(size_t)15, wb = (size_t)B * bi->F * 4;
+            VS_TRY(st_boost.alloc(col * bi->F + wb));
+            char* p = st_boost.as<char>();
+            for (int j = 0; j < bi->F; ++j) {
+                VS_HIP(hipMemcpyAsync(p + col * j, bi->fields[j], (size_t)idx->n_rows * 4, hipMemcpyHostToDevice, s));
+                bo.field[j] = reinterpret_cast<const uint32_t*>(p + col * j);
+            }
+            VS_HIP(hipMemcpyAsync(p + col * bi->F, bi->weights, wb, hipMemcpyHostToDevice, s));
+            bo.w = reinterpret_cast<const float*>(p + col * bi->F);
+        }
+        rc.boost = &bo;
     }
     VS_HIP(hipMemsetAsync(rc.count, 0, sz_cnt, s));
     if (rc.words) {
@@ -548,9 +688,28 @@ extern "C" int vs_index_search_range(vs_index* idx, const void* q, int q_dtype, 
             VS_HIP(hipMemcpy2DAsync(out_words, (size_t)ld_words * 4, rc.words, (size_t)ld_words * 4, (size_t)n_words * 4, (size_t)B, hipMemcpyDeviceToHost, s));
     }
     // staging buffers die here: a call that used any waits for its work (device pointers + a stream: only enqueued)
-    if (!stream || st_in.p || st_out.p) VS_HIP(hipStreamSynchronize(s));
+    if (!stream || st_in.p || st_out.p || st_boost.p) VS_HIP(hipStreamSynchronize(s));
     if (Profiler::get().on) Profiler::get().drain();
     return VS_OK;
+}
+
+}  // namespace
+}  // namespace vs
+
+extern "C" int vs_index_search_range(vs_index* idx, const void* q, int q_dtype, int64_t ldq, int32_t B, const float* thr, int32_t max_hits,
+                                     const uint32_t* filter, int64_t filter_bit0, int64_t filter_ld, int64_t id_offset, int64_t* out_ids,
+                                     float* out_scores, int64_t* out_count, uint32_t* out_words, int64_t ld_words, void* stream) {
+    return range_entry(idx, q, q_dtype, ldq, B, thr, max_hits, filter, filter_bit0, filter_ld, id_offset, out_ids, out_scores, out_count, out_words,
+                       ld_words, nullptr, stream);
+}
+
+extern "C" int vs_index_search_boosted(vs_index* idx, const void* q, int q_dtype, int64_t ldq, int32_t B, const float* thr, int32_t max_hits,
+                                       const uint32_t* filter, int64_t filter_bit0, int64_t filter_ld, int64_t id_offset, int64_t* out_ids,
+                                       float* out_scores, int64_t* out_count, uint32_t* out_words, int64_t ld_words, const void* const* fields,
+                                       const int32_t* field_dtypes, int32_t n_fields, const float* weights, int mode, void* stream) {
+    const BoostIn bi{fields, field_dtypes, n_fields, weights, mode};
+    return range_entry(idx, q, q_dtype, ldq, B, thr, max_hits, filter, filter_bit0, filter_ld, id_offset, out_ids, out_scores, out_count, out_words,
+                       ld_words, &bi, stream);
 }
 
 extern "C" int vs_index_last_range_plan(const vs_index* idx, int32_t* out_chunks, int64_t* out_rows_per_chunk) {

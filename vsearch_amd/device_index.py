@@ -747,15 +747,80 @@ def _range_args(q, min_score, max_hits):
     return B, np.ascontiguousarray(thr), max_hits
 
 
+BOOST_MODES = {"add": nat.BOOST_ADD, "mul": nat.BOOST_MUL}
+MAX_BOOST_FIELDS = nat.BOOST_MAX_FIELDS
+
+
+def _boost_args(q, boosts, weights, mode, min_score, max_hits, n_rows=None):
+    """Argument checks of a boosted search that need no device -> (B, thresholds float32 ndarray [B], max_hits, (fields, dtypes, weights
+    [B, F], mode code)).  boosts: 1..4 value columns [n_rows], float32 or int32 (value_column() converts), numpy or torch.  weights: one per
+    field (shared by the queries) or [B, F]; host weights must be finite, a CUDA tensor is passed as it is (a NaN there makes its query
+    match nothing).  min_score None: no floor (-inf)."""
+    if mode not in BOOST_MODES:
+        raise ValueError(f"mode must be one of {sorted(BOOST_MODES)}, got {mode!r}")
+    B, thr, K = _range_args(q, -np.inf if min_score is None else min_score, max_hits)
+    if hasattr(boosts, "ndim") or not isinstance(boosts, (list, tuple)):
+        raise TypeError("boosts must be a list of value columns (one array per field)")
+    F = len(boosts)
+    if not 1 <= F <= MAX_BOOST_FIELDS:
+        raise ValueError(f"a boosted search takes 1..{MAX_BOOST_FIELDS} fields, got {F}")
+    dtypes = []
+    for j, f in enumerate(boosts):
+        if f is None or not hasattr(f, "shape"):
+            raise TypeError(f"boosts[{j}] is not an array of values")
+        dtypes.append(_value_dtype(f))
+        if len(f.shape) != 1 or (n_rows is not None and int(f.shape[0]) != int(n_rows)):
+            raise ValueError(f"boosts[{j}] must hold one entry per row{'' if n_rows is None else f' ({int(n_rows)})'}, got shape {tuple(f.shape)}")
+    if _is_torch(weights) and weights.is_cuda:
+        w = weights
+        if w.dim() == 1:
+            w = w.unsqueeze(0).expand(B, -1)
+        if tuple(w.shape) != (B, F):
+            raise ValueError(f"weights: one per field ({F}), or [B, F] = [{B}, {F}]; got shape {tuple(weights.shape)}")
+        w = w.float().contiguous()
+    else:
+        w = np.asarray(weights.detach().numpy() if _is_torch(weights) else weights, dtype=np.float32)
+        if w.ndim == 1:
+            w = np.broadcast_to(w[None, :], (B, w.shape[0]))
+        if w.ndim != 2 or w.shape != (B, F):
+            raise ValueError(f"weights: one per field ({F}), or [B, F] = [{B}, {F}]; got shape {tuple(np.shape(weights))}")
+        if not np.isfinite(w).all():
+            raise ValueError("weights must be finite")
+        w = np.ascontiguousarray(w, dtype=np.float32)
+    return B, thr, K, (list(boosts), dtypes, w, BOOST_MODES[mode])
+
+
+def _boost_c_args(boost, device):
+    """(fields, dtypes, weights, mode) -> (the trailing arguments of vs_index_search_boosted, what they point into).  device: a torch device --
+    columns and weights are moved there -- or None: host arrays."""
+    fields, dtypes, w, mode = boost
+    if device is not None:
+        import torch
+        fs = [(f if _is_torch(f) else torch.from_numpy(np.ascontiguousarray(f))).to(device).contiguous() for f in fields]
+        wt = (w if _is_torch(w) else torch.from_numpy(w)).to(device).contiguous()
+        ptrs, wp = [f.data_ptr() for f in fs], wt.data_ptr()
+    else:
+        fs = [np.ascontiguousarray(f.numpy() if _is_torch(f) else f) for f in fields]
+        wt = w
+        ptrs, wp = [f.ctypes.data for f in fs], wt.ctypes.data
+    F = len(fs)
+    return ((C.c_void_p * F)(*ptrs), (C.c_int32 * F)(*dtypes), F, C.c_void_p(wp), mode), (fs, wt)
+
+
+def _boost_on_device(boost):
+    return boost is not None and (any(_is_torch(f) and f.is_cuda for f in boost[0]) or (_is_torch(boost[2]) and boost[2].is_cuda))
+
+
 def _words_to_int32(words_i64):
     """uint32 values held in int64 -> the int32 words of a DocFilter"""
     import torch
     return (words_i64 - ((words_i64 >> 31) << 32)).to(torch.int32)
 
 
-def _range_shards(group, q, min_score, max_hits, filter, want_words):
+def _range_shards(group, q, min_score, max_hits, filter, want_words, boost=None):
     """Range search of a ShardGroup: every shard with its id_offset (and its bit range of the filter); lists merged with vs_merge_topk on
-    the first shard's GPU, counts summed, bitmaps placed at their bit offsets -> (ids, scores, counts, words | None) on that GPU."""
+    the first shard's GPU, counts summed, bitmaps placed at their bit offsets -> (ids, scores, counts, words | None) on that GPU.
+    boost (a boosted search: _boost_args' tuple over the group's rows): every shard gets its row slice of every field."""
     import torch
     B, thr, K = _range_args(q, min_score, max_hits)
     nat.require_device()
@@ -774,7 +839,8 @@ def _range_shards(group, q, min_score, max_hits, filter, want_words):
         dev = torch.device("cuda", sh.device)
         n = int(sh.info().n_rows)
         fs = f.to(dev) if f is not None else None
-        ids, sc, cnt, w = sh._range_call(qt.to(dev), thr, K, fs, row0, want_words, filter_bit0=row0)
+        bs = None if boost is None else ([f[row0:row0 + n] for f in boost[0]],) + tuple(boost[1:])
+        ids, sc, cnt, w = sh._range_call(qt.to(dev), thr, K, fs, row0, want_words, filter_bit0=row0, boost=bs)
         counts += cnt.to(dev0)
         if K:
             lists.append((ids.to(dev0), sc.to(dev0)))
@@ -2987,14 +3053,15 @@ class DeviceIndex:
         return _diversify(self, ids, scores, k, lam, sim, max_row_bytes)
 
     # ---- range search: every document scoring at least a threshold (vs_index_search_range) -------------------------------------------
-    def _range_call(self, q, thr, max_hits, filter, id_offset, want_words, filter_bit0=0):
+    def _range_call(self, q, thr, max_hits, filter, id_offset, want_words, filter_bit0=0, boost=None):
         """One vs_index_search_range call -> (ids, scores, counts, words | None).  A torch CUDA q runs on device buffers and torch's current
-        stream; anything else on host buffers (blocking).  thr: float32 ndarray [B]; filter: None or a DocFilter on this index's device."""
+        stream; anything else on host buffers (blocking).  thr: float32 ndarray [B]; filter: None or a DocFilter on this index's device.
+        boost: None, or _boost_args' tuple -- then the call is vs_index_search_boosted, its columns and weights in the kind of the call."""
         p, dt, keep, B, ldq = self._q_args(q)
         n = int(self.info().n_rows)
         W = (n + 31) // 32
         K = int(max_hits)
-        fn = nat.lib().vs_index_search_range
+        fn = nat.lib().vs_index_search_range if boost is None else nat.lib().vs_index_search_boosted
         if _is_torch(q) and q.is_cuda:
             import torch
             dev = torch.device("cuda", self.device)
@@ -3004,15 +3071,16 @@ class DeviceIndex:
             counts = torch.empty(B, dtype=torch.int64, device=dev)
             words = torch.empty((B, W), dtype=torch.int32, device=dev) if want_words else None
             fp = C.c_void_p(filter.words.data_ptr()) if filter is not None else None
+            extra, keep_boost = _boost_c_args(boost, dev) if boost is not None else ((), None)
             nat.check(fn(self._h, p, dt, ldq, B, C.c_void_p(t_thr.data_ptr()), K, fp, int(filter_bit0), filter.ld if filter is not None else 0,
                          int(id_offset), _ptr(ids) if K else None, _ptr(scores) if K else None, _ptr(counts), _ptr(words) if want_words else None, W,
-                         current_stream(self.device)))
+                         *extra, current_stream(self.device)))
             return ids, scores, counts, words
-        if filter is not None:
+        if filter is not None or _boost_on_device(boost):
             # the filter's words live on the GPU and the call takes all-host or all-device buffers: run on the device, bring the results back
             import torch
             qd = (q if _is_torch(q) else torch.from_numpy(np.ascontiguousarray(q))).to(torch.device("cuda", self.device))
-            out = self._range_call(qd, thr, K, filter, id_offset, want_words, filter_bit0)
+            out = self._range_call(qd, thr, K, filter, id_offset, want_words, filter_bit0, boost)
             out = tuple(t.cpu() if t is not None else None for t in out)
             return out if _is_torch(q) else tuple(t.numpy() if t is not None else None for t in out)
         ids = np.empty((B, K), dtype=np.int64)
@@ -3020,7 +3088,8 @@ class DeviceIndex:
         counts = np.empty(B, dtype=np.int64)
         words = np.empty((B, W), dtype=np.int32) if want_words else None
         ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None and a.size else None
-        nat.check(fn(self._h, p, dt, ldq, B, ptr(thr), K, None, 0, 0, int(id_offset), ptr(ids), ptr(scores), ptr(counts), ptr(words), W, None))
+        extra, keep_boost = _boost_c_args(boost, None) if boost is not None else ((), None)
+        nat.check(fn(self._h, p, dt, ldq, B, ptr(thr), K, None, 0, 0, int(id_offset), ptr(ids), ptr(scores), ptr(counts), ptr(words), W, *extra, None))
         if _is_torch(q):
             import torch
             return (torch.from_numpy(ids), torch.from_numpy(scores), torch.from_numpy(counts), torch.from_numpy(words) if want_words else None)
@@ -3034,6 +3103,41 @@ class DeviceIndex:
             from .doc_filter import as_doc_filter
             f = as_doc_filter(filter, int(self.info().n_rows), device=self.device, batch=B)
         return self._range_call(q, thr, K, f, id_offset, want_words)
+
+    def _boosted(self, q, boosts, weights, mode, min_score, max_hits, filter, id_offset, want_words):
+        B, thr, K, boost = _boost_args(q, boosts, weights, mode, min_score, max_hits, int(self.info().n_rows))
+        nat.require_device()
+        f = None
+        if filter is not None:
+            from .doc_filter import as_doc_filter
+            f = as_doc_filter(filter, int(self.info().n_rows), device=self.device, batch=B)
+        return self._range_call(q, thr, K, f, id_offset, want_words, boost=boost)
+
+    def search_boosted(self, q, boosts, weights, mode: str = "add", min_score=None, max_hits: int = 100, filter=None,
+                       id_offset: int = 0) -> RangeResults:
+        """search_range with a BOOSTED score in the place of the score: relevance plus ("add") or times ("mul") a weighted sum of up to 4
+        numeric fields, exact -- every live, allowed document is scored, so with min_score=None the list is the exact top max_hits by
+        boosted score, not a rescore window.  boosts: a list of value columns [n_rows] (float32 / int32, value_column() converts; NaN /
+        INT32_MIN = no value, which is neutral); weights: one per field, or [B, F].  S = the fp64 row sum of search_range before its
+        rounding, t_j = fp64(w_j) * fp64(value_j) (0 for w_j == 0 or a missing value); "add": fl32(((S + t_0) + t_1) ...), "mul":
+        fl32(S * (((1 + t_0) + t_1) ...)); a NaN result matches nothing.  With every weight 0 it is search_range bit for bit.  min_score:
+        a floor on the boosted score (None: none).  -> RangeResults(ids, boosted scores, counts) as search_range."""
+        ids, scores, counts, _ = self._boosted(q, boosts, weights, mode, min_score, max_hits, filter, id_offset, False)
+        return RangeResults(ids, scores, counts)
+
+    def count_boosted(self, q, boosts, weights, mode: str = "add", min_score=None, filter=None):
+        """The number of live, allowed documents whose boosted score is at least min_score, per query: int64 [B]."""
+        return self._boosted(q, boosts, weights, mode, min_score, 0, filter, 0, False)[2]
+
+    def boosted_filter(self, q, boosts, weights, mode: str = "add", min_score=None, filter=None):
+        """The documents search_boosted matches, as a per-query DocFilter [B, W] on the index's device (as match_filter)."""
+        from .doc_filter import DocFilter
+        import torch
+        _boost_args(q, boosts, weights, mode, min_score, 0)
+        dev = torch.device("cuda", self.device)
+        qd = q.to(dev) if _is_torch(q) else torch.from_numpy(np.ascontiguousarray(q)).to(dev)
+        words = self._boosted(qd, boosts, weights, mode, min_score, 0, filter, 0, True)[3]
+        return DocFilter(words, int(self.info().n_rows))
 
     def last_range_plan(self):
         """(row chunks, rows a chunk) of the scan the most recent range search on this index took (vs_index_last_range_plan)"""
@@ -3723,6 +3827,25 @@ class ShardGroup:
         """DeviceIndex.match_filter over the group's rows: the shards' bitmaps at their bit offsets, on the first shard's GPU."""
         from .doc_filter import DocFilter
         return DocFilter(_range_shards(self, q, min_score, 0, filter, True)[3], self.n_rows)
+
+    def _boosted(self, q, boosts, weights, mode, min_score, max_hits, filter, want_words):
+        _, thr, K, boost = _boost_args(q, boosts, weights, mode, min_score, max_hits, self.n_rows)
+        return _range_shards(self, q, thr, K, filter, want_words, boost)
+
+    def search_boosted(self, q, boosts, weights, mode: str = "add", min_score=None, max_hits: int = 100, filter=None) -> RangeResults:
+        """DeviceIndex.search_boosted over the group's rows (global ids): search_range's shard rule -- every shard gets its row slice of every
+        field, its id_offset and its bit range of the filter; lists merged, counts summed.  Equal to the unsharded index bit for bit."""
+        ids, sc, counts, _ = self._boosted(q, boosts, weights, mode, min_score, max_hits, filter, False)
+        return RangeResults(*_range_out(q, ids, sc, counts))
+
+    def count_boosted(self, q, boosts, weights, mode: str = "add", min_score=None, filter=None):
+        """DeviceIndex.count_boosted over the group's rows: the shards' counts summed."""
+        return _range_out(q, self._boosted(q, boosts, weights, mode, min_score, 0, filter, False)[2])[0]
+
+    def boosted_filter(self, q, boosts, weights, mode: str = "add", min_score=None, filter=None):
+        """DeviceIndex.boosted_filter over the group's rows: the shards' bitmaps at their bit offsets, on the first shard's GPU."""
+        from .doc_filter import DocFilter
+        return DocFilter(self._boosted(q, boosts, weights, mode, min_score, 0, filter, True)[3], self.n_rows)
 
     # ---- facet counts -----------------------------------------------------------------------------------------------------------------------
     def facet_counts(self, labels, n_labels: int, filter=None, rows_per_chunk: int = 0) -> FacetCounts:

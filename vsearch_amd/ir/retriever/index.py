@@ -29,6 +29,7 @@ from ...device_index import ValuePercentiles, _percentile_args, quantile_lerp
 from ...device_index import FacetValueHistogram, FacetValueStats
 from ...device_index import FacetValuePercentiles, MAX_VALUE_RANKS
 from ...device_index import SetIds, SetSample, _set_sample_args, _set_window_args
+from ...device_index import BOOST_MODES, MAX_BOOST_FIELDS
 from ...device_index import _col_mask
 
 logger = logging.getLogger(__name__)
@@ -527,6 +528,42 @@ class Index:
         with other filters through ``&``, ``|``, ``~``."""
         target, q = self._range_queries(q_embs, min_score, 0)
         return target.match_filter(q, min_score, filter=filter)
+
+    # ---- boosted search (not in the reference: rank by relevance and numeric fields together, exact) ----------------------------------------
+    def _boost_fields(self, boosts, B):
+        """the argument errors of `boosts` that need no device -> (field names, weights float32 [B, F])"""
+        if not isinstance(boosts, dict) or not boosts:
+            raise TypeError('boosts must be a non-empty dict of value field -> weight, e.g. {"recency": 0.3}')
+        if len(boosts) > MAX_BOOST_FIELDS:
+            raise ValueError(f"a boosted search takes at most {MAX_BOOST_FIELDS} fields, got {len(boosts)}")
+        store = self._value_store()
+        for name in boosts:
+            if name not in store:
+                raise KeyError(f"no value field {name!r}: set_values() or values_from_samples() first (fields: {list(store)})")
+        w = np.empty((B, len(boosts)), dtype=np.float32)
+        for j, (name, wj) in enumerate(boosts.items()):
+            wj = np.asarray(wj.detach().cpu().numpy() if isinstance(wj, torch.Tensor) else wj, dtype=np.float32)
+            if wj.ndim > 1 or (wj.ndim == 1 and wj.shape[0] != B):
+                raise ValueError(f"the weight of {name!r}: a number, or one per query ({B}); got shape {tuple(wj.shape)}")
+            w[:, j] = wj
+        if not np.isfinite(w).all():
+            raise ValueError("weights must be finite")
+        return list(boosts), w
+
+    def search_boosted(self, q_embs, k: int = 100, boosts=None, mode: str = "add", min_score=None, filter=None) -> RangeResults:
+        """The exact top k by BOOSTED score: relevance plus (mode="add") or times (mode="mul") a weighted sum of up to 4 value fields
+        (``set_values`` / ``values_from_samples``), e.g. boosts={"recency": 0.3, "views": 0.1}; a weight is a number or one per query.
+        "add": score + sum_j w_j * value_j; "mul": score * (1 + sum_j w_j * value_j); a document without a value gets no boost from that
+        field.  Every document is scored -- this is no rescore of a deeper top-k -- with one pinned numerics (``DeviceIndex.search_boosted``),
+        so the result is reproducible bit for bit.  min_score: a floor on the boosted score.  -> RangeResults(ids, boosted scores, counts):
+        counts [B] is the number of documents at or above the floor (all live, allowed ones without one).  k in 0..2048.  Deleted documents
+        and `filter` (as ``search``) apply.  Works on a row-sharded index as well."""
+        if mode not in BOOST_MODES:
+            raise ValueError(f"mode must be one of {sorted(BOOST_MODES)}, got {mode!r}")
+        names, w = self._boost_fields(boosts, 1 if q_embs.ndim == 1 else int(q_embs.shape[0]))      # (before any device work)
+        target, q = self._range_queries(q_embs, -np.inf if min_score is None else min_score, k)
+        res = target.search_boosted(q, [self._value_field(n) for n in names], w, mode=mode, min_score=min_score, max_hits=int(k), filter=filter)
+        return RangeResults(self._to_api(res.ids), self._to_api(res.scores.to(self._dtype)), self._to_api(res.counts))
 
     # ---- facets (not in the reference: per-label counts of a document set, the summary beside a result list) ------------------------------
     def _facet_store(self):

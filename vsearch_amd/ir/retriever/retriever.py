@@ -122,6 +122,26 @@ class Retriever(BiEncoder):
         q_emb = self.process_query(queries, dropout, a, batch_size=batch_size)
         return index.search_range(q_emb, min_score, max_hits=max_hits, filter=filter)
 
+    def retrieve_boosted(self, queries: Union[List[str], np.ndarray, T], k: int = 5, boosts=None, mode: str = "add", min_score=None,
+                         dropout: float = 0, a: int = None, index: Index = None, batch_size: int = 32, filter=None, must=None, must_not=None,
+                         should=None, min_should: int = None) -> RangeResults:
+        """The exact top k by relevance and value fields together -- ``Index.search_boosted`` behind the query encoder:
+        boosts={"recency": 0.3, "views": 0.1} adds (mode="add") or multiplies in (mode="mul") a weighted sum of the documents' values.
+        Every document is scored, so no hit is lost behind a rescore window.  `filter` and the term constraints as in ``retrieve``."""
+        index = index or self.index
+        if index is None:
+            raise RuntimeError("no index: call build_index / load_index first")
+        if must is not None or must_not is not None or should is not None or min_should is not None:
+            terms = self.term_filter(must=must, must_not=must_not, should=should, min_should=min_should, index=index)
+            if filter is not None:
+                from ...doc_filter import as_doc_filter
+                filter = as_doc_filter(filter, terms.n_rows, device=terms.device) & terms
+            else:
+                filter = terms
+        a = a or self.encoder_q.config.topk
+        q_emb = self.process_query(queries, dropout, a, batch_size=batch_size)
+        return index.search_boosted(q_emb, k=k, boosts=boosts, mode=mode, min_score=min_score, filter=filter)
+
     def retrieve_facets(self, queries: Union[List[str], np.ndarray, T], field: str, min_score, topn: int = 10, min_count: int = 1,
                         dropout: float = 0, a: int = None, index: Index = None, batch_size: int = 32, filter=None, must=None, must_not=None,
                         should=None, min_should: int = None):
