@@ -1206,8 +1206,16 @@ VS_API int vs_merge_topk(const int64_t* cand_ids, const float* cand_scores, int3
 
 /* ---- sparsify: src/ir/utils/sparse.py + the tail of VDREncoder.embed (vdr.py:152-169) -------- */
 
-/* build_topk_mask (sparse.py:8-14): mask[b, c] = 1 iff x[b, c] is among the k largest of row b
- * (ties at the k-th value: lower column wins).  x: [B, V] fp32 device/host, mask: [B, V] uint8.    */
+/* Selection rule of every top-k mask below (vs_topk_mask, vs_embed_mask, vs_embed_mask_to_csr): a row's k largest ORDER KEYS, ties at
+ * the k-th key: lower column wins.  The order key of an fp32 value is its bit pattern with the sign bit set (non-negative values) or
+ * with all bits inverted (negative values), compared as an unsigned integer.  That is the float order on all values that compare,
+ * and beyond it: +0.0 ranks above -0.0 (for the row [-0.0, +0.0, -1.0] and k = 1 column 1 is selected, not column 0), and NaNs rank by
+ * bit pattern: positive NaNs above +inf, negative NaNs below -inf.  Only vs_topk_mask's bytes can show which of two zeros was taken:
+ * a kept and a dropped zero are the same bits in vs_embed_mask's output, and the CSR holds neither.
+ * (tests/_sparsify_ref.py restates this rule; tests/test_gpu_sparsify_edges.py pins the kernels to it)                              */
+
+/* build_topk_mask (sparse.py:8-14): mask[b, c] = 1 iff x[b, c] is among the k largest of row b by the rule above
+ * (ties at the k-th key: lower column wins).  x: [B, V] fp32 device/host, mask: [B, V] uint8.    */
 VS_API int vs_topk_mask(const float* x, int32_t B, int32_t V, int64_t ld, int32_t k, uint8_t* mask, int device, void* stream);
 
 /* build_bow_mask (sparse.py:21-29): multi-hot of token ids over `vocab`, first `shift` columns
@@ -1225,8 +1233,11 @@ VS_API int vs_embed_mask(float* emb, int64_t ld, const int64_t* ids, int32_t B, 
 /* The mask stage of VDREncoder.embed FUSED with Tensor.to_sparse_csr() (vdr.py:152-169 + retriever.py:304; SURVEY.md 8(f1) "write CSR
  * rows directly"): x [B, V] fp32 (device; NOT modified) -> the CSR of x * (topk_mask | lexical_mask): int64 rowptr [B + 1], int32 cols /
  * fp32 vals [cap] (device; cap >= B * (topk + L) always suffices; nnz = rowptr[B]).  One read of [B, V] instead of the five passes of
- * vs_embed_mask + vs_dense_to_csr.  VS_EUNSUPPORTED outside the fused kernel's range (topk <= 0, V > 32 Ki, topk + L > 8192): use
- * those two.                                                                                      */
+ * vs_embed_mask + vs_dense_to_csr.  VS_EUNSUPPORTED outside the fused kernel's range (topk <= 0, V > 32 Ki, min(V, topk + L) > 8192):
+ * use those two.
+ * What is stored: the KEPT elements that are not +-0.0, in column order (a kept NaN or +-inf is stored as it is).  The fused call
+ * expects finite input: an unselected NaN or +-inf is dropped, where vs_embed_mask + vs_dense_to_csr (and torch) store the NaN that
+ * x * 0 makes of it.  On finite input the two paths give the same CSR bit for bit.                                                  */
 VS_API int vs_embed_mask_to_csr(const float* x, int64_t ld, const int64_t* ids, int32_t B, int32_t L, int32_t vocab, int32_t shift,
                                 int32_t topk, int activate_lexical, int64_t* rowptr, int32_t* cols, float* vals, int64_t cap,
                                 int device, void* stream);

@@ -39,7 +39,8 @@ def elu1p(x):
 
 def build_topk_mask(embs, k: int = 768, dim: int = -1):
     """Bool mask of the k largest entries of each row (sparse.py:8-14). Ties at the k-th value go to
-    the lowest column ids (torch.topk leaves them unspecified)."""
+    the lowest column ids (torch.topk leaves them unspecified).  Values compare by their order key
+    (include/vsearch_hip.h): the float order, with +0.0 above -0.0 and NaNs by bit pattern."""
     if isinstance(embs, np.ndarray):
         embs = torch.from_numpy(embs)
     if dim not in (-1, embs.dim() - 1):
@@ -97,7 +98,8 @@ FUSED_CSR_MAX_KEPT = 8192      # kMrStage (csrc/mask_rows_fast.h): kept elements
 def embed_mask_to_csr(emb: torch.Tensor, input_ids, vocab_size: int, shift_num: int, topk: int, activate_lexical: bool):
     """The mask stage of VDREncoder.embed (vdr.py:152-169) fused with Tensor.to_sparse_csr() (retriever.py:304): pooled activations
     emb [B, V] (CUDA fp32, NOT modified) -> (rowptr int64 [B+1], cols int32 [nnz], vals fp32 [nnz]) of emb * (topk_mask | lexical_mask).
-    One read of [B, V]; the masked dense batch is never written.  NotImplementedError outside the fused kernel's range (topk <= 0,
+    One read of [B, V]; the masked dense batch is never written.  Expects finite input: an unselected NaN / inf is dropped, where
+    apply_embed_mask_ + dense_to_csr store the NaN of x * 0 (include/vsearch_hip.h).  NotImplementedError outside the fused kernel's range (topk <= 0,
     V > 32 Ki, topk + L > 8192): callers then use apply_embed_mask_ + dense_to_csr."""
     assert emb.is_cuda and emb.dtype == torch.float32 and emb.is_contiguous()
     dev = _dev_of(emb)
