@@ -447,8 +447,8 @@ VS_API int vs_term_sum_topn(const int64_t* sums, int64_t ld_sums, const int64_t*
  * device pointers on the index's device / `device` (VS_EINVAL for a mix); device pointers and a non-NULL stream only enqueue (the slab is freed
  * behind a stream synchronisation either way).  A dense index on the matrix cores keeps no packets: VS_EUNSUPPORTED.
  * Not covered: the top-m nearest centroids and soft assignment; the dense matrix kind; a shard group has no entry point of its own (every shard
- * assigns its rows with its bit range of the filter: a row's value depends on nothing but the row) and the one-process-per-GPU RCCL path has none; a
- * fused per-label sums kernel (the k-means update goes through vs_label_bitmaps and vs_index_term_sums, 64 clusters a call).                    */
+ * assigns its rows with its bit range of the filter: a row's value depends on nothing but the row) and the one-process-per-GPU RCCL path has none.
+ * (The k-means update takes the sums of all K clusters from one vs_index_label_term_sums call, below.)                                          */
 #define VS_ASSIGN_MAX_K 4096         /* centroids of one vs_index_assign call */
 #define VS_LABEL_MAX_VALUES 4096     /* bitmaps of one vs_label_bitmaps call */
 VS_API int vs_assign_plan(int64_t n_rows, int32_t K, int32_t n_cols, int64_t rows_per_chunk, int32_t* out_slice_w, int32_t* out_slices,
@@ -458,6 +458,56 @@ VS_API int vs_index_assign(vs_index* index, const float* centroids, int64_t ldc,
                            int64_t filter_bit0, int64_t rows_per_chunk, int32_t* out_labels, float* out_values, void* stream);
 VS_API int vs_label_bitmaps(const int32_t* labels, int64_t n_rows, const int32_t* values, int32_t B, int64_t bit0, uint32_t* out_words,
                             int64_t ld_words, int device, void* stream);
+
+/* ---- per-label term aggregations: the term sums / term counts of every label's rows in one pass (no reference counterpart) -------------------
+ * The "x facet label" product of vs_index_term_sums and vs_index_term_counts: the centroid of every cluster, category or article at once.  Every
+ * row has one label, so the work is one visit per stored cell whatever the number of labels; the answers are the integers of the calls above, so
+ * row l equals, bit for bit, vs_index_term_sums / vs_index_term_counts on the set "label == l AND set".
+ * Inputs: a CSR-packet index; labels int32 [n_rows]; n_labels in 1..VS_LABEL_TERM_MAX_LABELS; ONE document set -- bit bit0 + r of `words` stands
+ * for row r, words == NULL: every row; the handle's live bitmap is ANDed in at bit 0 whatever bit0 is; bits at or past bit0 + n_rows are ignored.
+ * vs_index_label_term_sums: sums [n_labels, ld_sums] int64 (ld_sums >= n_cols): sums [l, c] = the sum of fx(v) -- the fixed point of the term sums,
+ *   unchanged: a binary store, the padding column, stored +-0, NaN and the wrap modulo 2^64 as there -- over the stored cells (r, c) of the set
+ *   rows with labels [r] == l.  total [n_labels] int64: the set rows of each label.  other [1] int64: the set rows whose label is outside [0,
+ *   n_labels) (-1 = "no label" included); they contribute nowhere.  total.sum() + other [0] = vs_set_count of the same set.  Every element
+ *   of sums [:, 0 .. n_cols), of total and of other is written; columns [n_cols, ld_sums) are not touched.
+ * vs_index_label_term_counts: the same shape; counts [l, c] = the set rows of label l that HAVE column c (stored with a non-zero value: the
+ *   definition of vs_index_term_counts).  A binary index's sums are its counts x 2^24.
+ * vs_label_order: the set rows grouped by label, the first stage of the two calls, public so that it can be pinned: ptr int64 [n_labels + 1],
+ *   the exclusive bases of the per-label set-row counts (ptr [n_labels] = the rows listed); rows uint32 [n_rows], of which the first ptr [n_labels]
+ *   are written: rows [ptr [l] .. ptr [l + 1]) are the set rows of label l in NO SPECIFIED ORDER (compare them sorted); other [1] as above.  Any
+ *   index kind.  Up to VS_FACET_LDS_BINS labels a workgroup counts and ranks its chunk's rows in an LDS histogram and reserves a label's range with
+ *   one global atomic; above, every set row takes one global atomic.
+ * Kernels (label_terms.hip): the label order (count, one-workgroup scan, place), a small kernel that cuts every label's segment into items of at
+ * most rows_per_item rows -- sum over labels of ceil(cnt / rows_per_item) of them --, and one 1024-thread workgroup per (item, column tile) that
+ * zeroes a tile of 64-bit (sums) or 32-bit (counts) LDS bins, streams the packets of the item's rows and flushes the non-zero bins with 64-bit
+ * atomics into row `label`.  The grid is sized by the bound max_items = ceil(n_rows / rows_per_item) + n_labels; items past the real count exit
+ * at once -- nothing is read back to the host between the stages.  The scratch (4 bytes a row, 16 an item, 24 a label) is kept by the handle.
+ * vs_label_term_plan: the launch for these arguments -- pure host arithmetic, no device needed.  tile_cols as in vs_term_sum_plan (0 = automatic,
+ *   else 1..VS_TERM_SUM_TILE_COLS taken as given).  rows_per_item = 0: automatic -- the chunk rule of the term aggregations over `tiles` work
+ *   items (~ 1024 / tiles items over the rows, at least 2048 rows each); any other value must be a positive multiple of 64 and is taken as given.
+ *   Both are tuning knobs: NO OUTPUT DEPENDS ON THE PLAN.
+ * Errors: NULL handle, labels or outputs, n_labels outside 1..VS_LABEL_TERM_MAX_LABELS, bit0 < 0, rows_per_item no multiple of 64, tile_cols outside
+ * 0..VS_TERM_SUM_TILE_COLS, ld too short, n_labels x ld beyond VS_LABEL_TERM_MAX_CELLS (1 GiB of int64: 4546 labels at 29 523 columns), max_items x
+ * tiles beyond VS_LABEL_TERM_MAX_WORK_ITEMS (a launch of 1024-thread workgroups holds fewer than 2^32 threads): VS_EINVAL -- checked before the device is
+ * touched.  Pointers: all host (staged; the call blocks) or all
+ * device pointers on the index's device (VS_EINVAL for a mix); device pointers and a non-NULL stream only enqueue.  A dense index on the matrix
+ * cores keeps no packets: VS_EUNSUPPORTED (vs_label_order serves it).
+ * Not covered: B > 1 sets in one call; two label arrays crossed; a sorted order inside a label; id-list driven sets; the dense matrix kind; a
+ * shard group has no entry point of its own (every shard takes its slice of the labels and its bit range of the set; the integer outputs are
+ * added, any top-n taken after the sum) and the one-process-per-GPU RCCL path has none.                                                          */
+#define VS_LABEL_TERM_MAX_LABELS 65536      /* labels of one call */
+#define VS_LABEL_TERM_MAX_CELLS (1ll << 27) /* n_labels x ld of one call: 1 GiB of int64 */
+#define VS_LABEL_TERM_MAX_WORK_ITEMS 4194303 /* max_items x tiles of one call: (2^32 - 1) / 1024 workgroups of 1024 threads */
+VS_API int vs_label_term_plan(int64_t n_rows, int32_t n_labels, int32_t n_cols, int64_t rows_per_item, int32_t tile_cols, int32_t* out_tiles,
+                              int32_t* out_tile_cols, int64_t* out_rows_per_item, int64_t* out_max_items);
+VS_API int vs_label_order(vs_index* index, const uint32_t* words, int64_t bit0, const int32_t* labels, int32_t n_labels, int64_t* ptr,
+                          uint32_t* rows, int64_t* other, void* stream);
+VS_API int vs_index_label_term_sums(vs_index* index, const uint32_t* words, int64_t bit0, const int32_t* labels, int32_t n_labels,
+                                    int64_t rows_per_item, int32_t tile_cols, int64_t* sums, int64_t ld_sums, int64_t* total, int64_t* other,
+                                    void* stream);
+VS_API int vs_index_label_term_counts(vs_index* index, const uint32_t* words, int64_t bit0, const int32_t* labels, int32_t n_labels,
+                                      int64_t rows_per_item, int32_t tile_cols, int64_t* counts, int64_t ld_counts, int64_t* total, int64_t* other,
+                                      void* stream);
 
 /* ---- numeric fields: range filters, stats, histograms and sort by value over a per-row quantity (no reference counterpart) ------------------
  * A field is one 32-bit value per row: values [n_rows] of dtype VS_VAL_F32 (fp32) or VS_VAL_I32 (int32).  A row may have NO value: the missing

@@ -35,6 +35,8 @@ TERM_LDS_COLS, TERM_MAX_TOPN, TERM_LIFT, TERM_JLH = 36864, 1024, 0, 1
 TERM_FX_SHIFT, TERM_FX_CLAMP_LOG2, TERM_SUM_TILE_COLS = 24, 20, 18432
 # clustering (VS_ASSIGN_MAX_K, VS_LABEL_MAX_VALUES): the most centroids of vs_index_assign, the most bitmaps of vs_label_bitmaps
 ASSIGN_MAX_K, LABEL_MAX_VALUES = 4096, 4096
+# per-label term aggregations (VS_LABEL_TERM_MAX_*): the most labels, the most cells (n_labels x ld), the most work items (max_items x tiles) of one call
+LABEL_TERM_MAX_LABELS, LABEL_TERM_MAX_CELLS, LABEL_TERM_MAX_WORK_ITEMS = 65536, 1 << 27, 4194303
 # numeric fields (VS_VAL_*, VS_VALUE_MAX_*): the value types, the most ranges of vs_value_range_bitmaps, edges of a histogram, rows of vs_value_topk
 VAL_F32, VAL_I32, VALUE_MAX_RANGES, VALUE_MAX_EDGES, VALUE_MAX_TOPK = 0, 1, 4096, 1025, 1024
 # percentiles (VS_VALUE_RADIX_*, VS_VALUE_MAX_RANKS, VS_QUANTILE_*): bins of a radix level, the levels, the most ranks of a call, the rank rules
@@ -100,6 +102,10 @@ _SIGNATURES = {
     "vs_centroid_half_norms": ([_vp, _i64, _i32, _i32, _int, _vp, _int, _vp], _int),
     "vs_index_assign": ([_vp, _vp, _i64, _i32, _vp, _vp, _i64, _i64, _vp, _vp, _vp], _int),
     "vs_label_bitmaps": ([_vp, _i64, _vp, _i32, _i64, _vp, _i64, _int, _vp], _int),
+    "vs_label_term_plan": ([_i64, _i32, _i32, _i64, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i64)], _int),
+    "vs_label_order": ([_vp, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp], _int),
+    "vs_index_label_term_sums": ([_vp, _vp, _i64, _vp, _i32, _i64, _i32, _vp, _i64, _vp, _vp, _vp], _int),
+    "vs_index_label_term_counts": ([_vp, _vp, _i64, _vp, _i32, _i64, _i32, _vp, _i64, _vp, _vp, _vp], _int),
     "vs_value_range_bitmaps": ([_vp, _int, _i64, _vp, _vp, _i32, _i64, _vp, _i64, _int, _vp], _int),
     "vs_value_plan": ([_i64, _i32, _i32, _int, _i64, C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i64)], _int),
     "vs_value_stats": ([_vp, _i64, _i64, _vp, _i32, _vp, _int, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _int, _vp], _int),

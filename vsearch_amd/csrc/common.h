@@ -322,6 +322,7 @@ struct vs_index {
     vs::DevBuf ws_q, ws_cand, ws_out_ids, ws_out_scores, ws_misc, ws_mq_meta, ws_mq_q, ws_mq_cand, ws_fb, ws_pace;
     vs::DevBuf ws_filt;           // a host filter's bitmap staged on the device
     vs::DevBuf ws_qpad;           // the one-query scan of an index too wide for its LDS image: the queries as rows of n_cols + 1 floats
+    vs::DevBuf ws_label;          // the per-label term aggregations (label_terms.hip): label counts and bases, the set rows grouped by label, the item table
     vs::FilterArgs filt{};        // the document filter of the search in progress (vs_index_search_filtered; words == nullptr: none)
     bool logical_dense = false;   // dense Index stored as CSR packets (sparsity-aware dense index)
     // tombstones (mutable.hip): deletion state of the handle, applied by every search as a document filter

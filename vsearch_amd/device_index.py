@@ -1057,13 +1057,21 @@ def _term_ids(ids):
     return ids
 
 
-def _top_terms(obj, filter, ids, topn, method, min_count, background):
-    """term_counts of the set, the background (given, or every live document: one more pass), then the top-n on the object's first GPU"""
-    import torch
-    topn, method, min_count = _term_topn_args(topn, method, min_count)
+def _background_arg(background):
     if background is not None and (not isinstance(background, tuple) or len(background) != 2):
         raise TypeError("background must be a TermCounts (what term_counts() returns)")
-    fg = obj.term_counts(filter=filter, ids=ids)
+
+
+def _top_terms(obj, filter, ids, topn, method, min_count, background):
+    """term_counts of the set, the background (given, or every live document: one more pass), then the top-n on the object's first GPU"""
+    topn, method, min_count = _term_topn_args(topn, method, min_count)
+    _background_arg(background)
+    return _top_terms_of(obj, obj.term_counts(filter=filter, ids=ids), topn, method, min_count, background)
+
+
+def _top_terms_of(obj, fg, topn, method, min_count, background):
+    """the top-n of counts already taken: fg = (counts [B, V], total [B]) on obj's GPU, one row a query -- or a label (_label_top_terms)"""
+    import torch
     dev = fg.counts.device
     if background is None and method != "count":
         background = obj.term_counts()
@@ -1208,6 +1216,77 @@ def _top_weights(obj, filter, ids, topn, min_count):
     counts = obj.term_counts(filter=filter, ids=ids).counts if min_count > 0 else None
     cols, scores, sums = term_sum_topn(res.sums, res.total, topn, counts=counts, min_count=min_count, device=obj.device)
     return TopWeights(cols, scores, sums, res.total)
+
+
+# ---- per-label term aggregations: the term sums / counts of every label's rows in one pass (vs_label_term_plan, vs_label_order, ------------------
+# vs_index_label_term_sums, vs_index_label_term_counts)
+MAX_LABEL_TERM_LABELS = nat.LABEL_TERM_MAX_LABELS
+MAX_LABEL_TERM_CELLS = nat.LABEL_TERM_MAX_CELLS
+
+
+class LabelTermSums(NamedTuple):
+    """label_term_sums: per label the fixed-point weight the set's documents with that label put on each vocabulary column (sums int64
+    [n_labels, n_cols], ``TermSums``'s fixed point), the set's documents of each label (total int64 [n_labels]) and its documents whose
+    label is outside [0, n_labels) (other int64 [1]): total.sum() + other is the size of the set.  Row l is, bit for bit, ``term_sums`` of
+    the set ``from_labels(labels, [l]) & filter``."""
+    sums: Any
+    total: Any
+    other: Any
+
+    def values(self):
+        """the sums as float64 [n_labels, n_cols]: sums * 2^-24"""
+        return TermSums(self.sums, self.total).values()
+
+    def mean(self):
+        """every label's centroid, float32 [n_labels, n_cols]: ``TermSums.mean``'s chain; a label without documents gets an all-zero row"""
+        return TermSums(self.sums, self.total).mean()
+
+
+class LabelTermCounts(NamedTuple):
+    """label_term_counts: per label the set's documents with that label that have each vocabulary column (counts int64 [n_labels, n_cols]),
+    with total [n_labels] and other [1] as in ``LabelTermSums``."""
+    counts: Any
+    total: Any
+    other: Any
+
+
+class LabelOrder(NamedTuple):
+    """label_order: the set's documents grouped by label -- rows int64 [n_set], of which rows[ptr[l]:ptr[l + 1]] are the documents of label
+    l in no specified order; ptr int64 [n_labels + 1]; other int64 [1], the set's documents whose label is outside [0, n_labels)."""
+    ptr: Any
+    rows: Any
+    other: Any
+
+
+def label_term_plan(n_rows: int, n_labels: int, n_cols: int, rows_per_item: int = 0, tile_cols: int = 0):
+    """The launch vs_index_label_term_sums / _counts take for these arguments (vs_label_term_plan; pure host arithmetic, no GPU needed) ->
+    (tiles, tile_cols, rows_per_item, max_items): a workgroup owns one column tile of one item, at most rows_per_item rows of one label;
+    the grid holds max_items = ceil(n_rows / rows_per_item) + n_labels items a tile."""
+    tiles, tc, rpi, items = C.c_int32(0), C.c_int32(0), C.c_int64(0), C.c_int64(0)
+    nat.check(nat.lib().vs_label_term_plan(int(n_rows), int(n_labels), int(n_cols), int(rows_per_item), int(tile_cols), C.byref(tiles),
+                                           C.byref(tc), C.byref(rpi), C.byref(items)))
+    return tiles.value, tc.value, rpi.value, items.value
+
+
+def label_term_slices(n_labels: int, n_cols: int):
+    """The labels [0, n_labels) cut into slices (l0, n) that one label_term_sums / label_term_counts call takes: n <= 65 536 and n x n_cols <=
+    2^27.  A caller with more cells than one call holds -- a k-means of K = 4096 clusters over 65 535 columns -- takes a slice a call with
+    ``labels - l0`` as the labels (a label outside the slice falls outside [0, n): it contributes nowhere); the integers are those of one call."""
+    step = max(1, min(MAX_LABEL_TERM_LABELS, MAX_LABEL_TERM_CELLS // max(int(n_cols), 1)))
+    return [(l0, min(step, int(n_labels) - l0)) for l0 in range(0, int(n_labels), step)]
+
+
+def _label_term_args(labels, n_labels, n_rows, n_cols=None, rows_per_item=0, tile_cols=0):
+    """Argument checks of a per-label term aggregation that need no device -> (n_labels, rows_per_item, tile_cols)"""
+    n_labels, _ = _facet_args(labels, n_labels, n_rows)
+    if n_labels > MAX_LABEL_TERM_LABELS:
+        raise ValueError(f"n_labels must be in 1..{MAX_LABEL_TERM_LABELS}, got {n_labels}")
+    if n_cols is not None and n_labels * int(n_cols) > MAX_LABEL_TERM_CELLS:
+        raise ValueError(f"n_labels x n_cols = {n_labels * int(n_cols)} is more than {MAX_LABEL_TERM_CELLS} cells (1 GiB of int64)")
+    if isinstance(rows_per_item, bool) or not isinstance(rows_per_item, (int, np.integer)) or rows_per_item < 0 or rows_per_item % 64:
+        raise ValueError(f"rows_per_item must be 0 (automatic) or a positive multiple of 64, got {rows_per_item!r}")
+    _, tile_cols = _term_sum_args(0, tile_cols)
+    return n_labels, int(rows_per_item), tile_cols
 
 
 # ---- clustering: the nearest of K centroids for every row (vs_assign_plan, vs_index_assign, vs_centroid_half_norms, vs_label_bitmaps) -----------
@@ -1816,7 +1895,7 @@ def _facet_quantile_batches(q, ranks, cells, call):
     return (torch.cat([p[0] for p in parts], dim=2), torch.cat([p[1] for p in parts], dim=2)) + tuple(parts[0][2:])
 
 
-KMEANS_UPDATE_BATCH = 64                               # clusters whose sums one term_sums call of the update takes
+KMEANS_UPDATE_BATCH = 64                               # clusters a term_sums call took when the update went through from_labels (kept: callers batch by it)
 KMEANS_METRICS = ("dot", "l2")
 
 
@@ -1865,11 +1944,11 @@ def kmeans_loop(target, centroids, iters: int, metric: str = "l2", filter=None):
     """Lloyd's iteration over the rows of `target` (a DeviceIndex or a ShardGroup) from float32 start centroids [K, V] on its GPU ->
     (centroids, labels, values, n_iter, changed).  Per iteration: bias = -half_norms(C) under "l2" (none under "dot"); labels, values =
     assign(C, bias, filter); changed = the rows whose label differs from the previous assignment (first: the rows assigned); stop when
-    nothing changed; else, for the clusters in batches of 64, C[j] = term_sums(filter=from_labels(labels, batch) & filter).mean() where the
-    cluster has rows -- an empty cluster keeps its centroid.  The labels returned are the assignment under the centroids returned (one
+    nothing changed; else C = label_term_sums(labels, K, filter).mean() -- the sums of all K clusters in one pass, bit for bit those of
+    term_sums(filter=from_labels(labels, [j]) & filter) -- where the cluster has rows; an empty cluster keeps its centroid.  Where K x V is
+    more than the 2^27 cells of one call (label_term_slices) the update takes a slice of the clusters a pass: any K <= 4096 serves at any V.  The labels returned are the assignment under the centroids returned (one
     closing assign when the loop ends on `iters`).  Deterministic: every step is pinned bit for bit."""
     import torch
-    from .doc_filter import DocFilter
     dev = torch.device("cuda", target.device)
     C_ = centroids.detach().to(dev).to(torch.float32).contiguous().clone()
     K = int(C_.shape[0])
@@ -1887,14 +1966,10 @@ def kmeans_loop(target, centroids, iters: int, metric: str = "l2", filter=None):
         prev = cur
         if n_changed == 0:
             break
-        for b0 in range(0, K, KMEANS_UPDATE_BATCH):
-            batch = np.arange(b0, min(K, b0 + KMEANS_UPDATE_BATCH), dtype=np.int32)
-            sets = DocFilter.from_labels(cur.labels, batch, device=dev)
-            if filter is not None:
-                sets = sets & filter
-            ts = target.term_sums(filter=sets)
-            has = (ts.total > 0).reshape(-1, 1)
-            C_[b0:b0 + batch.size] = torch.where(has, ts.mean(), C_[b0:b0 + batch.size])
+        for l0, n in label_term_slices(K, int(C_.shape[1])):          # all K clusters in one pass (a row outside the filter carries -1) -- a
+            lab = cur.labels if n == K else cur.labels - l0           # slice a pass where K x V is more than one call's 2^27 cells
+            ts = target.label_term_sums(lab, n, filter=filter)
+            C_[l0:l0 + n] = torch.where((ts.total > 0).reshape(-1, 1), ts.mean(), C_[l0:l0 + n])
         stale = True
     if stale:
         prev = step()
@@ -2340,6 +2415,83 @@ def _term_sums(obj, filter, ids, rows_per_chunk, tile_cols):
         raise ValueError("the set is given by `filter` or by `ids`, not both")
     rows_per_chunk, tile_cols = _term_sum_args(rows_per_chunk, tile_cols)
     return _term_agg(obj, _TERM_SUMS, filter, ids, rows_per_chunk, (tile_cols,))
+
+
+def _one_set(obj, filter, what):
+    """filter= of a call that takes ONE document set -> (None | a shared DocFilter on obj's GPU, n_rows | None)"""
+    n = None if filter is None else obj.n_rows
+    f = _doc_set(filter, n, obj.device)
+    if f is not None and f.per_query:
+        raise ValueError(f"{what} takes ONE document set, not a per-query filter")
+    return f, n
+
+
+def _label_terms(obj, fn, result, labels, n_labels, filter, rows_per_item, tile_cols):
+    """label_term_sums / label_term_counts: every part takes its slice of the labels and its bit range of the set; the integer outputs are
+    added on obj's GPU -> result(matrix [L, V], total [L], other [1])"""
+    n_labels, rows_per_item, tile_cols = _label_term_args(labels, n_labels, obj.n_rows, _n_cols_of(obj), rows_per_item, tile_cols)
+    f, n = _one_set(obj, filter, fn)
+    nat.require_device()
+    import torch
+
+    def one(sh, l, fs, row0):
+        with torch.cuda.device(torch.device("cuda", sh.device)):   # (a shard of a group runs with its GPU current)
+            return sh._label_term_call(fn, l, n_labels, fs, row0, rows_per_item, tile_cols)
+    return result(*_facet_out(labels, *_add_parts(_shard_parts(obj, f, (_lab(labels),), one, n))))
+
+
+def _label_order(obj, labels, n_labels, filter):
+    """label_order: the parts' orders, each over its own rows, placed label by label behind one another (a part's rows + its first row)"""
+    n_labels, _, _ = _label_term_args(labels, n_labels, obj.n_rows)
+    f, n = _one_set(obj, filter, "label_order")
+    nat.require_device()
+    import torch
+    dev = torch.device("cuda", obj.device)
+
+    def one(sh, l, fs, row0):
+        with torch.cuda.device(torch.device("cuda", sh.device)):
+            ptr, rows, other = sh._label_order_call(l, n_labels, fs, row0)
+        return ptr, (rows[:int(ptr[-1])].to(torch.int64) & 0xFFFFFFFF) + row0, other
+    parts = _shard_parts(obj, f, (_lab(labels),), one, n)
+    if len(parts) == 1:
+        return LabelOrder(*_facet_out(labels, *parts[0]))
+    cnts = [p[0][1:] - p[0][:-1] for p in parts]
+    ptr = torch.zeros(n_labels + 1, dtype=torch.int64, device=dev)
+    ptr[1:] = torch.cumsum(sum(cnts[1:], cnts[0]), 0)
+    rows = torch.empty(int(ptr[-1]), dtype=torch.int64, device=dev)
+    before = torch.zeros(n_labels, dtype=torch.int64, device=dev)
+    ar = torch.arange(n_labels, device=dev)
+    for (p_ptr, p_rows, _), cnt in zip(parts, cnts):
+        lab = torch.repeat_interleave(ar, cnt)                     # the label of every entry of the part's order
+        at = torch.arange(p_rows.numel(), device=dev) - p_ptr[:-1][lab]
+        rows[ptr[:-1][lab] + before[lab] + at] = p_rows
+        before += cnt
+    return LabelOrder(*_facet_out(labels, ptr, rows, sum((p[2] for p in parts[1:]), parts[0][2])))
+
+
+def _label_top_weights(obj, labels, n_labels, filter, topn, min_count):
+    """label_term_sums of the set (and its label_term_counts when min_count asks for them: a second pass over the set and the cells, the
+    label order built again), then the top-n of every label on obj's first GPU -> TopWeights [n_labels, topn]"""
+    import torch
+    topn, min_count = _weight_topn_args(topn, min_count)
+    lab = labels if _is_torch(labels) else torch.from_numpy(np.ascontiguousarray(labels))
+    parts = []
+    for l0, n in label_term_slices(int(n_labels), _n_cols_of(obj)):                  # (one slice unless n_labels x V is more than one call holds)
+        sl = lab if n == int(n_labels) else lab - l0
+        res = obj.label_term_sums(sl, n, filter=filter)
+        counts = obj.label_term_counts(sl, n, filter=filter).counts if min_count > 0 else None       # (a second pass, label order included)
+        parts.append(term_sum_topn(res.sums, res.total, topn, counts=counts, min_count=min_count, device=obj.device) + (res.total,))
+    return TopWeights(*(parts[0] if len(parts) == 1 else (torch.cat(x) for x in zip(*parts))))
+
+
+def _label_top_terms(obj, labels, n_labels, filter, topn, method, min_count, background):
+    """label_term_counts of the set, then every label's top-n against the background -> TopTerms [n_labels, topn]"""
+    import torch
+    topn, method, min_count = _term_topn_args(topn, method, min_count)
+    _background_arg(background)
+    lab = labels if _is_torch(labels) else torch.from_numpy(np.ascontiguousarray(labels))
+    fg = obj.label_term_counts(lab, n_labels, filter=filter)
+    return _top_terms_of(obj, TermCounts(fg.counts, fg.total), topn, method, min_count, background)
 
 
 def _assign(obj, centroids, bias, filter, rows_per_chunk):
@@ -3464,6 +3616,53 @@ class DeviceIndex:
         its documents have.  topn in 1..1024."""
         return _top_weights(self, filter, ids, topn, min_count)
 
+    # ---- per-label term aggregations (vs_index_label_term_sums, vs_index_label_term_counts, vs_label_order) -------------------------------------
+    def _label_term_call(self, fn, labels_dev, n_labels, f, bit0, rows_per_item, tile_cols):
+        """One vs_index_label_term_sums / _counts call (fn) on device buffers and torch's current stream -> ([L, V], total [L], other [1]) int64
+        CUDA tensors.  labels_dev: int32 CUDA tensor [n_rows] on this index's device; f: None or a shared DocFilter there, read from bit
+        `bit0` on."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        V = self._n_cols()
+        out = torch.empty((n_labels, V), dtype=torch.int64, device=dev)
+        total = torch.empty(n_labels, dtype=torch.int64, device=dev)
+        other = torch.empty(1, dtype=torch.int64, device=dev)
+        nat.check(getattr(nat.lib(), fn)(self._h, _ptr(f.words) if f is not None else None, int(bit0), _ptr(labels_dev), int(n_labels),
+                                         int(rows_per_item), int(tile_cols), _ptr(out), V, _ptr(total), _ptr(other), current_stream(self.device)))
+        return out, total, other
+
+    def _label_order_call(self, labels_dev, n_labels, f, bit0):
+        """One vs_label_order call on device buffers -> (ptr int64 [L + 1], rows int32 [n_rows] holding uint32 row numbers, other int64 [1])"""
+        import torch
+        dev = torch.device("cuda", self.device)
+        ptr = torch.empty(n_labels + 1, dtype=torch.int64, device=dev)
+        rows = torch.empty(self.n_rows, dtype=torch.int32, device=dev)
+        other = torch.empty(1, dtype=torch.int64, device=dev)
+        nat.check(nat.lib().vs_label_order(self._h, _ptr(f.words) if f is not None else None, int(bit0), _ptr(labels_dev), int(n_labels),
+                                           _ptr(ptr), _ptr(rows), _ptr(other), current_stream(self.device)))
+        return ptr, rows, other
+
+    def label_term_sums(self, labels, n_labels: int, filter=None, rows_per_item: int = 0, tile_cols: int = 0) -> LabelTermSums:
+        """``term_sums`` per label, for every label at once: the centroid of every cluster, category or article of ONE document set ->
+        LabelTermSums(sums [n_labels, V], total [n_labels], other [1]), int64; ``.values()`` float64, ``.mean()`` the centroids float32.
+        labels: integer codes [n_rows] as for ``facet_counts`` (outside [0, n_labels): counted into `other`, contributes nowhere); n_labels
+        <= 65 536 and n_labels x V <= 2^27; filter: one set (a shared DocFilter, a bool mask [N] or ids), None = every live document.  One
+        visit per stored cell whatever n_labels; row l is bit for bit ``term_sums(filter=from_labels(labels, [l]) & filter)``.
+        rows_per_item: 0 = automatic, else a multiple of 64; tile_cols: as in ``term_sums`` (tuning knobs: no output depends on them).
+        numpy labels -> numpy out; tensor labels -> tensors on the index's device, enqueued on torch's current stream."""
+        return _label_terms(self, "vs_index_label_term_sums", LabelTermSums, labels, n_labels, filter, rows_per_item, tile_cols)
+
+    def label_term_counts(self, labels, n_labels: int, filter=None, rows_per_item: int = 0, tile_cols: int = 0) -> LabelTermCounts:
+        """``term_counts`` per label, for every label at once -> LabelTermCounts(counts [n_labels, V], total [n_labels], other [1]), int64:
+        the set's documents of each label that have each column (stored with a non-zero value).  Arguments as ``label_term_sums``."""
+        return _label_terms(self, "vs_index_label_term_counts", LabelTermCounts, labels, n_labels, filter, rows_per_item, tile_cols)
+
+    def label_order(self, labels, n_labels: int, filter=None) -> LabelOrder:
+        """The documents of one set grouped by label (vs_label_order, the first stage of ``label_term_sums``) -> LabelOrder(ptr int64
+        [n_labels + 1], rows int64 [n_set], other [1]): rows[ptr[l]:ptr[l + 1]] are the set's documents of label l, in no specified order.
+        BLOCKING, unlike ``label_term_sums``: the number of listed rows is read back from the device to size `rows`."""
+        return _label_order(self, labels, n_labels, filter)
+
     # ---- clustering: the nearest of K centroids for every row (vs_index_assign) ------------------------------------------------------------------
     def _round_f16(self) -> bool:
         return int(self.info().store_dtype) == nat.VS_F16
@@ -3921,6 +4120,22 @@ class ShardGroup:
     def top_weight_terms(self, filter=None, ids=None, topn: int = 20, min_count: int = 0) -> TopWeights:
         """DeviceIndex.top_weight_terms over the group's rows: the top-n is taken after the shards' sums are added, never per shard."""
         return _top_weights(self, filter, ids, topn, min_count)
+
+    def label_term_sums(self, labels, n_labels: int, filter=None, rows_per_item: int = 0, tile_cols: int = 0) -> LabelTermSums:
+        """DeviceIndex.label_term_sums over the group's rows: labels and filter are global.  Every shard takes its slice of the labels and
+        its bit range of the filter on its own GPU; sums, total and other are added on the first shard's GPU.  The additions are integer:
+        equal to the unsharded index bit for bit."""
+        return _label_terms(self, "vs_index_label_term_sums", LabelTermSums, labels, n_labels, filter, rows_per_item, tile_cols)
+
+    def label_term_counts(self, labels, n_labels: int, filter=None, rows_per_item: int = 0, tile_cols: int = 0) -> LabelTermCounts:
+        """DeviceIndex.label_term_counts over the group's rows, as ``label_term_sums``."""
+        return _label_terms(self, "vs_index_label_term_counts", LabelTermCounts, labels, n_labels, filter, rows_per_item, tile_cols)
+
+    def label_order(self, labels, n_labels: int, filter=None) -> LabelOrder:
+        """DeviceIndex.label_order over the group's rows: a label's segment holds the shards' segments one behind the other, global ids.
+        Every shard's count of listed rows is read back before the next shard is called: the shards run one after the other (a facade for
+        pinning the order, not a hot path -- ``label_term_sums`` keeps the order on the device and only enqueues)."""
+        return _label_order(self, labels, n_labels, filter)
 
     def assign(self, centroids, bias=None, filter=None, rows_per_chunk: int = 0) -> Assignment:
         """DeviceIndex.assign over the group's rows: the centroids and the bias are copied to every shard's GPU, every shard assigns its rows

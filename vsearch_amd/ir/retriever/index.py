@@ -31,6 +31,7 @@ from ...device_index import FacetValuePercentiles, MAX_VALUE_RANKS
 from ...device_index import SetIds, SetSample, _set_sample_args, _set_window_args
 from ...device_index import BOOST_MODES, MAX_BOOST_FIELDS
 from ...device_index import _col_mask
+from ...device_index import LabelTermCounts, LabelTermSums, _label_top_terms, _label_top_weights
 
 logger = logging.getLogger(__name__)
 
@@ -1142,6 +1143,78 @@ class Index:
         cols = torch.where(top.cols >= 0, top.cols + shift, top.cols) if shift else top.cols
         return TopWeights(*(self._to_api(t) for t in (cols, top.scores, top.sums, top.total)))
 
+    # ---- term aggregations by facet label (not in the reference: the centroid and the terms of every cluster, category or article at once) -----
+    def _facet_term_set(self, field, q_embs, min_score, filter):
+        """the set and the labels of a by-facet term aggregation -> (search target, codes, n_labels, names, one shared DocFilter | None);
+        argument errors before any device work"""
+        if (q_embs is None) != (min_score is None):
+            raise ValueError("q_embs and min_score go together: the set is match_filter(q_embs, min_score, filter), or the filter alone")
+        if self.index_type == IndexType.DENSE:
+            raise NotImplementedError("the term aggregations read the sparse rows: a dense Index is not covered")
+        if q_embs is not None and (getattr(q_embs, "ndim", 2) != 2 or int(q_embs.shape[0]) != 1):
+            raise ValueError("a by-facet term aggregation takes ONE document set: one query [1, V], not a batch")
+        from ...doc_filter import DocFilter
+        many = filter.n_queries if isinstance(filter, DocFilter) else (int(filter.shape[0]) if getattr(filter, "ndim", 1) == 2 else None)
+        if many is not None and many != 1:
+            raise ValueError("a by-facet term aggregation takes ONE document set, not a per-query filter")
+        if field != "groups" and field not in self._facet_store():
+            raise KeyError(f"no facet field {field!r}: set_facet() or facet_from_samples() first (fields: {list(self._facet_store())})")
+        codes, n_labels, names = self._facet_field(field)
+        target, gpu_ord = self._explain_target()
+        if q_embs is not None:
+            filter = self.match_filter(q_embs, min_score, filter=filter)
+        if filter is not None:
+            from ...doc_filter import as_doc_filter
+            filter = as_doc_filter(filter, self._n_rows(), device=torch.device("cuda", gpu_ord))
+            if filter.per_query:
+                if filter.n_queries != 1:
+                    raise ValueError("a by-facet term aggregation takes ONE document set, not a per-query filter")
+                filter = DocFilter(filter.words[0], filter.n_rows)
+        return target, codes, n_labels, names, filter
+
+    def term_sums_by_facet(self, field: str, q_embs=None, min_score=None, filter=None) -> LabelTermSums:
+        """``term_sums`` per label of facet field `field` (``set_facet`` / ``facet_from_samples``; "groups" = the group ids), for every label
+        at once -> LabelTermSums(sums [n_labels, V], total [n_labels], other [1]), int64: row l is bit for bit ``term_sums`` of the set's
+        documents with label l; other counts the set's documents without a label.  ONE set: one query [1, V] with min_score (the documents
+        ``match_filter`` matches), `filter` alone, or neither: every live document -- a batch of queries or a per-query filter raises
+        ValueError.  One pass over the stored cells whatever the number of labels (at most 65 536, and n_labels x V <= 2^27).  Works on a
+        row-sharded index as well (not on the one-process-per-GPU path of ``vsearch_amd.distributed``, and not on a dense index)."""
+        target, codes, n_labels, _, f = self._facet_term_set(field, q_embs, min_score, filter)
+        return LabelTermSums(*(self._to_api(t) for t in target.label_term_sums(codes, n_labels, filter=f)))
+
+    def term_counts_by_facet(self, field: str, q_embs=None, min_score=None, filter=None) -> LabelTermCounts:
+        """``term_counts`` per label of facet field `field` -> LabelTermCounts(counts [n_labels, V], total [n_labels], other [1]); the set
+        as in ``term_sums_by_facet``."""
+        target, codes, n_labels, _, f = self._facet_term_set(field, q_embs, min_score, filter)
+        return LabelTermCounts(*(self._to_api(t) for t in target.label_term_counts(codes, n_labels, filter=f)))
+
+    def centroids_by_facet(self, field: str, q_embs=None, min_score=None, filter=None) -> torch.Tensor:
+        """The mean vector of every label's documents -> float32 [n_labels, V] in the vector's space, ready for ``index.search``: the
+        centroid of every cluster, category or article at once.  A label without documents in the set gets an all-zero row."""
+        return self.term_sums_by_facet(field, q_embs, min_score, filter=filter).mean()
+
+    def centroid_terms_by_facet(self, field: str, topn: int = 20, min_count: int = 0, q_embs=None, min_score=None, filter=None) -> TopWeights:
+        """Per label the columns its documents put the most weight on -> TopWeights(cols [n_labels, topn], scores, sums, total [n_labels]),
+        as ``centroid_terms`` lists them for one set; min_count > 0 takes the per-label counts as well."""
+        _weight_topn_args(topn, min_count)
+        target, codes, n_labels, _, f = self._facet_term_set(field, q_embs, min_score, filter)
+        top = _label_top_weights(target, codes, n_labels, f, int(topn), int(min_count))
+        shift = int(getattr(self, "shift", 0) or 0)
+        cols = torch.where(top.cols >= 0, top.cols + shift, top.cols) if shift else top.cols
+        return TopWeights(*(self._to_api(t) for t in (cols, top.scores, top.sums, top.total)))
+
+    def significant_terms_by_facet(self, field: str, topn: int = 20, method: str = "jlh", min_count: int = 1, background=None, q_embs=None,
+                                   min_score=None, filter=None) -> TopTerms:
+        """Per label the columns over-represented in its documents against a background -> TopTerms(cols [n_labels, topn], scores, df, bg,
+        total [n_labels]), as ``significant_terms`` lists them for one set (method "jlh" | "lift" | "count"); background=None counts every
+        live document in the same call."""
+        _term_topn_args(topn, method, min_count)
+        target, codes, n_labels, _, f = self._facet_term_set(field, q_embs, min_score, filter)
+        top = _label_top_terms(target, codes, n_labels, f, int(topn), method, int(min_count), background)
+        shift = int(getattr(self, "shift", 0) or 0)
+        cols = torch.where(top.cols >= 0, top.cols + shift, top.cols) if shift else top.cols
+        return TopTerms(*(self._to_api(t) for t in (cols, top.scores, top.df, top.bg, top.total)))
+
     # ---- clustering (not in the reference: the nearest of K centroids for every document, and Lloyd's k-means around it) --------------------------
     def _cluster_target(self, filter):
         """-> (search target, its GPU, one shared DocFilter there | None); a dense index raises NotImplementedError before any device work"""
@@ -1182,7 +1255,7 @@ class Index:
         float32 [N], counts int64 [K], n_iter, changed).  init: int64 row ids [K] (those documents are the start centroids), float32
         centroids [K, V], or None: K distinct live, allowed documents drawn with ``torch.randperm`` under a CPU generator seeded with
         `seed`.  Each iteration assigns (``assign``) and, unless nothing changed, moves every centroid to the mean of its documents
-        (``term_sums`` of the K label sets, 64 clusters a pass); an empty cluster keeps its centroid.  The labels and values returned are
+        (``label_term_sums``: the sums of all K clusters in one pass); an empty cluster keeps its centroid.  The labels and values returned are
         the assignment under the centroids returned.  Deterministic, bit for bit: two runs are identical.  metric "l2" (Euclidean) or "dot"
         (the largest dot product: spherical k-means without the normalisation).  The centroids are queries for ``search``; the labels feed
         ``set_facet``, ``set_groups`` (see ``cluster``) and ``DocFilter.from_labels``."""
@@ -1232,15 +1305,10 @@ class Index:
         """Per cluster the columns its documents put the most weight on -> TopWeights(cols [K, topn], scores, sums, total [K]); cols in the
         index file's column space (+ ``shift``), scores the mean weight, total the cluster's size.  labels: ``kmeans(...).labels``."""
         _weight_topn_args(topn, 0)
-        from ...doc_filter import DocFilter
         target, gpu, _ = self._cluster_target(None)
         lab = (labels if isinstance(labels, torch.Tensor) else torch.from_numpy(np.asarray(labels))).to(gpu)
         K = _kmeans_args(n_clusters, 0, "l2")[0]
-        parts = []
-        for b0 in range(0, K, KMEANS_UPDATE_BATCH):
-            ts = target.term_sums(filter=DocFilter.from_labels(lab, np.arange(b0, min(K, b0 + KMEANS_UPDATE_BATCH), dtype=np.int32), device=gpu))
-            parts.append(term_sum_topn(ts.sums, ts.total, int(topn), device=gpu.index) + (ts.total,))
-        cols, scores, sums, total = (torch.cat([p[i] for p in parts]) for i in range(4))
+        cols, scores, sums, total = _label_top_weights(target, lab, K, None, int(topn), 0)     # all K clusters in one pass
         shift = int(getattr(self, "shift", 0) or 0)
         cols = torch.where(cols >= 0, cols + shift, cols) if shift else cols
         return TopWeights(*(self._to_api(t) for t in (cols, scores, sums, total)))

@@ -387,6 +387,44 @@ class Retriever(BiEncoder):
             out.append([(name, float(s), int(d)) for name, s, d in zip(names, scores[b][live], sums[b][live])])
         return out
 
+    def facet_terms(self, field: str, queries: Union[List[str], np.ndarray, T] = None, min_score=None, topn: int = 10, method: str = "weight",
+                    min_count: int = None, background=None, dropout: float = 0, a: int = None, index: Index = None, batch_size: int = 32,
+                    filter=None):
+        """What every label of facet field `field` is about, for all labels at once -- ``Index.centroid_terms_by_facet`` (method "weight":
+        the tokens the label's documents put the most weight on) or ``Index.significant_terms_by_facet`` ("jlh" | "lift" | "count": the
+        tokens over-represented in them) behind the query encoder -> {label name: (docs, [(token, score), ...])}, docs the documents of
+        the set with that label; name is the label's code where the field has no names.  The set: ONE query with `min_score` (its matches),
+        `filter` alone, or neither: every live document.  min_count: None = the method's default (0 for "weight", 1 otherwise)."""
+        if method not in ("weight", "jlh", "lift", "count"):
+            raise ValueError(f'method must be "weight", "jlh", "lift" or "count", got {method!r}')
+        if (queries is None) != (min_score is None):
+            raise ValueError("queries and min_score go together: the set is one query's matches, the filter alone, or every live document")
+        if queries is not None and not isinstance(queries, str) and len(queries) != 1:
+            raise ValueError("facet_terms takes ONE document set: one query, not a batch")
+        index = index or self.index
+        if index is None:
+            raise RuntimeError("no index: call build_index / load_index first")
+        q_emb = None
+        if queries is not None:
+            q_emb = self.process_query([queries] if isinstance(queries, str) else queries, dropout, a or self.encoder_q.config.topk,
+                                       batch_size=batch_size)
+        if method == "weight":
+            top = index.centroid_terms_by_facet(field, topn=topn, min_count=0 if min_count is None else min_count, q_embs=q_emb,
+                                                min_score=min_score, filter=filter)
+        else:
+            top = index.significant_terms_by_facet(field, topn=topn, method=method, min_count=1 if min_count is None else min_count,
+                                                   background=background, q_embs=q_emb, min_score=min_score, filter=filter)
+        names = index.facet_names(field)
+        shift = int(self.encoder_p.config.shift_vocab_num)
+        tok = self.encoder_p.tokenizer
+        cols, scores, total = (t.cpu().numpy() for t in (top.cols, top.scores, top.total))
+        out = {}
+        for l in range(cols.shape[0]):
+            live = cols[l] >= 0
+            toks = tok.convert_ids_to_tokens([int(x) + shift for x in cols[l][live]])
+            out[names[l] if names is not None else l] = (int(total[l]), [(t, float(s)) for t, s in zip(toks, scores[l][live])])
+        return out
+
     def cluster_documents(self, n_clusters: int, topn: int = 10, index: Index = None, **args):
         """Partition the indexed documents into `n_clusters` clusters (``Index.cluster``: Lloyd's k-means on the GPU, the labels stored as
         facet field "cluster") and name every cluster by its tokens -> per cluster (size, [(token, mean weight), ...]), the vocabulary
