@@ -1,7 +1,9 @@
 // agg_call.h -- the host side every aggregation call shares (facets, term counts, term sums, numeric fields, percentiles): the small helpers of
-// an entry point, staging a set's bitmaps, the [B, n] int64 matrix + [B] vectors output pattern, the launch ladder over an index's store dtype,
+// an entry point, the opening and the tail of a call, where a call's set lives (SetSrc: the free form's arguments, or an index) and the staging
+// of its bitmaps, the [B, n] int64 matrix + [B] vectors output pattern, the launch ladders over a plan's query tile and an index's store dtype,
 // and the kernel arguments of the term aggregations.  The buffers of a call follow staging.h: all host (staged, copied back, the call blocks)
-// or all device (only enqueued).
+// or all device (only enqueued).  An aggregation over a bitmap set is a kernel body, a check, one body function over a SetSrc and two
+// extern "C" wrappers.
 #pragma once
 #include "common.h"
 #include "packets.h"
@@ -35,6 +37,72 @@ inline int launch_rc(int rc, hipStream_t s) {
     return rc;
 }
 
+// the launches of a call, looked at once they are all enqueued: "<name> launch failed: <hip string>"
+inline int launch_failed(const char* name, hipStream_t s) {
+    const hipError_t le = hipGetLastError();
+    if (le == hipSuccess) return VS_OK;
+    (void)hipStreamSynchronize(s);                                  // staging buffers and scratch die with the caller
+    return fail(VS_EHIP, "%s launch failed: %s", name, hipGetErrorString(le));
+}
+
+// how a call ends: kStream as finish_call does (device buffers on a stream: only enqueued); kSync always synchronises, for a call that owns
+// scratch the kernels use (it is freed when the call returns)
+enum class Finish { kStream, kSync };
+
+// The tail of a call, once everything is enqueued: the look at the launches, the stage mark, back() -> code (the copies to host buffers) and
+// the finish.
+template <class Back>
+int close_call(const char* name, bool dev, void* stream, hipStream_t s, Finish fin, Back back) {
+    VS_TRY(launch_failed(name, s));
+    VS_STAGE(name, s);
+    if (!dev) VS_TRY(launch_rc(back(), s));
+    if (fin == Finish::kStream) return finish_call(dev, stream, s);
+    VS_HIP(hipStreamSynchronize(s));
+    if (Profiler::get().on) Profiler::get().drain();
+    return VS_OK;
+}
+
+// The opening of a call: its buffers are all host or all device pointers on `device` (-> dev), the device is set, the stream cast.
+struct NamedPtr {
+    const char* name;
+    const void* p;
+};
+struct Call {
+    bool dev = false;
+    void* stream = nullptr;
+    hipStream_t s = nullptr;
+    int open(int device, void* stream_, std::initializer_list<NamedPtr> bufs) {
+        const void* ptrs[16];
+        const char* names[16];
+        int n = 0;
+        for (const NamedPtr& b : bufs) {
+            if (n == 16) return fail(VS_EINVAL, "too many buffers in one call");
+            names[n] = b.name;
+            ptrs[n++] = b.p;
+        }
+        VS_TRY(pointers_kind(ptrs, names, n, device, &dev));
+        VS_HIP(hipSetDevice(device));
+        stream = stream_;
+        s = (hipStream_t)stream_;
+        return VS_OK;
+    }
+    // enqueue() -> code stages, zeroes and launches; whatever it returns early with, the stream is drained before the call's buffers die
+    template <class Enqueue, class Back>
+    int run(const char* name, Finish fin, Enqueue enqueue, Back back) {
+        VS_TRY(launch_rc(enqueue(), s));
+        return close_call(name, dev, stream, s, fin, back);
+    }
+};
+
+// f(QT) as a std::integral_constant for the query tile of a plan: 8 | 4 | 2 | 1
+template <class F>
+int launch_by_qt(int qt, F f) {
+    if (qt == 8) return f(std::integral_constant<int, 8>{});
+    if (qt == 4) return f(std::integral_constant<int, 4>{});
+    if (qt == 2) return f(std::integral_constant<int, 2>{});
+    return f(std::integral_constant<int, 1>{});
+}
+
 // tombstones are ANDed in, as every search does (the live bitmap starts at bit 0 whatever bit0 is)
 inline const uint32_t* live_words(vs_index* idx) { return idx->has_tomb ? idx->live.as<uint32_t>() : nullptr; }
 
@@ -45,23 +113,56 @@ inline int csr_index_ok(const vs_index* idx, const char* what) {
     return VS_OK;
 }
 
-// The staged bitmaps of a set.  and_user: a caller's second bitmap (of the kind of the other pointers, at bit0); and_dev: a device bitmap at
-// bit 0 (an index's live rows).  At most one of the two.
+// Where the set of a call lives: the packed bitmaps, the rows behind them and the device.  The second bitmap ANDed in is a caller's and_user
+// (of the kind of the other pointers, at bit0) or a device and_dev at bit 0 (an index's live rows): at most one of the two.
+struct SetSrc {
+    const uint32_t* words = nullptr;
+    int64_t bit0 = 0, ld_words = 0;
+    int32_t B = 0;
+    int64_t n_rows = 0;
+    int device = 0;
+    const uint32_t *and_user = nullptr, *and_dev = nullptr;
+    bool free_form = false;           // the device is the caller's word and still unchecked
+    bool per_query() const { return words && ld_words != 0; }
+    // after the device-free argument checks, before any pointer is looked at
+    int device_ok() const { return free_form ? device_in_range(device) : VS_OK; }
+};
+// the free form: vs_X(words, ..., and_words, ..., n_rows, ..., device)
+inline SetSrc free_set(const uint32_t* words, int64_t bit0, int64_t ld_words, const uint32_t* and_words, int32_t B, int64_t n_rows, int device) {
+    SetSrc r;
+    r.words = words, r.bit0 = bit0, r.ld_words = ld_words, r.B = B, r.n_rows = n_rows, r.device = device;
+    r.and_user = and_words;
+    r.free_form = true;
+    return r;
+}
+// the index-bound form: vs_index_X(idx, words, ...) -- the index's rows on its device, its live rows ANDed in
+inline SetSrc index_set(vs_index& idx, const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B) {
+    SetSrc r;
+    r.words = words, r.bit0 = bit0, r.ld_words = ld_words, r.B = B, r.n_rows = idx.n_rows, r.device = idx.device;
+    r.and_dev = live_words(&idx);
+    return r;
+}
+inline int index_set(vs_index* idx, const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B, SetSrc* out) {
+    if (!idx) return fail(VS_EINVAL, "NULL argument");
+    *out = index_set(*idx, words, bit0, ld_words, B);
+    return VS_OK;
+}
+
+// The staged bitmaps of a set.
 struct BitmapStage {
     Staged w, a;
-    int in(const uint32_t* words, int64_t bit0, int64_t ld_words, const uint32_t* and_user, const uint32_t* and_dev, int32_t B, int64_t n_rows,
-           int64_t rows_per_chunk, bool dev, hipStream_t s, RowSet* out) {
-        const int64_t span = (bit0 + n_rows + 31) >> 5;
+    int in(const SetSrc& src, int64_t rows_per_chunk, bool dev, hipStream_t s, RowSet* out) {
+        const int64_t span = (src.bit0 + src.n_rows + 31) >> 5;
         uint32_t *d_w, *d_a;
-        VS_TRY(w.in(words, (size_t)((B - 1) * ld_words + span), dev, true, s, &d_w));
-        VS_TRY(a.in(and_user, (size_t)span, dev, true, s, &d_a));
+        VS_TRY(w.in(src.words, (size_t)((src.B - 1) * src.ld_words + span), dev, true, s, &d_w));
+        VS_TRY(a.in(src.and_user, (size_t)span, dev, true, s, &d_a));
         out->words = d_w;
-        out->bit0 = bit0;
-        out->ld_words = words ? ld_words : 0;
-        out->and_words = and_user ? d_a : and_dev;
-        out->and_bit0 = and_user ? bit0 : 0;
-        out->n_rows = n_rows;
-        out->B = B;
+        out->bit0 = src.bit0;
+        out->ld_words = src.words ? src.ld_words : 0;
+        out->and_words = src.and_user ? d_a : src.and_dev;
+        out->and_bit0 = src.and_user ? src.bit0 : 0;
+        out->n_rows = src.n_rows;
+        out->B = src.B;
         out->rows_per_chunk = rows_per_chunk;
         return VS_OK;
     }
@@ -76,11 +177,10 @@ struct SetArgs {
 struct SetStage {
     BitmapStage b;
     Staged v;
-    int in(const uint32_t* words, int64_t bit0, int64_t ld_words, const uint32_t* and_user, const uint32_t* and_dev, int32_t B, const void* values,
-           int dtype, int64_t n_rows, int64_t rows_per_chunk, bool dev, hipStream_t s, SetArgs* out) {
-        VS_TRY(b.in(words, bit0, ld_words, and_user, and_dev, B, n_rows, rows_per_chunk, dev, s, &out->set));
+    int in(const SetSrc& src, const void* values, int dtype, int64_t rows_per_chunk, bool dev, hipStream_t s, SetArgs* out) {
+        VS_TRY(b.in(src, rows_per_chunk, dev, s, &out->set));
         uint32_t* d_v;
-        VS_TRY(v.in(static_cast<const uint32_t*>(values), (size_t)n_rows, dev, true, s, &d_v));
+        VS_TRY(v.in(static_cast<const uint32_t*>(values), (size_t)src.n_rows, dev, true, s, &d_v));
         out->values = d_v;
         out->dtype = dtype;
         return VS_OK;
@@ -194,9 +294,7 @@ int term_agg_call(vs_index* idx, const uint32_t* words, int64_t bit0, int64_t ld
         ProfScope prof(prof_name, s);
         VS_TRY(launch_rc(dispatch_store(idx->store_dtype, ids != nullptr, [&](auto sd, auto is_ids) { return launch(sd, is_ids, a, o); }), s));
     }
-    VS_STAGE(prof_name, s);
-    if (!dev) VS_TRY(o.back(s));
-    return finish_call(dev, stream, s);
+    return close_call(prof_name, dev, stream, s, Finish::kStream, [&] { return o.back(s); });
 }
 
 }  // namespace vs

@@ -314,9 +314,7 @@ extern "C" int vs_centroid_half_norms(const float* c, int64_t ldc, int32_t K, in
         hipLaunchKernelGGL(half_norms_kernel, dim3((unsigned)K), dim3(kNormThreads), 0, s, d_c, ldc, n_cols, round_f16 != 0, d_o);
         VS_HIP(hipGetLastError());
     }
-    VS_STAGE("half_norms", s);
-    if (!dev) VS_TRY(st_o.back(s));
-    return finish_call(dev, stream, s);
+    return close_call("half_norms", dev, stream, s, Finish::kStream, [&] { return st_o.back(s); });
 }
 
 extern "C" int vs_index_assign(vs_index* idx, const float* centroids, int64_t ldc, int32_t K, const float* bias, const uint32_t* filter,
@@ -381,14 +379,10 @@ extern "C" int vs_index_assign(vs_index* idx, const float* centroids, int64_t ld
         (void)hipStreamSynchronize(s);                                // the slab and the staging buffers die here
         return rc;
     }
-    VS_STAGE("assign", s);
-    if (!dev) {
+    return close_call("assign", dev, stream, s, Finish::kSync, [&] {      // (the slab is freed when the call returns)
         VS_TRY(st_l.back(s));
-        VS_TRY(st_v.back(s));
-    }
-    VS_HIP(hipStreamSynchronize(s));                                  // the slab is freed before the call returns
-    if (Profiler::get().on) Profiler::get().drain();
-    return VS_OK;
+        return st_v.back(s);
+    });
 }
 
 extern "C" int vs_label_bitmaps(const int32_t* labels, int64_t n_rows, const int32_t* values, int32_t B, int64_t bit0, uint32_t* out_words,
@@ -422,7 +416,5 @@ extern "C" int vs_label_bitmaps(const int32_t* labels, int64_t n_rows, const int
         hipLaunchKernelGGL(label_bitmaps_kernel, dim3((unsigned)((waves + kBitmapThreads / 64 - 1) / (kBitmapThreads / 64))), dim3(kBitmapThreads), 0, s, a);
         VS_HIP(hipGetLastError());
     }
-    VS_STAGE("label_bitmaps", s);
-    if (!dev) VS_TRY(st_o.back(s));
-    return finish_call(dev, stream, s);
+    return close_call("label_bitmaps", dev, stream, s, Finish::kStream, [&] { return st_o.back(s); });
 }

@@ -200,12 +200,7 @@ int fq_launch_qt(const FqArgs& a, const FacetQuantilePlan& p, dim3 grid, size_t 
 
 template <bool TOP>
 int fq_launch_top(const FqArgs& a, const FacetQuantilePlan& p, dim3 grid, size_t lds, hipStream_t s) {
-    switch (p.qt) {
-        case 8: return fq_launch_qt<8, TOP>(a, p, grid, lds, s);
-        case 4: return fq_launch_qt<4, TOP>(a, p, grid, lds, s);
-        case 2: return fq_launch_qt<2, TOP>(a, p, grid, lds, s);
-        default: return fq_launch_qt<1, TOP>(a, p, grid, lds, s);
-    }
+    return launch_by_qt(p.qt, [&](auto t) { return fq_launch_qt<decltype(t)::value, TOP>(a, p, grid, lds, s); });
 }
 
 // zero a level's counts (and missing, total, other at level 0) and count; everything on the device
@@ -225,19 +220,12 @@ int fq_counts_launch(FqArgs a, const FacetQuantilePlan& plan, hipStream_t s) {
     return a.level == 0 ? fq_launch_top<true>(a, plan, grid, lds, s) : fq_launch_top<false>(a, plan, grid, lds, s);
 }
 
-int launch_failed(const char* what, hipStream_t s) {
-    const hipError_t le = hipGetLastError();
-    if (le == hipSuccess) return VS_OK;
-    (void)hipStreamSynchronize(s);                                  // staging buffers die with the caller
-    return fail(VS_EHIP, "%s launch failed: %s", what, hipGetErrorString(le));
-}
-
 // the set, the labels, R and the scratch of a call -> the plan of `level`
-int check_fq_set(const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B, const int32_t* labels, int32_t n_labels, const void* values,
-                 int dtype, int64_t n_rows, int32_t R, int level, int64_t rows_per_chunk, bool have_outputs, FacetQuantilePlan* plan) {
+int check_fq_set(const SetSrc& src, const int32_t* labels, int32_t n_labels, const void* values, int dtype, int32_t R, int level,
+                 int64_t rows_per_chunk, bool have_outputs, FacetQuantilePlan* plan) {
     char msg[256];
-    return plan_or_fail(facet_quantile_check_set(labels && values && have_outputs, words != nullptr, bit0, ld_words, B, dtype, n_rows, n_labels, R,
-                                                 level, rows_per_chunk, plan, msg, sizeof msg), msg);
+    return plan_or_fail(facet_quantile_check_set(labels && values && have_outputs, src.words != nullptr, src.bit0, src.ld_words, src.B, dtype, src.n_rows,
+                                                 n_labels, R, level, rows_per_chunk, plan, msg, sizeof msg), msg);
 }
 
 // q with its method, or ranks [B, n_labels, R]: host arrays are looked at before the device is
@@ -253,144 +241,125 @@ int check_ranks_arg(const double* q, int method, const int64_t* ranks, int64_t c
     return VS_OK;
 }
 
-int counts_call(int device, const uint32_t* words, int64_t bit0, int64_t ld_words, const uint32_t* and_user, const uint32_t* and_dev, int32_t B,
-                const int32_t* labels, int32_t n_labels, const void* values, int dtype, int64_t n_rows, int level, int32_t R,
-                const uint32_t* slot_prefix, const int32_t* n_slots, const FacetQuantilePlan& plan, int64_t* counts, int64_t* missing, int64_t* total,
-                int64_t* other, void* stream) {
+// vs_facet_value_radix_counts and vs_index_facet_value_radix_counts: one level's counts on the set's device
+int facet_radix_counts(const SetSrc& src, const int32_t* labels, int32_t n_labels, const void* values, int dtype, int level, int32_t R,
+                       const uint32_t* slot_prefix, const int32_t* n_slots, int64_t rows_per_chunk, int64_t* counts, int64_t* missing, int64_t* total,
+                       int64_t* other, void* stream) {
+    FacetQuantilePlan plan;
+    char msg[256];
+    VS_TRY(check_fq_set(src, labels, n_labels, values, dtype, R, level, rows_per_chunk, counts != nullptr, &plan));
+    VS_TRY(plan_or_fail(facet_quantile_check_level_args(level, slot_prefix && n_slots, missing && total && other, msg, sizeof msg), msg));
+    VS_TRY(src.device_ok());
     if (level != 0) missing = total = other = nullptr;
     else slot_prefix = nullptr, n_slots = nullptr;
-    const void* ptrs[10] = {words, and_user, labels, values, slot_prefix, n_slots, counts, missing, total, other};
-    const char* names[10] = {"words", "and_words", "labels", "values", "slot_prefix", "n_slots", "counts", "missing", "total", "other"};
-    bool dev = false;
-    VS_TRY(pointers_kind(ptrs, names, 10, device, &dev));
-    VS_HIP(hipSetDevice(device));
-    hipStream_t s = (hipStream_t)stream;
+    Call c;
+    VS_TRY(c.open(src.device, stream, {{"words", src.words}, {"and_words", src.and_user}, {"labels", labels}, {"values", values},
+                                       {"slot_prefix", slot_prefix}, {"n_slots", n_slots}, {"counts", counts}, {"missing", missing}, {"total", total},
+                                       {"other", other}}));
+    const int32_t B = src.B;
     SetStage st;
     Staged st_l, st_p, st_n, st_c, st_m, st_t, st_o;
-    FqArgs a{};
-    const size_t cells = (size_t)B * (size_t)n_labels;
-    VS_TRY(st.in(words, bit0, ld_words, and_user, and_dev, B, values, dtype, n_rows, plan.rows_per_chunk, dev, s, &a.s));
-    int32_t *d_l, *d_n;
-    uint32_t* d_p;
-    int64_t *d_c, *d_m, *d_t, *d_o;
-    VS_TRY(st_l.in(labels, (size_t)n_rows, dev, true, s, &d_l));
-    VS_TRY(st_p.in(slot_prefix, cells * R, dev, true, s, &d_p));
-    VS_TRY(st_n.in(n_slots, cells, dev, true, s, &d_n));
-    VS_TRY(st_c.in(counts, level_counts(B, n_labels, R, level), dev, false, s, &d_c));
-    VS_TRY(st_m.in(missing, cells, dev, false, s, &d_m));
-    VS_TRY(st_t.in(total, (size_t)B, dev, false, s, &d_t));
-    VS_TRY(st_o.in(other, (size_t)B, dev, false, s, &d_o));
-    a.labels = d_l;
-    a.n_labels = n_labels;
-    a.level = level;
-    a.R = R;
-    a.slot_prefix = d_p;
-    a.n_slots = d_n;
-    a.counts = reinterpret_cast<unsigned long long*>(d_c);
-    a.missing = reinterpret_cast<unsigned long long*>(d_m);
-    a.total = reinterpret_cast<unsigned long long*>(d_t);
-    a.other = reinterpret_cast<unsigned long long*>(d_o);
-    VS_TRY(launch_rc(fq_counts_launch(a, plan, s), s));
-    VS_TRY(launch_failed("facet_value_radix_counts", s));
-    VS_STAGE("facet_value_radix_counts", s);
-    if (!dev) {
-        VS_TRY(st_c.back(s));
-        VS_TRY(st_m.back(s));
-        VS_TRY(st_t.back(s));
-        VS_TRY(st_o.back(s));
-    }
-    return finish_call(dev, stream, s);
+    return c.run("facet_value_radix_counts", Finish::kStream, [&] {
+        FqArgs a{};
+        const size_t cells = (size_t)B * (size_t)n_labels;
+        VS_TRY(st.in(src, values, dtype, plan.rows_per_chunk, c.dev, c.s, &a.s));
+        int32_t *d_l, *d_n;
+        uint32_t* d_p;
+        int64_t *d_c, *d_m, *d_t, *d_o;
+        VS_TRY(st_l.in(labels, (size_t)src.n_rows, c.dev, true, c.s, &d_l));
+        VS_TRY(st_p.in(slot_prefix, cells * R, c.dev, true, c.s, &d_p));
+        VS_TRY(st_n.in(n_slots, cells, c.dev, true, c.s, &d_n));
+        VS_TRY(st_c.in(counts, level_counts(B, n_labels, R, level), c.dev, false, c.s, &d_c));
+        VS_TRY(st_m.in(missing, cells, c.dev, false, c.s, &d_m));
+        VS_TRY(st_t.in(total, (size_t)B, c.dev, false, c.s, &d_t));
+        VS_TRY(st_o.in(other, (size_t)B, c.dev, false, c.s, &d_o));
+        a.labels = d_l;
+        a.n_labels = n_labels;
+        a.level = level;
+        a.R = R;
+        a.slot_prefix = d_p;
+        a.n_slots = d_n;
+        a.counts = reinterpret_cast<unsigned long long*>(d_c);
+        a.missing = reinterpret_cast<unsigned long long*>(d_m);
+        a.total = reinterpret_cast<unsigned long long*>(d_t);
+        a.other = reinterpret_cast<unsigned long long*>(d_o);
+        return fq_counts_launch(a, plan, c.s);
+    }, [&] {
+        VS_TRY(st_c.back(c.s));
+        VS_TRY(st_m.back(c.s));
+        VS_TRY(st_t.back(c.s));
+        return st_o.back(c.s);
+    });
 }
 
-int quantiles_call(int device, const uint32_t* words, int64_t bit0, int64_t ld_words, const uint32_t* and_user, const uint32_t* and_dev, int32_t B,
-                   const int32_t* labels, int32_t n_labels, const void* values, int dtype, int64_t n_rows, const double* q, int method,
-                   const int64_t* ranks, int32_t R, const FacetQuantilePlan* plans, void* out_values, int64_t* out_ranks, int64_t* count,
-                   int64_t* missing, int64_t* total, int64_t* other, void* stream) {
+// vs_facet_value_quantiles and vs_index_facet_value_quantiles: every level's counts and steps on the set's device
+int facet_value_quantiles(const SetSrc& src, const int32_t* labels, int32_t n_labels, const void* values, int dtype, const double* q, int method,
+                          const int64_t* ranks, int32_t R, int64_t rows_per_chunk, void* out_values, int64_t* out_ranks, int64_t* count,
+                          int64_t* missing, int64_t* total, int64_t* other, void* stream) {
+    FacetQuantilePlan plans[VS_VALUE_RADIX_LEVELS];
+    for (int level = 0; level < VS_VALUE_RADIX_LEVELS; ++level)
+        VS_TRY(check_fq_set(src, labels, n_labels, values, dtype, R, level, rows_per_chunk, out_values && out_ranks && count && missing && total && other,
+                            plans + level));
+    VS_TRY(check_ranks_arg(q, method, ranks, (int64_t)src.B * n_labels, R));
+    VS_TRY(src.device_ok());
     if (q) ranks = nullptr;
-    const void* ptrs[12] = {words, and_user, labels, values, q, ranks, out_values, out_ranks, count, missing, total, other};
-    const char* names[12] = {"words", "and_words", "labels", "values", "q", "ranks", "out_values", "out_ranks", "count", "missing", "total", "other"};
-    bool dev = false;
-    VS_TRY(pointers_kind(ptrs, names, 12, device, &dev));
-    VS_HIP(hipSetDevice(device));
-    hipStream_t s = (hipStream_t)stream;
+    Call c;
+    VS_TRY(c.open(src.device, stream, {{"words", src.words}, {"and_words", src.and_user}, {"labels", labels}, {"values", values}, {"q", q},
+                                       {"ranks", ranks}, {"out_values", out_values}, {"out_ranks", out_ranks}, {"count", count}, {"missing", missing},
+                                       {"total", total}, {"other", other}}));
     SetStage st;
     Staged st_l, st_q, st_r, st_v, st_o, st_c, st_m, st_t, st_x;
-    FqArgs ca{};
-    const size_t cells = (size_t)B * (size_t)n_labels, n_br = cells * (size_t)R, n_cnt = n_br * VS_VALUE_RADIX_BINS;
-    VS_TRY(st.in(words, bit0, ld_words, and_user, and_dev, B, values, dtype, n_rows, plans[0].rows_per_chunk, dev, s, &ca.s));
-    int32_t* d_l;
-    double* d_q;
-    uint32_t* d_v;
-    int64_t *d_r, *d_or, *d_c, *d_m, *d_t, *d_x;
-    VS_TRY(st_l.in(labels, (size_t)n_rows, dev, true, s, &d_l));
-    VS_TRY(st_q.in(q, (size_t)R, dev, true, s, &d_q));
-    VS_TRY(st_r.in(ranks, n_br, dev, true, s, &d_r));
-    VS_TRY(st_v.in(static_cast<uint32_t*>(out_values), n_br, dev, false, s, &d_v));
-    VS_TRY(st_o.in(out_ranks, n_br, dev, false, s, &d_or));
-    VS_TRY(st_c.in(count, cells, dev, false, s, &d_c));
-    VS_TRY(st_m.in(missing, cells, dev, false, s, &d_m));
-    VS_TRY(st_t.in(total, (size_t)B, dev, false, s, &d_t));
-    VS_TRY(st_x.in(other, (size_t)B, dev, false, s, &d_x));
-    // scratch: the counts of a level, then the step's state
-    DevBuf scratch;
-    VS_TRY(scratch.alloc(n_cnt * 8 + n_br * 8 + 3 * n_br * 4 + cells * 4));
-    unsigned long long* d_counts = scratch.as<unsigned long long>();
-    int64_t* rank_res = reinterpret_cast<int64_t*>(d_counts + n_cnt);
-    int32_t* rank_slot = reinterpret_cast<int32_t*>(rank_res + n_br);
-    uint32_t* rank_prefix = reinterpret_cast<uint32_t*>(rank_slot + n_br);
-    uint32_t* slot_prefix = rank_prefix + n_br;
-    int32_t* n_slots = reinterpret_cast<int32_t*>(slot_prefix + n_br);
-    ca.labels = d_l;
-    ca.n_labels = n_labels;
-    ca.R = R;
-    ca.slot_prefix = slot_prefix;
-    ca.n_slots = n_slots;
-    ca.counts = d_counts;
-    ca.missing = reinterpret_cast<unsigned long long*>(d_m);
-    ca.total = reinterpret_cast<unsigned long long*>(d_t);
-    ca.other = reinterpret_cast<unsigned long long*>(d_x);
-    int rc = VS_OK;
-    for (int level = 0; level < VS_VALUE_RADIX_LEVELS && rc == VS_OK; ++level) {
-        ca.level = level;
-        rc = fq_counts_launch(ca, plans[level], s);
-        if (rc == VS_OK) rc = launch_failed("facet_value_radix_counts", s);
-        // the step of the percentiles, a (query, label) cell as one of its queries (on the null stream it synchronises, which costs nothing here)
-        if (rc == VS_OK)
-            rc = vs_value_radix_step(level, reinterpret_cast<const int64_t*>(d_counts), (int32_t)cells, R, d_q, method, d_r, rank_res, rank_slot,
-                                     rank_prefix, slot_prefix, n_slots, d_c, d_or, d_v, dtype, device, stream);
-    }
-    if (rc != VS_OK) {
-        (void)hipStreamSynchronize(s);                              // the scratch and the staging buffers die here
-        return rc;
-    }
-    VS_STAGE("facet_value_quantiles", s);
-    if (!dev) {
-        VS_TRY(st_v.back(s));
-        VS_TRY(st_o.back(s));
-        VS_TRY(st_c.back(s));
-        VS_TRY(st_m.back(s));
-        VS_TRY(st_t.back(s));
-        VS_TRY(st_x.back(s));
-    }
-    VS_HIP(hipStreamSynchronize(s));                                // the scratch is freed before the call returns
-    if (Profiler::get().on) Profiler::get().drain();
-    return VS_OK;
-}
-
-int check_quantiles(const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B, const int32_t* labels, int32_t n_labels, const void* values,
-                    int dtype, int64_t n_rows, const double* q, int method, const int64_t* ranks, int32_t R, int64_t rows_per_chunk,
-                    bool have_outputs, FacetQuantilePlan* plans) {
-    for (int level = 0; level < VS_VALUE_RADIX_LEVELS; ++level)
-        VS_TRY(check_fq_set(words, bit0, ld_words, B, labels, n_labels, values, dtype, n_rows, R, level, rows_per_chunk, have_outputs, plans + level));
-    return check_ranks_arg(q, method, ranks, (int64_t)B * n_labels, R);
-}
-
-int check_counts(const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B, const int32_t* labels, int32_t n_labels, const void* values,
-                 int dtype, int64_t n_rows, int level, int32_t R, const uint32_t* slot_prefix, const int32_t* n_slots, int64_t rows_per_chunk,
-                 const int64_t* counts, const int64_t* missing, const int64_t* total, const int64_t* other, FacetQuantilePlan* plan) {
-    char msg[256];
-    VS_TRY(check_fq_set(words, bit0, ld_words, B, labels, n_labels, values, dtype, n_rows, R, level, rows_per_chunk, counts != nullptr, plan));
-    return plan_or_fail(facet_quantile_check_level_args(level, slot_prefix && n_slots, missing && total && other, msg, sizeof msg), msg);
+    DevBuf scratch;                                               // the counts of a level, then the step's state
+    return c.run("facet_value_quantiles", Finish::kSync, [&] {
+        FqArgs ca{};
+        const size_t cells = (size_t)src.B * (size_t)n_labels, n_br = cells * (size_t)R, n_cnt = n_br * VS_VALUE_RADIX_BINS;
+        VS_TRY(st.in(src, values, dtype, plans[0].rows_per_chunk, c.dev, c.s, &ca.s));
+        int32_t* d_l;
+        double* d_q;
+        uint32_t* d_v;
+        int64_t *d_r, *d_or, *d_c, *d_m, *d_t, *d_x;
+        VS_TRY(st_l.in(labels, (size_t)src.n_rows, c.dev, true, c.s, &d_l));
+        VS_TRY(st_q.in(q, (size_t)R, c.dev, true, c.s, &d_q));
+        VS_TRY(st_r.in(ranks, n_br, c.dev, true, c.s, &d_r));
+        VS_TRY(st_v.in(static_cast<uint32_t*>(out_values), n_br, c.dev, false, c.s, &d_v));
+        VS_TRY(st_o.in(out_ranks, n_br, c.dev, false, c.s, &d_or));
+        VS_TRY(st_c.in(count, cells, c.dev, false, c.s, &d_c));
+        VS_TRY(st_m.in(missing, cells, c.dev, false, c.s, &d_m));
+        VS_TRY(st_t.in(total, (size_t)src.B, c.dev, false, c.s, &d_t));
+        VS_TRY(st_x.in(other, (size_t)src.B, c.dev, false, c.s, &d_x));
+        VS_TRY(scratch.alloc(n_cnt * 8 + n_br * 8 + 3 * n_br * 4 + cells * 4));
+        unsigned long long* d_counts = scratch.as<unsigned long long>();
+        int64_t* rank_res = reinterpret_cast<int64_t*>(d_counts + n_cnt);
+        int32_t* rank_slot = reinterpret_cast<int32_t*>(rank_res + n_br);
+        uint32_t* rank_prefix = reinterpret_cast<uint32_t*>(rank_slot + n_br);
+        uint32_t* slot_prefix = rank_prefix + n_br;
+        int32_t* n_slots = reinterpret_cast<int32_t*>(slot_prefix + n_br);
+        ca.labels = d_l;
+        ca.n_labels = n_labels;
+        ca.R = R;
+        ca.slot_prefix = slot_prefix;
+        ca.n_slots = n_slots;
+        ca.counts = d_counts;
+        ca.missing = reinterpret_cast<unsigned long long*>(d_m);
+        ca.total = reinterpret_cast<unsigned long long*>(d_t);
+        ca.other = reinterpret_cast<unsigned long long*>(d_x);
+        for (int level = 0; level < VS_VALUE_RADIX_LEVELS; ++level) {
+            ca.level = level;
+            VS_TRY(fq_counts_launch(ca, plans[level], c.s));
+            VS_TRY(launch_failed("facet_value_radix_counts", c.s));
+            // the step of the percentiles, a (query, label) cell as one of its queries (on the null stream it synchronises, which costs nothing here)
+            VS_TRY(vs_value_radix_step(level, reinterpret_cast<const int64_t*>(d_counts), (int32_t)cells, R, d_q, method, d_r, rank_res, rank_slot,
+                                       rank_prefix, slot_prefix, n_slots, d_c, d_or, d_v, dtype, src.device, stream));
+        }
+        return VS_OK;
+    }, [&] {
+        VS_TRY(st_v.back(c.s));
+        VS_TRY(st_o.back(c.s));
+        VS_TRY(st_c.back(c.s));
+        VS_TRY(st_m.back(c.s));
+        VS_TRY(st_t.back(c.s));
+        return st_x.back(c.s);
+    });
 }
 
 }  // namespace
@@ -415,47 +384,34 @@ extern "C" int vs_facet_value_quantiles(const uint32_t* words, int64_t bit0, int
                                         const int32_t* labels, int32_t n_labels, const void* values, int dtype, int64_t n_rows, const double* q,
                                         int method, const int64_t* ranks, int32_t R, int64_t rows_per_chunk, void* out_values, int64_t* out_ranks,
                                         int64_t* count, int64_t* missing, int64_t* total, int64_t* other, int device, void* stream) {
-    FacetQuantilePlan plans[VS_VALUE_RADIX_LEVELS];
-    VS_TRY(check_quantiles(words, bit0, ld_words, B, labels, n_labels, values, dtype, n_rows, q, method, ranks, R, rows_per_chunk,
-                           out_values && out_ranks && count && missing && total && other, plans));
-    VS_TRY(device_in_range(device));
-    return quantiles_call(device, words, bit0, ld_words, and_words, nullptr, B, labels, n_labels, values, dtype, n_rows, q, method, ranks, R, plans,
-                          out_values, out_ranks, count, missing, total, other, stream);
+    return facet_value_quantiles(free_set(words, bit0, ld_words, and_words, B, n_rows, device), labels, n_labels, values, dtype, q, method, ranks, R,
+                                 rows_per_chunk, out_values, out_ranks, count, missing, total, other, stream);
 }
 
 extern "C" int vs_index_facet_value_quantiles(vs_index* idx, const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B, const int32_t* labels,
                                               int32_t n_labels, const void* values, int dtype, const double* q, int method, const int64_t* ranks,
                                               int32_t R, int64_t rows_per_chunk, void* out_values, int64_t* out_ranks, int64_t* count,
                                               int64_t* missing, int64_t* total, int64_t* other, void* stream) {
-    if (!idx) return fail(VS_EINVAL, "NULL argument");
-    FacetQuantilePlan plans[VS_VALUE_RADIX_LEVELS];
-    VS_TRY(check_quantiles(words, bit0, ld_words, B, labels, n_labels, values, dtype, idx->n_rows, q, method, ranks, R, rows_per_chunk,
-                           out_values && out_ranks && count && missing && total && other, plans));
-    // tombstones are ANDed in, as every search does (the live bitmap starts at bit 0 whatever bit0 is)
-    return quantiles_call(idx->device, words, bit0, ld_words, nullptr, live_words(idx), B, labels, n_labels, values, dtype, idx->n_rows, q, method, ranks,
-                          R, plans, out_values, out_ranks, count, missing, total, other, stream);
+    SetSrc src;
+    VS_TRY(index_set(idx, words, bit0, ld_words, B, &src));
+    return facet_value_quantiles(src, labels, n_labels, values, dtype, q, method, ranks, R, rows_per_chunk, out_values, out_ranks, count, missing, total,
+                                 other, stream);
 }
 
 extern "C" int vs_facet_value_radix_counts(const uint32_t* words, int64_t bit0, int64_t ld_words, const uint32_t* and_words, int32_t B,
                                            const int32_t* labels, int32_t n_labels, const void* values, int dtype, int64_t n_rows, int level, int32_t R,
                                            const uint32_t* slot_prefix, const int32_t* n_slots, int64_t rows_per_chunk, int64_t* counts,
                                            int64_t* missing, int64_t* total, int64_t* other, int device, void* stream) {
-    FacetQuantilePlan plan;
-    VS_TRY(check_counts(words, bit0, ld_words, B, labels, n_labels, values, dtype, n_rows, level, R, slot_prefix, n_slots, rows_per_chunk, counts,
-                        missing, total, other, &plan));
-    VS_TRY(device_in_range(device));
-    return counts_call(device, words, bit0, ld_words, and_words, nullptr, B, labels, n_labels, values, dtype, n_rows, level, R, slot_prefix, n_slots, plan,
-                       counts, missing, total, other, stream);
+    return facet_radix_counts(free_set(words, bit0, ld_words, and_words, B, n_rows, device), labels, n_labels, values, dtype, level, R, slot_prefix,
+                              n_slots, rows_per_chunk, counts, missing, total, other, stream);
 }
 
 extern "C" int vs_index_facet_value_radix_counts(vs_index* idx, const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B,
                                                  const int32_t* labels, int32_t n_labels, const void* values, int dtype, int level, int32_t R,
                                                  const uint32_t* slot_prefix, const int32_t* n_slots, int64_t rows_per_chunk, int64_t* counts,
                                                  int64_t* missing, int64_t* total, int64_t* other, void* stream) {
-    if (!idx) return fail(VS_EINVAL, "NULL argument");
-    FacetQuantilePlan plan;
-    VS_TRY(check_counts(words, bit0, ld_words, B, labels, n_labels, values, dtype, idx->n_rows, level, R, slot_prefix, n_slots, rows_per_chunk, counts,
-                        missing, total, other, &plan));
-    return counts_call(idx->device, words, bit0, ld_words, nullptr, live_words(idx), B, labels, n_labels, values, dtype, idx->n_rows, level, R,
-                       slot_prefix, n_slots, plan, counts, missing, total, other, stream);
+    SetSrc src;
+    VS_TRY(index_set(idx, words, bit0, ld_words, B, &src));
+    return facet_radix_counts(src, labels, n_labels, values, dtype, level, R, slot_prefix, n_slots, rows_per_chunk, counts, missing, total, other,
+                              stream);
 }

@@ -376,132 +376,106 @@ int hist_launch_qt(const FacetValuePlan& p, const FvHistArgs& a, dim3 grid, hipS
     return VS_OK;
 }
 
-// the launch ladder over the plan's tile
-template <class F>
-int launch_by_qt(const FacetValuePlan& p, F f) {
-    if (p.qt == 8) return f(std::integral_constant<int, 8>{});
-    if (p.qt == 4) return f(std::integral_constant<int, 4>{});
-    if (p.qt == 2) return f(std::integral_constant<int, 2>{});
-    return f(std::integral_constant<int, 1>{});
-}
-
-// One stats call on `device`.  and_user / and_dev: BitmapStage's (agg_call.h).
-int stats_call(int device, const uint32_t* words, int64_t bit0, int64_t ld_words, const uint32_t* and_user, const uint32_t* and_dev, int32_t B,
-               const int32_t* labels, int32_t n_labels, const void* values, int dtype, int64_t n_rows, const FacetValuePlan& plan, int64_t* count,
-               int64_t* missing, void* out_min, void* out_max, int64_t* sum, int64_t ld_out, int64_t* total, int64_t* other, void* stream) {
-    const void* ptrs[11] = {words, and_user, labels, values, count, missing, out_min, out_max, sum, total, other};
-    const char* names[11] = {"words", "and_words", "labels", "values", "count", "missing", "out_min", "out_max", "sum", "total", "other"};
-    bool dev = false;
-    VS_TRY(pointers_kind(ptrs, names, 11, device, &dev));
-    VS_HIP(hipSetDevice(device));
-    hipStream_t s = (hipStream_t)stream;
+// vs_facet_value_stats and vs_index_facet_value_stats: one call on the set's device
+int facet_value_stats(const SetSrc& src, const int32_t* labels, int32_t n_labels, const void* values, int dtype, int64_t rows_per_chunk,
+                      int64_t* count, int64_t* missing, void* out_min, void* out_max, int64_t* sum, int64_t ld_out, int64_t* total, int64_t* other,
+                      void* stream) {
+    FacetValuePlan plan;
+    char msg[256];
+    VS_TRY(plan_or_fail(facet_value_check_stats(labels && values && count && missing && out_min && out_max && sum && total && other,
+                                                src.words != nullptr, src.bit0, src.ld_words, src.B, dtype, src.n_rows, n_labels, rows_per_chunk, ld_out,
+                                                &plan, msg, sizeof msg), msg));
+    VS_TRY(src.device_ok());
+    Call c;
+    VS_TRY(c.open(src.device, stream, {{"words", src.words}, {"and_words", src.and_user}, {"labels", labels}, {"values", values}, {"count", count},
+                                       {"missing", missing}, {"out_min", out_min}, {"out_max", out_max}, {"sum", sum}, {"total", total},
+                                       {"other", other}}));
+    const int32_t B = src.B;
     SetStage st;
     Staged st_l;
-    FvStatsArgs a{};
-    int32_t* d_l;
-    VS_TRY(st.in(words, bit0, ld_words, and_user, and_dev, B, values, dtype, n_rows, plan.rows_per_chunk, dev, s, &a.s));
-    VS_TRY(st_l.in(labels, (size_t)n_rows, dev, true, s, &d_l));
-    a.labels = d_l;
-    a.n_labels = n_labels;
     CountsOut o_cnt, o_mis, o_sum;                                // (host outputs: three dense matrices, total and other behind the first)
     KeysOut o_key;
-    VS_TRY(o_cnt.bind(dev, count, ld_out, n_labels, B, {total, other}, s));
-    VS_TRY(o_mis.bind(dev, missing, ld_out, n_labels, B, {}, s));
-    VS_TRY(o_sum.bind(dev, sum, ld_out, n_labels, B, {}, s));
-    VS_TRY(o_key.bind(dev, out_min, out_max, ld_out, n_labels, B, s));
-    a.count = o_cnt.mat;
-    a.missing = o_mis.mat;
-    a.sum = o_sum.mat;
-    a.min_key = o_key.lo;
-    a.max_key = o_key.hi;
-    a.ld = o_cnt.ld;
-    a.total = o_cnt.vec[0];
-    a.other = o_cnt.vec[1];
-    {
-        ProfScope prof("facet_value_stats", s);
+    return c.run("facet_value_stats", Finish::kStream, [&] {
+        FvStatsArgs a{};
+        int32_t* d_l;
+        VS_TRY(st.in(src, values, dtype, plan.rows_per_chunk, c.dev, c.s, &a.s));
+        VS_TRY(st_l.in(labels, (size_t)src.n_rows, c.dev, true, c.s, &d_l));
+        a.labels = d_l;
+        a.n_labels = n_labels;
+        VS_TRY(o_cnt.bind(c.dev, count, ld_out, n_labels, B, {total, other}, c.s));
+        VS_TRY(o_mis.bind(c.dev, missing, ld_out, n_labels, B, {}, c.s));
+        VS_TRY(o_sum.bind(c.dev, sum, ld_out, n_labels, B, {}, c.s));
+        VS_TRY(o_key.bind(c.dev, out_min, out_max, ld_out, n_labels, B, c.s));
+        a.count = o_cnt.mat;
+        a.missing = o_mis.mat;
+        a.sum = o_sum.mat;
+        a.min_key = o_key.lo;
+        a.max_key = o_key.hi;
+        a.ld = o_cnt.ld;
+        a.total = o_cnt.vec[0];
+        a.other = o_cnt.vec[1];
+        ProfScope prof("facet_value_stats", c.s);
         const dim3 grid((unsigned)plan.chunks, (unsigned)ceil_div64(B, plan.qt));
-        VS_TRY(launch_rc(launch_by_qt(plan, [&](auto qt) { return stats_launch_qt<decltype(qt)::value>(plan, a, grid, s); }), s));
+        VS_TRY(launch_by_qt(plan.qt, [&](auto qt) { return stats_launch_qt<decltype(qt)::value>(plan, a, grid, c.s); }));
         const int64_t cells = (int64_t)B * n_labels;
-        hipLaunchKernelGGL(facet_value_finish_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, a.min_key, a.max_key, a.count, cells, n_labels,
-                           a.ld, dtype);
-    }
-    const hipError_t le = hipGetLastError();
-    if (le != hipSuccess) {
-        (void)hipStreamSynchronize(s);                              // staging buffers die here
-        return fail(VS_EHIP, "facet_value_stats launch failed: %s", hipGetErrorString(le));
-    }
-    VS_STAGE("facet_value_stats", s);
-    if (!dev) {
-        VS_TRY(o_cnt.back(s));
-        VS_TRY(o_mis.back(s));
-        VS_TRY(o_sum.back(s));
-        VS_TRY(o_key.back(s));
-    }
-    return finish_call(dev, stream, s);
+        hipLaunchKernelGGL(facet_value_finish_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, c.s, a.min_key, a.max_key, a.count, cells,
+                           n_labels, a.ld, dtype);
+        return VS_OK;
+    }, [&] {
+        VS_TRY(o_cnt.back(c.s));
+        VS_TRY(o_mis.back(c.s));
+        VS_TRY(o_sum.back(c.s));
+        return o_key.back(c.s);
+    });
 }
 
-int hist_call(int device, const uint32_t* words, int64_t bit0, int64_t ld_words, const uint32_t* and_user, const uint32_t* and_dev, int32_t B,
-              const int32_t* labels, int32_t n_labels, const void* values, int dtype, int64_t n_rows, const void* edges, int32_t n_edges,
-              const FacetValuePlan& plan, int64_t* counts, int64_t ld_counts, int64_t* below, int64_t* above, int64_t* missing, int64_t* total,
-              int64_t* other, void* stream) {
-    const void* ptrs[11] = {words, and_user, labels, values, edges, counts, below, above, missing, total, other};
-    const char* names[11] = {"words", "and_words", "labels", "values", "edges", "counts", "below", "above", "missing", "total", "other"};
-    bool dev = false;
-    VS_TRY(pointers_kind(ptrs, names, 11, device, &dev));
-    VS_HIP(hipSetDevice(device));
-    hipStream_t s = (hipStream_t)stream;
+// vs_facet_value_histogram and vs_index_facet_value_histogram (a host edges array is looked at before the device is, as vs_value_histogram does)
+int facet_value_histogram(const SetSrc& src, const int32_t* labels, int32_t n_labels, const void* values, int dtype, const void* edges,
+                          int32_t n_edges, int64_t rows_per_chunk, int64_t* counts, int64_t ld_counts, int64_t* below, int64_t* above,
+                          int64_t* missing, int64_t* total, int64_t* other, void* stream) {
+    FacetValuePlan plan;
+    char msg[256];
+    VS_TRY(plan_or_fail(facet_value_check_hist(labels && values && edges && counts && below && above && missing && total && other, src.words != nullptr,
+                                               src.bit0, src.ld_words, src.B, dtype, src.n_rows, n_labels, n_edges, rows_per_chunk, ld_counts, &plan, msg,
+                                               sizeof msg), msg));
+    if (!is_device_ptr(edges)) VS_TRY(plan_or_fail(value_check_edges_host(static_cast<const uint32_t*>(edges), n_edges, dtype, msg, sizeof msg), msg));
+    VS_TRY(src.device_ok());
+    Call c;
+    VS_TRY(c.open(src.device, stream, {{"words", src.words}, {"and_words", src.and_user}, {"labels", labels}, {"values", values}, {"edges", edges},
+                                       {"counts", counts}, {"below", below}, {"above", above}, {"missing", missing}, {"total", total},
+                                       {"other", other}}));
+    const int32_t B = src.B;
     SetStage st;
     Staged st_l, st_e;
-    FvHistArgs a{};
-    int32_t* d_l;
-    uint32_t* d_e;
-    VS_TRY(st.in(words, bit0, ld_words, and_user, and_dev, B, values, dtype, n_rows, plan.rows_per_chunk, dev, s, &a.s));
-    VS_TRY(st_l.in(labels, (size_t)n_rows, dev, true, s, &d_l));
-    VS_TRY(st_e.in(static_cast<const uint32_t*>(edges), (size_t)n_edges, dev, true, s, &d_e));
-    a.labels = d_l;
-    a.n_labels = n_labels;
-    a.edges = d_e;
-    a.n_edges = n_edges;
     CountsOut out;                                                // B x n_labels rows of n_edges - 1 columns, three [B x n_labels] vectors
     VecsOut tail;
-    VS_TRY(out.bind(dev, counts, ld_counts, n_edges - 1, B * n_labels, {below, above, missing}, s));
-    VS_TRY(tail.bind(dev, total, other, B, s));
-    a.counts = out.mat;
-    a.ld_counts = out.ld;
-    a.below = out.vec[0];
-    a.above = out.vec[1];
-    a.missing = out.vec[2];
-    a.total = tail.vec[0];
-    a.other = tail.vec[1];
-    {
-        ProfScope prof("facet_value_histogram", s);
+    return c.run("facet_value_histogram", Finish::kStream, [&] {
+        FvHistArgs a{};
+        int32_t* d_l;
+        uint32_t* d_e;
+        VS_TRY(st.in(src, values, dtype, plan.rows_per_chunk, c.dev, c.s, &a.s));
+        VS_TRY(st_l.in(labels, (size_t)src.n_rows, c.dev, true, c.s, &d_l));
+        VS_TRY(st_e.in(static_cast<const uint32_t*>(edges), (size_t)n_edges, c.dev, true, c.s, &d_e));
+        a.labels = d_l;
+        a.n_labels = n_labels;
+        a.edges = d_e;
+        a.n_edges = n_edges;
+        VS_TRY(out.bind(c.dev, counts, ld_counts, n_edges - 1, B * n_labels, {below, above, missing}, c.s));
+        VS_TRY(tail.bind(c.dev, total, other, B, c.s));
+        a.counts = out.mat;
+        a.ld_counts = out.ld;
+        a.below = out.vec[0];
+        a.above = out.vec[1];
+        a.missing = out.vec[2];
+        a.total = tail.vec[0];
+        a.other = tail.vec[1];
+        ProfScope prof("facet_value_histogram", c.s);
         const dim3 grid((unsigned)plan.chunks, (unsigned)ceil_div64(B, plan.qt));
-        VS_TRY(launch_rc(launch_by_qt(plan, [&](auto qt) { return hist_launch_qt<decltype(qt)::value>(plan, a, grid, s); }), s));
-    }
-    VS_STAGE("facet_value_histogram", s);
-    if (!dev) {
-        VS_TRY(out.back(s));
-        VS_TRY(tail.back(s));
-    }
-    return finish_call(dev, stream, s);
-}
-
-int check_stats(const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B, const int32_t* labels, int32_t n_labels, const void* values,
-                int dtype, int64_t n_rows, int64_t rows_per_chunk, int64_t ld_out, bool have_outputs, FacetValuePlan* plan) {
-    char msg[256];
-    return plan_or_fail(facet_value_check_stats(labels && values && have_outputs, words != nullptr, bit0, ld_words, B, dtype, n_rows, n_labels,
-                                                rows_per_chunk, ld_out, plan, msg, sizeof msg), msg);
-}
-
-// a host edges array is looked at before the device is, as vs_value_histogram does
-int check_hist(const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B, const int32_t* labels, int32_t n_labels, const void* values,
-               int dtype, int64_t n_rows, const void* edges, int32_t n_edges, int64_t rows_per_chunk, int64_t ld_counts, bool have_outputs,
-               FacetValuePlan* plan) {
-    char msg[256];
-    VS_TRY(plan_or_fail(facet_value_check_hist(labels && values && edges && have_outputs, words != nullptr, bit0, ld_words, B, dtype, n_rows, n_labels,
-                                               n_edges, rows_per_chunk, ld_counts, plan, msg, sizeof msg), msg));
-    if (is_device_ptr(edges)) return VS_OK;
-    return plan_or_fail(value_check_edges_host(static_cast<const uint32_t*>(edges), n_edges, dtype, msg, sizeof msg), msg);
+        return launch_by_qt(plan.qt, [&](auto qt) { return hist_launch_qt<decltype(qt)::value>(plan, a, grid, c.s); });
+    }, [&] {
+        VS_TRY(out.back(c.s));
+        return tail.back(c.s);
+    });
 }
 
 }  // namespace
@@ -523,46 +497,32 @@ extern "C" int vs_facet_value_stats(const uint32_t* words, int64_t bit0, int64_t
                                     const int32_t* labels, int32_t n_labels, const void* values, int dtype, int64_t n_rows, int64_t rows_per_chunk,
                                     int64_t* count, int64_t* missing, void* out_min, void* out_max, int64_t* sum, int64_t ld_out, int64_t* total,
                                     int64_t* other, int device, void* stream) {
-    FacetValuePlan plan;
-    VS_TRY(check_stats(words, bit0, ld_words, B, labels, n_labels, values, dtype, n_rows, rows_per_chunk, ld_out,
-                       count && missing && out_min && out_max && sum && total && other, &plan));
-    VS_TRY(device_in_range(device));
-    return stats_call(device, words, bit0, ld_words, and_words, nullptr, B, labels, n_labels, values, dtype, n_rows, plan, count, missing, out_min,
-                      out_max, sum, ld_out, total, other, stream);
+    return facet_value_stats(free_set(words, bit0, ld_words, and_words, B, n_rows, device), labels, n_labels, values, dtype, rows_per_chunk, count,
+                             missing, out_min, out_max, sum, ld_out, total, other, stream);
 }
 
 extern "C" int vs_index_facet_value_stats(vs_index* idx, const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B, const int32_t* labels,
                                           int32_t n_labels, const void* values, int dtype, int64_t rows_per_chunk, int64_t* count, int64_t* missing,
                                           void* out_min, void* out_max, int64_t* sum, int64_t ld_out, int64_t* total, int64_t* other, void* stream) {
-    if (!idx) return fail(VS_EINVAL, "NULL argument");
-    FacetValuePlan plan;
-    VS_TRY(check_stats(words, bit0, ld_words, B, labels, n_labels, values, dtype, idx->n_rows, rows_per_chunk, ld_out,
-                       count && missing && out_min && out_max && sum && total && other, &plan));
-    // tombstones are ANDed in, as every search does (the live bitmap starts at bit 0 whatever bit0 is)
-    return stats_call(idx->device, words, bit0, ld_words, nullptr, live_words(idx), B, labels, n_labels, values, dtype, idx->n_rows, plan, count, missing,
-                      out_min, out_max, sum, ld_out, total, other, stream);
+    SetSrc src;
+    VS_TRY(index_set(idx, words, bit0, ld_words, B, &src));
+    return facet_value_stats(src, labels, n_labels, values, dtype, rows_per_chunk, count, missing, out_min, out_max, sum, ld_out, total, other, stream);
 }
 
 extern "C" int vs_facet_value_histogram(const uint32_t* words, int64_t bit0, int64_t ld_words, const uint32_t* and_words, int32_t B,
                                         const int32_t* labels, int32_t n_labels, const void* values, int dtype, int64_t n_rows, const void* edges,
                                         int32_t n_edges, int64_t rows_per_chunk, int64_t* counts, int64_t ld_counts, int64_t* below, int64_t* above,
                                         int64_t* missing, int64_t* total, int64_t* other, int device, void* stream) {
-    FacetValuePlan plan;
-    VS_TRY(check_hist(words, bit0, ld_words, B, labels, n_labels, values, dtype, n_rows, edges, n_edges, rows_per_chunk, ld_counts,
-                      counts && below && above && missing && total && other, &plan));
-    VS_TRY(device_in_range(device));
-    return hist_call(device, words, bit0, ld_words, and_words, nullptr, B, labels, n_labels, values, dtype, n_rows, edges, n_edges, plan, counts,
-                     ld_counts, below, above, missing, total, other, stream);
+    return facet_value_histogram(free_set(words, bit0, ld_words, and_words, B, n_rows, device), labels, n_labels, values, dtype, edges, n_edges,
+                                 rows_per_chunk, counts, ld_counts, below, above, missing, total, other, stream);
 }
 
 extern "C" int vs_index_facet_value_histogram(vs_index* idx, const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B, const int32_t* labels,
                                               int32_t n_labels, const void* values, int dtype, const void* edges, int32_t n_edges,
                                               int64_t rows_per_chunk, int64_t* counts, int64_t ld_counts, int64_t* below, int64_t* above,
                                               int64_t* missing, int64_t* total, int64_t* other, void* stream) {
-    if (!idx) return fail(VS_EINVAL, "NULL argument");
-    FacetValuePlan plan;
-    VS_TRY(check_hist(words, bit0, ld_words, B, labels, n_labels, values, dtype, idx->n_rows, edges, n_edges, rows_per_chunk, ld_counts,
-                      counts && below && above && missing && total && other, &plan));
-    return hist_call(idx->device, words, bit0, ld_words, nullptr, live_words(idx), B, labels, n_labels, values, dtype, idx->n_rows, edges, n_edges, plan,
-                     counts, ld_counts, below, above, missing, total, other, stream);
+    SetSrc src;
+    VS_TRY(index_set(idx, words, bit0, ld_words, B, &src));
+    return facet_value_histogram(src, labels, n_labels, values, dtype, edges, n_edges, rows_per_chunk, counts, ld_counts, below, above, missing, total,
+                                 other, stream);
 }

@@ -153,54 +153,47 @@ int facet_launch_qt(const FacetPlan& p, const FacetArgs& a, dim3 grid, hipStream
 }
 
 // the argument checks that need no device
-int facet_check(const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B, const int32_t* labels, int64_t n_rows, int32_t n_labels,
-                int64_t rows_per_chunk, const int64_t* counts, int64_t ld_counts, const int64_t* total, const int64_t* other, FacetPlan* plan) {
+int facet_check(const SetSrc& src, const int32_t* labels, int32_t n_labels, int64_t rows_per_chunk, const int64_t* counts, int64_t ld_counts,
+                const int64_t* total, const int64_t* other, FacetPlan* plan) {
     if (!labels || !counts || !total || !other) return fail(VS_EINVAL, "NULL argument");
-    if (bit0 < 0) return fail(VS_EINVAL, "bit0 must be >= 0");
-    VS_TRY(facet_plan(n_rows, B, n_labels, words && ld_words != 0, rows_per_chunk, plan));
+    if (src.bit0 < 0) return fail(VS_EINVAL, "bit0 must be >= 0");
+    VS_TRY(facet_plan(src.n_rows, src.B, n_labels, src.per_query(), rows_per_chunk, plan));
     char msg[256];
-    VS_TRY(plan_or_fail(check_ld_words(words != nullptr, bit0, ld_words, n_rows, msg, sizeof msg), msg));
+    VS_TRY(plan_or_fail(check_ld_words(src.words != nullptr, src.bit0, src.ld_words, src.n_rows, msg, sizeof msg), msg));
     if (ld_counts < n_labels) return fail(VS_EINVAL, "ld_counts = %lld is shorter than n_labels = %d", (long long)ld_counts, n_labels);
-    if (plan->chunks > 0x7FFFFFFF || ceil_div64(B, plan->qt) > 65535)
-        return fail(VS_EINVAL, "%lld chunks x %d queries are too many for one call", (long long)plan->chunks, B);
+    if (plan->chunks > 0x7FFFFFFF || ceil_div64(src.B, plan->qt) > 65535)
+        return fail(VS_EINVAL, "%lld chunks x %d queries are too many for one call", (long long)plan->chunks, src.B);
     return VS_OK;
 }
 
-// One call on `device`.  and_user / and_dev: BitmapStage's (agg_call.h).
-int facet_call(int device, const uint32_t* words, int64_t bit0, int64_t ld_words, const uint32_t* and_user, const uint32_t* and_dev, int32_t B,
-               const int32_t* labels, int64_t n_rows, int32_t n_labels, const FacetPlan& plan, int64_t* counts, int64_t ld_counts, int64_t* total,
-               int64_t* other, void* stream) {
-    const void* ptrs[6] = {words, and_user, labels, counts, total, other};
-    const char* names[6] = {"words", "and_words", "labels", "counts", "total", "other"};
-    bool dev = false;
-    VS_TRY(pointers_kind(ptrs, names, 6, device, &dev));
-    VS_HIP(hipSetDevice(device));
-    hipStream_t s = (hipStream_t)stream;
+// vs_facet_counts and vs_index_facet_counts: one call on the set's device
+int facet_counts(const SetSrc& src, const int32_t* labels, int32_t n_labels, int64_t rows_per_chunk, int64_t* counts, int64_t ld_counts,
+                 int64_t* total, int64_t* other, void* stream) {
+    FacetPlan plan;
+    VS_TRY(facet_check(src, labels, n_labels, rows_per_chunk, counts, ld_counts, total, other, &plan));
+    VS_TRY(src.device_ok());
+    Call c;
+    VS_TRY(c.open(src.device, stream, {{"words", src.words}, {"and_words", src.and_user}, {"labels", labels}, {"counts", counts}, {"total", total},
+                                       {"other", other}}));
     BitmapStage st;
     Staged st_l;
     CountsOut out;
-    FacetArgs a{};
-    int32_t* d_l;
-    VS_TRY(st.in(words, bit0, ld_words, and_user, and_dev, B, n_rows, plan.rows_per_chunk, dev, s, &a.set));
-    VS_TRY(st_l.in(labels, (size_t)n_rows, dev, true, s, &d_l));
-    a.labels = d_l;
-    a.n_labels = n_labels;
-    VS_TRY(out.bind(dev, counts, ld_counts, n_labels, B, {total, other}, s));
-    a.counts = out.mat;
-    a.ld_counts = out.ld;
-    a.total = out.vec[0];
-    a.other = out.vec[1];
-    {
-        ProfScope prof("facet_counts", s);
-        const dim3 grid((unsigned)plan.chunks, (unsigned)ceil_div64(B, plan.qt));
-        VS_TRY(launch_rc(plan.qt == 8 ? facet_launch_qt<8>(plan, a, grid, s)
-                         : plan.qt == 4 ? facet_launch_qt<4>(plan, a, grid, s)
-                         : plan.qt == 2 ? facet_launch_qt<2>(plan, a, grid, s)
-                                        : facet_launch_qt<1>(plan, a, grid, s), s));
-    }
-    VS_STAGE("facet_counts", s);
-    if (!dev) VS_TRY(out.back(s));
-    return finish_call(dev, stream, s);
+    return c.run("facet_counts", Finish::kStream, [&] {
+        FacetArgs a{};
+        int32_t* d_l;
+        VS_TRY(st.in(src, plan.rows_per_chunk, c.dev, c.s, &a.set));
+        VS_TRY(st_l.in(labels, (size_t)src.n_rows, c.dev, true, c.s, &d_l));
+        a.labels = d_l;
+        a.n_labels = n_labels;
+        VS_TRY(out.bind(c.dev, counts, ld_counts, n_labels, src.B, {total, other}, c.s));
+        a.counts = out.mat;
+        a.ld_counts = out.ld;
+        a.total = out.vec[0];
+        a.other = out.vec[1];
+        ProfScope prof("facet_counts", c.s);
+        const dim3 grid((unsigned)plan.chunks, (unsigned)ceil_div64(src.B, plan.qt));
+        return launch_by_qt(plan.qt, [&](auto qt) { return facet_launch_qt<decltype(qt)::value>(plan, a, grid, c.s); });
+    }, [&] { return out.back(c.s); });
 }
 
 // ---- top-n ---------------------------------------------------------------------------------------------------------------------------
@@ -248,20 +241,16 @@ extern "C" int vs_facet_plan(int64_t n_rows, int32_t B, int32_t n_labels, int pe
 extern "C" int vs_facet_counts(const uint32_t* words, int64_t bit0, int64_t ld_words, const uint32_t* and_words, int32_t B, const int32_t* labels,
                                int64_t n_rows, int32_t n_labels, int64_t rows_per_chunk, int64_t* counts, int64_t ld_counts, int64_t* total,
                                int64_t* other, int device, void* stream) {
-    FacetPlan plan;
-    VS_TRY(facet_check(words, bit0, ld_words, B, labels, n_rows, n_labels, rows_per_chunk, counts, ld_counts, total, other, &plan));
-    VS_TRY(device_in_range(device));
-    return facet_call(device, words, bit0, ld_words, and_words, nullptr, B, labels, n_rows, n_labels, plan, counts, ld_counts, total, other, stream);
+    return facet_counts(free_set(words, bit0, ld_words, and_words, B, n_rows, device), labels, n_labels, rows_per_chunk, counts, ld_counts, total,
+                        other, stream);
 }
 
 extern "C" int vs_index_facet_counts(vs_index* idx, const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B, const int32_t* labels,
                                      int32_t n_labels, int64_t rows_per_chunk, int64_t* counts, int64_t ld_counts, int64_t* total, int64_t* other,
                                      void* stream) {
-    if (!idx) return fail(VS_EINVAL, "NULL argument");
-    FacetPlan plan;
-    VS_TRY(facet_check(words, bit0, ld_words, B, labels, idx->n_rows, n_labels, rows_per_chunk, counts, ld_counts, total, other, &plan));
-    return facet_call(idx->device, words, bit0, ld_words, nullptr, live_words(idx), B, labels, idx->n_rows, n_labels, plan, counts, ld_counts, total,
-                      other, stream);
+    SetSrc src;
+    VS_TRY(index_set(idx, words, bit0, ld_words, B, &src));
+    return facet_counts(src, labels, n_labels, rows_per_chunk, counts, ld_counts, total, other, stream);
 }
 
 extern "C" int vs_facet_topn(const int64_t* counts, int64_t ld_counts, int32_t B, int32_t n_labels, int32_t n, int64_t min_count,
@@ -272,32 +261,26 @@ extern "C" int vs_facet_topn(const int64_t* counts, int64_t ld_counts, int32_t B
     if (n < 1 || n > VS_FACET_MAX_TOPN) return fail(VS_EINVAL, "n must be in 1..%d (got %d)", VS_FACET_MAX_TOPN, n);
     if (ld_counts < n_labels) return fail(VS_EINVAL, "ld_counts = %lld is shorter than n_labels = %d", (long long)ld_counts, n_labels);
     VS_TRY(device_in_range(device));
-    const void* ptrs[3] = {counts, out_labels, out_counts};
-    const char* names[3] = {"counts", "out_labels", "out_counts"};
-    bool dev = false;
-    VS_TRY(pointers_kind(ptrs, names, 3, device, &dev));
-    VS_HIP(hipSetDevice(device));
-    hipStream_t s = (hipStream_t)stream;
+    Call c;
+    VS_TRY(c.open(device, stream, {{"counts", counts}, {"out_labels", out_labels}, {"out_counts", out_counts}}));
     Staged st[3];
-    TopnArgs a{};
-    int64_t* d_counts;
-    VS_TRY(st[0].in(counts, (size_t)(B - 1) * (size_t)ld_counts + (size_t)n_labels, dev, true, s, &d_counts));
-    VS_TRY(st[1].in(out_labels, (size_t)B * n, dev, false, s, &a.out_labels));
-    VS_TRY(st[2].in(out_counts, (size_t)B * n, dev, false, s, &a.out_counts));
-    a.counts = d_counts;
-    a.ld_counts = ld_counts;
-    a.n_labels = n_labels;
-    a.n = n;
-    a.min_count = std::max<int64_t>(min_count, 1);
-    {
-        ProfScope prof("facet_topn", s);
-        hipLaunchKernelGGL(facet_topn_kernel, dim3((unsigned)B), dim3(kFacetThreads), 0, s, a);
+    return c.run("facet_topn", Finish::kStream, [&] {
+        TopnArgs a{};
+        int64_t* d_counts;
+        VS_TRY(st[0].in(counts, (size_t)(B - 1) * (size_t)ld_counts + (size_t)n_labels, c.dev, true, c.s, &d_counts));
+        VS_TRY(st[1].in(out_labels, (size_t)B * n, c.dev, false, c.s, &a.out_labels));
+        VS_TRY(st[2].in(out_counts, (size_t)B * n, c.dev, false, c.s, &a.out_counts));
+        a.counts = d_counts;
+        a.ld_counts = ld_counts;
+        a.n_labels = n_labels;
+        a.n = n;
+        a.min_count = std::max<int64_t>(min_count, 1);
+        ProfScope prof("facet_topn", c.s);
+        hipLaunchKernelGGL(facet_topn_kernel, dim3((unsigned)B), dim3(kFacetThreads), 0, c.s, a);
         VS_HIP(hipGetLastError());
-    }
-    VS_STAGE("facet_topn", s);
-    if (!dev) {
-        VS_TRY(st[1].back(s));
-        VS_TRY(st[2].back(s));
-    }
-    return finish_call(dev, stream, s);
+        return VS_OK;
+    }, [&] {
+        VS_TRY(st[1].back(c.s));
+        return st[2].back(c.s);
+    });
 }

@@ -342,12 +342,10 @@ int label_term_call(vs_index* idx, const uint32_t* words, int64_t bit0, const in
             return term_launch<decltype(sd)::value, decltype(is_counts)::value>(a, grid, s);
         }), s));
     }
-    VS_STAGE(prof_name, s);
-    if (!dev) {
+    return close_call(prof_name, dev, stream, s, Finish::kStream, [&] {
         VS_TRY(o.back(s));
-        VS_TRY(st_o.back(s));
-    }
-    return finish_call(dev, stream, s);
+        return st_o.back(s);
+    });
 }
 
 }  // namespace
@@ -399,13 +397,11 @@ extern "C" int vs_label_order(vs_index* idx, const uint32_t* words, int64_t bit0
         VS_HIP(hipMemsetAsync(d_ptr, 0, ((size_t)n_labels + 1) * 8, s));
         VS_HIP(hipMemsetAsync(d_other, 0, 8, s));
     }
-    VS_STAGE("label_order", s);
-    if (!dev) {
+    return close_call("label_order", dev, stream, s, Finish::kStream, [&] {
         VS_TRY(st_p.back(s));
         VS_TRY(st_r.back(s));
-        VS_TRY(st_o.back(s));
-    }
-    return finish_call(dev, stream, s);
+        return st_o.back(s);
+    });
 }
 
 extern "C" int vs_index_label_term_sums(vs_index* idx, const uint32_t* words, int64_t bit0, const int32_t* labels, int32_t n_labels,

@@ -249,12 +249,7 @@ int radix_launch_qt(const RadixArgs& a, dim3 grid, size_t lds, hipStream_t s) {
 
 template <bool TOP>
 int radix_launch_top(const RadixArgs& a, int32_t qt, dim3 grid, size_t lds, hipStream_t s) {
-    switch (qt) {
-        case 8: return radix_launch_qt<8, TOP>(a, grid, lds, s);
-        case 4: return radix_launch_qt<4, TOP>(a, grid, lds, s);
-        case 2: return radix_launch_qt<2, TOP>(a, grid, lds, s);
-        default: return radix_launch_qt<1, TOP>(a, grid, lds, s);
-    }
+    return launch_by_qt(qt, [&](auto t) { return radix_launch_qt<decltype(t)::value, TOP>(a, grid, lds, s); });
 }
 
 // zero a level's counts (and missing at level 0) and count; everything on the device
@@ -274,21 +269,13 @@ int radix_step_launch(const StepArgs& a, hipStream_t s) {
     return VS_OK;
 }
 
-int launch_failed(const char* what, hipStream_t s) {
-    const hipError_t le = hipGetLastError();
-    if (le == hipSuccess) return VS_OK;
-    (void)hipStreamSynchronize(s);                                  // staging buffers die with the caller
-    return fail(VS_EHIP, "%s launch failed: %s", what, hipGetErrorString(le));
-}
-
 // the set, R and the scratch of a call -> the plan
-int check_quant_set(const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B, const void* values, int dtype, int64_t n_rows, int32_t R,
-                    int64_t rows_per_chunk, bool have_outputs, ValuePlan* plan) {
+int check_quant_set(const SetSrc& src, const void* values, int dtype, int32_t R, int64_t rows_per_chunk, bool have_outputs, ValuePlan* plan) {
     char msg[256];
     VS_TRY(plan_or_fail(quantile_check_ranks(R, msg, sizeof msg), msg));
-    VS_TRY(plan_or_fail(value_check_set(values && have_outputs, words != nullptr, bit0, ld_words, B, dtype, n_rows, 0, rows_per_chunk,
-                                        quantile_qt(R, true), plan, msg, sizeof msg), msg));
-    return plan_or_fail(quantile_check_scratch(B, R, msg, sizeof msg), msg);
+    VS_TRY(plan_or_fail(value_check_set(values && have_outputs, src.words != nullptr, src.bit0, src.ld_words, src.B, dtype, src.n_rows, 0,
+                                        rows_per_chunk, quantile_qt(R, true), plan, msg, sizeof msg), msg));
+    return plan_or_fail(quantile_check_scratch(src.B, R, msg, sizeof msg), msg);
 }
 
 // q with its method, or ranks: host arrays are looked at before the device is
@@ -304,110 +291,111 @@ int check_ranks_arg(const double* q, int method, const int64_t* ranks, int32_t B
     return VS_OK;
 }
 
-int counts_call(int device, const uint32_t* words, int64_t bit0, int64_t ld_words, const uint32_t* and_user, const uint32_t* and_dev, int32_t B,
-                const void* values, int dtype, int64_t n_rows, int level, int32_t R, const uint32_t* slot_prefix, const int32_t* n_slots,
-                const ValuePlan& plan, int64_t* counts, int64_t* missing, void* stream) {
-    if (level != 0) missing = nullptr;
-    else slot_prefix = nullptr, n_slots = nullptr;
-    const void* ptrs[7] = {words, and_user, values, slot_prefix, n_slots, counts, missing};
-    const char* names[7] = {"words", "and_words", "values", "slot_prefix", "n_slots", "counts", "missing"};
-    bool dev = false;
-    VS_TRY(pointers_kind(ptrs, names, 7, device, &dev));
-    VS_HIP(hipSetDevice(device));
-    hipStream_t s = (hipStream_t)stream;
-    SetStage st;
-    Staged st_p, st_n, st_c, st_m;
-    RadixArgs a{};
-    VS_TRY(st.in(words, bit0, ld_words, and_user, and_dev, B, values, dtype, n_rows, plan.rows_per_chunk, dev, s, &a.s));
-    uint32_t* d_p;
-    int32_t* d_n;
-    int64_t *d_c, *d_m;
-    VS_TRY(st_p.in(slot_prefix, (size_t)B * R, dev, true, s, &d_p));
-    VS_TRY(st_n.in(n_slots, (size_t)B, dev, true, s, &d_n));
-    VS_TRY(st_c.in(counts, level_counts(B, R, level), dev, false, s, &d_c));
-    VS_TRY(st_m.in(missing, (size_t)B, dev, false, s, &d_m));
-    a.level = level;
-    a.R = R;
-    a.slot_prefix = d_p;
-    a.n_slots = d_n;
-    a.counts = reinterpret_cast<unsigned long long*>(d_c);
-    a.missing = reinterpret_cast<unsigned long long*>(d_m);
-    VS_TRY(radix_counts_launch(a, plan, s));
-    VS_TRY(launch_failed("value_radix_counts", s));
-    VS_STAGE("value_radix_counts", s);
-    if (!dev) {
-        VS_TRY(st_c.back(s));
-        VS_TRY(st_m.back(s));
-    }
-    return finish_call(dev, stream, s);
+int check_counts_arg(int level, const uint32_t* slot_prefix, const int32_t* n_slots, const int64_t* missing) {
+    char msg[256];
+    VS_TRY(plan_or_fail(quantile_check_level(level, msg, sizeof msg), msg));
+    if (level == 0 ? !missing : (!slot_prefix || !n_slots)) return fail(VS_EINVAL, "NULL argument: level %d needs %s", level,
+                                                                        level == 0 ? "missing" : "slot_prefix and n_slots");
+    return VS_OK;
 }
 
-int quantiles_call(int device, const uint32_t* words, int64_t bit0, int64_t ld_words, const uint32_t* and_user, const uint32_t* and_dev, int32_t B,
-                   const void* values, int dtype, int64_t n_rows, const double* q, int method, const int64_t* ranks, int32_t R,
-                   const ValuePlan& plan, void* out_values, int64_t* out_ranks, int64_t* count, int64_t* missing, void* stream) {
+// vs_value_radix_counts and vs_index_value_radix_counts: one level's counts on the set's device
+int radix_counts(const SetSrc& src, const void* values, int dtype, int level, int32_t R, const uint32_t* slot_prefix, const int32_t* n_slots,
+                 int64_t rows_per_chunk, int64_t* counts, int64_t* missing, void* stream) {
+    ValuePlan plan;
+    VS_TRY(check_quant_set(src, values, dtype, R, rows_per_chunk, counts != nullptr, &plan));
+    VS_TRY(check_counts_arg(level, slot_prefix, n_slots, missing));
+    VS_TRY(src.device_ok());
+    if (level != 0) missing = nullptr;
+    else slot_prefix = nullptr, n_slots = nullptr;
+    Call c;
+    VS_TRY(c.open(src.device, stream, {{"words", src.words}, {"and_words", src.and_user}, {"values", values}, {"slot_prefix", slot_prefix},
+                                       {"n_slots", n_slots}, {"counts", counts}, {"missing", missing}}));
+    const int32_t B = src.B;
+    SetStage st;
+    Staged st_p, st_n, st_c, st_m;
+    return c.run("value_radix_counts", Finish::kStream, [&] {
+        RadixArgs a{};
+        VS_TRY(st.in(src, values, dtype, plan.rows_per_chunk, c.dev, c.s, &a.s));
+        uint32_t* d_p;
+        int32_t* d_n;
+        int64_t *d_c, *d_m;
+        VS_TRY(st_p.in(slot_prefix, (size_t)B * R, c.dev, true, c.s, &d_p));
+        VS_TRY(st_n.in(n_slots, (size_t)B, c.dev, true, c.s, &d_n));
+        VS_TRY(st_c.in(counts, level_counts(B, R, level), c.dev, false, c.s, &d_c));
+        VS_TRY(st_m.in(missing, (size_t)B, c.dev, false, c.s, &d_m));
+        a.level = level;
+        a.R = R;
+        a.slot_prefix = d_p;
+        a.n_slots = d_n;
+        a.counts = reinterpret_cast<unsigned long long*>(d_c);
+        a.missing = reinterpret_cast<unsigned long long*>(d_m);
+        return radix_counts_launch(a, plan, c.s);
+    }, [&] {
+        VS_TRY(st_c.back(c.s));
+        return st_m.back(c.s);
+    });
+}
+
+// vs_value_quantiles and vs_index_value_quantiles: every level's counts and steps on the set's device
+int value_quantiles(const SetSrc& src, const void* values, int dtype, const double* q, int method, const int64_t* ranks, int32_t R,
+                    int64_t rows_per_chunk, void* out_values, int64_t* out_ranks, int64_t* count, int64_t* missing, void* stream) {
+    ValuePlan plan;
+    VS_TRY(check_quant_set(src, values, dtype, R, rows_per_chunk, out_values && out_ranks && count && missing, &plan));
+    VS_TRY(check_ranks_arg(q, method, ranks, src.B, R));
+    VS_TRY(src.device_ok());
     if (q) ranks = nullptr;
-    const void* ptrs[9] = {words, and_user, values, q, ranks, out_values, out_ranks, count, missing};
-    const char* names[9] = {"words", "and_words", "values", "q", "ranks", "out_values", "out_ranks", "count", "missing"};
-    bool dev = false;
-    VS_TRY(pointers_kind(ptrs, names, 9, device, &dev));
-    VS_HIP(hipSetDevice(device));
-    hipStream_t s = (hipStream_t)stream;
+    Call c;
+    VS_TRY(c.open(src.device, stream, {{"words", src.words}, {"and_words", src.and_user}, {"values", values}, {"q", q}, {"ranks", ranks},
+                                       {"out_values", out_values}, {"out_ranks", out_ranks}, {"count", count}, {"missing", missing}}));
+    const int32_t B = src.B;
     SetStage st;
     Staged st_q, st_r, st_v, st_o, st_c, st_m;
-    RadixArgs ca{};
-    StepArgs sa{};
-    VS_TRY(st.in(words, bit0, ld_words, and_user, and_dev, B, values, dtype, n_rows, plan.rows_per_chunk, dev, s, &ca.s));
-    double* d_q;
-    int64_t *d_r, *d_m;
-    VS_TRY(st_q.in(q, (size_t)R, dev, true, s, &d_q));
-    VS_TRY(st_r.in(ranks, (size_t)B * R, dev, true, s, &d_r));
-    VS_TRY(st_v.in(static_cast<uint32_t*>(out_values), (size_t)B * R, dev, false, s, &sa.out_values));
-    VS_TRY(st_o.in(out_ranks, (size_t)B * R, dev, false, s, &sa.out_ranks));
-    VS_TRY(st_c.in(count, (size_t)B, dev, false, s, &sa.count));
-    VS_TRY(st_m.in(missing, (size_t)B, dev, false, s, &d_m));
-    // scratch: the counts of a level, then the step's state
-    const size_t n_cnt = (size_t)B * (size_t)R * VS_VALUE_RADIX_BINS, n_br = (size_t)B * (size_t)R;
-    DevBuf scratch;
-    VS_TRY(scratch.alloc(n_cnt * 8 + n_br * 8 + 3 * n_br * 4 + (size_t)B * 4));
-    unsigned long long* d_counts = scratch.as<unsigned long long>();
-    sa.rank_res = reinterpret_cast<int64_t*>(d_counts + n_cnt);
-    sa.rank_slot = reinterpret_cast<int32_t*>(sa.rank_res + n_br);
-    sa.rank_prefix = reinterpret_cast<uint32_t*>(sa.rank_slot + n_br);
-    sa.slot_prefix = sa.rank_prefix + n_br;
-    sa.n_slots = reinterpret_cast<int32_t*>(sa.slot_prefix + n_br);
-    sa.method = method;
-    sa.dtype = dtype;
-    sa.B = B;
-    sa.R = R;
-    sa.counts = reinterpret_cast<const int64_t*>(d_counts);
-    sa.q = d_q;
-    sa.ranks = d_r;
-    ca.R = R;
-    ca.slot_prefix = sa.slot_prefix;
-    ca.n_slots = sa.n_slots;
-    ca.counts = d_counts;
-    ca.missing = reinterpret_cast<unsigned long long*>(d_m);
-    int rc = VS_OK;
-    for (int level = 0; level < VS_VALUE_RADIX_LEVELS && rc == VS_OK; ++level) {
-        ca.level = sa.level = level;
-        rc = radix_counts_launch(ca, plan, s);
-        if (rc == VS_OK) rc = radix_step_launch(sa, s);
-    }
-    if (rc != VS_OK) {
-        (void)hipStreamSynchronize(s);                              // the scratch and the staging buffers die here
-        return rc;
-    }
-    VS_TRY(launch_failed("value_quantiles", s));
-    VS_STAGE("value_quantiles", s);
-    if (!dev) {
-        VS_TRY(st_v.back(s));
-        VS_TRY(st_o.back(s));
-        VS_TRY(st_c.back(s));
-        VS_TRY(st_m.back(s));
-    }
-    VS_HIP(hipStreamSynchronize(s));                                // the scratch is freed before the call returns
-    if (Profiler::get().on) Profiler::get().drain();
-    return VS_OK;
+    DevBuf scratch;                                               // the counts of a level, then the step's state
+    return c.run("value_quantiles", Finish::kSync, [&] {
+        RadixArgs ca{};
+        StepArgs sa{};
+        VS_TRY(st.in(src, values, dtype, plan.rows_per_chunk, c.dev, c.s, &ca.s));
+        double* d_q;
+        int64_t *d_r, *d_m;
+        VS_TRY(st_q.in(q, (size_t)R, c.dev, true, c.s, &d_q));
+        VS_TRY(st_r.in(ranks, (size_t)B * R, c.dev, true, c.s, &d_r));
+        VS_TRY(st_v.in(static_cast<uint32_t*>(out_values), (size_t)B * R, c.dev, false, c.s, &sa.out_values));
+        VS_TRY(st_o.in(out_ranks, (size_t)B * R, c.dev, false, c.s, &sa.out_ranks));
+        VS_TRY(st_c.in(count, (size_t)B, c.dev, false, c.s, &sa.count));
+        VS_TRY(st_m.in(missing, (size_t)B, c.dev, false, c.s, &d_m));
+        const size_t n_cnt = (size_t)B * (size_t)R * VS_VALUE_RADIX_BINS, n_br = (size_t)B * (size_t)R;
+        VS_TRY(scratch.alloc(n_cnt * 8 + n_br * 8 + 3 * n_br * 4 + (size_t)B * 4));
+        unsigned long long* d_counts = scratch.as<unsigned long long>();
+        sa.rank_res = reinterpret_cast<int64_t*>(d_counts + n_cnt);
+        sa.rank_slot = reinterpret_cast<int32_t*>(sa.rank_res + n_br);
+        sa.rank_prefix = reinterpret_cast<uint32_t*>(sa.rank_slot + n_br);
+        sa.slot_prefix = sa.rank_prefix + n_br;
+        sa.n_slots = reinterpret_cast<int32_t*>(sa.slot_prefix + n_br);
+        sa.method = method;
+        sa.dtype = dtype;
+        sa.B = B;
+        sa.R = R;
+        sa.counts = reinterpret_cast<const int64_t*>(d_counts);
+        sa.q = d_q;
+        sa.ranks = d_r;
+        ca.R = R;
+        ca.slot_prefix = sa.slot_prefix;
+        ca.n_slots = sa.n_slots;
+        ca.counts = d_counts;
+        ca.missing = reinterpret_cast<unsigned long long*>(d_m);
+        for (int level = 0; level < VS_VALUE_RADIX_LEVELS; ++level) {
+            ca.level = sa.level = level;
+            VS_TRY(radix_counts_launch(ca, plan, c.s));
+            VS_TRY(radix_step_launch(sa, c.s));
+        }
+        return VS_OK;
+    }, [&] {
+        VS_TRY(st_v.back(c.s));
+        VS_TRY(st_o.back(c.s));
+        VS_TRY(st_c.back(c.s));
+        return st_m.back(c.s);
+    });
 }
 
 }  // namespace
@@ -427,57 +415,31 @@ extern "C" int vs_value_quantile_plan(int64_t n_rows, int32_t B, int32_t R, int 
 extern "C" int vs_value_quantiles(const uint32_t* words, int64_t bit0, int64_t ld_words, const uint32_t* and_words, int32_t B, const void* values,
                                   int dtype, int64_t n_rows, const double* q, int method, const int64_t* ranks, int32_t R, int64_t rows_per_chunk,
                                   void* out_values, int64_t* out_ranks, int64_t* count, int64_t* missing, int device, void* stream) {
-    ValuePlan plan;
-    VS_TRY(check_quant_set(words, bit0, ld_words, B, values, dtype, n_rows, R, rows_per_chunk, out_values && out_ranks && count && missing, &plan));
-    VS_TRY(check_ranks_arg(q, method, ranks, B, R));
-    VS_TRY(device_in_range(device));
-    return quantiles_call(device, words, bit0, ld_words, and_words, nullptr, B, values, dtype, n_rows, q, method, ranks, R, plan, out_values, out_ranks,
-                          count, missing, stream);
+    return value_quantiles(free_set(words, bit0, ld_words, and_words, B, n_rows, device), values, dtype, q, method, ranks, R, rows_per_chunk, out_values,
+                           out_ranks, count, missing, stream);
 }
 
 extern "C" int vs_index_value_quantiles(vs_index* idx, const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B, const void* values,
                                         int dtype, const double* q, int method, const int64_t* ranks, int32_t R, int64_t rows_per_chunk,
                                         void* out_values, int64_t* out_ranks, int64_t* count, int64_t* missing, void* stream) {
-    if (!idx) return fail(VS_EINVAL, "NULL argument");
-    ValuePlan plan;
-    VS_TRY(check_quant_set(words, bit0, ld_words, B, values, dtype, idx->n_rows, R, rows_per_chunk, out_values && out_ranks && count && missing,
-                           &plan));
-    VS_TRY(check_ranks_arg(q, method, ranks, B, R));
-    // tombstones are ANDed in, as every search does (the live bitmap starts at bit 0 whatever bit0 is)
-    return quantiles_call(idx->device, words, bit0, ld_words, nullptr, live_words(idx), B, values, dtype, idx->n_rows, q, method, ranks, R, plan,
-                          out_values, out_ranks, count, missing, stream);
+    SetSrc src;
+    VS_TRY(index_set(idx, words, bit0, ld_words, B, &src));
+    return value_quantiles(src, values, dtype, q, method, ranks, R, rows_per_chunk, out_values, out_ranks, count, missing, stream);
 }
-
-namespace {
-int check_counts_arg(int level, const uint32_t* slot_prefix, const int32_t* n_slots, const int64_t* missing) {
-    char msg[256];
-    VS_TRY(plan_or_fail(quantile_check_level(level, msg, sizeof msg), msg));
-    if (level == 0 ? !missing : (!slot_prefix || !n_slots)) return fail(VS_EINVAL, "NULL argument: level %d needs %s", level,
-                                                                        level == 0 ? "missing" : "slot_prefix and n_slots");
-    return VS_OK;
-}
-}  // namespace
 
 extern "C" int vs_value_radix_counts(const uint32_t* words, int64_t bit0, int64_t ld_words, const uint32_t* and_words, int32_t B, const void* values,
                                      int dtype, int64_t n_rows, int level, int32_t R, const uint32_t* slot_prefix, const int32_t* n_slots,
                                      int64_t rows_per_chunk, int64_t* counts, int64_t* missing, int device, void* stream) {
-    ValuePlan plan;
-    VS_TRY(check_quant_set(words, bit0, ld_words, B, values, dtype, n_rows, R, rows_per_chunk, counts != nullptr, &plan));
-    VS_TRY(check_counts_arg(level, slot_prefix, n_slots, missing));
-    VS_TRY(device_in_range(device));
-    return counts_call(device, words, bit0, ld_words, and_words, nullptr, B, values, dtype, n_rows, level, R, slot_prefix, n_slots, plan, counts, missing,
-                       stream);
+    return radix_counts(free_set(words, bit0, ld_words, and_words, B, n_rows, device), values, dtype, level, R, slot_prefix, n_slots, rows_per_chunk,
+                        counts, missing, stream);
 }
 
 extern "C" int vs_index_value_radix_counts(vs_index* idx, const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B, const void* values,
                                            int dtype, int level, int32_t R, const uint32_t* slot_prefix, const int32_t* n_slots,
                                            int64_t rows_per_chunk, int64_t* counts, int64_t* missing, void* stream) {
-    if (!idx) return fail(VS_EINVAL, "NULL argument");
-    ValuePlan plan;
-    VS_TRY(check_quant_set(words, bit0, ld_words, B, values, dtype, idx->n_rows, R, rows_per_chunk, counts != nullptr, &plan));
-    VS_TRY(check_counts_arg(level, slot_prefix, n_slots, missing));
-    return counts_call(idx->device, words, bit0, ld_words, nullptr, live_words(idx), B, values, dtype, idx->n_rows, level, R, slot_prefix, n_slots, plan,
-                       counts, missing, stream);
+    SetSrc src;
+    VS_TRY(index_set(idx, words, bit0, ld_words, B, &src));
+    return radix_counts(src, values, dtype, level, R, slot_prefix, n_slots, rows_per_chunk, counts, missing, stream);
 }
 
 extern "C" int vs_value_radix_step(int level, const int64_t* counts, int32_t B, int32_t R, const double* q, int method, const int64_t* ranks,
@@ -524,7 +486,5 @@ extern "C" int vs_value_radix_step(int level, const int64_t* counts, int32_t B, 
     a.out_ranks = out_ranks;
     a.out_values = static_cast<uint32_t*>(out_values);
     VS_TRY(radix_step_launch(a, s));
-    VS_TRY(launch_failed("value_radix_step", s));
-    VS_STAGE("value_radix_step", s);
-    return finish_call(true, stream, s);
+    return close_call("value_radix_step", true, stream, s, Finish::kStream, [] { return VS_OK; });
 }

@@ -275,123 +275,97 @@ __global__ __launch_bounds__(kSetThreads) void set_invert_kernel(FromIdsArgs a) 
 // ---- host side -------------------------------------------------------------------------------------------------------------------------------
 unsigned grid_over(int64_t items) { return (unsigned)std::min<int64_t>(std::max<int64_t>(1, ceil_div64(items, kSetThreads)), 65535 * 16); }
 
-int launch_failed(const char* what, hipStream_t s) {
-    const hipError_t le = hipGetLastError();
-    if (le == hipSuccess) return VS_OK;
-    (void)hipStreamSynchronize(s);                                  // staging buffers and the scratch die here
-    return fail(VS_EHIP, "%s launch failed: %s", what, hipGetErrorString(le));
-}
-
-// One count (limit = 0, out_ids NULL) or ids call on `device`.  and_user: a caller's second bitmap (of the kind of the other pointers, at
-// bit0); and_dev: a device bitmap at bit 0 (an index's live rows).  At most one of the two.
-int ids_call(int device, const uint32_t* words, int64_t bit0, int64_t ld_words, const uint32_t* and_user, const uint32_t* and_dev, int32_t B,
-             int64_t n_rows, const int64_t* offsets, int64_t limit, int64_t id_offset, const SetListPlan& plan, int64_t* out_ids, int64_t* out_counts,
-             void* stream) {
-    const void* ptrs[5] = {words, and_user, offsets, out_ids, out_counts};
-    const char* names[5] = {"words", "and_words", "offsets", "out_ids", "out_counts"};
-    bool dev = false;
-    VS_TRY(pointers_kind(ptrs, names, 5, device, &dev));
-    VS_HIP(hipSetDevice(device));
-    hipStream_t s = (hipStream_t)stream;
+// vs_set_count (limit = 0, out_ids NULL), vs_set_ids and their vs_index_* forms: one call on the set's device.  Host arrays are looked at before
+// the device is (a pointer the runtime does not know, or no runtime at all: a host pointer).
+int set_ids(const SetSrc& src, const int64_t* offsets, int64_t limit, int64_t id_offset, int64_t rows_per_chunk, int64_t* out_ids,
+            int64_t* out_counts, void* stream) {
+    SetListPlan plan;
+    char msg[256];
+    VS_TRY(plan_or_fail(set_list_check_set(out_counts != nullptr, src.words != nullptr, src.bit0, src.ld_words, src.B, src.n_rows, rows_per_chunk, &plan,
+                                           msg, sizeof msg), msg));
+    VS_TRY(plan_or_fail(set_list_check_ids(limit, src.B, out_ids != nullptr, msg, sizeof msg), msg));
+    if (offsets && !is_device_ptr(offsets)) VS_TRY(plan_or_fail(set_list_check_offsets_host(offsets, src.B, msg, sizeof msg), msg));
+    VS_TRY(src.device_ok());
+    if (!limit) out_ids = nullptr;
+    Call c;
+    VS_TRY(c.open(src.device, stream, {{"words", src.words}, {"and_words", src.and_user}, {"offsets", offsets}, {"out_ids", out_ids},
+                                       {"out_counts", out_counts}}));
+    const int32_t B = src.B;
     BitmapStage st;
     Staged st_off, st_ids, st_cnt;
     DevBuf scratch;
-    ListArgs a{};
-    int64_t* d_off;
-    VS_TRY(st.in(words, bit0, ld_words, and_user, and_dev, B, n_rows, plan.rows_per_chunk, dev, s, &a.set));
-    VS_TRY(st_off.in(offsets, (size_t)B, dev, true, s, &d_off));
-    VS_TRY(st_ids.in(out_ids, (size_t)B * (size_t)limit, dev, false, s, &a.out_ids));
-    VS_TRY(st_cnt.in(out_counts, (size_t)B, dev, false, s, &a.out_counts));
-    const size_t cells = (size_t)B * (size_t)plan.spans;
-    VS_TRY(scratch.alloc(cells * (limit ? 12 : 4)));               // the bases (8-byte aligned: first), then the counts
-    a.span_base = limit ? scratch.as<int64_t>() : nullptr;
-    a.span_count = reinterpret_cast<uint32_t*>(scratch.as<char>() + (limit ? cells * 8 : 0));
-    a.spans = plan.spans;
-    a.offsets = d_off;
-    a.limit = limit;
-    a.id_offset = id_offset;
     const char* name = limit ? "set_ids" : "set_count";
-    {
-        ProfScope prof(name, s);
+    return c.run(name, Finish::kSync, [&] {
+        ListArgs a{};
+        int64_t* d_off;
+        VS_TRY(st.in(src, plan.rows_per_chunk, c.dev, c.s, &a.set));
+        VS_TRY(st_off.in(offsets, (size_t)B, c.dev, true, c.s, &d_off));
+        VS_TRY(st_ids.in(out_ids, (size_t)B * (size_t)limit, c.dev, false, c.s, &a.out_ids));
+        VS_TRY(st_cnt.in(out_counts, (size_t)B, c.dev, false, c.s, &a.out_counts));
+        const size_t cells = (size_t)B * (size_t)plan.spans;
+        VS_TRY(scratch.alloc(cells * (limit ? 12 : 4)));           // the bases (8-byte aligned: first), then the counts
+        a.span_base = limit ? scratch.as<int64_t>() : nullptr;
+        a.span_count = reinterpret_cast<uint32_t*>(scratch.as<char>() + (limit ? cells * 8 : 0));
+        a.spans = plan.spans;
+        a.offsets = d_off;
+        a.limit = limit;
+        a.id_offset = id_offset;
+        ProfScope prof(name, c.s);
         const dim3 grid((unsigned)plan.chunks, (unsigned)B);
-        hipLaunchKernelGGL(set_count_kernel, grid, dim3(kSetThreads), 0, s, a);
-        hipLaunchKernelGGL(set_scan_kernel, dim3((unsigned)B), dim3(kSetThreads), 0, s, a);
+        hipLaunchKernelGGL(set_count_kernel, grid, dim3(kSetThreads), 0, c.s, a);
+        hipLaunchKernelGGL(set_scan_kernel, dim3((unsigned)B), dim3(kSetThreads), 0, c.s, a);
         if (limit) {
-            hipLaunchKernelGGL(set_write_kernel, grid, dim3(kSetThreads), 0, s, a);
-            hipLaunchKernelGGL(set_tail_kernel, dim3(grid_over(limit), (unsigned)B), dim3(kSetThreads), 0, s, a);
+            hipLaunchKernelGGL(set_write_kernel, grid, dim3(kSetThreads), 0, c.s, a);
+            hipLaunchKernelGGL(set_tail_kernel, dim3(grid_over(limit), (unsigned)B), dim3(kSetThreads), 0, c.s, a);
         }
-    }
-    VS_TRY(launch_failed(name, s));
-    VS_STAGE(name, s);
-    if (!dev) {
-        VS_TRY(st_ids.back(s));
-        VS_TRY(st_cnt.back(s));
-    }
-    VS_HIP(hipStreamSynchronize(s));                                // the scratch is freed before the call returns
-    if (Profiler::get().on) Profiler::get().drain();
-    return VS_OK;
+        return VS_OK;
+    }, [&] {
+        VS_TRY(st_ids.back(c.s));
+        return st_cnt.back(c.s);
+    });
 }
 
-int sample_call(int device, const uint32_t* words, int64_t bit0, int64_t ld_words, const uint32_t* and_user, const uint32_t* and_dev, int32_t B,
-                int64_t n_rows, const uint64_t* seeds, int32_t n, int64_t id_offset, const SetListPlan& plan, int64_t* out_ids, uint32_t* out_hash,
-                int64_t* out_counts, void* stream) {
-    const void* ptrs[6] = {words, and_user, seeds, out_ids, out_hash, out_counts};
-    const char* names[6] = {"words", "and_words", "seeds", "out_ids", "out_hash", "out_counts"};
-    bool dev = false;
-    VS_TRY(pointers_kind(ptrs, names, 6, device, &dev));
-    VS_HIP(hipSetDevice(device));
-    hipStream_t s = (hipStream_t)stream;
+// vs_set_sample and vs_index_set_sample
+int set_sample(const SetSrc& src, const uint64_t* seeds, int32_t n, int64_t id_offset, int64_t rows_per_chunk, int64_t* out_ids, uint32_t* out_hash,
+               int64_t* out_counts, void* stream) {
+    SetListPlan plan;
+    char msg[256];
+    VS_TRY(plan_or_fail(set_list_check_set(seeds && out_ids && out_counts, src.words != nullptr, src.bit0, src.ld_words, src.B, src.n_rows,
+                                           rows_per_chunk, &plan, msg, sizeof msg), msg));
+    VS_TRY(plan_or_fail(set_list_check_sample(n, src.B, plan, msg, sizeof msg), msg));
+    VS_TRY(src.device_ok());
+    Call c;
+    VS_TRY(c.open(src.device, stream, {{"words", src.words}, {"and_words", src.and_user}, {"seeds", seeds}, {"out_ids", out_ids},
+                                       {"out_hash", out_hash}, {"out_counts", out_counts}}));
+    const int32_t B = src.B;
     BitmapStage st;
     Staged st_seed, st_ids, st_hash, st_cnt;
     DevBuf scratch;
-    SampleArgs a{};
-    uint64_t* d_seed;
-    VS_TRY(st.in(words, bit0, ld_words, and_user, and_dev, B, n_rows, plan.rows_per_chunk, dev, s, &a.set));
-    VS_TRY(st_seed.in(seeds, (size_t)B, dev, true, s, &d_seed));
-    VS_TRY(st_ids.in(out_ids, (size_t)B * n, dev, false, s, &a.out_ids));
-    VS_TRY(st_hash.in(out_hash, (size_t)B * n, dev, false, s, &a.out_hash));
-    VS_TRY(st_cnt.in(out_counts, (size_t)B, dev, false, s, &a.out_counts));
-    const size_t lists = (size_t)B * (size_t)plan.chunks;
-    VS_TRY(scratch.alloc(lists * (size_t)n * 8 + lists * 4));      // the keys, then the chunks' counts
-    a.seeds = d_seed;
-    a.n = n;
-    a.chunks = plan.chunks;
-    a.scratch = scratch.as<uint64_t>();
-    a.chunk_count = reinterpret_cast<uint32_t*>(a.scratch + lists * (size_t)n);
-    a.id_offset = id_offset;
-    {
-        ProfScope prof("set_sample", s);
-        hipLaunchKernelGGL(set_sample_chunk_kernel, dim3((unsigned)plan.chunks, (unsigned)B), dim3(kSetThreads), 0, s, a);
-        hipLaunchKernelGGL(set_sample_merge_kernel, dim3((unsigned)B), dim3(kSetThreads), 0, s, a);
-    }
-    VS_TRY(launch_failed("set_sample", s));
-    VS_STAGE("set_sample", s);
-    if (!dev) {
-        VS_TRY(st_ids.back(s));
-        VS_TRY(st_hash.back(s));
-        VS_TRY(st_cnt.back(s));
-    }
-    VS_HIP(hipStreamSynchronize(s));                                // the scratch is freed before the call returns
-    if (Profiler::get().on) Profiler::get().drain();
-    return VS_OK;
-}
-
-// host arrays are looked at before the device is (a pointer the runtime does not know, or no runtime at all: a host pointer)
-int check_ids(const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B, int64_t n_rows, const int64_t* offsets, int64_t limit,
-              int64_t rows_per_chunk, const int64_t* out_ids, const int64_t* out_counts, SetListPlan* plan) {
-    char msg[256];
-    VS_TRY(plan_or_fail(set_list_check_set(out_counts != nullptr, words != nullptr, bit0, ld_words, B, n_rows, rows_per_chunk, plan, msg, sizeof msg), msg));
-    VS_TRY(plan_or_fail(set_list_check_ids(limit, B, out_ids != nullptr, msg, sizeof msg), msg));
-    if (offsets && !is_device_ptr(offsets)) VS_TRY(plan_or_fail(set_list_check_offsets_host(offsets, B, msg, sizeof msg), msg));
-    return VS_OK;
-}
-
-int check_sample(const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B, int64_t n_rows, const uint64_t* seeds, int32_t n,
-                 int64_t rows_per_chunk, const int64_t* out_ids, const int64_t* out_counts, SetListPlan* plan) {
-    char msg[256];
-    VS_TRY(plan_or_fail(set_list_check_set(seeds && out_ids && out_counts, words != nullptr, bit0, ld_words, B, n_rows, rows_per_chunk, plan, msg,
-                                           sizeof msg), msg));
-    return plan_or_fail(set_list_check_sample(n, B, *plan, msg, sizeof msg), msg);
+    return c.run("set_sample", Finish::kSync, [&] {
+        SampleArgs a{};
+        uint64_t* d_seed;
+        VS_TRY(st.in(src, plan.rows_per_chunk, c.dev, c.s, &a.set));
+        VS_TRY(st_seed.in(seeds, (size_t)B, c.dev, true, c.s, &d_seed));
+        VS_TRY(st_ids.in(out_ids, (size_t)B * n, c.dev, false, c.s, &a.out_ids));
+        VS_TRY(st_hash.in(out_hash, (size_t)B * n, c.dev, false, c.s, &a.out_hash));
+        VS_TRY(st_cnt.in(out_counts, (size_t)B, c.dev, false, c.s, &a.out_counts));
+        const size_t lists = (size_t)B * (size_t)plan.chunks;
+        VS_TRY(scratch.alloc(lists * (size_t)n * 8 + lists * 4));  // the keys, then the chunks' counts
+        a.seeds = d_seed;
+        a.n = n;
+        a.chunks = plan.chunks;
+        a.scratch = scratch.as<uint64_t>();
+        a.chunk_count = reinterpret_cast<uint32_t*>(a.scratch + lists * (size_t)n);
+        a.id_offset = id_offset;
+        ProfScope prof("set_sample", c.s);
+        hipLaunchKernelGGL(set_sample_chunk_kernel, dim3((unsigned)plan.chunks, (unsigned)B), dim3(kSetThreads), 0, c.s, a);
+        hipLaunchKernelGGL(set_sample_merge_kernel, dim3((unsigned)B), dim3(kSetThreads), 0, c.s, a);
+        return VS_OK;
+    }, [&] {
+        VS_TRY(st_ids.back(c.s));
+        VS_TRY(st_hash.back(c.s));
+        return st_cnt.back(c.s);
+    });
 }
 
 }  // namespace
@@ -412,56 +386,42 @@ extern "C" int vs_set_list_plan(int64_t n_rows, int32_t B, int per_query, int64_
 
 extern "C" int vs_set_count(const uint32_t* words, int64_t bit0, int64_t ld_words, const uint32_t* and_words, int32_t B, int64_t n_rows,
                             int64_t rows_per_chunk, int64_t* out_counts, int device, void* stream) {
-    SetListPlan plan;
-    VS_TRY(check_ids(words, bit0, ld_words, B, n_rows, nullptr, 0, rows_per_chunk, nullptr, out_counts, &plan));
-    VS_TRY(device_in_range(device));
-    return ids_call(device, words, bit0, ld_words, and_words, nullptr, B, n_rows, nullptr, 0, 0, plan, nullptr, out_counts, stream);
+    return set_ids(free_set(words, bit0, ld_words, and_words, B, n_rows, device), nullptr, 0, 0, rows_per_chunk, nullptr, out_counts, stream);
 }
 
 extern "C" int vs_index_set_count(vs_index* idx, const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B, int64_t rows_per_chunk,
                                   int64_t* out_counts, void* stream) {
-    if (!idx) return fail(VS_EINVAL, "NULL argument");
-    SetListPlan plan;
-    VS_TRY(check_ids(words, bit0, ld_words, B, idx->n_rows, nullptr, 0, rows_per_chunk, nullptr, out_counts, &plan));
-    return ids_call(idx->device, words, bit0, ld_words, nullptr, live_words(idx), B, idx->n_rows, nullptr, 0, 0, plan, nullptr, out_counts, stream);
+    SetSrc src;
+    VS_TRY(index_set(idx, words, bit0, ld_words, B, &src));
+    return set_ids(src, nullptr, 0, 0, rows_per_chunk, nullptr, out_counts, stream);
 }
 
 extern "C" int vs_set_ids(const uint32_t* words, int64_t bit0, int64_t ld_words, const uint32_t* and_words, int32_t B, int64_t n_rows,
                           const int64_t* offsets, int64_t limit, int64_t id_offset, int64_t rows_per_chunk, int64_t* out_ids, int64_t* out_counts,
                           int device, void* stream) {
-    SetListPlan plan;
-    VS_TRY(check_ids(words, bit0, ld_words, B, n_rows, offsets, limit, rows_per_chunk, out_ids, out_counts, &plan));
-    VS_TRY(device_in_range(device));
-    return ids_call(device, words, bit0, ld_words, and_words, nullptr, B, n_rows, offsets, limit, id_offset, plan, limit ? out_ids : nullptr, out_counts,
-                    stream);
+    return set_ids(free_set(words, bit0, ld_words, and_words, B, n_rows, device), offsets, limit, id_offset, rows_per_chunk, out_ids, out_counts, stream);
 }
 
 extern "C" int vs_index_set_ids(vs_index* idx, const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B, const int64_t* offsets, int64_t limit,
                                 int64_t id_offset, int64_t rows_per_chunk, int64_t* out_ids, int64_t* out_counts, void* stream) {
-    if (!idx) return fail(VS_EINVAL, "NULL argument");
-    SetListPlan plan;
-    VS_TRY(check_ids(words, bit0, ld_words, B, idx->n_rows, offsets, limit, rows_per_chunk, out_ids, out_counts, &plan));
-    return ids_call(idx->device, words, bit0, ld_words, nullptr, live_words(idx), B, idx->n_rows, offsets, limit, id_offset, plan,
-                    limit ? out_ids : nullptr, out_counts, stream);
+    SetSrc src;
+    VS_TRY(index_set(idx, words, bit0, ld_words, B, &src));
+    return set_ids(src, offsets, limit, id_offset, rows_per_chunk, out_ids, out_counts, stream);
 }
 
 extern "C" int vs_set_sample(const uint32_t* words, int64_t bit0, int64_t ld_words, const uint32_t* and_words, int32_t B, int64_t n_rows,
                              const uint64_t* seeds, int32_t n, int64_t id_offset, int64_t rows_per_chunk, int64_t* out_ids, uint32_t* out_hash,
                              int64_t* out_counts, int device, void* stream) {
-    SetListPlan plan;
-    VS_TRY(check_sample(words, bit0, ld_words, B, n_rows, seeds, n, rows_per_chunk, out_ids, out_counts, &plan));
-    VS_TRY(device_in_range(device));
-    return sample_call(device, words, bit0, ld_words, and_words, nullptr, B, n_rows, seeds, n, id_offset, plan, out_ids, out_hash, out_counts, stream);
+    return set_sample(free_set(words, bit0, ld_words, and_words, B, n_rows, device), seeds, n, id_offset, rows_per_chunk, out_ids, out_hash, out_counts,
+                      stream);
 }
 
 extern "C" int vs_index_set_sample(vs_index* idx, const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B, const uint64_t* seeds, int32_t n,
                                    int64_t id_offset, int64_t rows_per_chunk, int64_t* out_ids, uint32_t* out_hash, int64_t* out_counts,
                                    void* stream) {
-    if (!idx) return fail(VS_EINVAL, "NULL argument");
-    SetListPlan plan;
-    VS_TRY(check_sample(words, bit0, ld_words, B, idx->n_rows, seeds, n, rows_per_chunk, out_ids, out_counts, &plan));
-    return sample_call(idx->device, words, bit0, ld_words, nullptr, live_words(idx), B, idx->n_rows, seeds, n, id_offset, plan, out_ids, out_hash,
-                       out_counts, stream);
+    SetSrc src;
+    VS_TRY(index_set(idx, words, bit0, ld_words, B, &src));
+    return set_sample(src, seeds, n, id_offset, rows_per_chunk, out_ids, out_hash, out_counts, stream);
 }
 
 extern "C" int vs_set_from_ids(const int64_t* ids, int32_t B, int64_t m, int64_t ld_ids, int64_t n_rows, int64_t bit0, int allow, uint32_t* out_words,
@@ -470,34 +430,27 @@ extern "C" int vs_set_from_ids(const int64_t* ids, int32_t B, int64_t m, int64_t
     VS_TRY(plan_or_fail(set_list_check_from_ids(ids != nullptr, out_words != nullptr, B, m, ld_ids, n_rows, bit0, ld_words, msg, sizeof msg), msg));
     if (m > 0 && !is_device_ptr(ids)) VS_TRY(plan_or_fail(set_list_check_id_lists_host(ids, B, m, ld_ids, n_rows, msg, sizeof msg), msg));
     VS_TRY(device_in_range(device));
-    const void* ptrs[2] = {m > 0 ? ids : nullptr, out_words};
-    const char* names[2] = {"ids", "out_words"};
-    bool dev = false;
-    VS_TRY(pointers_kind(ptrs, names, 2, device, &dev));
-    VS_HIP(hipSetDevice(device));
-    hipStream_t s = (hipStream_t)stream;
-    FromIdsArgs a{};
-    a.m = m;
-    a.ld_ids = ld_ids;
-    a.n_rows = n_rows;
-    a.bit0 = bit0;
-    a.n_words = (bit0 + n_rows + 31) >> 5;
-    a.ld_words = ld_words;
+    Call c;
+    VS_TRY(c.open(device, stream, {{"ids", m > 0 ? ids : nullptr}, {"out_words", out_words}}));
     Staged st_i, st_o;
-    int64_t* d_i = nullptr;
-    if (m > 0) VS_TRY(st_i.in(ids, (size_t)(B - 1) * (size_t)ld_ids + (size_t)m, dev, true, s, &d_i));
-    // (a host buffer's gaps between the rows come back as they went in: the staged copy starts from the caller's words)
-    VS_TRY(st_o.in(out_words, (size_t)(B - 1) * (size_t)ld_words + (size_t)a.n_words, dev, true, s, &a.out));
-    a.ids = d_i;
-    if (ld_words == a.n_words || B == 1) VS_HIP(hipMemsetAsync(a.out, 0, ((size_t)(B - 1) * (size_t)ld_words + (size_t)a.n_words) * 4, s));
-    else VS_HIP(hipMemset2DAsync(a.out, (size_t)ld_words * 4, 0, (size_t)a.n_words * 4, (size_t)B, s));
-    {
-        ProfScope prof("set_from_ids", s);
-        if (m > 0) hipLaunchKernelGGL(set_scatter_kernel, dim3(std::min(grid_over(m), 65535u), (unsigned)B), dim3(kSetThreads), 0, s, a);
-        if (!allow) hipLaunchKernelGGL(set_invert_kernel, dim3(std::min(grid_over(a.n_words), 65535u), (unsigned)B), dim3(kSetThreads), 0, s, a);
-    }
-    VS_TRY(launch_failed("set_from_ids", s));
-    VS_STAGE("set_from_ids", s);
-    if (!dev) VS_TRY(st_o.back(s));
-    return finish_call(dev, stream, s);
+    return c.run("set_from_ids", Finish::kStream, [&] {
+        FromIdsArgs a{};
+        a.m = m;
+        a.ld_ids = ld_ids;
+        a.n_rows = n_rows;
+        a.bit0 = bit0;
+        a.n_words = (bit0 + n_rows + 31) >> 5;
+        a.ld_words = ld_words;
+        int64_t* d_i = nullptr;
+        if (m > 0) VS_TRY(st_i.in(ids, (size_t)(B - 1) * (size_t)ld_ids + (size_t)m, c.dev, true, c.s, &d_i));
+        // (a host buffer's gaps between the rows come back as they went in: the staged copy starts from the caller's words)
+        VS_TRY(st_o.in(out_words, (size_t)(B - 1) * (size_t)ld_words + (size_t)a.n_words, c.dev, true, c.s, &a.out));
+        a.ids = d_i;
+        if (ld_words == a.n_words || B == 1) VS_HIP(hipMemsetAsync(a.out, 0, ((size_t)(B - 1) * (size_t)ld_words + (size_t)a.n_words) * 4, c.s));
+        else VS_HIP(hipMemset2DAsync(a.out, (size_t)ld_words * 4, 0, (size_t)a.n_words * 4, (size_t)B, c.s));
+        ProfScope prof("set_from_ids", c.s);
+        if (m > 0) hipLaunchKernelGGL(set_scatter_kernel, dim3(std::min(grid_over(m), 65535u), (unsigned)B), dim3(kSetThreads), 0, c.s, a);
+        if (!allow) hipLaunchKernelGGL(set_invert_kernel, dim3(std::min(grid_over(a.n_words), 65535u), (unsigned)B), dim3(kSetThreads), 0, c.s, a);
+        return VS_OK;
+    }, [&] { return st_o.back(c.s); });
 }

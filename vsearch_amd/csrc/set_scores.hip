@@ -202,7 +202,7 @@ extern "C" int vs_index_set_scores(vs_index* idx, const void* q, int q_dtype, in
     Staged st_q;
     DevBuf st_out;
     SetScoreArgs a{};
-    VS_TRY(st.in(words, bit0, ld_words, nullptr, live_words(idx), B, n, plan.rows_per_chunk, dev, s, &a.set));
+    VS_TRY(st.in(index_set(*idx, words, bit0, ld_words, B), plan.rows_per_chunk, dev, s, &a.set));
     const size_t q_elems = (size_t)(B - 1) * (size_t)ldq + (size_t)idx->n_cols;
     const void* d_q = q;
     if (!dev) {
@@ -232,8 +232,8 @@ extern "C" int vs_index_set_scores(vs_index* idx, const void* q, int q_dtype, in
                                                      : launch_set_scores<VM_BIN>(a, grid, lds, s);
         VS_TRY(launch_rc(rcode, s));
     }
-    VS_STAGE("set_scores", s);
-    if (!dev)
+    return close_call("set_scores", dev, stream, s, Finish::kStream, [&] {
         VS_HIP(hipMemcpy2DAsync(out_scores, (size_t)ld_scores * 4, a.out, (size_t)n * 4, (size_t)n * 4, (size_t)B, hipMemcpyDeviceToHost, s));
-    return finish_call(dev, stream, s);
+        return VS_OK;
+    });
 }

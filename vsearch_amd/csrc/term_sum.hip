@@ -209,8 +209,8 @@ extern "C" int vs_term_sum_topn(const int64_t* sums, int64_t ld_sums, const int6
         hipLaunchKernelGGL(term_sum_topn_kernel, dim3((unsigned)B), dim3(kTopnThreads), 0, s, a);
         VS_HIP(hipGetLastError());
     }
-    VS_STAGE("term_sum_topn", s);
-    if (!dev)
+    return close_call("term_sum_topn", dev, stream, s, Finish::kStream, [&] {
         for (int i = 3; i < 6; ++i) VS_TRY(st[i].back(s));
-    return finish_call(dev, stream, s);
+        return VS_OK;
+    });
 }

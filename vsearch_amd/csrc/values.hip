@@ -288,146 +288,6 @@ __global__ __launch_bounds__(kValThreads) void value_topk_merge_kernel(TopArgs a
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------------------------
-// One stats call on `device`.  and_user: a caller's second bitmap (of the kind of the other pointers, at bit0); and_dev: a device bitmap at
-// bit 0 (an index's live rows).  At most one of the two.
-int stats_call(int device, const uint32_t* words, int64_t bit0, int64_t ld_words, const uint32_t* and_user, const uint32_t* and_dev, int32_t B,
-               const void* values, int dtype, int64_t n_rows, const ValuePlan& plan, int64_t* count, int64_t* missing, void* out_min, void* out_max,
-               int64_t* sum, void* stream) {
-    const void* ptrs[8] = {words, and_user, values, count, missing, out_min, out_max, sum};
-    const char* names[8] = {"words", "and_words", "values", "count", "missing", "out_min", "out_max", "sum"};
-    bool dev = false;
-    VS_TRY(pointers_kind(ptrs, names, 8, device, &dev));
-    VS_HIP(hipSetDevice(device));
-    hipStream_t s = (hipStream_t)stream;
-    SetStage st;
-    StatsArgs a{};
-    VS_TRY(st.in(words, bit0, ld_words, and_user, and_dev, B, values, dtype, n_rows, plan.rows_per_chunk, dev, s, &a.s));
-    DevBuf out;                                                   // host outputs: count, missing, sum [B] x 8 bytes, then min, max [B] x 4
-    if (dev) {
-        a.count = reinterpret_cast<unsigned long long*>(count);
-        a.missing = reinterpret_cast<unsigned long long*>(missing);
-        a.sum = reinterpret_cast<unsigned long long*>(sum);
-        a.min_key = static_cast<uint32_t*>(out_min);
-        a.max_key = static_cast<uint32_t*>(out_max);
-    } else {
-        VS_TRY(out.alloc((size_t)B * 32));
-        a.count = out.as<unsigned long long>();
-        a.missing = a.count + B;
-        a.sum = a.missing + B;
-        a.min_key = reinterpret_cast<uint32_t*>(a.sum + B);
-        a.max_key = a.min_key + B;
-    }
-    VS_HIP(hipMemsetAsync(a.count, 0, (size_t)B * 8, s));
-    VS_HIP(hipMemsetAsync(a.missing, 0, (size_t)B * 8, s));
-    VS_HIP(hipMemsetAsync(a.sum, 0, (size_t)B * 8, s));
-    VS_HIP(hipMemsetAsync(a.min_key, 0xFF, (size_t)B * 4, s));
-    VS_HIP(hipMemsetAsync(a.max_key, 0, (size_t)B * 4, s));
-    {
-        ProfScope prof("value_stats", s);
-        const dim3 grid((unsigned)plan.chunks, (unsigned)ceil_div64(B, plan.qt));
-        if (plan.qt == 8) hipLaunchKernelGGL(value_stats_kernel<8>, grid, dim3(kValThreads), 0, s, a);
-        else hipLaunchKernelGGL(value_stats_kernel<1>, grid, dim3(kValThreads), 0, s, a);
-        hipLaunchKernelGGL(value_finish_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, a.min_key, a.max_key, a.count, B, dtype);
-    }
-    const hipError_t le = hipGetLastError();
-    if (le != hipSuccess) {
-        (void)hipStreamSynchronize(s);                              // staging buffers die here
-        return fail(VS_EHIP, "value_stats launch failed: %s", hipGetErrorString(le));
-    }
-    VS_STAGE("value_stats", s);
-    if (!dev) {
-        VS_HIP(hipMemcpyAsync(count, a.count, (size_t)B * 8, hipMemcpyDeviceToHost, s));
-        VS_HIP(hipMemcpyAsync(missing, a.missing, (size_t)B * 8, hipMemcpyDeviceToHost, s));
-        VS_HIP(hipMemcpyAsync(sum, a.sum, (size_t)B * 8, hipMemcpyDeviceToHost, s));
-        VS_HIP(hipMemcpyAsync(out_min, a.min_key, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-        VS_HIP(hipMemcpyAsync(out_max, a.max_key, (size_t)B * 4, hipMemcpyDeviceToHost, s));
-    }
-    return finish_call(dev, stream, s);
-}
-
-int hist_call(int device, const uint32_t* words, int64_t bit0, int64_t ld_words, const uint32_t* and_user, const uint32_t* and_dev, int32_t B,
-              const void* values, int dtype, int64_t n_rows, const void* edges, int32_t n_edges, const ValuePlan& plan, int64_t* counts,
-              int64_t ld_counts, int64_t* below, int64_t* above, int64_t* missing, void* stream) {
-    const void* ptrs[8] = {words, and_user, values, edges, counts, below, above, missing};
-    const char* names[8] = {"words", "and_words", "values", "edges", "counts", "below", "above", "missing"};
-    bool dev = false;
-    VS_TRY(pointers_kind(ptrs, names, 8, device, &dev));
-    VS_HIP(hipSetDevice(device));
-    hipStream_t s = (hipStream_t)stream;
-    SetStage st;
-    Staged st_e;
-    HistArgs a{};
-    VS_TRY(st.in(words, bit0, ld_words, and_user, and_dev, B, values, dtype, n_rows, plan.rows_per_chunk, dev, s, &a.s));
-    uint32_t* d_e;
-    VS_TRY(st_e.in(static_cast<const uint32_t*>(edges), (size_t)n_edges, dev, true, s, &d_e));
-    a.edges = d_e;
-    a.n_edges = n_edges;
-    CountsOut out;
-    VS_TRY(out.bind(dev, counts, ld_counts, n_edges - 1, B, {below, above, missing}, s));
-    a.counts = out.mat;
-    a.ld_counts = out.ld;
-    a.below = out.vec[0];
-    a.above = out.vec[1];
-    a.missing = out.vec[2];
-    {
-        ProfScope prof("value_histogram", s);
-        const dim3 grid((unsigned)plan.chunks, (unsigned)ceil_div64(B, plan.qt));
-        const size_t lds = ((size_t)n_edges + (size_t)plan.qt * ((size_t)n_edges + 2)) * 4;      // at most 37 KB
-        if (plan.qt == 8) hipLaunchKernelGGL(value_hist_kernel<8>, grid, dim3(kValThreads), lds, s, a);
-        else hipLaunchKernelGGL(value_hist_kernel<1>, grid, dim3(kValThreads), lds, s, a);
-    }
-    const hipError_t le = hipGetLastError();
-    if (le != hipSuccess) {
-        (void)hipStreamSynchronize(s);                              // staging buffers die here
-        return fail(VS_EHIP, "value_histogram launch failed: %s", hipGetErrorString(le));
-    }
-    VS_STAGE("value_histogram", s);
-    if (!dev) VS_TRY(out.back(s));
-    return finish_call(dev, stream, s);
-}
-
-int topk_call(int device, const uint32_t* words, int64_t bit0, int64_t ld_words, const uint32_t* and_user, const uint32_t* and_dev, int32_t B,
-              const void* values, int dtype, int64_t n_rows, int32_t k, int descending, int64_t id_offset, const ValuePlan& plan, int64_t* out_ids,
-              void* out_values, void* stream) {
-    const void* ptrs[5] = {words, and_user, values, out_ids, out_values};
-    const char* names[5] = {"words", "and_words", "values", "out_ids", "out_values"};
-    bool dev = false;
-    VS_TRY(pointers_kind(ptrs, names, 5, device, &dev));
-    VS_HIP(hipSetDevice(device));
-    hipStream_t s = (hipStream_t)stream;
-    SetStage st;
-    Staged st_i, st_v;
-    DevBuf scratch;
-    TopArgs a{};
-    VS_TRY(st.in(words, bit0, ld_words, and_user, and_dev, B, values, dtype, n_rows, plan.rows_per_chunk, dev, s, &a.s));
-    VS_TRY(st_i.in(out_ids, (size_t)B * k, dev, false, s, &a.out_ids));
-    VS_TRY(st_v.in(static_cast<uint32_t*>(out_values), (size_t)B * k, dev, false, s, &a.out_values));
-    VS_TRY(scratch.alloc((size_t)B * (size_t)plan.chunks * (size_t)k * 8));
-    a.k = k;
-    a.flip = descending ? 0u : 0xFFFFFFFFu;
-    a.chunks = plan.chunks;
-    a.scratch = scratch.as<uint64_t>();
-    a.id_offset = id_offset;
-    {
-        ProfScope prof("value_topk", s);
-        hipLaunchKernelGGL(value_topk_chunk_kernel, dim3((unsigned)plan.chunks, (unsigned)B), dim3(kValThreads), 0, s, a);
-        hipLaunchKernelGGL(value_topk_merge_kernel, dim3((unsigned)B), dim3(kValThreads), 0, s, a);
-    }
-    const hipError_t le = hipGetLastError();
-    if (le != hipSuccess) {
-        (void)hipStreamSynchronize(s);                              // staging buffers and the scratch die here
-        return fail(VS_EHIP, "value_topk launch failed: %s", hipGetErrorString(le));
-    }
-    VS_STAGE("value_topk", s);
-    if (!dev) {
-        VS_TRY(st_i.back(s));
-        VS_TRY(st_v.back(s));
-    }
-    VS_HIP(hipStreamSynchronize(s));                                // the scratch is freed before the call returns
-    if (Profiler::get().on) Profiler::get().drain();
-    return VS_OK;
-}
-
 // host arrays are looked at before the device is (a pointer the runtime does not know, or no runtime at all: a host pointer)
 int check_edges(const void* edges, int32_t n_edges, int dtype) {
     if (is_device_ptr(edges)) return VS_OK;
@@ -435,29 +295,134 @@ int check_edges(const void* edges, int32_t n_edges, int dtype) {
     return plan_or_fail(value_check_edges_host(static_cast<const uint32_t*>(edges), n_edges, dtype, msg, sizeof msg), msg);
 }
 
-int check_stats(const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B, const void* values, int dtype, int64_t n_rows, int64_t rows_per_chunk,
-                bool have_outputs, ValuePlan* plan) {
+// the set of a call -> its plan (n_bins: the LDS slots of a query, 0 = none; max_qt: the widest tile of the kernel)
+int check_set(const SetSrc& src, bool have_ptrs, int dtype, int32_t n_bins, int64_t rows_per_chunk, int32_t max_qt, ValuePlan* plan) {
     char msg[256];
-    return plan_or_fail(value_check_set(values && have_outputs, words != nullptr, bit0, ld_words, B, dtype, n_rows, 0, rows_per_chunk, 8, plan, msg,
-                                        sizeof msg), msg);
+    return plan_or_fail(value_check_set(have_ptrs, src.words != nullptr, src.bit0, src.ld_words, src.B, dtype, src.n_rows, n_bins, rows_per_chunk, max_qt,
+                                        plan, msg, sizeof msg), msg);
 }
 
-int check_hist(const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B, const void* values, int dtype, int64_t n_rows, const void* edges,
-               int32_t n_edges, int64_t rows_per_chunk, int64_t ld_counts, bool have_outputs, ValuePlan* plan) {
+// vs_value_stats and vs_index_value_stats: one call on the set's device
+int value_stats(const SetSrc& src, const void* values, int dtype, int64_t rows_per_chunk, int64_t* count, int64_t* missing, void* out_min,
+                void* out_max, int64_t* sum, void* stream) {
+    ValuePlan plan;
+    VS_TRY(check_set(src, values && count && missing && out_min && out_max && sum, dtype, 0, rows_per_chunk, 8, &plan));
+    VS_TRY(src.device_ok());
+    Call c;
+    VS_TRY(c.open(src.device, stream, {{"words", src.words}, {"and_words", src.and_user}, {"values", values}, {"count", count}, {"missing", missing},
+                                       {"out_min", out_min}, {"out_max", out_max}, {"sum", sum}}));
+    const int32_t B = src.B;
+    SetStage st;
+    StatsArgs a{};
+    DevBuf out;                                                   // host outputs: count, missing, sum [B] x 8 bytes, then min, max [B] x 4
+    return c.run("value_stats", Finish::kStream, [&] {
+        VS_TRY(st.in(src, values, dtype, plan.rows_per_chunk, c.dev, c.s, &a.s));
+        if (c.dev) {
+            a.count = reinterpret_cast<unsigned long long*>(count);
+            a.missing = reinterpret_cast<unsigned long long*>(missing);
+            a.sum = reinterpret_cast<unsigned long long*>(sum);
+            a.min_key = static_cast<uint32_t*>(out_min);
+            a.max_key = static_cast<uint32_t*>(out_max);
+        } else {
+            VS_TRY(out.alloc((size_t)B * 32));
+            a.count = out.as<unsigned long long>();
+            a.missing = a.count + B;
+            a.sum = a.missing + B;
+            a.min_key = reinterpret_cast<uint32_t*>(a.sum + B);
+            a.max_key = a.min_key + B;
+        }
+        VS_HIP(hipMemsetAsync(a.count, 0, (size_t)B * 8, c.s));
+        VS_HIP(hipMemsetAsync(a.missing, 0, (size_t)B * 8, c.s));
+        VS_HIP(hipMemsetAsync(a.sum, 0, (size_t)B * 8, c.s));
+        VS_HIP(hipMemsetAsync(a.min_key, 0xFF, (size_t)B * 4, c.s));
+        VS_HIP(hipMemsetAsync(a.max_key, 0, (size_t)B * 4, c.s));
+        ProfScope prof("value_stats", c.s);
+        const dim3 grid((unsigned)plan.chunks, (unsigned)ceil_div64(B, plan.qt));
+        if (plan.qt == 8) hipLaunchKernelGGL(value_stats_kernel<8>, grid, dim3(kValThreads), 0, c.s, a);
+        else hipLaunchKernelGGL(value_stats_kernel<1>, grid, dim3(kValThreads), 0, c.s, a);
+        hipLaunchKernelGGL(value_finish_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, c.s, a.min_key, a.max_key, a.count, B, dtype);
+        return VS_OK;
+    }, [&] {
+        VS_HIP(hipMemcpyAsync(count, a.count, (size_t)B * 8, hipMemcpyDeviceToHost, c.s));
+        VS_HIP(hipMemcpyAsync(missing, a.missing, (size_t)B * 8, hipMemcpyDeviceToHost, c.s));
+        VS_HIP(hipMemcpyAsync(sum, a.sum, (size_t)B * 8, hipMemcpyDeviceToHost, c.s));
+        VS_HIP(hipMemcpyAsync(out_min, a.min_key, (size_t)B * 4, hipMemcpyDeviceToHost, c.s));
+        VS_HIP(hipMemcpyAsync(out_max, a.max_key, (size_t)B * 4, hipMemcpyDeviceToHost, c.s));
+        return VS_OK;
+    });
+}
+
+// vs_value_histogram and vs_index_value_histogram
+int value_histogram(const SetSrc& src, const void* values, int dtype, const void* edges, int32_t n_edges, int64_t rows_per_chunk, int64_t* counts,
+                    int64_t ld_counts, int64_t* below, int64_t* above, int64_t* missing, void* stream) {
+    ValuePlan plan;
     char msg[256];
-    if (!values || !edges || !have_outputs) return fail(VS_EINVAL, "NULL argument");
+    if (!values || !edges || !counts || !below || !above || !missing) return fail(VS_EINVAL, "NULL argument");
     VS_TRY(plan_or_fail(value_check_hist(n_edges, ld_counts, msg, sizeof msg), msg));
-    VS_TRY(plan_or_fail(value_check_set(true, words != nullptr, bit0, ld_words, B, dtype, n_rows, n_edges + 2, rows_per_chunk, 8, plan, msg, sizeof msg),
-                        msg));
-    return check_edges(edges, n_edges, dtype);
+    VS_TRY(check_set(src, true, dtype, n_edges + 2, rows_per_chunk, 8, &plan));
+    VS_TRY(check_edges(edges, n_edges, dtype));
+    VS_TRY(src.device_ok());
+    Call c;
+    VS_TRY(c.open(src.device, stream, {{"words", src.words}, {"and_words", src.and_user}, {"values", values}, {"edges", edges}, {"counts", counts},
+                                       {"below", below}, {"above", above}, {"missing", missing}}));
+    SetStage st;
+    Staged st_e;
+    CountsOut out;
+    return c.run("value_histogram", Finish::kStream, [&] {
+        HistArgs a{};
+        VS_TRY(st.in(src, values, dtype, plan.rows_per_chunk, c.dev, c.s, &a.s));
+        uint32_t* d_e;
+        VS_TRY(st_e.in(static_cast<const uint32_t*>(edges), (size_t)n_edges, c.dev, true, c.s, &d_e));
+        a.edges = d_e;
+        a.n_edges = n_edges;
+        VS_TRY(out.bind(c.dev, counts, ld_counts, n_edges - 1, src.B, {below, above, missing}, c.s));
+        a.counts = out.mat;
+        a.ld_counts = out.ld;
+        a.below = out.vec[0];
+        a.above = out.vec[1];
+        a.missing = out.vec[2];
+        ProfScope prof("value_histogram", c.s);
+        const dim3 grid((unsigned)plan.chunks, (unsigned)ceil_div64(src.B, plan.qt));
+        const size_t lds = ((size_t)n_edges + (size_t)plan.qt * ((size_t)n_edges + 2)) * 4;      // at most 37 KB
+        if (plan.qt == 8) hipLaunchKernelGGL(value_hist_kernel<8>, grid, dim3(kValThreads), lds, c.s, a);
+        else hipLaunchKernelGGL(value_hist_kernel<1>, grid, dim3(kValThreads), lds, c.s, a);
+        return VS_OK;
+    }, [&] { return out.back(c.s); });
 }
 
-int check_topk(const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B, const void* values, int dtype, int64_t n_rows, int32_t k,
-               int64_t rows_per_chunk, bool have_outputs, ValuePlan* plan) {
+// vs_value_topk and vs_index_value_topk
+int value_topk(const SetSrc& src, const void* values, int dtype, int32_t k, int descending, int64_t id_offset, int64_t rows_per_chunk,
+               int64_t* out_ids, void* out_values, void* stream) {
+    ValuePlan plan;
     char msg[256];
-    VS_TRY(plan_or_fail(value_check_set(values && have_outputs, words != nullptr, bit0, ld_words, B, dtype, n_rows, 0, rows_per_chunk, 1, plan, msg,
-                                        sizeof msg), msg));
-    return plan_or_fail(value_check_topk(k, B, *plan, msg, sizeof msg), msg);
+    VS_TRY(check_set(src, values && out_ids && out_values, dtype, 0, rows_per_chunk, 1, &plan));
+    VS_TRY(plan_or_fail(value_check_topk(k, src.B, plan, msg, sizeof msg), msg));
+    VS_TRY(src.device_ok());
+    Call c;
+    VS_TRY(c.open(src.device, stream, {{"words", src.words}, {"and_words", src.and_user}, {"values", values}, {"out_ids", out_ids},
+                                       {"out_values", out_values}}));
+    SetStage st;
+    Staged st_i, st_v;
+    DevBuf scratch;
+    return c.run("value_topk", Finish::kSync, [&] {
+        TopArgs a{};
+        VS_TRY(st.in(src, values, dtype, plan.rows_per_chunk, c.dev, c.s, &a.s));
+        VS_TRY(st_i.in(out_ids, (size_t)src.B * k, c.dev, false, c.s, &a.out_ids));
+        VS_TRY(st_v.in(static_cast<uint32_t*>(out_values), (size_t)src.B * k, c.dev, false, c.s, &a.out_values));
+        VS_TRY(scratch.alloc((size_t)src.B * (size_t)plan.chunks * (size_t)k * 8));
+        a.k = k;
+        a.flip = descending ? 0u : 0xFFFFFFFFu;
+        a.chunks = plan.chunks;
+        a.scratch = scratch.as<uint64_t>();
+        a.id_offset = id_offset;
+        ProfScope prof("value_topk", c.s);
+        hipLaunchKernelGGL(value_topk_chunk_kernel, dim3((unsigned)plan.chunks, (unsigned)src.B), dim3(kValThreads), 0, c.s, a);
+        hipLaunchKernelGGL(value_topk_merge_kernel, dim3((unsigned)src.B), dim3(kValThreads), 0, c.s, a);
+        return VS_OK;
+    }, [&] {
+        VS_TRY(st_i.back(c.s));
+        return st_v.back(c.s);
+    });
 }
 
 }  // namespace
@@ -481,102 +446,74 @@ extern "C" int vs_value_range_bitmaps(const void* values, int dtype, int64_t n_r
     if (!is_device_ptr(lo) && !is_device_ptr(hi))
         VS_TRY(plan_or_fail(value_check_bounds_host(static_cast<const uint32_t*>(lo), static_cast<const uint32_t*>(hi), B, dtype, msg, sizeof msg), msg));
     VS_TRY(device_in_range(device));
-    const void* ptrs[4] = {values, lo, hi, out_words};
-    const char* names[4] = {"values", "lo", "hi", "out_words"};
-    bool dev = false;
-    VS_TRY(pointers_kind(ptrs, names, 4, device, &dev));
-    VS_HIP(hipSetDevice(device));
-    hipStream_t s = (hipStream_t)stream;
-    RangeArgs a{};
-    a.dtype = dtype;
-    a.n_rows = n_rows;
-    a.B = B;
-    a.bit0 = bit0;
-    a.n_words = (bit0 + n_rows + 31) >> 5;
+    Call c;
+    VS_TRY(c.open(device, stream, {{"values", values}, {"lo", lo}, {"hi", hi}, {"out_words", out_words}}));
     Staged st_v, st_l, st_h, st_o;
-    uint32_t *d_v, *d_l, *d_h;
-    VS_TRY(st_v.in(static_cast<const uint32_t*>(values), (size_t)n_rows, dev, true, s, &d_v));
-    VS_TRY(st_l.in(static_cast<const uint32_t*>(lo), (size_t)B, dev, true, s, &d_l));
-    VS_TRY(st_h.in(static_cast<const uint32_t*>(hi), (size_t)B, dev, true, s, &d_h));
-    // (a host buffer's gaps between the rows come back as they went in: the staged copy starts from the caller's words)
-    VS_TRY(st_o.in(out_words, (size_t)(B - 1) * (size_t)ld_words + (size_t)a.n_words, dev, true, s, &a.out));
-    a.values = d_v;
-    a.lo = d_l;
-    a.hi = d_h;
-    a.ld = ld_words;
-    {
-        ProfScope prof("value_range_bitmaps", s);
+    return c.run("value_range_bitmaps", Finish::kStream, [&] {
+        RangeArgs a{};
+        a.dtype = dtype;
+        a.n_rows = n_rows;
+        a.B = B;
+        a.bit0 = bit0;
+        a.n_words = (bit0 + n_rows + 31) >> 5;
+        uint32_t *d_v, *d_l, *d_h;
+        VS_TRY(st_v.in(static_cast<const uint32_t*>(values), (size_t)n_rows, c.dev, true, c.s, &d_v));
+        VS_TRY(st_l.in(static_cast<const uint32_t*>(lo), (size_t)B, c.dev, true, c.s, &d_l));
+        VS_TRY(st_h.in(static_cast<const uint32_t*>(hi), (size_t)B, c.dev, true, c.s, &d_h));
+        // (a host buffer's gaps between the rows come back as they went in: the staged copy starts from the caller's words)
+        VS_TRY(st_o.in(out_words, (size_t)(B - 1) * (size_t)ld_words + (size_t)a.n_words, c.dev, true, c.s, &a.out));
+        a.values = d_v;
+        a.lo = d_l;
+        a.hi = d_h;
+        a.ld = ld_words;
+        ProfScope prof("value_range_bitmaps", c.s);
         const int64_t waves = (a.n_words + 1) / 2;
-        hipLaunchKernelGGL(value_range_kernel, dim3((unsigned)((waves + kValWaves - 1) / kValWaves)), dim3(kValThreads), 0, s, a);
-    }
-    const hipError_t le = hipGetLastError();
-    if (le != hipSuccess) {
-        (void)hipStreamSynchronize(s);
-        return fail(VS_EHIP, "value_range_bitmaps launch failed: %s", hipGetErrorString(le));
-    }
-    VS_STAGE("value_range_bitmaps", s);
-    if (!dev) VS_TRY(st_o.back(s));
-    return finish_call(dev, stream, s);
+        hipLaunchKernelGGL(value_range_kernel, dim3((unsigned)((waves + kValWaves - 1) / kValWaves)), dim3(kValThreads), 0, c.s, a);
+        return VS_OK;
+    }, [&] { return st_o.back(c.s); });
 }
 
 extern "C" int vs_value_stats(const uint32_t* words, int64_t bit0, int64_t ld_words, const uint32_t* and_words, int32_t B, const void* values,
                               int dtype, int64_t n_rows, int64_t rows_per_chunk, int64_t* count, int64_t* missing, void* out_min, void* out_max,
                               int64_t* sum, int device, void* stream) {
-    ValuePlan plan;
-    VS_TRY(check_stats(words, bit0, ld_words, B, values, dtype, n_rows, rows_per_chunk, count && missing && out_min && out_max && sum, &plan));
-    VS_TRY(device_in_range(device));
-    return stats_call(device, words, bit0, ld_words, and_words, nullptr, B, values, dtype, n_rows, plan, count, missing, out_min, out_max, sum, stream);
+    return value_stats(free_set(words, bit0, ld_words, and_words, B, n_rows, device), values, dtype, rows_per_chunk, count, missing, out_min, out_max,
+                       sum, stream);
 }
 
 extern "C" int vs_index_value_stats(vs_index* idx, const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B, const void* values, int dtype,
                                     int64_t rows_per_chunk, int64_t* count, int64_t* missing, void* out_min, void* out_max, int64_t* sum,
                                     void* stream) {
-    if (!idx) return fail(VS_EINVAL, "NULL argument");
-    ValuePlan plan;
-    VS_TRY(check_stats(words, bit0, ld_words, B, values, dtype, idx->n_rows, rows_per_chunk, count && missing && out_min && out_max && sum, &plan));
-    // tombstones are ANDed in, as every search does (the live bitmap starts at bit 0 whatever bit0 is)
-    return stats_call(idx->device, words, bit0, ld_words, nullptr, live_words(idx), B, values, dtype, idx->n_rows, plan, count, missing, out_min, out_max,
-                      sum, stream);
+    SetSrc src;
+    VS_TRY(index_set(idx, words, bit0, ld_words, B, &src));
+    return value_stats(src, values, dtype, rows_per_chunk, count, missing, out_min, out_max, sum, stream);
 }
 
 extern "C" int vs_value_histogram(const uint32_t* words, int64_t bit0, int64_t ld_words, const uint32_t* and_words, int32_t B, const void* values,
                                   int dtype, int64_t n_rows, const void* edges, int32_t n_edges, int64_t rows_per_chunk, int64_t* counts,
                                   int64_t ld_counts, int64_t* below, int64_t* above, int64_t* missing, int device, void* stream) {
-    ValuePlan plan;
-    VS_TRY(check_hist(words, bit0, ld_words, B, values, dtype, n_rows, edges, n_edges, rows_per_chunk, ld_counts, counts && below && above && missing,
-                      &plan));
-    VS_TRY(device_in_range(device));
-    return hist_call(device, words, bit0, ld_words, and_words, nullptr, B, values, dtype, n_rows, edges, n_edges, plan, counts, ld_counts, below, above,
-                     missing, stream);
+    return value_histogram(free_set(words, bit0, ld_words, and_words, B, n_rows, device), values, dtype, edges, n_edges, rows_per_chunk, counts,
+                           ld_counts, below, above, missing, stream);
 }
 
 extern "C" int vs_index_value_histogram(vs_index* idx, const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B, const void* values,
                                         int dtype, const void* edges, int32_t n_edges, int64_t rows_per_chunk, int64_t* counts, int64_t ld_counts,
                                         int64_t* below, int64_t* above, int64_t* missing, void* stream) {
-    if (!idx) return fail(VS_EINVAL, "NULL argument");
-    ValuePlan plan;
-    VS_TRY(check_hist(words, bit0, ld_words, B, values, dtype, idx->n_rows, edges, n_edges, rows_per_chunk, ld_counts,
-                      counts && below && above && missing, &plan));
-    return hist_call(idx->device, words, bit0, ld_words, nullptr, live_words(idx), B, values, dtype, idx->n_rows, edges, n_edges, plan, counts, ld_counts,
-                     below, above, missing, stream);
+    SetSrc src;
+    VS_TRY(index_set(idx, words, bit0, ld_words, B, &src));
+    return value_histogram(src, values, dtype, edges, n_edges, rows_per_chunk, counts, ld_counts, below, above, missing, stream);
 }
 
 extern "C" int vs_value_topk(const uint32_t* words, int64_t bit0, int64_t ld_words, const uint32_t* and_words, int32_t B, const void* values,
                              int dtype, int64_t n_rows, int32_t k, int descending, int64_t id_offset, int64_t rows_per_chunk, int64_t* out_ids,
                              void* out_values, int device, void* stream) {
-    ValuePlan plan;
-    VS_TRY(check_topk(words, bit0, ld_words, B, values, dtype, n_rows, k, rows_per_chunk, out_ids && out_values, &plan));
-    VS_TRY(device_in_range(device));
-    return topk_call(device, words, bit0, ld_words, and_words, nullptr, B, values, dtype, n_rows, k, descending, id_offset, plan, out_ids, out_values,
-                     stream);
+    return value_topk(free_set(words, bit0, ld_words, and_words, B, n_rows, device), values, dtype, k, descending, id_offset, rows_per_chunk, out_ids,
+                      out_values, stream);
 }
 
 extern "C" int vs_index_value_topk(vs_index* idx, const uint32_t* words, int64_t bit0, int64_t ld_words, int32_t B, const void* values, int dtype,
                                    int32_t k, int descending, int64_t id_offset, int64_t rows_per_chunk, int64_t* out_ids, void* out_values,
                                    void* stream) {
-    if (!idx) return fail(VS_EINVAL, "NULL argument");
-    ValuePlan plan;
-    VS_TRY(check_topk(words, bit0, ld_words, B, values, dtype, idx->n_rows, k, rows_per_chunk, out_ids && out_values, &plan));
-    return topk_call(idx->device, words, bit0, ld_words, nullptr, live_words(idx), B, values, dtype, idx->n_rows, k, descending, id_offset, plan, out_ids,
-                     out_values, stream);
+    SetSrc src;
+    VS_TRY(index_set(idx, words, bit0, ld_words, B, &src));
+    return value_topk(src, values, dtype, k, descending, id_offset, rows_per_chunk, out_ids, out_values, stream);
 }
