@@ -990,6 +990,39 @@ VS_API int vs_prune_plan(int64_t n_rows, int64_t n_packets, int32_t n_cols, int 
 VS_API int vs_index_prune(const vs_index* src, int32_t topk, float min_value, const uint32_t* col_keep, const vs_index* protect, int64_t rows_extra,
                           int64_t packets_extra, int device, vs_index** out, int32_t* out_kept);
 
+/* ---- sub-index: any rows, in any order, as a new index (no reference counterpart: the reference indexes its tensor, index.py:163-179) ----------
+ * vs_index_slice_rows takes a contiguous range, vs_index_compact the live rows in order, vs_index_prune all rows thinner; vs_index_select_rows
+ * takes "these rows, in this order": a NEW index on GPU `device` whose row j is row ids[j] - id_offset of `src`.
+ *   - Packets are copied whole on the device: column ids, value bits, the order inside a row and the padding of a row's last packet do not
+ *     change, so a row scores bit for bit what it scored in `src`.  nnz is recounted, lanes_per_row picked for the new shape, a dense index
+ *     stored as packets stays reported VS_KIND_DENSE.  `src` is untouched; the result has no postings copy yet (vs_index_prepare).
+ *   - ids [n] int64: any order, repeats allowed (oversampling, a bootstrap); host pointers, or device pointers on src's device.  Every id has
+ *     to name a stored row: an id outside [id_offset, id_offset + n_rows) -- -1 included -- is VS_EINVAL and no handle is made.  Host ids are
+ *     checked on the host; device ids by the first kernel, whose flag is read back with the totals.  n == 0: VS_EINVAL ("empty selection").
+ *   - Tombstones travel with the rows: with deletions on `src`, new row j is deleted iff its source row is (the live count is right, and
+ *     vs_index_restore_rows on the result brings the row back).  A source without tombstones, or a selection without a deleted row, gives a handle without a live bitmap: it
+ *     behaves, and is written to .vsx, as an index built from the same CSR.
+ *   - fp32 / fp16 / binary stores.  The dense matrix kind: a row gather of the padded matrix, rows_extra == packets_extra == 0 and the same
+ *     device only, as in vs_index_compact.
+ *   - rows_extra / packets_extra / device, the 2^32 row and packet limits (repeats can select more packets than `src` stores: the sum is taken
+ *     in 64 bits) and the VS_ENOMEM naming the bytes are vs_index_compact's.  Blocking.
+ * Four steps on src's GPU: stat (a thread an id: the range check and the source row's packets, summed over blocks of 4096 ids), the scan of
+ * the block sums and map (the new row pointers; with tombstones the live words of the new rows, two whole words a wave from a ballot), gather
+ * (a wave takes 64 new rows -- one contiguous packet range of the new index -- and issues the loads of four 64-packet steps, held in registers,
+ * before it stores),
+ * the recount of the non-zeros.
+ * vs_select_plan: pure host arithmetic, no device -- the scratch the call allocates next to both indexes: 8 bytes an id (host ids are staged
+ *   on the device), the block sums, the totals.  n outside 1..2^32 - 2: VS_EINVAL.  The output may be NULL.
+ * vs_select_split: pure host arithmetic -- how a selection of GLOBAL ids is dealt to the shards of a row-sharded index.  Shard s holds the
+ *   rows [cuts[s], cuts[s + 1]) (cuts [n_shards + 1] int64, ascending from 0); the ids are dealt IN THE ORDER GIVEN, out_begin [n_shards + 1]:
+ *   positions [out_begin[s], out_begin[s + 1]) of ids belong to shard s.  The shards side by side are the unsharded selection exactly when
+ *   the shard of ids[i] never decreases along i; a list that goes back to an earlier shard would move a row across shards: VS_EINVAL, as is
+ *   an id outside [0, cuts[n_shards]).  Host pointers only.                                                                                 */
+VS_API int vs_select_plan(int64_t n_ids, int64_t* out_scratch_bytes);
+VS_API int vs_select_split(const int64_t* ids, int64_t n, const int64_t* cuts, int32_t n_shards, int64_t* out_begin);
+VS_API int vs_index_select_rows(const vs_index* src, const int64_t* ids, int64_t n, int64_t id_offset, int64_t rows_extra, int64_t packets_extra,
+                                int device, vs_index** out);
+
 /* ---- term constraints: must / must-not / should filters built from the index's own columns (no reference counterpart) --------------------
  * A row HAS term c (a column id in [0, n_cols)) iff it stores column c with a non-zero value; under a threshold thr, iff the stored value
  * v satisfies v >= thr (an fp16 store widens exactly, as vs_index_get_rows; a binary index stores 1; a stored zero counts under thr <= 0).

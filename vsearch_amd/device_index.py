@@ -223,6 +223,48 @@ def prune_plan(n_rows, n_packets, n_cols, store_dtype, topk=0, has_protect=False
     return reg.value, scratch.value, lds.value
 
 
+def select_plan(n):
+    """vs_select_plan (pure host arithmetic) -> scratch_bytes: what select_rows() of n ids allocates next to both indexes"""
+    scratch = C.c_int64(0)
+    nat.check(nat.lib().vs_select_plan(int(n), C.byref(scratch)))
+    return scratch.value
+
+
+def _select_ids(ids):
+    """The id list of select_rows() -> (int64 1-D numpy array | CUDA tensor, on_device); an empty list is a ValueError (checked before the
+    library is reached)."""
+    ids, on_dev = _row_ids(ids)
+    if int(ids.shape[0]) == 0:
+        raise ValueError("empty selection: select_rows() needs at least one id")
+    return ids, on_dev
+
+
+def split_by_shard(ids, cuts):
+    """vs_select_split (pure host arithmetic): global ids dealt to the shards whose rows are [cuts[s], cuts[s + 1]), IN THE ORDER GIVEN ->
+    begin int64 [n_shards + 1]: ids[begin[s]:begin[s + 1]] are shard s's.  A list that goes back to an earlier shard raises ValueError."""
+    ids = np.ascontiguousarray(ids, dtype=np.int64)
+    cuts = np.ascontiguousarray(cuts, dtype=np.int64)
+    if ids.ndim != 1 or cuts.ndim != 1 or cuts.size < 2:
+        raise ValueError("ids must be 1-D, cuts 1-D with one entry more than there are shards")
+    begin = np.zeros(cuts.size, dtype=np.int64)
+    nat.check(nat.lib().vs_select_split(C.c_void_p(ids.ctypes.data) if ids.size else None, int(ids.size), C.c_void_p(cuts.ctypes.data), int(cuts.size) - 1,
+                                        C.c_void_p(begin.ctypes.data)))
+    return begin
+
+
+def _split_on_device(ids, cuts):
+    """split_by_shard for ids that live on a GPU: the same rule with torch on that GPU -- only the per-shard counts come to the host"""
+    import torch
+    edges = torch.tensor(cuts, dtype=torch.int64, device=ids.device)
+    if int(ids.min()) < 0 or int(ids.max()) >= int(cuts[-1]):
+        raise ValueError(f"the selection holds a document id outside [0, {int(cuts[-1])})")
+    shard = torch.bucketize(ids, edges[1:], right=True)           # the shard of every id: the first whose end lies beyond it
+    if bool((shard[1:] < shard[:-1]).any()):
+        raise ValueError("the selection goes back to an earlier shard: a selection cannot move rows across shards")
+    counts = torch.bincount(shard, minlength=len(cuts) - 1).cpu().numpy()
+    return np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+
+
 def _by_example_args(ids, weights=None, q=None, k=None, a=None):
     """Argument checks of queries_from_rows() / search_by_example() that need no device -> (B, m, on_device)"""
     on_dev = _int64_ids(ids, 2)
@@ -3093,6 +3135,34 @@ class DeviceIndex:
             nat.check(nat.lib().vs_index_prune(*args))
         return DeviceIndex(h), kept
 
+    def select_rows(self, ids, rows_extra: int = 0, packets_extra: int = 0, device: int = None, id_offset: int = 0) -> "DeviceIndex":
+        """-> a new DeviceIndex whose row j is row ids[j] - id_offset of this one (vs_index_select_rows): any order, repeats kept, packets copied
+        whole -- a row scores bit for bit what it scores here.  ids: integers, 1-D, numpy or torch, on the host or on this index's GPU (a
+        tensor on another GPU is moved); an id outside the index -- -1 included -- and an empty list raise ValueError.  Deleted rows are
+        carried as deleted.  This index is untouched.  rows_extra / packets_extra / device as in compact(), and compact()'s retry: if HBM
+        cannot hold both, this index's postings copy is dropped (prepare() rebuilds it) and the call retried once."""
+        ids, on_dev = _select_ids(ids)
+        rows_extra, packets_extra = _compact_args(rows_extra, packets_extra)
+        nat.require_device()
+        if on_dev and ids.device.index != self.device:
+            ids = ids.to(f"cuda:{self.device}")
+        device = self.device if device is None else int(device)
+        h = C.c_void_p()
+        args = (self._h, C.c_void_p(ids.data_ptr() if on_dev else ids.ctypes.data), int(ids.shape[0]), int(id_offset), rows_extra, packets_extra, device,
+                C.byref(h))
+        if on_dev:
+            import torch
+            torch.cuda.current_stream(self.device).synchronize()    # (the ids were made on torch's stream; the call runs on the null stream)
+        try:
+            nat.check(nat.lib().vs_index_select_rows(*args))
+        except MemoryError:
+            if not self.info().aux_bytes:
+                raise
+            self.set_option("blocked_postings", 0)             # releases the copy; back to auto for the next prepare()
+            self.set_option("blocked_postings", -1)
+            nat.check(nat.lib().vs_index_select_rows(*args))
+        return DeviceIndex(h)
+
     # ---- term constraints (vsearch_amd.doc_filter.DocFilter.from_terms) ------------------------------
     def _term_words(self, cols, thr=None, want_df=False, live_only=True, ld=None):
         info = self.info()
@@ -3917,6 +3987,22 @@ class ShardGroup:
             new.append(c)
             kepts.append(kept)
         return ShardGroup(new), (np.concatenate(kepts) if kepts else np.zeros(0, dtype=np.int32))
+
+    def select_rows(self, ids) -> "ShardGroup":
+        """DeviceIndex.select_rows with GLOBAL ids -> a new ShardGroup: the ids are dealt to the shards in the order given
+        (split_by_shard), every shard selects its own on its own GPU, and the new group is the new shards side by side; a shard that
+        receives no id is left out.  That is the unsharded selection exactly when the shard of ids[j] never decreases along j -- ascending
+        ids, every filter's set_ids() -- and anything else raises ValueError: a selection does not move rows across shards."""
+        ids, on_dev = _select_ids(ids)
+        nat.require_device()
+        parts = self._parts
+        cuts = [row0 for _, row0 in parts] + [self.n_rows]
+        begin = _split_on_device(ids, cuts) if on_dev else split_by_shard(ids, cuts)
+        new = []
+        for (sh, row0), a, b in zip(parts, begin[:-1], begin[1:]):
+            if b > a:
+                new.append(sh.select_rows(ids[int(a):int(b)], id_offset=row0))
+        return ShardGroup(new)
 
     # ---- term constraints -----------------------------------------------------------------------------------
     def _term_words(self, cols, thr=None, want_df=False, live_only=True, ld=None):

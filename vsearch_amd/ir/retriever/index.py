@@ -28,7 +28,8 @@ from ...device_index import SortedResults, ValueHistogram, ValueStats, value_col
 from ...device_index import ValuePercentiles, _percentile_args, quantile_lerp
 from ...device_index import FacetValueHistogram, FacetValueStats
 from ...device_index import FacetValuePercentiles, MAX_VALUE_RANKS
-from ...device_index import SetIds, SetSample, _set_sample_args, _set_window_args
+from ...device_index import SetIds, SetSample, _set_sample_args, _set_window_args, MAX_SET_IDS
+from ...device_index import _select_ids, _value_keys
 from ...device_index import BOOST_MODES, MAX_BOOST_FIELDS
 from ...device_index import _col_mask
 from ...device_index import LabelTermCounts, LabelTermSums, _label_top_terms, _label_top_weights
@@ -1574,6 +1575,105 @@ class Index:
             new._dev = new_target
             new._prepare()
         return new
+
+    # ---- sub-index (not in the reference: a document set, or the whole index in another order, as a new index) ----------------------------------
+    def _set_member_ids(self, filter):
+        """every live document of ONE set (a shared filter, or None = all) in ascending order: int64 tensor on the search target's GPU, listed
+        by set_ids in pages of MAX_SET_IDS"""
+        target = self._explain_target()[0]
+        counts = target.set_count(filter=filter)
+        if int(counts.numel()) != 1:
+            raise ValueError(f"a sub-index is made of ONE document set: a shared filter or the match set of one query, got a batch of {int(counts.numel())}")
+        total = int(counts[0])
+        if total == 0:
+            raise ValueError("empty selection: the set holds no live document")
+        pages = [target.set_ids(filter=filter, offset=o, limit=min(MAX_SET_IDS, total - o)).ids[0] for o in range(0, total, MAX_SET_IDS)]
+        return pages[0] if len(pages) == 1 else torch.cat(pages)
+
+    def _selected(self, ids):
+        """the new index of documents `ids` (int64, host numpy or a tensor on the search target's GPU) in that order, everything attached"""
+        target, gpu_ord = self._explain_target()
+        gpu = torch.device("cuda", gpu_ord)
+        sharded = isinstance(target, ShardGroup)
+        new_target = target.select_rows(ids)
+        src = (ids if isinstance(ids, torch.Tensor) else torch.from_numpy(ids)).to(gpu)
+        new = copy.copy(self)
+        new._vector = None                                          # re-exported from the selected rows on demand
+        new._dev = None
+        new._source_ids = src
+        if self._shape is not None:
+            new._shape = (int(src.shape[0]), self._shape[1])
+        if self.data is not None or (self.low_memory and getattr(self, "offsets", None) is not None):
+            new.data, offsets = remap_text_store(self.data, getattr(self, "offsets", None) if self.low_memory else None, src.cpu().numpy())
+            if offsets is not None:
+                new.offsets = offsets
+        if self.groups is not None:                                 # new document j keeps the group of source_ids[j]
+            new._groups = self._groups.index_select(0, src.to(self._groups.device)).to(gpu)
+        if getattr(self, "_facets", None) is not None:              # ... its label of every facet field, with the field's n_labels and names
+            new._facets = {name: (c.index_select(0, src.to(c.device)).to(gpu), n_labels, names) for name, (c, n_labels, names) in self._facets.items()}
+        if getattr(self, "_values", None) is not None:              # ... and its value of every value field
+            new._values = {name: v.index_select(0, src.to(v.device)).to(gpu) for name, v in self._values.items()}
+        if sharded:
+            new._shards, new._group = None, None
+            new._adopt_shards(list(new_target._shards))
+            new_target.close()
+        else:
+            new._dev = new_target
+            new._prepare()
+        return new
+
+    def subset(self, q_embs=None, min_score=None, filter=None, ids=None):
+        """A NEW index of the same class holding a document set of this one (vs_index_select_rows on the GPU; this index is left exactly as
+        it was).  The set as in ``list_ids``: `filter` alone (what ``search(filter=)`` accepts, shared by the batch), or with q_embs and
+        min_score the documents ``match_filter`` matches for ONE query (B = 1); the documents come in ascending id order and deleted ones are
+        never selected.  Or ids=: exactly these documents in exactly this order, repeats kept (an oversample, a bootstrap, ``sample_ids(...)
+        .ids[0]``), a deleted id carried as deleted; -1 raises.  Rows are copied whole, so a document scores bit for bit what it scores here.
+        The new index carries the texts, the groups, every facet field (n_labels and names) and every value field of its documents, and
+        ``source_ids``.  A row-sharded index is selected shard by shard on its GPUs and keeps its sharding (a shard left without documents
+        is dropped); there ids= must not go back to an earlier shard (ValueError): a selection does not move rows across shards."""
+        if ids is not None:
+            if q_embs is not None or min_score is not None or filter is not None:
+                raise ValueError("ids= names the documents itself: it goes without q_embs, min_score and filter")
+            picked, on_dev = _select_ids(ids.detach() if isinstance(ids, torch.Tensor) else ids)
+            if on_dev:
+                picked = picked.to(torch.device("cuda", self._explain_target()[1]))
+            return self._selected(picked)
+        if q_embs is not None and min_score is not None:
+            q = torch.from_numpy(q_embs) if isinstance(q_embs, np.ndarray) else q_embs
+            if q.dim() == 2 and int(q.shape[0]) != 1:
+                raise ValueError(f"a sub-index is made of ONE document set: the match set of one query, got a batch of {int(q.shape[0])}")
+        return self._selected(self._set_member_ids(self._egress_set(q_embs, min_score, filter)))
+
+    @property
+    def source_ids(self):
+        """int64 [len]: document j of this index is document source_ids[j] of the index ``subset`` / ``sorted_by`` made it from (None for
+        an index that was not made by them)"""
+        src = getattr(self, "_source_ids", None)
+        return None if src is None else self._to_api(src)
+
+    def sorted_by(self, field, descending: bool = False):
+        """A NEW index holding the LIVE documents of this one ordered by a field (this index is untouched): a facet field (or "groups") orders
+        by (label, id) with the documents without a label last; a value field by (value, id) on the order keys of the numeric fields -- -0.0
+        and +0.0 tie -- with the documents without a value last; descending reverses the field's order only: ties still go by ascending id
+        and the missing stay last.  The order is a stable argsort on the GPU; everything ``subset`` carries is carried, ``source_ids``
+        included.  This supplies the operation -- documents of a label in one run of rows --, not a recommendation when to use it.  A
+        row-sharded index raises NotImplementedError (the order would move rows across shards); SCORE is not a field."""
+        if field is SCORE:
+            raise ValueError("SCORE is not a field of sorted_by: scores belong to a query, not to the index")
+        target, gpu_ord = self._explain_target()
+        if isinstance(target, ShardGroup):
+            raise NotImplementedError("sorted_by moves documents across the shards of a row-sharded index: sort before shard_rows()")
+        if field == "groups" or field in (getattr(self, "_facets", None) or {}):
+            keys = self._facet_field(field)[0].to(torch.int64) + 1    # 0 = no label
+        else:
+            keys = _value_keys(self._value_field(field))             # 0 = no value
+        live = self._set_member_ids(None)
+        k = keys.index_select(0, live)
+        missing = k == 0
+        if descending:
+            k = 0xFFFFFFFF - k
+        k = torch.where(missing, torch.full_like(k, 1 << 32), k)
+        return self._selected(live.index_select(0, torch.argsort(k, stable=True)))
 
     def _add_csr(self, vectors):
         """vectors -> (indptr, indices, data) of the rows to append"""

@@ -797,6 +797,30 @@ class Retriever(BiEncoder):
             self.index = new
         return new
 
+    def subset_index(self, filter=None, query=None, min_score=None, ids=None, inplace: bool = True, index: Index = None) -> Index:
+        """Index.subset -> the new index of a document set: `filter`, or the documents one `query` (a text, or its embedding [1, V]) scores at
+        least `min_score`, or the documents `ids` in that order; inplace: it replaces retriever.index (the old index object stays valid for
+        whoever holds it)."""
+        index = index or self.index
+        if index is None:
+            raise RuntimeError("no index: call build_index / load_index first")
+        q_embs = None if query is None else self.process_query(query)
+        new = index.subset(q_embs=q_embs, min_score=min_score, filter=filter, ids=ids)
+        if inplace:
+            self.index = new
+        return new
+
+    def sort_index_by(self, field, descending: bool = False, inplace: bool = True, index: Index = None) -> Index:
+        """Index.sorted_by -> the new index of the live documents ordered by a facet or value field (e.g. the labels ``cluster`` stored);
+        inplace: it replaces retriever.index."""
+        index = index or self.index
+        if index is None:
+            raise RuntimeError("no index: call build_index / load_index first")
+        new = index.sorted_by(field, descending=descending)
+        if inplace:
+            self.index = new
+        return new
+
     def save_index(self, path):
         self.index.save(path)
 
