@@ -1023,6 +1023,47 @@ VS_API int vs_select_split(const int64_t* ids, int64_t n, const int64_t* cuts, i
 VS_API int vs_index_select_rows(const vs_index* src, const int64_t* ids, int64_t n, int64_t id_offset, int64_t rows_extra, int64_t packets_extra,
                                 int device, vs_index** out);
 
+/* ---- reweighted index: row statistics, and cells rescaled by row and column (no reference counterpart: the reference multiplies its tensor) ------
+ * Every call above moves stored cells without changing a value.  vs_index_row_stats reads a row's magnitude, vs_index_rescale makes a NEW
+ * index with the source's sparsity and new values.  Row r has stored cells (col_t, v_t), t = 0..n-1 in STORED ORDER (the order
+ * vs_index_export_csr returns; padding cells are not cells); w_t is v_t widened to fp32, and 1 on a binary index (VS_NONE).
+ * vs_index_row_stats: n_rows entries each, any output may be NULL, the non-NULL ones all host pointers or all device pointers on src's device.
+ *   - cells[r]   = n, the stored cells.
+ *   - nonzero[r] = the cells with w_t != 0 (+0.0 and -0.0 are zero): the term constraints' "has a column".
+ *   - l1[r]      = the sum of fp64(|w_t|);  sumsq[r] = the sum of fp64(w_t) * fp64(w_t), each product exact in fp64.  Both are fp64 sums in
+ *     ONE pinned order, the order of the exact scores: lane l of the row's wave (l = 0..63) adds the cells of packets p0 + l, p0 + l + 64, ...
+ *     cell by cell from +0.0 (a packet holds 8 consecutive cells; p0 is the row's first packet), then for o = 32, 16, .. 1 every lane adds the sum
+ *     of lane l xor o to its own.  A loop on the host reproduces them bit for bit whatever the magnitudes (a NaN cell gives some NaN).  No
+ *     square root is taken: that keeps every output reproducible.
+ *   - max[r]     = the largest w_t as fp32; a NaN cell is skipped, a zero maximum is +0.0 whatever the signs of the zeros, a row with no
+ *     non-NaN cell gives NaN (0x7FC00000), the numeric fields' "no value".
+ *   An empty row has 0 / 0 / +0.0 / +0.0 / NaN.  Deleted rows are stored rows and get their statistics.  A dense matrix index: VS_EUNSUPPORTED;
+ *   a dense index stored as packets is a CSR index here.  One wave a row, 64 consecutive rows a wave, 256 a workgroup: the outputs are written
+ *   as runs.  Blocking.
+ * vs_index_rescale: a NEW index on GPU `device` with src's row pointers, src's packets' column ids bit for bit (padding included), src's
+ *   tombstones (as vs_index_prune carries them: vs_index_restore_rows brings a deleted row back rescaled), src's nnz, and no postings copy yet
+ *   (vs_index_prepare).  `src` is untouched.  row_scale [n_rows], col_scale [n_cols]: float32, each a host pointer or a device pointer on src's
+ *   device, each may be NULL = a scale of 1 that is not multiplied in.  out_dtype: VS_F32 or VS_F16 (VS_NONE: VS_EINVAL, binarising is not covered).
+ *   - a real cell: x = fl64(fl64(fp64(w) * fp64(row_scale[r])) * fp64(col_scale[col])), products left to right, a NULL scale skipped; the stored
+ *     value is fl32(x), for a fp16 result fl16(fl32(x)), both roundings to nearest even.  With one scale the fp64 product is exact: the fp32
+ *     value is the correctly rounded fp32 product w * s.  With no scale and out_dtype == src's dtype the value bits are copied.
+ *   - scales are data and are not checked: zero, negative, infinite and NaN scales give the IEEE result (a NaN result is any NaN); subnormal
+ *     results are kept, never flushed.
+ *   - a padding cell keeps id n_cols and value +0 whatever the scales are (an infinite scale does not turn it into a NaN): no scale applies to it.
+ *   - a binary source has w = 1 in every real cell and becomes a valued index.  A dense matrix index: VS_EUNSUPPORTED.
+ *   - rows_extra / packets_extra / device, the 2^32 row and packet limits and the VS_ENOMEM naming the bytes are vs_index_compact's.  Blocking.
+ *   One kernel on src's GPU: a wave takes 64 consecutive rows (one contiguous packet range), a lane a packet -- it finds the packet's row among
+ *   the run's row pointers (only with a row scale), reads ids and values once and writes ids and values once, four 64-packet steps in flight.
+ * vs_rescale_plan: pure host arithmetic, no device -- the scratch the call allocates next to both indexes when the scales given are host
+ *   pointers (4 bytes a row, 4 a column), the LDS of a workgroup, and out_col_route: 0 = no column scales, 1 = the column scales are held as an
+ *   LDS image (n_cols <= 40 960: the image fits the 160 KB of a CU), 2 = they are read from memory.  Any output may be NULL.  n_cols > 65535:
+ *   VS_EUNSUPPORTED; a bad dtype, out_dtype VS_NONE, a negative count: VS_EINVAL.                                                            */
+VS_API int vs_index_row_stats(const vs_index* src, int32_t* out_cells, int32_t* out_nonzero, double* out_l1, double* out_sumsq, float* out_max);
+VS_API int vs_rescale_plan(int64_t n_rows, int64_t n_packets, int32_t n_cols, int src_dtype, int out_dtype, int has_row_scale, int has_col_scale,
+                           int64_t* out_scratch_bytes, int32_t* out_lds_bytes, int32_t* out_col_route);
+VS_API int vs_index_rescale(const vs_index* src, const float* row_scale, const float* col_scale, int out_dtype, int64_t rows_extra,
+                            int64_t packets_extra, int device, vs_index** out);
+
 /* ---- term constraints: must / must-not / should filters built from the index's own columns (no reference counterpart) --------------------
  * A row HAS term c (a column id in [0, n_cols)) iff it stores column c with a non-zero value; under a threshold thr, iff the stored value
  * v satisfies v >= thr (an fp16 store widens exactly, as vs_index_get_rows; a binary index stores 1; a stored zero counts under thr <= 0).

@@ -162,6 +162,9 @@ _SIGNATURES = {
     "vs_select_plan": ([_i64, C.POINTER(_i64)], _int),
     "vs_select_split": ([_vp, _i64, _vp, _i32, _vp], _int),
     "vs_index_select_rows": ([_vp, _vp, _i64, _i64, _i64, _i64, _int, C.POINTER(_vp)], _int),
+    "vs_index_row_stats": ([_vp, _vp, _vp, _vp, _vp, _vp], _int),
+    "vs_rescale_plan": ([_i64, _i64, _i32, _int, _int, _int, _int, C.POINTER(_i64), C.POINTER(_i32), C.POINTER(_i32)], _int),
+    "vs_index_rescale": ([_vp, _vp, _vp, _int, _i64, _i64, _int, C.POINTER(_vp)], _int),
     "vs_index_term_bitmaps": ([_vp, _vp, _vp, _i32, _vp, _i64, _vp, _int, _vp], _int),
     "vs_term_filter_combine": ([_vp, _i64, _i64, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i64, _int, _vp], _int),
     "vs_index_prepare": ([_vp, _vp], _int),

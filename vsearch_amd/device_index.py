@@ -230,6 +230,68 @@ def select_plan(n):
     return scratch.value
 
 
+class RowStats(NamedTuple):
+    """row_stats(): per stored row -- cells int32 (stored cells), nonzero int32 (cells with a non-zero value), l1 float64 (sum of |w|), sumsq
+    float64 (sum of w * w, each product exact), max float32 (largest value; NaN = no value).  The sums are fp64 sums in the pinned order of
+    the exact scores; no square root is taken."""
+    cells: Any
+    nonzero: Any
+    l1: Any
+    sumsq: Any
+    max: Any
+
+
+_STORE_DTYPES = {"fp32": nat.VS_F32, "float32": nat.VS_F32, "fp16": nat.VS_F16, "float16": nat.VS_F16, nat.VS_F32: nat.VS_F32, nat.VS_F16: nat.VS_F16}
+COL_SCALE_ROUTES = ("none", "lds", "memory")         # vs_rescale_plan's out_col_route
+
+
+def _rescale_dtype(dtype, src_dtype):
+    """out_dtype of rescale(): None keeps a valued source's dtype; a binary source then has none to keep (ValueError)"""
+    if dtype is None:
+        if src_dtype == nat.VS_NONE:
+            raise ValueError("a binary index has no value dtype to keep: pass dtype='fp32' or 'fp16'")
+        return int(src_dtype)
+    if isinstance(dtype, (type, np.dtype)):
+        dtype = np.dtype(dtype).name
+    elif str(dtype) in ("torch.float32", "torch.float16"):
+        dtype = str(dtype)[6:]
+    if isinstance(dtype, bool) or dtype not in _STORE_DTYPES:
+        raise ValueError(f"dtype must be 'fp32' or 'fp16' (binarising an index is not covered), got {dtype!r}")
+    return _STORE_DTYPES[dtype]
+
+
+def _scale_arg(x, n, name, device):
+    """A scale of rescale() -> (float32 contiguous numpy array | CUDA tensor on `device`, pointer) or (None, None); the length is checked before
+    the library is reached"""
+    if x is None:
+        return None, None
+    if _is_torch(x):
+        import torch
+        if x.dtype == torch.bool or x.is_complex():
+            raise TypeError(f"{name} must be numbers, got {x.dtype}")
+        if x.ndim != 1 or int(x.shape[0]) != n:
+            raise ValueError(f"{name} must have shape ({n},), got {tuple(x.shape)}")
+        if x.is_cuda:
+            x = x.detach().to(device=f"cuda:{device}", dtype=torch.float32).contiguous()
+            return x, C.c_void_p(x.data_ptr()) if n else None
+        x = x.detach().numpy()
+    a = np.asarray(x)
+    if a.dtype == np.bool_ or not (np.issubdtype(a.dtype, np.floating) or np.issubdtype(a.dtype, np.integer)):
+        raise TypeError(f"{name} must be numbers, got {a.dtype}")
+    if a.shape != (n,):
+        raise ValueError(f"{name} must have shape ({n},), got {a.shape}")
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    return a, C.c_void_p(a.ctypes.data) if n else None
+
+
+def rescale_plan(n_rows, n_packets, n_cols, src_dtype, out_dtype, has_row_scale=False, has_col_scale=False):
+    """vs_rescale_plan (pure host arithmetic) -> (scratch_bytes, lds_bytes, col_route: "none" | "lds" | "memory")"""
+    scratch, lds, route = C.c_int64(0), C.c_int32(0), C.c_int32(0)
+    nat.check(nat.lib().vs_rescale_plan(int(n_rows), int(n_packets), int(n_cols), int(src_dtype), int(out_dtype), 1 if has_row_scale else 0,
+                                        1 if has_col_scale else 0, C.byref(scratch), C.byref(lds), C.byref(route)))
+    return scratch.value, lds.value, COL_SCALE_ROUTES[route.value]
+
+
 def _select_ids(ids):
     """The id list of select_rows() -> (int64 1-D numpy array | CUDA tensor, on_device); an empty list is a ValueError (checked before the
     library is reached)."""
@@ -3163,6 +3225,59 @@ class DeviceIndex:
             nat.check(nat.lib().vs_index_select_rows(*args))
         return DeviceIndex(h)
 
+    # ---- reweighted index ------------------------------------------------------------------------------
+    def row_stats(self) -> RowStats:
+        """-> RowStats(cells, nonzero, l1, sumsq, max): tensors [n_rows] on the index's device, one entry a stored row, deleted rows included
+        (vs_index_row_stats).  l1 and sumsq are float64 sums in the pinned order of the exact scores -- bit-reproducible; the root of sumsq is
+        the caller's (Index.row_norms).  A dense matrix index raises NotImplementedError.  Blocking."""
+        import torch
+        nat.require_device()
+        n = self.n_rows
+        dev = torch.device("cuda", self.device)
+        out = RowStats(torch.zeros(n, dtype=torch.int32, device=dev), torch.zeros(n, dtype=torch.int32, device=dev),
+                       torch.zeros(n, dtype=torch.float64, device=dev), torch.zeros(n, dtype=torch.float64, device=dev),
+                       torch.full((n,), float("nan"), dtype=torch.float32, device=dev))
+        torch.cuda.current_stream(self.device).synchronize()    # (the outputs were made on torch's stream; the call runs on the null stream)
+        nat.check(nat.lib().vs_index_row_stats(self._h, *[C.c_void_p(t.data_ptr()) if n else None for t in out]))
+        return out
+
+    def rescale_plan(self, row_scale=None, col_scale=None, dtype=None):
+        """what rescale() with these arguments would take -> (scratch_bytes, lds_bytes, col_route: "none" | "lds" | "memory"); scales are
+        only tested for None (vs_rescale_plan: pure host arithmetic)"""
+        info = self.info()
+        return rescale_plan(info.n_rows, info.n_packets, info.n_cols, info.store_dtype, _rescale_dtype(dtype, int(info.store_dtype)),
+                            row_scale is not None, col_scale is not None)
+
+    def rescale(self, row_scale=None, col_scale=None, dtype=None, rows_extra: int = 0, packets_extra: int = 0, device: int = None) -> "DeviceIndex":
+        """-> a new DeviceIndex with this one's rows, cells and column ids whose stored values are value * row_scale[row] * col_scale[column]
+        (vs_index_rescale): products in float64, left to right, rounded once to float32 and then, for dtype "fp16", to float16; with one scale
+        that is numpy's float32 product.  row_scale [n_rows], col_scale [n_cols]: numbers, numpy or torch, on the host or on a GPU (moved to
+        this index's); None = 1, not multiplied in.  dtype: "fp32" | "fp16" | None = the source's (a binary index, whose cells all hold 1, then
+        raises ValueError).  Padding cells stay 0 whatever the scales.  Deleted rows are carried as deleted; this index is untouched.
+        rows_extra / packets_extra / device as in compact(), and compact()'s retry: if HBM cannot hold both, this index's postings copy is
+        dropped (prepare() rebuilds it) and the call retried once.  A dense matrix index raises NotImplementedError."""
+        rows_extra, packets_extra = _compact_args(rows_extra, packets_extra)
+        nat.require_device()
+        info = self.info()
+        out_dtype = _rescale_dtype(dtype, int(info.store_dtype))
+        rs, p_rs = _scale_arg(row_scale, int(info.n_rows), "row_scale", self.device)
+        cs, p_cs = _scale_arg(col_scale, int(info.n_cols), "col_scale", self.device)
+        device = self.device if device is None else int(device)
+        if _is_torch(rs) or _is_torch(cs):
+            import torch
+            torch.cuda.current_stream(self.device).synchronize()    # (the scales were made on torch's stream; the call runs on the null stream)
+        h = C.c_void_p()
+        args = (self._h, p_rs, p_cs, out_dtype, rows_extra, packets_extra, device, C.byref(h))
+        try:
+            nat.check(nat.lib().vs_index_rescale(*args))
+        except MemoryError:
+            if not self.info().aux_bytes:
+                raise
+            self.set_option("blocked_postings", 0)             # releases the copy; back to auto for the next prepare()
+            self.set_option("blocked_postings", -1)
+            nat.check(nat.lib().vs_index_rescale(*args))
+        return DeviceIndex(h)
+
     # ---- term constraints (vsearch_amd.doc_filter.DocFilter.from_terms) ------------------------------
     def _term_words(self, cols, thr=None, want_df=False, live_only=True, ld=None):
         info = self.info()
@@ -4002,6 +4117,37 @@ class ShardGroup:
         for (sh, row0), a, b in zip(parts, begin[:-1], begin[1:]):
             if b > a:
                 new.append(sh.select_rows(ids[int(a):int(b)], id_offset=row0))
+        return ShardGroup(new)
+
+    # ---- reweighted index -------------------------------------------------------------------------------------
+    def row_stats(self) -> RowStats:
+        """DeviceIndex.row_stats of every shard on its own GPU, concatenated on the first shard's: every row is independent, so the answer is
+        the unsharded one bit for bit."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        parts = [sh.row_stats() for sh in self._shards]
+        return RowStats(*[torch.cat([p[i].to(dev) for p in parts]) for i in range(5)])
+
+    def rescale_plan(self, row_scale=None, col_scale=None, dtype=None):
+        """DeviceIndex.rescale_plan of every shard -> a list of (scratch_bytes, lds_bytes, col_route)"""
+        return [sh.rescale_plan(row_scale, col_scale, dtype) for sh in self._shards]
+
+    def rescale(self, row_scale=None, col_scale=None, dtype=None, rows_extra: int = 0, packets_extra: int = 0) -> "ShardGroup":
+        """DeviceIndex.rescale on every shard's own GPU -> a new ShardGroup cut at the same rows.  row_scale [the group's rows] is cut at the
+        shard boundaries, col_scale goes to every shard's GPU; every row is independent, so the shards side by side are the unsharded result
+        bit for bit.  The spare capacity goes to the last shard."""
+        rows_extra, packets_extra = _compact_args(rows_extra, packets_extra)
+        n = self.n_rows
+        if row_scale is not None:
+            if not hasattr(row_scale, "shape"):
+                row_scale = np.asarray(row_scale)
+            if tuple(row_scale.shape) != (n,):
+                raise ValueError(f"row_scale must have shape ({n},), got {tuple(row_scale.shape)}")
+        new = []
+        for i, (sh, row0) in enumerate(self._parts):
+            last = i == len(self._shards) - 1
+            rs = row_scale[row0:row0 + sh.n_rows] if row_scale is not None else None
+            new.append(sh.rescale(rs, col_scale, dtype, rows_extra if last else 0, packets_extra if last else 0))
         return ShardGroup(new)
 
     # ---- term constraints -----------------------------------------------------------------------------------

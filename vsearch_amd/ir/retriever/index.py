@@ -30,6 +30,7 @@ from ...device_index import FacetValueHistogram, FacetValueStats
 from ...device_index import FacetValuePercentiles, MAX_VALUE_RANKS
 from ...device_index import SetIds, SetSample, _set_sample_args, _set_window_args, MAX_SET_IDS
 from ...device_index import _select_ids, _value_keys
+from ...device_index import RowStats, _rescale_dtype
 from ...device_index import BOOST_MODES, MAX_BOOST_FIELDS
 from ...device_index import _col_mask
 from ...device_index import LabelTermCounts, LabelTermSums, _label_top_terms, _label_top_weights
@@ -1576,6 +1577,83 @@ class Index:
             new._prepare()
         return new
 
+    # ---- reweighted index (not in the reference: row norms, and the stored values times a scale per document and per column) -------------------
+    def row_stats(self) -> RowStats:
+        """Per stored document (deleted ones included): RowStats(cells int32, nonzero int32, l1 float64, sumsq float64, max float32) -- the
+        stored cells, those with a non-zero value, the sum of |value|, the sum of value^2 and the largest value (NaN: no value), read from the
+        stored rows on the GPU (vs_index_row_stats).  The sums are float64 in the pinned order of the exact scores: bit-reproducible, and
+        the same sharded or not.  Each is ready to be a value field (set_values).  A dense index on the matrix cores raises
+        NotImplementedError."""
+        return RowStats(*[self._to_api(t) for t in self._explain_target()[0].row_stats()])
+
+    def row_norms(self, p=2):
+        """float32 [N]: the L1 (p = 1) or L2 (p = 2) norm of every stored document; the float64 root of row_stats().sumsq is taken on the
+        device and cast to float32."""
+        if isinstance(p, bool) or p not in (1, 2):
+            raise ValueError(f"p must be 1 or 2, got {p!r}")
+        st = self._explain_target()[0].row_stats()
+        return self._to_api((st.l1 if p == 1 else torch.sqrt(st.sumsq)).to(torch.float32))
+
+    def rescaled(self, row_scale=None, col_scale=None, dtype=None):
+        """A NEW index of the same documents and cells whose stored values are value * row_scale[document] * col_scale[column]
+        (vs_index_rescale on the GPU; this index is left exactly as it was): products in float64, rounded once to float32 and then, for dtype
+        "fp16", to float16.  row_scale [N], col_scale [V]: numbers, numpy or torch; None = 1.  dtype: "fp32" | "fp16" | None = the stored
+        dtype (a bag-of-token index, whose cells hold 1: the dtype it reports for its vector).  Ids do not move: the new index shares the text store, the groups, the
+        facet and the value fields, and carries the deletions, as ``pruned`` does; a row-sharded index is rescaled shard by shard on its
+        GPUs.  A BoTIndex comes back as a SparseIndex.  A dense index on the matrix cores raises NotImplementedError."""
+        target, gpu_ord = self._explain_target()
+        sharded = isinstance(target, ShardGroup)
+        first = target._shards[0] if sharded else target
+        src_dtype = int(first.info().store_dtype)
+        if dtype is None and src_dtype == nat.VS_NONE:               # binary rows: the dtype the index reports for its vector
+            dtype = "fp16" if self._dtype == torch.float16 else "fp32"
+        out_dtype = _rescale_dtype(dtype, src_dtype)
+        new_target = target.rescale(row_scale, col_scale, out_dtype)
+        new = copy.copy(self)                                       # the text store (data / offsets) is shared: ids did not move
+        if isinstance(new, BoTIndex):
+            new.__class__ = SparseIndex                             # a valued index now (BoTIndex adds nothing to SparseIndex but _binary(): see there)
+        new._vector = None                                          # re-exported from the rescaled rows on demand
+        new._dev = None
+        new._dtype = torch.float16 if out_dtype == nat.VS_F16 else torch.float32
+        for name in ("_facets", "_values"):                         # the columns are shared, the registries are the new index's own
+            if getattr(self, name, None) is not None:
+                setattr(new, name, dict(getattr(self, name)))
+        if sharded:
+            new._shards, new._group = None, None
+            new._adopt_shards(list(new_target._shards))
+            new_target.close()
+        else:
+            new._dev = new_target
+            new._prepare()
+        return new
+
+    def normalized(self, p=2):
+        """``rescaled`` to unit L1 / L2 length: row_scale = float32(1 / norm) with the norm in float64; a document whose norm is 0 or not
+        finite keeps scale 1.  Searched by the fast path, a unit-length index ranks by cosine for any one query."""
+        if isinstance(p, bool) or p not in (1, 2):
+            raise ValueError(f"p must be 1 or 2, got {p!r}")
+        st = self._explain_target()[0].row_stats()
+        norm = st.l1 if p == 1 else torch.sqrt(st.sumsq)
+        ok = torch.isfinite(norm) & (norm > 0)
+        scale = torch.where(ok, 1.0 / torch.where(ok, norm, torch.ones_like(norm)), torch.ones_like(norm)).to(torch.float32)
+        return self.rescaled(row_scale=scale)
+
+    def astype(self, dtype):
+        """A NEW index with the same cells stored as "fp16" or "fp32" (``rescaled`` without a scale: float32 -> float16 rounds to nearest
+        even, float16 -> float32 is exact), converted on the GPU."""
+        if dtype is None:
+            raise ValueError("astype needs a dtype: 'fp16' or 'fp32'")
+        return self.rescaled(dtype=dtype)
+
+    def idf_weights(self, k: float = 0.5):
+        """float32 [V]: log(1 + (N - df + k) / (df + k)) per column, N the live documents and df the live documents that store the column
+        with a non-zero value (term_counts()), computed in float64 on the device; 0 where df is 0.  ``rescaled(col_scale=idf_weights())``
+        of a BoTIndex is the IDF-weighted lexical index."""
+        df = self.term_counts().counts[0].to(torch.float64)
+        n = float(self.n_live)
+        w = torch.log(1.0 + (n - df + float(k)) / (df + float(k)))
+        return self._to_api(torch.where(df > 0, w, torch.zeros_like(w)).to(torch.float32))
+
     # ---- sub-index (not in the reference: a document set, or the whole index in another order, as a new index) ----------------------------------
     def _set_member_ids(self, filter):
         """every live document of ONE set (a shared filter, or None = all) in ascending order: int64 tensor on the search target's GPU, listed
@@ -2221,5 +2299,5 @@ class BoTIndex(SparseIndex):
                  device: str = "cpu", low_memory: bool = False, shift: int = 0, devices=None):
         super().__init__(index_file, data_file, fp16, device, low_memory, shift, devices)
 
-    def _binary(self) -> bool:
-        return True
+    def _binary(self) -> bool:                                      # the ONLY difference from SparseIndex: rescaled() relies on it when it hands
+        return True                                                 # a copy of a BoTIndex back as a SparseIndex

@@ -797,6 +797,45 @@ class Retriever(BiEncoder):
             self.index = new
         return new
 
+    def normalize_index(self, p=2, inplace: bool = False, index: Index = None) -> Index:
+        """Index.normalized -> the index with every document at unit length (cosine ranking on the fast path); inplace: it replaces
+        retriever.index (the old index object stays valid for whoever holds it)."""
+        index = index or self.index
+        if index is None:
+            raise RuntimeError("no index: call build_index / load_index first")
+        new = index.normalized(p)
+        if inplace:
+            self.index = new
+        return new
+
+    def reweight_index(self, token_weights=None, idf: bool = False, dtype=None, inplace: bool = False, index: Index = None) -> Index:
+        """Index.rescaled by column -> the reweighted index.  token_weights: {column id or vocabulary token: weight} (tokens resolved the way
+        prune_index resolves drop_tokens; the columns not named keep weight 1); idf: multiply in Index.idf_weights() (float32 product).  With
+        neither the index is only converted to `dtype`.  inplace: it replaces retriever.index."""
+        from ...doc_filter import terms_to_columns
+        index = index or self.index
+        if index is None:
+            raise RuntimeError("no index: call build_index / load_index first")
+        scale = None
+        if idf:
+            scale = index.idf_weights().cpu().numpy()
+        if token_weights is not None:
+            if not hasattr(token_weights, "items"):
+                raise TypeError(f"token_weights must be a dict of token -> weight, got {type(token_weights).__name__}")
+            keys = list(token_weights.keys())
+            cols = terms_to_columns(keys, self.encoder_p.tokenizer.vocab, int(self.encoder_p.config.shift_vocab_num), "token_weights")
+            n_cols = int(index._vector_meta()[0][1])
+            if scale is None:
+                scale = np.ones(n_cols, dtype=np.float32)
+            for c, key in zip(cols, keys):
+                if isinstance(c, bool) or not isinstance(c, (int, np.integer)) or not 0 <= int(c) < n_cols:
+                    raise ValueError(f"token_weights: {key!r} is not a column in [0, {n_cols})")
+                scale[int(c)] = np.float32(scale[int(c)]) * np.float32(token_weights[key])
+        new = index.rescaled(col_scale=scale, dtype=dtype)
+        if inplace:
+            self.index = new
+        return new
+
     def subset_index(self, filter=None, query=None, min_score=None, ids=None, inplace: bool = True, index: Index = None) -> Index:
         """Index.subset -> the new index of a document set: `filter`, or the documents one `query` (a text, or its embedding [1, V]) scores at
         least `min_score`, or the documents `ids` in that order; inplace: it replaces retriever.index (the old index object stays valid for
