@@ -1064,6 +1064,48 @@ VS_API int vs_rescale_plan(int64_t n_rows, int64_t n_packets, int32_t n_cols, in
 VS_API int vs_index_rescale(const vs_index* src, const float* row_scale, const float* col_scale, int out_dtype, int64_t rows_extra,
                             int64_t packets_extra, int device, vs_index** out);
 
+/* ---- combined index: the weighted cell-wise sum of two indexes of the same rows (no reference counterpart: the reference adds its tensors) ---------
+ * Every index-to-index call above keeps or shrinks the source's sparsity.  vs_index_combine makes a NEW index on GPU `device` whose row r is
+ * wa * (row r of a) + wb * (row r of b), cell by cell.  A score is linear in the stored cells -- q . (wa A + wb B)^T = wa q . A^T + wb q . B^T --, so
+ * a search of the result ranks by the weighted sum of the two scores, over the whole corpus.  `a` and `b` are untouched.
+ *   - sources: CSR-kind indexes (fp32, fp16 or binary store, independently) on the same GPU with equal n_rows and equal n_cols; a == b is
+ *     allowed.  A dense matrix index: VS_EUNSUPPORTED; a dense index stored as packets is combined like any other (the result is reported
+ *     VS_KIND_DENSE when both sources are).  Unequal shapes, different devices, NULL handles, out_dtype outside {VS_F32, VS_F16}: VS_EINVAL
+ *     (VS_NONE: binarising is not covered).
+ *   - the columns of result row r: the set of columns either source row stores, each once, in ASCENDING column order, 8 to a packet, the last
+ *     packet padded with column id n_cols and value +0; a row with no cell has 0 packets.  The sparsity is the union of the STORED cells: an
+ *     explicitly stored zero is a cell, and a sum that cancels to zero stays a cell.  The stored order inside the source rows is arbitrary
+ *     and does not enter.
+ *   - a source row that stores one column twice would make the sum depend on the order: VS_EINVAL naming the source and the lowest such row
+ *     (index a before index b at the same row).  The count step finds it on the device; nothing is allocated for the result.
+ *   - values: w = the stored value widened to fp32 (1 for a binary source); a column in both rows gets x = fp64(wa) * fp64(w_a) + fp64(wb) *
+ *     fp64(w_b), a column in one row the one product, in fp64 -- each product is exact there, the sum is rounded once.  The stored value is
+ *     fl32(x), for a fp16 result fl16(fl32(x)), both roundings to nearest even: numpy's np.float32(np.float64(wa) * a + np.float64(wb) * b)
+ *     reproduces every bit.  Weights are data: 0, negative, infinite and NaN weights give the IEEE result (a NaN result is any NaN);
+ *     subnormal results are kept, never flushed.
+ *   - tombstones: cells come from the stored rows whether or not a row is deleted; the result's deleted rows are a's OR b's, and
+ *     vs_index_restore_rows brings them back combined.  The result has no postings copy yet (vs_index_prepare).
+ *   - rows_extra / packets_extra / device, the 2^32 row and packet limits and the VS_ENOMEM naming the bytes are vs_index_prune's; nnz = the
+ *     union cells; lanes_per_row is picked for the new shape.  Blocking.
+ * Three steps on the sources' GPU.  count: a wave a row sets the row's columns in two per-wave LDS bitmaps of n_cols bits (LDS atomicOr; a
+ *   bit found set already is the repeated column), counts b's cells whose bit a's bitmap lacks -- the union is a's cells plus those -- and
+ *   clears the words it set by walking the packets again.  scan: the new row pointers, the non-zeros summed on the way.  fill: the same
+ *   bitmaps plus a per-word exclusive popcount prefix of the union; a cell's place in the result row is prefix[word] + popc(union bits below
+ *   it) -- no sort and no atomic decides a place.  The row is staged in LDS, one 32-bit slot a union cell: a's lanes store the final bits of
+ *   the columns b lacks and the raw value of the shared ones, b's lanes then finish the shared columns and their own; ids (from the union's
+ *   set bits) and values leave as 16-byte stores.  Rows with cells_a + cells_b <= wave_cells (2048) are filled a wave a row, four waves a
+ *   workgroup (a row of up to 1024 cells a side is read once and held in registers, a longer one is read again by every pass); a longer row by one 1024-thread
+ *   workgroup, whose slots hold a union of up to group_cells (32 768) cells.  A larger union is
+ *   possible only beyond 32 768 columns: VS_EUNSUPPORTED from the count step, naming the row.
+ * vs_combine_plan: pure host arithmetic, no device -- the limits of the two routes, the LDS of a fill workgroup of either route, and the
+ *   scratch the call allocates next to the three indexes (4 bytes a row, the list of long rows, the scan's block sums).  Any output may be
+ *   NULL.  n_cols > 65535: VS_EUNSUPPORTED; a bad dtype, out_dtype VS_NONE, a negative count: VS_EINVAL.                                    */
+VS_API int vs_combine_plan(int64_t n_rows, int64_t packets_a, int64_t packets_b, int32_t n_cols, int dtype_a, int dtype_b, int out_dtype,
+                           int32_t* out_wave_cells, int32_t* out_group_cells, int32_t* out_wave_lds_bytes, int32_t* out_group_lds_bytes,
+                           int64_t* out_scratch_bytes);
+VS_API int vs_index_combine(const vs_index* a, const vs_index* b, float wa, float wb, int out_dtype, int64_t rows_extra, int64_t packets_extra,
+                            int device, vs_index** out);
+
 /* ---- term constraints: must / must-not / should filters built from the index's own columns (no reference counterpart) --------------------
  * A row HAS term c (a column id in [0, n_cols)) iff it stores column c with a non-zero value; under a threshold thr, iff the stored value
  * v satisfies v >= thr (an fp16 store widens exactly, as vs_index_get_rows; a binary index stores 1; a stored zero counts under thr <= 0).

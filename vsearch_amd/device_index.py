@@ -292,6 +292,40 @@ def rescale_plan(n_rows, n_packets, n_cols, src_dtype, out_dtype, has_row_scale=
     return scratch.value, lds.value, COL_SCALE_ROUTES[route.value]
 
 
+class CombinePlan(NamedTuple):
+    """combine_plan(): wave_cells -- rows whose stored cells on both sides together are at most this many are filled a wave a row --,
+    group_cells -- the largest union a longer row, filled by a workgroup, may have --, the LDS bytes of a fill workgroup of either route, and
+    the scratch bytes the call allocates next to the three indexes."""
+    wave_cells: int
+    group_cells: int
+    wave_lds_bytes: int
+    group_lds_bytes: int
+    scratch_bytes: int
+
+
+def combine_plan(n_rows, packets_a, packets_b, n_cols, dtype_a, dtype_b, out_dtype):
+    """vs_combine_plan (pure host arithmetic) -> CombinePlan"""
+    wc, gc, wl, gl, scratch = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int64(0)
+    nat.check(nat.lib().vs_combine_plan(int(n_rows), int(packets_a), int(packets_b), int(n_cols), int(dtype_a), int(dtype_b), int(out_dtype),
+                                        C.byref(wc), C.byref(gc), C.byref(wl), C.byref(gl), C.byref(scratch)))
+    return CombinePlan(wc.value, gc.value, wl.value, gl.value, scratch.value)
+
+
+def _combine_dtype(dtype, dtype_a, dtype_b):
+    """out_dtype of combine(): None gives fp32, unless both sources are fp16"""
+    if dtype is None:
+        return nat.VS_F16 if dtype_a == nat.VS_F16 and dtype_b == nat.VS_F16 else nat.VS_F32
+    return _rescale_dtype(dtype, nat.VS_F32)
+
+
+def _combine_weight(w, name):
+    """A weight of combine() -> float (rounded to float32 by the call); anything that is not a real number is a TypeError"""
+    if isinstance(w, bool) or not isinstance(w, (int, float, np.integer, np.floating)):
+        raise TypeError(f"{name} must be a number, got {type(w).__name__}")
+    with np.errstate(over="ignore"):
+        return float(np.float32(w))
+
+
 def _select_ids(ids):
     """The id list of select_rows() -> (int64 1-D numpy array | CUDA tensor, on_device); an empty list is a ValueError (checked before the
     library is reached)."""
@@ -3278,6 +3312,46 @@ class DeviceIndex:
             nat.check(nat.lib().vs_index_rescale(*args))
         return DeviceIndex(h)
 
+    # ---- combined index ---------------------------------------------------------------------------------
+    def combine_plan(self, other, dtype=None) -> CombinePlan:
+        """what combine() with `other` would take -> CombinePlan (vs_combine_plan: pure host arithmetic)"""
+        if not isinstance(other, DeviceIndex):
+            raise TypeError(f"other must be a DeviceIndex, got {type(other).__name__}")
+        a, b = self.info(), other.info()
+        return combine_plan(a.n_rows, a.n_packets, b.n_packets, a.n_cols, a.store_dtype, b.store_dtype,
+                            _combine_dtype(dtype, int(a.store_dtype), int(b.store_dtype)))
+
+    def combine(self, other, wa=1.0, wb=1.0, dtype=None, rows_extra: int = 0, packets_extra: int = 0, device: int = None) -> "DeviceIndex":
+        """-> a new DeviceIndex whose row r is wa * (row r of this index) + wb * (row r of `other`), cell by cell (vs_index_combine): the
+        columns of a row are the union of the columns either row stores, in ascending order -- a stored zero is a cell, a sum that cancels
+        stays one --; a value is np.float32(np.float64(wa) * a + np.float64(wb) * b), the one product where one side lacks the column, a
+        binary side counting 1, then rounded to float16 for dtype "fp16".  A score is linear in the cells, so searching the result ranks by
+        wa * (this index's score) + wb * (other's score) over every row.  other: a DeviceIndex of the same rows and columns on the same GPU
+        (any store; `self` itself is allowed).  dtype: "fp32" | "fp16" | None = fp32 unless both sources are fp16.  A row that stores a
+        column twice raises ValueError naming it; a dense matrix index NotImplementedError.  Deleted rows: either side's.  Both indexes are
+        untouched.  rows_extra / packets_extra / device as in compact(), and prune()'s retry: if HBM cannot hold all three, the sources'
+        postings copies are dropped (prepare() rebuilds them) and the call retried once."""
+        if not isinstance(other, DeviceIndex):
+            raise TypeError(f"other must be a DeviceIndex, got {type(other).__name__}")
+        wa, wb = _combine_weight(wa, "wa"), _combine_weight(wb, "wb")
+        rows_extra, packets_extra = _compact_args(rows_extra, packets_extra)
+        nat.require_device()
+        out_dtype = _combine_dtype(dtype, int(self.info().store_dtype), int(other.info().store_dtype))
+        device = self.device if device is None else int(device)
+        h = C.c_void_p()
+        args = (self._h, other._h, C.c_float(wa), C.c_float(wb), out_dtype, rows_extra, packets_extra, device, C.byref(h))
+        try:
+            nat.check(nat.lib().vs_index_combine(*args))
+        except MemoryError:
+            holders = [x for x in ((self,) if other is self else (self, other)) if x.info().aux_bytes]
+            if not holders:
+                raise
+            for x in holders:
+                x.set_option("blocked_postings", 0)            # releases the copy; back to auto for the next prepare()
+                x.set_option("blocked_postings", -1)
+            nat.check(nat.lib().vs_index_combine(*args))
+        return DeviceIndex(h)
+
     # ---- term constraints (vsearch_amd.doc_filter.DocFilter.from_terms) ------------------------------
     def _term_words(self, cols, thr=None, want_df=False, live_only=True, ld=None):
         info = self.info()
@@ -4148,6 +4222,31 @@ class ShardGroup:
             last = i == len(self._shards) - 1
             rs = row_scale[row0:row0 + sh.n_rows] if row_scale is not None else None
             new.append(sh.rescale(rs, col_scale, dtype, rows_extra if last else 0, packets_extra if last else 0))
+        return ShardGroup(new)
+
+    # ---- combined index ---------------------------------------------------------------------------------------
+    def _same_cuts(self, other):
+        if not isinstance(other, ShardGroup):
+            raise TypeError(f"other must be a ShardGroup, got {type(other).__name__}")
+        mine, theirs = [s.n_rows for s in self._shards], [s.n_rows for s in other._shards]
+        if mine != theirs:
+            raise ValueError(f"the other group is cut into rows {theirs}, this group into {mine}: shard i is combined with shard i")
+
+    def combine_plan(self, other, dtype=None):
+        """DeviceIndex.combine_plan of every pair of shards -> a list of CombinePlan"""
+        self._same_cuts(other)
+        return [a.combine_plan(b, dtype) for a, b in zip(self._shards, other._shards)]
+
+    def combine(self, other, wa=1.0, wb=1.0, dtype=None, rows_extra: int = 0, packets_extra: int = 0) -> "ShardGroup":
+        """DeviceIndex.combine shard by shard on the shards' own GPUs -> a new ShardGroup cut at the same rows.  other: a ShardGroup cut at
+        the same rows, shard i on shard i's GPU (else ValueError).  Every row is independent, so the shards side by side are the unsharded
+        result bit for bit.  The spare capacity goes to the last shard."""
+        self._same_cuts(other)
+        rows_extra, packets_extra = _compact_args(rows_extra, packets_extra)
+        new = []
+        for i, (a, b) in enumerate(zip(self._shards, other._shards)):
+            last = i == len(self._shards) - 1
+            new.append(a.combine(b, wa, wb, dtype, rows_extra if last else 0, packets_extra if last else 0))
         return ShardGroup(new)
 
     # ---- term constraints -----------------------------------------------------------------------------------

@@ -30,7 +30,7 @@ from ...device_index import FacetValueHistogram, FacetValueStats
 from ...device_index import FacetValuePercentiles, MAX_VALUE_RANKS
 from ...device_index import SetIds, SetSample, _set_sample_args, _set_window_args, MAX_SET_IDS
 from ...device_index import _select_ids, _value_keys
-from ...device_index import RowStats, _rescale_dtype
+from ...device_index import RowStats, _rescale_dtype, _combine_dtype
 from ...device_index import BOOST_MODES, MAX_BOOST_FIELDS
 from ...device_index import _col_mask
 from ...device_index import LabelTermCounts, LabelTermSums, _label_top_terms, _label_top_weights
@@ -1613,6 +1613,51 @@ class Index:
         if isinstance(new, BoTIndex):
             new.__class__ = SparseIndex                             # a valued index now (BoTIndex adds nothing to SparseIndex but _binary(): see there)
         new._vector = None                                          # re-exported from the rescaled rows on demand
+        new._dev = None
+        new._dtype = torch.float16 if out_dtype == nat.VS_F16 else torch.float32
+        for name in ("_facets", "_values"):                         # the columns are shared, the registries are the new index's own
+            if getattr(self, name, None) is not None:
+                setattr(new, name, dict(getattr(self, name)))
+        if sharded:
+            new._shards, new._group = None, None
+            new._adopt_shards(list(new_target._shards))
+            new_target.close()
+        else:
+            new._dev = new_target
+            new._prepare()
+        return new
+
+    # ---- combined index (not in the reference: the weighted cell-wise sum of two indexes of the same documents) -------------------------------
+    def combined(self, other, weight=1.0, other_weight=1.0, dtype=None):
+        """A NEW SparseIndex whose document r is weight * (document r of this index) + other_weight * (document r of `other`), cell by cell
+        over the union of the two documents' stored columns (vs_index_combine on the GPU; both indexes are left exactly as they were).  A
+        score is linear in the stored cells, so ``combined.search(q, k)`` is the exact top k of weight * score + other_weight * other's score
+        over the whole corpus -- the hybrid ranking that search_hybrid only approximates from candidate lists:
+        ``sparse.combined(bot.rescaled(col_scale=bot.idf_weights()), 1.0, 0.3).search(q, k)``.  other: any SparseIndex / BoTIndex of the
+        same length and width (a bag-of-token cell counts 1).  dtype: "fp32" | "fp16" | None = fp32 unless both store fp16.  Ids do not
+        move: the new index shares this index's text store, groups, facet and value fields, as ``rescaled`` does; a document deleted in
+        either index is deleted.  A BoTIndex comes back valued, as a SparseIndex.  Row-sharded indexes are combined shard by shard on
+        their GPUs and have to be cut at the same rows.  A document that stores a column twice raises ValueError; a dense Index
+        NotImplementedError."""
+        if not isinstance(other, Index):
+            raise TypeError(f"other must be an index of the same documents, got {type(other).__name__}")
+        if not isinstance(self, SparseIndex) or not isinstance(other, SparseIndex):
+            raise NotImplementedError("combined() adds the stored cells of two SparseIndex / BoTIndex: a dense Index has none (build it sparse)")
+        target, gpu_ord = self._explain_target()
+        o_target = other._explain_target()[0]
+        sharded = isinstance(target, ShardGroup)
+        if isinstance(o_target, ShardGroup) != sharded:
+            raise ValueError("other must be row-sharded exactly as this index is (or neither)")
+        first, o_first = (target._shards[0], o_target._shards[0]) if sharded else (target, o_target)
+        if len(self) != len(other) or int(first.info().n_cols) != int(o_first.info().n_cols):
+            raise ValueError(f"this index is {len(self)} x {int(first.info().n_cols)}, other {len(other)} x {int(o_first.info().n_cols)}: "
+                             f"document r is combined with document r, column by column")
+        out_dtype = _combine_dtype(dtype, int(first.info().store_dtype), int(o_first.info().store_dtype))
+        new_target = target.combine(o_target, weight, other_weight, out_dtype)
+        new = copy.copy(self)                                       # the text store (data / offsets) is shared: ids did not move
+        if isinstance(new, BoTIndex):
+            new.__class__ = SparseIndex                             # a valued index now
+        new._vector = None                                          # re-exported from the combined rows on demand
         new._dev = None
         new._dtype = torch.float16 if out_dtype == nat.VS_F16 else torch.float32
         for name in ("_facets", "_values"):                         # the columns are shared, the registries are the new index's own

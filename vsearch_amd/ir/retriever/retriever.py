@@ -836,6 +836,18 @@ class Retriever(BiEncoder):
             self.index = new
         return new
 
+    def combine_index(self, other: Index, weight=1.0, other_weight=1.0, inplace: bool = False, dtype=None, index: Index = None) -> Index:
+        """Index.combined -> the index of weight * retriever.index + other_weight * other, cell by cell: its search is the exact hybrid
+        ranking by the weighted sum of the two scores.  other: an index of the same documents (e.g. the bag-of-token index, rescaled by
+        idf_weights()).  inplace: it replaces retriever.index (the old index object stays valid for whoever holds it)."""
+        index = index or self.index
+        if index is None:
+            raise RuntimeError("no index: call build_index / load_index first")
+        new = index.combined(other, weight, other_weight, dtype=dtype)
+        if inplace:
+            self.index = new
+        return new
+
     def subset_index(self, filter=None, query=None, min_score=None, ids=None, inplace: bool = True, index: Index = None) -> Index:
         """Index.subset -> the new index of a document set: `filter`, or the documents one `query` (a text, or its embedding [1, V]) scores at
         least `min_score`, or the documents `ids` in that order; inplace: it replaces retriever.index (the old index object stays valid for
