@@ -1106,6 +1106,41 @@ VS_API int vs_combine_plan(int64_t n_rows, int64_t packets_a, int64_t packets_b,
 VS_API int vs_index_combine(const vs_index* a, const vs_index* b, float wa, float wb, int out_dtype, int64_t rows_extra, int64_t packets_extra,
                             int device, vs_index** out);
 
+/* ---- joined index: the rows of several indexes, one source behind the other, as a new index (reference: vstack(shards), index.py:172-175) --------
+ * vs_index_select_rows picks rows of ONE index, vs_index_combine unions the cells of two indexes of the same rows; vs_index_concat puts the
+ * rows of srcs[1] behind those of srcs[0], and so on: a NEW index on GPU `device`.  The sources are untouched.
+ *   - sources: n_src in 1..256 CSR-kind handles on one GPU with equal n_cols; fp32, fp16 and binary stores may be mixed freely, the same handle
+ *     may appear more than once, a source with 0 rows contributes nothing.  A total of 0 rows: VS_EINVAL ("empty join").  A dense matrix index:
+ *     VS_EUNSUPPORTED; a dense index stored as packets joins like any other (the result is reported VS_KIND_DENSE only when every source is).
+ *     A NULL handle, unequal widths, sources on different GPUs, n_src outside 1..256, negative extras: VS_EINVAL.
+ *   - out_dtype: VS_F32 or VS_F16; VS_NONE only when every source is binary -- the result is then binary --, otherwise VS_EINVAL (binarising
+ *     is not covered).
+ *   - row pointers: with R_s and P_s the rows and the packets of the sources before source s, new row pointer R_s + r is src_pk_s[r] + P_s;
+ *     the last pointer is the packet total.
+ *   - packets move whole: the 16 bytes of column ids, padding included, are copied bit for bit.  A source whose store equals out_dtype has its
+ *     value bits copied; a source of another store is converted cell by cell under vs_index_rescale's rule with no scale: fp16 -> fp32 is
+ *     exact, fp32 -> fp16 rounds once to nearest even (overflow to +-inf, subnormals kept, a NaN stays a NaN), a binary source's real cell
+ *     becomes 1.0, and a padding cell keeps id n_cols and value +0 whatever the source store was.  A row therefore scores bit for bit what
+ *     it scored in a source of the result's dtype.
+ *   - tombstones travel with the rows: a result row is deleted iff its source row is.  When no source row is deleted the handle has no live
+ *     bitmap: it behaves, and is written to .vsx, as an index built from the joined CSR.  Bits past the last row stay set.
+ *   - nnz is the sum of the sources' nnz, lanes_per_row is picked for the new shape, the result has no postings copy yet (vs_index_prepare).
+ *   - rows_extra / packets_extra / device, the 2^32 row and packet limits, the VS_ENOMEM naming the bytes and the move to another GPU are
+ *     vs_index_select_rows's.  Blocking.
+ * Two launches on the sources' GPU whatever n_src is.  A device table of per-source entries (row base, packet base, the four array pointers,
+ * the store, the live words or NULL) is read into LDS once by every workgroup.  map: a thread a result row finds its source by a branch-free
+ * search over the row bases and writes the rebased pointer; with tombstones on any source the live words of the new rows, two whole words a
+ * wave from a ballot, and the dead count.  copy: a wave takes 256 contiguous result packets, a lane a packet of each 64-packet step; a step
+ * whose first and last packet fall into one source takes that source for all lanes (decided wave-uniformly), a step across a boundary
+ * searches a lane at a time; the loads of four steps, 16 bytes each, are in flight before the first store, values are converted in registers.
+ * vs_concat_plan: pure host arithmetic, no device -- rows [n_src], packets [n_src], dtypes [n_src] of the sources -> the totals, the scratch
+ *   the call allocates next to the indexes (48 bytes a source for the table + the counters) and the LDS of a workgroup.  Any output may be
+ *   NULL.  The shape errors of the call; n_cols > 65535 and totals of 2^32 - 1 rows or 2^32 packets and more: VS_EUNSUPPORTED.              */
+VS_API int vs_concat_plan(int32_t n_src, const int64_t* rows, const int64_t* packets, int32_t n_cols, const int* dtypes, int out_dtype,
+                          int64_t* out_rows, int64_t* out_packets, int64_t* out_scratch_bytes, int32_t* out_lds_bytes);
+VS_API int vs_index_concat(const vs_index* const* srcs, int32_t n_src, int out_dtype, int64_t rows_extra, int64_t packets_extra,
+                           int device, vs_index** out);
+
 /* ---- term constraints: must / must-not / should filters built from the index's own columns (no reference counterpart) --------------------
  * A row HAS term c (a column id in [0, n_cols)) iff it stores column c with a non-zero value; under a threshold thr, iff the stored value
  * v satisfies v >= thr (an fp16 store widens exactly, as vs_index_get_rows; a binary index stores 1; a stored zero counts under thr <= 0).

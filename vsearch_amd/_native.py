@@ -167,6 +167,8 @@ _SIGNATURES = {
     "vs_index_rescale": ([_vp, _vp, _vp, _int, _i64, _i64, _int, C.POINTER(_vp)], _int),
     "vs_combine_plan": ([_i64, _i64, _i64, _i32, _int, _int, _int, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i64)], _int),
     "vs_index_combine": ([_vp, _vp, C.c_float, C.c_float, _int, _i64, _i64, _int, C.POINTER(_vp)], _int),
+    "vs_concat_plan": ([_i32, _vp, _vp, _i32, _vp, _int, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i64), C.POINTER(_i32)], _int),
+    "vs_index_concat": ([_vp, _i32, _int, _i64, _i64, _int, C.POINTER(_vp)], _int),
     "vs_index_term_bitmaps": ([_vp, _vp, _vp, _i32, _vp, _i64, _vp, _int, _vp], _int),
     "vs_term_filter_combine": ([_vp, _i64, _i64, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i32, _vp, _i64, _int, _vp], _int),
     "vs_index_prepare": ([_vp, _vp], _int),

@@ -326,6 +326,58 @@ def _combine_weight(w, name):
         return float(np.float32(w))
 
 
+class ConcatPlan(NamedTuple):
+    """concat_plan(): the rows and the packets of the joined index, the scratch bytes the call allocates next to the indexes (the source
+    table and the counters) and the LDS bytes of a workgroup (the table's image)."""
+    rows: int
+    packets: int
+    scratch_bytes: int
+    lds_bytes: int
+
+
+CONCAT_MAX_SOURCES = 256                             # kConcatMaxSources
+
+
+def concat_plan(rows, packets, n_cols, dtypes, out_dtype) -> ConcatPlan:
+    """vs_concat_plan (pure host arithmetic) -> ConcatPlan.  rows, packets, dtypes: one entry a source (dtypes: VS_F32 | VS_F16 | VS_NONE);
+    out_dtype: VS_F32 | VS_F16, or VS_NONE when every source is binary."""
+    rows = np.ascontiguousarray(rows, dtype=np.int64)
+    packets = np.ascontiguousarray(packets, dtype=np.int64)
+    dtypes = np.ascontiguousarray(dtypes, dtype=np.int32)
+    if rows.ndim != 1 or packets.shape != rows.shape or dtypes.shape != rows.shape:
+        raise ValueError("rows, packets and dtypes must be 1-D with one entry a source")
+    r, k, scratch, lds = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int32(0)
+    ptr = lambda a: C.c_void_p(a.ctypes.data) if a.size else None
+    nat.check(nat.lib().vs_concat_plan(int(rows.size), ptr(rows), ptr(packets), int(n_cols), ptr(dtypes), int(out_dtype), C.byref(r), C.byref(k),
+                                       C.byref(scratch), C.byref(lds)))
+    return ConcatPlan(r.value, k.value, scratch.value, lds.value)
+
+
+def _concat_dtype(dtype, src_dtypes):
+    """out_dtype of concat(): None gives binary if every source is binary, fp16 if every valued source stores fp16, else fp32"""
+    if dtype is None:
+        valued = [d for d in src_dtypes if d != nat.VS_NONE]
+        if not valued:
+            return nat.VS_NONE
+        return nat.VS_F16 if all(d == nat.VS_F16 for d in valued) else nat.VS_F32
+    if dtype in ("binary", nat.VS_NONE) and not isinstance(dtype, bool):
+        if any(d != nat.VS_NONE for d in src_dtypes):
+            raise ValueError("dtype 'binary' with a valued source: binarising an index is not covered ('fp32' or 'fp16')")
+        return nat.VS_NONE
+    return _rescale_dtype(dtype, nat.VS_F32)
+
+
+def _concat_sources(first, others, cls):
+    """[first] + others as a list of `cls`; others: one index or a sequence of them.  More than CONCAT_MAX_SOURCES raise ValueError"""
+    others = [others] if isinstance(others, cls) else list(others)
+    for o in others:
+        if not isinstance(o, cls):
+            raise TypeError(f"others must be {cls.__name__}s, got {type(o).__name__}")
+    if 1 + len(others) > CONCAT_MAX_SOURCES:
+        raise ValueError(f"a join takes at most {CONCAT_MAX_SOURCES} sources, got {1 + len(others)} (join in stages)")
+    return [first] + others
+
+
 def _select_ids(ids):
     """The id list of select_rows() -> (int64 1-D numpy array | CUDA tensor, on_device); an empty list is a ValueError (checked before the
     library is reached)."""
@@ -3352,6 +3404,43 @@ class DeviceIndex:
             nat.check(nat.lib().vs_index_combine(*args))
         return DeviceIndex(h)
 
+    # ---- joined index -----------------------------------------------------------------------------------
+    def concat_plan(self, others, dtype=None) -> ConcatPlan:
+        """what concat() with `others` would take -> ConcatPlan (vs_concat_plan: pure host arithmetic)"""
+        infos = [x.info() for x in _concat_sources(self, others, DeviceIndex)]
+        dts = [int(i.store_dtype) for i in infos]
+        return concat_plan([i.n_rows for i in infos], [i.n_packets for i in infos], infos[0].n_cols, dts, _concat_dtype(dtype, dts))
+
+    def concat(self, others, dtype=None, rows_extra: int = 0, packets_extra: int = 0, device: int = None) -> "DeviceIndex":
+        """-> a new DeviceIndex whose rows are this index's, then those of others[0], and so on (vs_index_concat): packets are copied whole,
+        so a row scores bit for bit what it scored in a source of the result's dtype.  others: a DeviceIndex or a sequence of them (up to
+        256 sources in all), on this index's GPU, of the same n_cols; fp32, fp16 and binary stores may be mixed, the same index may appear
+        more than once, an index without rows contributes nothing.  dtype: "fp32" | "fp16" | "binary" | None = binary if all sources are
+        binary, fp16 if all valued sources store fp16, else fp32.  A source of another store is converted cell by cell: fp16 -> fp32 exactly,
+        fp32 -> fp16 rounded once to nearest even, a binary cell becomes 1; "binary" with a valued source raises ValueError.  Deleted rows
+        are carried as deleted.  Every source is untouched.  A dense matrix index raises NotImplementedError.  rows_extra / packets_extra /
+        device as in compact(), and prune()'s retry: if HBM cannot hold them all, the sources' postings copies are dropped (prepare()
+        rebuilds them) and the call retried once."""
+        srcs = _concat_sources(self, others, DeviceIndex)
+        rows_extra, packets_extra = _compact_args(rows_extra, packets_extra)
+        nat.require_device()
+        out_dtype = _concat_dtype(dtype, [int(x.info().store_dtype) for x in srcs])
+        device = self.device if device is None else int(device)
+        arr = (C.c_void_p * len(srcs))(*[x._h for x in srcs])
+        h = C.c_void_p()
+        args = (arr, len(srcs), out_dtype, rows_extra, packets_extra, device, C.byref(h))
+        try:
+            nat.check(nat.lib().vs_index_concat(*args))
+        except MemoryError:
+            holders = [x for x in {id(x): x for x in srcs}.values() if x.info().aux_bytes]
+            if not holders:
+                raise
+            for x in holders:
+                x.set_option("blocked_postings", 0)            # releases the copy; back to auto for the next prepare()
+                x.set_option("blocked_postings", -1)
+            nat.check(nat.lib().vs_index_concat(*args))
+        return DeviceIndex(h)
+
     # ---- term constraints (vsearch_amd.doc_filter.DocFilter.from_terms) ------------------------------
     def _term_words(self, cols, thr=None, want_df=False, live_only=True, ld=None):
         info = self.info()
@@ -4248,6 +4337,30 @@ class ShardGroup:
             last = i == len(self._shards) - 1
             new.append(a.combine(b, wa, wb, dtype, rows_extra if last else 0, packets_extra if last else 0))
         return ShardGroup(new)
+
+    # ---- joined index ---------------------------------------------------------------------------------------
+    def gathered(self, device: int = None, dtype=None) -> DeviceIndex:
+        """-> the group's rows as ONE DeviceIndex on GPU `device` (default: the first shard's), the shards one behind the other: global row
+        ids do not change, deleted rows stay deleted.  Every shard that lives elsewhere is brought to the target GPU with the device-to-device
+        slice (slice_rows(0, n, device)), then one concat() joins them; dtype as in DeviceIndex.concat.  During the call the target GPU holds
+        the moved shards AND the result at once -- twice the group's packets less the target's own shard; the moved copies are freed before
+        the call returns.  The group is untouched."""
+        nat.require_device()
+        device = self.device if device is None else int(device)
+        if len(self._shards) > CONCAT_MAX_SOURCES:
+            raise ValueError(f"a join takes at most {CONCAT_MAX_SOURCES} sources, the group has {len(self._shards)} shards")
+        moved, local = [], []
+        try:
+            for sh in self._shards:
+                if sh.device == device:
+                    local.append(sh)
+                else:
+                    local.append(sh.slice_rows(0, sh.n_rows, device))
+                    moved.append(local[-1])
+            return local[0].concat(local[1:], dtype=dtype, device=device)
+        finally:
+            for m in moved:
+                m.close()
 
     # ---- term constraints -----------------------------------------------------------------------------------
     def _term_words(self, cols, thr=None, want_df=False, live_only=True, ld=None):

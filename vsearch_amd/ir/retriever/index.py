@@ -31,6 +31,7 @@ from ...device_index import FacetValuePercentiles, MAX_VALUE_RANKS
 from ...device_index import SetIds, SetSample, _set_sample_args, _set_window_args, MAX_SET_IDS
 from ...device_index import _select_ids, _value_keys
 from ...device_index import RowStats, _rescale_dtype, _combine_dtype
+from ...device_index import CONCAT_MAX_SOURCES, _concat_dtype
 from ...device_index import BOOST_MODES, MAX_BOOST_FIELDS
 from ...device_index import _col_mask
 from ...device_index import LabelTermCounts, LabelTermSums, _label_top_terms, _label_top_weights
@@ -1507,6 +1508,7 @@ class Index:
             self._dev = new
             self._prepare()
         self._vector = None                                         # re-exported from the new rows on demand
+        self._parts = None                                          # (the sources of a joined index no longer lie at their places)
         if self._shape is not None:
             self._shape = (int(old.shape[0]), self._shape[1])
         if self.groups is not None:                                 # new document j keeps the group of old_ids[j]
@@ -1724,6 +1726,7 @@ class Index:
         new._vector = None                                          # re-exported from the selected rows on demand
         new._dev = None
         new._source_ids = src
+        new._parts = None
         if self._shape is not None:
             new._shape = (int(src.shape[0]), self._shape[1])
         if self.data is not None or (self.low_memory and getattr(self, "offsets", None) is not None):
@@ -1797,6 +1800,97 @@ class Index:
             k = 0xFFFFFFFF - k
         k = torch.where(missing, torch.full_like(k, 1 << 32), k)
         return self._selected(live.index_select(0, torch.argsort(k, stable=True)))
+
+    # ---- joined index (the reference's load step, vstack(shards) at index.py:172-175, for indexes that are on the GPU already) -------------------
+    @staticmethod
+    def _concat_fields(sources):
+        """The field rules of ``concatenated`` over the source indexes, raised before any device work -> (grouped, {facet field: (n_labels,
+        names)}, [value fields]).  Groups: every source has them or none does.  A facet or value field of one source must exist in every
+        source; a facet field with equal names (or none anywhere: n_labels is the maximum), a value field with equal dtype."""
+        grouped = [getattr(s, "_groups", None) is not None for s in sources]
+        if any(grouped) and not all(grouped):
+            raise ValueError(f"groups: source {grouped.index(False)} has no groups, source {grouped.index(True)} has: every source has them or none does")
+        facets, values = {}, []
+        stores = [getattr(s, "_facets", None) or {} for s in sources]
+        for name in [n for st in stores for n in st]:
+            if name in facets:
+                continue
+            lacking = [i for i, st in enumerate(stores) if name not in st]
+            if lacking:
+                raise ValueError(f"facet field {name!r} is missing in source {lacking[0]}: a carried field must exist in every source")
+            names = [st[name][2] for st in stores]
+            if any(nm != names[0] for nm in names[1:]):
+                bad = next(i for i, nm in enumerate(names) if nm != names[0])
+                raise ValueError(f"facet field {name!r}: the label names of source {bad} differ from source 0's (codes are not remapped by name)")
+            facets[name] = (len(names[0]) if names[0] is not None else max(st[name][1] for st in stores), names[0])
+        stores = [getattr(s, "_values", None) or {} for s in sources]
+        for name in [n for st in stores for n in st]:
+            if name in values:
+                continue
+            lacking = [i for i, st in enumerate(stores) if name not in st]
+            if lacking:
+                raise ValueError(f"value field {name!r} is missing in source {lacking[0]}: a carried field must exist in every source")
+            dts = [st[name].dtype for st in stores]
+            if any(dt != dts[0] for dt in dts[1:]):
+                bad = next(i for i, dt in enumerate(dts) if dt != dts[0])
+                raise ValueError(f"value field {name!r} is {dts[0]} in source 0 and {dts[bad]} in source {bad}: the dtypes must be equal")
+            values.append(name)
+        return all(grouped), facets, values
+
+    def concatenated(self, *others, dtype=None):
+        """A NEW index of the class of this one holding this index's documents, then those of others[0], and so on (vs_index_concat on the
+        GPU; every source is left exactly as it was): document j of source s is document ``parts[s] + j`` of the result.  Rows are copied
+        whole, so a document scores bit for bit what it scored in a source of the result's dtype.  others: SparseIndex / BoTIndex of the same
+        width on this index's GPU, stored as fp32, fp16 or bag-of-token in any mix (up to 256 sources; the same index may appear twice).
+        dtype: "fp32" | "fp16" | None = bag-of-token if all are, fp16 if all valued sources store fp16, else fp32; a BoTIndex joined with a
+        valued index comes back a SparseIndex, its cells 1.  Carried: the texts, the `data` lists one behind the other, when EVERY source
+        holds its texts in memory -- otherwise the result has no text store, as an index built without a data file --; the groups (every
+        source has them or none does); the facet fields (a field must exist in every source with equal names; without names n_labels is
+        the maximum) and the value fields (in every source, of equal dtype) -- anything else raises ValueError naming the field before any
+        device work --; deletions travel with their documents.  Group ids and facet codes are taken as they are: not offset, not remapped.
+        A dense Index on the matrix cores raises NotImplementedError, as does a row-sharded source: ``unsharded()`` it first."""
+        sources = [self] + list(others)
+        for o in sources:
+            if not isinstance(o, Index):
+                raise TypeError(f"concatenated() joins indexes, got {type(o).__name__}")
+            if getattr(o, "_group", None) is not None:
+                raise NotImplementedError("a row-sharded index is not joined as it is: unsharded() makes it one index on one GPU first")
+        if not all(isinstance(o, SparseIndex) for o in sources):
+            raise NotImplementedError("concatenated() joins the stored rows of SparseIndex / BoTIndex: a dense Index has none (build it sparse)")
+        if len(sources) > CONCAT_MAX_SOURCES:
+            raise ValueError(f"a join takes at most {CONCAT_MAX_SOURCES} sources, got {len(sources)} (join in stages)")
+        grouped, facets, values = self._concat_fields(sources)
+        targets = [s._explain_target()[0] for s in sources]
+        gpu = torch.device("cuda", targets[0].device)
+        out_dtype = _concat_dtype(dtype, [int(t.info().store_dtype) for t in targets])
+        new_target = targets[0].concat(targets[1:], dtype=out_dtype)
+        counts = [int(t.n_rows) for t in targets]
+        new = copy.copy(self)
+        if out_dtype != nat.VS_NONE and isinstance(new, BoTIndex):
+            new.__class__ = SparseIndex                             # a valued index now
+        new._vector = None                                          # re-exported from the joined rows on demand
+        new._dev = None
+        new._source_ids = None
+        new._parts = torch.tensor(np.concatenate([[0], np.cumsum(counts)]), dtype=torch.int64)
+        if out_dtype != nat.VS_NONE:
+            new._dtype = torch.float16 if out_dtype == nat.VS_F16 else torch.float32
+        new._shape = (int(sum(counts)), int(targets[0].info().n_cols))
+        for gone in ("offsets", "data_file"):                       # texts on disk are not carried: the result has no text store then
+            new.__dict__.pop(gone, None)
+        new.low_memory = False
+        new.data = [x for s in sources for x in s.data] if all(s.data is not None and not s.low_memory for s in sources) else None
+        new._groups = torch.cat([s._groups.to(gpu) for s in sources]) if grouped else None
+        new._facets = {name: (torch.cat([s._facets[name][0].to(gpu) for s in sources]), n_labels, names) for name, (n_labels, names) in facets.items()} or None
+        new._values = {name: torch.cat([s._values[name].to(gpu) for s in sources]) for name in values} or None
+        new._dev = new_target
+        new._prepare()
+        return new
+
+    @property
+    def parts(self):
+        """int64 [S + 1] of an index ``concatenated`` made: document j of source s is document parts[s] + j (None for any other index, and
+        once ``subset`` / ``sorted_by`` / ``compact`` have moved the documents)"""
+        return getattr(self, "_parts", None)
 
     def _add_csr(self, vectors):
         """vectors -> (indptr, indices, data) of the rows to append"""
@@ -2011,6 +2105,28 @@ class SparseIndex(Index):
     def shard_devices(self):
         """GPU ordinal of every row shard (None: the index is not sharded)"""
         return [sh.device for sh in self._shards] if self._shards else None
+
+    def unsharded(self, device=None):
+        """A NEW index holding this row-sharded index as ONE index on one GPU (ShardGroup.gathered: every shard is brought to the target GPU
+        by a device-to-device copy, then one vs_index_concat joins them; this index is left exactly as it was).  device: a GPU ordinal or
+        "cuda:i", default the first shard's.  Ids do not move: the new index shares the text store, the groups, the facet and the value
+        fields, and carries the deletions, as ``rescaled`` does.  During the call the target GPU holds the moved shards and the result at
+        once.  ``index.unsharded().sorted_by(field)`` is the sorted order a sharded index cannot be given; the result can be cut into
+        another number of shards (shard_rows) or saved as one file.  An index that is not sharded raises ValueError."""
+        if self._group is None:
+            raise ValueError("the index is not row-sharded: there is nothing to gather")
+        gpu_ord = self._shards[0].device if device is None else (int(device) if isinstance(device, int) else _gpu_ordinal(device))
+        new_target = self._group.gathered(device=gpu_ord)
+        new = copy.copy(self)                                       # the text store (data / offsets) is shared: ids did not move
+        new._vector = None                                          # re-exported from the gathered rows on demand
+        new._shards, new._group, new._devices = None, None, None
+        for name in ("_facets", "_values"):                         # the columns are shared, the registries are the new index's own
+            if getattr(self, name, None) is not None:
+                setattr(new, name, dict(getattr(self, name)))
+        new.device = f"cuda:{gpu_ord}"
+        new._dev = new_target
+        new._prepare()
+        return new
 
     def search(self, q_embs: torch.Tensor, k: int, filter=None) -> SearchResults:
         if self._group is None:

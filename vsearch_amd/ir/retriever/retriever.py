@@ -848,6 +848,19 @@ class Retriever(BiEncoder):
             self.index = new
         return new
 
+    def merge_index(self, other, inplace: bool = True, index: Index = None, dtype=None) -> Index:
+        """Index.concatenated -> the index of retriever.index's documents with those of `other` (an index, or a sequence of them) behind
+        them: last night's documents, embedded and indexed as a small index of their own, join the main one without leaving the GPU.
+        inplace: it replaces retriever.index (the old index object stays valid for whoever holds it)."""
+        index = index or self.index
+        if index is None:
+            raise RuntimeError("no index: call build_index / load_index first")
+        others = [other] if isinstance(other, Index) else list(other)
+        new = index.concatenated(*others, dtype=dtype)
+        if inplace:
+            self.index = new
+        return new
+
     def subset_index(self, filter=None, query=None, min_score=None, ids=None, inplace: bool = True, index: Index = None) -> Index:
         """Index.subset -> the new index of a document set: `filter`, or the documents one `query` (a text, or its embedding [1, V]) scores at
         least `min_score`, or the documents `ids` in that order; inplace: it replaces retriever.index (the old index object stays valid for
