@@ -191,6 +191,21 @@ def test_row_counts(n_rows):
         check(build(cb, VN, nat.VS_NONE), build(ca, VN), 0.5, 2.0, "fp16")
 
 
+@pytest.mark.parametrize("n_rows", [4096, 4097])
+def test_row_pointers_from_unions_of_0_8_and_9_cells(n_rows):
+    """the scan from the union counts to the row pointers: one scan block, and a second block of one row; unions of no packet, exactly one packet
+    and one cell more"""
+    rng = np.random.default_rng(n_rows)
+    uni = rng.choice([0, 8, 9], size=n_rows)
+    uni[-1] = 9                                                                              # the row of the second block holds two packets
+    base = np.argsort(rng.random((n_rows, 60)), axis=1)
+    ca = from_rows([base[r, :min(uni[r], 5)] for r in range(n_rows)], rng)                   # 5 cells of a, cells 3 .. u of b: two shared columns
+    cb = from_rows([base[r, 3:uni[r]] for r in range(n_rows)], rng)
+    new, _ = check(build(ca, VN), build(cb, VN), 1.0, -0.5)
+    assert np.array_equal(new.export_csr()[0], np.concatenate([[0], np.cumsum(uni)]))
+    assert new.info().n_packets == int(((uni + 7) // 8).sum())
+
+
 def test_an_index_without_a_packet():
     rng = np.random.default_rng(4)
     full = build(from_rows(random_rows([3] * 70, VN, rng), rng), VN)

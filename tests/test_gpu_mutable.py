@@ -20,6 +20,8 @@ from vsearch_amd import _native as nat
 from vsearch_amd.device_index import DeviceIndex, ShardGroup
 from vsearch_amd.doc_filter import DocFilter
 
+import _select_ref as select_ref
+
 pytestmark = pytest.mark.gpu
 RTOL = 1e-4
 
@@ -339,6 +341,69 @@ def test_compact_equals_the_index_of_the_surviving_rows(store):
     assert (old2 == np.arange(keep.size)).all()
     for a, b in zip(copy.export_csr(), ref.export_csr()):
         assert (a == b).all()
+
+
+# The packets of a compaction move by the gather of the sub-index (select.hip): a wave takes a run of 64 new rows and rounds of four 64-packet
+# steps, 256 packets a round.  (cells of the source rows, surviving rows) at the edges of a run and of a round; a deleted row of 3 cells stands
+# before every survivor of the interleaved cases, so that no packet keeps its place.  Rows of 9 / 25 / 30 / 33 cells: 2 / 4 / 4 / 5 packets.
+def _before_each(lens):
+    src = np.full(2 * len(lens), 3, dtype=np.int64)
+    src[1::2] = lens
+    return src, np.arange(1, 2 * len(lens), 2)
+
+
+GATHER_CASES = {
+    "65 rows: a full run and a run of one row": _before_each([9] * 64 + [17]),
+    "a run of 257 packets: lane 0 of a second round": _before_each([9] * 64 + [25] * 63 + [33]),
+    "a run of exactly 256 packets: one round": _before_each([9] * 64 + [30] * 64),
+    "a run of empty rows between two runs": _before_each([9] * 64 + [0] * 64 + [9] * 64),
+    "the source's last row alone": (np.array([5, 9, 0, 17, 12]), np.array([4])),
+    "every row survives": (np.array([0, 1, 8, 9, 40] * 26), np.arange(130)),
+}
+
+
+@pytest.mark.parametrize("case", list(GATHER_CASES))
+@pytest.mark.parametrize("store", [nat.VS_F32, nat.VS_F16, nat.VS_NONE])
+def test_compact_moves_packets_by_the_shared_gather(store, case):
+    lens, keep = GATHER_CASES[case]
+    rng = np.random.default_rng(41)
+    ip = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    ix = np.concatenate([np.sort(rng.permutation(V)[:ln]) for ln in lens]).astype(np.int64)
+    d = rng.standard_normal(int(ip[-1])).astype(np.float32)
+    idx = DeviceIndex.from_csr(ip, ix, None if store == nat.VS_NONE else d, V, store_dtype=store)
+    src = idx.export_csr()                                             # the stored rows: fp16 values as stored
+    dead = np.setdiff1d(np.arange(len(lens)), keep)
+    if dead.size:
+        idx.delete_rows(dead)
+    new, old = idx.compact()
+    assert (old == keep).all()
+    want = select_ref.select_ref(*src, keep)                           # the host gather of the surviving rows
+    got = new.export_csr()
+    assert np.array_equal(got[0], want[0]), "row pointers"
+    assert np.array_equal(got[1], want[1]), "columns"
+    assert got[2].dtype == want[2].dtype == np.float32 and np.array_equal(got[2].view(np.uint32), want[2].view(np.uint32)), "value bits"
+    info = new.info()
+    assert (info.n_rows, info.nnz, info.n_packets) == (keep.size, int(lens[keep].sum()), int(((lens[keep] + 7) // 8).sum()))
+    assert info.store_dtype == store and new.n_live == keep.size
+
+
+@pytest.mark.parametrize("survivors", ["one row", "all but row 0"])
+def test_compact_gathers_the_rows_of_a_matrix(survivors):
+    n, Cc = 70, 96
+    rng = np.random.default_rng(43)
+    mat = rng.standard_normal((n, Cc)).astype(np.float32)
+    keep = np.array([37]) if survivors == "one row" else np.arange(1, n)
+    idx = DeviceIndex.from_dense(mat)
+    assert idx.info().n_packets == 0                                   # the matrix-core kind
+    idx.delete_rows(np.setdiff1d(np.arange(n), keep))
+    new, old = idx.compact()
+    assert (old == keep).all()
+    # the matrix as a CSR of full rows, gathered on the host
+    _, _, want = select_ref.select_ref(np.arange(n + 1) * Cc, np.tile(np.arange(Cc), n), mat.reshape(-1), keep)
+    got = new.export_dense()
+    assert got.shape == (keep.size, Cc) and np.array_equal(np.ascontiguousarray(got).view(np.uint32).reshape(-1), want.view(np.uint32))
+    info = new.info()
+    assert (info.n_rows, info.nnz, new.n_live) == (keep.size, keep.size * Cc, keep.size)
 
 
 def test_compact_a_dense_index_stored_as_packets():

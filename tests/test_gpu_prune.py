@@ -103,6 +103,12 @@ def test_row_counts_cross_the_scan_block(n_rows):
     src = build(make_csr(rng.integers(0, 21, size=n_rows), VN, rng), VN)
     out, want = check(src, topk=5)
     assert want[3].max() == 5 and (n_rows == 1 or want[3].min() == 0)
+    # the scan from the kept counts to the row pointers at the packet edge: rows that keep 0, 8 and 9 cells (no packet, one, two), no cut
+    lens = rng.choice([0, 8, 9], size=n_rows)
+    lens[-1] = 9
+    out, want = check(build(make_csr(lens, VN, rng), VN), topk=None)
+    assert np.array_equal(want[3], lens) and np.array_equal(out.export_csr()[0], np.concatenate([[0], np.cumsum(lens)]))
+    assert out.info().n_packets == int(((lens + 7) // 8).sum())
 
 
 # ---- ties at the cut ---------------------------------------------------------------------------------------------------------------------------------

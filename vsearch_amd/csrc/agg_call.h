@@ -17,14 +17,6 @@ namespace vs {
 
 inline int plan_or_fail(int rc, const char* msg) { return rc == VS_OK ? VS_OK : fail(rc, "%s", msg); }
 
-inline int device_in_range(int device) {
-    VS_TRY(need_device());
-    int ndev = 0;
-    VS_HIP(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(VS_EINVAL, "device %d out of range", device);
-    return VS_OK;
-}
-
 inline int finish_call(bool dev, void* stream, hipStream_t s) {
     if (!stream || !dev) VS_HIP(hipStreamSynchronize(s));
     if (Profiler::get().on) Profiler::get().drain();

@@ -1,5 +1,6 @@
-// block_scan.h -- the two-level exclusive scan over the rows of an index that vs_index_compact (mutable.hip) and vs_index_prune (prune.hip)
-// share: a pair of uint32 counts a row, blocks of kScanRows rows.  Level one is the caller's -- a workgroup sums its block's rows with
+// block_scan.h -- the two-level exclusive scan over the rows of an index that vs_index_compact (mutable.hip), vs_index_select_rows (select.hip)
+// and the pointers-from-counts pair of vs_index_prune and vs_index_combine (new_index.hip) share: a pair of uint32 counts a row, blocks of
+// kScanRows rows.  Level one is the caller's -- a workgroup sums its block's rows with
 // block_excl_scan --, level two is scan_block_sums_kernel over the block sums, and the caller's map kernel scans inside a block again from the
 // block's base.
 #pragma once

@@ -14,6 +14,7 @@
 //     id -1 / score -inf.  Under the canonical order the top k of "all rows minus E" lies inside the top k + |E|: exact.
 #include "common.h"
 #include "csr_scan.h"
+#include "new_index.h"
 
 #include <algorithm>
 
@@ -311,15 +312,6 @@ __global__ __launch_bounds__(64) void topk_exclude_kernel(const int64_t* ids, co
 }
 
 // ---- host helpers ------------------------------------------------------------------------------------------------------------------
-int need_device() {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        (void)hipGetLastError();
-        return fail(VS_ENODEVICE, "no HIP device visible: libvsearch_hip has no CPU fallback");
-    }
-    return VS_OK;
-}
-
 int device_of(const void* p, int* d) {
     hipPointerAttribute_t attr;
     VS_HIP(hipPointerGetAttributes(&attr, p));

@@ -1,10 +1,11 @@
 // combine.hip -- the combined index: a NEW index whose row r holds wa * (row r of a) + wb * (row r of b), cell by cell over the union of the two
 // rows' stored columns (vs_index_combine; the semantics are pinned in vsearch_hip.h).  No reference counterpart: the reference adds its tensors
-// and rebuilds.  Three steps on the sources' GPU in the shape of vs_index_prune: count (a wave a row: the union's size, repeated columns), scan
-// (block_scan.h), fill (a wave a row, or a 1024-thread workgroup a long row: the row is staged in LDS and leaves as 16-byte stores).  The
-// host-only part is combine_check.h.  Nothing here touches a walk or scan kernel.
+// and rebuilds.  Three steps on the sources' GPU: count (a wave a row: the union's size, repeated columns), scan (row pointers from the union
+// counts: the shared pair of new_index.h), fill (a wave a row, or a 1024-thread workgroup a long row: the row is staged in LDS and leaves as
+// 16-byte stores).  The scaffold of the call is new_index.h, the host-only part combine_check.h.  Nothing here touches a walk or scan kernel.
 #include "block_scan.h"
 #include "common.h"
+#include "new_index.h"
 #include "packets.h"
 #include "combine_check.h"
 
@@ -14,15 +15,6 @@
 using namespace vs;
 
 namespace {
-
-int need_device() {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        (void)hipGetLastError();
-        return fail(VS_ENODEVICE, "no HIP device visible: libvsearch_hip has no CPU fallback");
-    }
-    return VS_OK;
-}
 
 CombineShape shape_of(const vs_index* a) {
     CombineShape s;
@@ -45,7 +37,7 @@ struct CombineTotals {
 };
 static_assert(sizeof(CombineTotals) == kCombineTotalsBytes, "the plan counts these bytes");
 
-constexpr uint32_t kLongBit = 0x80000000u;            // of a row's union count: cells_a + cells_b exceed the wave route's slots
+constexpr uint32_t kLongBit = 0x80000000u;            // of a row's union count: cells_a + cells_b exceed the wave route's slots (bit 31: the scan of new_index.h skips it)
 
 // the writes of a team to LDS precede its reads behind this point.  A team is a wave (LDS executes a wave's operations in order; the fence
 // keeps the compiler's order and waits for the counter) or the whole workgroup
@@ -212,41 +204,6 @@ __global__ __launch_bounds__(kCombineThreads) void combine_count_kernel(CountArg
         const uint32_t a0 = k.a.pk[r], na = k.a.pk[r + 1] - a0, b0 = k.b.pk[r], nb = k.b.pk[r + 1] - b0;
         if (na <= 64u * kCombineRegPackets && nb <= 64u * kCombineRegPackets) count_row<true>(k, r, a0, na, b0, nb, bits_a, bits_b, lane);
         else count_row<false>(k, r, a0, na, b0, nb, bits_a, bits_b, lane);
-    }
-}
-
-// ---- step (b): scan -- (union cells, new packets) a row; the packets give the new row pointers, the cells the non-zeros ------------------------------
-__device__ __forceinline__ uint2 union_stat(const uint32_t* ucnt, int64_t r, int64_t n_rows) {
-    if (r >= n_rows) return make_uint2(0u, 0u);
-    const uint32_t u = ucnt[r] & ~kLongBit;
-    return make_uint2(u, (u + 7u) >> 3);
-}
-
-// (a block's cells fit 32 bits: 4096 rows x 65535; their sum over the index goes to *nnz, the scanned .x of the block sums is not used)
-__global__ __launch_bounds__(256) void combine_sums_kernel(const uint32_t* ucnt, int64_t n_rows, uint2* sums, unsigned long long* nnz) {
-    __shared__ uint2 sh[4];
-    const int64_t r0 = (int64_t)blockIdx.x * kScanRows;
-    uint2 acc = make_uint2(0u, 0u);
-    for (int it = 0; it < kScanItems; ++it) acc = add2(acc, union_stat(ucnt, r0 + it * 256 + threadIdx.x, n_rows));
-    uint2 tot;
-    (void)block_excl_scan<4>(acc, sh, &tot);
-    if (threadIdx.x == 0) {
-        sums[blockIdx.x] = tot;
-        if (tot.x) atomicAdd(nnz, (unsigned long long)tot.x);
-    }
-}
-
-__global__ __launch_bounds__(256) void combine_map_kernel(const uint32_t* ucnt, int64_t n_rows, const uint2* sums, uint32_t* new_pk) {
-    __shared__ uint2 sh[4];
-    const int64_t r0 = (int64_t)blockIdx.x * kScanRows;
-    uint2 carry = sums[blockIdx.x];
-    for (int it = 0; it < kScanItems; ++it) {
-        const int64_t r = r0 + it * 256 + threadIdx.x;
-        const uint2 v = union_stat(ucnt, r, n_rows);
-        uint2 tot;
-        const uint2 ex = block_excl_scan<4>(v, sh, &tot);
-        if (r < n_rows) new_pk[r] = carry.y + ex.y;
-        carry = add2(carry, tot);
     }
 }
 
@@ -547,17 +504,13 @@ extern "C" int vs_index_combine(const vs_index* a, const vs_index* b, float wa, 
     int rc = combine_check_args(a != nullptr, b != nullptr, out != nullptr, out_dtype, rows_extra, packets_extra, msg, sizeof msg);
     if (rc == VS_OK) rc = combine_check_sources(shape_of(a), shape_of(b), msg, sizeof msg);
     if (rc != VS_OK) return fail(rc, "%s", msg);
-    VS_TRY(need_device());
-    int ndev = 0;
-    VS_HIP(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(VS_EINVAL, "device %d out of range (have %d)", device, ndev);
+    VS_TRY(device_in_range(device));
     const int64_t n = a->n_rows;
     CombinePlan plan;
     rc = combine_plan(n, a->n_packets, b->n_packets, a->n_cols, a->store_dtype, b->store_dtype, out_dtype, &plan, msg, sizeof msg);
     if (rc != VS_OK) return fail(rc, "%s", msg);
 
-    VS_HIP(hipSetDevice(a->device));
-    VS_HIP(hipDeviceSynchronize());                            // work enqueued on a caller's stream; everything below runs on the null stream
+    VS_TRY(open_sources(a->device));
     // scratch: union counts, the list of long rows, block sums, the totals
     DevBuf ucnt, long_rows, sums, tot;
     if (ucnt.alloc(std::max<size_t>((size_t)n * 4, 4)) != VS_OK || long_rows.alloc(std::max<size_t>((size_t)plan.long_rows_cap * 4, 4)) != VS_OK)
@@ -585,28 +538,17 @@ extern "C" int vs_index_combine(const vs_index* a, const vs_index* b, float wa, 
     }
     // (b) scan
     uint2* d_sums = sums.as<uint2>();
-    hipLaunchKernelGGL(combine_sums_kernel, dim3((unsigned)plan.scan_blocks), dim3(256), 0, 0, (const uint32_t*)ucnt.p, n, d_sums, &tot.as<CombineTotals>()->nnz);
-    hipLaunchKernelGGL(scan_block_sums_kernel<0>, dim3(1), dim3(1024), 0, 0, d_sums, plan.scan_blocks, d_sums + plan.scan_blocks);
-    VS_HIP(hipGetLastError());
-    uint32_t total[2] = {0u, 0u};
-    VS_HIP(hipMemcpy(total, d_sums + plan.scan_blocks, 8, hipMemcpyDeviceToHost));
+    int64_t p_new = 0;
+    VS_TRY(cells_scan(ucnt.as<int32_t>(), n, plan.scan_blocks, d_sums, &tot.as<CombineTotals>()->nnz, &p_new));
     VS_HIP(hipMemcpy(&h_tot, tot.p, sizeof h_tot, hipMemcpyDeviceToHost));
     rc = combine_check_flags(h_tot.repeat_a, h_tot.repeat_b, h_tot.too_wide, msg, sizeof msg);
-    const int64_t p_new = total[1];
-    if (rc == VS_OK) rc = combine_check_capacity(n, p_new, rows_extra, packets_extra, msg, sizeof msg);
+    if (rc == VS_OK) rc = new_index_check_capacity("combined", n, p_new, rows_extra, packets_extra, msg, sizeof msg);
     if (rc != VS_OK) return fail(rc, "%s", msg);
     if ((int64_t)h_tot.n_long > plan.long_rows_cap) return fail(VS_EHIP, "the count step listed %u long rows, the bound is %lld", h_tot.n_long, (long long)plan.long_rows_cap);
-    const size_t vb = out_dtype == VS_F32 ? 32 : 16;
-    vs_index* idx = nullptr;
-    if (vs_index_create_reserved(n + rows_extra, p_new + packets_extra, a->n_cols, out_dtype, a->device, &idx) != VS_OK) {
-        const size_t need = (size_t)(p_new + packets_extra) * (16 + vb) + (size_t)(n + rows_extra + 1) * 4;
-        return fail(VS_ENOMEM, "combining needs %zu bytes of HBM for the new index next to the sources' (drop the postings copy of a source)", need);
-    }
-    struct Guard { vs_index* p; ~Guard() { if (p) vs_index_destroy(p); } } guard{idx};
-    hipLaunchKernelGGL(combine_map_kernel, dim3((unsigned)plan.scan_blocks), dim3(256), 0, 0, (const uint32_t*)ucnt.p, n, (const uint2*)d_sums, idx->pk_ptr.as<uint32_t>());
-    VS_HIP(hipGetLastError());
-    const uint32_t last = (uint32_t)p_new;
-    VS_HIP(hipMemcpy(idx->pk_ptr.as<uint32_t>() + n, &last, 4, hipMemcpyHostToDevice));
+    IndexGuard guard{nullptr};
+    VS_TRY(new_csr_index("combining", "sources' (drop the postings copy of a source)", n, p_new, rows_extra, packets_extra, a->n_cols, out_dtype, a->device, &guard));
+    vs_index* idx = guard.p;
+    VS_TRY(cells_row_pointers(ucnt.as<int32_t>(), n, plan.scan_blocks, d_sums, p_new, idx->pk_ptr.as<uint32_t>()));
     // (c) fill
     if (p_new > 0) {
         FillArgs k;
@@ -627,31 +569,15 @@ extern "C" int vs_index_combine(const vs_index* a, const vs_index* b, float wa, 
         else if (sa == VS_F16) VS_TRY(launch_fill_sb<VS_F16>(sb, out_dtype, plan, a->cu_count, k));
         else VS_TRY(launch_fill_sb<VS_NONE>(sb, out_dtype, plan, a->cu_count, k));
     }
-    idx->n_rows = n;
-    idx->n_packets = p_new;
-    idx->nnz = (int64_t)h_tot.nnz;
-    idx->logical_dense = a->logical_dense && b->logical_dense;
-    idx->lanes_per_row = pick_lanes(p_new, n);
-    VS_HIP(hipDeviceSynchronize());
-    // the deleted rows are a's or b's: the live words are ANDed on the host (a bit a row: 125 KB a million rows)
+    set_csr_shape(idx, n, p_new, (int64_t)h_tot.nnz, a->logical_dense && b->logical_dense);
+    // the deleted rows are a's or b's: the live words are ANDed on the host (a bit a row: 125 KB a million rows); restore() brings a deleted
+    // row back combined
     std::vector<uint32_t> live_a, live_b;
     const bool tomb = (a->has_tomb || b->has_tomb) && n > 0;
     if (tomb) {
         VS_TRY(tomb_to_host(a, live_a));
         VS_TRY(tomb_to_host(b, live_b));
-        VS_HIP(hipDeviceSynchronize());
         for (size_t i = 0; i < live_a.size(); ++i) live_a[i] &= live_b[i];
     }
-    if (device != a->device) {                                  // the new index moves to its GPU; the copy on the sources' GPU is dropped
-        vs_index* moved = nullptr;
-        VS_TRY(move_csr(idx, device, &moved));
-        VS_HIP(hipSetDevice(a->device));
-        vs_index_destroy(idx);
-        idx = moved;
-        guard.p = idx;
-    }
-    if (tomb) VS_TRY(tomb_from_host(idx, live_a.data()));       // restore() brings a deleted row back combined
-    guard.p = nullptr;
-    *out = idx;
-    return VS_OK;
+    return hand_over(guard, a->device, device, TombFrom::host_words(tomb ? live_a.data() : nullptr), out);
 }

@@ -3,7 +3,7 @@
 // Plain C++ with no HIP in it, so that a stand-alone program can run them under a host sanitizer (tests/test_combine_cpu.py builds one).
 #pragma once
 
-#include "set_check.h"
+#include "new_index_check.h"
 
 namespace vs {
 
@@ -33,12 +33,10 @@ struct CombinePlan {
 constexpr int kCombineTotalsBytes = 64;               // the device words the host reads after the scan (CombineTotals of combine.hip)
 
 inline int64_t combine_words(int32_t n_cols) { return ((int64_t)n_cols + 31) >> 5; }
-inline bool combine_store_ok(int dt) { return dt == VS_F32 || dt == VS_F16 || dt == VS_NONE; }
-inline bool combine_out_ok(int dt) { return dt == VS_F32 || dt == VS_F16; }
 
 inline int combine_check_out_dtype(int out_dtype, char* msg, size_t cap) {
     if (out_dtype == VS_NONE) return snprintf(msg, cap, "out_dtype VS_NONE: binarising an index is not covered (VS_F32 or VS_F16)"), VS_EINVAL;
-    if (!combine_out_ok(out_dtype)) return snprintf(msg, cap, "out_dtype must be VS_F32 or VS_F16 (got %d)", out_dtype), VS_EINVAL;
+    if (!valued_dtype_ok(out_dtype)) return snprintf(msg, cap, "out_dtype must be VS_F32 or VS_F16 (got %d)", out_dtype), VS_EINVAL;
     return VS_OK;
 }
 
@@ -54,7 +52,7 @@ inline int combine_plan(int64_t n_rows, int64_t packets_a, int64_t packets_b, in
         return snprintf(msg, cap, "n_packets must be in 0..2^32 - 1 (got %lld and %lld)", (long long)packets_a, (long long)packets_b), VS_EINVAL;
     if (n_cols < 1) return snprintf(msg, cap, "n_cols must be positive (got %d)", n_cols), VS_EINVAL;
     if (n_cols > kTermMaxCols) return snprintf(msg, cap, "n_cols = %d > %d: column ids are stored as uint16", n_cols, kTermMaxCols), VS_EUNSUPPORTED;
-    if (!combine_store_ok(dtype_a) || !combine_store_ok(dtype_b)) return snprintf(msg, cap, "bad source store_dtype %d / %d", dtype_a, dtype_b), VS_EINVAL;
+    if (!store_dtype_ok(dtype_a) || !store_dtype_ok(dtype_b)) return snprintf(msg, cap, "bad source store_dtype %d / %d", dtype_a, dtype_b), VS_EINVAL;
     const int rc = combine_check_out_dtype(out_dtype, msg, cap);
     if (rc != VS_OK) return rc;
     CombinePlan p;
@@ -81,7 +79,7 @@ struct CombineShape {
 
 // the arguments of vs_index_combine that need neither a handle nor a device
 inline int combine_check_args(bool have_a, bool have_b, bool have_out, int out_dtype, int64_t rows_extra, int64_t packets_extra, char* msg, size_t cap) {
-    if (rows_extra < 0 || packets_extra < 0) return snprintf(msg, cap, "rows_extra and packets_extra must be >= 0"), VS_EINVAL;
+    if (new_index_check_extra(rows_extra, packets_extra, msg, cap) != VS_OK) return VS_EINVAL;
     const int rc = combine_check_out_dtype(out_dtype, msg, cap);
     if (rc != VS_OK) return rc;
     if (!have_a || !have_b || !have_out) return snprintf(msg, cap, "NULL argument"), VS_EINVAL;
@@ -109,13 +107,6 @@ inline int combine_check_flags(uint32_t repeat_a, uint32_t repeat_b, uint32_t to
     }
     if (too_wide != kCombineNoRow)
         return snprintf(msg, cap, "row %u has a union of more than %d cells: a combined row is staged in LDS", too_wide, kCombineGroupCells), VS_EUNSUPPORTED;
-    return VS_OK;
-}
-
-// the limits of vs_index_compact: row and packet counts with their spare capacity fit 32 bits
-inline int combine_check_capacity(int64_t n_rows, int64_t new_packets, int64_t rows_extra, int64_t packets_extra, char* msg, size_t cap) {
-    if (rows_extra > (1ll << 32) || packets_extra > (1ll << 32) || n_rows + rows_extra >= (1ll << 32) - 1 || new_packets + packets_extra >= (1ll << 32))
-        return snprintf(msg, cap, "the combined index with its spare capacity exceeds 2^32 rows or packets"), VS_EUNSUPPORTED;
     return VS_OK;
 }
 

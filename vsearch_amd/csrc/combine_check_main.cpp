@@ -96,11 +96,11 @@ int main() {
     expect("flags a repeat before a wide row", combine_check_flags(9, kCombineNoRow, 2, msg, sizeof msg), VS_EINVAL, msg, "row 9 of index a");
     expect("flags too wide", combine_check_flags(kCombineNoRow, kCombineNoRow, 5, msg, sizeof msg), VS_EUNSUPPORTED, msg, "row 5 has a union of more than 32768 cells");
     // ---- the capacity rule ---------------------------------------------------------------------------------------------------------------------------------------
-    expect("capacity ok", combine_check_capacity(100, 1000, 5, 7, msg, sizeof msg), VS_OK, msg, "");
-    expect("capacity nothing", combine_check_capacity(0, 0, 0, 0, msg, sizeof msg), VS_OK, msg, "");
-    expect("capacity rows", combine_check_capacity(0xFFFFFFF0ll, 10, 0xF, 0, msg, sizeof msg), VS_EUNSUPPORTED, msg, "2^32");
-    expect("capacity packets", combine_check_capacity(10, 0xFFFFFFF0ll, 0, 0x10, msg, sizeof msg), VS_EUNSUPPORTED, msg, "2^32");
-    expect("capacity huge extra", combine_check_capacity(10, 10, 0x7FFFFFFFFFFFFFFFll, 0, msg, sizeof msg), VS_EUNSUPPORTED, msg, "2^32");
+    expect("capacity ok", new_index_check_capacity("combined", 100, 1000, 5, 7, msg, sizeof msg), VS_OK, msg, "");
+    expect("capacity nothing", new_index_check_capacity("combined", 0, 0, 0, 0, msg, sizeof msg), VS_OK, msg, "");
+    expect("capacity rows", new_index_check_capacity("combined", 0xFFFFFFF0ll, 10, 0xF, 0, msg, sizeof msg), VS_EUNSUPPORTED, msg, "2^32");
+    expect("capacity packets", new_index_check_capacity("combined", 10, 0xFFFFFFF0ll, 0, 0x10, msg, sizeof msg), VS_EUNSUPPORTED, msg, "2^32");
+    expect("capacity huge extra", new_index_check_capacity("combined", 10, 10, 0x7FFFFFFFFFFFFFFFll, 0, msg, sizeof msg), VS_EUNSUPPORTED, msg, "2^32");
 
     if (failures) {
         fprintf(stderr, "combine_check: %d failures\n", failures);

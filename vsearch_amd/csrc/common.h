@@ -235,9 +235,7 @@ int tomb_dead_count(const vs_index* idx, int64_t* out);                         
 int tomb_from_bits(vs_index* dst, const vs_index* src, int64_t row0);                 // dst's tombstones = src's bits [row0, row0 + dst->n_rows) (vs_index_slice_rows)
 int tomb_from_host(vs_index* idx, const uint32_t* words);                             // tombstones from (n_rows + 31) / 32 host words (vs_index_load_native)
 int tomb_to_host(const vs_index* idx, std::vector<uint32_t>& words);                  // the words vs_index_save_native writes
-// ---- mutable.hip: what vs_index_compact and vs_index_prune (prune.hip) share ---------------------
-int pick_lanes(int64_t n_packets, int64_t n_rows);                                    // lanes_per_row of a CSR index of that shape (csr_index.hip's rule)
-int move_csr(const vs_index* a, int device, vs_index** out);                          // a CSR index with its capacity, copied whole to another GPU (no tombstones)
+// (what the calls that return a new index share -- pick_lanes, move_csr, the scaffold of a call --: new_index.h)
 
 inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }

@@ -3,9 +3,10 @@
 // are already on the GPU.  Packets are copied whole, so a row scores bit for bit what it scored in a source of the result's dtype; a source of
 // another store is converted in registers under vs_index_rescale's rule with no scale; the sources' tombstones travel with the rows.  Two
 // launches for ALL sources -- map (row pointers, live words) and copy (packets) -- over a device table of per-source entries that every workgroup
-// reads into LDS once and searches.  The shape is select.hip's (map, gather); the host-only part is concat_check.h.  Nothing here touches a walk
-// or scan kernel.
+// reads into LDS once and searches.  The scaffold of the call is new_index.h, the host-only part concat_check.h.  Nothing here touches a walk or
+// scan kernel.
 #include "common.h"
+#include "new_index.h"
 #include "packets.h"
 #include "concat_check.h"
 
@@ -15,17 +16,6 @@
 using namespace vs;
 
 namespace {
-
-int need_device() {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        (void)hipGetLastError();
-        return fail(VS_ENODEVICE, "no HIP device visible: libvsearch_hip has no CPU fallback");
-    }
-    return VS_OK;
-}
-
-int64_t bit_words(int64_t rows) { return (rows + 31) >> 5; }
 
 ConcatShape shape_of(const vs_index* a) {
     ConcatShape s;
@@ -58,9 +48,8 @@ __device__ __forceinline__ uint32_t global_word(uint64_t base, size_t i) { retur
 
 // ---- map ---------------------------------------------------------------------------------------------------------------------------------------
 // A thread a result row: it finds its source among the row bases and writes the rebased row pointer; thread n_rows writes the last pointer.  With
-// tombstones on any source the live bits of the new rows as well, in the pattern of select_map_kernel: the 64 rows of a wave are two whole words
-// of the new bitmap, written from a ballot with plain stores (bits past the last new row stay set: rows still to be appended are live); *dead
-// counts the cleared ones.
+// tombstones on any source the live bits of the new rows as well: the 64 rows of a wave are two whole words of the new bitmap
+// (live_words_from_ballot); *dead counts the cleared ones.
 struct ConcatMapLds {
     uint64_t pk[kConcatMaxSources];                               // const uint32_t*
     uint64_t live[kConcatMaxSources];                             // const uint32_t*, or 0
@@ -82,7 +71,6 @@ __global__ __launch_bounds__(kConcatThreads) void concat_map_kernel(const Concat
         }
     }
     __syncthreads();
-    const int lane = threadIdx.x & 63;
     const int64_t r = (int64_t)blockIdx.x * kConcatThreads + threadIdx.x;
     bool is_dead = false;
     if (r < n_rows) {
@@ -94,13 +82,7 @@ __global__ __launch_bounds__(kConcatThreads) void concat_map_kernel(const Concat
     } else if (r == n_rows) {
         new_pk[r] = n_packets;
     }
-    if (new_live) {
-        const unsigned long long dead_bits = __ballot(is_dead);
-        const int64_t w0 = r - lane;                                           // the wave's first row: a multiple of 64
-        if (lane == 0 && w0 < n_rows) new_live[w0 >> 5] = ~(uint32_t)dead_bits;
-        if (lane == 32 && w0 + 32 < n_rows) new_live[(w0 >> 5) + 1] = ~(uint32_t)(dead_bits >> 32);
-        if (lane == 0 && dead_bits) atomicAdd(dead, (unsigned long long)__popcll(dead_bits));
-    }
+    if (new_live) live_words_from_ballot(is_dead, r, n_rows, new_live, dead);
 }
 
 // ---- copy --------------------------------------------------------------------------------------------------------------------------------------
@@ -225,16 +207,6 @@ __global__ __launch_bounds__(kConcatThreads) void concat_copy_kernel(const Conca
     }
 }
 
-// the new handle's bitmap: every row it can ever hold live (the layout of mutable.hip: whole 16-byte quads over max(rows_cap, n_rows) rows)
-int alloc_live(vs_index* idx, int64_t n_rows) {
-    const int64_t words = (bit_words(std::max(idx->rows_cap, n_rows)) + 3) / 4 * 4;
-    VS_TRY(idx->live.alloc(std::max<size_t>((size_t)words * 4, 16)));
-    VS_TRY(idx->dead_cnt.alloc(8));
-    VS_HIP(hipMemset(idx->live.p, 0xFF, idx->live.bytes));
-    VS_HIP(hipMemset(idx->dead_cnt.p, 0, 8));
-    return VS_OK;
-}
-
 }  // namespace
 
 extern "C" int vs_concat_plan(int32_t n_src, const int64_t* rows, const int64_t* packets, int32_t n_cols, const int* dtypes, int out_dtype, int64_t* out_rows,
@@ -270,17 +242,13 @@ extern "C" int vs_index_concat(const vs_index* const* srcs, int32_t n_src, int o
     }
     ConcatPlan plan;
     rc = concat_plan(n_src, rows.data(), packets.data(), shapes[0].n_cols, dtypes.data(), out_dtype, &plan, msg, sizeof msg);
-    if (rc == VS_OK) rc = concat_check_capacity(plan.rows, plan.packets, rows_extra, packets_extra, msg, sizeof msg);
+    if (rc == VS_OK) rc = new_index_check_capacity("joined", plan.rows, plan.packets, rows_extra, packets_extra, msg, sizeof msg);
     if (rc != VS_OK) return fail(rc, "%s", msg);
-    VS_TRY(need_device());
-    int ndev = 0;
-    VS_HIP(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(VS_EINVAL, "device %d out of range (have %d)", device, ndev);
+    VS_TRY(device_in_range(device));
     const int src_device = shapes[0].device;
     const int64_t n = plan.rows, p_new = plan.packets;
 
-    VS_HIP(hipSetDevice(src_device));
-    VS_HIP(hipDeviceSynchronize());                            // deletions enqueued on a caller's stream; everything below runs on the null stream
+    VS_TRY(open_sources(src_device));
     std::vector<ConcatEntry> table((size_t)n_src);
     concat_fill_bases(shapes.data(), n_src, table.data());
     bool any_tomb = false, all_dense = true;
@@ -304,13 +272,11 @@ extern "C" int vs_index_concat(const vs_index* const* srcs, int32_t n_src, int o
     unsigned long long* d_dead = reinterpret_cast<unsigned long long*>((char*)scratch.p + table_bytes);
     VS_HIP(hipMemset(d_dead, 0, kConcatCounterBytes));
 
-    const size_t vb = out_dtype == VS_F32 ? 32 : (out_dtype == VS_F16 ? 16 : 0);
-    vs_index* idx = nullptr;
-    if (vs_index_create_reserved(n + rows_extra, p_new + packets_extra, shapes[0].n_cols, out_dtype, src_device, &idx) != VS_OK) {
-        const size_t need = (size_t)(p_new + packets_extra) * (16 + vb) + (size_t)(n + rows_extra + 1) * 4;
-        return fail(VS_ENOMEM, "the join needs %zu bytes of HBM for the new index next to the sources' (drop the postings copies of the sources, or join fewer rows)", need);
-    }
-    struct Guard { vs_index* p; ~Guard() { if (p) vs_index_destroy(p); } } guard{idx};
+    const size_t vb = value_bytes(out_dtype);
+    IndexGuard guard{nullptr};
+    VS_TRY(new_csr_index("the join", "sources' (drop the postings copies of the sources, or join fewer rows)", n, p_new, rows_extra, packets_extra, shapes[0].n_cols,
+                         out_dtype, src_device, &guard));
+    vs_index* idx = guard.p;
     if (any_tomb) VS_TRY(alloc_live(idx, n));
     // 1. map
     hipLaunchKernelGGL(concat_map_kernel, dim3((unsigned)concat_map_grid(n)), dim3(kConcatThreads), 0, 0, d_table, n_src, n, (uint32_t)p_new,
@@ -335,36 +301,7 @@ extern "C" int vs_index_concat(const vs_index* const* srcs, int32_t n_src, int o
 #undef VS_CONCAT_LAUNCH
         VS_HIP(hipGetLastError());
     }
-    idx->n_rows = n;
-    idx->n_packets = p_new;
-    idx->nnz = nnz;
-    idx->logical_dense = all_dense;
-    idx->lanes_per_row = pick_lanes(p_new, n);
-    if (any_tomb) {                                             // the dead count the map kernel found
-        unsigned long long dead = 0;
-        VS_HIP(hipMemcpy(&dead, d_dead, 8, hipMemcpyDeviceToHost));
-        if (dead > 0) {
-            VS_HIP(hipMemcpy(idx->dead_cnt.p, &dead, 8, hipMemcpyHostToDevice));
-            idx->has_tomb = true;
-        } else {                                                // no joined row is deleted: a handle without a live bitmap, as from sources without tombstones
-            VS_HIP(hipDeviceSynchronize());
-            idx->live.release();
-            idx->dead_cnt.release();
-        }
-    }
-    VS_HIP(hipDeviceSynchronize());
-    if (device != src_device) {                                 // the new index moves to its GPU, its tombstones behind it; the copy on the sources' GPU is dropped
-        vs_index* moved = nullptr;
-        VS_TRY(move_csr(idx, device, &moved));
-        struct Guard moved_guard{moved};
-        VS_TRY(tomb_from_bits(moved, idx, 0));
-        VS_HIP(hipSetDevice(src_device));
-        vs_index_destroy(idx);
-        guard.p = nullptr;
-        idx = moved;
-        moved_guard.p = nullptr;
-    }
-    guard.p = nullptr;
-    *out = idx;
-    return VS_OK;
+    set_csr_shape(idx, n, p_new, nnz, all_dense);
+    if (any_tomb) VS_TRY(settle_dead(idx, d_dead));
+    return hand_over(guard, src_device, device, TombFrom::own_bits(), out);   // the tombstones travel behind the index
 }

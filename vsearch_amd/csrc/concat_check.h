@@ -3,7 +3,7 @@
 // Plain C++ with no HIP in it, so that a stand-alone program can run them under a host sanitizer (tests/test_concat_cpu.py builds one).
 #pragma once
 
-#include "set_check.h"
+#include "new_index_check.h"
 
 namespace vs {
 
@@ -41,8 +41,6 @@ struct ConcatPlan {
     bool all_binary = true;
 };
 
-inline bool concat_store_ok(int dt) { return dt == VS_F32 || dt == VS_F16 || dt == VS_NONE; }
-
 inline int concat_check_n_src(int32_t n_src, char* msg, size_t cap) {
     if (n_src < 1 || n_src > kConcatMaxSources) return snprintf(msg, cap, "n_src must be in 1..%d (got %d)", kConcatMaxSources, n_src), VS_EINVAL;
     return VS_OK;
@@ -58,14 +56,6 @@ inline int concat_check_out_dtype(int out_dtype, bool all_binary, char* msg, siz
     return VS_OK;
 }
 
-// the 2^32 limits of vs_index_select_rows on the 64-bit totals
-inline int concat_check_capacity(int64_t rows, int64_t packets, int64_t rows_extra, int64_t packets_extra, char* msg, size_t cap) {
-    if (rows_extra > (1ll << 32) || packets_extra > (1ll << 32) || packets >= (1ll << 32) || rows + rows_extra >= (1ll << 32) - 1 ||
-        packets + packets_extra >= (1ll << 32))
-        return snprintf(msg, cap, "the joined index with its spare capacity exceeds 2^32 rows or packets"), VS_EUNSUPPORTED;
-    return VS_OK;
-}
-
 inline int concat_plan(int32_t n_src, const int64_t* rows, const int64_t* packets, int32_t n_cols, const int* dtypes, int out_dtype, ConcatPlan* out, char* msg,
                        size_t cap) {
     int rc = concat_check_n_src(n_src, msg, cap);
@@ -78,7 +68,7 @@ inline int concat_plan(int32_t n_src, const int64_t* rows, const int64_t* packet
         if (rows[s] < 0 || rows[s] >= 0xFFFFFFFFll) return snprintf(msg, cap, "source %d: n_rows must be in 0..2^32 - 2 (got %lld)", s, (long long)rows[s]), VS_EINVAL;
         if (packets[s] < 0 || packets[s] >= (1ll << 32))
             return snprintf(msg, cap, "source %d: n_packets must be in 0..2^32 - 1 (got %lld)", s, (long long)packets[s]), VS_EINVAL;
-        if (!concat_store_ok(dtypes[s])) return snprintf(msg, cap, "source %d: bad store_dtype %d", s, dtypes[s]), VS_EINVAL;
+        if (!store_dtype_ok(dtypes[s])) return snprintf(msg, cap, "source %d: bad store_dtype %d", s, dtypes[s]), VS_EINVAL;
         p.rows += rows[s];                             // (256 terms below 2^32 each: no overflow)
         p.packets += packets[s];
         p.all_binary = p.all_binary && dtypes[s] == VS_NONE;
@@ -86,7 +76,7 @@ inline int concat_plan(int32_t n_src, const int64_t* rows, const int64_t* packet
     rc = concat_check_out_dtype(out_dtype, p.all_binary, msg, cap);
     if (rc != VS_OK) return rc;
     if (p.rows == 0) return snprintf(msg, cap, "empty join: the sources hold no row"), VS_EINVAL;
-    rc = concat_check_capacity(p.rows, p.packets, 0, 0, msg, cap);
+    rc = new_index_check_capacity("joined", p.rows, p.packets, 0, 0, msg, cap);
     if (rc != VS_OK) return rc;
     p.scratch_bytes = (int64_t)n_src * (int64_t)sizeof(ConcatEntry) + kConcatCounterBytes;
     p.lds_bytes = std::max(kConcatMapLds, kConcatCopyLds);
@@ -96,7 +86,7 @@ inline int concat_plan(int32_t n_src, const int64_t* rows, const int64_t* packet
 
 // the arguments of vs_index_concat that need neither a handle nor a device
 inline int concat_check_args(bool have_srcs, bool have_out, int32_t n_src, int64_t rows_extra, int64_t packets_extra, char* msg, size_t cap) {
-    if (rows_extra < 0 || packets_extra < 0) return snprintf(msg, cap, "rows_extra and packets_extra must be >= 0"), VS_EINVAL;
+    if (new_index_check_extra(rows_extra, packets_extra, msg, cap) != VS_OK) return VS_EINVAL;
     const int rc = concat_check_n_src(n_src, msg, cap);
     if (rc != VS_OK) return rc;
     if (!have_srcs || !have_out) return snprintf(msg, cap, "NULL argument"), VS_EINVAL;

@@ -92,10 +92,10 @@ int main() {
     expect("out_dtype fp32", concat_check_out_dtype(VS_F32, true, msg, sizeof msg), VS_OK, msg, "");
     expect("out_dtype none", concat_check_out_dtype(VS_NONE, true, msg, sizeof msg), VS_OK, msg, "");
     expect("out_dtype none valued", concat_check_out_dtype(VS_NONE, false, msg, sizeof msg), VS_EINVAL, msg, "binarising");
-    expect("capacity ok", concat_check_capacity(100, 1000, 5, 7, msg, sizeof msg), VS_OK, msg, "");
-    expect("capacity rows", concat_check_capacity(0xFFFFFFF0ll, 10, 0xF, 0, msg, sizeof msg), VS_EUNSUPPORTED, msg, "2^32");
-    expect("capacity packets", concat_check_capacity(10, 0xFFFFFFF0ll, 0, 0x10, msg, sizeof msg), VS_EUNSUPPORTED, msg, "2^32");
-    expect("capacity huge extra", concat_check_capacity(10, 10, 0x7FFFFFFFFFFFFFFFll, 0, msg, sizeof msg), VS_EUNSUPPORTED, msg, "2^32");
+    expect("capacity ok", new_index_check_capacity("joined", 100, 1000, 5, 7, msg, sizeof msg), VS_OK, msg, "");
+    expect("capacity rows", new_index_check_capacity("joined", 0xFFFFFFF0ll, 10, 0xF, 0, msg, sizeof msg), VS_EUNSUPPORTED, msg, "2^32");
+    expect("capacity packets", new_index_check_capacity("joined", 10, 0xFFFFFFF0ll, 0, 0x10, msg, sizeof msg), VS_EUNSUPPORTED, msg, "2^32");
+    expect("capacity huge extra", new_index_check_capacity("joined", 10, 10, 0x7FFFFFFFFFFFFFFFll, 0, msg, sizeof msg), VS_EUNSUPPORTED, msg, "2^32");
     expect_true("grid map: one more thread for the last pointer", concat_map_grid(255) == 1 && concat_map_grid(256) == 2 && concat_map_grid(1) == 1);
     expect_true("grid copy", concat_copy_grid(1, 256) == 1 && concat_copy_grid(1024, 256) == 1 && concat_copy_grid(1025, 256) == 2 &&
                                  concat_copy_grid(1ll << 31, 256) == 256 * 32);

@@ -1,6 +1,7 @@
 // csr_index.hip -- SparseIndex / BoTIndex device container and its search entry points.
 //   reference: src/ir/retriever/index.py:128-218 (containers), :88-94 (search)
 #include "csr_internal.h"
+#include "new_index.h"
 #include "synth_device.h"
 
 #include <algorithm>
@@ -347,7 +348,7 @@ extern "C" int vs_index_create_reserved(int64_t rows_cap, int64_t packets_cap, i
     if (packets_cap < 0 || packets_cap >= (1ll << 32)) return fail(VS_EUNSUPPORTED, "packets_cap must be in [0, 2^32)");
     vs_index* idx = nullptr;
     VS_TRY(new_index(device, &idx));
-    struct Guard { vs_index* p; ~Guard() { if (p) vs_index_destroy(p); } } guard{idx};
+    IndexGuard guard{idx};
     idx->kind = VS_KIND_CSR;
     idx->store_dtype = store_dtype;
     idx->n_rows = 0;
@@ -397,7 +398,7 @@ extern "C" int vs_index_slice_rows(const vs_index* src, int64_t row0, int64_t n_
     if (packets < 0) return fail(VS_EINVAL, "row pointers decrease");
     vs_index* idx = nullptr;
     VS_TRY(vs_index_create_reserved(n_rows, packets, src->n_cols, src->store_dtype, device, &idx));
-    struct Guard { vs_index* p; ~Guard() { if (p) vs_index_destroy(p); } } guard{idx};
+    IndexGuard guard{idx};
     const size_t vb = src->store_dtype == VS_F32 ? 32 : (src->store_dtype == VS_F16 ? 16 : 0);
     auto copy = [&](void* dst, const void* from, size_t bytes) -> int {
         if (bytes == 0) return VS_OK;
@@ -479,7 +480,7 @@ extern "C" int vs_index_create_synthetic(uint64_t seed, int64_t row0, int64_t n_
     if (kind == 1) store_dtype = VS_NONE;
     vs_index* idx = nullptr;
     VS_TRY(new_index(device, &idx));
-    struct Guard { vs_index* p; ~Guard() { if (p) vs_index_destroy(p); } } guard{idx};
+    IndexGuard guard{idx};
     idx->kind = VS_KIND_CSR;
     idx->store_dtype = store_dtype;
     idx->n_rows = n_rows;
@@ -1119,7 +1120,7 @@ extern "C" int vs_index_load_native(const char* path, int device, vs_index** out
     }
     vs_index* idx = nullptr;
     VS_TRY(vs_index_create_reserved(h.n_rows, h.n_packets, h.n_cols, h.store_dtype, device, &idx));
-    struct Guard { vs_index* p; ~Guard() { if (p) vs_index_destroy(p); } } guard{idx};
+    IndexGuard guard{idx};
     {
         PinnedPair pp;
         VS_TRY(pp.init());

@@ -5,6 +5,7 @@
 #include "common.h"
 #include "csr_scan.h"
 #include "dense_csr.h"
+#include "new_index.h"
 
 #include <algorithm>
 
@@ -407,7 +408,7 @@ extern "C" int vs_index_create_dense(const void* mat, int dtype, int store_dtype
     VS_HIP(hipSetDevice(device));
     vs_index* idx = new (std::nothrow) vs_index();
     if (!idx) return fail(VS_ENOMEM, "host allocation failed");
-    struct Guard { vs_index* p; ~Guard() { if (p) vs_index_destroy(p); } } guard{idx};
+    IndexGuard guard{idx};
     hipDeviceProp_t prop;
     VS_HIP(hipGetDeviceProperties(&prop, device));
     idx->device = device;
@@ -486,7 +487,7 @@ extern "C" int vs_index_create_dense_auto(const void* mat, int dtype, int store_
         return vs_index_create_dense(mat, dtype, store_dtype, n_rows, n_cols, ld, device, out);
     vs_index* idx = nullptr;
     VS_TRY(vs_index_create_reserved(n_rows, packets, n_cols, store_dtype, device, &idx));
-    struct Guard { vs_index* p; ~Guard() { if (p) vs_index_destroy(p); } } guard{idx};
+    IndexGuard guard{idx};
     idx->logical_dense = true;
     // pass 2: dense rows -> CSR (ordered compaction on the device) -> packets
     DevBuf d_rp, d_cols, d_vals;

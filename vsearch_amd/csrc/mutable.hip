@@ -1,8 +1,10 @@
 // mutable.hip -- the writable index: tombstones kept in the handle (delete / restore rows, applied by every search as a document filter)
-// and compaction (a new index of the live rows, with spare capacity for appends).  No reference counterpart: the reference's index is
+// and compaction (a new index of the live rows, with spare capacity for appends: the scan and the map that finds the live rows are here, the
+// rest is the scaffold and the shared kernels of new_index.h -- the packets move by the gather of select.hip).  No reference counterpart: the reference's index is
 // a tensor that is rebuilt (index.py:163-179).  Nothing here touches a walk or scan kernel: deletion reaches them as FilterArgs.
 #include "block_scan.h"
 #include "common.h"
+#include "new_index.h"
 
 #include <algorithm>
 
@@ -10,16 +12,6 @@ using namespace vs;
 
 namespace {
 
-int need_device() {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        (void)hipGetLastError();
-        return fail(VS_ENODEVICE, "no HIP device visible: libvsearch_hip has no CPU fallback");
-    }
-    return VS_OK;
-}
-
-int64_t bit_words(int64_t rows) { return (rows + 31) >> 5; }
 // words of the handle's live bitmap: the rows it can ever hold, rounded to whole 16-byte quads (the AND kernel reads and writes quads)
 int64_t live_words(const vs_index* idx) { return (bit_words(std::max(idx->rows_cap, idx->n_rows)) + 3) / 4 * 4; }
 
@@ -98,10 +90,6 @@ __global__ __launch_bounds__(256) void live_out_kernel(const uint32_t* live, int
     }
 }
 
-unsigned grid_for(int64_t items, int per_block = 256, int64_t cap = 8192) {
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((items + per_block - 1) / per_block, cap));
-}
-
 // the handle's bitmap, allocated on the first deletion: every row (and every row still to be appended) live
 int ensure_live(vs_index* idx, hipStream_t s) {
     const size_t bytes = (size_t)live_words(idx) * 4;
@@ -110,14 +98,6 @@ int ensure_live(vs_index* idx, hipStream_t s) {
     VS_TRY(idx->dead_cnt.alloc(8));
     VS_HIP(hipMemsetAsync(idx->live.p, 0xFF, idx->live.bytes, s));
     VS_HIP(hipMemsetAsync(idx->dead_cnt.p, 0, 8, s));
-    return VS_OK;
-}
-
-int ptr_on(const void* p, int device, const char* what) {
-    if (!is_device_ptr(p)) return VS_OK;
-    hipPointerAttribute_t attr;
-    VS_HIP(hipPointerGetAttributes(&attr, p));
-    if (attr.device != device) return fail(VS_EINVAL, "%s lives on device %d, the index on device %d", what, attr.device, device);
     return VS_OK;
 }
 
@@ -139,8 +119,8 @@ int tomb_update(vs_index* idx, const int64_t* ids, int64_t n, int64_t id_offset,
     }
     if (n == 0) return VS_OK;
     const bool dev_ids = is_device_ptr(ids);
-    if (dev_ids) VS_TRY(ptr_on(ids, idx->device, "ids"));
-    else
+    VS_TRY(ptr_on(ids, dev_ids, idx->device, "ids"));
+    if (!dev_ids)
         for (int64_t i = 0; i < n; ++i) {
             const int64_t row = ids[i] - id_offset;
             if (ids[i] != -1 && (row < 0 || row >= idx->n_rows))
@@ -152,10 +132,10 @@ int tomb_update(vs_index* idx, const int64_t* ids, int64_t n, int64_t id_offset,
     const void* d_ids = nullptr;
     VS_TRY(to_device(ids, (size_t)n * 8, stage, s, &d_ids));
     if (del)
-        hipLaunchKernelGGL(tomb_update_kernel<1>, dim3(grid_for(n)), dim3(256), 0, s, (const int64_t*)d_ids, n, id_offset, idx->n_rows, idx->live.as<uint32_t>(),
+        hipLaunchKernelGGL(tomb_update_kernel<1>, dim3(grid_for(n, 256, 8192)), dim3(256), 0, s, (const int64_t*)d_ids, n, id_offset, idx->n_rows, idx->live.as<uint32_t>(),
                            idx->dead_cnt.as<unsigned long long>());
     else
-        hipLaunchKernelGGL(tomb_update_kernel<0>, dim3(grid_for(n)), dim3(256), 0, s, (const int64_t*)d_ids, n, id_offset, idx->n_rows, idx->live.as<uint32_t>(),
+        hipLaunchKernelGGL(tomb_update_kernel<0>, dim3(grid_for(n, 256, 8192)), dim3(256), 0, s, (const int64_t*)d_ids, n, id_offset, idx->n_rows, idx->live.as<uint32_t>(),
                            idx->dead_cnt.as<unsigned long long>());
     VS_HIP(hipGetLastError());
     if (del) idx->has_tomb = true;
@@ -212,7 +192,7 @@ static int recount(vs_index* idx) {
     VS_TRY(cnt.alloc(8));
     VS_HIP(hipMemset(cnt.p, 0, 8));
     if (idx->n_rows > 0)
-        hipLaunchKernelGGL(count_bits_kernel, dim3(grid_for(bit_words(idx->n_rows))), dim3(256), 0, 0, idx->live.as<uint32_t>(), idx->n_rows,
+        hipLaunchKernelGGL(count_bits_kernel, dim3(grid_for(bit_words(idx->n_rows), 256, 8192)), dim3(256), 0, 0, idx->live.as<uint32_t>(), idx->n_rows,
                            cnt.as<unsigned long long>());
     VS_HIP(hipGetLastError());
     int64_t live = 0;
@@ -264,7 +244,7 @@ int tomb_to_host(const vs_index* idx, std::vector<uint32_t>& words) {
     VS_HIP(hipSetDevice(idx->device));
     DevBuf tmp;
     VS_TRY(tmp.alloc(words.size() * 4));
-    hipLaunchKernelGGL(live_out_kernel, dim3(grid_for((int64_t)words.size())), dim3(256), 0, 0, idx->has_tomb ? idx->live.as<uint32_t>() : nullptr, idx->n_rows,
+    hipLaunchKernelGGL(live_out_kernel, dim3(grid_for((int64_t)words.size(), 256, 8192)), dim3(256), 0, 0, idx->has_tomb ? idx->live.as<uint32_t>() : nullptr, idx->n_rows,
                        tmp.as<uint32_t>(), (int64_t)words.size());
     VS_HIP(hipGetLastError());
     VS_HIP(hipMemcpy(words.data(), tmp.p, words.size() * 4, hipMemcpyDeviceToHost));
@@ -303,17 +283,16 @@ extern "C" int vs_index_live_bitmap(const vs_index* idx, uint32_t* out_words, in
     if (n_words < bit_words(idx->n_rows)) return fail(VS_EINVAL, "n_words = %lld is shorter than the %lld words of %lld rows", (long long)n_words,
                                                       (long long)bit_words(idx->n_rows), (long long)idx->n_rows);
     if (n_words == 0) return VS_OK;
-    VS_TRY(ptr_on(out_words, idx->device, "out_words"));
-    VS_HIP(hipSetDevice(idx->device));
-    VS_HIP(hipDeviceSynchronize());                            // (deletions enqueued on a caller's stream)
     const bool out_dev = is_device_ptr(out_words);
+    VS_TRY(ptr_on(out_words, out_dev, idx->device, "out_words"));
+    VS_TRY(open_sources(idx->device));
     DevBuf tmp;
     uint32_t* d = out_words;
     if (!out_dev) {
         VS_TRY(tmp.alloc((size_t)n_words * 4));
         d = tmp.as<uint32_t>();
     }
-    hipLaunchKernelGGL(live_out_kernel, dim3(grid_for(n_words)), dim3(256), 0, 0, idx->has_tomb ? idx->live.as<uint32_t>() : nullptr, idx->n_rows, d, n_words);
+    hipLaunchKernelGGL(live_out_kernel, dim3(grid_for(n_words, 256, 8192)), dim3(256), 0, 0, idx->has_tomb ? idx->live.as<uint32_t>() : nullptr, idx->n_rows, d, n_words);
     VS_HIP(hipGetLastError());
     if (!out_dev) VS_HIP(hipMemcpy(out_words, d, (size_t)n_words * 4, hipMemcpyDeviceToHost));
     VS_HIP(hipDeviceSynchronize());
@@ -364,112 +343,21 @@ __global__ __launch_bounds__(256) void compact_map_kernel(const uint32_t* live, 
     }
 }
 
-// step 2: packet gather.  A wave takes a run of 64 new rows: their packets are one contiguous range of the new index, lane p of it finds its row
-// among the run's 65 row pointers (held one a lane, searched with shuffles) and copies the packet whole -- 16 bytes of column ids, VB bytes of
-// values.  Padding sits in a row's last packet and moves with it.
-template <int VB>
-__global__ __launch_bounds__(256) void compact_gather_kernel(const int64_t* old_ids, const uint32_t* src_pk, const uint32_t* new_pk, int64_t n_new,
-                                                             const uint4* src_cols, const uint4* src_vals, uint4* dst_cols, uint4* dst_vals) {
-    const int lane = threadIdx.x & 63;
-    const int64_t n_runs = (n_new + 63) >> 6;
-    for (int64_t run = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); run < n_runs; run += (int64_t)gridDim.x * 4) {
-        const int64_t j = run * 64 + lane;
-        const uint32_t np = new_pk[j < n_new ? j : n_new];
-        const uint32_t sp = j < n_new ? src_pk[old_ids[j]] : 0u;
-        const int64_t j_end = (run * 64 + 64 < n_new) ? run * 64 + 64 : n_new;
-        const uint32_t p_begin = __shfl(np, 0, 64), p_end = new_pk[j_end];
-        for (int64_t base = p_begin; base < (int64_t)p_end; base += 64) {
-            const int64_t p = base + lane;
-            int i = 0;                                            // the last row of the run whose first packet is <= p: the row p belongs to
-#pragma unroll
-            for (int step = 32; step > 0; step >>= 1) {
-                const uint32_t v = __shfl(np, i + step, 64);
-                if ((int64_t)v <= p) i += step;
-            }
-            const uint32_t npi = __shfl(np, i, 64), spi = __shfl(sp, i, 64);
-            if (p < (int64_t)p_end) {
-                const size_t s = (size_t)spi + (size_t)(p - (int64_t)npi);
-                dst_cols[p] = src_cols[s];
-                if (VB == 16) dst_vals[p] = src_vals[s];
-                if (VB == 32) {
-                    dst_vals[(size_t)p * 2] = src_vals[s * 2];
-                    dst_vals[(size_t)p * 2 + 1] = src_vals[s * 2 + 1];
-                }
-            }
-        }
-    }
-}
-
-// dense (matrix-core) index: row gather of the padded matrix, 16 bytes a lane (ldp is a multiple of 32 floats)
-__global__ __launch_bounds__(256) void compact_dense_kernel(const int64_t* old_ids, int64_t n_new, int64_t quads_per_row, const uint4* src, uint4* dst) {
-    const int64_t n = n_new * quads_per_row;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const int64_t j = i / quads_per_row, c = i % quads_per_row;
-        dst[i] = src[(size_t)old_ids[j] * (size_t)quads_per_row + (size_t)c];
-    }
-}
-
-// step 3: non-zeros of the new index (pads sit at the tail of a row's last packet only)
-__global__ __launch_bounds__(256) void compact_nnz_kernel(const uint32_t* pk, int64_t n_rows, const uint16_t* cols, int32_t n_cols, unsigned long long* out) {
-    unsigned long long nnz = 0;
-    for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < n_rows; r += (int64_t)gridDim.x * 256) {
-        const uint32_t a = pk[r], b = pk[r + 1];
-        if (b > a) {
-            nnz += (unsigned long long)(b - a - 1) * 8ull;
-#pragma unroll
-            for (int i = 0; i < 8; ++i) nnz += cols[(size_t)(b - 1) * 8 + i] != (uint16_t)n_cols ? 1ull : 0ull;
-        }
-    }
-    for (int o = 32; o > 0; o >>= 1) nnz += __shfl_xor(nnz, o, 64);
-    if ((threadIdx.x & 63) == 0 && nnz) atomicAdd(out, nnz);
-}
-
 }  // namespace
 
-namespace vs {
-
-int pick_lanes(int64_t n_packets, int64_t n_rows) {             // (csr_index.hip: pick_lanes_per_row)
-    const double mp = n_rows > 0 ? (double)n_packets / (double)n_rows : 1.0;
-    int g = 4;
-    while (g < 64 && mp / g > 4.0) g <<= 1;
-    return g;
-}
-
-// a CSR index with its capacity, moved whole to another GPU (peer copies): compaction across devices compacts on the source's GPU first
-int move_csr(const vs_index* a, int device, vs_index** out) {
-    vs_index* idx = nullptr;
-    VS_TRY(vs_index_create_reserved(a->rows_cap, a->packets_cap, a->n_cols, a->store_dtype, device, &idx));
-    struct Guard { vs_index* p; ~Guard() { if (p) vs_index_destroy(p); } } guard{idx};
-    const size_t vb = a->store_dtype == VS_F32 ? 32 : (a->store_dtype == VS_F16 ? 16 : 0);
-    VS_HIP(hipMemcpyPeer(idx->pk_ptr.p, device, a->pk_ptr.p, a->device, (size_t)(a->n_rows + 1) * 4));
-    if (a->n_packets) VS_HIP(hipMemcpyPeer(idx->cols.p, device, a->cols.p, a->device, (size_t)a->n_packets * 16));
-    if (a->n_packets && vb) VS_HIP(hipMemcpyPeer(idx->vals.p, device, a->vals.p, a->device, (size_t)a->n_packets * vb));
-    idx->n_rows = a->n_rows;
-    idx->n_packets = a->n_packets;
-    idx->nnz = a->nnz;
-    idx->logical_dense = a->logical_dense;
-    idx->lanes_per_row = a->lanes_per_row;
-    guard.p = nullptr;
-    *out = idx;
-    return VS_OK;
-}
-
-}  // namespace vs
-
 extern "C" int vs_index_compact(const vs_index* src, int64_t rows_extra, int64_t packets_extra, int device, vs_index** out, int64_t* out_old_ids) {
+    char msg[512] = {0};
     VS_TRY(need_device());
     if (!src || !out) return fail(VS_EINVAL, "NULL argument");
     *out = nullptr;
-    if (rows_extra < 0 || packets_extra < 0) return fail(VS_EINVAL, "rows_extra and packets_extra must be >= 0");
-    int ndev = 0;
-    VS_HIP(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(VS_EINVAL, "device %d out of range (have %d)", device, ndev);
+    if (new_index_check_extra(rows_extra, packets_extra, msg, sizeof msg) != VS_OK) return fail(VS_EINVAL, "%s", msg);
+    VS_TRY(device_in_range(device));
     const bool dense = src->kind != VS_KIND_CSR;
     if (dense && (rows_extra || packets_extra)) return fail(VS_EINVAL, "a dense (matrix) index has no append: rows_extra and packets_extra must be 0");
     if (dense && device != src->device) return fail(VS_EUNSUPPORTED, "a dense (matrix) index compacts on its own device");
-    if (out_old_ids) VS_TRY(ptr_on(out_old_ids, src->device, "out_old_ids"));
-    VS_HIP(hipSetDevice(src->device));
-    VS_HIP(hipDeviceSynchronize());                            // deletions enqueued on a caller's stream; everything below runs on the null stream
+    const bool ids_dev = is_device_ptr(out_old_ids);
+    VS_TRY(ptr_on(out_old_ids, ids_dev, src->device, "out_old_ids"));
+    VS_TRY(open_sources(src->device));
     const int64_t n = src->n_rows;
     const uint32_t* live = src->has_tomb ? src->live.as<uint32_t>() : nullptr;
     const uint32_t* pk = dense ? nullptr : src->pk_ptr.as<uint32_t>();
@@ -485,84 +373,37 @@ extern "C" int vs_index_compact(const vs_index* src, int64_t rows_extra, int64_t
     VS_HIP(hipMemcpy(tot, d_sums + n_blocks, 8, hipMemcpyDeviceToHost));
     const int64_t n_new = tot[0], p_new = tot[1];
     if (dense && n_new == 0) return fail(VS_EINVAL, "every row is deleted: a dense (matrix) index cannot be empty");
-    const bool ids_dev = out_old_ids && is_device_ptr(out_old_ids);
     DevBuf old_buf;
     int64_t* d_old = out_old_ids;
     if (!ids_dev) {
         VS_TRY(old_buf.alloc(std::max<size_t>((size_t)n_new * 8, 8)));
         d_old = old_buf.as<int64_t>();
     }
-    vs_index* idx = nullptr;
-    struct Guard { vs_index* p; ~Guard() { if (p) vs_index_destroy(p); } } guard{nullptr};
+    IndexGuard guard{nullptr};
     if (!dense) {
-        if (n_new + rows_extra >= (1ll << 32) - 1 || p_new + packets_extra >= (1ll << 32)) return fail(VS_EUNSUPPORTED, "the compacted index with its spare capacity exceeds 2^32 rows or packets");
-        const size_t vb = src->store_dtype == VS_F32 ? 32 : (src->store_dtype == VS_F16 ? 16 : 0);
-        if (vs_index_create_reserved(n_new + rows_extra, p_new + packets_extra, src->n_cols, src->store_dtype, src->device, &idx) != VS_OK) {
-            const size_t need = (size_t)(p_new + packets_extra) * (16 + vb) + (size_t)(n_new + rows_extra + 1) * 4;
-            return fail(VS_ENOMEM, "compaction needs %zu bytes of HBM for the new index next to the source's (drop the postings copy of the source, or compact onto another GPU)", need);
-        }
-        guard.p = idx;
+        const int rc = new_index_check_capacity("compacted", n_new, p_new, rows_extra, packets_extra, msg, sizeof msg);
+        if (rc != VS_OK) return fail(rc, "%s", msg);
+        VS_TRY(new_csr_index("compaction", "source's (drop the postings copy of the source, or compact onto another GPU)", n_new, p_new, rows_extra, packets_extra,
+                             src->n_cols, src->store_dtype, src->device, &guard));
+        vs_index* idx = guard.p;
         hipLaunchKernelGGL(compact_map_kernel, dim3((unsigned)n_blocks), dim3(256), 0, 0, live, pk, n, (const uint2*)d_sums, d_old, idx->pk_ptr.as<uint32_t>());
         VS_HIP(hipGetLastError());
         const uint32_t last = (uint32_t)p_new;
         VS_HIP(hipMemcpy(idx->pk_ptr.as<uint32_t>() + n_new, &last, 4, hipMemcpyHostToDevice));
-        // 2. gather
-        if (p_new > 0) {
-            const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(((n_new + 63) / 64 + 3) / 4, (int64_t)src->cu_count * 32));
-            const uint4 *sc = src->cols.as<uint4>(), *sv = src->vals.as<uint4>();
-            uint4 *dc = idx->cols.as<uint4>(), *dv = idx->vals.as<uint4>();
-            const uint32_t* npk = idx->pk_ptr.as<uint32_t>();
-            if (vb == 32) hipLaunchKernelGGL(compact_gather_kernel<32>, dim3(grid), dim3(256), 0, 0, (const int64_t*)d_old, pk, npk, n_new, sc, sv, dc, dv);
-            else if (vb == 16) hipLaunchKernelGGL(compact_gather_kernel<16>, dim3(grid), dim3(256), 0, 0, (const int64_t*)d_old, pk, npk, n_new, sc, sv, dc, dv);
-            else hipLaunchKernelGGL(compact_gather_kernel<0>, dim3(grid), dim3(256), 0, 0, (const int64_t*)d_old, pk, npk, n_new, sc, sv, dc, dv);
-            VS_HIP(hipGetLastError());
-        }
+        // 2. gather: the live rows are a selection, old_ids its id list
+        if (p_new > 0) VS_TRY(launch_packet_gather(src, d_old, 0, idx->pk_ptr.as<uint32_t>(), n_new, idx->cols.as<uint4>(), idx->vals.as<uint4>()));
         // 3. non-zeros
         DevBuf cnt;
         VS_TRY(cnt.alloc(8));
         VS_HIP(hipMemset(cnt.p, 0, 8));
-        if (n_new > 0)
-            hipLaunchKernelGGL(compact_nnz_kernel, dim3(grid_for(n_new, 256, 4096)), dim3(256), 0, 0, idx->pk_ptr.as<uint32_t>(), n_new, idx->cols.as<uint16_t>(),
-                               src->n_cols, cnt.as<unsigned long long>());
-        VS_HIP(hipGetLastError());
+        VS_TRY(launch_nnz_recount(idx, n_new, cnt.as<unsigned long long>()));
         unsigned long long nnz = 0;
         VS_HIP(hipMemcpy(&nnz, cnt.p, 8, hipMemcpyDeviceToHost));
-        idx->n_rows = n_new;
-        idx->n_packets = p_new;
-        idx->nnz = (int64_t)nnz;
-        idx->logical_dense = src->logical_dense;
-        idx->lanes_per_row = pick_lanes(p_new, n_new);
+        set_csr_shape(idx, n_new, p_new, (int64_t)nnz, src->logical_dense);
     } else {
-        idx = new (std::nothrow) vs_index();
-        if (!idx) return fail(VS_ENOMEM, "host allocation failed");
-        guard.p = idx;
-        idx->kind = VS_KIND_DENSE;
-        idx->device = src->device;
-        idx->cu_count = src->cu_count;
-        idx->store_dtype = src->store_dtype;
-        idx->n_rows = n_new;
-        idx->n_cols = src->n_cols;
-        idx->nnz = n_new * (int64_t)src->n_cols;
-        const size_t row_bytes = src->mat.bytes / (size_t)n;               // the padded row (dense.hip: a multiple of 32 floats)
-        if (idx->mat.alloc((size_t)n_new * row_bytes) != VS_OK)
-            return fail(VS_ENOMEM, "compaction needs %zu bytes of HBM for the new matrix next to the source's", (size_t)n_new * row_bytes);
         hipLaunchKernelGGL(compact_map_kernel, dim3((unsigned)n_blocks), dim3(256), 0, 0, live, pk, n, (const uint2*)d_sums, d_old, (uint32_t*)nullptr);
-        const int64_t qpr = (int64_t)(row_bytes / 16);
-        hipLaunchKernelGGL(compact_dense_kernel, dim3(grid_for(n_new * qpr, 256, (int64_t)src->cu_count * 32)), dim3(256), 0, 0, (const int64_t*)d_old, n_new, qpr,
-                           src->mat.as<uint4>(), idx->mat.as<uint4>());
-        VS_HIP(hipGetLastError());
+        VS_TRY(new_dense_rows("compaction", src, d_old, 0, n_new, &guard));
     }
     if (out_old_ids && !ids_dev && n_new > 0) VS_HIP(hipMemcpy(out_old_ids, d_old, (size_t)n_new * 8, hipMemcpyDeviceToHost));
-    VS_HIP(hipDeviceSynchronize());
-    if (device != src->device) {                                // the compacted index moves to its GPU; the copy on the source's GPU is dropped
-        vs_index* moved = nullptr;
-        VS_TRY(move_csr(idx, device, &moved));
-        VS_HIP(hipSetDevice(src->device));
-        vs_index_destroy(idx);
-        guard.p = nullptr;
-        idx = moved;
-    }
-    guard.p = nullptr;
-    *out = idx;
-    return VS_OK;
+    return hand_over(guard, src->device, device, TombFrom::none(), out);   // the live rows alone: nothing is deleted in the new index
 }

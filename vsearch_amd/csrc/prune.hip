@@ -1,11 +1,11 @@
 // prune.hip -- index pruning: a NEW index holding, for every row of a CSR index, a pinned subset of its stored cells (vs_index_prune; the
 // semantics are pinned in vsearch_hip.h).  The reference fixes a document's sparsity when it embeds it -- embed(..., topk = 768), mask =
 // bow_mask | topk_mask (encoder/vdr.py:102-168) --; the stored rows hold everything a smaller topk needs, so the index built with topk = m is
-// made here from the index built with topk = 768 and the bag-of-token rows (the protect index).  Three steps on the source's GPU, shaped like
-// vs_index_compact (mutable.hip): select (a keep byte a source packet, a kept count a row), scan (block_scan.h), pack.  Nothing here touches a
-// walk or scan kernel.
-#include "block_scan.h"
+// made here from the index built with topk = 768 and the bag-of-token rows (the protect index).  Three steps on the source's GPU: select (a
+// keep byte a source packet, a kept count a row), scan (row pointers from the kept counts: the shared pair of new_index.h), pack.  The
+// scaffold of the call is new_index.h.  Nothing here touches a walk or scan kernel.
 #include "common.h"
+#include "new_index.h"
 #include "prune_check.h"
 
 #include <algorithm>
@@ -14,24 +14,6 @@
 using namespace vs;
 
 namespace {
-
-int need_device() {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        (void)hipGetLastError();
-        return fail(VS_ENODEVICE, "no HIP device visible: libvsearch_hip has no CPU fallback");
-    }
-    return VS_OK;
-}
-
-// a device pointer of the caller's belongs to the source's GPU
-int ptr_on(const void* p, bool on_device, int device, const char* what) {
-    if (!on_device) return VS_OK;
-    hipPointerAttribute_t attr;
-    VS_HIP(hipPointerGetAttributes(&attr, p));
-    if (attr.device != device) return fail(VS_EINVAL, "%s lives on device %d, the index on device %d", what, attr.device, device);
-    return VS_OK;
-}
 
 // this wave's LDS writes precede its LDS reads behind this point (LDS executes a wave's operations in order; the fence keeps the compiler's
 // order and waits for the counter)
@@ -281,41 +263,6 @@ __global__ __launch_bounds__(kPruneThreads) void prune_select_kernel(SelectArgs 
     }
 }
 
-// ---- step (b): scan -- (kept cells, new packets) a row; the packets give the new row pointers, the cells the non-zeros ---------------------------
-__device__ __forceinline__ uint2 kept_stat(const int32_t* kept, int64_t r, int64_t n_rows) {
-    if (r >= n_rows) return make_uint2(0u, 0u);
-    const uint32_t k = (uint32_t)kept[r];
-    return make_uint2(k, (k + 7u) >> 3);
-}
-
-// (a block's cells fit 32 bits: 4096 rows x 65535; their sum over the index goes to *nnz, the scanned .x of the block sums is not used)
-__global__ __launch_bounds__(256) void prune_sums_kernel(const int32_t* kept, int64_t n_rows, uint2* sums, unsigned long long* nnz) {
-    __shared__ uint2 sh[4];
-    const int64_t r0 = (int64_t)blockIdx.x * kScanRows;
-    uint2 acc = make_uint2(0u, 0u);
-    for (int it = 0; it < kScanItems; ++it) acc = add2(acc, kept_stat(kept, r0 + it * 256 + threadIdx.x, n_rows));
-    uint2 tot;
-    (void)block_excl_scan<4>(acc, sh, &tot);
-    if (threadIdx.x == 0) {
-        sums[blockIdx.x] = tot;
-        if (tot.x) atomicAdd(nnz, (unsigned long long)tot.x);
-    }
-}
-
-__global__ __launch_bounds__(256) void prune_map_kernel(const int32_t* kept, int64_t n_rows, const uint2* sums, uint32_t* new_pk) {
-    __shared__ uint2 sh[4];
-    const int64_t r0 = (int64_t)blockIdx.x * kScanRows;
-    uint2 carry = sums[blockIdx.x];
-    for (int it = 0; it < kScanItems; ++it) {
-        const int64_t r = r0 + it * 256 + threadIdx.x;
-        const uint2 v = kept_stat(kept, r, n_rows);
-        uint2 tot;
-        const uint2 ex = block_excl_scan<4>(v, sh, &tot);
-        if (r < n_rows) new_pk[r] = carry.y + ex.y;
-        carry = add2(carry, tot);
-    }
-}
-
 // ---- step (c): pack ---------------------------------------------------------------------------------------------------------------------------
 struct PackArgs {
     const uint32_t* pk;               // the source
@@ -420,17 +367,14 @@ extern "C" int vs_index_prune(const vs_index* src, int32_t topk, float min_value
     char msg[512] = {0};
     if (out) *out = nullptr;
     const bool has_min = !std::isnan(min_value);
-    int rc = prune_check_extra(rows_extra, packets_extra, msg, sizeof msg);
+    int rc = new_index_check_extra(rows_extra, packets_extra, msg, sizeof msg);
     if (rc == VS_OK) rc = prune_check_rules(topk, has_min, src ? src->store_dtype : VS_F32, msg, sizeof msg);
     if (rc != VS_OK) return fail(rc, "%s", msg);
     if (!src || !out) return fail(VS_EINVAL, "NULL argument");
     rc = prune_check_source(shape_of(src), msg, sizeof msg);
     if (rc == VS_OK && protect) rc = prune_check_protect(shape_of(src), shape_of(protect), msg, sizeof msg);
     if (rc != VS_OK) return fail(rc, "%s", msg);
-    VS_TRY(need_device());
-    int ndev = 0;
-    VS_HIP(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(VS_EINVAL, "device %d out of range (have %d)", device, ndev);
+    VS_TRY(device_in_range(device));
     const bool keep_dev = is_device_ptr(col_keep), kept_dev = is_device_ptr(out_kept);
     rc = prune_check_pointers(col_keep != nullptr, keep_dev, out_kept != nullptr, kept_dev, msg, sizeof msg);
     if (rc != VS_OK) return fail(rc, "%s", msg);
@@ -440,8 +384,7 @@ extern "C" int vs_index_prune(const vs_index* src, int32_t topk, float min_value
     rc = prune_plan(src->n_rows, src->n_packets, src->n_cols, src->store_dtype, topk, protect != nullptr, &plan, msg, sizeof msg);
     if (rc != VS_OK) return fail(rc, "%s", msg);
 
-    VS_HIP(hipSetDevice(src->device));
-    VS_HIP(hipDeviceSynchronize());                            // work enqueued on a caller's stream; everything below runs on the null stream
+    VS_TRY(open_sources(src->device));
     const int64_t n = src->n_rows, n_src_packets = src->n_packets;
     const int sd = src->store_dtype;
     // scratch: keep bytes, kept counts, block sums, the non-zero count
@@ -482,27 +425,17 @@ extern "C" int vs_index_prune(const vs_index* src, int32_t topk, float min_value
     }
     // (b) scan
     uint2* d_sums = sums.as<uint2>();
-    hipLaunchKernelGGL(prune_sums_kernel, dim3((unsigned)plan.scan_blocks), dim3(256), 0, 0, (const int32_t*)d_kept, n, d_sums, cnt.as<unsigned long long>());
-    hipLaunchKernelGGL(scan_block_sums_kernel<0>, dim3(1), dim3(1024), 0, 0, d_sums, plan.scan_blocks, d_sums + plan.scan_blocks);
-    VS_HIP(hipGetLastError());
-    uint32_t tot[2] = {0u, 0u};
-    VS_HIP(hipMemcpy(tot, d_sums + plan.scan_blocks, 8, hipMemcpyDeviceToHost));
+    int64_t p_new = 0;
+    VS_TRY(cells_scan(d_kept, n, plan.scan_blocks, d_sums, cnt.as<unsigned long long>(), &p_new));
     unsigned long long nnz = 0;
     VS_HIP(hipMemcpy(&nnz, cnt.p, 8, hipMemcpyDeviceToHost));
-    const int64_t p_new = tot[1];
-    rc = prune_check_capacity(n, p_new, rows_extra, packets_extra, msg, sizeof msg);
+    rc = new_index_check_capacity("pruned", n, p_new, rows_extra, packets_extra, msg, sizeof msg);
     if (rc != VS_OK) return fail(rc, "%s", msg);
-    const size_t vb = sd == VS_F32 ? 32 : (sd == VS_F16 ? 16 : 0);
-    vs_index* idx = nullptr;
-    if (vs_index_create_reserved(n + rows_extra, p_new + packets_extra, src->n_cols, sd, src->device, &idx) != VS_OK) {
-        const size_t need = (size_t)(p_new + packets_extra) * (16 + vb) + (size_t)(n + rows_extra + 1) * 4;
-        return fail(VS_ENOMEM, "pruning needs %zu bytes of HBM for the new index next to the source's (drop the postings copy of the source, or prune onto fewer cells)", need);
-    }
-    struct Guard { vs_index* p; ~Guard() { if (p) vs_index_destroy(p); } } guard{idx};
-    hipLaunchKernelGGL(prune_map_kernel, dim3((unsigned)plan.scan_blocks), dim3(256), 0, 0, (const int32_t*)d_kept, n, (const uint2*)d_sums, idx->pk_ptr.as<uint32_t>());
-    VS_HIP(hipGetLastError());
-    const uint32_t last = (uint32_t)p_new;
-    VS_HIP(hipMemcpy(idx->pk_ptr.as<uint32_t>() + n, &last, 4, hipMemcpyHostToDevice));
+    IndexGuard guard{nullptr};
+    VS_TRY(new_csr_index("pruning", "source's (drop the postings copy of the source, or prune onto fewer cells)", n, p_new, rows_extra, packets_extra, src->n_cols,
+                         sd, src->device, &guard));
+    vs_index* idx = guard.p;
+    VS_TRY(cells_row_pointers(d_kept, n, plan.scan_blocks, d_sums, p_new, idx->pk_ptr.as<uint32_t>()));
     // (c) pack
     if (p_new > 0) {
         PackArgs a;
@@ -521,23 +454,7 @@ extern "C" int vs_index_prune(const vs_index* src, int32_t topk, float min_value
         else hipLaunchKernelGGL(prune_pack_kernel<VS_NONE>, dim3(grid), dim3(kPruneThreads), 0, 0, a);
         VS_HIP(hipGetLastError());
     }
-    idx->n_rows = n;
-    idx->n_packets = p_new;
-    idx->nnz = (int64_t)nnz;
-    idx->logical_dense = src->logical_dense;
-    idx->lanes_per_row = pick_lanes(p_new, n);
+    set_csr_shape(idx, n, p_new, (int64_t)nnz, src->logical_dense);
     if (out_kept && !kept_dev && n > 0) VS_HIP(hipMemcpy(out_kept, d_kept, (size_t)n * 4, hipMemcpyDeviceToHost));
-    VS_HIP(hipDeviceSynchronize());
-    if (device != src->device) {                                // the pruned index moves to its GPU; the copy on the source's GPU is dropped
-        vs_index* moved = nullptr;
-        VS_TRY(move_csr(idx, device, &moved));
-        VS_HIP(hipSetDevice(src->device));
-        vs_index_destroy(idx);
-        idx = moved;
-        guard.p = idx;
-    }
-    VS_TRY(tomb_from_bits(idx, src, 0));                       // rows are 1:1 with the source's: deleted rows stay deleted, restore() brings them back pruned
-    guard.p = nullptr;
-    *out = idx;
-    return VS_OK;
+    return hand_over(guard, src->device, device, TombFrom::source_bits(src), out);
 }

@@ -4,6 +4,7 @@
 // Plain C++ with no HIP in it, so that a stand-alone program can run them under a host sanitizer (tests/test_prune_cpu.py builds one).
 #pragma once
 
+#include "new_index_check.h"
 #include "value_check.h"
 
 namespace vs {
@@ -26,7 +27,7 @@ struct PrunePlan {
 // the rules against the store: a binary index holds 1 everywhere, so a cut by value is a mistake of the caller's
 inline int prune_check_rules(int32_t topk, bool has_min, int store_dtype, char* msg, size_t cap) {
     if (topk < 0 || topk > kPruneMaxTopk) return snprintf(msg, cap, "topk must be in 0..%d (0: no cut; got %d)", kPruneMaxTopk, topk), VS_EINVAL;
-    if (store_dtype != VS_F32 && store_dtype != VS_F16 && store_dtype != VS_NONE) return snprintf(msg, cap, "bad store_dtype %d", store_dtype), VS_EINVAL;
+    if (!store_dtype_ok(store_dtype)) return snprintf(msg, cap, "bad store_dtype %d", store_dtype), VS_EINVAL;
     if (store_dtype == VS_NONE && (topk > 0 || has_min))
         return snprintf(msg, cap, "topk and min_value need stored values: every value of a binary index is 1 (col_keep alone is allowed)"), VS_EINVAL;
     return VS_OK;
@@ -78,18 +79,6 @@ inline int prune_check_pointers(bool have_keep, bool keep_on_device, bool have_k
     if (have_keep && have_kept && keep_on_device != kept_on_device)
         return snprintf(msg, cap, "col_keep is a %s pointer and out_kept a %s pointer: pass both on the host or both on the device", keep_on_device ? "device" : "host",
                         kept_on_device ? "device" : "host"), VS_EINVAL;
-    return VS_OK;
-}
-
-inline int prune_check_extra(int64_t rows_extra, int64_t packets_extra, char* msg, size_t cap) {
-    if (rows_extra < 0 || packets_extra < 0) return snprintf(msg, cap, "rows_extra and packets_extra must be >= 0"), VS_EINVAL;
-    return VS_OK;
-}
-
-// the limits of vs_index_compact: row and packet counts with their spare capacity fit 32 bits
-inline int prune_check_capacity(int64_t n_rows, int64_t new_packets, int64_t rows_extra, int64_t packets_extra, char* msg, size_t cap) {
-    if (rows_extra > (1ll << 32) || packets_extra > (1ll << 32) || n_rows + rows_extra >= (1ll << 32) - 1 || new_packets + packets_extra >= (1ll << 32))
-        return snprintf(msg, cap, "the pruned index with its spare capacity exceeds 2^32 rows or packets"), VS_EUNSUPPORTED;
     return VS_OK;
 }
 

@@ -175,13 +175,13 @@ int main() {
     expect("pointers one", prune_check_pointers(true, true, false, false, msg, sizeof msg), VS_OK, msg, "");
     expect("pointers mixed", prune_check_pointers(true, true, true, false, msg, sizeof msg), VS_EINVAL, msg, "both");
     expect("pointers mixed 2", prune_check_pointers(true, false, true, true, msg, sizeof msg), VS_EINVAL, msg, "both");
-    expect("extra ok", prune_check_extra(0, 5, msg, sizeof msg), VS_OK, msg, "");
-    expect("extra rows", prune_check_extra(-1, 0, msg, sizeof msg), VS_EINVAL, msg, ">= 0");
-    expect("extra packets", prune_check_extra(0, -1, msg, sizeof msg), VS_EINVAL, msg, ">= 0");
-    expect("capacity ok", prune_check_capacity(100, 1000, 5, 7, msg, sizeof msg), VS_OK, msg, "");
-    expect("capacity rows", prune_check_capacity(0xFFFFFFF0ll, 10, 0xF, 0, msg, sizeof msg), VS_EUNSUPPORTED, msg, "2^32");
-    expect("capacity packets", prune_check_capacity(10, 0xFFFFFFF0ll, 0, 0x10, msg, sizeof msg), VS_EUNSUPPORTED, msg, "2^32");
-    expect("capacity huge extra", prune_check_capacity(10, 10, 0x7FFFFFFFFFFFFFFFll, 0, msg, sizeof msg), VS_EUNSUPPORTED, msg, "2^32");
+    expect("extra ok", new_index_check_extra(0, 5, msg, sizeof msg), VS_OK, msg, "");
+    expect("extra rows", new_index_check_extra(-1, 0, msg, sizeof msg), VS_EINVAL, msg, ">= 0");
+    expect("extra packets", new_index_check_extra(0, -1, msg, sizeof msg), VS_EINVAL, msg, ">= 0");
+    expect("capacity ok", new_index_check_capacity("pruned", 100, 1000, 5, 7, msg, sizeof msg), VS_OK, msg, "");
+    expect("capacity rows", new_index_check_capacity("pruned", 0xFFFFFFF0ll, 10, 0xF, 0, msg, sizeof msg), VS_EUNSUPPORTED, msg, "2^32");
+    expect("capacity packets", new_index_check_capacity("pruned", 10, 0xFFFFFFF0ll, 0, 0x10, msg, sizeof msg), VS_EUNSUPPORTED, msg, "2^32");
+    expect("capacity huge extra", new_index_check_capacity("pruned", 10, 10, 0x7FFFFFFFFFFFFFFFll, 0, msg, sizeof msg), VS_EUNSUPPORTED, msg, "2^32");
 
     if (failures) {
         fprintf(stderr, "prune_check: %d failures\n", failures);

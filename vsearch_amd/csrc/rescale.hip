@@ -2,8 +2,10 @@
 // sparsity whose values are the source's times a scale per row and a scale per column, in fp32 or fp16 (vs_index_rescale; the arithmetic is
 // pinned in vsearch_hip.h).  No reference counterpart: the reference's index is a tensor that is multiplied and rebuilt.  The sparsity is kept, so
 // the row pointers and the packets' column ids are the source's bit for bit and only the value array is new: one bandwidth-bound stream in the
-// shape of the gather of select.hip.  The host-only part is rescale_check.h.  Nothing here touches a walk or scan kernel.
+// shape of the gather of select.hip.  The scaffold of the call is new_index.h, the host-only part rescale_check.h.  Nothing here touches a
+// walk or scan kernel.
 #include "common.h"
+#include "new_index.h"
 #include "packets.h"
 #include "rescale_check.h"
 
@@ -12,24 +14,6 @@
 using namespace vs;
 
 namespace {
-
-int need_device() {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        (void)hipGetLastError();
-        return fail(VS_ENODEVICE, "no HIP device visible: libvsearch_hip has no CPU fallback");
-    }
-    return VS_OK;
-}
-
-// a device pointer of the caller's belongs to the source's GPU
-int ptr_on(const void* p, bool on_device, int device, const char* what) {
-    if (!on_device) return VS_OK;
-    hipPointerAttribute_t attr;
-    VS_HIP(hipPointerGetAttributes(&attr, p));
-    if (attr.device != device) return fail(VS_EINVAL, "%s lives on device %d, the index on device %d", what, attr.device, device);
-    return VS_OK;
-}
 
 RescaleShape shape_of(const vs_index* a) {
     RescaleShape s;
@@ -311,8 +295,7 @@ extern "C" int vs_index_row_stats(const vs_index* src, int32_t* out_cells, int32
     for (int i = 0; i < 5; ++i) VS_TRY(ptr_on(outs[i], ((on_dev >> i) & 1u) != 0u, src->device, names[i]));
     const int64_t n = src->n_rows;
     if (n == 0 || have == 0u) return VS_OK;
-    VS_HIP(hipSetDevice(src->device));
-    VS_HIP(hipDeviceSynchronize());                            // work enqueued on a caller's stream; everything below runs on the null stream
+    VS_TRY(open_sources(src->device));
     const bool host = on_dev == 0u;
     DevBuf stage;
     void* dev[5] = {out_cells, out_nonzero, out_l1, out_sumsq, out_max};
@@ -359,31 +342,24 @@ extern "C" int vs_index_rescale(const vs_index* src, const float* row_scale, con
     int rc = rescale_check_args(src != nullptr, out != nullptr, out_dtype, rows_extra, packets_extra, msg, sizeof msg);
     if (rc == VS_OK) rc = rescale_check_source(shape_of(src), "rescale", msg, sizeof msg);
     if (rc != VS_OK) return fail(rc, "%s", msg);
-    VS_TRY(need_device());
-    int ndev = 0;
-    VS_HIP(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(VS_EINVAL, "device %d out of range (have %d)", device, ndev);
+    VS_TRY(device_in_range(device));
     VS_TRY(ptr_on(row_scale, is_device_ptr(row_scale), src->device, "row_scale"));
     VS_TRY(ptr_on(col_scale, is_device_ptr(col_scale), src->device, "col_scale"));
     const int64_t n = src->n_rows, n_packets = src->n_packets;
     RescalePlan plan;
     rc = rescale_plan(n, n_packets, src->n_cols, src->store_dtype, out_dtype, row_scale != nullptr, col_scale != nullptr, &plan, msg, sizeof msg);
-    if (rc == VS_OK) rc = rescale_check_capacity(n, n_packets, rows_extra, packets_extra, msg, sizeof msg);
+    if (rc == VS_OK) rc = new_index_check_capacity("rescaled", n, n_packets, rows_extra, packets_extra, msg, sizeof msg);
     if (rc != VS_OK) return fail(rc, "%s", msg);
 
-    VS_HIP(hipSetDevice(src->device));
-    VS_HIP(hipDeviceSynchronize());                            // scales enqueued on a caller's stream; everything below runs on the null stream
+    VS_TRY(open_sources(src->device));
     DevBuf rs_stage, cs_stage;
     const void *d_rs = nullptr, *d_cs = nullptr;
     if (row_scale && n > 0) VS_TRY(to_device(row_scale, (size_t)n * 4, rs_stage, 0, &d_rs));
     if (col_scale) VS_TRY(to_device(col_scale, (size_t)src->n_cols * 4, cs_stage, 0, &d_cs));
-    const size_t vb = out_dtype == VS_F32 ? 32 : 16;
-    vs_index* idx = nullptr;
-    if (vs_index_create_reserved(n + rows_extra, n_packets + packets_extra, src->n_cols, out_dtype, src->device, &idx) != VS_OK) {
-        const size_t need = (size_t)(n_packets + packets_extra) * (16 + vb) + (size_t)(n + rows_extra + 1) * 4;
-        return fail(VS_ENOMEM, "rescaling needs %zu bytes of HBM for the new index next to the source's (drop the postings copy of the source)", need);
-    }
-    struct Guard { vs_index* p; ~Guard() { if (p) vs_index_destroy(p); } } guard{idx};
+    IndexGuard guard{nullptr};
+    VS_TRY(new_csr_index("rescaling", "source's (drop the postings copy of the source)", n, n_packets, rows_extra, packets_extra, src->n_cols, out_dtype, src->device,
+                         &guard));
+    vs_index* idx = guard.p;
     VS_HIP(hipMemcpy(idx->pk_ptr.p, src->pk_ptr.p, (size_t)(n + 1) * 4, hipMemcpyDeviceToDevice));      // the row pointers are the source's
     if (n_packets > 0) {
         RescaleArgs a;
@@ -400,22 +376,6 @@ extern "C" int vs_index_rescale(const vs_index* src, const float* row_scale, con
         else if (src->store_dtype == VS_F16) VS_TRY(launch_rescale_od<VS_F16>(out_dtype, plan, src->cu_count, a));
         else VS_TRY(launch_rescale_od<VS_NONE>(out_dtype, plan, src->cu_count, a));
     }
-    idx->n_rows = n;
-    idx->n_packets = n_packets;
-    idx->nnz = src->nnz;
-    idx->logical_dense = src->logical_dense;
-    idx->lanes_per_row = pick_lanes(n_packets, n);
-    VS_HIP(hipDeviceSynchronize());
-    if (device != src->device) {                                // the new index moves to its GPU; the copy on the source's GPU is dropped
-        vs_index* moved = nullptr;
-        VS_TRY(move_csr(idx, device, &moved));
-        VS_HIP(hipSetDevice(src->device));
-        vs_index_destroy(idx);
-        idx = moved;
-        guard.p = idx;
-    }
-    VS_TRY(tomb_from_bits(idx, src, 0));                       // rows are 1:1 with the source's: deleted rows stay deleted, restore() brings them back rescaled
-    guard.p = nullptr;
-    *out = idx;
-    return VS_OK;
+    set_csr_shape(idx, n, n_packets, src->nnz, src->logical_dense);
+    return hand_over(guard, src->device, device, TombFrom::source_bits(src), out);
 }

@@ -3,7 +3,7 @@
 // Plain C++ with no HIP in it, so that a stand-alone program can run them under a host sanitizer (tests/test_rescale_cpu.py builds one).
 #pragma once
 
-#include "set_check.h"
+#include "new_index_check.h"
 
 namespace vs {
 
@@ -32,17 +32,15 @@ struct RescalePlan {
     int64_t scratch_bytes = 0;                        // host scales staged on the device: 4 bytes a row and 4 a column, for the scales given
 };
 
-inline bool rescale_dtype_ok(int dt) { return dt == VS_F32 || dt == VS_F16; }
-
 inline int rescale_plan(int64_t n_rows, int64_t n_packets, int32_t n_cols, int src_dtype, int out_dtype, bool has_row_scale, bool has_col_scale,
                         RescalePlan* out, char* msg, size_t cap) {
     if (n_rows < 0 || n_rows >= 0xFFFFFFFFll) return snprintf(msg, cap, "n_rows must be in 0..2^32 - 2 (got %lld)", (long long)n_rows), VS_EINVAL;
     if (n_packets < 0 || n_packets >= (1ll << 32)) return snprintf(msg, cap, "n_packets must be in 0..2^32 - 1 (got %lld)", (long long)n_packets), VS_EINVAL;
     if (n_cols < 1) return snprintf(msg, cap, "n_cols must be positive (got %d)", n_cols), VS_EINVAL;
     if (n_cols > kTermMaxCols) return snprintf(msg, cap, "n_cols = %d > %d: column ids are stored as uint16", n_cols, kTermMaxCols), VS_EUNSUPPORTED;
-    if (src_dtype != VS_F32 && src_dtype != VS_F16 && src_dtype != VS_NONE) return snprintf(msg, cap, "bad source store_dtype %d", src_dtype), VS_EINVAL;
+    if (!store_dtype_ok(src_dtype)) return snprintf(msg, cap, "bad source store_dtype %d", src_dtype), VS_EINVAL;
     if (out_dtype == VS_NONE) return snprintf(msg, cap, "out_dtype VS_NONE: binarising an index is not covered (VS_F32 or VS_F16)"), VS_EINVAL;
-    if (!rescale_dtype_ok(out_dtype)) return snprintf(msg, cap, "out_dtype must be VS_F32 or VS_F16 (got %d)", out_dtype), VS_EINVAL;
+    if (!valued_dtype_ok(out_dtype)) return snprintf(msg, cap, "out_dtype must be VS_F32 or VS_F16 (got %d)", out_dtype), VS_EINVAL;
     RescalePlan p;
     if (has_col_scale) {
         const bool fits = n_cols <= kRescaleImgMaxCols;
@@ -65,9 +63,9 @@ struct RescaleShape {
 
 // the arguments of vs_index_rescale that need neither the handle nor a device
 inline int rescale_check_args(bool have_src, bool have_out, int out_dtype, int64_t rows_extra, int64_t packets_extra, char* msg, size_t cap) {
-    if (rows_extra < 0 || packets_extra < 0) return snprintf(msg, cap, "rows_extra and packets_extra must be >= 0"), VS_EINVAL;
+    if (new_index_check_extra(rows_extra, packets_extra, msg, cap) != VS_OK) return VS_EINVAL;
     if (out_dtype == VS_NONE) return snprintf(msg, cap, "out_dtype VS_NONE: binarising an index is not covered (VS_F32 or VS_F16)"), VS_EINVAL;
-    if (!rescale_dtype_ok(out_dtype)) return snprintf(msg, cap, "out_dtype must be VS_F32 or VS_F16 (got %d)", out_dtype), VS_EINVAL;
+    if (!valued_dtype_ok(out_dtype)) return snprintf(msg, cap, "out_dtype must be VS_F32 or VS_F16 (got %d)", out_dtype), VS_EINVAL;
     if (!have_src || !have_out) return snprintf(msg, cap, "NULL argument"), VS_EINVAL;
     return VS_OK;
 }
@@ -86,13 +84,6 @@ inline int stats_check_outputs(bool have_src, uint32_t have, uint32_t on_device,
     on_device &= have;
     if (on_device != 0u && on_device != have)
         return snprintf(msg, cap, "the outputs mix host and device pointers: pass all of them on the host or all on the device"), VS_EINVAL;
-    return VS_OK;
-}
-
-// the limits of vs_index_compact: row and packet counts with their spare capacity fit 32 bits
-inline int rescale_check_capacity(int64_t n_rows, int64_t n_packets, int64_t rows_extra, int64_t packets_extra, char* msg, size_t cap) {
-    if (rows_extra > (1ll << 32) || packets_extra > (1ll << 32) || n_rows + rows_extra >= (1ll << 32) - 1 || n_packets + packets_extra >= (1ll << 32))
-        return snprintf(msg, cap, "the rescaled index with its spare capacity exceeds 2^32 rows or packets"), VS_EUNSUPPORTED;
     return VS_OK;
 }
 

@@ -90,11 +90,11 @@ int main() {
     expect("stats mixed", stats_check_outputs(true, 31u, 4u, msg, sizeof msg), VS_EINVAL, msg, "mix host and device");
     expect("stats mixed two", stats_check_outputs(true, 3u, 1u, msg, sizeof msg), VS_EINVAL, msg, "mix host and device");
     expect("stats src", stats_check_outputs(false, 31u, 0u, msg, sizeof msg), VS_EINVAL, msg, "NULL");
-    expect("capacity ok", rescale_check_capacity(100, 1000, 5, 7, msg, sizeof msg), VS_OK, msg, "");
-    expect("capacity nothing", rescale_check_capacity(0, 0, 0, 0, msg, sizeof msg), VS_OK, msg, "");
-    expect("capacity rows", rescale_check_capacity(0xFFFFFFF0ll, 10, 0xF, 0, msg, sizeof msg), VS_EUNSUPPORTED, msg, "2^32");
-    expect("capacity packets", rescale_check_capacity(10, 0xFFFFFFF0ll, 0, 0x10, msg, sizeof msg), VS_EUNSUPPORTED, msg, "2^32");
-    expect("capacity huge extra", rescale_check_capacity(10, 10, 0x7FFFFFFFFFFFFFFFll, 0, msg, sizeof msg), VS_EUNSUPPORTED, msg, "2^32");
+    expect("capacity ok", new_index_check_capacity("rescaled", 100, 1000, 5, 7, msg, sizeof msg), VS_OK, msg, "");
+    expect("capacity nothing", new_index_check_capacity("rescaled", 0, 0, 0, 0, msg, sizeof msg), VS_OK, msg, "");
+    expect("capacity rows", new_index_check_capacity("rescaled", 0xFFFFFFF0ll, 10, 0xF, 0, msg, sizeof msg), VS_EUNSUPPORTED, msg, "2^32");
+    expect("capacity packets", new_index_check_capacity("rescaled", 10, 0xFFFFFFF0ll, 0, 0x10, msg, sizeof msg), VS_EUNSUPPORTED, msg, "2^32");
+    expect("capacity huge extra", new_index_check_capacity("rescaled", 10, 10, 0x7FFFFFFFFFFFFFFFll, 0, msg, sizeof msg), VS_EUNSUPPORTED, msg, "2^32");
     expect_true("image bytes", rescale_img_bytes(1) == 16 && rescale_img_bytes(4) == 16 && rescale_img_bytes(5) == 32 && rescale_img_bytes(29523) == 118096);
 
     if (failures) {

@@ -3,7 +3,7 @@
 // Plain C++ with no HIP in it, so that a stand-alone program can run them under a host sanitizer (tests/test_select_cpu.py builds one).
 #pragma once
 
-#include "set_check.h"
+#include "new_index_check.h"
 
 namespace vs {
 
@@ -36,7 +36,7 @@ struct SelectShape {
 
 // the arguments that need neither the handle nor a device
 inline int select_check_args(bool have_src, bool have_ids, bool have_out, int64_t n, int64_t rows_extra, int64_t packets_extra, char* msg, size_t cap) {
-    if (rows_extra < 0 || packets_extra < 0) return snprintf(msg, cap, "rows_extra and packets_extra must be >= 0"), VS_EINVAL;
+    if (new_index_check_extra(rows_extra, packets_extra, msg, cap) != VS_OK) return VS_EINVAL;
     if (!have_src || !have_out) return snprintf(msg, cap, "NULL argument"), VS_EINVAL;
     if (n == 0) return snprintf(msg, cap, "empty selection: n must be positive"), VS_EINVAL;
     if (n < 0 || n > kSelectMaxIds) return snprintf(msg, cap, "n must be in 1..2^32 - 2 (got %lld)", (long long)n), VS_EINVAL;
@@ -60,15 +60,6 @@ inline int select_check_dense(const SelectShape& src, int64_t rows_extra, int64_
     if (src.kind == VS_KIND_CSR) return VS_OK;
     if (rows_extra || packets_extra) return snprintf(msg, cap, "a dense (matrix) index has no append: rows_extra and packets_extra must be 0"), VS_EINVAL;
     if (device != src.device) return snprintf(msg, cap, "a dense (matrix) index is selected from on its own device"), VS_EUNSUPPORTED;
-    return VS_OK;
-}
-
-// the limits of vs_index_compact: row and packet counts with their spare capacity fit 32 bits.  new_packets is the 64-bit sum: repeats can
-// select more packets than the source stores
-inline int select_check_capacity(int64_t n, int64_t new_packets, int64_t rows_extra, int64_t packets_extra, char* msg, size_t cap) {
-    if (rows_extra > (1ll << 32) || packets_extra > (1ll << 32) || new_packets < 0 || new_packets >= (1ll << 32) || n + rows_extra >= (1ll << 32) - 1 ||
-        new_packets + packets_extra >= (1ll << 32))
-        return snprintf(msg, cap, "the selected index with its spare capacity exceeds 2^32 rows or packets"), VS_EUNSUPPORTED;
     return VS_OK;
 }
 

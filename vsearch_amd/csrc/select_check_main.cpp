@@ -78,11 +78,17 @@ int main() {
     expect("dense rows_extra", select_check_dense(dense, 1, 0, 1, msg, sizeof msg), VS_EINVAL, msg, "no append");
     expect("dense packets_extra", select_check_dense(dense, 0, 1, 1, msg, sizeof msg), VS_EINVAL, msg, "no append");
     expect("dense device", select_check_dense(dense, 0, 0, 0, msg, sizeof msg), VS_EUNSUPPORTED, msg, "own device");
-    expect("capacity ok", select_check_capacity(100, 1000, 5, 7, msg, sizeof msg), VS_OK, msg, "");
-    expect("capacity rows", select_check_capacity(0xFFFFFFF0ll, 10, 0xF, 0, msg, sizeof msg), VS_EUNSUPPORTED, msg, "2^32");
-    expect("capacity packets", select_check_capacity(10, 0xFFFFFFF0ll, 0, 0x10, msg, sizeof msg), VS_EUNSUPPORTED, msg, "2^32");
-    expect("capacity repeats past 2^32", select_check_capacity(1ll << 20, 1ll << 33, 0, 0, msg, sizeof msg), VS_EUNSUPPORTED, msg, "2^32");
-    expect("capacity huge extra", select_check_capacity(10, 10, 0x7FFFFFFFFFFFFFFFll, 0, msg, sizeof msg), VS_EUNSUPPORTED, msg, "2^32");
+    for (const char* noun : {"selected", "compacted"}) {                    // (vs_index_compact has no check header of its own: its noun is covered here)
+        char text[96];
+        snprintf(text, sizeof text, "the %s index with its spare capacity exceeds 2^32 rows or packets", noun);
+        expect("capacity ok", new_index_check_capacity(noun, 100, 1000, 5, 7, msg, sizeof msg), VS_OK, msg, "");
+        expect("capacity rows", new_index_check_capacity(noun, 0xFFFFFFF0ll, 10, 0xF, 0, msg, sizeof msg), VS_EUNSUPPORTED, msg, "2^32");
+        expect("capacity packets", new_index_check_capacity(noun, 10, 0xFFFFFFF0ll, 0, 0x10, msg, sizeof msg), VS_EUNSUPPORTED, msg, "2^32");
+        expect("capacity repeats past 2^32", new_index_check_capacity(noun, 1ll << 20, 1ll << 33, 0, 0, msg, sizeof msg), VS_EUNSUPPORTED, msg, "2^32");
+        expect("capacity huge extra", new_index_check_capacity(noun, 10, 10, 0x7FFFFFFFFFFFFFFFll, 0, msg, sizeof msg), VS_EUNSUPPORTED, msg, "2^32");
+        expect_true("capacity: the whole sentence with the call's noun", strcmp(msg, text) == 0);
+    }
+    expect_true("new_index_bytes", new_index_bytes(10, 100, 32) == 100 * 48 + 44 && new_index_bytes(0, 0, 0) == 4 && value_bytes(VS_F16) == 16);
     // ---- the split rule -------------------------------------------------------------------------------------------------------------------------------------
     std::vector<int64_t> begin;
     const std::vector<int64_t> cuts = {0, 10, 10, 25, 40};                    // four shards, the second one empty

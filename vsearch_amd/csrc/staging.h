@@ -2,19 +2,11 @@
 // all host pointers (staged on the device, copied back, the call blocks) or all device pointers on the call's device (only enqueued).
 #pragma once
 #include "common.h"
+#include "new_index.h"
 
 #include <algorithm>
 
 namespace vs {
-
-inline int need_device() {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        (void)hipGetLastError();
-        return fail(VS_ENODEVICE, "no HIP device visible: libvsearch_hip has no CPU fallback");
-    }
-    return VS_OK;
-}
 
 inline int device_ok(const void* p, int device, const char* what) {
     hipPointerAttribute_t attr;

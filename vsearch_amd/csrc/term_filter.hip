@@ -9,6 +9,7 @@
 // values of the hit entries (valued stores: the non-zero / threshold test) and ORs the bit into the tile with an LDS atomic.  The tile
 // leaves as whole lines.  The terms of a pass travel in the kernel's arguments, so a call with device outputs only enqueues work.
 #include "common.h"
+#include "new_index.h"
 
 #include <algorithm>
 #include <cmath>
@@ -23,17 +24,6 @@ constexpr int kRunWords = kRunRows / 32;
 constexpr int kScanThreads = 512;
 constexpr int kScanUnroll = 4;          // packets a lane has in flight
 constexpr int kPkLds = kRunRows + 4;    // row pointers of a run (kRunRows + 1), kept 16-byte sized
-
-int need_device() {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        (void)hipGetLastError();
-        return fail(VS_ENODEVICE, "no HIP device visible: libvsearch_hip has no CPU fallback");
-    }
-    return VS_OK;
-}
-
-int64_t bit_words(int64_t rows) { return (rows + 31) >> 5; }
 
 int check_device(const void* p, int device, const char* what) {
     if (!is_device_ptr(p)) return VS_OK;
@@ -288,10 +278,6 @@ __global__ __launch_bounds__(256) void term_rebase_or_kernel(const uint32_t* src
         const uint32_t v = __funnelshift_l(lo, hi, sh);            // (hi << sh) | (lo >> (32 - sh)); sh == 0: hi
         if (v) d[j] |= v;
     }
-}
-
-unsigned grid_for(int64_t items, int per_block = 256, int64_t cap = 4096) {
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((items + per_block - 1) / per_block, cap));
 }
 
 template <int SD>

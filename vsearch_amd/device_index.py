@@ -164,6 +164,22 @@ def _compact_args(rows_extra, packets_extra):
     return int(rows_extra), int(packets_extra)
 
 
+def _new_index_call(fn, args, sources):
+    """One call of the library that returns a new index next to its sources (compact, prune, select_rows, rescale, combine, concat).  If HBM
+    cannot hold them all, the postings copy of every distinct source that has one is dropped (prepare() rebuilds it) and the call retried
+    once; with no copy to drop the MemoryError stands."""
+    try:
+        nat.check(fn(*args))
+    except MemoryError:
+        holders = [x for x in {id(x): x for x in sources}.values() if x.info().aux_bytes]
+        if not holders:
+            raise
+        for x in holders:
+            x.set_option("blocked_postings", 0)                # releases the copy; back to auto for the next prepare()
+            x.set_option("blocked_postings", -1)
+        nat.check(fn(*args))
+
+
 def _prune_args(topk, min_value):
     """The cut rules of prune() -> (topk for the library: 0 = no cut, min_value: NaN = none); checked before the library is reached."""
     if topk is None:
@@ -3240,15 +3256,7 @@ class DeviceIndex:
         old = np.empty(self.n_live, dtype=np.int64)
         h = C.c_void_p()
         args = (self._h, rows_extra, packets_extra, device, C.byref(h), C.c_void_p(old.ctypes.data) if old.size else None)
-        try:
-            nat.check(nat.lib().vs_index_compact(*args))
-        except MemoryError:
-            info = self.info()
-            if not info.aux_bytes:
-                raise
-            self.set_option("blocked_postings", 0)             # releases the copy; back to auto for the next prepare()
-            self.set_option("blocked_postings", -1)
-            nat.check(nat.lib().vs_index_compact(*args))
+        _new_index_call(nat.lib().vs_index_compact, args, (self,))
         return DeviceIndex(h), old
 
     def prune(self, topk=None, min_value=None, keep_cols=None, drop_cols=None, protect=None, rows_extra: int = 0, packets_extra: int = 0,
@@ -3273,14 +3281,7 @@ class DeviceIndex:
         args = (self._h, topk, C.c_float(min_value), C.c_void_p(words.ctypes.data) if words is not None else None,
                 protect._h if protect is not None else None, rows_extra, packets_extra, device, C.byref(h),
                 C.c_void_p(kept.ctypes.data) if kept.size else None)
-        try:
-            nat.check(nat.lib().vs_index_prune(*args))
-        except MemoryError:
-            if not self.info().aux_bytes:
-                raise
-            self.set_option("blocked_postings", 0)             # releases the copy; back to auto for the next prepare()
-            self.set_option("blocked_postings", -1)
-            nat.check(nat.lib().vs_index_prune(*args))
+        _new_index_call(nat.lib().vs_index_prune, args, (self,))
         return DeviceIndex(h), kept
 
     def select_rows(self, ids, rows_extra: int = 0, packets_extra: int = 0, device: int = None, id_offset: int = 0) -> "DeviceIndex":
@@ -3301,14 +3302,7 @@ class DeviceIndex:
         if on_dev:
             import torch
             torch.cuda.current_stream(self.device).synchronize()    # (the ids were made on torch's stream; the call runs on the null stream)
-        try:
-            nat.check(nat.lib().vs_index_select_rows(*args))
-        except MemoryError:
-            if not self.info().aux_bytes:
-                raise
-            self.set_option("blocked_postings", 0)             # releases the copy; back to auto for the next prepare()
-            self.set_option("blocked_postings", -1)
-            nat.check(nat.lib().vs_index_select_rows(*args))
+        _new_index_call(nat.lib().vs_index_select_rows, args, (self,))
         return DeviceIndex(h)
 
     # ---- reweighted index ------------------------------------------------------------------------------
@@ -3354,14 +3348,7 @@ class DeviceIndex:
             torch.cuda.current_stream(self.device).synchronize()    # (the scales were made on torch's stream; the call runs on the null stream)
         h = C.c_void_p()
         args = (self._h, p_rs, p_cs, out_dtype, rows_extra, packets_extra, device, C.byref(h))
-        try:
-            nat.check(nat.lib().vs_index_rescale(*args))
-        except MemoryError:
-            if not self.info().aux_bytes:
-                raise
-            self.set_option("blocked_postings", 0)             # releases the copy; back to auto for the next prepare()
-            self.set_option("blocked_postings", -1)
-            nat.check(nat.lib().vs_index_rescale(*args))
+        _new_index_call(nat.lib().vs_index_rescale, args, (self,))
         return DeviceIndex(h)
 
     # ---- combined index ---------------------------------------------------------------------------------
@@ -3392,16 +3379,7 @@ class DeviceIndex:
         device = self.device if device is None else int(device)
         h = C.c_void_p()
         args = (self._h, other._h, C.c_float(wa), C.c_float(wb), out_dtype, rows_extra, packets_extra, device, C.byref(h))
-        try:
-            nat.check(nat.lib().vs_index_combine(*args))
-        except MemoryError:
-            holders = [x for x in ((self,) if other is self else (self, other)) if x.info().aux_bytes]
-            if not holders:
-                raise
-            for x in holders:
-                x.set_option("blocked_postings", 0)            # releases the copy; back to auto for the next prepare()
-                x.set_option("blocked_postings", -1)
-            nat.check(nat.lib().vs_index_combine(*args))
+        _new_index_call(nat.lib().vs_index_combine, args, (self, other))
         return DeviceIndex(h)
 
     # ---- joined index -----------------------------------------------------------------------------------
@@ -3429,16 +3407,7 @@ class DeviceIndex:
         arr = (C.c_void_p * len(srcs))(*[x._h for x in srcs])
         h = C.c_void_p()
         args = (arr, len(srcs), out_dtype, rows_extra, packets_extra, device, C.byref(h))
-        try:
-            nat.check(nat.lib().vs_index_concat(*args))
-        except MemoryError:
-            holders = [x for x in {id(x): x for x in srcs}.values() if x.info().aux_bytes]
-            if not holders:
-                raise
-            for x in holders:
-                x.set_option("blocked_postings", 0)            # releases the copy; back to auto for the next prepare()
-                x.set_option("blocked_postings", -1)
-            nat.check(nat.lib().vs_index_concat(*args))
+        _new_index_call(nat.lib().vs_index_concat, args, srcs)
         return DeviceIndex(h)
 
     # ---- term constraints (vsearch_amd.doc_filter.DocFilter.from_terms) ------------------------------
